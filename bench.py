@@ -22,7 +22,8 @@ bounded search, the reference's default ladder and the extension grid are legs o
 
 Usage: python bench.py --gpus N --steps K --warmup W   (N > 1: under torch.distributed.run, or plainly --
 then the N ranks are started as a child job)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: rank 0 also writes what the last timed step returned
+(see dump_outputs) so that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -80,6 +81,47 @@ def full_alignment(mm, eng, geoms, cfg, plan=None, precision=1):
         print(f"[bench trace] within {1e3 * (t1 - t0):.3f} ms, between {1e3 * (time.perf_counter() - t1):.3f} ms",
               file=sys.stderr)
     return logs, rot, evals + e2, unresolved
+
+
+DUMP_BUDGET_BYTES = 60_000_000    # --dump-outputs: data bytes of all arrays together (64 MB with room for the .npy headers)
+
+
+def step_outputs(res, case, ext):
+    """What a caller of the timed path receives from one step, as float64 arrays by name.  res = (logs, between rotations,
+    pose_evals, chain steps re-searched) of a 4-phase step, or (winners, None, pose_evals, 0) of the EXTENSION grid;
+    case = the step's pullbacks, which the alignment moves in place."""
+    logs, rot, evals, unresolved = res
+    out = {"pose_evals": [evals], "chain_steps_researched": [unresolved]}
+    if ext is not None:
+        out["winners"] = np.asarray(logs, dtype=np.float64).reshape(-1, 5)   # (pullback, frame, shift, angle, cost)
+        return out
+    out["between_rotations"] = rot
+    for i, (lg, g) in enumerate(zip(logs, case)):
+        out[f"within_logs_{i}"] = np.asarray(list(lg), dtype=np.float64).reshape(-1, 7)   # (id, matched_to, rot_deg, tx, ty, cx, cy)
+        for name in ("lumen", "cath", "centroids", "ref", "extra"):
+            if getattr(g, name) is not None:
+                out[f"{name}_{i}"] = getattr(g, name)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array to out_dir/<name>.npy as float64.  When they hold more than DUMP_BUDGET_BYTES together, each
+    keeps the same share of its rows, chosen by a generator seeded from its name (sorted): the same arguments give the
+    same rows in every run.  Returns what was written."""
+    import zlib
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        if share < 1.0 and a.ndim and a.shape[0] > 1:
+            rows = np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], max(1, int(a.shape[0] * share)),
+                                                                          replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written, "row_share": share}
 
 
 def run_steps(ks, search, finish, pipelined, stage=None, lookahead=2, begin=None, stager=False, pre=None, finishers=1):
@@ -560,7 +602,12 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline (default: the GPU box's CPU share per GPU, 16, or fewer cores)")
     ap.add_argument("--check", action="store_true", help="verify the result against the CPU oracle (slow)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (within logs, between rotations, the moved "
+                         "pullbacks; float64) as DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -627,6 +674,8 @@ def main():
     if rehearse > 1:
         if world != 1:
             raise SystemExit("MM_BENCH_REHEARSE_WORLD is a single-process rehearsal")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: a MM_BENCH_REHEARSE_WORLD run times a share of the search, it computes no alignment")
         if os.environ.get("MM_EXCHANGE", "rccl") == "rccl":
             rehearse_comm = mm.Comm(mm.Comm.unique_id(), 0, 1, local_rank)   # the library's own communicator
         else:
@@ -944,6 +993,8 @@ def main():
                          f"); result signatures per step: {sig}")
     if args.precision != "bounded":
         bound = None
+    # (every rank holds the same alignment -- compared across ranks at the end -- so rank 0 writes it)
+    dumped = dump_outputs(args.dump_outputs, step_outputs(res, main_leg["last_case"], ext)) if args.dump_outputs and rank == 0 else None
 
     def same_result(leg):
         r2 = leg["results"][-1]
@@ -1158,6 +1209,8 @@ def main():
             out["unit"] = "candidates resolved/s"
             out["metric"] += " -- BOUNDED SEARCH: candidates ruled out by a lower bound or evaluated (same winners), not pose-evals"
         out.update(extra)
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         if not args.no_cpu_baseline and world == 1:
             try:
                 avail = len(os.sched_getaffinity(0))

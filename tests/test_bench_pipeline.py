@@ -1,21 +1,50 @@
-"""bench.py's two-stage step pipeline (run_steps): ordering guarantees, results and error propagation.
-Pure host logic, no GPU."""
+"""bench.py's two-stage step pipeline (run_steps): ordering guarantees, results and error propagation; the
+--dump-outputs writer.  Pure host logic, no GPU."""
 import importlib.util
 import os
 import threading
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def run_steps():
+def bench():
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return mod.run_steps
+    return mod
+
+
+@pytest.fixture(scope="module")
+def run_steps(bench):
+    return bench.run_steps
+
+
+def test_dump_outputs_writes_float64_and_samples_the_same_rows_beyond_the_budget(bench, tmp_path, monkeypatch):
+    rng = np.random.default_rng(5)
+    arrays = {"lumen_0": rng.normal(size=(40000, 3)), "logs_0": rng.normal(size=(300, 7)).astype(np.float32),
+              "pose_evals": [123456789]}
+    info = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert info["row_share"] == 1.0 and info["arrays"] == 3
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, np.asarray(a, dtype=np.float64))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100_000)
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert a["bytes"] == b["bytes"] <= 100_000 and 0 < a["row_share"] < 1
+    for name, full in arrays.items():
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert np.array_equal(x, y)                                  # a fixed sample: the same rows in every run
+        full = np.asarray(full, dtype=np.float64)
+        if full.shape[0] > 1:
+            assert 0 < x.shape[0] < full.shape[0]
+            rows = {r.tobytes() for r in full}
+            assert all(r.tobytes() in rows for r in x)              # rows of the output, not new values
 
 
 @pytest.mark.parametrize("pipelined", [False, True])

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,31 @@ def test_bench_contract_on_a_small_workload():
     assert d["bounded_search"]["identical_to_bruteforce_result"] is True
     assert d["f64_exact"]["identical_to_headline_result"] is True and d["f64_exact"]["dtype"] == "f64"
     assert d["sequential"]["ms_per_step"] > 0
+
+
+def test_bench_dumps_the_last_steps_outputs(mm, oracle, tmp_path):
+    """--dump-outputs: the same arguments give the same arrays in two runs, and they are the alignment the CPU oracle
+    computes for the workload's case (within logs, between rotations, moved pullbacks)."""
+    from helpers import to_oracle
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny", "--no-extra-legs", "--no-cpu-baseline"]
+    d = run_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert d["steps"] == 2 and d["outputs_dumped"]["row_share"] == 1.0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == d["outputs_dumped"]["arrays"]
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float64 and np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n), equal_nan=True), n
+    og = [to_oracle(oracle, g) for g in mm.synthetic_case(12, 501)]
+    for i, o in enumerate(og):
+        assert np.array_equal(got[f"within_logs_{i}"], np.asarray(oracle.align_within_chain(o, 2.0, 180.0, True, 501),
+                                                                   dtype=np.float64).reshape(-1, 7))
+    rot = [oracle.align_between(og[i], og[j], 180.0, 2.0, 501) for i, j in ((0, 1), (2, 3), (0, 2), (1, 3))]
+    assert np.array_equal(got["between_rotations"], np.asarray(rot))
+    for i, o in enumerate(og):
+        assert np.array_equal(got[f"lumen_{i}"], o.lumen) and np.array_equal(got[f"cath_{i}"], o.cath)
+        assert np.array_equal(got[f"centroids_{i}"], o.centroids)
+    assert got["pose_evals"][0] == d["config"]["pose_evals_per_step"]
 
 
 @pytest.mark.parametrize("exchange", ["device", "gather"])
