@@ -148,6 +148,13 @@ int  mm_engine_set_bound_min_candidates(mm_engine* e, int64_t n);
  * shapes is screened outright on the matrix pipe, without bound rounds); on == 0 keeps the packed-FMA kernels of rounds 1-3
  * (the A/B switch of bench.py's bounded_search leg).  Same winners and costs either way. */
 int  mm_engine_set_bound_matrix(mm_engine* e, int on);
+/* MM_PRECISION_F32_MATRIX screens pairs of 64 .. 544 points per set without the 32 x 32 tiles of the distance matrix that
+ * provably hold no row or column minimum (default, on != 0; bit-identical screened values); on == 0 computes every tile
+ * (the A/B switch). */
+int  mm_engine_set_screen_cull(mm_engine* e, int on);
+/* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
+ * out[1] what the full screen computes for the same candidates. */
+int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
 
 /* TEST HOOK (nothing in the product calls it): the lower bound MM_PRECISION_F32_BOUNDED's bound kernels give every
  * candidate of one search -- out_lb2[i] <= (exact cost of candidate i)^2 up to *e2 (error bound of the kernel's squared
@@ -163,6 +170,17 @@ int  mm_lower_bounds(mm_engine* e, const double* rx, const double* ry, int nr, c
  * Hausdorff value (*value2 = the maximum over both).  Sets of 64 .. 528 points. */
 int  mm_pick_minima(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                     double cx, double cy, double angle, int flags, float* row_min2, float* col_min2, float* value2, double* e2);
+
+/* TEST HOOK (nothing in the product calls it): every candidate's screened squared Hausdorff value (MM_PRECISION_F32_MATRIX,
+ * brute force) of one search, through the culled screen (cull != 0) or the full one; *e2 = the error bound of the squared
+ * values.  Sets of 64 .. 544 points. */
+int  mm_screen_values(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                      double cx, double cy, const double* angles, int n_angles, int flags, int cull, float* out_sq2, double* e2);
+/* TEST HOOK (host only): the culled screen's tile bound for f32 sets relative to the rotation centre, scaled by 2^e, the
+ * target rotated by (c, s): circles[4 * (row tiles + column tiles)] (cx, cy, r, 0; column centres rotated) and
+ * thr[row tiles * column tiles], below every screened squared distance of the tile pair when > 0 (error bound e2). */
+int  mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int e, float c,
+                         float s, double e2, float* circles, float* thr);
 
 /* ---- the metric: hausdorff_distance (process_utils.rs:78-82) ------------------------ */
 /* f64-exact on the device; empty set on either side -> 0.0 (process_utils.rs:86-88). */

@@ -98,6 +98,11 @@ hipError_t launch_screen_fast(const BatchDev& b, int max_na, int max_nbp, hipStr
 // of their pairs must have sets of mx_min_points() .. mx_max_points() points, a target set whose variant (mx_variant) is
 // (nct, multi), a reference set of at most a_cap row tiles of 32, and PairDesc::pad0 = the pair's scale exponent
 hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int nct, int multi, int a_cap, hipStream_t s);
+// the same screen without the tiles that provably hold no minimum (k_screen_mx_cull): pairs whose variant mx_cull_takes;
+// tiles (nullable): device counter of the tiles computed
+hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
+                                 hipStream_t s);
+bool       mx_cull_takes(int nct, int multi, int a_cap);
 hipError_t launch_screen_none(const BatchDev& b, int work_begin, int n_work, hipStream_t s);   // screened value 0 for every candidate
 void       mx_variant(int n_tgt, int* nct, int* multi);
 size_t     lds_bytes_mx(int nct, bool multi, int a_cap, int waves);

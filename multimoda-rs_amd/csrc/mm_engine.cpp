@@ -12,6 +12,7 @@
 // cos/sin tables are computed on the host with glibc sin/cos (what Rust's f64::sin/cos
 // call on linux-gnu) and shared by pairs with identical candidate lists.
 #include "mm_engine.h"
+#include "mm_tile_bound.h"
 #include "mm_pool.h"
 #include "mm_trace.h"
 
@@ -653,7 +654,15 @@ int Plan::run(bool screen_only)
                     int64_t cand = 0;
                     for (int k = 0; k < g.work_count; ++k) cand += host_work[(size_t)(g.work_begin + k)].cnt;
                     eng->screened[g.kind == 2 ? 2 + g.multi : (g.kind == 3 ? 4 : g.kind)] += cand;
-                    if (g.kind == 2) {
+                    if (g.kind == 2 && eng->screen_cull && mx_cull_takes(g.nct, g.multi, g.a_cap)) {
+                        int64_t tiles = 0;
+                        for (int k = 0; k < g.work_count; ++k) {
+                            const WorkItem& w = host_work[(size_t)(g.work_begin + k)];
+                            tiles += (int64_t)w.cnt * ((host_pairs[(size_t)w.pair].n_ref + 31) / 32) * g.nct;
+                        }
+                        eng->cull_tiles_full += tiles;
+                        e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, s);
+                    } else if (g.kind == 2) {
                         e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s);
                     } else if (g.kind == 3) {
                         e = launch_screen_none(dev, g.work_begin, g.work_count, s);
@@ -1050,6 +1059,10 @@ int mm_engine_create(int device, void* stream, mm_engine** out)
         if (e2 != hipSuccess) { (void)hipStreamDestroy(en->stream); delete en; return hip_error(e2, "hipStreamCreateWithPriority"); }
         en->own_aux = true;
     }
+    if (hipMalloc((void**)&en->dev_tiles, 8) != hipSuccess || hipMemset(en->dev_tiles, 0, 8) != hipSuccess) {
+        mm_engine_destroy(reinterpret_cast<mm_engine*>(en));
+        return set_error(MM_ERR_HIP, "hipMalloc (tile counter)");
+    }
     *out = reinterpret_cast<mm_engine*>(en);
     return MM_OK;
 }
@@ -1068,6 +1081,7 @@ void mm_engine_destroy(mm_engine* h)
     if (e->pof_done) (void)hipEventDestroy(e->pof_done);
     if (e->tail_done) (void)hipEventDestroy(e->tail_done);
     if (e->dev_stats) (void)hipFree(e->dev_stats);
+    if (e->dev_tiles) (void)hipFree(e->dev_tiles);
     if (e->own_aux) (void)hipStreamDestroy(e->aux);
     if (e->own_stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -1195,6 +1209,27 @@ int mm_engine_bound_stats(mm_engine* h, int64_t out[5])
     return MM_OK;
 }
 
+int mm_engine_set_screen_cull(mm_engine* h, int on)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    e->screen_cull = on != 0;
+    return MM_OK;
+}
+
+int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e || !out) return set_error(MM_ERR_INVALID, "engine or out == NULL");
+    MM_HIP(hipSetDevice(e->device));
+    if (int src = e->sync_all()) return src;
+    unsigned long long d = 0;
+    if (e->dev_tiles) MM_HIP(hipMemcpy(&d, e->dev_tiles, 8, hipMemcpyDeviceToHost));
+    out[0] = (int64_t)d;
+    out[1] = e->cull_tiles_full.load();
+    return MM_OK;
+}
+
 int mm_engine_screen_stats(mm_engine* h, int64_t out[5])
 {
     Engine* e = reinterpret_cast<Engine*>(h);
@@ -1305,6 +1340,69 @@ int mm_pick_minima(mm_engine* h, const double* rx, const double* ry, int nr, con
     if (value2) MM_HIP(hipMemcpyAsync(value2, plan.dev.sq32, 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));
     if (e2) *e2 = plan.host_pairs[0].e2;
+    return MM_OK;
+}
+
+// TEST HOOK: every candidate's screened squared value (MM_PRECISION_F32_MATRIX, brute force) of one search, through the
+// culled screen (cull != 0) or the full one.  Sets of 64 .. 544 points: the pair must take the matrix-pipe screen in one
+// block (else MM_ERR_INVALID).  *e2: the error bound of the squared values.
+int mm_screen_values(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                     double cx, double cy, const double* angles, int n_angles, int flags, int cull, float* out_sq2, double* e2)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e || !rx || !ry || !tx || !ty || !angles || !out_sq2 || nr <= 0 || nt <= 0 || n_angles <= 0)
+        return set_error(MM_ERR_INVALID, "mm_screen_values: bad arguments");
+    MM_HIP(hipSetDevice(e->device));
+    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
+    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
+    Plan plan;
+    int rc = plan.stage_sets(e, sets, true);
+    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_MATRIX, 0, INT32_MAX, false);
+    if (rc) return rc;
+    bool ok = plan.A == n_angles && !plan.groups.empty();
+    for (const Plan::ScreenGroup& g : plan.groups) ok = ok && g.kind == 2 && mx_cull_takes(g.nct, g.multi, g.a_cap);
+    if (!ok) return set_error(MM_ERR_INVALID, "mm_screen_values: these sets do not take the matrix-pipe screen in one block");
+    const bool keep = e->screen_cull;
+    e->screen_cull = cull != 0;
+    rc = plan.run(true);
+    e->screen_cull = keep;
+    if (rc) return rc;
+    MM_HIP(hipMemcpyAsync(out_sq2, plan.dev.sq32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
+    MM_HIP(hipStreamSynchronize(plan.stream));
+    if (e2) *e2 = plan.host_pairs[0].e2;
+    return MM_OK;
+}
+
+// TEST HOOK (host only, no device): the culled screen's tile bound (mm_tile_bound.h) for the f32 point sets (rx, ry) and
+// (tx, ty) -- coordinates relative to the rotation centre, as the point pool holds them -- scaled by 2^e, the target
+// rotated by (c, s): circles[4 * (nrt + nct)] (row tiles, then column tiles, each cx, cy, r, 0; column centres rotated) and
+// thr[nrt * nct] (row-major), the threshold every screened squared distance of the tile is >= (when > 0) for an error
+// bound e2 (unscaled).
+int mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int e, float c,
+                        float s, double e2, float* circles, float* thr)
+{
+    if (!rx || !ry || !tx || !ty || !circles || !thr || nr <= 0 || nt <= 0 || nr > 1 << 20 || nt > 1 << 20 || e < -126 || e > 126)
+        return set_error(MM_ERR_INVALID, "mm_tile_bound_probe: bad arguments");
+    const int nrt = (nr + 31) / 32, nct = (nt + 31) / 32;
+    const float S = std::ldexp(1.0f, e);
+    const float e2s = mm_tile_e2s(e2, e);
+    for (int i = 0; i < nrt; ++i) {
+        float* o = circles + 4 * i;
+        mm_tile_circle(rx, ry, 32 * i, nr, S, o, o + 1, o + 2);
+        o[3] = 0.0f;
+    }
+    for (int j = 0; j < nct; ++j) {
+        float* o = circles + 4 * (nrt + j);
+        float ux, uy;
+        mm_tile_circle(tx, ty, 32 * j, nt, S, &ux, &uy, o + 2);
+        o[0] = std::fma(ux, c, -(uy * s)); o[1] = std::fma(ux, s, uy * c); o[3] = 0.0f;
+    }
+    for (int i = 0; i < nrt; ++i)
+        for (int j = 0; j < nct; ++j) {
+            const float* a = circles + 4 * i;
+            const float* b = circles + 4 * (nrt + j);
+            thr[i * nct + j] = mm_tile_threshold(mm_tile_gap(a[0], a[1], a[2], b[0], b[1], b[2]), e2s);
+        }
     return MM_OK;
 }
 

@@ -79,6 +79,11 @@ struct Engine {
     // (mm_engine_screen_stats; atomics: levels are staged from several host threads)
     std::atomic<int64_t> screened[5] = {};
     unsigned long long* dev_stats = nullptr;
+    // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull (mm_engine_set_screen_cull); its tile
+    // counts (mm_engine_screen_tiles): computed (device counter) and what the full kernel computes for the same candidates
+    bool screen_cull = true;
+    unsigned long long* dev_tiles = nullptr;
+    std::atomic<int64_t> cull_tiles_full{0};
     int profile_begin(hipStream_t s);
     int profile_end(hipStream_t s, double pair_evals, int64_t candidates);
 };

@@ -555,6 +555,7 @@ k_screen_fast(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ w
 // the engine groups the work items by variant, one launch per group.
 // -------------------------------------------------------------------------------------
 #include "mm_screen_mx_asm.inc"
+#include "mm_tile_bound.h"
 
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
@@ -975,6 +976,316 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 }
 int mx_min_points() { return 64; }
 int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
+
+// -------------------------------------------------------------------------------------
+// k_screen_mx_cull<NCT>: k_screen_mx<NCT, false> (sets of 64 .. 544 points, the whole target set per wave) without the tiles
+// that provably hold no row minimum and no column minimum.  Same operands, same work split (one wave, one candidate; the
+// workgroup's four waves share the staged row fragments; no barrier in the candidate loop); every tile it computes gives
+// the same 1024 values as the full kernel's, in the DUAL form (D = A.B for the column minima, D' = B.A for the row minima,
+// both in-lane: a row tile meets few column tiles, which the single form's LDS row transpose cannot amortise).
+//
+// The bound (mm_tile_bound.h): a bounding circle per row tile (once per work item) and per column tile (unrotated, once per
+// work item; per candidate only its centre is rotated, by the f32 cos / sin the columns take), and per tile pair (I, J)
+// a threshold thr(I, J) <= every SCREENED squared distance of the tile (a rigorous lower bound of the exact squared
+// distance, less the screen's error bound PairDesc::e2).
+// Two phases per candidate:
+//   1. every tile with thr <= 0 (the circles are close: no skip possible), and -- for a row tile or column tile that has
+//      none -- the tile of its nearest partner; the row minima go to a wave-private row store, the column minima stay in
+//      one register per column tile.  After it every row and column has a finite minimum.
+//   2. every other tile, unless thr(I, J) >= max(Umax_I, Vmax_J), with Umax_I the largest row minimum of row tile I and
+//      Vmax_J the largest column minimum of column tile J after phase 1 (integer order on the f32 bits, as every minimum
+//      here is taken).  A row tile with nothing left after phase 1 is final: its largest row minimum is Umax_I.
+// The bookkeeping has no serial cross-lane step per row tile: thr of all tile pairs is computed one pair per lane into a
+// wave-private table; lane I then builds row tile I's two masks in-lane from that table, from its row minima in the row
+// store and from the column maxima published in LDS; the phase loops only read the wave-uniform mask of a row tile
+// (v_readlane) and run its tiles, the next row tile's A fragment already requested.
+// Why the value is bit-identical to the full kernel's: a skipped tile's values v are >= thr > 0; every row r of tile I has
+// a current minimum m_r <= Umax_I <= thr <= v (minima only decrease, so the phase-1 maximum stays an upper bound), so v
+// cannot become r's minimum, and the same for every column of J with Vmax_J.  Every row and column minimum is therefore
+// the minimum over all 32 x NCT (resp. 32 x nrt) values, which is what the full kernel computes, and so is their maximum.
+// (A positive f32 compares like its bits as an integer; a negative minimum -- rounding below 0 for coincident points --
+// is below every positive threshold in that order too.)  The mask of a row tile is wave-uniform (one candidate per
+// wave): a scalar bit test and a branch per tile.
+// -------------------------------------------------------------------------------------
+typedef float f16x16 __attribute__((ext_vector_type(16)));
+
+static constexpr int MXC_ROW_TILES_MAX = 17;
+
+static __device__ __forceinline__ int min3i(int a, int b, int c) { return min(a, min(b, c)); }
+
+// fold the 16 values of one lane's share of a tile into acc (8 three-operand minima, five of them independent)
+static __device__ __forceinline__ int mxc_fold(int acc, const f16x16& d)
+{
+    const int a0 = min3i(__float_as_int(d[0]), __float_as_int(d[1]), __float_as_int(d[2]));
+    const int a1 = min3i(__float_as_int(d[3]), __float_as_int(d[4]), __float_as_int(d[5]));
+    const int a2 = min3i(__float_as_int(d[6]), __float_as_int(d[7]), __float_as_int(d[8]));
+    const int a3 = min3i(__float_as_int(d[9]), __float_as_int(d[10]), __float_as_int(d[11]));
+    const int a4 = min3i(__float_as_int(d[12]), __float_as_int(d[13]), __float_as_int(d[14]));
+    acc = min3i(acc, a0, a1);
+    acc = min3i(acc, a2, a3);
+    return min3i(acc, a4, __float_as_int(d[15]));
+}
+
+// the two halves of the wave meet: lanes l and l + 32 both get min(v_l, v_{l+32})
+static __device__ __forceinline__ int mxc_meet(int v)
+{
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    return min((int)r[0], (int)r[1]);
+}
+
+// max over lanes 0 .. 31
+static __device__ __forceinline__ int half_max_i32_dpp(int v)
+{
+    v = dpp_max_i32<0xB1>(v); v = dpp_max_i32<0x4E>(v); v = dpp_max_i32<0x141>(v); v = dpp_max_i32<0x140>(v);
+    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
+    return r0 > r1 ? r0 : r1;
+}
+
+// the tiles of `mask` for one row tile (A fragment af): their column minima into cm, their row minima into rmin -- per tile
+// D = A.B and D' = B.A, both MFMAs in flight before the minima
+template <int NCT>
+static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, const h4v (&bh)[NCT], int (&cm)[NCT], int& rmin)
+{
+    const f16x16 z = {};
+#pragma unroll
+    for (int t = 0; t < NCT; ++t) {
+        if ((mask >> t) & 1) {
+            // a column fragment's K slots 4..7 repeat its slots 0..3 (mx_col_coords / mx_col_norm): kept as 8 bytes, widened here
+            const h4v v = bh[t];
+            const h8v b = h8v{v[0], v[1], v[2], v[3], v[0], v[1], v[2], v[3]};
+            const f16x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, z, 0, 0, 0);
+            const f16x16 e = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, af, z, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            cm[t] = mxc_fold(cm[t], d);
+            rmin = mxc_fold(rmin, e);
+        }
+    }
+}
+
+size_t lds_bytes_mx_cull(int nct, int a_cap)
+{
+    return (size_t)a_cap * 64 * 16 + (size_t)4 * nct * 64 * 8 + (size_t)4 * a_cap * 32 * 4 * 2 + (size_t)(nct + a_cap) * 16 +
+           (size_t)MX_ITEM * 12;
+}
+
+template <int NCT>
+__global__ void __launch_bounds__(256, 2)
+k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work, int a_cap,
+                 const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
+                 const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done)
+{
+    constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128;
+    extern __shared__ __align__(16) unsigned char smem[];
+    h8v* s_a = reinterpret_cast<h8v*>(smem);                          // [a_cap][64] row fragments of the pair (all waves)
+    h4v* s_bw = reinterpret_cast<h4v*>(s_a + a_cap * 64);            // [WAVES][NCT][64] column fragments of the wave's candidate
+    int* s_rsx = reinterpret_cast<int*>(s_bw + WAVES * NCT * 64);    // [WAVES][a_cap][32] row store (row minima after a phase)
+    float* s_thx = reinterpret_cast<float*>(s_rsx + WAVES * a_cap * 32);   // [WAVES][a_cap][32] thr(I, J) of the candidate
+    float4* s_circ = reinterpret_cast<float4*>(s_thx + WAVES * a_cap * 32); // [NCT + a_cap] circles: columns (unrotated), rows
+    float* s_cs = reinterpret_cast<float*>(s_circ + NCT + a_cap);     // [MX_ITEM][2] cos, sin of the work item's candidates
+    int* s_ci = reinterpret_cast<int*>(s_cs + 2 * MX_ITEM);           // [MX_ITEM] their indices in the pair's list
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31;
+    h4v* s_b = s_bw + wave * NCT * 64;
+    int* s_rs = s_rsx + wave * a_cap * 32;
+    float* s_th = s_thx + wave * a_cap * 32;
+    // column tile t's 32 minima after phase 1 go to the coordinate half of its fragments (read into registers by then; the
+    // norm half, written once per work item, is not touched): [NCT][VS] ints, 32 used per row
+    int* s_v = reinterpret_cast<int*>(s_b);
+    unsigned long long done = 0;
+
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work; wi += gridDim.x) {
+        const WorkItem w = work[wi];
+        const PairDesc pd = pairs[w.pair];
+        const int na = pd.n_ref, nb = pd.n_tgt;
+        const int nrt = (na + 31) >> 5;
+        const float S = __builtin_ldexpf(1.0f, pd.pad0), inv_s2 = __builtin_ldexpf(1.0f, -2 * pd.pad0);
+        const float e2s = mm_tile_e2s(pd.e2, pd.pad0);
+
+        __syncthreads();
+        for (int t = tid; t < 2 * w.cnt; t += 64 * WAVES) {
+            const int a = w.a0 + (t >> 1);
+            s_cs[t] = (t & 1) ? sinv[pd.tab_off + a] : cosv[pd.tab_off + a];
+            if (!(t & 1)) s_ci[t >> 1] = a;
+        }
+        mx_stage_rows<64 * WAVES>(s_a, nrt, na, ptx + pd.ref_off, pty + pd.ref_off, S, tid);
+        float tx[NQ], ty[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int j = lane + 64 * q;
+            const int jc = j < nb ? j : nb - 1;
+            tx[q] = S * ptx[pd.tgt_off + jc]; ty[q] = S * pty[pd.tgt_off + jc];
+            if (j < NB) s_b[(j >> 5) * 64 + (j & 31) + 32] = mx_col_norm(tx[q], ty[q]);
+        }
+        // the circles: thread t < NCT column tile t, thread 64 + t row tile t
+        if (tid < NCT) {
+            float cx, cy, r;
+            mm_tile_circle(ptx + pd.tgt_off, pty + pd.tgt_off, tid * 32, nb, S, &cx, &cy, &r);
+            s_circ[tid] = float4{cx, cy, r, 0.0f};
+        } else if (tid >= 64 && tid < 64 + nrt) {
+            float cx, cy, r;
+            mm_tile_circle(ptx + pd.ref_off, pty + pd.ref_off, (tid - 64) * 32, na, S, &cx, &cy, &r);
+            s_circ[NCT + tid - 64] = float4{cx, cy, r, 0.0f};
+        }
+        __syncthreads();
+
+        for (int k = wave; k < w.cnt; k += WAVES) {
+            const float c = s_cs[2 * k], s = s_cs[2 * k + 1];
+            const int a = s_ci[k];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int j = lane + 64 * q;
+                if (j < NB) {
+                    const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
+                    const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
+                    s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                }
+            }
+            // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
+            __asm__ volatile("" ::: "memory");
+            h4v bf[NCT];
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) bf[t] = s_b[t * 64 + lane];
+            __asm__ volatile("" ::: "memory");
+
+            // ---- thr(I, J) of every tile pair, one pair per lane (no cross-lane step, the loads of a pass issued together) ----
+            for (int p = lane; p < nrt * NCT; p += 64) {
+                const int I = p / NCT, J = p - I * NCT;
+                const float4 rc = s_circ[NCT + I], cc = s_circ[J];
+                const float bx = __builtin_fmaf(cc.x, c, -(cc.y * s)), by = __builtin_fmaf(cc.x, s, cc.y * c);
+                s_th[I * 32 + J] = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, bx, by, cc.z), e2s);
+            }
+            __asm__ volatile("" ::: "memory");
+            // lane I (< nrt): phase-1 mask of row tile I -- every tile with thr <= 0, else the one with the smallest thr.
+            // lane 32 + J (J < NCT): column tile J's nearest row tile when none of its tiles has thr <= 0
+            unsigned m1 = 0;
+            int lone_i = -1;
+            if (lane < nrt) {
+                float best = __builtin_inff();
+                int bj = 0;
+#pragma unroll
+                for (int J = 0; J < NCT; ++J) {
+                    const float t = s_th[lane * 32 + J];
+                    if (!(t > 0.0f)) m1 |= 1u << J;
+                    if (t < best) { best = t; bj = J; }
+                }
+                if (!m1) m1 = 1u << bj;
+            } else if (lane >= 32 && lane - 32 < NCT) {
+                const int J = lane - 32;
+                bool cov = false;
+                float best = __builtin_inff();
+                int bi = 0;
+                for (int I = 0; I < nrt; ++I) {
+                    const float t = s_th[I * 32 + J];
+                    cov = cov || !(t > 0.0f);
+                    if (t < best) { best = t; bi = I; }
+                }
+                lone_i = cov ? -1 : bi;
+            }
+            for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
+                const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
+                if (lane == I) m1 |= 1u << (L - 32);
+            }
+
+            // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
+            int cm[NCT];
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
+            h8v af = s_a[lane];
+            for (int I = 0; I < nrt; ++I) {
+                const unsigned mask = __builtin_amdgcn_readlane(m1, I);
+                const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
+                int rmin = 0x7f800000;
+                mxc_tiles<NCT>(mask, af, bf, cm, rmin);
+                rmin = mxc_meet(rmin);
+                if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                done += __builtin_popcount(mask);
+                af = an;
+            }
+            // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                cm[t] = mxc_meet(cm[t]);
+                if (lane < 32) s_v[t * VS + lane] = cm[t];
+            }
+            __asm__ volatile("" ::: "memory");
+            if (lane < NCT) {
+                const int4* q = reinterpret_cast<const int4*>(s_v + lane * VS);
+                int v = (int)0x80000000;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; v = max(v, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+                s_v[lane * VS + 40] = v;                                  // (inside the coordinate half, past the 32 minima)
+            }
+            __asm__ volatile("" ::: "memory");
+            // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
+            unsigned m2 = 0;
+            int rowmax = 0;
+            if (lane < nrt) {
+                const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
+                int umax = (int)0x80000000;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+#pragma unroll
+                for (int J = 0; J < NCT; ++J) {
+                    const float t = s_th[lane * 32 + J];
+                    const int lim = max(umax, s_v[J * VS + 40]);
+                    if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
+                }
+                m2 &= ~m1;
+                if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
+            }
+
+            // ---- phase 2: only the row tiles with tiles left ----
+            for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
+                const int I = __builtin_ctzll(rows);
+                const unsigned mask = __builtin_amdgcn_readlane(m2, I);
+                const h8v ai = s_a[I * 64 + lane];
+                int rmin = s_rs[I * 32 + l32];
+                mxc_tiles<NCT>(mask, ai, bf, cm, rmin);
+                rmin = mxc_meet(rmin);
+                done += __builtin_popcount(mask);
+                rowmax = max(rowmax, rmin);
+            }
+            int m = rowmax;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
+            m = wave_max_i32_dpp(m);
+            if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+        }
+    }
+    if (tiles_done && lane == 0 && done) atomicAdd(tiles_done, done);
+}
+
+template <int NCT>
+static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int n_work, int a_cap, unsigned long long* tiles,
+                                   hipStream_t s)
+{
+    const size_t lds = lds_bytes_mx_cull(NCT, a_cap);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_screen_mx_cull<NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_screen_mx_cull<NCT>), dim3(n_work), dim3(256), lds, s, b.pairs, work, n_work, a_cap, b.p32x, b.p32y,
+                       b.cos32, b.sin32, b.sq32, tiles);
+    return hipGetLastError();
+}
+
+bool mx_cull_takes(int nct, int multi, int a_cap)
+{
+    return !multi && nct >= MM_SCREEN_MX_NCT_MIN && nct <= MX_TMAX && a_cap >= 1 && a_cap <= MXC_ROW_TILES_MAX;
+}
+
+hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
+                                 hipStream_t s)
+{
+    if (n_work <= 0) return hipSuccess;
+    if (!mx_cull_takes(nct, 0, a_cap)) return hipErrorInvalidValue;
+    const WorkItem* w = b.work + work_begin;
+#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, s);
+    switch (nct) {
+        MM_MXC(2) MM_MXC(3) MM_MXC(4) MM_MXC(5) MM_MXC(6) MM_MXC(7) MM_MXC(8) MM_MXC(9) MM_MXC(10) MM_MXC(11) MM_MXC(12)
+        MM_MXC(13) MM_MXC(14) MM_MXC(15) MM_MXC(16) MM_MXC(17)
+        default: return hipErrorInvalidValue;
+    }
+#undef MM_MXC
+}
 
 // -------------------------------------------------------------------------------------
 // Bounded screen.  For subsets A' of the reference set and B' of the target set,

@@ -1,0 +1,79 @@
+// Tile bound of the culled matrix-pipe screen (k_screen_mx_cull, mm_kernels.hip): a bounding circle per tile of 32
+// consecutive points and a lower bound of the squared distance between any two points of two tiles.  Shared by the kernel
+// and the host (mm_tile_bound_probe, the test hook that checks it against f64), so both run the same f32 operations.
+//
+// Units are the screen's scaled units (x = 2^e * coordinate, every point of the pair within 512 of the rotation centre:
+// every coordinate, centre and radius below 2^10 in magnitude, every distance below 2^11).
+#pragma once
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define MM_TB_HD __host__ __device__
+#else
+#define MM_TB_HD
+#endif
+
+// square root: the hardware instruction on the device (1 ulp), the correctly rounded one on the host -- the slack of the
+// bounds below covers either; a denormal argument flushed to 0 only lowers a gap, and a radius carries 2^-10 absolute
+MM_TB_HD inline float mm_tb_sqrt(float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_sqrtf(x);
+#else
+    return sqrtf(x);
+#endif
+}
+
+// Bounding circle of the points (S * px[k], S * py[k]), k = base .. base + 31, indices clamped to n - 1 (the padding rows
+// and columns of a tile duplicate the set's last point, as the screen's fragments do).  Centre: middle of the bounding box.
+// Radius: rounded UP -- the computed distance of a point from the centre carries at most 5 roundings of relative size 2^-24
+// (difference, square, fma, sqrt), the factor 1 + 2^-18 covers 64 of them and 2^-10 covers the f32 underflow of squares of
+// differences below 2^-60 -- so every point of the tile lies inside the circle, exactly.
+MM_TB_HD inline void mm_tile_circle(const float* px, const float* py, int base, int n, float S, float* cx, float* cy, float* r)
+{
+    float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
+    for (int k = 0; k < 32; ++k) {
+        const int i = base + k < n ? base + k : n - 1;
+        const float x = S * px[i], y = S * py[i];
+        x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+    }
+    const float mx = 0.5f * (x0 + x1), my = 0.5f * (y0 + y1);
+    float m = 0.0f;
+    for (int k = 0; k < 32; ++k) {
+        const int i = base + k < n ? base + k : n - 1;
+        const float dx = S * px[i] - mx, dy = S * py[i] - my;
+        m = fmaxf(m, fmaf(dx, dx, dy * dy));
+    }
+    *cx = mx; *cy = my;
+    *r = mm_tb_sqrt(m) * 1.000003814697265625f + 0.0009765625f;       // (1 + 2^-18), 2^-10
+}
+
+// Lower bound of the distance between a point of circle (ax, ay, ar) and a point of circle (bx, by, br), the second circle's
+// centre rotated in f32 like its points (the rotation's roundings of a point and of the centre, and of the f32 cos / sin
+// against the exact angle, move a point at most 2^-11 against its circle): |a - b| >= |ca - cb| - ar - br - 2^-11.  The
+// computed |ca - cb| is at most 5 roundings (2^-24 each) above the exact one: the factor 1 - 2^-18 takes it below; the
+// three subtractions round by at most 2^-13 each (magnitudes below 2^11); the slack 2^-7 holds both.  <= 0: no bound.
+MM_TB_HD inline float mm_tile_gap(float ax, float ay, float ar, float bx, float by, float br)
+{
+    const float dx = ax - bx, dy = ay - by;
+    const float d = mm_tb_sqrt(fmaf(dx, dx, dy * dy));
+    return d * 0.999996185302734375f - (ar + br) - 0.0078125f;       // (1 - 2^-18), 2^-7
+}
+
+// Threshold of a tile pair: every SCREENED squared distance of the tile is >= the returned value (when it is > 0).
+// gap <= the exact distance of any pair, so gap^2 <= the exact squared distance; the screen's value lies within e2s of the
+// exact one (e2s = PairDesc::e2 in scaled units, rounded up).  gap^2 rounds once, the product with 1 - 2^-17 once, the
+// difference once (relative to the product): (1 - 2^-17)(1 + 2^-24)^2 < 1 - 2^-24 keeps the result below gap^2 - e2s.
+// Negative: no threshold (the circles are too close for any skip).
+MM_TB_HD inline float mm_tile_threshold(float gap, float e2s)
+{
+    if (!(gap > 0.0f)) return -1.0f;
+    const float g2 = gap * gap;
+    return g2 * 0.99999237060546875f - e2s;                          // (1 - 2^-17)
+}
+
+// e2 (unscaled, f64) in scaled units, rounded up: 2^(2e) is exact, the conversion to f32 rounds by at most 2^-24
+MM_TB_HD inline float mm_tile_e2s(double e2, int e)
+{
+    return (float)std::ldexp(e2, 2 * e) * 1.000003814697265625f;
+}

@@ -1,0 +1,120 @@
+"""The culled matrix-pipe screen (k_screen_mx_cull) against the full one (k_screen_mx): every candidate's screened squared
+value must be BIT-identical -- a skipped tile holds no row or column minimum (the kernel header's argument) -- on shapes
+where much is culled (contours of consecutive frames), where nothing is (concentric equal circles), where little is
+(identical sets, unordered clouds), on the error-bound test's worst-case constructions and at the set sizes of the tile
+edges.  The hook: mm_screen_values (include/mm_hausdorff.h)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+def _same(engine, ref, tgt, angles, centre=(0.0, 0.0)):
+    full, e2a = engine.screen_values(ref, tgt, angles, centre, cull=False)
+    t0 = engine.screen_tiles()
+    cull, e2b = engine.screen_values(ref, tgt, angles, centre, cull=True)
+    t1 = engine.screen_tiles()
+    assert e2a == e2b
+    bad = np.nonzero(full.view(np.uint32) != cull.view(np.uint32))[0]
+    assert bad.size == 0, (bad[:8], full[bad[:8]], cull[bad[:8]])
+    done, total = t1[0] - t0[0], t1[1] - t0[1]
+    nrt, nct = (len(ref) + 31) // 32, (len(tgt) + 31) // 32
+    assert total == len(angles) * nrt * nct
+    assert 0 < done <= total
+    return done / total
+
+
+def _frame_sets(pullback, k):
+    lum = pullback.lumen[pullback.lumen_off[k]:pullback.lumen_off[k + 1], :2]
+    cath = pullback.cath[pullback.cath_off[k]:pullback.cath_off[k + 1], :2]
+    return np.concatenate([lum, cath], axis=0)
+
+
+def test_config3_frame_pairs_all_rotations(engine, mm):
+    from multimoda_rs_amd import synth
+    g = synth.synthetic_case(5)[0]
+    angles = np.radians(np.linspace(-180.0, 180.0, 721))
+    fracs = []
+    for k in range(4):
+        ref, tgt = _frame_sets(g, k), _frame_sets(g, k + 1)
+        assert len(ref) == 521 and len(tgt) == 521
+        centre = tuple(ref.mean(axis=0))
+        fracs.append(_same(engine, ref, tgt, angles, centre))
+    assert max(fracs) < 0.5, fracs                      # contours of consecutive frames: most tiles culled
+
+
+def _circle(n, r, phase=0.0):
+    t = phase + np.linspace(0, 2 * np.pi, n, endpoint=False)
+    return np.stack([r * np.cos(t), r * np.sin(t)], axis=1)
+
+
+@pytest.mark.parametrize("n", [64, 65, 96, 223, 521, 544])
+def test_sizes(engine, n):
+    rng = np.random.default_rng(n)
+    angles = np.radians(np.linspace(-30.0, 30.0, 61))
+    t = np.linspace(0, 2 * np.pi, n, endpoint=False)
+    r = 3.0 * (1 + 0.15 * np.sin(3 * t))
+    ref = np.stack([r * np.cos(t), r * np.sin(t)], axis=1)
+    tgt = ref * 1.02 + rng.normal(0, 0.01, ref.shape)
+    _same(engine, ref, tgt, angles)
+    _same(engine, ref, tgt[: max(64, n // 2)], angles)          # unequal sizes both ways
+    _same(engine, tgt[: max(64, n // 2)], ref, angles)
+
+
+def test_nothing_to_cull_and_little_to_cull(engine):
+    rng = np.random.default_rng(7)
+    angles = np.radians(np.linspace(-180.0, 180.0, 181))
+    # concentric equal circles: every column is equally far from a ring -- nothing can be skipped for long
+    a = _circle(256, 5.0)
+    _same(engine, a, _circle(256, 5.0, phase=0.01), angles)
+    # identical sets
+    b = _circle(300, 2.0) * (1 + 0.2 * np.sin(np.linspace(0, 6 * np.pi, 300)))[:, None]
+    _same(engine, b, b.copy(), angles)
+    # unordered random clouds
+    c, d = rng.normal(0, 1.0, (400, 2)), rng.normal(0.1, 1.1, (333, 2))
+    _same(engine, c, d, angles)
+    _same(engine, d, c, angles)
+
+
+def test_error_bound_worst_cases(engine):
+    """The constructions of tests/test_gpu_mx_error_bound.py: coordinates on f16 ties, a far outlier with everything else
+    tiny, near-identical sets, one deciding pair; angles whose f32 (cos, sin) is furthest from unit norm."""
+    rng = np.random.default_rng(20240)
+    a = np.linspace(-np.pi, np.pi, 200001)[:-1]
+    c32, s32 = np.cos(a).astype(np.float32).astype(np.float64), np.sin(a).astype(np.float32).astype(np.float64)
+    angles = np.sort(np.concatenate([a[np.argsort(np.abs(c32 * c32 + s32 * s32 - 1.0))[-48:]], [0.0]]))
+    for n in (64, 223, 449, 544):
+        for rmax in (511.9, 256.01):
+            t = np.sort(rng.uniform(0, 2 * np.pi, n))
+            p = rmax * (1.0 - 0.3 * rng.uniform(0, 1, n) ** 4)[:, None] * np.stack([np.cos(t), np.sin(t)], axis=1)
+            sp = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(p), 2.0 ** -10))) - 10)
+            ties = (np.floor(p / sp) + 0.5) * sp
+            ties *= np.minimum(1.0, rmax / np.hypot(ties[:, 0], ties[:, 1]))[:, None] * (1 - 1e-7)
+            _same(engine, ties, ties + rng.choice([-0.0625, 0.0625, 0.03125], size=ties.shape), angles)
+            tg = ties.copy(); tg[n // 2] *= 0.75
+            _same(engine, ties, tg, angles)
+        small = rng.normal(0, 2.0 ** -9, (n, 2))
+        far = small.copy(); far[0] = (500.0, -100.0)
+        _same(engine, far, small + 2.0 ** -11, angles)
+        _same(engine, small + 2.0 ** -11, far, angles)
+        for scale in (2.0 ** -7, 3.0e4):
+            _same(engine, far * scale, (small + 2.0 ** -11) * scale, angles)
+
+
+def test_search_results_are_the_same_with_and_without_culling(engine, mm):
+    from multimoda_rs_amd import synth
+    g = synth.synthetic_case(3)[1]
+    ref, tgt = _frame_sets(g, 0), _frame_sets(g, 1)
+    angles = np.radians(np.linspace(-180.0, 180.0, 721))
+    centre = tuple(ref.mean(axis=0))
+    out = []
+    for cull in (False, True):
+        engine.set_screen_cull(cull)
+        try:
+            out.append(engine.best_rotation(ref, tgt, angles, centre, skip_zero=True, precision=mm.MM_PRECISION_F32_MATRIX,
+                                            return_costs=True))
+        finally:
+            engine.set_screen_cull(True)
+    (i0, a0, c0, k0), (i1, a1, c1, k1) = out
+    assert (i0, a0, c0) == (i1, a1, c1)
+    assert np.array_equal(np.asarray(k0), np.asarray(k1))
