@@ -140,6 +140,9 @@ int  mm_engine_bound_stats(mm_engine* e, int64_t out[5]);
  * MM_PRECISION_F32_MATRIX chooses per PAIR: only pairs with a set of fewer than 64 or more than 2048 points (or a radius
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
+/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix and mm_engine_set_screen_cull apply to the levels staged
+ * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
+ * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
  * 16384): a dozen dependent launches cost more than screening a small batch outright. 0 = always. */
 int  mm_engine_set_bound_min_candidates(mm_engine* e, int64_t n);

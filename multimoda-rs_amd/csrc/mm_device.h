@@ -70,9 +70,10 @@ struct BatchDev {
     // bounded screen (MM_PRECISION_F32_BOUNDED)
     const WorkItem* work_lb;   // bound kernel's work list (more candidates per workgroup)
     int32_t   n_work_lb, lb_stride;
-    int32_t   lb_mx;       // > 0: the bounds come from the matrix pipe (k_bound_mx); value = row tiles per set of its LDS layout
+    int32_t   lb_mx;       // bounded search on the matrix pipe: row tiles per set of k_bound_mx's LDS layout
     int32_t   lb_mx_qt, lb_mx_nc;   // its variant: column tiles of queries per side (1 | 2), candidates per wave at once (1 | 2)
-    int32_t   kept_mx_nct, kept_mx_acap;   // > 0: the picks' and the survivors' screen is k_screen_mx<kept_mx_nct, false> (every pair: that variant)
+    int32_t   kept_mx_nct, kept_mx_acap;   // > 0: the bounded search runs on the matrix pipe; the picks' and the survivors'
+                                           // screen is k_screen_mx<kept_mx_nct, false> (every pair) with LDS for kept_mx_acap row tiles
     float*    lb32;        // per-candidate lower bound of the screened squared value
     int32_t*  pick_idx;    // [2 * n_pairs] per pair: candidate with the smallest bound after round 1 / round 3 (-1: none)
     WorkItem* items_pick;  // [2 * n_pairs] queue entries of the two picks

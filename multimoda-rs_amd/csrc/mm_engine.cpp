@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <array>
 #include <vector>
 
@@ -250,11 +251,51 @@ static double mx_e2(double rho_a, double rho_b)
     return u * (47.0 * R * R + 6.0 * rho_a * rho_a + 27.0 * rho_b * rho_b);
 }
 
+// The matrix-pipe kernels' scale exponent e: 2^e rmax in [256, 512) (f16 pieces, their doubles and |x|^2 / 256 stay in range)
+static int mx_scale_exp(double rmax)
+{
+    int k = 0;
+    (void)std::frexp(rmax * (1.0 + 1e-6), &k);   // radius < 2^k
+    return 9 - k;
+}
+
+// The screen of one pair searched without bound rounds; `multi`, `nct`, `cls`: the matrix pipe's variant (mx_variant) and
+// LDS class.  Pairs sort by (screen, multi, nct, cls), and a run of equal ones forms one launch (Plan::groups).
+struct PairScreen {
+    Screen screen; int multi, nct, cls;
+    auto key() const { return std::tie(screen, multi, nct, cls); }
+};
+
+// The matrix-pipe screen, chosen PER PAIR (MM_PRECISION_F32_MATRIX, or a bounded search without its bound rounds) for a
+// pair of nr, nt points and radii ra, rb: sets of mx_min_points() .. mx_max_points() points (the kernel is instantiated per
+// column-tile count, its row-tile count is a run-time operand, larger target sets are cut into column blocks) and radii the
+// scale exponent can take; then also *scale_exp and *e2, the error bound of its squared values.  A set of fewer than 64
+// points: no f32 screen, every candidate is scored exactly (cheap at that size, and no packed-FMA kernel runs under this
+// precision unless a set exceeds mx_max_points()).  Any other pair keeps `outside` (the packed-FMA screen, or in a batch
+// whose largest sets exceed that kernel's registers the direct form) and its e2.
+static PairScreen mx_pair_screen(int nr, int nt, double ra, double rb, Screen outside, int* scale_exp, double* e2)
+{
+    if (std::min(nr, nt) < mx_min_points() && std::max(nr, nt) <= mx_max_points()) return {Screen::None, 0, 0, 0};
+    const double rmax = std::max(ra, rb);
+    if (nr < mx_min_points() || nr > mx_max_points() || nt < mx_min_points() || nt > mx_max_points() || !(rmax > 1.0e-30) ||
+        !(rmax < 1.0e30))
+        return {outside, 0, 0, 0};
+    // LDS is sized per launch by the largest reference set of the group: up to 17 row tiles leave room for two workgroups
+    // per CU, more than that for one -- two classes, so that one long contour does not halve the occupancy of every other
+    // pair's launch
+    PairScreen c{Screen::Matrix, 0, 0, (nr + 31) / 32 <= 17 ? 0 : 1};
+    mx_variant(nt, &c.nct, &c.multi);
+    *scale_exp = mx_scale_exp(rmax);
+    *e2 = mx_e2(ra, rb);
+    return c;
+}
+
 int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_t angle_begin, int32_t angle_end,
-                      bool want_costs_, hipStream_t st)
+                      bool want_costs_, hipStream_t st, const ScreenOptions* opts_)
 {
     Engine* e = eng;
     if (!st) st = stream;
+    opts = opts_ ? *opts_ : e->screen_opts;
     precision = precision_;
     want_costs = want_costs_;
     slice_end = angle_end;
@@ -350,17 +391,11 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     use_fast = expanded && max_na <= max_rows_fast() && max_nbp <= max_target_points_fast();
     if (expanded && !use_fast)
         for (PairDesc& d : host_pairs) d.e2 = 0.0;
-    // Matrix-pipe screen, chosen PER PAIR: sets of mx_min_points() .. mx_max_points() points (the kernel is instantiated
-    // per column-tile count, its row-tile count is a run-time operand, larger target sets are cut into column blocks), a
-    // scale exponent that puts the larger radius into [256, 512) (f16 pieces, their doubles and |x|^2 / 256 stay in range),
-    // and the error bound of its squared values (mx_e2 below).  A pair outside that range keeps the packed-FMA screen (or,
-    // in a batch whose largest sets exceed that kernel's registers, the direct form) with that kernel's own e2; its work
-    // items form a group of their own (Plan::groups).
     // the bound rounds pay for themselves on sets of a few dozen points or more and on batches that keep
     // the device busy for several rounds of workgroups (a dozen dependent launches cost more than
     // screening a small batch outright: the between stage's 2 x 722 candidates are 40 % faster without);
     // per-candidate costs need every candidate evaluated
-    use_lb = precision == MM_PRECISION_F32_BOUNDED && use_fast && !want_costs && A > 0 && A >= e->bound_min_candidates &&
+    use_lb = precision == MM_PRECISION_F32_BOUNDED && use_fast && !want_costs && A > 0 && A >= opts.bound_min_candidates &&
              std::min(max_na, max_nt) >= 64 && std::max(max_na, max_nt) <= lb_max_points();
     // The bound rounds on the matrix pipe (k_bound_mx) and the survivors through k_screen_mx: every non-trivial pair with
     // sets of 64 .. lb_mx_max_points() points and a radius f16 can be scaled to; the pairs then carry the scale exponent and
@@ -368,7 +403,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     // rows, pass 2 target queries against reference rows).  The two per-pair picks stay on the packed-FMA screen (it emits
     // the row / column minima the third round's query choice needs); its e2 is the smaller one.
     lb_mx_tiles = 0; kept_nct = 0; kept_acap = 0;
-    if (use_lb && e->bound_matrix) {
+    if (use_lb && opts.bound_matrix) {
         bool ok = true;
         int tiles = 1, nct0 = -1, acap = 1;
         for (int p = 0; p < P && ok; ++p) {
@@ -399,9 +434,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
                 PairDesc& d = host_pairs[p];
                 if (trivial[p] || d.n_ang == 0) continue;
                 const double ra = set_rho[pairs[p].ref_set], rb = set_rho[pairs[p].tgt_set];
-                int k = 0;
-                (void)std::frexp(std::max(ra, rb) * (1.0 + 1e-6), &k);
-                d.pad0 = 9 - k;
+                d.pad0 = mx_scale_exp(std::max(ra, rb));
                 d.e2 = std::max(mx_e2(ra, rb), mx_e2(rb, ra));
             }
         }
@@ -409,31 +442,16 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     // A bounded search that does not run its bound rounds (small batch, per-candidate costs asked for, sets outside the
     // bound kernel's range) screens every candidate: on the matrix pipe, like MM_PRECISION_F32_MATRIX.
     const bool mx_wanted = precision == MM_PRECISION_F32_MATRIX || (precision == MM_PRECISION_F32_BOUNDED && !use_lb);
-    use_mx = false;
-    std::vector<int> pair_key((size_t)P, 0);       // 0: direct form, 1: packed FMA, else 2 + the matrix kernel's variant
+    bool use_mx = false;
+    const Screen outside = use_fast ? Screen::PackedFma : Screen::Direct;
+    std::vector<PairScreen> screen((size_t)P, PairScreen{outside, 0, 0, 0});
     if (mx_wanted && A > 0) {
         for (int p = 0; p < P; ++p) {
             PairDesc& d = host_pairs[p];
             if (trivial[p] || d.n_ang == 0) continue;
-            pair_key[(size_t)p] = use_fast ? 1 : 0;
-            // a set of fewer than 64 points: no f32 screen, every candidate is scored exactly (cheap at that size, and no
-            // packed-FMA kernel runs under this precision unless a set exceeds mx_max_points())
-            if (std::min(d.n_ref, d.n_tgt) < mx_min_points() && std::max(d.n_ref, d.n_tgt) <= mx_max_points()) { pair_key[(size_t)p] = -1; use_mx = true; continue; }
-            const double ra = set_rho[pairs[p].ref_set], rb = set_rho[pairs[p].tgt_set], rmax = std::max(ra, rb);
-            if (d.n_ref < mx_min_points() || d.n_ref > mx_max_points() || d.n_tgt < mx_min_points() || d.n_tgt > mx_max_points() ||
-                !(rmax > 1.0e-30) || !(rmax < 1.0e30))
-                continue;
-            int nct = 0, multi = 0, k = 0;
-            mx_variant(d.n_tgt, &nct, &multi);
-            // LDS is sized per launch by the largest reference set of the group: up to 17 row tiles leave room for two
-            // workgroups per CU, more than that for one -- two classes, so that one long contour does not halve the
-            // occupancy of every other pair's launch
-            const int nrt = (d.n_ref + 31) / 32, cls = nrt <= 17 ? 0 : 1;
-            (void)std::frexp(rmax * (1.0 + 1e-6), &k);   // radius < 2^k
-            d.pad0 = 9 - k;
-            d.e2 = mx_e2(ra, rb);
-            pair_key[(size_t)p] = 2 + ((((multi << 8) | nct) << 1 | cls) << 2);
-            use_mx = true;
+            screen[(size_t)p] = mx_pair_screen(d.n_ref, d.n_tgt, set_rho[pairs[p].ref_set], set_rho[pairs[p].tgt_set], outside,
+                                               &d.pad0, &d.e2);
+            use_mx = use_mx || screen[(size_t)p].screen != outside;
         }
     }
     if (max_nbp > max_target_points_f64() || (precision != MM_PRECISION_F64 && max_nbp > max_target_points_f32()))
@@ -458,10 +476,8 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     // 15.83 at 2312, 15.77 at 4624 (tools/exp_apb.sh).
     const int64_t apb_fill = std::max<int64_t>(1, (A + target_wgs - 1) / target_wgs);
     auto apb_of = [&](int p) {
-        if (!use_mx || pair_key[(size_t)p] < 2) return apb;
+        if (screen[(size_t)p].screen != Screen::Matrix) return apb;
         const PairDesc& d = host_pairs[p];
-        int nct = 0, multi = 0;
-        mx_variant(d.n_tgt, &nct, &multi);
         const int64_t tiles = (int64_t)((d.n_ref + 31) / 32) * ((d.n_tgt + 31) / 32);
         const int64_t per_wave = std::min<int64_t>(16, std::max<int64_t>(2, (2312 + tiles - 1) / tiles));
         return (int)std::max<int64_t>(apb, std::min<int64_t>(4 * per_wave, apb_fill));
@@ -475,7 +491,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
         // (stable: pair-major inside a group, as the XCD-aware work order wants it).
         std::vector<int> order((size_t)P);
         for (int p = 0; p < P; ++p) order[(size_t)p] = p;
-        if (use_mx) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return pair_key[(size_t)x] < pair_key[(size_t)y]; });
+        if (use_mx) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return screen[(size_t)x].key() < screen[(size_t)y].key(); });
         std::vector<int64_t> wstart((size_t)P + 1, 0);
         for (int q = 0; q < P; ++q) {
             const int ap = apb_of(order[(size_t)q]);
@@ -497,19 +513,21 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
                 }
             }
         });
-        if (use_mx)
+        // one launch per run of pairs with the same screen; a matrix group takes the culled kernel if it can
+        if (precision != MM_PRECISION_F64 && !use_lb)
             for (int q = 0; q < P;) {
-                const int key = pair_key[(size_t)order[(size_t)q]];
-                int q1 = q, a_cap = 1;
-                while (q1 < P && pair_key[(size_t)order[(size_t)q1]] == key) {
+                const PairScreen c = screen[(size_t)order[(size_t)q]];
+                ScreenGroup g{c.screen, c.nct, c.multi, 1, (int)wstart[(size_t)q], 0, 0, 0};
+                int q1 = q;
+                for (; q1 < P && screen[(size_t)order[(size_t)q1]].key() == c.key(); ++q1) {
                     const PairDesc& d = host_pairs[order[(size_t)q1]];
-                    if (d.n_ang > 0 && !trivial[order[(size_t)q1]]) a_cap = std::max(a_cap, (d.n_ref + 31) / 32);
-                    ++q1;
+                    if (d.n_ang > 0) g.a_cap = std::max(g.a_cap, (d.n_ref + 31) / 32);
+                    g.candidates += d.n_ang;
+                    g.tiles_full += (int64_t)d.n_ang * ((d.n_ref + 31) / 32) * c.nct;
                 }
-                const int wb = (int)wstart[(size_t)q], wc = (int)(wstart[(size_t)q1] - wstart[(size_t)q]);
-                if (wc > 0)
-                    groups.push_back(key < 0 ? ScreenGroup{3, 0, 0, 0, wb, wc} : key < 2 ? ScreenGroup{key, 0, 0, 0, wb, wc}
-                                             : ScreenGroup{2, ((key - 2) >> 3) & 0xff, ((key - 2) >> 11) & 1, a_cap, wb, wc});
+                g.work_count = (int)(wstart[(size_t)q1] - wstart[(size_t)q]);
+                if (g.screen == Screen::Matrix && opts.screen_cull && mx_cull_takes(g.nct, g.multi, g.a_cap)) g.screen = Screen::MatrixCull;
+                if (g.work_count > 0) groups.push_back(g);
                 q = q1;
             }
     }
@@ -518,8 +536,8 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     W_lb = 0; lb_runs_cap = 0; lb_pair_evals = 0.0; lb_sparse_total = 0;
     if (use_lb) {
         // every lb_stride-th point of either set is a query; the subset has to fit the kernel's registers
-        const int qmax = lb_mx_tiles > 0 ? 32 * e->bound_matrix_qt : lb_max_query_points();
-        lb_stride = std::max(lb_mx_tiles > 0 ? 1 : 8, (std::max(max_na, max_nt) + qmax - 1) / qmax);
+        const int qmax = kept_nct > 0 ? 32 * opts.bound_matrix_qt : lb_max_query_points();
+        lb_stride = std::max(kept_nct > 0 ? 1 : 8, (std::max(max_na, max_nt) + qmax - 1) / qmax);
         // first round: every lb_candidate_step()-th candidate and the last one, 32 of them per workgroup
         // (4 waves x 8: amortises staging the reference set)
         const int apb_lb = 32, cstep = lb_candidate_step();
@@ -553,7 +571,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     const size_t o_lb32 = take(use_lb ? (size_t)A * 4 : 0), o_pick = take(use_lb ? (size_t)P * 8 : 0);
     const size_t o_items_pick = take(use_lb ? (size_t)P * 2 * sizeof(WorkItem) : 0);
     const size_t o_items_lb = take(use_lb ? (size_t)lb_runs_cap * 3 * sizeof(WorkItem) : 0);
-    const size_t o_klist = take(use_lb && lb_mx_tiles > 0 ? (size_t)A * 4 : 0);
+    const size_t o_klist = take(kept_nct > 0 ? (size_t)A * 4 : 0);
     const size_t o_emit = take(use_lb ? (size_t)P * (size_t)(emit_rows + emit_cols) * 4 : 0);
     const size_t o_qlist = take(use_lb ? (size_t)P * 2 * (size_t)lb_list_queries() * 4 : 0);
     const size_t o_bc = take((size_t)P * 8), o_bi = take((size_t)P * 4), o_nr = take((size_t)P * 4);
@@ -601,7 +619,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     dev.items = (WorkItem*)(B + o_items); dev.n_items = (int32_t*)(B + o_nitems);
     dev.work_lb = (const WorkItem*)(B + o_work_lb); dev.n_work_lb = W_lb; dev.lb_stride = lb_stride;
     dev.lb_mx = lb_mx_tiles; dev.kept_mx_nct = kept_nct; dev.kept_mx_acap = kept_acap;
-    dev.lb_mx_qt = e->bound_matrix_qt; dev.lb_mx_nc = e->bound_matrix_nc;
+    dev.lb_mx_qt = opts.bound_matrix_qt; dev.lb_mx_nc = opts.bound_matrix_nc;
     dev.lb32 = (float*)(B + o_lb32); dev.pick_idx = (int32_t*)(B + o_pick); dev.items_pick = (WorkItem*)(B + o_items_pick);
     dev.items_lb = (WorkItem*)(B + o_items_lb); dev.emit = (float*)(B + o_emit); dev.emit_rows = emit_rows; dev.emit_cols = emit_cols;
     dev.qlist = (int32_t*)(B + o_qlist); dev.klist = (int32_t*)(B + o_klist);
@@ -609,6 +627,18 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     dev.near_cnt = (int32_t*)(B + o_nc); dev.near_idx = (int32_t*)(B + o_ni);
     dev.all_costs = want_costs ? (double*)(B + off_all_costs) : nullptr;
     return MM_OK;
+}
+
+// Engine::screened's slot of a screen: [0] direct form, [1] packed FMA, [2] / [3] matrix pipe in one block / in column
+// blocks, [4] exact f64
+static int screened_slot(Screen screen, int multi)
+{
+    switch (screen) {
+    case Screen::Direct: return 0;
+    case Screen::PackedFma: return 1;
+    case Screen::Matrix: case Screen::MatrixCull: return 2 + multi;
+    default: return 4;   // Screen::None: every candidate scored exactly
+    }
 }
 
 int Plan::run(bool screen_only)
@@ -648,34 +678,22 @@ int Plan::run(bool screen_only)
             if (eng->profile) { eng->bound_offered += A; eng->bound_round1 += lb_sparse_total; }
         } else {
             if ((prc = eng->profile_begin(s))) return prc;
-            if (use_mx) {
-                e = hipSuccess;
-                for (const ScreenGroup& g : groups) {
-                    int64_t cand = 0;
-                    for (int k = 0; k < g.work_count; ++k) cand += host_work[(size_t)(g.work_begin + k)].cnt;
-                    eng->screened[g.kind == 2 ? 2 + g.multi : (g.kind == 3 ? 4 : g.kind)] += cand;
-                    if (g.kind == 2 && eng->screen_cull && mx_cull_takes(g.nct, g.multi, g.a_cap)) {
-                        int64_t tiles = 0;
-                        for (int k = 0; k < g.work_count; ++k) {
-                            const WorkItem& w = host_work[(size_t)(g.work_begin + k)];
-                            tiles += (int64_t)w.cnt * ((host_pairs[(size_t)w.pair].n_ref + 31) / 32) * g.nct;
-                        }
-                        eng->cull_tiles_full += tiles;
-                        e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, s);
-                    } else if (g.kind == 2) {
-                        e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s);
-                    } else if (g.kind == 3) {
-                        e = launch_screen_none(dev, g.work_begin, g.work_count, s);
-                    } else {
-                        BatchDev sub = dev;              // the pairs outside the matrix kernel's range: their own work items
-                        sub.work = dev.work + g.work_begin; sub.n_work = g.work_count;
-                        e = g.kind == 1 ? launch_screen_fast(sub, max_na, max_nbp, s) : launch_screen_f32(sub, max_na, max_nbp, s);
-                    }
-                    if (e != hipSuccess) break;
+            e = hipSuccess;
+            for (const ScreenGroup& g : groups) {
+                eng->screened[screened_slot(g.screen, g.multi)] += g.candidates;
+                BatchDev sub = dev;              // the direct-form and packed-FMA kernels take their group's work items here
+                sub.work = dev.work + g.work_begin; sub.n_work = g.work_count;
+                switch (g.screen) {
+                case Screen::None: e = launch_screen_none(dev, g.work_begin, g.work_count, s); break;
+                case Screen::Direct: e = launch_screen_f32(sub, max_na, max_nbp, s); break;
+                case Screen::PackedFma: e = launch_screen_fast(sub, max_na, max_nbp, s); break;
+                case Screen::Matrix: e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s); break;
+                case Screen::MatrixCull:
+                    eng->cull_tiles_full += g.tiles_full;
+                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, s);
+                    break;
                 }
-            } else {
-                eng->screened[use_fast ? 1 : 0] += A;
-                e = use_fast ? launch_screen_fast(dev, max_na, max_nbp, s) : launch_screen_f32(dev, max_na, max_nbp, s);
+                if (e != hipSuccess) break;
             }
             if (e != hipSuccess) return hip_error(e, "screen kernel launch");
             if ((prc = eng->profile_end(s, pair_evals, A))) return prc;
@@ -1179,7 +1197,7 @@ int mm_engine_set_bound_min_candidates(mm_engine* h, int64_t n)
 {
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e || n < 0) return set_error(MM_ERR_INVALID, "engine == NULL or n < 0");
-    e->bound_min_candidates = n;
+    e->screen_opts.bound_min_candidates = n;
     return MM_OK;
 }
 
@@ -1187,11 +1205,11 @@ int mm_engine_set_bound_matrix(mm_engine* h, int on)
 {
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    e->bound_matrix = on != 0;
+    e->screen_opts.bound_matrix = on != 0;
     if (on > 1) {      // experiments: 10 * (query tiles per side) + (candidates per wave), e.g. 21
         const int qt = on / 10, nc = on % 10;
         if ((qt != 1 && qt != 2) || (nc != 1 && nc != 2)) return set_error(MM_ERR_INVALID, "mm_engine_set_bound_matrix: variant must be 11, 12, 21 or 22");
-        e->bound_matrix_qt = qt; e->bound_matrix_nc = nc;
+        e->screen_opts.bound_matrix_qt = qt; e->screen_opts.bound_matrix_nc = nc;
     }
     return MM_OK;
 }
@@ -1213,7 +1231,7 @@ int mm_engine_set_screen_cull(mm_engine* h, int on)
 {
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    e->screen_cull = on != 0;
+    e->screen_opts.screen_cull = on != 0;
     return MM_OK;
 }
 
@@ -1289,15 +1307,13 @@ int mm_lower_bounds(mm_engine* h, const double* rx, const double* ry, int nr, co
     MM_HIP(hipSetDevice(e->device));
     std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
     std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
-    const int64_t keep_min = e->bound_min_candidates;
-    const bool keep_mx = e->bound_matrix;
-    e->bound_min_candidates = 0; e->bound_matrix = matrix != 0;
+    ScreenOptions opts = e->screen_opts;
+    opts.bound_min_candidates = 0; opts.bound_matrix = matrix != 0;
     Plan plan;
     int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false);
-    e->bound_min_candidates = keep_min; e->bound_matrix = keep_mx;
+    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
     if (rc) return rc;
-    if (!plan.use_lb || (matrix != 0) != (plan.lb_mx_tiles > 0)) return set_error(MM_ERR_INVALID, "mm_lower_bounds: the bound kernel asked for does not take these sets");
+    if (!plan.use_lb || (matrix != 0) != (plan.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_lower_bounds: the bound kernel asked for does not take these sets");
     BatchDev sub = plan.dev;
     sub.work_lb = plan.dev.work; sub.n_work_lb = plan.W;      // every candidate, step 1 (WorkItem::pad == 0)
     const int nap = (plan.max_na + 31) & ~31, nbp = (plan.max_nt + 31) & ~31;
@@ -1319,15 +1335,13 @@ int mm_pick_minima(mm_engine* h, const double* rx, const double* ry, int nr, con
     MM_HIP(hipSetDevice(e->device));
     std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
     std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, &angle, 1, 0.0, 0.0}};
-    const int64_t keep_min = e->bound_min_candidates;
-    const bool keep_mx = e->bound_matrix;
-    e->bound_min_candidates = 0; e->bound_matrix = true;
+    ScreenOptions opts = e->screen_opts;
+    opts.bound_min_candidates = 0; opts.bound_matrix = true;
     Plan plan;
     int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false);
-    e->bound_min_candidates = keep_min; e->bound_matrix = keep_mx;
+    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
     if (rc) return rc;
-    if (!plan.use_lb || plan.lb_mx_tiles <= 0) return set_error(MM_ERR_INVALID, "mm_pick_minima: the matrix-pipe bounded search does not take these sets");
+    if (!plan.use_lb || plan.kept_nct <= 0) return set_error(MM_ERR_INVALID, "mm_pick_minima: the matrix-pipe bounded search does not take these sets");
     const WorkItem item{0, 0, 1, 0};
     const int32_t counters[8] = {0, 1, 0, 0, 0, 0, 0, 0};
     MM_HIP(hipMemcpyAsync(plan.dev.items_pick, &item, sizeof item, hipMemcpyHostToDevice, plan.stream));
@@ -1355,18 +1369,17 @@ int mm_screen_values(mm_engine* h, const double* rx, const double* ry, int nr, c
     MM_HIP(hipSetDevice(e->device));
     std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
     std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
+    ScreenOptions opts = e->screen_opts;
+    opts.bound_min_candidates = 0; opts.screen_cull = cull != 0;
     Plan plan;
     int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_MATRIX, 0, INT32_MAX, false);
+    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_MATRIX, 0, INT32_MAX, false, nullptr, &opts);
     if (rc) return rc;
     bool ok = plan.A == n_angles && !plan.groups.empty();
-    for (const Plan::ScreenGroup& g : plan.groups) ok = ok && g.kind == 2 && mx_cull_takes(g.nct, g.multi, g.a_cap);
+    for (const Plan::ScreenGroup& g : plan.groups)
+        ok = ok && (g.screen == Screen::Matrix || g.screen == Screen::MatrixCull) && mx_cull_takes(g.nct, g.multi, g.a_cap);
     if (!ok) return set_error(MM_ERR_INVALID, "mm_screen_values: these sets do not take the matrix-pipe screen in one block");
-    const bool keep = e->screen_cull;
-    e->screen_cull = cull != 0;
-    rc = plan.run(true);
-    e->screen_cull = keep;
-    if (rc) return rc;
+    if ((rc = plan.run(true))) return rc;
     MM_HIP(hipMemcpyAsync(out_sq2, plan.dev.sq32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));
     if (e2) *e2 = plan.host_pairs[0].e2;

@@ -18,6 +18,16 @@ extern thread_local std::string g_last_error;
 int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);
 
+// The switches that choose a level's screens.  The engine holds the defaults (mm_engine_set_*); Plan::stage_level copies
+// them into the plan, and everything from there on -- the screen of every pair, the device description, run() -- reads
+// the plan's copy.
+struct ScreenOptions {
+    int64_t bound_min_candidates = 16384;   // MM_PRECISION_F32_BOUNDED: smaller batches skip the bound rounds
+    bool bound_matrix = true;               // MM_PRECISION_F32_BOUNDED: bounds, picks and survivors on the matrix pipe
+    int bound_matrix_qt = 1, bound_matrix_nc = 1;   // k_bound_mx's variant: query tiles per side, candidates per wave
+    bool screen_cull = true;                // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull
+};
+
 // One device + one stream + grow-only staging buffers (pinned host, device) reused by the
 // transient plans behind mm_best_rotation_batch, so the per-call cost in the sequential
 // chain is one H2D copy, the kernel launches and one D2H copy.
@@ -69,19 +79,16 @@ struct Engine {
     int64_t prof_candidates = 0;
     // bounded screen (MM_PRECISION_F32_BOUNDED) while profiling: candidates offered / bounded in round 1 (host
     // counts), device accumulators [1] bounded in round 2, [2] fully screened
-    int64_t bound_min_candidates = 16384;   // smaller batches skip the bound rounds (mm_engine_set_bound_min_candidates)
     int64_t bound_offered = 0, bound_round1 = 0;
-    bool bound_matrix = true;          // MM_PRECISION_F32_BOUNDED: bounds and survivors on the matrix pipe (mm_engine_set_bound_matrix)
-    int bound_matrix_qt = 1, bound_matrix_nc = 1;
-    bool bound_matrix_kept = false;    // survivors through k_screen_mx (measured slower than the packed-FMA screen: off)   // k_bound_mx's variant: query tiles per side, candidates per wave
+    // the switches levels staged from now on take (mm_engine_set_*)
+    ScreenOptions screen_opts;
     // candidates screened since the engine was created, by kernel: [0] direct-form f32, [1] packed FMA, [2] matrix pipe
     // (whole target set per wave), [3] matrix pipe (target set in column blocks), [4] exact f64 for every candidate
     // (mm_engine_screen_stats; atomics: levels are staged from several host threads)
     std::atomic<int64_t> screened[5] = {};
     unsigned long long* dev_stats = nullptr;
-    // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull (mm_engine_set_screen_cull); its tile
-    // counts (mm_engine_screen_tiles): computed (device counter) and what the full kernel computes for the same candidates
-    bool screen_cull = true;
+    // k_screen_mx_cull's tile counts (mm_engine_screen_tiles): computed (device counter) and what the full kernel computes
+    // for the same candidates
     unsigned long long* dev_tiles = nullptr;
     std::atomic<int64_t> cull_tiles_full{0};
     int profile_begin(hipStream_t s);
@@ -107,6 +114,11 @@ struct BatchResult {
     std::vector<int32_t> best_idx, n_rescored, near_cnt, near_idx;  // near_idx: kMaxNear per pair
     std::vector<double> best_cost;
 };
+
+// The screen of a pair searched without bound rounds, in the order the work list lays out its groups: none (a set of fewer
+// than 64 points: every candidate is scored exactly), direct-form f32, packed FMA, the matrix pipe (k_screen_mx), the
+// matrix pipe without the tiles that hold no minimum (k_screen_mx_cull).
+enum class Screen { None, Direct, PackedFma, Matrix, MatrixCull };
 
 // A staged batch: point pool (uploaded once) + a re-stageable level (descriptors, candidate
 // tables, outputs).  Transient plans borrow the engine's grow-only buffers.
@@ -139,15 +151,20 @@ struct Plan {
     std::vector<uint8_t> trivial;             // pair has an empty set: every cost is 0.0
     bool want_costs = false;
     bool use_fast = false;                    // expanded-form screening kernel selected
-    bool use_mx = false;                      // matrix-pipe screening kernel selected (MM_PRECISION_F32_MATRIX)
-    // MM_PRECISION_F32_MATRIX: the work list is grouped by screen variant, one launch per group.  kind 3 = no screen (a set of fewer than 64 points: every candidate scored exactly); kind 2 = k_screen_mx
-    // <nct, multi> with LDS for a_cap row tiles; kind 1 / 0 = the pairs outside its range (fewer than 64 or more than 2048
-    // points, radii f16 cannot scale): packed-FMA screen / direct-form f32 screen
-    struct ScreenGroup { int kind, nct, multi, a_cap, work_begin, work_count; };
+    ScreenOptions opts;                       // the switches this level was staged with
+    // Screens without bound rounds: the work list is grouped by screen, one launch per group, in the order of Screen and
+    // (multi, nct, cls).  Matrix / MatrixCull: k_screen_mx<nct, multi> / k_screen_mx_cull<nct> with LDS for a_cap row tiles;
+    // candidates and tiles_full (MatrixCull: the tiles the full kernel computes) feed Engine::screened / cull_tiles_full.
+    struct ScreenGroup {
+        Screen screen; int nct, multi, a_cap, work_begin, work_count;
+        int64_t candidates, tiles_full;
+    };
     std::vector<ScreenGroup> groups;
     bool use_lb = false;                      // lower-bound pass in front of the screen (MM_PRECISION_F32_BOUNDED)
     int W_lb = 0, lb_stride = 0, lb_runs_cap = 0, max_nt = 1;
-    int lb_mx_tiles = 0, kept_nct = 0, kept_acap = 0;   // bounded search on the matrix pipe (BatchDev::lb_mx, kept_mx_*)
+    // bounded search on the matrix pipe (kept_nct > 0): row tiles of k_bound_mx's LDS layout, k_screen_mx's variant for the
+    // picks and the survivors and its LDS cap (BatchDev::lb_mx, kept_mx_*)
+    int lb_mx_tiles = 0, kept_nct = 0, kept_acap = 0;
     double lb_pair_evals = 0.0;               // pair-distances of the first bound round
     int64_t lb_sparse_total = 0;              // candidates the first bound round scores
     std::vector<WorkItem> host_work_lb;
@@ -157,8 +174,9 @@ struct Plan {
     int alloc_pool(Engine* e, const std::vector<int32_t>& lens, bool transient);
     // `st` (nullable -> this->stream): the stream the staging copies go to
     int stage_sets(Engine* e, const std::vector<SetRef>& sets, bool transient, hipStream_t st = nullptr);
+    // `opts` (nullable -> the engine's current switches): what the level is staged with
     int stage_level(const std::vector<PairSpec>& pairs, int precision, int32_t angle_begin, int32_t angle_end,
-                    bool want_costs, hipStream_t st = nullptr);
+                    bool want_costs, hipStream_t st = nullptr, const ScreenOptions* opts = nullptr);
     int run(bool screen_only);
     int mark_search_done();   // resident plans: record Engine::search_done behind the dominant kernel
     int fetch(BatchResult& out, double* all_costs_plan_order);

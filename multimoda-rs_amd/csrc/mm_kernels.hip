@@ -1806,7 +1806,7 @@ template <bool FINAL>
 __global__ void __launch_bounds__(256)
 k_lb_keep(const PairDesc* __restrict__ pairs, const float* __restrict__ lb32, float* __restrict__ sq32,
           const int32_t* __restrict__ pick_idx, const int32_t* __restrict__ pick2, WorkItem* __restrict__ items,
-          int* __restrict__ n_items, unsigned long long* __restrict__ stats, uint8_t* __restrict__ flags)
+          int* __restrict__ n_items, unsigned long long* __restrict__ stats)
 {
     const int p = blockIdx.x, tid = threadIdx.x;
     const PairDesc pd = pairs[p];
@@ -1822,9 +1822,7 @@ k_lb_keep(const PairDesc* __restrict__ pairs, const float* __restrict__ lb32, fl
             const double sv = (double)lb32[pd.out_off + a] - pd.e2;
             const bool stays = a == c1 || a == c2 || sqrt(sv > 0.0 ? sv : 0.0) <= ub;
             if (stays) { if (first < 0) first = a; last = a; }
-            if (!FINAL && flags) flags[pd.out_off + a] = stays ? 1 : 0;     // every candidate of the pair: no stale flag survives
         }
-        if (!FINAL && flags) continue;   // (k_bound_mx_scan collects the flagged candidates itself and counts them)
         if (FINAL)
             for (int a = lo; a < hi; ++a)
                 if (a < first || a > last) sq32[pd.out_off + a] = __int_as_float(0x7f800000);
@@ -2287,6 +2285,10 @@ size_t lds_bytes_lb(int nap, int nbp) { return ((size_t)nap + (size_t)nbp) * 16;
 
 int lb_mx_max_points() { return 1024; }     // 32 row tiles per set: 64 KB of row fragments
 
+// the bounded search runs on the matrix pipe: bounds from k_bound_mx, survivors from k_lb_keep_mx, picks and survivors
+// screened by k_screen_mx<kept_mx_nct, false>
+static bool lb_matrix(const BatchDev& b) { return b.kept_mx_nct > 0; }
+
 // b.lb_mx_qt column tiles of queries per side (32 queries each), b.lb_mx_nc candidates per wave at once
 template <int QT, int NC, bool LIST>
 static hipError_t launch_lb_mx_v(const BatchDev& b, const WorkItem* work, int n_host, const int* n_dev, int cap, hipStream_t s)
@@ -2316,7 +2318,7 @@ template <int RP, bool LIST>
 static hipError_t launch_lb_t(const BatchDev& b, const WorkItem* work, int n_host, const int* n_dev, int cap,
                               int max_nap, int max_nbp, hipStream_t s)
 {
-    if (b.lb_mx > 0) return launch_lb_mx_t<LIST>(b, work, n_host, n_dev, cap, s);
+    if (lb_matrix(b)) return launch_lb_mx_t<LIST>(b, work, n_host, n_dev, cap, s);
     auto kern = k_screen_lb<RP, LIST>;
     const size_t lds = lds_bytes_lb(max_nap, max_nbp);
     if (lds > 48 * 1024) {
@@ -2361,7 +2363,7 @@ static hipError_t launch_lb_mx_scan(const BatchDev& b, int stat_slot, hipStream_
 hipError_t launch_screen_lb_queued(const BatchDev& b, int max_nap, int max_nbp, int cap, hipStream_t s)
 {
     if (cap <= 0) return hipSuccess;
-    if (b.lb_mx > 0) return launch_lb_mx_scan<false>(b, 1, s);
+    if (lb_matrix(b)) return launch_lb_mx_scan<false>(b, 1, s);
     return launch_lb_t<kLbRP, false>(b, b.items_lb, 0, b.n_items + 2, cap, max_nap, max_nbp, s);
 }
 
@@ -2369,7 +2371,7 @@ hipError_t launch_screen_lb_queued(const BatchDev& b, int max_nap, int max_nbp, 
 hipError_t launch_screen_lb_list(const BatchDev& b, int max_nap, int max_nbp, int cap, hipStream_t s)
 {
     if (cap <= 0) return hipSuccess;
-    if (b.lb_mx > 0) return launch_lb_mx_scan<true>(b, 3, s);
+    if (lb_matrix(b)) return launch_lb_mx_scan<true>(b, 3, s);
     return launch_lb_t<kLbListRP, true>(b, b.items_lb + cap, 0, b.n_items + 3, cap, max_nap, max_nbp, s);
 }
 
@@ -2389,7 +2391,7 @@ hipError_t launch_lb_pick(const BatchDev& b, int round, hipStream_t s)
 hipError_t launch_screen_picks(const BatchDev& b, int round, int max_na, int max_nbp, hipStream_t s)
 {
     if (b.n_pairs <= 0) return hipSuccess;
-    if (b.kept_mx_nct > 0) {
+    if (lb_matrix(b)) {
         // bounded search on the matrix pipe: the pick's value (the pair's upper bound) comes from the matrix kernel, and so
         // do, for the first pick, the row / column minima from which k_lb_topk chooses the third round's queries (the
         // generated block's `emit` form) -- no packed-FMA kernel runs under this precision any more (why that matters:
@@ -2431,7 +2433,7 @@ hipError_t launch_lb_topk(const BatchDev& b, int max_n, hipStream_t s)
 hipError_t launch_lb_spread(const BatchDev& b, hipStream_t s)
 {
     if (b.n_pairs <= 0) return hipSuccess;
-    uint8_t* flags = b.lb_mx > 0 ? b.flag : nullptr;
+    uint8_t* flags = lb_matrix(b) ? b.flag : nullptr;
     if (flags) {       // the candidates that need a bound of their own are flagged (k_bound_mx_scan), not queued
         hipError_t e = hipMemsetAsync(flags, 0, (size_t)b.n_cand, s);
         if (e != hipSuccess) return e;
@@ -2445,7 +2447,7 @@ hipError_t launch_lb_spread(const BatchDev& b, hipStream_t s)
 hipError_t launch_lb_keep(const BatchDev& b, int final, int cap, hipStream_t s)
 {
     if (b.n_pairs <= 0) return hipSuccess;
-    if (b.lb_mx > 0 && b.kept_mx_nct > 0) {
+    if (lb_matrix(b)) {
         if (!final)
             hipLaunchKernelGGL(k_lb_keep_mx<false>, dim3(b.n_pairs), dim3(256), 0, s, b.pairs, b.lb32, b.sq32, b.pick_idx,
                                (const int32_t*)nullptr, b.klist, b.items_lb + cap, b.n_items + 3, b.stats, b.flag);
@@ -2457,11 +2459,10 @@ hipError_t launch_lb_keep(const BatchDev& b, int final, int cap, hipStream_t s)
     }
     if (!final)
         hipLaunchKernelGGL(k_lb_keep<false>, dim3(b.n_pairs), dim3(256), 0, s, b.pairs, b.lb32, b.sq32, b.pick_idx,
-                           (const int32_t*)nullptr, b.items_lb + cap, b.n_items + 3, b.stats, b.lb_mx > 0 ? b.flag : (uint8_t*)nullptr);
+                           (const int32_t*)nullptr, b.items_lb + cap, b.n_items + 3, b.stats);
     else
         hipLaunchKernelGGL(k_lb_keep<true>, dim3(b.n_pairs), dim3(256), 0, s, b.pairs, b.lb32, b.sq32, b.pick_idx,
-                           (const int32_t*)(b.pick_idx + b.n_pairs), b.items_lb + 2 * (size_t)cap, b.n_items + 5, b.stats,
-                           (uint8_t*)nullptr);
+                           (const int32_t*)(b.pick_idx + b.n_pairs), b.items_lb + 2 * (size_t)cap, b.n_items + 5, b.stats);
     return hipGetLastError();
 }
 
@@ -2470,7 +2471,7 @@ hipError_t launch_screen_kept(const BatchDev& b, int max_na, int max_nbp, int ca
     if (cap <= 0) return hipSuccess;
     // every pair of the batch takes the same variant of the matrix-pipe screen: the survivors go through it (<= 8 entries
     // of a pair's list of survivors per queue item, one wave per candidate)
-    if (b.kept_mx_nct > 0)
+    if (lb_matrix(b))
         return launch_mx_any(b, b.items_lb + 2 * (size_t)cap, 0, b.n_items + 5, cap, b.kept_mx_nct, 0, b.kept_mx_acap, s, 4, b.klist);
     return launch_fast_any(b, b.items_lb + 2 * (size_t)cap, 0, b.n_items + 5, cap, max_na, max_nbp, false, s);
 }

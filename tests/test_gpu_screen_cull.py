@@ -118,3 +118,27 @@ def test_search_results_are_the_same_with_and_without_culling(engine, mm):
     (i0, a0, c0, k0), (i1, a1, c1, k1) = out
     assert (i0, a0, c0) == (i1, a1, c1)
     assert np.array_equal(np.asarray(k0), np.asarray(k1))
+
+
+def test_resident_plan_keeps_the_cull_switch_it_was_staged_with(engine, mm):
+    """The switches are read when a level is staged: a plan created with culling on still culls after it is turned off."""
+    from multimoda_rs_amd import synth
+    g = synth.synthetic_case(3)[1]
+    ref, tgt = _frame_sets(g, 0), _frame_sets(g, 1)
+    assert 64 <= min(len(ref), len(tgt)) and max(len(ref), len(tgt)) <= 544
+    angles = np.radians(np.linspace(-180.0, 180.0, 721))
+    centre = ref.mean(axis=0)
+    batch = mm.IndexedBatch([ref, tgt], [centre, centre], [0], [1], angles)
+    engine.set_screen_cull(True)
+    plan = engine.plan(batch, precision=mm.MM_PRECISION_F32_MATRIX)
+    try:
+        engine.set_screen_cull(False)
+        t0 = engine.screen_tiles()
+        plan.run()
+        t1 = engine.screen_tiles()
+    finally:
+        plan.close()
+        engine.set_screen_cull(True)
+    done, total = t1[0] - t0[0], t1[1] - t0[1]
+    assert total == len(angles) * ((len(ref) + 31) // 32) * ((len(tgt) + 31) // 32)
+    assert 0 < done < total
