@@ -1,7 +1,9 @@
 /*
  * mm_ccta.h -- C ABI of the CCTA diameter search: 41 radial scalings of a
  * vessel region scored by the symmetric RMS nearest-neighbour distance to a reference cloud, in
- * 3-D.  Same conventions as mm_hausdorff.h.  Points are xyz triples (f64), caller-owned.
+ * 3-D; and of the CCTA mesh labelling that produces the regions it scales (aorta / RCA / LCA,
+ * with occlusion removal by ray casting at an acute take-off).  Same conventions as
+ * mm_hausdorff.h.  Points are xyz triples (f64), caller-owned.
  *
  * Reference interfaces replaced (paths relative to the reference checkout):
  *   src/ccta/adjust_mesh/scale_coronary.rs:8-63     centerline_based_wall_diameter_optimization
@@ -12,13 +14,20 @@
  *   src/ccta/adjust_mesh/scale_coronary.rs:218-261  centerline_based_diameter_morphing
  *   src/ccta/adjust_mesh/scale_coronary.rs:263-340  find_points_by_cl_region_rs, find_cl_points_in_range
  *   src/ccta/adjust_mesh/scale_coronary.rs:342-409  clean_up_non_section_points
- * Python entry points that bind them: src/ccta/binding/ccta_py.rs:263-481
- * (adjust_diameter_centerline_morphing_simple, find_proximal_distal_scaling, find_aortic_scaling,
- * find_aortic_wall_scaling), wrapped by multimodars/ccta/scaling.py.
+ *   src/ccta/adjust_mesh/label_coronary.rs:29-197  ray_triangle_intersection, remove_occluded_points_ray_triangle_rust
+ *   src/ccta/adjust_mesh/label_coronary.rs:201-289 find_centerline_bounded_points, find_faces_near_points
+ *   src/ccta/adjust_mesh/label_coronary.rs:296-640 find_aortic_points, final_reclassification
+ * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481
+ * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
+ * find_aortic_points, final_reclassification, adjust_diameter_centerline_morphing_simple,
+ * find_proximal_distal_scaling, find_aortic_scaling, find_aortic_wall_scaling), wrapped by
+ * multimodars/ccta/labeling.py (label_geometry) and multimodars/ccta/scaling.py.
  *
  * All nearest-neighbour minima are computed on the device in exact f64 (mm_nn_kernels.hip); the
  * per-point minima are summed on the host in index order (the reference's rayon sum has no fixed
- * order; the sequential one is among those it can produce).
+ * order; the sequential one is among those it can produce).  The labelling's ray-triangle tests run
+ * on the device in exact f64 (mm_ray_kernels.hip); its radius queries use the same exact radius
+ * counts as mm_clean_outlier_points; the bookkeeping on adjacency graphs is host C++.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -78,6 +87,42 @@ int     mm_clean_outlier_points(mm_engine* e, const double* cleanup_xyz, int64_t
 int     mm_find_points_by_cl_region(mm_engine* e, const mm_clpoint* cl, const uint32_t* cl_frame_index, int64_t ncl,
                                     const double* frame_centroids_xyz, int64_t n_frames, const double* points_xyz,
                                     int64_t n, uint8_t* label);
+
+/* ---- mesh labelling (label_coronary.rs).  Flag outputs: the caller selects the points. ---------------------------- */
+
+/* find_centerline_bounded_points (:201-235): inside[i] = 1 iff some centerline point lies within squared distance
+ * <= radius * radius of point i.  Returns the number inside; an empty point set or centerline is MM_ERR_INVALID
+ * (the reference's Err, :206-209). */
+int64_t mm_centerline_bounded_points(mm_engine* e, const mm_clpoint* cl, int64_t ncl, const double* pts_xyz, int64_t n,
+                                     double radius, uint8_t* inside);
+/* find_faces_near_points (:242-289): a vertex matches iff some point lies within squared distance <= tol * tol;
+ * face_selected[f] = 1 iff a corner of face f matches.  faces: nf index triples into vertices; an index out of range
+ * is MM_ERR_INVALID.  Returns the number of faces selected (0 if any input is empty). */
+int64_t mm_faces_near_points(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                             const double* pts_xyz, int64_t n, double tol, uint8_t* face_selected);
+/* remove_occluded_points_ray_triangle_rust (:70-197).  tri: nf triangles of 9 doubles (v0, v1, v2).  Rays run from
+ * every aortic centerline point to the coronary points take(ceil(range_mm / s)).step_by(ceil(step_size_mm / s)), s
+ * the mean of the two centerlines' mean spacings (Rust's saturating casts); a ray that hits at least 3 faces excludes
+ * the one of smallest t (ties: lowest index).  removed[i] = 1 iff a vertex of an excluded face lies within squared
+ * distance <= 0.5 of point i; face_excluded (nullable) receives the excluded faces.  Returns the number removed.
+ * Empty points, faces or aortic centerline: nothing removed; a step of 0 points: MM_ERR_INVALID (a panic there). */
+int64_t mm_occluded_points(mm_engine* e, const mm_clpoint* cl_coronary, int64_t ncc, const mm_clpoint* cl_aorta,
+                           int64_t nca, double range_mm, const double* pts_xyz, int64_t n, const double* tri,
+                           int64_t nf, double step_size_mm, uint8_t* removed, uint8_t* face_excluded);
+/* find_aortic_points (:296-313), host: keep[i] = 1 iff vertex i is bit-for-bit in neither a nor b.  Returns the
+ * number kept. */
+int64_t mm_find_aortic_points(const double* vertices_xyz, int64_t nv, const double* a_xyz, int64_t na,
+                              const double* b_xyz, int64_t nb, uint8_t* keep);
+/* final_reclassification (:337-640), host.  label[v]: 0 aorta, 1 rca, 2 lca, 3 rca removed, 4 lca removed.  Points
+ * are matched to vertices by bit pattern (the last of duplicated vertices wins) and applied in the order rca, lca,
+ * rca removed, lca removed; then minority components move to a neighbouring label (> 70 % of their boundary) and
+ * removed vertices are restored by round-synchronous majority votes.  Of equally large largest components the one
+ * with the smallest vertex index is kept (the reference picks one of them in hash order).  A face index out of range
+ * is MM_ERR_INVALID. */
+int     mm_final_reclassification(const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                                  const double* rca_xyz, int64_t nr, const double* lca_xyz, int64_t nl,
+                                  const double* rca_removed_xyz, int64_t nrr, const double* lca_removed_xyz, int64_t nlr,
+                                  uint8_t* label);
 
 #ifdef __cplusplus
 }

@@ -120,7 +120,9 @@ int  mm_engine_wait_exchange(mm_engine* waiter, mm_engine* other);
 /* Per-launch timing of the dominant (candidate-scoring) kernel with hipEvents recorded on
  * the engine's stream around every launch.  mm_engine_profile_read synchronizes, returns
  * the number of launches, their summed device time (ms), the pair-distance evaluations
- * (2*Na*Nb per candidate) and candidates they covered, and resets the accumulators. */
+ * (2*Na*Nb per candidate) and candidates they covered, and resets the accumulators.  The ray
+ * pass of mm_occluded_points (mm_ccta.h) is timed the same way, one launch per call, its
+ * ray-triangle tests counted as pair evaluations. */
 int  mm_engine_profile(mm_engine* e, int enable);
 int  mm_engine_profile_read(mm_engine* e, int64_t* n_launches, double* ms_total,
                             double* pair_evals, int64_t* candidates);

@@ -99,6 +99,8 @@ EXPORTS_CCTA = [
     "mm_nn_min_sq_batch", "mm_symmetric_nn_distance", "mm_diameter_morphing", "mm_find_region_points",
     "mm_aortic_diameter_optimization", "mm_diameter_optimization", "mm_wall_diameter_optimization",
     "mm_clean_outlier_points", "mm_find_points_by_cl_region",
+    "mm_centerline_bounded_points", "mm_faces_near_points", "mm_occluded_points", "mm_find_aortic_points",
+    "mm_final_reclassification",
 ]
 
 
@@ -414,6 +416,16 @@ def lib():
     L.mm_find_points_by_cl_region.argtypes = [P, P, P, I64, P, I64, P, I64, P]
     L.mm_wall_diameter_optimization.restype = I
     L.mm_wall_diameter_optimization.argtypes = [P, I64, P, P, I64, C.POINTER(D)]
+    L.mm_centerline_bounded_points.restype = I64
+    L.mm_centerline_bounded_points.argtypes = [P, P, I64, P, I64, D, P]
+    L.mm_faces_near_points.restype = I64
+    L.mm_faces_near_points.argtypes = [P, P, I64, P, I64, P, I64, D, P]
+    L.mm_occluded_points.restype = I64
+    L.mm_occluded_points.argtypes = [P, P, I64, P, I64, D, P, I64, P, I64, D, P, P]
+    L.mm_find_aortic_points.restype = I64
+    L.mm_find_aortic_points.argtypes = [P, I64, P, I64, P, I64, P]
+    L.mm_final_reclassification.restype = I
+    L.mm_final_reclassification.argtypes = [P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P]
     _lib = L
     return L
 

@@ -1,4 +1,7 @@
-"""CCTA diameter search, mirroring the reference's entry points
+"""CCTA mesh labelling and diameter search.  Labelling mirrors the reference's
+``label_geometry`` (multimodars/ccta/labeling.py:23-280) and the entry points it composes
+(src/ccta/binding/ccta_py.rs:52-262, implementation src/ccta/adjust_mesh/label_coronary.rs); the
+diameter search mirrors the reference's entry points
 ``adjust_diameter_centerline_morphing_simple`` / ``find_proximal_distal_scaling`` /
 ``find_aortic_scaling`` / ``find_aortic_wall_scaling`` (src/ccta/binding/ccta_py.rs:263-481;
 implementation src/ccta/adjust_mesh/scale_coronary.rs:8-261) and the wrapper
@@ -211,3 +214,152 @@ def find_points_by_cl_region(centerline: Centerline, frames, points, engine: Opt
                                                 N._ptr(lab)), "find_points_by_cl_region")
     out = (p[lab == 0].copy(), p[lab == 1].copy(), np.concatenate([p[lab == 2], p[lab == 3], p[lab == 4]], axis=0))
     return out + (lab,) if return_labels else out
+
+
+# ---- mesh labelling (src/ccta/adjust_mesh/label_coronary.rs, multimodars/ccta/labeling.py) -----------------------
+
+def _faces3(faces) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
+
+
+def _tris(faces) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(faces, dtype=np.float64).reshape(-1, 9))
+
+
+def find_centerline_bounded_points_simple(centerline: Centerline, points, radius: float,
+                                          engine: Optional[N.Engine] = None) -> np.ndarray:
+    """ccta_py.rs:52-76 -> find_centerline_bounded_points (label_coronary.rs:201-235): the points within ``radius`` of
+    some centerline point (squared distance <= radius * radius), in input order, duplicates kept.  An empty point set
+    or centerline raises ValueError, as the reference does."""
+    p = _p3(points)
+    if p.shape[0] == 0 or len(centerline) == 0:
+        raise ValueError("find_centerline_bounded_points failed because `Centerline` is empty")
+    inside = np.zeros(p.shape[0], dtype=np.uint8)
+    k = N.lib().mm_centerline_bounded_points(_engine(engine).handle, N._ptr(centerline.points), len(centerline),
+                                             N._ptr(p), p.shape[0], float(radius), N._ptr(inside))
+    if k < 0:
+        N.check(int(k), "find_centerline_bounded_points_simple")
+    return p[inside == 1].copy()
+
+
+def find_faces_near_points(vertices, faces, points, tol: float = 1e-6, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """ccta_py.rs:176-207 -> label_coronary.rs:242-289: every face (in face order) with a corner within ``tol`` of one
+    of ``points``, as an ``(F, 3, 3)`` array of its corner coordinates."""
+    v, f, p = _p3(vertices), _faces3(faces), _p3(points)
+    sel = np.zeros(f.shape[0], dtype=np.uint8)
+    k = N.lib().mm_faces_near_points(_engine(engine).handle, N._ptr(v), v.shape[0], N._ptr(f), f.shape[0], N._ptr(p),
+                                     p.shape[0], float(tol), N._ptr(sel))
+    if k < 0:
+        N.check(int(k), "find_faces_near_points")
+    return v[f[sel == 1]].reshape(-1, 3, 3).copy()
+
+
+def occluded_point_flags(centerline_coronary: Centerline, centerline_aorta: Centerline, range_mm: float, points, faces,
+                         step_size_mm: float = 1.0, engine: Optional[N.Engine] = None):
+    """The flags behind remove_occluded_points_ray_triangle: (removed per point, excluded per face) as uint8 arrays."""
+    p, t = _p3(points), _tris(faces)
+    removed = np.zeros(p.shape[0], dtype=np.uint8)
+    excluded = np.zeros(t.shape[0], dtype=np.uint8)
+    k = N.lib().mm_occluded_points(_engine(engine).handle, N._ptr(centerline_coronary.points), len(centerline_coronary),
+                                   N._ptr(centerline_aorta.points), len(centerline_aorta), float(range_mm), N._ptr(p),
+                                   p.shape[0], N._ptr(t), t.shape[0], float(step_size_mm), N._ptr(removed),
+                                   N._ptr(excluded))
+    if k < 0:
+        N.check(int(k), "remove_occluded_points_ray_triangle")
+    return removed, excluded
+
+
+def remove_occluded_points_ray_triangle(centerline_coronary: Centerline, centerline_aorta: Centerline, range_mm: float,
+                                        points, faces, step_size_mm: float = 1.0,
+                                        engine: Optional[N.Engine] = None) -> np.ndarray:
+    """ccta_py.rs:78-150 -> label_coronary.rs:70-197: rays from every aortic centerline point to the coronary points
+    within ``range_mm`` of the ostium (every ``step_size_mm``); a ray that crosses at least 3 of ``faces`` (``(F, 3, 3)``
+    triangles) excludes the face it hits first, and the points within squared distance 0.5 of a vertex of an excluded
+    face are removed.  Returns the remaining points in input order.  The ray-triangle tests run on the device in
+    exact f64 (csrc/mm_ray_kernels.hip)."""
+    p = _p3(points)
+    removed, _ = occluded_point_flags(centerline_coronary, centerline_aorta, range_mm, p, faces, step_size_mm, engine)
+    return p[removed == 0].copy()
+
+
+def find_aortic_points(vertices, points_a, points_b) -> np.ndarray:
+    """ccta_py.rs:209-235 -> label_coronary.rs:296-313 (host): the vertices whose coordinates are bit for bit in
+    neither ``points_a`` nor ``points_b``, in vertex order."""
+    v, a, b = _p3(vertices), _p3(points_a), _p3(points_b)
+    keep = np.zeros(v.shape[0], dtype=np.uint8)
+    k = N.lib().mm_find_aortic_points(N._ptr(v), v.shape[0], N._ptr(a), a.shape[0], N._ptr(b), b.shape[0], N._ptr(keep))
+    if k < 0:
+        N.check(int(k), "find_aortic_points")
+    return v[keep == 1].copy()
+
+
+def final_reclassification(vertices, faces, rca_points, lca_points, rca_removed_points, lca_removed_points,
+                           return_labels: bool = False):
+    """ccta_py.rs:237-262 -> label_coronary.rs:337-640 (host): vertex labels from the four point lists, smoothed on
+    the mesh adjacency (minority components join a neighbouring label, removed vertices are restored by majority
+    votes).  Returns (aorta, rca, lca, rca_removed, lca_removed) vertices in vertex order (and the per-vertex labels
+    0..4 with ``return_labels``).  Of equally large largest components the one holding the smallest vertex index is
+    kept; the reference picks one of them in hash order, so this is one of its possible outcomes."""
+    v, f = _p3(vertices), _faces3(faces)
+    lists = [_p3(x) for x in (rca_points, lca_points, rca_removed_points, lca_removed_points)]
+    lab = np.zeros(v.shape[0], dtype=np.uint8)
+    args = []
+    for x in lists:
+        args += [N._ptr(x), x.shape[0]]
+    N.check(N.lib().mm_final_reclassification(N._ptr(v), v.shape[0], N._ptr(f), f.shape[0], *args, N._ptr(lab)),
+            "final_reclassification")
+    out = tuple(v[lab == k].copy() for k in range(5))
+    return out + (lab,) if return_labels else out
+
+
+def _apply_occlusion_removal(range_mm: float, step_size_mm: float, tol: float, cl_aorta: Centerline,
+                             cl_coronary: Centerline, vertices, faces, found, engine):
+    """labeling.py:252-280: (removed, kept) of the points ``found`` near a coronary centerline."""
+    tris = find_faces_near_points(vertices, faces, found, tol, engine=engine)
+    removed, _ = occluded_point_flags(cl_coronary, cl_aorta, range_mm, found, tris, step_size_mm, engine)
+    kept = found[removed == 0].copy()
+    # `[p for p in found if p not in set(kept)]`: a point with a NaN coordinate equals nothing, so it lands in both
+    gone = (removed == 1) | np.isnan(found).any(axis=1)
+    return found[gone].copy(), kept
+
+
+def label_geometry(mesh, centerline_aorta: Centerline, centerline_rca: Centerline, centerline_lca: Centerline,
+                   acute_takeoff_rca: bool = False, acute_takeoff_lca: bool = False, range_mm_takeoff_rca: float = 60.0,
+                   range_mm_takeoff_lca: float = 60.0, step_size_mm: float = 1.0,
+                   bounding_sphere_radius_mm_rca: float = 3.0, bounding_sphere_radius_mm_lca: float = 3.0,
+                   tolerance_float: float = 1e-6, control_plot: bool = True,
+                   engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/labeling.py:23-250: label the vertices of a CCTA surface mesh as aorta, RCA or LCA.
+
+    ``mesh``: a ``(vertices, faces)`` pair or any object with ``.vertices`` / ``.faces`` (a ``trimesh.Trimesh``
+    works; it is not read here).  The vertices within the bounding sphere radius of a coronary centerline are that
+    coronary's; with an acute take-off the points behind the aortic wall are removed by ray casting; outliers are
+    cleaned against the aorta and the labels smoothed on the mesh adjacency (final_reclassification).  No file is
+    read and nothing is plotted (``control_plot`` is accepted and ignored).  Returns the reference's dict: ``"mesh"``
+    (what was passed), ``"aorta_points"``, ``"rca_points"``, ``"lca_points"``, ``"rca_removed_points"``,
+    ``"lca_removed_points"`` as ``(n, 3)`` arrays."""
+    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
+        vertices, faces = mesh.vertices, mesh.faces
+    else:
+        vertices, faces = mesh
+    v, f = _p3(vertices), _faces3(faces)
+    eng = _engine(engine)
+    rca_found = find_centerline_bounded_points_simple(centerline_rca, v, bounding_sphere_radius_mm_rca, engine=eng)
+    lca_found = find_centerline_bounded_points_simple(centerline_lca, v, bounding_sphere_radius_mm_lca, engine=eng)
+    empty = np.zeros((0, 3), dtype=np.float64)
+    if acute_takeoff_rca:
+        rca_removed, rca_kept = _apply_occlusion_removal(range_mm_takeoff_rca, step_size_mm, tolerance_float,
+                                                         centerline_aorta, centerline_rca, v, f, rca_found, eng)
+    else:
+        rca_removed, rca_kept = empty, rca_found
+    if acute_takeoff_lca:
+        lca_removed, lca_kept = _apply_occlusion_removal(range_mm_takeoff_lca, step_size_mm, tolerance_float,
+                                                         centerline_aorta, centerline_lca, v, f, lca_found, eng)
+    else:
+        lca_removed, lca_kept = empty, lca_found
+    aortic = find_aortic_points(v, rca_kept, lca_kept)
+    lca_pts, aortic2 = clean_outlier_points(lca_kept, aortic, 2.0, 0.4, engine=eng)      # labeling.py:184-189
+    rca_pts, _ = clean_outlier_points(rca_kept, aortic2, 2.0, 0.4, engine=eng)
+    aorta, rca, lca, rca_rm, lca_rm = final_reclassification(v, f, rca_pts, lca_pts, rca_removed, lca_removed)
+    return {"mesh": mesh, "aorta_points": aorta, "rca_points": rca, "lca_points": lca, "rca_removed_points": rca_rm,
+            "lca_removed_points": lca_rm}

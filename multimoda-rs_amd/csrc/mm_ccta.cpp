@@ -8,6 +8,8 @@
 #include <cmath>
 #include <cstring>
 #include <numeric>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/mm_ccta.h"
@@ -596,6 +598,254 @@ int engine_of(mm_engine* h, Engine*& e)
     return MM_OK;
 }
 
+
+// ---- mesh labelling (src/ccta/adjust_mesh/label_coronary.rs) -----------------------------------------------------
+
+// Centerline::mean_spacing (centerline.rs:304-320): mean distance of consecutive points of the first branch (the
+// points before the first change of branch id), 1.0 below two points; summed in index order
+double cl_mean_spacing(const mm_clpoint* cl, int64_t n)
+{
+    if (n <= 0) return 1.0;
+    int64_t end = 1;
+    while (end < n && cl[end].branch_id == cl[0].branch_id) ++end;
+    if (end < 2) return 1.0;
+    double s = 0.0;
+    for (int64_t i = 1; i < end; ++i) {
+        const double dx = cl[i - 1].x - cl[i].x, dy = cl[i - 1].y - cl[i].y, dz = cl[i - 1].z - cl[i].z;
+        s += std::sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    return s / (double)(end - 1);
+}
+
+// Rust's saturating `x as usize`: NaN and negatives -> 0, beyond the range -> the maximum
+uint64_t sat_usize(double x)
+{
+    if (!(x > 0.0)) return 0;
+    if (x >= 18446744073709551616.0) return UINT64_MAX;
+    return (uint64_t)x;
+}
+
+std::vector<double> cl_xyz(const mm_clpoint* cl, int64_t n)
+{
+    std::vector<double> v((size_t)n * 3);
+    for (int64_t i = 0; i < n; ++i) { v[3 * i] = cl[i].x; v[3 * i + 1] = cl[i].y; v[3 * i + 2] = cl[i].z; }
+    return v;
+}
+
+// remove_occluded_points_ray_triangle_rust (:70-197).  removed[i] = 1: point i goes; excluded[f] = 1: face f is the
+// closest hit of some ray that hits >= 3 faces.  Rays on the device (mm_ray_kernels.hip), the vertex pass on the
+// radius-count path.
+int occluded_points(Engine* e, const mm_clpoint* cc, int64_t ncc, const mm_clpoint* ca, int64_t nca, double range_mm,
+                    const double* pts, int64_t n, const double* tri, int64_t nf, double step_mm,
+                    std::vector<uint8_t>& removed, std::vector<uint8_t>& excluded)
+{
+    removed.assign((size_t)n, 0);
+    excluded.assign((size_t)nf, 0);
+    if (n == 0 || nf == 0 || nca == 0) return MM_OK;                                   // :78-80; no aortic point, no ray
+    const double spacing = (cl_mean_spacing(ca, nca) + cl_mean_spacing(cc, ncc)) / 2.0;   // :85
+    const uint64_t step = sat_usize(std::ceil(step_mm / spacing));                         // :86
+    const uint64_t range = sat_usize(std::ceil(range_mm / spacing));                       // :89
+    if (step == 0) return set_error(MM_ERR_INVALID, "mm_occluded_points: step_size_mm / spacing gives a step of 0 points");
+    // the coronary points of .take(range).step_by(step) (:104-108)
+    std::vector<int64_t> cor;
+    const uint64_t lim = std::min<uint64_t>(range, (uint64_t)ncc);
+    for (uint64_t i = 0; i < lim;) {
+        cor.push_back((int64_t)i);
+        if (step >= lim - i) break;
+        i += step;
+    }
+    const int64_t R = nca * (int64_t)cor.size();
+    if (R == 0) return MM_OK;
+    const int ch = ray_chunk_faces(), rb = ray_block_rays();
+    const int64_t n_chunks = (nf + ch - 1) / ch, n_rblk = (R + rb - 1) / rb;
+    const size_t part_bytes = ray_partial_bytes() * (size_t)R * (size_t)n_chunks;
+    if (R > INT32_MAX / 8 || nf > INT32_MAX / 16 || n_chunks * n_rblk > INT32_MAX || part_bytes > ((size_t)4 << 30))
+        return set_error(MM_ERR_TOO_LARGE, "mm_occluded_points: too many rays x faces for one pass");
+    const size_t o_tri = up256((size_t)R * 6 * 8), in_bytes = up256(o_tri + (size_t)nf * 9 * 8);
+    const size_t o_part = in_bytes, o_cl = up256(o_part + part_bytes), total = up256(o_cl + (size_t)R * 4);
+    int rc = e->ensure(e->host_pts, std::max(in_bytes, (size_t)R * 4), true);
+    if (rc) return rc;
+    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
+    unsigned char* h = (unsigned char*)e->host_pts.p;
+    double* hr = (double*)h;
+    double* ht = (double*)(h + o_tri);
+    const int64_t nc = (int64_t)cor.size();
+    for (int64_t a = 0; a < nca; ++a)
+        for (int64_t k = 0; k < nc; ++k) {
+            const int64_t r = a * nc + k;
+            const mm_clpoint& o = ca[a];
+            const mm_clpoint& c = cc[cor[(size_t)k]];
+            hr[r] = o.x; hr[R + r] = o.y; hr[2 * R + r] = o.z;
+            hr[3 * R + r] = c.x - o.x; hr[4 * R + r] = c.y - o.y; hr[5 * R + r] = c.z - o.z;        // :117 coronary - aorta
+        }
+    for (int64_t f = 0; f < nf; ++f) {
+        const double* t = tri + 9 * f;
+        for (int ax = 0; ax < 3; ++ax) {
+            ht[(size_t)ax * nf + f] = t[ax];                                                         // v0
+            ht[(size_t)(3 + ax) * nf + f] = t[3 + ax] - t[ax];                                       // edge1 = v1 - v0 (:38)
+            ht[(size_t)(6 + ax) * nf + f] = t[6 + ax] - t[ax];                                       // edge2 = v2 - v0 (:39)
+        }
+    }
+    unsigned char* d = (unsigned char*)e->dev_pts.p;
+    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->profile_begin(e->stream))) return rc;
+    const hipError_t he = launch_ray_tri((const double*)d, (int)R, (const double*)(d + o_tri), (int)nf, d + o_part,
+                                         (int32_t*)(d + o_cl), e->stream);
+    if (he != hipSuccess) return hip_error(he, "ray-triangle launch");
+    if ((rc = e->profile_end(e->stream, (double)R * (double)nf, 0))) return rc;
+    MM_TRY_HIP(hipMemcpyAsync(h, d + o_cl, (size_t)R * 4, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    const int32_t* closest = (const int32_t*)h;
+    for (int64_t r = 0; r < R; ++r)
+        if (closest[r] >= 0) excluded[(size_t)closest[r]] = 1;
+    // :143-183 a point goes iff a vertex of an excluded face lies within squared distance 0.5
+    std::vector<double> ev;
+    for (int64_t f = 0; f < nf; ++f)
+        if (excluded[(size_t)f]) ev.insert(ev.end(), tri + 9 * f, tri + 9 * f + 9);
+    if (ev.empty()) return MM_OK;
+    std::vector<std::vector<uint32_t>> cnt;
+    if ((rc = radius_counts(e, {Set3{pts, n}, Set3{ev.data(), (int64_t)(ev.size() / 3)}}, {{0, 1}}, 0.5, cnt))) return rc;
+    for (int64_t i = 0; i < n; ++i) removed[(size_t)i] = cnt[0][(size_t)i] > 0 ? 1 : 0;
+    return MM_OK;
+}
+
+// exact bit-pattern key of a coordinate (bits_key, :293)
+struct BitsKey {
+    uint64_t x, y, z;
+    bool operator==(const BitsKey& o) const { return x == o.x && y == o.y && z == o.z; }
+};
+struct BitsHash {
+    size_t operator()(const BitsKey& k) const
+    {
+        uint64_t h = k.x * 0x9E3779B97F4A7C15ull;
+        h ^= k.y + 0x7F4A7C159E3779B9ull + (h << 6) + (h >> 2);
+        h ^= k.z + 0x94D049BB133111EBull + (h << 6) + (h >> 2);
+        return (size_t)h;
+    }
+};
+inline BitsKey bits_key(const double* p)
+{
+    BitsKey k;
+    std::memcpy(&k.x, p, 8); std::memcpy(&k.y, p + 1, 8); std::memcpy(&k.z, p + 2, 8);
+    return k;
+}
+
+// build_adjacency_map (ccta_py.rs:507-525) as sorted, de-duplicated neighbour lists (a face with a repeated corner
+// makes that vertex its own neighbour, as in the reference)
+struct Adjacency {
+    std::vector<int64_t> off, nb;
+    const int64_t* begin(int64_t v) const { return nb.data() + off[(size_t)v]; }
+    const int64_t* end(int64_t v) const { return nb.data() + off[(size_t)v + 1]; }
+};
+void build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, Adjacency& adj)
+{
+    std::vector<std::pair<int64_t, int64_t>> ed;
+    ed.reserve((size_t)nf * 6);
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t* v = faces + 3 * f;
+        const int64_t e[3][2] = {{v[0], v[1]}, {v[1], v[2]}, {v[2], v[0]}};
+        for (const auto& p : e) { ed.emplace_back(p[0], p[1]); ed.emplace_back(p[1], p[0]); }
+    }
+    std::sort(ed.begin(), ed.end());
+    ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
+    adj.off.assign((size_t)nv + 1, 0);
+    for (const auto& p : ed) ++adj.off[(size_t)p.first + 1];
+    for (int64_t v = 0; v < nv; ++v) adj.off[(size_t)v + 1] += adj.off[(size_t)v];
+    adj.nb.resize(ed.size());
+    for (size_t k = 0; k < ed.size(); ++k) adj.nb[k] = ed[k].second;   // sorted by first: already in CSR order
+}
+
+// reclassify_minority_components (:485-544).  Components are found from their smallest vertex upwards; the largest
+// one is kept out, and among equally large ones the one with the smallest vertex index: the reference picks one of
+// them in HashSet order, so this is one of the outcomes it can produce.
+void reclassify_minority(const Adjacency& adj, const std::vector<uint8_t>& labels, std::vector<uint8_t>& out,
+                         uint8_t subject, const std::vector<uint8_t>& targets)
+{
+    const int64_t nv = (int64_t)labels.size();
+    std::vector<int64_t> comp((size_t)nv, -1);
+    std::vector<std::vector<int64_t>> comps;
+    for (int64_t s = 0; s < nv; ++s) {
+        if (labels[(size_t)s] != subject || comp[(size_t)s] >= 0) continue;
+        const int64_t c = (int64_t)comps.size();
+        comps.emplace_back();
+        std::vector<int64_t> stack{s};
+        comp[(size_t)s] = c;
+        while (!stack.empty()) {
+            const int64_t v = stack.back();
+            stack.pop_back();
+            comps.back().push_back(v);
+            for (const int64_t* p = adj.begin(v); p != adj.end(v); ++p)
+                if (labels[(size_t)*p] == subject && comp[(size_t)*p] < 0) { comp[(size_t)*p] = c; stack.push_back(*p); }
+        }
+    }
+    if (comps.empty()) return;
+    size_t largest = 0;
+    for (size_t c = 1; c < comps.size(); ++c)
+        if (comps[c].size() > comps[largest].size()) largest = c;
+    std::vector<int64_t> mark((size_t)nv, -1);
+    for (size_t c = 0; c < comps.size(); ++c) {
+        if (c == largest) continue;
+        int64_t bsize = 0;                                                            // component_boundary (:463-476)
+        std::vector<int64_t> tcnt(targets.size(), 0);
+        for (const int64_t v : comps[c])
+            for (const int64_t* p = adj.begin(v); p != adj.end(v); ++p)
+                if (comp[(size_t)*p] != (int64_t)c && mark[(size_t)*p] != (int64_t)c) {
+                    mark[(size_t)*p] = (int64_t)c;
+                    ++bsize;
+                    for (size_t k = 0; k < targets.size(); ++k) tcnt[k] += labels[(size_t)*p] == targets[k] ? 1 : 0;
+                }
+        if (bsize == 0) continue;
+        for (size_t k = 0; k < targets.size(); ++k)
+            if ((double)tcnt[k] > (double)bsize * 0.7) {                                // :533-541, first target wins
+                for (const int64_t v : comps[c]) out[(size_t)v] = targets[k];
+                break;
+            }
+    }
+}
+
+// restore_removed_by_propagation (:546-631): round 0 tallies each removed vertex's real neighbours; every later round
+// the vertices decided in the previous round vote for their undecided removed neighbours, all votes of a round applied
+// together; a strict majority decides, ties stay undecided (and removed)
+void restore_removed(const Adjacency& adj, const std::vector<uint8_t>& labels, std::vector<uint8_t>& out,
+                     uint8_t removed_label, uint8_t target)
+{
+    const int64_t nv = (int64_t)labels.size();
+    std::vector<int64_t> tc((size_t)nv, 0), oc((size_t)nv, 0), dt((size_t)nv, 0), dn((size_t)nv, 0);
+    std::vector<int8_t> dec((size_t)nv, -1);
+    std::vector<uint8_t> touched((size_t)nv, 0);
+    std::vector<int64_t> frontier;
+    for (int64_t v = 0; v < nv; ++v) {
+        if (labels[(size_t)v] != removed_label) continue;
+        for (const int64_t* p = adj.begin(v); p != adj.end(v); ++p) {
+            const uint8_t l = labels[(size_t)*p];
+            if (l == removed_label) continue;
+            if (l == target) ++tc[(size_t)v]; else ++oc[(size_t)v];
+        }
+        if (tc[(size_t)v] != oc[(size_t)v]) { dec[(size_t)v] = tc[(size_t)v] > oc[(size_t)v] ? 1 : 0; frontier.push_back(v); }
+    }
+    while (!frontier.empty()) {
+        std::vector<int64_t> hit;
+        for (const int64_t v : frontier) {
+            const bool is_t = dec[(size_t)v] == 1;
+            for (const int64_t* p = adj.begin(v); p != adj.end(v); ++p) {
+                const int64_t u = *p;
+                if (labels[(size_t)u] != removed_label || dec[(size_t)u] >= 0) continue;
+                if (!touched[(size_t)u]) { touched[(size_t)u] = 1; hit.push_back(u); }
+                if (is_t) ++dt[(size_t)u]; else ++dn[(size_t)u];
+            }
+        }
+        std::vector<int64_t> next;
+        for (const int64_t u : hit) {
+            tc[(size_t)u] += dt[(size_t)u]; oc[(size_t)u] += dn[(size_t)u];
+            dt[(size_t)u] = dn[(size_t)u] = 0; touched[(size_t)u] = 0;
+            if (tc[(size_t)u] != oc[(size_t)u]) { dec[(size_t)u] = tc[(size_t)u] > oc[(size_t)u] ? 1 : 0; next.push_back(u); }
+        }
+        frontier.swap(next);
+    }
+    for (int64_t v = 0; v < nv; ++v)
+        if (dec[(size_t)v] == 1) out[(size_t)v] = target;
+}
+
 }  // namespace
 }  // namespace mm
 
@@ -804,6 +1054,118 @@ int mm_find_points_by_cl_region(mm_engine* h, const mm_clpoint* cl, const uint32
     if ((rc = clean_up_points(e, dist.data(), (int64_t)idist.size(), betw.data(), (int64_t)(betw.size() / 3), 1.0, 0.6, mv))) return rc;
     for (size_t k = 0; k < idist.size(); ++k)
         if (mv[k]) label[idist[k]] = 4;
+    return MM_OK;
+}
+
+
+// ---- mesh labelling ---------------------------------------------------------------------------------------------
+
+// find_centerline_bounded_points (label_coronary.rs:201-235)
+int64_t mm_centerline_bounded_points(mm_engine* h, const mm_clpoint* cl, int64_t ncl, const double* pts, int64_t n,
+                                     double radius, uint8_t* inside)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (n < 0 || ncl < 0 || (n > 0 && (!pts || !inside)) || (ncl > 0 && !cl))
+        return set_error(MM_ERR_INVALID, "mm_centerline_bounded_points: bad arguments");
+    if (n == 0 || ncl == 0) return set_error(MM_ERR_INVALID, "find_centerline_bounded_points failed because `Centerline` is empty");   // :206-209
+    const std::vector<double> c = cl_xyz(cl, ncl);
+    std::vector<std::vector<uint32_t>> cnt;
+    if ((rc = radius_counts(e, {Set3{pts, n}, Set3{c.data(), ncl}}, {{0, 1}}, radius * radius, cnt))) return rc;   // :226
+    int64_t k = 0;
+    for (int64_t i = 0; i < n; ++i) { inside[i] = cnt[0][(size_t)i] > 0 ? 1 : 0; k += inside[i]; }
+    return k;
+}
+
+// find_faces_near_points (:242-289)
+int64_t mm_faces_near_points(mm_engine* h, const double* vertices, int64_t nv, const int64_t* faces, int64_t nf,
+                             const double* pts, int64_t n, double tol, uint8_t* face_selected)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (nv < 0 || nf < 0 || n < 0 || (nv > 0 && !vertices) || (nf > 0 && (!faces || !face_selected)) || (n > 0 && !pts))
+        return set_error(MM_ERR_INVALID, "mm_faces_near_points: bad arguments");
+    if (nf > 0) std::memset(face_selected, 0, (size_t)nf);
+    if (n == 0 || nv == 0 || nf == 0) return 0;                                                   // :248-250
+    for (int64_t k = 0; k < 3 * nf; ++k)
+        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_faces_near_points: face index out of range");
+    std::vector<std::vector<uint32_t>> cnt;
+    if ((rc = radius_counts(e, {Set3{vertices, nv}, Set3{pts, n}}, {{0, 1}}, tol * tol, cnt))) return rc;   // :259-273
+    int64_t k = 0;
+    for (int64_t f = 0; f < nf; ++f) {
+        const int64_t* v = faces + 3 * f;
+        face_selected[f] = (cnt[0][(size_t)v[0]] | cnt[0][(size_t)v[1]] | cnt[0][(size_t)v[2]]) ? 1 : 0;
+        k += face_selected[f];
+    }
+    return k;
+}
+
+// remove_occluded_points_ray_triangle_rust (:70-197)
+int64_t mm_occluded_points(mm_engine* h, const mm_clpoint* cl_coronary, int64_t ncc, const mm_clpoint* cl_aorta,
+                           int64_t nca, double range_mm, const double* pts, int64_t n, const double* tri, int64_t nf,
+                           double step_size_mm, uint8_t* removed, uint8_t* face_excluded)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (ncc < 0 || nca < 0 || n < 0 || nf < 0 || (ncc > 0 && !cl_coronary) || (nca > 0 && !cl_aorta) ||
+        (n > 0 && (!pts || !removed)) || (nf > 0 && !tri))
+        return set_error(MM_ERR_INVALID, "mm_occluded_points: bad arguments");
+    std::vector<uint8_t> rm, ex;
+    if ((rc = occluded_points(e, cl_coronary, ncc, cl_aorta, nca, range_mm, pts, n, tri, nf, step_size_mm, rm, ex))) return rc;
+    int64_t k = 0;
+    for (int64_t i = 0; i < n; ++i) { removed[i] = rm[(size_t)i]; k += rm[(size_t)i]; }
+    if (face_excluded && nf > 0) std::memcpy(face_excluded, ex.data(), (size_t)nf);
+    return k;
+}
+
+// find_aortic_points (:296-313)
+int64_t mm_find_aortic_points(const double* vertices, int64_t nv, const double* a, int64_t na, const double* b,
+                              int64_t nb, uint8_t* keep)
+{
+    if (nv < 0 || na < 0 || nb < 0 || (nv > 0 && (!vertices || !keep)) || (na > 0 && !a) || (nb > 0 && !b))
+        return set_error(MM_ERR_INVALID, "mm_find_aortic_points: bad arguments");
+    std::unordered_set<BitsKey, BitsHash> ex;
+    ex.reserve((size_t)(na + nb));
+    for (int64_t i = 0; i < na; ++i) ex.insert(bits_key(a + 3 * i));
+    for (int64_t i = 0; i < nb; ++i) ex.insert(bits_key(b + 3 * i));
+    int64_t k = 0;
+    for (int64_t i = 0; i < nv; ++i) { keep[i] = ex.count(bits_key(vertices + 3 * i)) ? 0 : 1; k += keep[i]; }
+    return k;
+}
+
+// final_reclassification (:337-640)
+int mm_final_reclassification(const double* vertices, int64_t nv, const int64_t* faces, int64_t nf, const double* rca,
+                              int64_t nr, const double* lca, int64_t nl, const double* rca_rm, int64_t nrr,
+                              const double* lca_rm, int64_t nlr, uint8_t* label)
+{
+    if (nv < 0 || nf < 0 || nr < 0 || nl < 0 || nrr < 0 || nlr < 0 || (nv > 0 && (!vertices || !label)) ||
+        (nf > 0 && !faces) || (nr > 0 && !rca) || (nl > 0 && !lca) || (nrr > 0 && !rca_rm) || (nlr > 0 && !lca_rm))
+        return set_error(MM_ERR_INVALID, "mm_final_reclassification: bad arguments");
+    for (int64_t k = 0; k < 3 * nf; ++k)
+        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_final_reclassification: face index out of range");
+    std::unordered_map<BitsKey, int64_t, BitsHash> idx;                                   // :353-358 the last index wins
+    idx.reserve((size_t)nv);
+    for (int64_t i = 0; i < nv; ++i) idx[bits_key(vertices + 3 * i)] = i;
+    std::vector<uint8_t> labels((size_t)nv, 0);
+    auto apply = [&](const double* p, int64_t m, uint8_t l) {                             // :360-383 rca, lca, rca_rm, lca_rm
+        for (int64_t i = 0; i < m; ++i) {
+            const auto it = idx.find(bits_key(p + 3 * i));
+            if (it != idx.end()) labels[(size_t)it->second] = l;
+        }
+    };
+    apply(rca, nr, 1); apply(lca, nl, 2); apply(rca_rm, nrr, 3); apply(lca_rm, nlr, 4);
+    Adjacency adj;
+    build_adjacency(faces, nf, nv, adj);
+    std::vector<uint8_t> out = labels;
+    reclassify_minority(adj, labels, out, 0, {1, 2});                                      // :396-398 Logic A
+    reclassify_minority(adj, labels, out, 1, {0});
+    reclassify_minority(adj, labels, out, 2, {0});
+    restore_removed(adj, labels, out, 3, 1);                                               // :412-413 Logic B
+    restore_removed(adj, labels, out, 4, 2);
+    if (nv > 0) std::memcpy(label, out.data(), (size_t)nv);
     return MM_OK;
 }
 

@@ -160,6 +160,15 @@ hipError_t launch_nn3_sums(const void* pairs, int n_pairs, const double* out, do
 int        nn_queries_per_block();
 int        nn_chunk_points();
 int        nn_span_chunks();
+// ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
+// xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = ray_partial_bytes() x n_rays x
+// ceil(n_faces / ray_chunk_faces()) bytes of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits
+// at least 3 faces, else -1
+hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int n_faces, void* part, int32_t* closest,
+                          hipStream_t s);
+int        ray_chunk_faces();
+int        ray_block_rays();
+size_t     ray_partial_bytes();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers

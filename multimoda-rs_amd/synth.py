@@ -147,3 +147,55 @@ def synthetic_tube_case(n_points: int = 6000, n_reference: int = 5000, true_scal
 
     return dict(centerline=cl, points=tube(n_points, 1.6), reference=tube(n_reference, 1.6 + true_scaling_mm),
                 truth=true_scaling_mm)
+
+
+def _tube(centre: np.ndarray, n1: np.ndarray, n2: np.ndarray, radius: float, n_around: int, phase: float = 0.0):
+    """Rings of n_around vertices around the polyline `centre` (frames n1, n2 per point; the first vertex `phase`
+    steps past n1) and the two triangles of every quad between consecutive rings."""
+    a = 2.0 * np.pi * (np.arange(n_around) + phase) / n_around
+    v = (centre[:, None, :] + radius * (np.cos(a)[None, :, None] * n1[:, None, :] +
+                                         np.sin(a)[None, :, None] * n2[:, None, :])).reshape(-1, 3)
+    m = centre.shape[0]
+    i, j = np.meshgrid(np.arange(m - 1), np.arange(n_around), indexing="ij")
+    p00, p01 = i * n_around + j, i * n_around + (j + 1) % n_around
+    p10, p11 = p00 + n_around, p01 + n_around
+    f = np.stack([np.stack([p00, p10, p01], -1), np.stack([p01, p10, p11], -1)], axis=2).reshape(-1, 3)
+    return v, f
+
+
+def synthetic_takeoff_mesh(n_theta: int = 96, n_z: int = 60, aorta_radius: float = 15.0, length: float = 60.0,
+                           coronary_radius: float = 1.5, coronary_len: float = 40.0, n_around: int = 16,
+                           acute_takeoff: bool = True):
+    """A CCTA-like surface for the labelling (generator is ours): an open aortic cylinder about the z axis
+    (n_theta x (n_z + 1) vertices, half an angular step off the x axis) and two coronary tubes.  The RCA starts at
+    the wall at mid height; with ``acute_takeoff`` it winds up along the outside of the wall, its tube 0.1 mm from
+    it (the two walls fused, as in an intramural course); otherwise it leaves radially.  The LCA leaves radially on the opposite side.  Centerlines
+    are sampled every 0.5 mm (aorta every 1 mm).  Returns (vertices, faces, cl_aorta, cl_rca, cl_lca, n_aorta_faces)
+    with the aortic faces first."""
+    R = float(aorta_radius)
+    zc = np.linspace(0.0, length, n_z + 1)
+    ring = np.zeros((n_z + 1, 3))
+    ring[:, 2] = zc
+    ex = np.tile([1.0, 0.0, 0.0], (n_z + 1, 1))
+    ey = np.tile([0.0, 1.0, 0.0], (n_z + 1, 1))
+    va, fa = _tube(ring, ex, ey, R, n_theta, phase=0.5)
+    cl_aorta = np.stack([np.zeros(int(length) + 1), np.zeros(int(length) + 1), np.arange(int(length) + 1.0)], axis=1)
+    s = np.arange(0.0, coronary_len + 1e-9, 0.5)
+    if acute_takeoff:
+        rr = R + coronary_radius + 0.1
+        phi = s / rr
+        cl_rca = np.stack([rr * np.cos(phi), rr * np.sin(phi), length / 2 + 0.3 * s], axis=1)
+        radial = np.stack([np.cos(phi), np.sin(phi), np.zeros_like(phi)], axis=1)
+        tan = np.stack([-np.sin(phi), np.cos(phi), np.full_like(phi, 0.3)], axis=1)
+        tan /= np.linalg.norm(tan, axis=1, keepdims=True)
+        n1, n2 = radial, np.cross(tan, radial)
+    else:
+        cl_rca = np.stack([R + 0.5 + s, np.zeros_like(s), np.full_like(s, length / 2)], axis=1)
+        n1, n2 = np.tile([0.0, 1.0, 0.0], (s.size, 1)), np.tile([0.0, 0.0, 1.0], (s.size, 1))
+    vr, fr = _tube(cl_rca, n1, n2, coronary_radius, n_around)
+    cl_lca = np.stack([-(R + 0.5 + s), np.zeros_like(s), np.full_like(s, length / 2 - 10.0)], axis=1)
+    vl, fl = _tube(cl_lca, np.tile([0.0, 1.0, 0.0], (s.size, 1)), np.tile([0.0, 0.0, 1.0], (s.size, 1)),
+                   coronary_radius, n_around)
+    v = np.concatenate([va, vr, vl])
+    f = np.concatenate([fa, fr + va.shape[0], fl + va.shape[0] + vr.shape[0]]).astype(np.int64)
+    return v, f, cl_aorta, cl_rca, cl_lca, fa.shape[0]
