@@ -17,7 +17,11 @@
  *   src/ccta/adjust_mesh/label_coronary.rs:29-197  ray_triangle_intersection, remove_occluded_points_ray_triangle_rust
  *   src/ccta/adjust_mesh/label_coronary.rs:201-289 find_centerline_bounded_points, find_faces_near_points
  *   src/ccta/adjust_mesh/label_coronary.rs:296-640 find_aortic_points, final_reclassification
- * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481
+ *   src/ccta/discretizing/projecting.rs:13-200       walk_centerline_slices, voronoi_partition, project_to_plane
+ *   src/ccta/discretizing/resampling.rs:11-229       create_uniform_contours, resample_spline
+ *   src/ccta/discretizing.rs:13-22, discretizing/vessel_tree.rs:21-83  discretize_vessel_rs, from_results_dict
+ * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481, 724-920 (discretize_vessel,
+ * discretize_vessel_tree)
  * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
  * find_aortic_points, final_reclassification, adjust_diameter_centerline_morphing_simple,
  * find_proximal_distal_scaling, find_aortic_scaling, find_aortic_wall_scaling), wrapped by
@@ -27,7 +31,9 @@
  * per-point minima are summed on the host in index order (the reference's rayon sum has no fixed
  * order; the sequential one is among those it can produce).  The labelling's ray-triangle tests run
  * on the device in exact f64 (mm_ray_kernels.hip); its radius queries use the same exact radius
- * counts as mm_clean_outlier_points; the bookkeeping on adjacency graphs is host C++.
+ * counts as mm_clean_outlier_points; the bookkeeping on adjacency graphs is host C++.  The vessel discretisation's
+ * nearest-anchor assignment and plane projection run on the device in exact f64 (mm_slice_kernels.hip); its anchors
+ * and spline resampling are host f64.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -123,6 +129,37 @@ int     mm_final_reclassification(const double* vertices_xyz, int64_t nv, const 
                                   const double* rca_xyz, int64_t nr, const double* lca_xyz, int64_t nl,
                                   const double* rca_removed_xyz, int64_t nrr, const double* lca_removed_xyz, int64_t nlr,
                                   uint8_t* label);
+
+/* ---- vessel discretisation (src/ccta/discretizing).  Contours: n_points xyz triples each. ------------------------- */
+
+#define MM_SLICE_MAX_ANCHORS     (1 << 22)   /* anchors (slices) of one branch; more is MM_ERR_INVALID   */
+#define MM_DISCRETIZE_MAX_POINTS (1 << 20)   /* n_points of one resampled contour                        */
+
+/* The number of slice anchors of branch branch_id walked every step_size (walk_centerline_slices, projecting.rs:13-60):
+ * the upper bound on its contours.  0 for an absent branch or a NaN length; a step_size <= 0 or non-finite (the
+ * reference never ends) or more than MM_SLICE_MAX_ANCHORS anchors is MM_ERR_INVALID. */
+int64_t mm_slice_anchor_count(const mm_clpoint* cl, int64_t ncl, uint32_t branch_id, double step_size);
+/* voronoi_partition + project_to_plane (:62-118) on the device, n_jobs at once.  Job j: points pt_off[j] ..
+ * pt_off[j+1] (xyz triples), anchors anchor_off[j] .. anchor_off[j+1] (6 doubles each: position, unit normal).
+ * anchor_idx[i] = the job-local index of point i's nearest anchor (ties: the lowest; a NaN distance to anchor 0 pins the
+ * point there, a NaN distance to a later anchor never wins), proj_xyz[i] = the point projected onto that anchor's
+ * plane.  A job without anchors gives -1 and the point itself. */
+int     mm_nearest_anchor_project(mm_engine* e, int n_jobs, const int64_t* pt_off, const double* pts_xyz,
+                                  const int64_t* anchor_off, const double* anchors, int32_t* anchor_idx, double* proj_xyz);
+/* resample_spline (resampling.rs:69-90), host: the n points (in bucket order) sorted by angle about centroid, a closed
+ * Catmull-Rom spline through them, n_points uniform in arc length into out.  Returns 1, or 0 where the reference
+ * returns None (fewer than 3 points, no local basis, a spline shorter than 1e-10); a NaN angle (a panic in the
+ * reference) or n_points outside [2, MM_DISCRETIZE_MAX_POINTS] is MM_ERR_INVALID. */
+int     mm_resample_closed_contour(const double* pts, int64_t n, const double centroid[3], int64_t n_points, double* out);
+/* discretize_vessel_rs (discretizing.rs:13-22) for n_jobs (centerline, branch, points) jobs in one device pass.  Job j:
+ * centerline points cl_off[j] .. cl_off[j+1] of cl, branch branch_id[j], points pt_off[j] .. pt_off[j+1] (xyz).  It
+ * writes n_contours[j] contours at slots out_off[j] .. : ids (the anchor index, also the original frame), centroids_xyz
+ * (the anchor position) and n_points xyz triples per contour in out_xyz.  out_off[j+1] - out_off[j] must be at least
+ * mm_slice_anchor_count of the job.  Same errors as mm_slice_anchor_count and mm_resample_closed_contour. */
+int     mm_discretize_vessel_batch(mm_engine* e, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off,
+                                   const uint32_t* branch_id, const double* pts_xyz, const int64_t* pt_off,
+                                   double step_size, int64_t n_points, const int64_t* out_off, int64_t* n_contours,
+                                   int32_t* ids, double* centroids_xyz, double* out_xyz);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,8 @@ from .centerline import (Centerline, align_combined, align_manual, align_three_p
                          preprocess_centerline)
 from . import centerline
 from . import ccta
-from .ccta import (adjust_diameter_centerline_morphing_simple, clean_outlier_points, final_reclassification,
+from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_simple, clean_outlier_points,
+                   discretize_vessel, discretize_vessel_tree, final_reclassification,
                    find_aorta_scaling, find_aortic_points, find_aortic_scaling, find_aortic_wall_scaling,
                    find_centerline_bounded_points_simple, find_distal_and_proximal_scaling, find_faces_near_points,
                    find_points_by_cl_region, find_proximal_distal_scaling, label_geometry,
@@ -52,6 +53,7 @@ __all__ = [
     "find_points_by_cl_region", "clean_outlier_points",
     "find_centerline_bounded_points_simple", "find_faces_near_points", "remove_occluded_points_ray_triangle",
     "find_aortic_points", "final_reclassification", "label_geometry",
+    "discretize_vessel", "discretize_vessel_tree", "DiscretizedVesselTree",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",
 ]

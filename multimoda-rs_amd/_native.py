@@ -101,6 +101,7 @@ EXPORTS_CCTA = [
     "mm_clean_outlier_points", "mm_find_points_by_cl_region",
     "mm_centerline_bounded_points", "mm_faces_near_points", "mm_occluded_points", "mm_find_aortic_points",
     "mm_final_reclassification",
+    "mm_slice_anchor_count", "mm_nearest_anchor_project", "mm_resample_closed_contour", "mm_discretize_vessel_batch",
 ]
 
 
@@ -426,6 +427,14 @@ def lib():
     L.mm_find_aortic_points.argtypes = [P, I64, P, I64, P, I64, P]
     L.mm_final_reclassification.restype = I
     L.mm_final_reclassification.argtypes = [P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, P]
+    L.mm_slice_anchor_count.restype = I64
+    L.mm_slice_anchor_count.argtypes = [P, I64, C.c_uint32, D]
+    L.mm_nearest_anchor_project.restype = I
+    L.mm_nearest_anchor_project.argtypes = [P, I, P, P, P, P, P, P]
+    L.mm_resample_closed_contour.restype = I
+    L.mm_resample_closed_contour.argtypes = [P, I64, P, I64, P]
+    L.mm_discretize_vessel_batch.restype = I
+    L.mm_discretize_vessel_batch.argtypes = [P, I, P, P, P, P, P, D, I64, P, P, P, P, P]
     _lib = L
     return L
 

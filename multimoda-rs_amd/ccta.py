@@ -9,12 +9,15 @@ implementation src/ccta/adjust_mesh/scale_coronary.rs:8-261) and the wrapper
 
 Same argument names, order and meaning; points are ``(N, 3)`` arrays (or lists of tuples).  Each
 search scores its 41 scalings in one GPU batch (exact f64 nearest-neighbour minima,
-csrc/mm_nn_kernels.hip); there is no CPU fallback.
+csrc/mm_nn_kernels.hip); there is no CPU fallback.  The vessel discretisation mirrors ``discretize_vessel`` and
+``discretize_vessel_tree`` (src/ccta/binding/ccta_py.rs:724-920, multimodars/_processing.py:1507,
+multimodars/ccta/discretization_map.py:104-205; implementation src/ccta/discretizing).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+from dataclasses import dataclass, field
 from typing import Optional, Tuple
 
 import numpy as np
@@ -363,3 +366,215 @@ def label_geometry(mesh, centerline_aorta: Centerline, centerline_rca: Centerlin
     aorta, rca, lca, rca_rm, lca_rm = final_reclassification(v, f, rca_pts, lca_pts, rca_removed, lca_removed)
     return {"mesh": mesh, "aorta_points": aorta, "rca_points": rca, "lca_points": lca, "rca_removed_points": rca_rm,
             "lca_removed_points": lca_rm}
+
+
+# ---- vessel discretisation (src/ccta/discretizing) ------------------------------------------------------------------
+def _discretize_jobs(jobs, step_size: float, n_points: int, engine: Optional[N.Engine]):
+    """discretize_vessel_rs for every (centerline, points, branch_id) job in one device pass -> one contour list per
+    job."""
+    from .frames import Contour
+    L = N.lib()
+    cls = [c.points for c, _, _ in jobs]
+    pts = [_p3(p) for _, p, _ in jobs]
+    caps = []
+    for c, _, b in jobs:
+        k = L.mm_slice_anchor_count(N._ptr(c.points), len(c), int(b), float(step_size))
+        if k < 0:
+            N.check(int(k), "discretize_vessel")
+        caps.append(int(k))
+    nj = len(jobs)
+    cl_off = np.concatenate([[0], np.cumsum([len(c) for c in cls])]).astype(np.int64)
+    pt_off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    cl_all, xyz = np.ascontiguousarray(np.concatenate(cls)), np.ascontiguousarray(np.concatenate(pts))
+    bid = np.array([int(b) for _, _, b in jobs], dtype=np.uint32)
+    total = int(out_off[-1])
+    n_contours = np.zeros(nj, dtype=np.int64)
+    ids = np.zeros(total, dtype=np.int32)
+    cen = np.zeros((total, 3))
+    out = np.zeros((total, max(int(n_points), 0), 3))
+    N.check(L.mm_discretize_vessel_batch(_engine(engine).handle, nj, N._ptr(cl_all), N._ptr(cl_off), N._ptr(bid),
+                                         N._ptr(xyz), N._ptr(pt_off), float(step_size), int(n_points), N._ptr(out_off),
+                                         N._ptr(n_contours), N._ptr(ids), N._ptr(cen), N._ptr(out)), "discretize_vessel")
+    res = []
+    for j in range(nj):
+        o = int(out_off[j])
+        res.append([Contour(int(ids[o + k]), int(ids[o + k]), out[o + k].copy(), tuple(float(v) for v in cen[o + k]),
+                            kind="lumen") for k in range(int(n_contours[j]))])
+    return res
+
+
+def discretize_vessel(centerline: Centerline, points, branch_id: int = 0, step_size: float = 0.5, n_points: int = 200,
+                      engine: Optional[N.Engine] = None):
+    """ccta_py.rs:724-741 -> discretize_vessel_rs (src/ccta/discretizing.rs:13-22): cut branch ``branch_id`` of
+    ``centerline`` every ``step_size`` (arc length), give every point to its nearest slice anchor, project it onto that
+    anchor's plane, drop empty slices and the partial ones at both ends, and resample each remaining slice to
+    ``n_points`` points on a closed Catmull-Rom spline.  Returns ``frames.Contour`` objects (kind "lumen"); a
+    contour's ``id`` and ``original_frame`` are its slice index, its centroid the anchor.  The nearest-anchor pass runs
+    on the device in exact f64 (csrc/mm_slice_kernels.hip).  A ``step_size`` <= 0 or non-finite, or ``n_points`` < 2,
+    raises RuntimeError."""
+    return _discretize_jobs([(centerline, points, branch_id)], step_size, n_points, engine)[0]
+
+
+@dataclass
+class ReferenceTriplet:
+    """discretized_tree.rs:4-9"""
+    main_ref: Tuple[float, float, float]
+    counter_clock_ref: Tuple[float, float, float]
+    clock_ref: Tuple[float, float, float]
+
+
+def _t3(v) -> Tuple[float, float, float]:
+    return (float(v[0]), float(v[1]), float(v[2]))
+
+
+def _norm3(v) -> float:
+    return math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+
+
+def _sub3(a, b):
+    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+
+def _try_normalize(v):
+    """nalgebra try_normalize(1e-12), falling back to +z"""
+    n = _norm3(v)
+    return (v[0] / n, v[1] / n, v[2] / n) if n > 1e-12 else (0.0, 0.0, 1.0)
+
+
+def _first_min(vals) -> int:
+    k, best = 0, None
+    for i, x in enumerate(vals):
+        if best is None or x < best:
+            k, best = i, x
+    return k
+
+
+def _assign_cc_clock(p1, p2, centroid, normal, up):
+    """discretized_tree.rs:295-313: (counter_clock, clock) seen proximal -> distal"""
+    dn = (up[0] * normal[0] + up[1] * normal[1]) + up[2] * normal[2]
+    w = (up[0] - normal[0] * dn, up[1] - normal[1] * dn, up[2] - normal[2] * dn)
+    n = _norm3(w)
+    u = (w[0] / n, w[1] / n, w[2] / n) if n > 1e-12 else (0.0, 0.0, 0.0)
+    right = (u[1] * normal[2] - u[2] * normal[1], u[2] * normal[0] - u[0] * normal[2], u[0] * normal[1] - u[1] * normal[0])
+    d = _sub3(p1, centroid)
+    return (p1, p2) if (d[0] * right[0] + d[1] * right[1]) + d[2] * right[2] < 0.0 else (p2, p1)
+
+
+def _vessel_references(ao, main, branches):
+    """discretized_tree.rs:148-293: the ostium triplet, then one per side branch, sorted by main-vessel contour index"""
+    from .api import _find_closest_opposite_3d, _find_farthest_points
+    mc = [_t3(c.centroid) for c in main]
+    up = _try_normalize(_sub3(mc[0], ao))
+    tagged = []
+    first = main[0].points
+    if first.shape[0] > 2:
+        normal = _try_normalize(_sub3(mc[1], mc[0])) if len(main) > 1 else _try_normalize(_sub3(mc[0], ao))
+        (i, j), _ = _find_closest_opposite_3d(first)
+        pa, pb = _t3(first[i]), _t3(first[j])
+        main_ref = pa if _norm3(_sub3(pa, ao)) <= _norm3(_sub3(pb, ao)) else pb
+        (i, j), _ = _find_farthest_points(first)
+        cc, cl = _assign_cc_clock(_t3(first[i]), _t3(first[j]), mc[0], normal, up)
+        tagged.append((0, ReferenceTriplet(main_ref, cc, cl)))
+    for br in branches:
+        if not br:
+            continue
+        side = _t3(br[0].centroid)
+        k = _first_min([_norm3(_sub3(m, side)) for m in mc])
+        bc = mc[k]
+        if k + 1 < len(main):
+            normal = _try_normalize(_sub3(mc[k + 1], bc))
+        elif k > 0:
+            normal = _try_normalize(_sub3(bc, mc[k - 1]))
+        else:
+            normal = _try_normalize(_sub3(bc, ao))
+        pts = main[k].points
+        n = pts.shape[0]
+        if n < 4:
+            continue
+        ci = _first_min([_norm3(_sub3(_t3(p), side)) for p in pts])
+        q = n // 4
+        cc, cl = _assign_cc_clock(_t3(pts[(ci + q) % n]), _t3(pts[(ci + n - q) % n]), bc, normal, up)
+        tagged.append((k, ReferenceTriplet(side, cc, cl)))
+    tagged.sort(key=lambda x: x[0])
+    return [r for _, r in tagged]
+
+
+@dataclass
+class DiscretizedVesselTree:
+    """types/native/discretized_tree.rs:11-32: the discretised aorta, main vessels and side branches (branch i + 1 at
+    index i) with the orientation references of calculate_ref_pts."""
+    discretized_aorta: list
+    discretized_rca_main: list
+    discretized_lca_main: list
+    spacing: float
+    rca_branches: list = field(default_factory=list)
+    lca_branches: list = field(default_factory=list)
+    rca_references: list = field(default_factory=list)
+    lca_references: list = field(default_factory=list)
+    ao_rca: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    ao_lca: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    pts_cusp_rcc: Optional[list] = None
+    pts_cusp_lcc: Optional[list] = None
+    pts_cusp_acc: Optional[list] = None
+    index_stj_slice: Optional[int] = None
+    index_aa: Optional[int] = None
+
+    def calculate_ref_pts(self) -> "DiscretizedVesselTree":
+        """discretized_tree.rs:95-145: ao_rca / ao_lca = the centroid of the aorta slice nearest to the first contour
+        of the main vessel (the first of equal distances), and the reference triplets of each main vessel.  Updates
+        the tree in place and returns it."""
+        if not self.discretized_aorta:
+            return self
+        for main, branches, side in ((self.discretized_rca_main, self.rca_branches, "rca"),
+                                     (self.discretized_lca_main, self.lca_branches, "lca")):
+            if not main:
+                continue
+            c0 = _t3(main[0].centroid)
+            k = _first_min([_norm3(_sub3(_t3(a.centroid), c0)) for a in self.discretized_aorta])
+            ao = _t3(self.discretized_aorta[k].centroid)
+            setattr(self, "ao_" + side, ao)
+            setattr(self, side + "_references", _vessel_references(ao, main, branches))
+        return self
+
+
+def discretize_vessel_tree_raw(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Centerline, points_ao, points_rca_main,
+                               points_lca_main, side_branches_rca, side_branches_lca, branch_id_rca: int = 0,
+                               branch_id_lca: int = 0, step_size: float = 1.0, n_points: int = 100,
+                               calculate_ref_pts: bool = True, engine: Optional[N.Engine] = None) -> DiscretizedVesselTree:
+    """ccta_py.rs:874-920 -> DiscretizedVesselTree::from_results_dict (vessel_tree.rs:21-83): the aorta (branch 0),
+    both main vessels and every side branch (``side_branches_rca[i]`` on branch i + 1 of ``rca_cl``, likewise LCA),
+    all in one device pass; then calculate_ref_pts unless it is switched off."""
+    jobs = [(ao_cl, points_ao, 0), (rca_cl, points_rca_main, branch_id_rca), (lca_cl, points_lca_main, branch_id_lca)]
+    jobs += [(rca_cl, p, i + 1) for i, p in enumerate(side_branches_rca)]
+    jobs += [(lca_cl, p, i + 1) for i, p in enumerate(side_branches_lca)]
+    res = _discretize_jobs(jobs, step_size, n_points, engine)
+    nr = len(side_branches_rca)
+    tree = DiscretizedVesselTree(res[0], res[1], res[2], float(step_size), res[3:3 + nr], res[3 + nr:])
+    return tree.calculate_ref_pts() if calculate_ref_pts else tree
+
+
+def _extract_side_branches(results_dict: dict, prefix: str) -> list:
+    """discretization_map.py:104-114"""
+    out, i = [], 1
+    while f"{prefix}_side_{i}" in results_dict:
+        out.append(results_dict[f"{prefix}_side_{i}"])
+        i += 1
+    return out
+
+
+def discretize_vessel_tree(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Centerline, results_dict: dict,
+                           branch_id_rca: int = 0, branch_id_lca: int = 0, step_size: float = 1.0, n_points: int = 100,
+                           b_spline: bool = False, bspline_smoothing: float = 100.0, bspline_degree: int = 3,
+                           control_plot: bool = False, engine: Optional[N.Engine] = None) -> DiscretizedVesselTree:
+    """multimodars/ccta/discretization_map.py:117-205: discretise the aorta (``aorta_points`` + ``rca_removed_points``),
+    the main vessels (``rca_points_main`` / ``lca_points_main``) and the side branches (``rca_points_side_1``, ...) of
+    a labelled results dict, with reference points.  B-spline contours are not implemented (``b_spline=True`` raises
+    NotImplementedError); ``control_plot`` is accepted and ignored."""
+    if b_spline:
+        raise NotImplementedError("discretize_vessel_tree: b_spline contours are not implemented")
+    points_ao = np.concatenate([_p3(results_dict["aorta_points"]), _p3(results_dict["rca_removed_points"])])
+    return discretize_vessel_tree_raw(ao_cl, rca_cl, lca_cl, points_ao, results_dict["rca_points_main"],
+                                      results_dict["lca_points_main"], _extract_side_branches(results_dict, "rca_points"),
+                                      _extract_side_branches(results_dict, "lca_points"), branch_id_rca, branch_id_lca,
+                                      step_size, n_points, calculate_ref_pts=True, engine=engine)

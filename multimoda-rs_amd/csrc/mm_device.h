@@ -169,6 +169,12 @@ hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int 
 int        ray_chunk_faces();
 int        ray_block_rays();
 size_t     ray_partial_bytes();
+// nearest slice anchor and plane projection of the vessel discretisation (mm_slice_kernels.hip): jobs = SliceJob records
+// (point / anchor ranges), work = SliceWork records (job, first point) of slice_block_points() points each; pts = xyz
+// triples, anc = 6 doubles per anchor (position, unit normal); idx / proj at the point's position
+hipError_t launch_slice_nearest(const void* jobs, const void* work, int n_work, const double* pts, const double* anc,
+                                int32_t* idx, double* proj, hipStream_t s);
+int        slice_block_points();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers
