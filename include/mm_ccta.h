@@ -20,6 +20,7 @@
  *   src/ccta/discretizing/projecting.rs:13-200       walk_centerline_slices, voronoi_partition, project_to_plane
  *   src/ccta/discretizing/resampling.rs:11-229       create_uniform_contours, resample_spline
  *   src/ccta/discretizing.rs:13-22, discretizing/vessel_tree.rs:21-83  discretize_vessel_rs, from_results_dict
+ *   src/ccta/binding/ccta_py.rs:541-580, label_coronary.rs:428-455  keep_largest_connected_component
  * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481, 724-920 (discretize_vessel,
  * discretize_vessel_tree)
  * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
@@ -33,7 +34,8 @@
  * on the device in exact f64 (mm_ray_kernels.hip); its radius queries use the same exact radius
  * counts as mm_clean_outlier_points; the bookkeeping on adjacency graphs is host C++.  The vessel discretisation's
  * nearest-anchor assignment and plane projection run on the device in exact f64 (mm_slice_kernels.hip); its anchors
- * and spline resampling are host f64.
+ * and spline resampling are host f64.  The mesh morphing's nearest-centerline search and radial move run on the device
+ * in exact f64 (mm_morph_kernels.hip).
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -160,6 +162,29 @@ int     mm_discretize_vessel_batch(mm_engine* e, int n_jobs, const mm_clpoint* c
                                    const uint32_t* branch_id, const double* pts_xyz, const int64_t* pt_off,
                                    double step_size, int64_t n_points, const int64_t* out_off, int64_t* n_contours,
                                    int32_t* ids, double* centroids_xyz, double* out_xyz);
+
+/* ---- mesh morphing (src/ccta/adjust_mesh/scale_coronary.rs:218-260, src/ccta/binding/ccta_py.rs:541-580) ---------- */
+
+/* centerline_based_diameter_morphing (scale_coronary.rs:218-260) on the device, n_jobs at once.  Job j: centerline
+ * points cl_off[j] .. cl_off[j+1] of cl, points pt_off[j] .. pt_off[j+1] (xyz), adjustment adj[j].  nearest[i] = the
+ * job-local index of point i's nearest centerline point (best = DBL_MAX, index 0; a point replaces the best iff its
+ * squared distance is below it: ties keep the lowest index, NaN distances never win); out_xyz[i] = p + (v / |v|) * adj
+ * with v = p - that point, or p itself where |v| is 0 or NaN.  A job with points and no centerline point is
+ * MM_ERR_INVALID (a panic in the reference); a job without points is fine. */
+int     mm_centerline_morph_batch(mm_engine* e, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off,
+                                  const double* pts_xyz, const int64_t* pt_off, const double* adj, double* out_xyz,
+                                  int32_t* nearest);
+/* index[i] = the LAST key with the bit pattern of query i (bits_key, the reference's coord_to_idx maps), or -1.
+ * Returns the number of queries matched. */
+int64_t mm_match_points(const double* keys_xyz, int64_t nk, const double* queries_xyz, int64_t nq, int64_t* index);
+/* keep_largest_connected_component (ccta_py.rs:541-580), host.  The points are matched to vertices by bit pattern (the
+ * last of duplicated vertices wins); keep receives the vertex indices of the largest connected component of the face
+ * adjacency restricted to the matched vertices, ascending (capacity n).  Of equally large ones the component holding
+ * the smallest vertex index is kept (the reference picks one in hash order).  Returns their number, or 0 where the
+ * reference returns the points unchanged: fewer than 2 points, or none matches a vertex.  Face indices >= nv are
+ * never in the subset (as in the reference); a negative one is MM_ERR_INVALID. */
+int64_t mm_keep_largest_component(const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                                  const double* pts_xyz, int64_t n, int64_t* keep);
 
 #ifdef __cplusplus
 }

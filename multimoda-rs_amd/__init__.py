@@ -27,8 +27,9 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    discretize_vessel, discretize_vessel_tree, final_reclassification,
                    find_aorta_scaling, find_aortic_points, find_aortic_scaling, find_aortic_wall_scaling,
                    find_centerline_bounded_points_simple, find_distal_and_proximal_scaling, find_faces_near_points,
-                   find_points_by_cl_region, find_proximal_distal_scaling, label_geometry,
-                   remove_occluded_points_ray_triangle)
+                   find_points_by_cl_region, find_proximal_distal_scaling, keep_largest_connected_component,
+                   label_anomalous_region, label_geometry, remove_occluded_points_ray_triangle, scale,
+                   scale_region_centerline_morphing, sync_results_to_mesh)
 from .convert import numpy_to_geometry, to_array
 from .export import to_obj
 from . import export
@@ -54,6 +55,8 @@ __all__ = [
     "find_centerline_bounded_points_simple", "find_faces_near_points", "remove_occluded_points_ray_triangle",
     "find_aortic_points", "final_reclassification", "label_geometry",
     "discretize_vessel", "discretize_vessel_tree", "DiscretizedVesselTree",
+    "keep_largest_connected_component", "label_anomalous_region", "scale_region_centerline_morphing",
+    "sync_results_to_mesh", "scale",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",
 ]

@@ -102,6 +102,7 @@ EXPORTS_CCTA = [
     "mm_centerline_bounded_points", "mm_faces_near_points", "mm_occluded_points", "mm_find_aortic_points",
     "mm_final_reclassification",
     "mm_slice_anchor_count", "mm_nearest_anchor_project", "mm_resample_closed_contour", "mm_discretize_vessel_batch",
+    "mm_centerline_morph_batch", "mm_match_points", "mm_keep_largest_component",
 ]
 
 
@@ -435,6 +436,12 @@ def lib():
     L.mm_resample_closed_contour.argtypes = [P, I64, P, I64, P]
     L.mm_discretize_vessel_batch.restype = I
     L.mm_discretize_vessel_batch.argtypes = [P, I, P, P, P, P, P, D, I64, P, P, P, P, P]
+    L.mm_centerline_morph_batch.restype = I
+    L.mm_centerline_morph_batch.argtypes = [P, I, P, P, P, P, P, P, P]
+    L.mm_match_points.restype = I64
+    L.mm_match_points.argtypes = [P, I64, P, I64, P]
+    L.mm_keep_largest_component.restype = I64
+    L.mm_keep_largest_component.argtypes = [P, I64, P, I64, P, I64, P]
     _lib = L
     return L
 

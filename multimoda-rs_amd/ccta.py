@@ -11,10 +11,14 @@ Same argument names, order and meaning; points are ``(N, 3)`` arrays (or lists o
 search scores its 41 scalings in one GPU batch (exact f64 nearest-neighbour minima,
 csrc/mm_nn_kernels.hip); there is no CPU fallback.  The vessel discretisation mirrors ``discretize_vessel`` and
 ``discretize_vessel_tree`` (src/ccta/binding/ccta_py.rs:724-920, multimodars/_processing.py:1507,
-multimodars/ccta/discretization_map.py:104-205; implementation src/ccta/discretizing).
+multimodars/ccta/discretization_map.py:104-205; implementation src/ccta/discretizing).  The mesh morphing mirrors
+``label_anomalous_region`` (multimodars/ccta/labeling.py:283-389), ``scale_region_centerline_morphing`` /
+``sync_results_to_mesh`` (multimodars/ccta/scaling.py:16-80, 301-351) and ``scale`` (multimodars/ccta/__init__.py:171-258);
+its nearest-centerline search runs on the device (csrc/mm_morph_kernels.hip).
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 from dataclasses import dataclass, field
@@ -221,6 +225,14 @@ def find_points_by_cl_region(centerline: Centerline, frames, points, engine: Opt
 
 # ---- mesh labelling (src/ccta/adjust_mesh/label_coronary.rs, multimodars/ccta/labeling.py) -----------------------
 
+def _mesh_parts(mesh):
+    """(vertices, faces) of a ``(vertices, faces)`` pair or of any object with ``.vertices`` / ``.faces``."""
+    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
+        return mesh.vertices, mesh.faces
+    vertices, faces = mesh
+    return vertices, faces
+
+
 def _faces3(faces) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(faces, dtype=np.int64).reshape(-1, 3))
 
@@ -341,10 +353,7 @@ def label_geometry(mesh, centerline_aorta: Centerline, centerline_rca: Centerlin
     read and nothing is plotted (``control_plot`` is accepted and ignored).  Returns the reference's dict: ``"mesh"``
     (what was passed), ``"aorta_points"``, ``"rca_points"``, ``"lca_points"``, ``"rca_removed_points"``,
     ``"lca_removed_points"`` as ``(n, 3)`` arrays."""
-    if hasattr(mesh, "vertices") and hasattr(mesh, "faces"):
-        vertices, faces = mesh.vertices, mesh.faces
-    else:
-        vertices, faces = mesh
+    vertices, faces = _mesh_parts(mesh)
     v, f = _p3(vertices), _faces3(faces)
     eng = _engine(engine)
     rca_found = find_centerline_bounded_points_simple(centerline_rca, v, bounding_sphere_radius_mm_rca, engine=eng)
@@ -578,3 +587,140 @@ def discretize_vessel_tree(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Center
                                       results_dict["lca_points_main"], _extract_side_branches(results_dict, "rca_points"),
                                       _extract_side_branches(results_dict, "lca_points"), branch_id_rca, branch_id_lca,
                                       step_size, n_points, calculate_ref_pts=True, engine=engine)
+
+
+# ---- mesh morphing (src/ccta/adjust_mesh/scale_coronary.rs:218-260, multimodars/ccta/{labeling,scaling,__init__}.py) --
+
+def _match(keys, queries) -> np.ndarray:
+    """For every query row the index of the last key row equal to it by value, -1 if none: the reference's
+    ``tuple(v) in set(...)`` / ``{tuple(v): i}`` lookups.  As with Python floats, -0.0 equals 0.0 (folded to +0.0 in
+    both copies before the bit-pattern match of mm_match_points) and a row with a NaN equals nothing."""
+    k, q = _p3(keys).copy(), _p3(queries).copy()
+    k[k == 0.0] = 0.0
+    q[q == 0.0] = 0.0
+    idx = np.empty(q.shape[0], dtype=np.int64)
+    r = N.lib().mm_match_points(N._ptr(k), k.shape[0], N._ptr(q), q.shape[0], N._ptr(idx))
+    if r < 0:
+        N.check(int(r), "match_points")
+    idx[np.isnan(q).any(axis=1)] = -1
+    return idx
+
+
+def centerline_morph_batch(jobs, engine: Optional[N.Engine] = None):
+    """centerline_based_diameter_morphing (scale_coronary.rs:218-260) for every (centerline, points, adjustment) job in
+    one device pass (csrc/mm_morph_kernels.hip) -> [(moved (n, 3), nearest centerline index (n,) int32)] per job.  A job
+    with points and an empty centerline raises RuntimeError (the reference panics)."""
+    pts = [_p3(p) for _, p, _ in jobs]
+    cls = [c.points for c, _, _ in jobs]
+    pt_off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pts])]).astype(np.int64)
+    cl_off = np.concatenate([[0], np.cumsum([len(c) for c in cls])]).astype(np.int64)
+    xyz = np.ascontiguousarray(np.concatenate(pts)) if pts else np.zeros((0, 3))
+    cl_all = np.ascontiguousarray(np.concatenate(cls)) if cls else None
+    adj = np.array([float(a) for _, _, a in jobs], dtype=np.float64)
+    out = np.zeros_like(xyz)
+    nearest = np.zeros(xyz.shape[0], dtype=np.int32)
+    N.check(N.lib().mm_centerline_morph_batch(_engine(engine).handle, len(jobs), N._ptr(cl_all), N._ptr(cl_off),
+                                              N._ptr(xyz), N._ptr(pt_off), N._ptr(adj), N._ptr(out), N._ptr(nearest)),
+            "centerline_morph_batch")
+    return [(out[pt_off[j]:pt_off[j + 1]], nearest[pt_off[j]:pt_off[j + 1]]) for j in range(len(jobs))]
+
+
+def keep_largest_connected_component(vertices, faces, points) -> np.ndarray:
+    """ccta_py.rs:541-580 (host): the vertices, ascending, of the largest connected component of the face adjacency
+    restricted to the vertices matching ``points`` bit for bit (the last of duplicated vertices).  Fewer than 2 points,
+    or none matching a vertex: the points unchanged.  Of equally large components the one holding the smallest vertex
+    index is kept (the reference picks one in hash order and returns it in hash order).  Returns an ``(n, 3)`` array."""
+    v, f, p = _p3(vertices), _faces3(faces), _p3(points)
+    keep = np.zeros(p.shape[0], dtype=np.int64)
+    k = N.lib().mm_keep_largest_component(N._ptr(v), v.shape[0], N._ptr(f), f.shape[0], N._ptr(p), p.shape[0],
+                                          N._ptr(keep))
+    if k < 0:
+        N.check(int(k), "keep_largest_connected_component")
+    return p.copy() if k == 0 else v[keep[:k]].copy()
+
+
+def label_anomalous_region(centerline: Centerline, frames, results: dict, results_key: str = "rca_points",
+                           debug_plot: bool = False, engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/labeling.py:283-389: split ``results[results_key]`` into proximal, distal and anomalous points
+    along ``centerline`` (find_points_by_cl_region; ``frames``: a FlatGeometry or an (F, 3) array of centroids), keep
+    the largest mesh-connected component of each (against ``results["mesh"]``), drop the island points from
+    ``results[results_key]`` (order kept) and make ``"aorta_points"`` the mesh vertices, in vertex order, in none of
+    rca / lca / proximal / distal / anomalous.  Points are compared by value.  Mutates and returns ``results``, with
+    ``"proximal_points"``, ``"distal_points"``, ``"anomalous_points"`` as ``(n, 3)`` arrays.  ``debug_plot`` is
+    accepted and ignored."""
+    raw = find_points_by_cl_region(centerline, frames, results[results_key], engine=engine)
+    vertices, faces = _mesh_parts(results["mesh"])
+    v = _p3(vertices)
+    parts = [keep_largest_connected_component(v, faces, r) for r in raw]
+    dropped = np.concatenate([r[_match(k, r) < 0] for r, k in zip(raw, parts)])
+    if dropped.shape[0]:
+        pts = _p3(results[results_key])
+        results[results_key] = pts[_match(dropped, pts) < 0].copy()
+    results["proximal_points"], results["distal_points"], results["anomalous_points"] = parts
+    coronary = np.concatenate([_p3(results.get("rca_points", ())), _p3(results.get("lca_points", ())), *parts])
+    results["aorta_points"] = v[_match(coronary, v) < 0].copy()
+    return results
+
+
+def _with_vertices(mesh, vertices: np.ndarray):
+    """A mesh of the kind given with new vertices: a (vertices, faces) tuple, or a copy of the object (its own
+    ``copy()`` where it has one, as trimesh does, else a shallow copy) with ``.vertices`` replaced."""
+    if not (hasattr(mesh, "vertices") and hasattr(mesh, "faces")):
+        return (vertices, mesh[1])
+    m = mesh.copy() if callable(getattr(mesh, "copy", None)) else copy.copy(mesh)
+    m.vertices = vertices
+    return m
+
+
+def scale_region_centerline_morphing(mesh, region_points, centerline: Centerline, diameter_adjustment_mm: float,
+                                     engine: Optional[N.Engine] = None):
+    """multimodars/ccta/scaling.py:16-80: every vertex equal by value to one of ``region_points`` (duplicated vertices
+    all) moves by ``diameter_adjustment_mm`` along the direction from its nearest ``centerline`` point; the search and
+    the move run on the device in exact f64 (csrc/mm_morph_kernels.hip).  Returns a new mesh of the kind given (see
+    ``label_geometry``); the input is not modified.  Without a matching vertex the copy comes back unmoved and
+    ``centerline`` is not read."""
+    vertices, _ = _mesh_parts(mesh)
+    v = _p3(vertices)
+    moved = v.copy()
+    sel = np.flatnonzero(_match(region_points, v) >= 0)
+    if sel.size:
+        moved[sel] = centerline_morph_batch([(centerline, v[sel], diameter_adjustment_mm)], engine)[0][0]
+    return _with_vertices(mesh, moved)
+
+
+SYNC_KEYS = ("aorta_points", "rca_points", "lca_points", "rca_removed_points", "lca_removed_points", "proximal_points",
+             "distal_points", "anomalous_points", "boundary_points")
+
+
+def sync_results_to_mesh(results: dict, old_mesh, new_mesh) -> dict:
+    """multimodars/ccta/scaling.py:301-351: a new dict with ``"mesh"`` = ``new_mesh`` and the point lists of
+    SYNC_KEYS and of every ``boundary_points_*`` key remapped from their positions in ``old_mesh`` to the same vertices
+    of ``new_mesh`` (points equal by value; the last old vertex wins; unmatched points are dropped).  Missing or empty
+    keys and all other keys are left as they are."""
+    ov, nv = _p3(_mesh_parts(old_mesh)[0]), _p3(_mesh_parts(new_mesh)[0])
+    updated = dict(results)
+    updated["mesh"] = new_mesh
+    for key in SYNC_KEYS + tuple(sorted(k for k in updated if k.startswith("boundary_points_"))):
+        pts = updated.get(key)
+        if pts is None or len(pts) == 0:
+            continue
+        idx = _match(ov, pts)
+        updated[key] = nv[idx[idx >= 0]].copy()
+    return updated
+
+
+def scale(results: dict, cl_vessel: Centerline, cl_aorta: Centerline, aligned_frames: G.FlatGeometry,
+          engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/__init__.py:171-258: the proximal / distal scalings (find_distal_and_proximal_scaling) and the
+    aortic one (find_aorta_scaling) against ``aligned_frames``, then three morph + sync rounds: the distal points about
+    ``cl_vessel``, the aortic region (``aorta_points`` followed by ``rca_removed_points``) about ``cl_aorta``, the
+    proximal points about ``cl_vessel``.  Returns the synced results with the scaled mesh."""
+    prox_scaling, distal_scaling = find_distal_and_proximal_scaling(aligned_frames, cl_vessel, results, engine=engine)
+    aortic_scaling = find_aorta_scaling(aligned_frames, cl_aorta, results, engine=engine)
+    m = scale_region_centerline_morphing(results["mesh"], results["distal_points"], cl_vessel, distal_scaling, engine)
+    results = sync_results_to_mesh(results, results["mesh"], m)
+    aortic = np.concatenate([_p3(results["aorta_points"]), _p3(results["rca_removed_points"])])
+    m = scale_region_centerline_morphing(results["mesh"], aortic, cl_aorta, aortic_scaling, engine)
+    results = sync_results_to_mesh(results, results["mesh"], m)
+    m = scale_region_centerline_morphing(results["mesh"], results["proximal_points"], cl_vessel, prox_scaling, engine)
+    return sync_results_to_mesh(results, results["mesh"], m)

@@ -737,6 +737,8 @@ struct Adjacency {
     const int64_t* begin(int64_t v) const { return nb.data() + off[(size_t)v]; }
     const int64_t* end(int64_t v) const { return nb.data() + off[(size_t)v + 1]; }
 };
+// Edges with an end outside [0, nv) are left out: such a vertex is in no subset the callers walk (keep_largest takes
+// indices >= nv as the reference does; the other callers reject them up front).
 void build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, Adjacency& adj)
 {
     std::vector<std::pair<int64_t, int64_t>> ed;
@@ -744,7 +746,8 @@ void build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, Adjacency& ad
     for (int64_t f = 0; f < nf; ++f) {
         const int64_t* v = faces + 3 * f;
         const int64_t e[3][2] = {{v[0], v[1]}, {v[1], v[2]}, {v[2], v[0]}};
-        for (const auto& p : e) { ed.emplace_back(p[0], p[1]); ed.emplace_back(p[1], p[0]); }
+        for (const auto& p : e)
+            if (p[0] >= 0 && p[0] < nv && p[1] >= 0 && p[1] < nv) { ed.emplace_back(p[0], p[1]); ed.emplace_back(p[1], p[0]); }
     }
     std::sort(ed.begin(), ed.end());
     ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
@@ -755,17 +758,16 @@ void build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, Adjacency& ad
     for (size_t k = 0; k < ed.size(); ++k) adj.nb[k] = ed[k].second;   // sorted by first: already in CSR order
 }
 
-// reclassify_minority_components (:485-544).  Components are found from their smallest vertex upwards; the largest
-// one is kept out, and among equally large ones the one with the smallest vertex index: the reference picks one of
-// them in HashSet order, so this is one of the outcomes it can produce.
-void reclassify_minority(const Adjacency& adj, const std::vector<uint8_t>& labels, std::vector<uint8_t>& out,
-                         uint8_t subject, const std::vector<uint8_t>& targets)
+// connected_components (label_coronary.rs:428-455) of the vertices v < nv with in(v), on the mesh adjacency restricted
+// to them.  Components are found from their smallest vertex upwards; comp[v] = the component of v (-1 outside).
+template <class In>
+void components(const Adjacency& adj, int64_t nv, In in, std::vector<int64_t>& comp,
+                std::vector<std::vector<int64_t>>& comps)
 {
-    const int64_t nv = (int64_t)labels.size();
-    std::vector<int64_t> comp((size_t)nv, -1);
-    std::vector<std::vector<int64_t>> comps;
+    comp.assign((size_t)nv, -1);
+    comps.clear();
     for (int64_t s = 0; s < nv; ++s) {
-        if (labels[(size_t)s] != subject || comp[(size_t)s] >= 0) continue;
+        if (!in(s) || comp[(size_t)s] >= 0) continue;
         const int64_t c = (int64_t)comps.size();
         comps.emplace_back();
         std::vector<int64_t> stack{s};
@@ -775,13 +777,33 @@ void reclassify_minority(const Adjacency& adj, const std::vector<uint8_t>& label
             stack.pop_back();
             comps.back().push_back(v);
             for (const int64_t* p = adj.begin(v); p != adj.end(v); ++p)
-                if (labels[(size_t)*p] == subject && comp[(size_t)*p] < 0) { comp[(size_t)*p] = c; stack.push_back(*p); }
+                if (in(*p) && comp[(size_t)*p] < 0) { comp[(size_t)*p] = c; stack.push_back(*p); }
         }
     }
-    if (comps.empty()) return;
+}
+
+// The largest of the components (comps non-empty); among equally large ones the first found, i.e. the one holding the
+// smallest vertex index: the reference picks one of them in HashSet order, so this is one of the outcomes it can
+// produce.
+size_t largest_component(const std::vector<std::vector<int64_t>>& comps)
+{
     size_t largest = 0;
     for (size_t c = 1; c < comps.size(); ++c)
         if (comps[c].size() > comps[largest].size()) largest = c;
+    return largest;
+}
+
+// reclassify_minority_components (:485-544): every component of `subject` but the largest moves to a target label
+// that holds more than 70 % of its boundary.
+void reclassify_minority(const Adjacency& adj, const std::vector<uint8_t>& labels, std::vector<uint8_t>& out,
+                         uint8_t subject, const std::vector<uint8_t>& targets)
+{
+    const int64_t nv = (int64_t)labels.size();
+    std::vector<int64_t> comp;
+    std::vector<std::vector<int64_t>> comps;
+    components(adj, nv, [&](int64_t v) { return labels[(size_t)v] == subject; }, comp, comps);
+    if (comps.empty()) return;
+    const size_t largest = largest_component(comps);
     std::vector<int64_t> mark((size_t)nv, -1);
     for (size_t c = 0; c < comps.size(); ++c) {
         if (c == largest) continue;
@@ -844,6 +866,58 @@ void restore_removed(const Adjacency& adj, const std::vector<uint8_t>& labels, s
     }
     for (int64_t v = 0; v < nv; ++v)
         if (dec[(size_t)v] == 1) out[(size_t)v] = target;
+}
+
+
+// ---- centerline morphing (scale_coronary.rs:218-260) on the device ----------------------------------------------
+
+struct MorphJobH { int32_t p_off, np, c_off, nc; double adj; };   // MorphJob in mm_morph_kernels.hip
+struct MorphWorkH { int32_t job, p0; };
+
+// every point of every job moved about its nearest centerline point of that job (k_cl_morph); every job with points
+// has a centerline point (checked by the caller)
+int cl_morph(Engine* e, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off, const double* pts,
+             const int64_t* pt_off, const double* adj, double* out, int32_t* nearest)
+{
+    const int64_t NP = pt_off[n_jobs], NC = cl_off[n_jobs];
+    if (NP == 0) return MM_OK;
+    if (NP > INT32_MAX / 4 || NC > INT32_MAX / 4)
+        return set_error(MM_ERR_TOO_LARGE, "centerline morphing: too many points for one pass");
+    std::vector<MorphJobH> jobs((size_t)n_jobs);
+    std::vector<MorphWorkH> work;
+    double evals = 0.0;
+    const int bp = morph_block_points();
+    for (int j = 0; j < n_jobs; ++j) {
+        const int64_t np = pt_off[j + 1] - pt_off[j], nc = cl_off[j + 1] - cl_off[j];
+        jobs[(size_t)j] = MorphJobH{(int32_t)pt_off[j], (int32_t)np, (int32_t)cl_off[j], (int32_t)nc, adj[j]};
+        for (int64_t p0 = 0; p0 < np; p0 += bp) work.push_back(MorphWorkH{j, (int32_t)p0});
+        evals += (double)np * (double)nc;
+    }
+    const size_t o_cl = up256((size_t)NP * 24), o_jobs = up256(o_cl + (size_t)NC * 24);
+    const size_t o_work = up256(o_jobs + jobs.size() * sizeof(MorphJobH)), in_bytes = up256(o_work + work.size() * sizeof(MorphWorkH));
+    const size_t o_idx = in_bytes, o_out = up256(o_idx + (size_t)NP * 4), total = up256(o_out + (size_t)NP * 24);
+    int rc = e->ensure(e->host_pts, std::max(in_bytes, total - o_idx), true);
+    if (rc) return rc;
+    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
+    unsigned char* h = (unsigned char*)e->host_pts.p;
+    std::memcpy(h, pts, (size_t)NP * 24);
+    double* hc = (double*)(h + o_cl);
+    for (int64_t k = 0; k < NC; ++k) { hc[3 * k] = cl[k].x; hc[3 * k + 1] = cl[k].y; hc[3 * k + 2] = cl[k].z; }
+    std::memcpy(h + o_jobs, jobs.data(), jobs.size() * sizeof(MorphJobH));
+    std::memcpy(h + o_work, work.data(), work.size() * sizeof(MorphWorkH));
+    unsigned char* d = (unsigned char*)e->dev_pts.p;
+    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = e->profile_begin(e->stream))) return rc;
+    const hipError_t he = launch_cl_morph(d + o_jobs, d + o_work, (int)work.size(), (const double*)d,
+                                          (const double*)(d + o_cl), (int32_t*)(d + o_idx), (double*)(d + o_out),
+                                          e->stream);
+    if (he != hipSuccess) return hip_error(he, "centerline morphing launch");
+    if ((rc = e->profile_end(e->stream, evals, 0))) return rc;
+    MM_TRY_HIP(hipMemcpyAsync(h, d + o_idx, total - o_idx, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    std::memcpy(nearest, h, (size_t)NP * 4);
+    std::memcpy(out, h + (o_out - o_idx), (size_t)NP * 24);
+    return MM_OK;
 }
 
 }  // namespace
@@ -1167,6 +1241,74 @@ int mm_final_reclassification(const double* vertices, int64_t nv, const int64_t*
     restore_removed(adj, labels, out, 4, 2);
     if (nv > 0) std::memcpy(label, out.data(), (size_t)nv);
     return MM_OK;
+}
+
+// centerline_based_diameter_morphing (scale_coronary.rs:218-260) on the device, n_jobs at once
+int mm_centerline_morph_batch(mm_engine* h, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off,
+                              const double* pts_xyz, const int64_t* pt_off, const double* adj, double* out_xyz,
+                              int32_t* nearest)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (n_jobs < 0 || (n_jobs > 0 && (!cl_off || !pt_off || !adj)))
+        return set_error(MM_ERR_INVALID, "mm_centerline_morph_batch: bad arguments");
+    if (n_jobs == 0) return MM_OK;
+    if (!offsets_ok(cl_off, n_jobs) || !offsets_ok(pt_off, n_jobs))
+        return set_error(MM_ERR_INVALID, "mm_centerline_morph_batch: offsets must start at 0 and not decrease");
+    if ((pt_off[n_jobs] > 0 && (!pts_xyz || !out_xyz || !nearest)) || (cl_off[n_jobs] > 0 && !cl))
+        return set_error(MM_ERR_INVALID, "mm_centerline_morph_batch: bad arguments");
+    for (int j = 0; j < n_jobs; ++j)
+        if (pt_off[j + 1] > pt_off[j] && cl_off[j + 1] == cl_off[j])                       // centerline.points[0] panics
+            return set_error(MM_ERR_INVALID, "mm_centerline_morph_batch: a job with points has an empty centerline");
+    return cl_morph(e, n_jobs, cl, cl_off, pts_xyz, pt_off, adj, out_xyz, nearest);
+}
+
+// the reference's coord_to_idx lookups (bits_key): the last key of each bit pattern
+int64_t mm_match_points(const double* keys, int64_t nk, const double* queries, int64_t nq, int64_t* index)
+{
+    if (nk < 0 || nq < 0 || (nk > 0 && !keys) || (nq > 0 && (!queries || !index)))
+        return set_error(MM_ERR_INVALID, "mm_match_points: bad arguments");
+    std::unordered_map<BitsKey, int64_t, BitsHash> idx;
+    idx.reserve((size_t)nk);
+    for (int64_t i = 0; i < nk; ++i) idx[bits_key(keys + 3 * i)] = i;
+    int64_t k = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        const auto it = idx.find(bits_key(queries + 3 * i));
+        index[i] = it == idx.end() ? -1 : it->second;
+        k += index[i] >= 0;
+    }
+    return k;
+}
+
+// keep_largest_connected_component (ccta_py.rs:541-580)
+int64_t mm_keep_largest_component(const double* vertices, int64_t nv, const int64_t* faces, int64_t nf,
+                                  const double* pts, int64_t n, int64_t* keep)
+{
+    if (nv < 0 || nf < 0 || n < 0 || (nv > 0 && !vertices) || (nf > 0 && !faces) || (n > 0 && (!pts || !keep)))
+        return set_error(MM_ERR_INVALID, "mm_keep_largest_component: bad arguments");
+    for (int64_t k = 0; k < 3 * nf; ++k)
+        if (faces[k] < 0) return set_error(MM_ERR_INVALID, "mm_keep_largest_component: negative face index");
+    if (n < 2) return 0;                                                                   // :548-550
+    std::unordered_map<BitsKey, int64_t, BitsHash> idx;                                   // :552-555 the last index wins
+    idx.reserve((size_t)nv);
+    for (int64_t i = 0; i < nv; ++i) idx[bits_key(vertices + 3 * i)] = i;
+    std::vector<uint8_t> in((size_t)nv, 0);
+    bool any = false;
+    for (int64_t i = 0; i < n; ++i) {                                                      // :557-561
+        const auto it = idx.find(bits_key(pts + 3 * i));
+        if (it != idx.end()) { in[(size_t)it->second] = 1; any = true; }
+    }
+    if (!any) return 0;                                                                    // :562-564
+    Adjacency adj;
+    build_adjacency(faces, nf, nv, adj);
+    std::vector<int64_t> comp;
+    std::vector<std::vector<int64_t>> comps;
+    components(adj, nv, [&](int64_t v) { return in[(size_t)v] != 0; }, comp, comps);
+    std::vector<int64_t>& largest = comps[largest_component(comps)];                     // :567-571
+    std::sort(largest.begin(), largest.end());
+    std::copy(largest.begin(), largest.end(), keep);
+    return (int64_t)largest.size();
 }
 
 }  // extern "C"

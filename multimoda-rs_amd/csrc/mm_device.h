@@ -175,6 +175,12 @@ size_t     ray_partial_bytes();
 hipError_t launch_slice_nearest(const void* jobs, const void* work, int n_work, const double* pts, const double* anc,
                                 int32_t* idx, double* proj, hipStream_t s);
 int        slice_block_points();
+// radial morphing about the nearest centerline point (mm_morph_kernels.hip): jobs = MorphJob records (point /
+// centerline ranges, adjustment), work = MorphWork records (job, first point) of morph_block_points() points each;
+// pts / cl = xyz triples; nearest (job-local centerline index) / out (moved xyz) at the point's position
+hipError_t launch_cl_morph(const void* jobs, const void* work, int n_work, const double* pts, const double* cl,
+                           int32_t* nearest, double* out, hipStream_t s);
+int        morph_block_points();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers

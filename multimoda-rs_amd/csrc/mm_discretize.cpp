@@ -262,14 +262,6 @@ int nearest_project(Engine* e, int n_jobs, const int64_t* pt_off, const double* 
     return MM_OK;
 }
 
-bool offsets_ok(const int64_t* off, int n)
-{
-    if (off[0] != 0) return false;
-    for (int j = 0; j < n; ++j)
-        if (off[j + 1] < off[j]) return false;
-    return true;
-}
-
 }  // namespace
 }  // namespace mm
 

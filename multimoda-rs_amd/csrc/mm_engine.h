@@ -17,6 +17,14 @@ namespace mm {
 extern thread_local std::string g_last_error;
 int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);
+// n + 1 CSR offsets of a batch of jobs: they start at 0 and do not decrease
+inline bool offsets_ok(const int64_t* off, int n)
+{
+    if (off[0] != 0) return false;
+    for (int j = 0; j < n; ++j)
+        if (off[j + 1] < off[j]) return false;
+    return true;
+}
 
 // The switches that choose a level's screens.  The engine holds the defaults (mm_engine_set_*); Plan::stage_level copies
 // them into the plan, and everything from there on -- the screen of every pair, the device description, run() -- reads
