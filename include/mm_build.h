@@ -1,6 +1,7 @@
 /*
  * mm_build.h -- C ABI of the geometry builder and of the bookkeeping around the searches:
- * host f64 in the reference's operation order, no device work.  Same conventions as mm_hausdorff.h.
+ * host f64 in the reference's operation order, no device work -- except the lumen morphometry's contour measures
+ * (mm_contour_measures, csrc/mm_shape_kernels.hip).  Same conventions as mm_hausdorff.h.
  *
  * Reference interfaces replaced (paths relative to the reference checkout):
  *   src/intravascular/io/build.rs:9-205            build_geometry_from_inputdata (from an InputData)
@@ -9,6 +10,9 @@
  *   src/types/native/frame.rs:69-82,163-204        set_value(id), create_catheter_points
  *   src/types/native/geometry.rs:42-59,72-155,325-381  find_proximal_end_idx, reorder_frames,
  *                                                  ensure_proximal_at_position_zero
+ *   src/types/native/contour.rs:227-361            find_farthest_points, find_closest_opposite(_3d),
+ *                                                  elliptic_ratio, area
+ *   src/types/binding/py_geometry.rs:190-260       PyGeometry::get_summary
  * The Python layer's io.build_geometry_from_inputdata calls this; tests/test_refbuild.py compares the result with
  * an independent pure-Python restatement of the same reference code on every fixture directory, bit for bit.
  */
@@ -68,6 +72,32 @@ void mm_built_destroy(mm_built* b);
 /* Contour::compute_centroid (contour.rs:213-224) of n CSR contours of xyz triples: sequential sums / count, the
  * reference's fold; out [n*3] (a contour without points yields zeros).  Contours are independent: worker pool. */
 int  mm_contour_centroids(const double* xyz, const int64_t* off, int64_t n_contours, double* out);
+
+/* ---- lumen morphometry (csrc/mm_shape.cpp, csrc/mm_shape_kernels.hip) ----------------------------------------- */
+
+#define MM_MEASURE_CLOSEST_2D 1u   /* mm_contour_measures: also run find_closest_opposite (the 2-D pass, O(n^2)) */
+
+/* The measures of contour.rs on the device, every contour in one launch.  Contour c: points off[c] .. off[c+1] of xyz
+ * (rows of x, y, z).  out_val [n*5] = area (:345-361), major (find_farthest_points :227-242), minor_3d
+ * (find_closest_opposite_3d :313-333), minor_2d (find_closest_opposite :247-310), elliptic ratio (:335-343).
+ * out_idx [n*6] = the contour-local pairs of major, minor_3d and minor_2d, in the reference's orientation.  All in
+ * the reference's operation order, bit for bit, with its tie rules (the first pair of the largest / smallest value)
+ * and NaN rules (a NaN distance never wins).  The 2-D pass runs only with MM_MEASURE_CLOSEST_2D; its centre is
+ * centroid_xyz[c] where has_centroid[c] is set (both nullable), else the sequential mean of the points; its angles
+ * are taken with the C library's atan2 on the host.  Where the reference panics, a value is NaN and its pair
+ * (-1, -1): the major of an empty contour; minor_3d, minor_2d and the ratio of a contour of fewer than 3 points.  A
+ * skipped 2-D pass is NaN / (-1, -1) too.  Area is 0.0 below 3 points, as in the reference. */
+int  mm_contour_measures(mm_engine* e, int64_t n_contours, const int64_t* off, const double* xyz,
+                         const uint8_t* has_centroid, const double* centroid_xyz, uint32_t flags, double* out_val,
+                         int64_t* out_idx);
+/* PyGeometry::get_summary (py_geometry.rs:190-260) from per-frame lumen areas, elliptic ratios, point counts and
+ * frame centroids (xyz rows), host only.  out [3] = (mla, max_stenosis, stenosis_length): (0, 0, 0) without frames;
+ * biggest / mla fold f64::max / f64::min (NaN areas ignored); threshold 0.70 * biggest if every ratio is < 1.3, else
+ * 0.50 * biggest; the length is the longest run of frames with area < threshold, summed over successive centroid
+ * distances.  The ratio test stops at the first ratio >= 1.3 (Rust's all()), and a frame it reaches with fewer than
+ * 3 points is MM_ERR_INVALID (the reference panics there); frames behind it are not looked at. */
+int  mm_summary_from_measures(int64_t n_frames, const double* area, const double* ratio, const int64_t* n_points,
+                              const double* centroids_xyz, double* out);
 
 /* ---- the bookkeeping around the searches on a frame list (csrc/mm_frames.cpp) -----------------------------------
  * Reference interfaces replaced:

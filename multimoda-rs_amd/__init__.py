@@ -31,6 +31,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    label_anomalous_region, label_geometry, remove_occluded_points_ray_triangle, scale,
                    scale_region_centerline_morphing, sync_results_to_mesh)
 from .convert import numpy_to_geometry, to_array
+from . import morphometry
+from .morphometry import ContourMeasures, contour_measures
 from .export import to_obj
 from . import export
 from .extension import ShiftRotationSearch
@@ -57,6 +59,7 @@ __all__ = [
     "discretize_vessel", "discretize_vessel_tree", "DiscretizedVesselTree",
     "keep_largest_connected_component", "label_anomalous_region", "scale_region_centerline_morphing",
     "sync_results_to_mesh", "scale",
+    "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",
 ]

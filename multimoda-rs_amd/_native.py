@@ -77,7 +77,8 @@ class MMGeometry(C.Structure):
 # include/mm_build.h
 EXPORTS_BUILD = ["mm_build_geometry", "mm_build_geometry_lenient", "mm_built_dims", "mm_built_export", "mm_built_destroy", "mm_contour_centroids",
                  "mm_frames_from_flat", "mm_frames_dims", "mm_frames_export", "mm_frames_destroy",
-                 "mm_frames_finish_within", "mm_frames_postprocess_pair"]
+                 "mm_frames_finish_within", "mm_frames_postprocess_pair",
+                 "mm_contour_measures", "mm_summary_from_measures"]
 
 
 class MMRecord(C.Structure):
@@ -387,6 +388,10 @@ def lib():
     L.mm_built_destroy.argtypes = [P]
     L.mm_contour_centroids.restype = I
     L.mm_contour_centroids.argtypes = [P, P, I64, P]
+    L.mm_contour_measures.restype = I
+    L.mm_contour_measures.argtypes = [P, I64, P, P, P, P, C.c_uint32, P, P]
+    L.mm_summary_from_measures.restype = I
+    L.mm_summary_from_measures.argtypes = [I64, P, P, P, P, P]
     L.mm_frames_from_flat.restype = I
     L.mm_frames_from_flat.argtypes = [C.POINTER(MMFlatGeometry), C.POINTER(P)]
     L.mm_frames_dims.restype = I

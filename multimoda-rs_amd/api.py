@@ -59,6 +59,13 @@ class GeometryPair:
     geom_b: G.FlatGeometry
     label: str = ""
 
+    def get_summary(self, print_table: bool = True, engine: Optional[N.Engine] = None):
+        """PyGeometryPair.get_summary (py_geometry_pair.rs:70-200): ``((summary_a, summary_b), table)``, the table an
+        (F, 6) array ``[lumen id, area_a, ellip_a, area_b, ellip_b, z]`` per frame of geom_a, printed as the reference
+        prints it unless ``print_table`` is False.  Both geometries are measured in one launch (morphometry.py)."""
+        from .morphometry import pair_summary
+        return pair_summary(self, print_table, engine)
+
 
 def _with_contour_centroids(g: G.FlatGeometry) -> G.FlatGeometry:
     """Frame.lumen.centroid of a returned geometry (read by the centerline placement, centerline.py).

@@ -546,6 +546,15 @@ class DiscretizedVesselTree:
             setattr(self, side + "_references", _vessel_references(ao, main, branches))
         return self
 
+    def get_summary(self, engine: Optional[N.Engine] = None) -> dict:
+        """Lumen morphometry of every vessel of the tree (morphometry.tree_summary; no reference counterpart -- it
+        composes the reference's contour measures and geometry-summary rule): ``{"aorta": (summary, table),
+        "rca_main": ..., "lca_main": ..., "rca_branches": [...], "lca_branches": [...]}`` with summary = (mla,
+        max_stenosis, stenosis_length) and one table row ``[id, area, elliptic_ratio, major, minor_3d, z]`` per slice,
+        the slice centroid (anchor) standing in for the frame centroid.  The whole tree is measured in one launch."""
+        from .morphometry import tree_summary
+        return tree_summary(self, engine)
+
 
 def discretize_vessel_tree_raw(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Centerline, points_ao, points_rca_main,
                                points_lca_main, side_branches_rca, side_branches_lca, branch_id_rca: int = 0,

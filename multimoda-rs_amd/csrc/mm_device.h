@@ -181,6 +181,12 @@ int        slice_block_points();
 hipError_t launch_cl_morph(const void* jobs, const void* work, int n_work, const double* pts, const double* cl,
                            int32_t* nearest, double* out, hipStream_t s);
 int        morph_block_points();
+// lumen morphometry (mm_shape_kernels.hip): jobs = n_jobs ShapeJob records of shape_job_bytes() each (first point,
+// point count); xyz = point rows; theta = one angle per point, read only when want2d; val = 5 doubles per contour
+// (area, major, minor 3-D, minor 2-D, elliptic ratio), idx = 6 per contour (the three pairs, contour-local)
+hipError_t launch_contour_measures(const void* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
+                                   double* val, int64_t* idx, hipStream_t s);
+size_t     shape_job_bytes();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers

@@ -46,6 +46,26 @@ class Contour:
         """contour.rs:213-224: sequential sums / n; None for an empty contour."""
         self.centroid = None if len(self) == 0 else contour_centroid(self.points)
 
+    def get_area(self, engine=None) -> float:
+        """Contour::area (contour.rs:345-361), on the device (morphometry.py)."""
+        from .morphometry import get_area
+        return get_area(self, engine)
+
+    def get_elliptic_ratio(self, engine=None) -> float:
+        """Contour::elliptic_ratio (contour.rs:335-343), on the device."""
+        from .morphometry import get_elliptic_ratio
+        return get_elliptic_ratio(self, engine)
+
+    def find_farthest_points(self, engine=None):
+        """Contour::find_farthest_points (contour.rs:227-242): ``((p1, p2), distance)``, on the device."""
+        from .morphometry import find_farthest_points
+        return find_farthest_points(self, engine)
+
+    def find_closest_opposite(self, engine=None):
+        """Contour::find_closest_opposite (contour.rs:247-310): ``((p1, p2), distance)``, on the device."""
+        from .morphometry import find_closest_opposite
+        return find_closest_opposite(self, engine)
+
     def clone(self) -> "Contour":
         return Contour(self.id, self.original_frame, self.points.copy(), self.centroid, self.aortic_thickness,
                        self.pulmonary_thickness, self.kind, self.aortic.copy())

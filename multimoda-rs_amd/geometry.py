@@ -155,6 +155,12 @@ class FlatGeometry:
                             cp(self.extra_off), cp(self.extra), cp(self.has_ref), cp(self.ref), self.label,
                             dict(self.meta), cp(self.has_lumen_centroid), cp(self.lumen_centroids))
 
+    def get_summary(self, engine: Optional[N.Engine] = None):
+        """PyGeometry.get_summary (py_geometry.rs:190-260): ``(mla, max_stenosis, stenosis_length_mm)`` of the lumen
+        contours, measured on the device in one launch (morphometry.py)."""
+        from .morphometry import geometry_summary
+        return geometry_summary(self, engine)
+
     def frame_lumen(self, i: int) -> np.ndarray:
         return self.lumen[self.lumen_off[i]:self.lumen_off[i + 1]]
 
