@@ -149,9 +149,10 @@ int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
  * 16384): a dozen dependent launches cost more than screening a small batch outright. 0 = always. */
 int  mm_engine_set_bound_min_candidates(mm_engine* e, int64_t n);
 /* MM_PRECISION_F32_BOUNDED computes its lower bounds, its picks and its survivors on the f16 matrix pipe when every pair of
- * the batch has sets of 64 .. 544 points and the target sets share one column-tile count (default, on != 0; a batch of other
- * shapes is screened outright on the matrix pipe, without bound rounds); on == 0 keeps the packed-FMA kernels of rounds 1-3
- * (the A/B switch of bench.py's bounded_search leg).  Same winners and costs either way. */
+ * the batch has a reference set of 64 .. 528 points and a target set of 64 .. 544, and the target sets share one column-tile
+ * count (default, on != 0; a batch of other shapes is screened outright on the matrix pipe, without bound rounds); on == 0
+ * keeps the packed-FMA kernels of rounds 1-3 (the A/B switch of bench.py's bounded_search leg).  Same winners and costs
+ * either way. */
 int  mm_engine_set_bound_matrix(mm_engine* e, int on);
 /* MM_PRECISION_F32_MATRIX screens pairs of 64 .. 544 points per set without the 32 x 32 tiles of the distance matrix that
  * provably hold no row or column minimum (default, on != 0; bit-identical screened values); on == 0 computes every tile
@@ -168,6 +169,17 @@ int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
 int  mm_lower_bounds(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                      double cx, double cy, const double* angles, int n_angles, int flags, int matrix, float* out_lb2,
                      double* e2, double* delta, int* stride);
+/* TEST HOOK (nothing in the product calls it): the state MM_PRECISION_F32_BOUNDED's bound rounds leave for the shortlist in
+ * one search, every round run (no minimum batch size).  Per candidate: out_lb2[i] its final bound of the squared cost (+inf
+ * where the chord rule of the spread round ruled it out, else <= (exact cost)^2 up to *e2 and *delta as in
+ * mm_lower_bounds), out_sq2[i] its screened squared value (+inf for every candidate that did not survive the last round,
+ * within *e2 of the exact squared cost for the survivors and both picks); picks[2] the candidates the first and the second
+ * pick screened.  matrix != 0: the matrix-pipe rounds (a reference set of 64 .. 528 points, a target set of 64 .. 544),
+ * 0: the packed-FMA rounds (a reference set of 64 .. 528 points); MM_ERR_INVALID if the search would not take the rounds
+ * asked for. */
+int  mm_bound_state(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                    double cx, double cy, const double* angles, int n_angles, int flags, int matrix, float* out_lb2,
+                    float* out_sq2, int32_t* picks, double* e2, double* delta);
 /* TEST HOOK (nothing in the product calls it): what the first pick of the matrix-pipe bounded search leaves for the choice
  * of the third round's queries -- for ONE candidate angle the squared distance from every reference point to its nearest
  * rotated target point (row_min2[nr]) and from every rotated target point to its nearest reference point (col_min2[nt]),

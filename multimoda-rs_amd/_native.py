@@ -29,6 +29,7 @@ EXPORTS = [
     "mm_device_count", "mm_last_error", "mm_version",
     "mm_engine_create", "mm_engine_destroy", "mm_engine_synchronize", "mm_engine_stream", "mm_engine_wait_search",
     "mm_engine_profile", "mm_engine_profile_read", "mm_engine_profile_launches", "mm_engine_bound_stats", "mm_engine_screen_stats", "mm_engine_set_bound_matrix", "mm_lower_bounds", "mm_pick_minima",
+    "mm_bound_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
@@ -213,6 +214,8 @@ def lib():
     L.mm_pick_minima.argtypes = [P, P, P, I, P, P, I, D, D, D, I, P, P, P, P]
     L.mm_lower_bounds.restype = I
     L.mm_lower_bounds.argtypes = [P, P, P, I, P, P, I, D, D, P, I, I, I, P, P, P, P]
+    L.mm_bound_state.restype = I
+    L.mm_bound_state.argtypes = [P, P, P, I, P, P, I, D, D, P, I, I, I, P, P, P, P, P]
     L.mm_engine_set_bound_matrix.restype = I
     L.mm_engine_set_bound_matrix.argtypes = [P, I]
     L.mm_engine_screen_stats.restype = I
@@ -707,6 +710,21 @@ class Engine:
                                     float(centre[1]), _ptr(ang), len(ang), MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(matrix)),
                                     _ptr(out), C.byref(e2), C.byref(delta), C.byref(stride)), "mm_lower_bounds")
         return out, e2.value, delta.value, stride.value
+
+    def bound_state(self, ref, tgt, angles, centre, skip_zero=True, matrix=True):
+        """TEST HOOK (``mm_bound_state``): what every round of the bounded search leaves for the shortlist -- each
+        candidate's final bound (+inf: ruled out by the chord rule) and screened value (+inf: not a survivor) of the
+        SQUARED cost, both picks, e2 and delta."""
+        ref = np.ascontiguousarray(ref, dtype=np.float64); tgt = np.ascontiguousarray(tgt, dtype=np.float64)
+        rx, ry = np.ascontiguousarray(ref[:, 0]), np.ascontiguousarray(ref[:, 1])
+        tx, ty = np.ascontiguousarray(tgt[:, 0]), np.ascontiguousarray(tgt[:, 1])
+        ang = np.ascontiguousarray(angles, dtype=np.float64)
+        lb, sq = np.zeros(len(ang), dtype=np.float32), np.zeros(len(ang), dtype=np.float32)
+        picks, e2, delta = np.zeros(2, dtype=np.int32), C.c_double(0.0), C.c_double(0.0)
+        check(lib().mm_bound_state(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), float(centre[0]),
+                                   float(centre[1]), _ptr(ang), len(ang), MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(matrix)),
+                                   _ptr(lb), _ptr(sq), _ptr(picks), C.byref(e2), C.byref(delta)), "mm_bound_state")
+        return {"lb": lb, "sq": sq, "picks": (int(picks[0]), int(picks[1])), "e2": e2.value, "delta": delta.value}
 
     def pick_minima(self, ref, tgt, angle, centre, skip_zero=True):
         """TEST HOOK (``mm_pick_minima``): squared row minima, squared column minima, screened squared value and e2 of one

@@ -1327,6 +1327,37 @@ int mm_lower_bounds(mm_engine* h, const double* rx, const double* ry, int nr, co
     return MM_OK;
 }
 
+// What the bound rounds of one search leave behind them, as plan.run(true) stops short of the shortlist: per candidate the
+// final bound (out_lb2: +inf where k_lb_spread ruled it out) and screened value (out_sq2: +inf for every candidate that did
+// not survive), both picks, e2 and delta.  A test hook for the claims of rounds 2 - 7; nothing in the product calls it.
+int mm_bound_state(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                   double cx, double cy, const double* angles, int n_angles, int flags, int matrix, float* out_lb2,
+                   float* out_sq2, int32_t* picks, double* e2, double* delta)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e || !rx || !ry || !tx || !ty || !angles || !out_lb2 || !out_sq2 || !picks || nr <= 0 || nt <= 0 || n_angles <= 0)
+        return set_error(MM_ERR_INVALID, "mm_bound_state: bad arguments");
+    MM_HIP(hipSetDevice(e->device));
+    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
+    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
+    ScreenOptions opts = e->screen_opts;
+    opts.bound_min_candidates = 0; opts.bound_matrix = matrix != 0;
+    Plan plan;
+    int rc = plan.stage_sets(e, sets, true);
+    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
+    if (rc) return rc;
+    if (!plan.use_lb || (matrix != 0) != (plan.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_bound_state: the bound kernel asked for does not take these sets");
+    if ((rc = plan.run(true))) return rc;
+    MM_HIP(hipMemcpyAsync(out_lb2, plan.dev.lb32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
+    MM_HIP(hipMemcpyAsync(out_sq2, plan.dev.sq32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
+    MM_HIP(hipMemcpyAsync(picks, plan.dev.pick_idx, 4, hipMemcpyDeviceToHost, plan.stream));                 // pick_idx[0]
+    MM_HIP(hipMemcpyAsync(picks + 1, plan.dev.pick_idx + plan.P, 4, hipMemcpyDeviceToHost, plan.stream));    // pick_idx[P]
+    MM_HIP(hipStreamSynchronize(plan.stream));
+    if (e2) *e2 = plan.host_pairs[0].e2;
+    if (delta) *delta = plan.host_pairs[0].delta;
+    return MM_OK;
+}
+
 int mm_pick_minima(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                    double cx, double cy, double angle, int flags, float* row_min2, float* col_min2, float* value2, double* e2)
 {

@@ -18,68 +18,21 @@ import os
 import numpy as np
 import pytest
 
+from mx_worst_cases import angles_far_from_unit_norm, cases
+
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _angles_far_from_unit_norm(n=96):
-    a = np.linspace(-np.pi, np.pi, 200001)[:-1]
-    c, s = np.cos(a).astype(np.float32).astype(np.float64), np.sin(a).astype(np.float32).astype(np.float64)
-    dev = np.abs(c * c + s * s - 1.0)
-    pick = np.argsort(dev)[-n:]
-    return np.sort(a[pick])
-
-
-def _on_ties(rng, n, rmax, jitter):
-    """n points on a rough circle of radius <= rmax (scaled units): both coordinates snapped to f16 ties at their own
-    magnitude (spacing of f16 at |v|: 2^(floor(log2 |v|) - 10); a tie is an odd multiple of half of it), then moved by
-    `jitter` f32 ulps."""
-    t = np.sort(rng.uniform(0, 2 * np.pi, n))
-    r = rmax * (1.0 - 0.3 * rng.uniform(0, 1, n) ** 4)
-    p = np.stack([r * np.cos(t), r * np.sin(t)], axis=1)
-    mag = np.maximum(np.abs(p), 2.0 ** -10)
-    sp = 2.0 ** (np.floor(np.log2(mag)) - 10)
-    q = (np.floor(p / sp) + 0.5) * sp                                   # odd multiples of sp / 2: exactly between two f16 values
-    ulp32 = 2.0 ** (np.floor(np.log2(np.maximum(np.abs(q), 2.0 ** -100))) - 23)
-    q = q + jitter * ulp32
-    # keep inside the radius
-    nr = np.hypot(q[:, 0], q[:, 1])
-    q[nr > rmax] *= (rmax / nr[nr > rmax])[:, None] * (1 - 1e-7)
-    return q
-
-
-def _cases(rng):
-    """(name, ref, tgt) in scaled units around the centre (0, 0)."""
-    out = []
-    for n in (64, 223, 449, 544, 600):
-        for rmax in (511.9, 300.0, 256.01):
-            for jit in (-1, 0, 1):
-                out.append((f"ties n={n} r={rmax} jitter={jit}", _on_ties(rng, n, rmax, jit), _on_ties(rng, n, rmax, jit)))
-        # tgt = ref moved by a fraction of the f16 spacing: tiny true distances out of large coordinates (cancellation)
-        a = _on_ties(rng, n, 511.9, 0)
-        out.append((f"near-identical n={n}", a, a + rng.choice([-0.0625, 0.0625, 0.03125], size=a.shape)))
-        # one far outlier fixes rho; everything else tiny (lo pieces below f16's normal range after scaling)
-        small = rng.normal(0, 2.0 ** -9, (n, 2))
-        far = small.copy(); far[0] = (500.0, -100.0)
-        out.append((f"outlier-in-ref n={n}", far, small + 2.0 ** -11))
-        out.append((f"outlier-in-tgt n={n}", small + 2.0 ** -11, far))
-        # one pair decides: a ring of reference points, the targets ON them except one pushed out radially
-        ring = _on_ties(rng, n, 511.9, 0)
-        tg = ring.copy()
-        tg[n // 2] *= 0.75
-        out.append((f"single-deciding-pair n={n}", ring, tg))
-    return out
-
-
 @pytest.mark.parametrize("scale", [1.0, 2.0 ** -7, 3.0e4])
 def test_directed_search_for_the_largest_split_error(engine, oracle, mm, scale):
     rng = np.random.default_rng(20240)
-    angles = np.concatenate([_angles_far_from_unit_norm(), np.linspace(-np.pi, np.pi, 33)[:-1], [0.0]])
+    angles = np.concatenate([angles_far_from_unit_norm(), np.linspace(-np.pi, np.pi, 33)[:-1], [0.0]])
     angles = np.sort(angles)
     worst = {"frac_of_e2": 0.0, "interval_use": 0.0}
     n_checked = 0
-    for name, ref, tgt in _cases(rng):
+    for name, ref, tgt in cases(rng):
         ref, tgt = ref * scale, tgt * scale                    # a power of two (or not): the kernel rescales to [256, 512)
         before = engine.screen_stats()
         bi, ba, bc, costs = engine.best_rotation(ref, tgt, angles, (0.0, 0.0), skip_zero=True,
