@@ -35,7 +35,8 @@
  * counts as mm_clean_outlier_points; the bookkeeping on adjacency graphs is host C++.  The vessel discretisation's
  * nearest-anchor assignment and plane projection run on the device in exact f64 (mm_slice_kernels.hip); its anchors
  * and spline resampling are host f64.  The mesh morphing's nearest-centerline search and radial move run on the device
- * in exact f64 (mm_morph_kernels.hip).
+ * in exact f64 (mm_morph_kernels.hip).  The mesh trimming's face membership, open-edge counting and compaction run on the
+ * device (mm_trim_kernels.hip); its ring logic on the rim is host C++.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -185,6 +186,52 @@ int64_t mm_match_points(const double* keys_xyz, int64_t nk, const double* querie
  * never in the subset (as in the reference); a negative one is MM_ERR_INVALID. */
 int64_t mm_keep_largest_component(const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
                                   const double* pts_xyz, int64_t n, int64_t* keep);
+
+/* ---- mesh trimming (multimodars/ccta/boundary.py:26-325, stitching.py:110-352, __init__.py:341-373) --------------- */
+
+/* Faces are nf int64 index triples into nv vertices.  A face index outside [0, nv), a negative count, or nv or nf at 2^31
+ * or above is MM_ERR_INVALID (device indices are int32).  Rings follow a fixed walk rule where the reference follows
+ * CPython's set order: rings are discovered in increasing order of their smallest remaining vertex and start at it; from
+ * every vertex the walk goes to the smallest neighbour that is not the previous vertex and still remains; length ties
+ * keep discovery order.  target_n -1 reports every ring (the reference's None); 0 or below -1 is MM_ERR_INVALID. */
+
+/* build_adjacency_map (_processing.py:1476-1505, ccta_py.rs:507-525), host: off (nv + 1 entries) and nb (capacity 6 nf)
+ * receive the sorted, de-duplicated neighbour lists in CSR form (a repeated corner makes a vertex its own neighbour). */
+int     mm_build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, int64_t* off, int64_t* nb);
+/* The rim logic on an open-edge list (ne (a, b) pairs), host only: the rim graph (_boundary_graph), the components
+ * touching the seeds (_rims_touching; every component when ns == 0), the walk, and
+ *   clean == 0: _reduce_rings of the walk to target_n (order_boundary_rings);
+ *   clean == 1: one round of clean_open_boundary: rim = the vertices of the rims touching the seeds (none: no rings);
+ *               drop = those of degree != 2, else the _despike_ring spikes (despike_cos); else the reduced rings.
+ * counts[4] = {rings, ring vertices, drop, rim}; rings go back to back into ring_idx, their lengths into ring_len; drop
+ * and rim are ascending (read only with clean).  ring_len, ring_idx, drop and rim hold 2 ne entries each. */
+int     mm_boundary_rings(const int64_t* edges, int64_t ne, const int64_t* seeds, int64_t ns, const double* vertices_xyz,
+                          int64_t nv, int64_t target_n, double despike_cos, int clean, int64_t* ring_len,
+                          int64_t* ring_idx, int64_t* drop, int64_t* rim, int64_t* counts);
+/* open_boundary_edges (boundary.py:26-43) on the device: the edges used by exactly one face, as (smaller, larger) pairs
+ * in lexicographic order, into edges (capacity 3 nf pairs).  Returns their number. */
+int64_t mm_open_boundary_edges(mm_engine* e, const int64_t* faces, int64_t nf, int64_t nv, int64_t* edges);
+/* clean_open_boundary (boundary.py:257-325): every round re-derives the faces without the dropped vertices and their
+ * open edges on the device, then runs the clean round of mm_boundary_rings, growing the seeds by the rim; after
+ * max_rounds the rim is ordered as it stands.  drop (capacity nv) receives the culled vertices, ascending; rings as in
+ * mm_boundary_rings (capacity nv each).  counts[3] = {rings, ring vertices, drop}. */
+int     mm_clean_open_boundary(mm_engine* e, const int64_t* faces, int64_t nf, const double* vertices_xyz, int64_t nv,
+                               const int64_t* seeds, int64_t ns, int64_t target_n, double despike_cos,
+                               int64_t max_rounds, int64_t* drop, int64_t* ring_len, int64_t* ring_idx, int64_t* counts);
+/* One trim of a mesh on the device, from one upload of the mesh to one download of the result.  region[v] = 1 marks the
+ * vertices of the region.
+ *   mode 0 (remove_labeled_points_from_mesh, stitching.py:110-240): the vertices outside the region are kept;
+ *   mode 1 (keep_labeled_points_from_mesh, :243-352): the vertices of the region are kept;
+ *       both: a face survives with all three corners kept; the kept corners of the other faces seed the rim, which
+ *       clean_open_boundary(target_n, despike_cos, max_rounds) cleans; the vertices it culls go too;
+ *   mode 2 (_extract_region_with_border_faces, __init__.py:341-373): the faces with a corner in the region and the
+ *       vertices they use.
+ * out_vertices (capacity nv) and out_faces (capacity nf, remapped to the compacted order) receive the kept vertices and
+ * faces in their original order; rings (modes 0 and 1; old vertex indices; capacity nv each) as in mm_boundary_rings.
+ * counts[4] = {vertices, faces, rings, ring vertices}. */
+int     mm_trim_mesh(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                     const uint8_t* region, int mode, int64_t target_n, double despike_cos, int64_t max_rounds,
+                     double* out_vertices, int64_t* out_faces, int64_t* ring_len, int64_t* ring_idx, int64_t* counts);
 
 #ifdef __cplusplus
 }

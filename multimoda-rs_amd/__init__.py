@@ -29,7 +29,9 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    find_centerline_bounded_points_simple, find_distal_and_proximal_scaling, find_faces_near_points,
                    find_points_by_cl_region, find_proximal_distal_scaling, keep_largest_connected_component,
                    label_anomalous_region, label_geometry, remove_occluded_points_ray_triangle, scale,
-                   scale_region_centerline_morphing, sync_results_to_mesh)
+                   scale_region_centerline_morphing, sync_results_to_mesh, open_boundary_edges, order_boundary_rings,
+                   clean_open_boundary, remove_labeled_points_from_mesh, keep_labeled_points_from_mesh,
+                   extract_region_with_border_faces, export_section_stl, build_adjacency_map)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -58,7 +60,9 @@ __all__ = [
     "find_aortic_points", "final_reclassification", "label_geometry",
     "discretize_vessel", "discretize_vessel_tree", "DiscretizedVesselTree",
     "keep_largest_connected_component", "label_anomalous_region", "scale_region_centerline_morphing",
-    "sync_results_to_mesh", "scale",
+    "sync_results_to_mesh", "scale", "open_boundary_edges", "order_boundary_rings", "clean_open_boundary",
+    "remove_labeled_points_from_mesh", "keep_labeled_points_from_mesh", "extract_region_with_border_faces",
+    "export_section_stl", "build_adjacency_map",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

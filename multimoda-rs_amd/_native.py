@@ -105,6 +105,7 @@ EXPORTS_CCTA = [
     "mm_final_reclassification",
     "mm_slice_anchor_count", "mm_nearest_anchor_project", "mm_resample_closed_contour", "mm_discretize_vessel_batch",
     "mm_centerline_morph_batch", "mm_match_points", "mm_keep_largest_component",
+    "mm_build_adjacency", "mm_boundary_rings", "mm_open_boundary_edges", "mm_clean_open_boundary", "mm_trim_mesh",
 ]
 
 
@@ -450,6 +451,16 @@ def lib():
     L.mm_match_points.argtypes = [P, I64, P, I64, P]
     L.mm_keep_largest_component.restype = I64
     L.mm_keep_largest_component.argtypes = [P, I64, P, I64, P, I64, P]
+    L.mm_build_adjacency.restype = I
+    L.mm_build_adjacency.argtypes = [P, I64, I64, P, P]
+    L.mm_boundary_rings.restype = I
+    L.mm_boundary_rings.argtypes = [P, I64, P, I64, P, I64, I64, D, I, P, P, P, P, P]
+    L.mm_open_boundary_edges.restype = I64
+    L.mm_open_boundary_edges.argtypes = [P, P, I64, I64, P]
+    L.mm_clean_open_boundary.restype = I
+    L.mm_clean_open_boundary.argtypes = [P, P, I64, P, I64, P, I64, I64, D, I64, P, P, P, P]
+    L.mm_trim_mesh.restype = I
+    L.mm_trim_mesh.argtypes = [P, P, I64, P, I64, P, I, I64, D, I64, P, P, P, P, P]
     _lib = L
     return L
 

@@ -733,3 +733,276 @@ def scale(results: dict, cl_vessel: Centerline, cl_aorta: Centerline, aligned_fr
     results = sync_results_to_mesh(results, results["mesh"], m)
     m = scale_region_centerline_morphing(results["mesh"], results["proximal_points"], cl_vessel, prox_scaling, engine)
     return sync_results_to_mesh(results, results["mesh"], m)
+
+
+# ---- mesh trimming (multimodars/ccta/boundary.py, stitching.py:18-352, __init__.py:341-429) -------------------------
+
+TRIM_KEYS = ("aorta_points", "rca_points", "lca_points", "rca_removed_points", "lca_removed_points", "proximal_points",
+             "distal_points")
+BOUNDARY_RING_PREFIX = "boundary_points_"
+
+
+def _checked_faces(faces, nv: int) -> np.ndarray:
+    f = _faces3(faces)
+    if f.size and (f.min() < 0 or f.max() >= nv):
+        raise ValueError(f"face index out of range [0, {nv})")
+    return f
+
+
+def _target(target_n) -> int:
+    if target_n is None:
+        return -1
+    if int(target_n) < 1:
+        raise ValueError("target_n must be at least 1 (or None)")
+    return int(target_n)
+
+
+def _rings(ring_len: np.ndarray, ring_idx: np.ndarray, n_rings: int) -> list:
+    ends = np.cumsum(ring_len[:n_rings])
+    return [ring_idx[e - n:e].copy() for n, e in zip(ring_len[:n_rings], ends)]
+
+
+def build_adjacency_map(faces) -> dict:
+    """_processing.py:1476-1505 / ccta_py.rs:507-525: every vertex of ``faces`` -> the set of vertices it shares an edge
+    with (host, the labelling's adjacency builder).  ``build_adjacency_map([[0, 1, 2], [1, 2, 3]])[1] == {0, 2, 3}``."""
+    f = _faces3(faces)
+    if f.size == 0:
+        return {}
+    if f.min() < 0:
+        raise ValueError("negative face index")
+    nv = int(f.max()) + 1
+    off = np.zeros(nv + 1, dtype=np.int64)
+    nb = np.zeros(6 * f.shape[0], dtype=np.int64)
+    N.check(N.lib().mm_build_adjacency(N._ptr(f), f.shape[0], nv, N._ptr(off), N._ptr(nb)), "build_adjacency_map")
+    return {v: set(nb[off[v]:off[v + 1]].tolist()) for v in range(nv) if off[v + 1] > off[v]}
+
+
+def open_boundary_edges(faces, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """boundary.py:26-43: the edges used by exactly one face, each as (smaller, larger), in lexicographic order (as
+    ``np.unique(axis=0)`` gives them), ``(E, 2)`` int64.  A degenerate face's ``(v, v)`` edge counts like any other.
+    The edges are counted on the device (csrc/mm_trim_kernels.hip)."""
+    f = _faces3(faces)
+    if f.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if f.min() < 0:
+        raise ValueError("negative face index")
+    out = np.zeros((3 * f.shape[0], 2), dtype=np.int64)
+    k = N.lib().mm_open_boundary_edges(_engine(engine).handle, N._ptr(f), f.shape[0], int(f.max()) + 1, N._ptr(out))
+    if k < 0:
+        N.check(int(k), "open_boundary_edges")
+    return out[:k].copy()
+
+
+def boundary_rings_from_edges(edges, vertices, seeds=None, target_n=None, despike_cos: float = 0.0,
+                              clean: bool = False):
+    """The host rim logic on an open-edge list (no device): the rim graph, the rims touching ``seeds`` (all without
+    seeds), the walk (DESIGN §4.11 for its fixed rule) and, without ``clean``, the reduction to ``target_n`` rings
+    (order_boundary_rings).  With ``clean``, one round of clean_open_boundary.  Returns (rings, drop, rim): the rim
+    vertices touching the seeds and the vertices that round culls (ascending); rings only where nothing is culled."""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int64).reshape(-1, 2))
+    v = _p3(vertices)
+    s = np.ascontiguousarray(np.asarray(sorted(seeds) if seeds is not None else [], dtype=np.int64))
+    cap = 2 * e.shape[0] + 1
+    ring_len, ring_idx, drop, rim = (np.zeros(cap, dtype=np.int64) for _ in range(4))
+    counts = np.zeros(4, dtype=np.int64)
+    rc = N.lib().mm_boundary_rings(N._ptr(e), e.shape[0], N._ptr(s), s.shape[0], N._ptr(v), v.shape[0],
+                                   _target(target_n), float(despike_cos), int(bool(clean)), N._ptr(ring_len),
+                                   N._ptr(ring_idx), N._ptr(drop), N._ptr(rim), N._ptr(counts))
+    if rc == -2 and e.size and (e.min() < 0 or e.max() >= v.shape[0]):
+        raise ValueError("edge end out of range")
+    N.check(rc, "boundary_rings_from_edges")
+    return _rings(ring_len, ring_idx, int(counts[0])), drop[:counts[2]].copy(), rim[:counts[3]].copy()
+
+
+def order_boundary_rings(faces, vertices, seeds=None, target_n=None, engine: Optional[N.Engine] = None) -> list:
+    """boundary.py:223-254: the open boundary of ``faces`` ordered into rings (int64 vertex index arrays, largest
+    first) without touching the mesh; only the rims holding one of ``seeds`` when given; reduced to ``target_n`` rings
+    by joining nearest endpoints when given.  The reference's set-order walk is replaced by a fixed rule (DESIGN
+    §4.11)."""
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    edges = open_boundary_edges(f, engine) if f.size else np.zeros((0, 2), dtype=np.int64)
+    return boundary_rings_from_edges(edges, v, seeds, target_n)[0]
+
+
+def clean_open_boundary(faces, vertices, seeds, target_n=1, despike_cos: float = 0.0, max_rounds: int = 64,
+                        engine: Optional[N.Engine] = None):
+    """boundary.py:257-325: cull the rim vertices of ``faces`` that cannot form a clean ring (degree != 2, then the
+    bump spikes above ``despike_cos``), round by round, each round re-deriving the surviving faces and their open edges
+    on the device.  Returns (drop, rings): the culled vertices as a sorted int64 array and the rings (int64 arrays,
+    largest first, reduced to ``target_n``)."""
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    s = np.ascontiguousarray(np.asarray(sorted(seeds) if seeds is not None else [], dtype=np.int64))
+    nv = v.shape[0]
+    drop, ring_len, ring_idx = (np.zeros(nv + 1, dtype=np.int64) for _ in range(3))
+    counts = np.zeros(3, dtype=np.int64)
+    N.check(N.lib().mm_clean_open_boundary(_engine(engine).handle, N._ptr(f), f.shape[0], N._ptr(v), nv, N._ptr(s),
+                                           s.shape[0], _target(target_n), float(despike_cos), int(max_rounds),
+                                           N._ptr(drop), N._ptr(ring_len), N._ptr(ring_idx), N._ptr(counts)),
+            "clean_open_boundary")
+    return drop[:counts[2]].copy(), _rings(ring_len, ring_idx, int(counts[0]))
+
+
+def _with_mesh(mesh, vertices: np.ndarray, faces: np.ndarray):
+    """A mesh of the kind given with new vertices and faces (see _with_vertices)."""
+    if not (hasattr(mesh, "vertices") and hasattr(mesh, "faces")):
+        return (vertices, faces)
+    m = mesh.copy() if callable(getattr(mesh, "copy", None)) else copy.copy(mesh)
+    m.vertices = vertices
+    m.faces = faces
+    return m
+
+
+def _trim(v: np.ndarray, f: np.ndarray, region: np.ndarray, mode: int, target_n, engine):
+    """mm_trim_mesh: (kept vertices, remapped kept faces, rings in the old vertex indices)."""
+    nv, nf = v.shape[0], f.shape[0]
+    out_v = np.zeros((nv, 3), dtype=np.float64)
+    out_f = np.zeros((nf, 3), dtype=np.int64)
+    ring_len, ring_idx = np.zeros(nv + 1, dtype=np.int64), np.zeros(nv + 1, dtype=np.int64)
+    counts = np.zeros(4, dtype=np.int64)
+    N.check(N.lib().mm_trim_mesh(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), nf, N._ptr(region), mode,
+                                 _target(target_n) if mode != 2 else 1, 0.0, 64, N._ptr(out_v), N._ptr(out_f),
+                                 N._ptr(ring_len), N._ptr(ring_idx), N._ptr(counts)), "trim_mesh")
+    return out_v[:counts[0]].copy(), out_f[:counts[1]].copy(), _rings(ring_len, ring_idx, int(counts[2]))
+
+
+def _store_boundary_rings(updated: dict, vertices: np.ndarray, rings: list) -> None:
+    """stitching.py:18-37: stale ``boundary_points_*`` keys go, then ``boundary_points_1..k`` (one ring each, walk
+    order) and the flat ``boundary_points``."""
+    for key in [k for k in updated if k.startswith(BOUNDARY_RING_PREFIX)]:
+        del updated[key]
+    per_ring = [vertices[r] for r in rings]
+    for n, pts in enumerate(per_ring, start=1):
+        updated[f"{BOUNDARY_RING_PREFIX}{n}"] = pts
+    updated["boundary_points"] = np.concatenate(per_ring) if per_ring else np.zeros((0, 3), dtype=np.float64)
+
+
+def _region_points(results: dict, keys) -> np.ndarray:
+    parts = [_p3(results.get(k, ())) for k in keys]
+    return np.concatenate(parts) if parts else np.zeros((0, 3), dtype=np.float64)
+
+
+def _trim_results(results: dict, keys: list, mode: int, target_boundaries, engine) -> Optional[dict]:
+    pts = _region_points(results, keys)
+    if pts.shape[0] == 0:
+        return None
+    vertices, faces = _mesh_parts(results["mesh"])
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    idx = _match(v, pts)
+    idx = idx[idx >= 0]
+    if idx.size == 0:
+        return None
+    region = np.zeros(v.shape[0], dtype=np.uint8)
+    region[idx] = 1
+    new_v, new_f, rings = _trim(v, f, region, mode, target_boundaries, engine)
+    updated = dict(results)
+    updated["mesh"] = _with_mesh(results["mesh"], new_v, new_f)
+    _store_boundary_rings(updated, v, rings)
+    return updated
+
+
+def _filter_to(points, vertices: np.ndarray) -> np.ndarray:
+    p = _p3(points)
+    return p[_match(vertices, p) >= 0].copy()
+
+
+def remove_labeled_points_from_mesh(results: dict, region_keys="anomalous_points", target_boundaries: int = 1,
+                                    engine: Optional[N.Engine] = None) -> dict:
+    """stitching.py:110-240: delete the mesh vertices equal by value to the points under ``region_keys`` (a key or a
+    list of keys) and every face touching them, clean the rim the cut leaves (clean_open_boundary seeded by the kept
+    vertices that shared a face with a removed one; the vertices it culls go too) and remap the faces.  Returns a new
+    dict: ``"mesh"`` the trimmed mesh (of the kind given), the region keys cleared to ``(0, 3)`` arrays, the rings in
+    ``"boundary_points_1"``, ``"boundary_points_2"``, ... and flat in ``"boundary_points"``, and TRIM_KEYS filtered to
+    the surviving vertices.  Nothing to remove, or nothing matching: ``results`` itself, unchanged.  Face membership,
+    open edges and compaction run on the device (csrc/mm_trim_kernels.hip)."""
+    keys = [region_keys] if isinstance(region_keys, str) else list(region_keys)
+    updated = _trim_results(results, keys, 0, target_boundaries, engine)
+    if updated is None:
+        return results
+    new_v = _p3(_mesh_parts(updated["mesh"])[0])
+    for key in keys:
+        updated[key] = np.zeros((0, 3), dtype=np.float64)
+    for key in TRIM_KEYS:
+        if key in updated and key not in keys:
+            updated[key] = _filter_to(updated[key], new_v)
+    return updated
+
+
+def keep_labeled_points_from_mesh(results: dict, region_key, target_boundaries: int = 1,
+                                  engine: Optional[N.Engine] = None) -> dict:
+    """stitching.py:243-352: keep only the mesh vertices equal by value to the points under ``region_key`` (a key or a
+    list of keys, their union) and the faces with all corners among them, clean the rim as
+    remove_labeled_points_from_mesh does and filter TRIM_KEYS and the region keys to the surviving vertices.  Nothing
+    to keep, or nothing matching: ``results`` itself, unchanged."""
+    keys = [region_key] if isinstance(region_key, str) else list(region_key)
+    updated = _trim_results(results, keys, 1, target_boundaries, engine)
+    if updated is None:
+        return results
+    new_v = _p3(_mesh_parts(updated["mesh"])[0])
+    for key in TRIM_KEYS + tuple(keys):
+        if key in updated:
+            updated[key] = _filter_to(updated[key], new_v)
+    return updated
+
+
+def extract_region_with_border_faces(mesh, region_points, engine: Optional[N.Engine] = None):
+    """__init__.py:341-373: the sub-mesh of every face with a corner equal by value to one of ``region_points``, with
+    the vertices those faces use (in vertex order) and the faces remapped.  No matching vertex: an empty mesh of the
+    kind given."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    idx = _match(v, region_points)
+    idx = idx[idx >= 0]
+    if idx.size == 0:
+        return _with_mesh(mesh, np.zeros((0, 3), dtype=np.float64), np.zeros((0, 3), dtype=np.int64))
+    region = np.zeros(v.shape[0], dtype=np.uint8)
+    region[idx] = 1
+    new_v, new_f, _ = _trim(v, f, region, 2, None, engine)
+    return _with_mesh(mesh, new_v, new_f)
+
+
+def write_stl(path, vertices, faces) -> None:
+    """A binary STL of the triangles: our own 80-byte header, float32 unit face normals (zero for a degenerate face,
+    computed in f64) and float32 vertices."""
+    v, f = _p3(vertices), _faces3(faces)
+    tri = v[f] if f.size else np.zeros((0, 3, 3), dtype=np.float64)
+    n = np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]) if f.size else np.zeros((0, 3))
+    length = np.sqrt((n * n).sum(axis=1)) if f.size else np.zeros(0)
+    unit = np.zeros_like(n)
+    ok = length > 0
+    unit[ok] = n[ok] / length[ok, None]
+    rec = np.zeros(f.shape[0], dtype=np.dtype([("n", "<f4", (3,)), ("v", "<f4", (3, 3)), ("attr", "<u2")]))
+    rec["n"] = unit
+    rec["v"] = tri
+    header = b"multimoda-rs_amd binary STL".ljust(80, b" ")
+    with open(path, "wb") as fh:
+        fh.write(header)
+        fh.write(np.uint32(f.shape[0]).tobytes())
+        fh.write(rec.tobytes())
+
+
+def export_section_stl(results: dict, type: str = "all", output_dir=None, engine: Optional[N.Engine] = None) -> str:
+    """__init__.py:376-429: write ``<type>.stl`` into ``output_dir`` (default: the working directory) as a binary STL
+    (write_stl): ``"all"`` the whole mesh, ``"aorta"`` the mesh keep_labeled_points_from_mesh leaves of
+    aorta_points, rca_removed_points and lca_removed_points, ``"rca"`` / ``"lca"`` extract_region_with_border_faces
+    of rca_points / lca_points.  Returns the path written."""
+    import os
+    out_dir = "." if output_dir is None else str(output_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    region_keys = {"aorta": "aorta_points", "rca": "rca_points", "lca": "lca_points"}
+    mesh = results["mesh"]
+    if type == "all":
+        sub = mesh
+    elif type == "aorta":
+        sub = keep_labeled_points_from_mesh(results, ["aorta_points", "rca_removed_points", "lca_removed_points"],
+                                            engine=engine)["mesh"]
+    elif type in region_keys:
+        sub = extract_region_with_border_faces(mesh, results.get(region_keys[type], ()), engine=engine)
+    else:
+        raise ValueError(f"Unknown export type {type!r}. Choose one of: 'all', 'aorta', 'rca', 'lca'.")
+    path = os.path.join(out_dir, f"{type}.stl")
+    write_stl(path, *_mesh_parts(sub))
+    return path

@@ -187,6 +187,22 @@ int        morph_block_points();
 hipError_t launch_contour_measures(const void* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
                                    double* val, int64_t* idx, hipStream_t s);
 size_t     shape_job_bytes();
+// mesh trimming (mm_trim_kernels.hip): face = int32 triples, masks uint8 0 / 1.  trim_faces: fkeep per face (all corners
+// in `in`, or with any_mode some corner) and the corner marks (nullable); trim_open_edges: the edge keys (min << 32 | max)
+// used by exactly one kept face into out (capacity 3 nf), their number in *n_out, through a table of 2^log2_cap slots
+// (keys 8 B + counts 4 B each, cleared here; at least twice the insertions); trim_scan: idx[i] = exclusive prefix of the
+// nonzero flags (-1 at a zero), tile_sum (trim_scan_tiles(n) + 1 entries) ends with the total; trim_compact: the kept
+// vertices gathered and the kept faces remapped; trim_clear: mask[idx[i]] = 0
+hipError_t launch_trim_faces(const int32_t* face, long long nf, const uint8_t* in, int any_mode, uint8_t* fkeep,
+                             uint8_t* mark, hipStream_t s);
+hipError_t launch_trim_open_edges(const int32_t* face, long long nf, const uint8_t* fkeep, unsigned long long* keys,
+                                  unsigned int* cnt, int log2_cap, unsigned long long* out, unsigned long long* n_out,
+                                  hipStream_t s);
+size_t     trim_scan_tiles(long long n);
+hipError_t launch_trim_scan(const uint8_t* flag, long long n, long long* tile_sum, int32_t* idx, hipStream_t s);
+hipError_t launch_trim_compact(const double* v, long long nv, const int32_t* vidx, const int32_t* face, long long nf,
+                               const int32_t* fidx, double* out_v, int32_t* out_f, hipStream_t s);
+hipError_t launch_trim_clear(const int32_t* idx, long long n, uint8_t* mask, hipStream_t s);
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers
