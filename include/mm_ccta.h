@@ -55,6 +55,21 @@ extern "C" {
 int     mm_nn_min_sq_batch(mm_engine* e, int n_sets, const int64_t* set_off, const double* xyz,
                            int n_pairs, const int32_t* q_set, const int32_t* p_set,
                            const int64_t* out_off, double* out);
+/* TEST HOOK (nothing in the product calls it; no engine, no device): the host side of one nearest-neighbour batch
+ * (mm_nn_min_sq_batch, the scaling searches) and of one radius count (mm_clean_outlier_points), as their launch paths build
+ * it.  Sets: n_sets CSR ranges of xyz triples; a set with derived[s] != 0 (derived nullable) is its base points moved by
+ * adj[s] along unit (triples) where has (one flag per point) is set, as the scaling searches' morphed copies.
+ * order_like (nullable, one entry per set): the set whose staging order this one shares.  Pairs: q_set[k] / p_set[k].
+ * perm (one entry per point, by set_off): staged position j of set s holds its original point perm[set_off[s] + j]
+ * (the identity where a set is staged as given).  items (5 int32 each: list 0 = pass A of k_nn3_min, 1 = pass B,
+ * 2 = k_nn3_count for the squared radius r2; caller's pair; first staged query q0; first point c0; chunks) and item_lb2
+ * (the item's lower bound of the squared distance between its queries' and points' boxes) receive at most cap items,
+ * lists in that order.  info[6] = {items of pass A, of pass B, of the count, queries per block, points per chunk,
+ * chunks per unpruned item}. */
+int     mm_nn_plan(int n_sets, const int64_t* set_off, const double* xyz, const double* unit, const uint8_t* has,
+                   const uint8_t* derived, const double* adj, const int32_t* order_like, int n_pairs, const int32_t* q_set,
+                   const int32_t* p_set, double r2, int32_t* perm, int64_t* info, int32_t* items, double* item_lb2,
+                   int64_t cap);
 /* symmetric_nn_distance (:188-216); +inf if either set is empty */
 int     mm_symmetric_nn_distance(mm_engine* e, const double* a_xyz, int64_t na, const double* b_xyz, int64_t nb,
                                  double* out);

@@ -135,6 +135,9 @@ int  mm_engine_profile_launches(mm_engine* e, int64_t cap, float* ms, double* pa
  * out[3] in the third (decisive-point) round, out[4] candidates that went through the full f32
  * screen (the two per-pair picks not counted). */
 int  mm_engine_bound_stats(mm_engine* e, int64_t out[5]);
+/* The winner-only selection of refine_alignment_hausdorff since the engine was created: out[0] pairs offered, out[1]
+ * pairs evaluated exactly (the others were ruled out by their lower bounds). */
+int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
 /* Which kernel screened how many candidates since the engine was created (brute-force levels; the bounded search's
  * rounds are in mm_engine_bound_stats): out[0] direct-form f32, out[1] packed-FMA (expanded form), out[2] matrix pipe with
  * the whole target set per wave (64 .. 544 points), out[3] matrix pipe with the target set in column blocks (545 .. 2048
@@ -215,6 +218,18 @@ int mm_hausdorff_batch(mm_engine* e, int n_pairs,
                        const int64_t* a_off, const double* ax, const double* ay,
                        const int64_t* b_off, const double* bx, const double* by,
                        double* out, int32_t* first_min);
+
+/* TEST HOOK (nothing in the product calls it): the winner-only selection refine_alignment_hausdorff runs when it does not
+ * return every cost, on mm_hausdorff_batch's pairs.  *best / *best_cost: the first strict minimum over the pairs (-1 / +inf
+ * if n_pairs == 0); *n_exact: how many pairs were evaluated exactly.  *pruned != 0 where lower bounds ruled pairs out (at
+ * least 8 pairs, every set beyond the LDS kernel's 4080 points): bound[p] is then pair p's lower bound (every 16th point
+ * of either set against all of the other), *pick the pair with the smallest bound and *ub its exact cost; otherwise bound[]
+ * is NaN, *pick -1 and *ub NaN.  exact[p] = 1 for every pair evaluated exactly. */
+int mm_hausdorff_first_min_state(mm_engine* e, int n_pairs,
+                                 const int64_t* a_off, const double* ax, const double* ay,
+                                 const int64_t* b_off, const double* bx, const double* by,
+                                 int32_t* pruned, double* bound, int32_t* pick, double* ub, uint8_t* exact,
+                                 int32_t* best, double* best_cost, int64_t* n_exact);
 
 /* Host helpers of refine_alignment_hausdorff (align_algorithms.rs:339-451), exact:
  *   mm_refine_angles            `angle = init - range; while angle <= init + range { ..; angle += step }`

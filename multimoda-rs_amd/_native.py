@@ -28,8 +28,8 @@ MM_SEARCH_SKIP_ZERO = 1
 EXPORTS = [
     "mm_device_count", "mm_last_error", "mm_version",
     "mm_engine_create", "mm_engine_destroy", "mm_engine_synchronize", "mm_engine_stream", "mm_engine_wait_search",
-    "mm_engine_profile", "mm_engine_profile_read", "mm_engine_profile_launches", "mm_engine_bound_stats", "mm_engine_screen_stats", "mm_engine_set_bound_matrix", "mm_lower_bounds", "mm_pick_minima",
-    "mm_bound_state",
+    "mm_engine_profile", "mm_engine_profile_read", "mm_engine_profile_launches", "mm_engine_bound_stats", "mm_engine_first_min_stats", "mm_engine_screen_stats", "mm_engine_set_bound_matrix", "mm_lower_bounds", "mm_pick_minima",
+    "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
@@ -98,7 +98,7 @@ class MMFlatGeometry(C.Structure):
 
 # include/mm_ccta.h
 EXPORTS_CCTA = [
-    "mm_nn_min_sq_batch", "mm_symmetric_nn_distance", "mm_diameter_morphing", "mm_find_region_points",
+    "mm_nn_min_sq_batch", "mm_nn_plan", "mm_symmetric_nn_distance", "mm_diameter_morphing", "mm_find_region_points",
     "mm_aortic_diameter_optimization", "mm_diameter_optimization", "mm_wall_diameter_optimization",
     "mm_clean_outlier_points", "mm_find_points_by_cl_region",
     "mm_centerline_bounded_points", "mm_faces_near_points", "mm_occluded_points", "mm_find_aortic_points",
@@ -211,6 +211,8 @@ def lib():
     L.mm_engine_profile_launches.argtypes = [P, I64, P, P, C.POINTER(I64)]
     L.mm_engine_bound_stats.restype = I
     L.mm_engine_bound_stats.argtypes = [P, P]
+    L.mm_engine_first_min_stats.restype = I
+    L.mm_engine_first_min_stats.argtypes = [P, P]
     L.mm_pick_minima.restype = I
     L.mm_pick_minima.argtypes = [P, P, P, I, P, P, I, D, D, D, I, P, P, P, P]
     L.mm_lower_bounds.restype = I
@@ -237,6 +239,8 @@ def lib():
     L.mm_hausdorff_2d.argtypes = [P, P, P, I, P, P, I, C.POINTER(D)]
     L.mm_hausdorff_batch.restype = I
     L.mm_hausdorff_batch.argtypes = [P, I, P, P, P, P, P, P, P, C.POINTER(I32)]
+    L.mm_hausdorff_first_min_state.restype = I
+    L.mm_hausdorff_first_min_state.argtypes = [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P]
     L.mm_refine_angles.restype = I64
     L.mm_refine_angles.argtypes = [D, D, D, P, I64]
     L.mm_filter_points_in_region.restype = I64
@@ -411,6 +415,8 @@ def lib():
     # include/mm_ccta.h
     L.mm_nn_min_sq_batch.restype = I
     L.mm_nn_min_sq_batch.argtypes = [P, I, P, P, I, P, P, P, P]
+    L.mm_nn_plan.restype = I
+    L.mm_nn_plan.argtypes = [I, P, P, P, P, P, P, P, I, P, P, D, P, P, P, P, I64]
     L.mm_symmetric_nn_distance.restype = I
     L.mm_symmetric_nn_distance.argtypes = [P, P, I64, P, I64, C.POINTER(D)]
     L.mm_diameter_morphing.restype = I
@@ -791,6 +797,13 @@ class Engine:
         return {"offered": int(out[0]), "bounded_round1": int(out[1]), "bounded_round2": int(out[2]),
                 "bounded_round3": int(out[3]), "screened": int(out[4])}
 
+    def first_min_stats(self):
+        """The winner-only selection of refine_alignment_hausdorff since the engine was created: pairs offered and
+        pairs evaluated exactly (include/mm_hausdorff.h)."""
+        out = np.zeros(2, dtype=np.int64)
+        check(lib().mm_engine_first_min_stats(self._h, _ptr(out)), "mm_engine_first_min_stats")
+        return {"pairs": int(out[0]), "exact": int(out[1])}
+
     def profile_read(self):
         n, ms, pe, ca = C.c_int64(0), C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
         check(lib().mm_engine_profile_read(self._h, C.byref(n), C.byref(ms), C.byref(pe), C.byref(ca)),
@@ -831,6 +844,35 @@ class Engine:
         check(lib().mm_hausdorff_batch(self._h, n, _ptr(ao), _ptr(ax), _ptr(ay), _ptr(bo), _ptr(bx), _ptr(by),
                                        _ptr(out), C.byref(fm)), "mm_hausdorff_batch")
         return out, int(fm.value)
+
+    def hausdorff_first_min_state(self, pairs):
+        """TEST HOOK (``mm_hausdorff_first_min_state``): the winner-only selection of refine_alignment_hausdorff on
+        `pairs` (as :meth:`hausdorff_batch`) and what it did: whether lower bounds ruled pairs out, every pair's bound
+        (NaN where they did not), the pick, its exact cost ub, which pairs were evaluated exactly, best, best_cost,
+        n_exact."""
+        n = len(pairs)
+        A = [_xy(a) for a, _ in pairs]
+        B = [_xy(b) for _, b in pairs]
+
+        def pack(sets):
+            off = np.zeros(n + 1, dtype=np.int64)
+            off[1:] = np.cumsum([s.shape[0] for s in sets])
+            x = np.concatenate([s[:, 0] for s in sets]) if n else np.zeros(0)
+            y = np.concatenate([s[:, 1] for s in sets]) if n else np.zeros(0)
+            return off, _f64(x), _f64(y)
+
+        ao, ax, ay = pack(A)
+        bo, bx, by = pack(B)
+        bound, exact = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint8)
+        pruned, pick, ub = C.c_int32(0), C.c_int32(-1), C.c_double(0.0)
+        best, best_cost, n_exact = C.c_int32(-1), C.c_double(0.0), C.c_int64(0)
+        check(lib().mm_hausdorff_first_min_state(self._h, n, _ptr(ao), _ptr(ax), _ptr(ay), _ptr(bo), _ptr(bx), _ptr(by),
+                                                 C.byref(pruned), _ptr(bound), C.byref(pick), C.byref(ub), _ptr(exact),
+                                                 C.byref(best), C.byref(best_cost), C.byref(n_exact)),
+              "mm_hausdorff_first_min_state")
+        return {"pruned": bool(pruned.value), "bound": bound, "pick": int(pick.value), "ub": ub.value,
+                "exact": exact.astype(bool), "best": int(best.value), "best_cost": best_cost.value,
+                "n_exact": int(n_exact.value)}
 
     # -- one search ------------------------------------------------------------------
     def best_rotation(self, ref, tgt, angles, centre, skip_zero=True, precision=MM_PRECISION_F32_MATRIX,

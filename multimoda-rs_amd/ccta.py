@@ -57,6 +57,49 @@ def nn_min_sq(a, b, engine: Optional[N.Engine] = None) -> np.ndarray:
     return out
 
 
+def nn_plan(sets, pairs, r2: float = 0.0, order_like=None) -> dict:
+    """TEST HOOK (``mm_nn_plan``; host only, no engine): the work lists the nearest-neighbour launches build.  `sets`: (N, 3)
+    arrays, or dicts {"xyz", "unit", "has", "adj"} for a set whose points are xyz moved by adj along unit where has;
+    `pairs`: (query set, point set).  Returns every set's staging permutation ("perm": staged position -> original
+    point), the items of pass A, pass B and the radius count for `r2` ("a", "b", "count": int arrays of (pair, q0, c0,
+    n_chunks), "a_lb2" / "b_lb2" / "count_lb2" their bounds), and the block geometry ("qpb", "chunk", "span")."""
+    xyz, unit, has, adj, derived, off = [], [], [], [], [], [0]
+    for s in sets:
+        d = s if isinstance(s, dict) else {"xyz": s}
+        x = _p3(d["xyz"])
+        xyz.append(x)
+        derived.append(1 if "unit" in d else 0)
+        unit.append(_p3(d["unit"]) if "unit" in d else np.zeros_like(x))
+        has.append(np.asarray(d["has"], dtype=np.uint8).reshape(-1) if "unit" in d else np.zeros(len(x), dtype=np.uint8))
+        adj.append(float(d.get("adj", 0.0)))
+        off.append(off[-1] + len(x))
+    xyz = np.ascontiguousarray(np.concatenate(xyz) if xyz else np.zeros((0, 3)))
+    unit = np.ascontiguousarray(np.concatenate(unit) if unit else np.zeros((0, 3)))
+    has = np.ascontiguousarray(np.concatenate(has) if has else np.zeros(0, dtype=np.uint8))
+    adj, derived = np.array(adj, dtype=np.float64), np.array(derived, dtype=np.uint8)
+    set_off = np.array(off, dtype=np.int64)
+    q = np.array([p[0] for p in pairs], dtype=np.int32)
+    p_ = np.array([p[1] for p in pairs], dtype=np.int32)
+    ol = None if order_like is None else np.ascontiguousarray(order_like, dtype=np.int32)
+    perm = np.zeros(max(int(set_off[-1]), 1), dtype=np.int32)
+    info = np.zeros(6, dtype=np.int64)
+    args = [len(sets), N._ptr(set_off), N._ptr(xyz), N._ptr(unit), N._ptr(has), N._ptr(derived), N._ptr(adj),
+            N._ptr(ol), len(pairs), N._ptr(q), N._ptr(p_), float(r2), N._ptr(perm), N._ptr(info)]
+    N.check(N.lib().mm_nn_plan(*args, None, None, 0), "nn_plan")
+    cap = int(info[:3].sum())
+    items, lb2 = np.zeros((max(cap, 1), 5), dtype=np.int32), np.zeros(max(cap, 1), dtype=np.float64)
+    N.check(N.lib().mm_nn_plan(*args, N._ptr(items), N._ptr(lb2), cap), "nn_plan")
+    out = {"perm": [perm[off[s]:off[s + 1]].copy() for s in range(len(sets))],
+           "qpb": int(info[3]), "chunk": int(info[4]), "span": int(info[5])}
+    k = 0
+    for l, name in enumerate(("a", "b", "count")):
+        n = int(info[l])
+        assert n == 0 or (items[k:k + n, 0] == l).all()
+        out[name], out[name + "_lb2"] = items[k:k + n, 1:].copy(), lb2[k:k + n].copy()
+        k += n
+    return out
+
+
 def symmetric_nn_distance(a, b, engine: Optional[N.Engine] = None) -> float:
     """scale_coronary.rs:188-216 (RMS of the two mean squared nearest-neighbour distances)."""
     a, b = _p3(a), _p3(b)

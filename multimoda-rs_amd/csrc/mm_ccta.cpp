@@ -79,6 +79,159 @@ void slab_order(const Set3& st, std::vector<int32_t>& perm)
     }
 }
 
+// The host side of a nearest-neighbour batch, shared by the launch paths (nn_batch_view, radius_counts) and the
+// host-only test hook mm_nn_plan: the staging order of every set, the point-pool layout, the device pairs, the bounding
+// box of every group of qpb staged points, and the (query block, chunk) work items of each pair.
+constexpr int64_t kSortMin = 4096;   // smaller sets: original order, every chunk scanned
+
+struct NnPlan {
+    int qpb = 0, ch = 0, span = 0;
+    std::vector<int64_t> soff;                 // point-pool offset of every set
+    std::vector<int32_t> perm_of;              // set -> its entry of perms (-1: staged in original order)
+    std::vector<std::vector<int32_t>> perms;   // slab orders, one per distinct base set
+    std::vector<int64_t> perm_off;             // offset of every entry of perms in the permutation pool
+    std::vector<NnPairH> hp;                   // device pairs: both sets non-empty
+    std::vector<int> owner;                    // device pair -> caller's pair
+    int64_t nout = 0;
+    std::vector<int64_t> goff;                 // first group of every set
+    std::vector<double> box;                   // lo xyz, hi xyz of every group (filled by nn_plan_stage_set)
+    int64_t npts() const { return soff.back(); }
+};
+
+// Validates the pairs, sorts the large sets and lays out the pools.  order_like (nullable, one entry per set): the
+// set whose spatial order this one shares -- a morphed copy of a set moves every point by at most a few mm, so the 41
+// scalings of a search reuse one sort.
+int nn_plan_pairs(const std::vector<Set3>& sets, const std::vector<std::array<int32_t, 2>>& pr,
+                  const std::vector<int32_t>* order_like, const char* what, NnPlan& pl)
+{
+    const size_t S = sets.size();
+    for (size_t k = 0; k < pr.size(); ++k)
+        if (pr[k][0] < 0 || pr[k][1] < 0 || (size_t)pr[k][0] >= S || (size_t)pr[k][1] >= S)
+            return set_error(MM_ERR_INVALID, std::string(what) + ": set index out of range");
+    pl.qpb = nn_queries_per_block(); pl.ch = nn_chunk_points(); pl.span = nn_span_chunks();
+    pl.soff.assign(S + 1, 0);
+    for (size_t s = 0; s < S; ++s) pl.soff[s + 1] = pl.soff[s] + sets[s].n;
+
+    // ---- spatial orders: one sort per distinct base set ---------------------------------------
+    std::vector<int32_t> base(S, -1);
+    std::vector<int32_t> bases;   // distinct sets that get sorted
+    for (size_t s = 0; s < S; ++s) {
+        if (sets[s].n < kSortMin) continue;
+        int32_t b = order_like ? (*order_like)[s] : (int32_t)s;
+        if (b < 0 || (size_t)b >= S || sets[(size_t)b].n != sets[s].n) b = (int32_t)s;
+        base[s] = b;
+        if (std::find(bases.begin(), bases.end(), b) == bases.end()) bases.push_back(b);
+    }
+    pl.perms.assign(bases.size(), {});
+    { TraceTimer tt("nn: slab order");
+    parallel_for((int)bases.size(), [&](int k) { slab_order(sets[(size_t)bases[(size_t)k]], pl.perms[(size_t)k]); });
+    }
+    pl.perm_off.assign(bases.size() + 1, 0);
+    for (size_t k = 0; k < bases.size(); ++k) pl.perm_off[k + 1] = pl.perm_off[k] + (int64_t)pl.perms[k].size();
+    pl.perm_of.assign(S, -1);
+    for (size_t s = 0; s < S; ++s)
+        if (base[s] >= 0) pl.perm_of[s] = (int32_t)(std::find(bases.begin(), bases.end(), base[s]) - bases.begin());
+
+    // ---- pairs ----------------------------------------------------------------------------------
+    pl.hp.clear(); pl.owner.clear(); pl.nout = 0;
+    for (size_t k = 0; k < pr.size(); ++k) {
+        const int32_t q = pr[k][0], p = pr[k][1];
+        const int64_t nq = sets[(size_t)q].n, np = sets[(size_t)p].n;
+        if (nq == 0 || np == 0) continue;
+        pl.hp.push_back(NnPairH{(int32_t)pl.soff[(size_t)q], (int32_t)nq, (int32_t)pl.soff[(size_t)p], (int32_t)np, (int32_t)pl.nout,
+                                pl.perm_of[(size_t)q] >= 0 ? (int32_t)pl.perm_off[(size_t)pl.perm_of[(size_t)q]] : -1});
+        pl.owner.push_back((int)k);
+        pl.nout += nq;
+    }
+    if (pl.npts() > (int64_t)1 << 30 || pl.nout > (int64_t)1 << 30)
+        return set_error(MM_ERR_TOO_LARGE, std::string(what) + ": batch exceeds 2^30 points");
+    pl.goff.assign(S + 1, 0);
+    for (size_t s = 0; s < S; ++s) pl.goff[s + 1] = pl.goff[s] + (sets[s].n + pl.qpb - 1) / pl.qpb;
+    pl.box.assign((size_t)pl.goff.back() * 6, 0.0);
+    return MM_OK;
+}
+
+// The boxes of set si's groups of qpb staged points; where dx != nullptr, also its staged coordinates (dx[j] = point
+// j in staged order).  Derived sets are boxed from Set3::at, the arithmetic k_nn3_morph repeats on the device.
+void nn_plan_stage_set(const std::vector<Set3>& sets, NnPlan& pl, size_t si, double* dx, double* dy, double* dz)
+{
+    const Set3& st = sets[si];
+    const int32_t* pm = pl.perm_of[si] >= 0 ? pl.perms[(size_t)pl.perm_of[si]].data() : nullptr;
+    for (int64_t g0 = 0, g = pl.goff[si]; g0 < st.n; g0 += pl.qpb, ++g) {
+        double* b = pl.box.data() + (size_t)g * 6;
+        b[0] = b[1] = b[2] = DBL_MAX; b[3] = b[4] = b[5] = -DBL_MAX;
+        for (int64_t j = g0; j < std::min<int64_t>(st.n, g0 + pl.qpb); ++j) {
+            const int64_t i = pm ? (int64_t)pm[j] : j;
+            const double v[3] = {st.at(i, 0), st.at(i, 1), st.at(i, 2)};
+            if (dx) { dx[j] = v[0]; dy[j] = v[1]; dz[j] = v[2]; }
+            for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], v[a]); b[3 + a] = std::max(b[3 + a], v[a]); }
+        }
+    }
+}
+
+// squared distance between two boxes, shaved so that rounding can never overstate it
+inline double box_lb2(const double* a, const double* b)
+{
+    double s = 0.0;
+    for (int ax = 0; ax < 3; ++ax) {
+        const double gap = std::max(0.0, std::max(a[ax] - b[3 + ax], b[ax] - a[3 + ax]));
+        s += gap * gap;
+    }
+    return s * (1.0 - 1e-12);
+}
+
+// lb2 of query block qb of set q against chunk c of set p: a chunk's box is the union of its groups', so the smallest
+// of their distances
+inline double chunk_lb2(const NnPlan& pl, int32_t q, int64_t qb, int32_t p, int64_t c, int gpc)
+{
+    const double* bq = pl.box.data() + (size_t)(pl.goff[(size_t)q] + qb) * 6;
+    double lb2 = DBL_MAX;
+    for (int64_t g = c * gpc; g < std::min<int64_t>((c + 1) * gpc, pl.goff[(size_t)p + 1] - pl.goff[(size_t)p]); ++g)
+        lb2 = std::min(lb2, box_lb2(bq, pl.box.data() + (size_t)(pl.goff[(size_t)p] + g) * 6));
+    return lb2;
+}
+
+// Device pair i's items of k_nn3_min: pass A (wa) runs for every query block the chunk with the smallest lb2, pass B
+// (wb) every other chunk with its lb2.  Pairs that are not both sorted, or that have at most 2 chunks, scan everything
+// in pass A, span chunks per item.
+void nn_plan_min_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2>>& pr, size_t i, std::vector<NnWorkH>& wa,
+                       std::vector<NnWorkH>& wb)
+{
+    const int qpb = pl.qpb, ch = pl.ch, gpc = ch / qpb;   // groups per chunk
+    const int32_t q = pr[(size_t)pl.owner[i]][0], p = pr[(size_t)pl.owner[i]][1];
+    const int64_t nq = pl.hp[i].nq, np = pl.hp[i].np;
+    const int64_t n_chunks = (np + ch - 1) / ch;
+    const bool prune = pl.perm_of[(size_t)q] >= 0 && pl.perm_of[(size_t)p] >= 0 && n_chunks > 2 && gpc >= 1 && ch % qpb == 0;
+    if (!prune) {
+        for (int64_t q0 = 0; q0 < nq; q0 += qpb)
+            for (int64_t c0 = 0; c0 < np; c0 += (int64_t)pl.span * ch)
+                wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)c0, pl.span, 0.0});
+        return;
+    }
+    std::vector<std::pair<double, int32_t>> cand((size_t)n_chunks);
+    for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb) {
+        for (int64_t c = 0; c < n_chunks; ++c) cand[(size_t)c] = {chunk_lb2(pl, q, qb, p, c, gpc), (int32_t)c};
+        std::sort(cand.begin(), cand.end());   // nearest chunks first: they tighten the minima the others check
+        wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[0].second * ch, 1, 0.0});
+        for (size_t c = 1; c < cand.size(); ++c)
+            wb.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[c].second * ch, 1, cand[c].first});
+    }
+}
+
+// Device pair i's items of k_nn3_count: the (query block, chunk) combinations whose boxes come within r2
+void nn_plan_count_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2>>& pr, size_t i, double r2,
+                         std::vector<NnWorkH>& w)
+{
+    const int qpb = pl.qpb, ch = pl.ch, gpc = std::max(1, ch / qpb);
+    const int32_t q = pr[(size_t)pl.owner[i]][0], p = pr[(size_t)pl.owner[i]][1];
+    const int64_t nq = pl.hp[i].nq, np = pl.hp[i].np, n_chunks = (np + ch - 1) / ch;
+    for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb)
+        for (int64_t c = 0; c < n_chunks; ++c) {
+            const double lb2 = chunk_lb2(pl, q, qb, p, c, gpc);
+            if (lb2 <= r2) w.push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)(c * ch), 1, lb2});
+        }
+}
+
 // Per-query minima of every pair (sets[q] against sets[p]); one upload, two launches, one download.
 // view[k] = {pointer, count}: pair k's minima, in the query set's ORIGINAL order, inside the engine's pinned
 // staging buffer (valid until the next call on this engine); pointer == nullptr means "all +inf" (an empty
@@ -99,50 +252,18 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     if (sums) sums->assign(pr.size(), NAN);
     view.assign(pr.size(), MinView{nullptr, 0});
     const size_t S = sets.size();
-    std::vector<int64_t> soff(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) soff[s + 1] = soff[s] + sets[s].n;
-    const int64_t npts = soff.back();
-    const int qpb = nn_queries_per_block(), ch = nn_chunk_points(), span = nn_span_chunks();
-    constexpr int64_t kSortMin = 4096;   // smaller sets: original order, every chunk scanned
-
-    // ---- spatial orders: one sort per distinct base set ---------------------------------------
-    std::vector<int32_t> base(S, -1), perm_of(S, -1);
-    std::vector<int32_t> bases;   // distinct sets that get sorted
-    for (size_t s = 0; s < S; ++s) {
-        if (sets[s].n < kSortMin) continue;
-        int32_t b = order_like ? (*order_like)[s] : (int32_t)s;
-        if (b < 0 || (size_t)b >= S || sets[(size_t)b].n != sets[s].n) b = (int32_t)s;
-        base[s] = b;
-        if (std::find(bases.begin(), bases.end(), b) == bases.end()) bases.push_back(b);
-    }
-    std::vector<std::vector<int32_t>> perms(bases.size());
     TraceTimer tt_all("nn: batch total");
-    { TraceTimer tt("nn: slab order");
-    parallel_for((int)bases.size(), [&](int k) { slab_order(sets[(size_t)bases[(size_t)k]], perms[(size_t)k]); });
-    }
-    std::vector<int64_t> perm_off(bases.size() + 1, 0);
-    for (size_t k = 0; k < bases.size(); ++k) perm_off[k + 1] = perm_off[k] + (int64_t)perms[k].size();
-    for (size_t s = 0; s < S; ++s)
-        if (base[s] >= 0) perm_of[s] = (int32_t)(std::find(bases.begin(), bases.end(), base[s]) - bases.begin());
-
-    // ---- pairs, and the groups (half chunks = one query block) whose boxes are needed -------------
-    std::vector<NnPairH> hp;
-    std::vector<int> owner;   // device pair -> caller's pair
-    int64_t nout = 0;
-    for (size_t k = 0; k < pr.size(); ++k) {
-        const int32_t q = pr[k][0], p = pr[k][1];
-        if (q < 0 || p < 0 || (size_t)q >= S || (size_t)p >= S)
-            return set_error(MM_ERR_INVALID, "nn batch: set index out of range");
-        const int64_t nq = sets[(size_t)q].n, np = sets[(size_t)p].n;
-        view[k].n = nq;                       // fold(INFINITY, min) over an empty set: all +inf
-        if (nq == 0 || np == 0) continue;
-        hp.push_back(NnPairH{(int32_t)soff[(size_t)q], (int32_t)nq, (int32_t)soff[(size_t)p], (int32_t)np, (int32_t)nout,
-                             perm_of[(size_t)q] >= 0 ? (int32_t)perm_off[(size_t)perm_of[(size_t)q]] : -1});
-        owner.push_back((int)k);
-        nout += nq;
-    }
-    if (hp.empty()) return MM_OK;
-    if (npts > (int64_t)1 << 30 || nout > (int64_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "nn batch exceeds 2^30 points");
+    NnPlan pl;
+    int rc = nn_plan_pairs(sets, pr, order_like, "nn batch", pl);
+    if (rc) return rc;
+    for (size_t k = 0; k < pr.size(); ++k) view[k].n = sets[(size_t)pr[k][0]].n;   // fold(INFINITY, min) over an empty set: all +inf
+    if (pl.hp.empty()) return MM_OK;
+    const std::vector<NnPairH>& hp = pl.hp;
+    const std::vector<int>& owner = pl.owner;
+    const std::vector<int64_t>& soff = pl.soff;
+    const std::vector<int32_t>& perm_of = pl.perm_of;
+    const std::vector<int64_t>& perm_off = pl.perm_off;
+    const int64_t npts = pl.npts(), nout = pl.nout;
 
     // ---- stage the points (permuted where sorted) and the bounding box of every group of qpb points ---
     // derived sets: only their boxes are computed here; their coordinates are produced on the device from
@@ -167,19 +288,15 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     const size_t o_perm = up256(o_z + (size_t)npts * 8), o_aux = up256(o_perm + (size_t)perm_off.back() * 4);
     const size_t o_morph = up256(o_aux + (size_t)naux * 7 * 8), o_pairs = up256(o_morph + morphs.size() * sizeof(NnMorphH));
     const size_t pts_bytes = o_pairs;   // the work lists follow once they are known
-    int rc = e->ensure(e->host_pts, pts_bytes, true);
-    if (rc) return rc;
+    if ((rc = e->ensure(e->host_pts, pts_bytes, true))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
     double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
     double* haux = (double*)(h + o_aux);   // 7 planes of naux: bx by bz ux uy uz flag
-    std::vector<int64_t> goff(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) goff[s + 1] = goff[s] + (sets[s].n + qpb - 1) / qpb;
-    std::vector<double> box((size_t)goff.back() * 6);   // lo xyz, hi xyz
     { TraceTimer tt("nn: stage points + boxes");
     parallel_for((int)(S + aux.size()), [&](int job) {
         if ((size_t)job >= S) {   // one auxiliary pool entry
             const Aux& ax = aux[(size_t)job - S];
-            const int32_t* pm = ax.perm >= 0 ? perms[(size_t)ax.perm].data() : nullptr;
+            const int32_t* pm = ax.perm >= 0 ? pl.perms[(size_t)ax.perm].data() : nullptr;
             for (int64_t j = 0; j < ax.n; ++j) {
                 const int64_t i = pm ? (int64_t)pm[j] : j;
                 for (int a = 0; a < 3; ++a) {
@@ -190,68 +307,19 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
             }
             return;
         }
-        const int si = job;
-        const Set3& st = sets[(size_t)si];
-        const bool derived = aux_of[(size_t)si] >= 0;
-        double *dx = hx + soff[(size_t)si], *dy = hy + soff[(size_t)si], *dz = hz + soff[(size_t)si];
-        const int32_t* pm = perm_of[(size_t)si] >= 0 ? perms[(size_t)perm_of[(size_t)si]].data() : nullptr;
-        for (int64_t g0 = 0, g = goff[(size_t)si]; g0 < st.n; g0 += qpb, ++g) {
-            double* b = box.data() + (size_t)g * 6;
-            b[0] = b[1] = b[2] = DBL_MAX; b[3] = b[4] = b[5] = -DBL_MAX;
-            for (int64_t j = g0; j < std::min(st.n, g0 + qpb); ++j) {
-                const int64_t i = pm ? (int64_t)pm[j] : j;
-                const double v[3] = {st.at(i, 0), st.at(i, 1), st.at(i, 2)};
-                if (!derived) { dx[j] = v[0]; dy[j] = v[1]; dz[j] = v[2]; }
-                for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], v[a]); b[3 + a] = std::max(b[3 + a], v[a]); }
-            }
-        }
+        const size_t si = (size_t)job;
+        const bool derived = aux_of[si] >= 0;
+        nn_plan_stage_set(sets, pl, si, derived ? nullptr : hx + soff[si], hy + soff[si], hz + soff[si]);
     });
     }
-    for (size_t k = 0; k < perms.size(); ++k)
-        std::memcpy(h + o_perm + (size_t)perm_off[k] * 4, perms[k].data(), perms[k].size() * 4);
+    for (size_t k = 0; k < pl.perms.size(); ++k)
+        std::memcpy(h + o_perm + (size_t)perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
     if (!morphs.empty()) std::memcpy(h + o_morph, morphs.data(), morphs.size() * sizeof(NnMorphH));
 
     // ---- work lists -------------------------------------------------------------------------------
-    // squared distance between two boxes, shaved so that rounding can never overstate it
-    auto box_lb2 = [](const double* a, const double* b) {
-        double s = 0.0;
-        for (int ax = 0; ax < 3; ++ax) {
-            const double gap = std::max(0.0, std::max(a[ax] - b[3 + ax], b[ax] - a[3 + ax]));
-            s += gap * gap;
-        }
-        return s * (1.0 - 1e-12);
-    };
     TraceTimer tt_wl("nn: work lists");
-    const int gpc = ch / qpb;   // groups per chunk
     std::vector<std::vector<NnWorkH>> la(hp.size()), lb(hp.size());   // per pair, built over the worker pool
-    parallel_for((int)hp.size(), [&](int ii) {
-        const size_t i = (size_t)ii;
-        std::vector<NnWorkH>&wa = la[i], &wb = lb[i];
-        const int32_t q = pr[(size_t)owner[i]][0], p = pr[(size_t)owner[i]][1];
-        const int64_t nq = hp[i].nq, np = hp[i].np;
-        const int64_t n_chunks = (np + ch - 1) / ch;
-        const bool prune = perm_of[(size_t)q] >= 0 && perm_of[(size_t)p] >= 0 && n_chunks > 2 && gpc >= 1 && ch % qpb == 0;
-        if (!prune) {
-            for (int64_t q0 = 0; q0 < nq; q0 += qpb)
-                for (int64_t c0 = 0; c0 < np; c0 += (int64_t)span * ch)
-                    wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)c0, span, 0.0});
-            return;
-        }
-        std::vector<std::pair<double, int32_t>> cand((size_t)n_chunks);
-        for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb) {
-            const double* bq = box.data() + (size_t)(goff[(size_t)q] + qb) * 6;
-            for (int64_t c = 0; c < n_chunks; ++c) {
-                double lb2 = DBL_MAX;   // a chunk's box is the union of its groups': the smallest of their distances
-                for (int64_t g = c * gpc; g < std::min<int64_t>((c + 1) * gpc, goff[(size_t)p + 1] - goff[(size_t)p]); ++g)
-                    lb2 = std::min(lb2, box_lb2(bq, box.data() + (size_t)(goff[(size_t)p] + g) * 6));
-                cand[(size_t)c] = {lb2, (int32_t)c};
-            }
-            std::sort(cand.begin(), cand.end());   // nearest chunks first: they tighten the minima the others check
-            wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[0].second * ch, 1, 0.0});
-            for (size_t c = 1; c < cand.size(); ++c)
-                wb.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[c].second * ch, 1, cand[c].first});
-        }
-    });
+    parallel_for((int)hp.size(), [&](int ii) { nn_plan_min_items(pl, pr, (size_t)ii, la[(size_t)ii], lb[(size_t)ii]); });
     std::vector<NnWorkH> wa, wb;
     {
         size_t na_ = 0, nb_ = 0;
@@ -462,85 +530,29 @@ int radius_counts(Engine* e, const std::vector<Set3>& sets, const std::vector<st
 {
     counts.assign(pr.size(), {});
     const size_t S = sets.size();
-    std::vector<int64_t> soff(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) soff[s + 1] = soff[s] + sets[s].n;
-    const int64_t npts = soff.back();
-    const int qpb = nn_queries_per_block(), ch = nn_chunk_points();
-    constexpr int64_t kSortMin = 4096;
-    std::vector<std::vector<int32_t>> perms(S);
-    parallel_for((int)S, [&](int s) { if (sets[(size_t)s].n >= kSortMin) slab_order(sets[(size_t)s], perms[(size_t)s]); });
-    std::vector<int64_t> perm_off(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) perm_off[s + 1] = perm_off[s] + (int64_t)perms[s].size();
-
-    std::vector<NnPairH> hp;
-    std::vector<int> owner;
-    int64_t nout = 0;
-    for (size_t k = 0; k < pr.size(); ++k) {
-        const int32_t q = pr[k][0], p = pr[k][1];
-        if (q < 0 || p < 0 || (size_t)q >= S || (size_t)p >= S) return set_error(MM_ERR_INVALID, "radius counts: set index out of range");
-        counts[k].assign((size_t)sets[(size_t)q].n, 0u);
-        if (sets[(size_t)q].n == 0 || sets[(size_t)p].n == 0) continue;
-        hp.push_back(NnPairH{(int32_t)soff[(size_t)q], (int32_t)sets[(size_t)q].n, (int32_t)soff[(size_t)p], (int32_t)sets[(size_t)p].n,
-                             (int32_t)nout, perms[(size_t)q].empty() ? -1 : (int32_t)perm_off[(size_t)q]});
-        owner.push_back((int)k);
-        nout += sets[(size_t)q].n;
-    }
-    if (hp.empty()) return MM_OK;
-    if (npts > (int64_t)1 << 30 || nout > (int64_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "radius counts: batch exceeds 2^30 points");
-
-    // staged points (slab order where sorted) + bounding boxes of groups of ch points (ch is a multiple of qpb)
-    const size_t o_x = 0, o_y = up256((size_t)npts * 8), o_z = up256(o_y + (size_t)npts * 8);
-    const size_t o_perm = up256(o_z + (size_t)npts * 8), o_pairs = up256(o_perm + (size_t)perm_off.back() * 4);
-    int rc = e->ensure(e->host_pts, o_pairs, true);
+    NnPlan pl;
+    int rc = nn_plan_pairs(sets, pr, nullptr, "radius counts", pl);
     if (rc) return rc;
+    for (size_t k = 0; k < pr.size(); ++k) counts[k].assign((size_t)sets[(size_t)pr[k][0]].n, 0u);
+    if (pl.hp.empty()) return MM_OK;
+    const std::vector<NnPairH>& hp = pl.hp;
+    const std::vector<int>& owner = pl.owner;
+    const std::vector<int64_t>& soff = pl.soff;
+    const int64_t npts = pl.npts(), nout = pl.nout;
+
+    // staged points (slab order where sorted) + bounding boxes of groups of qpb points (a chunk's box is the union of
+    // its ch / qpb groups)
+    const size_t o_x = 0, o_y = up256((size_t)npts * 8), o_z = up256(o_y + (size_t)npts * 8);
+    const size_t o_perm = up256(o_z + (size_t)npts * 8), o_pairs = up256(o_perm + (size_t)pl.perm_off.back() * 4);
+    if ((rc = e->ensure(e->host_pts, o_pairs, true))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
     double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
-    const int g = qpb;   // box granularity: one query block; a chunk's box is the union of its ch / qpb groups
-    std::vector<int64_t> goff(S + 1, 0);
-    for (size_t s = 0; s < S; ++s) goff[s + 1] = goff[s] + (sets[s].n + g - 1) / g;
-    std::vector<double> box((size_t)goff.back() * 6);
-    parallel_for((int)S, [&](int si) {
-        const Set3& st = sets[(size_t)si];
-        const int32_t* pm = perms[(size_t)si].empty() ? nullptr : perms[(size_t)si].data();
-        double *dx = hx + soff[(size_t)si], *dy = hy + soff[(size_t)si], *dz = hz + soff[(size_t)si];
-        for (int64_t g0 = 0, gi = goff[(size_t)si]; g0 < st.n; g0 += g, ++gi) {
-            double* b = box.data() + (size_t)gi * 6;
-            b[0] = b[1] = b[2] = DBL_MAX; b[3] = b[4] = b[5] = -DBL_MAX;
-            for (int64_t j = g0; j < std::min<int64_t>(st.n, g0 + g); ++j) {
-                const int64_t i = pm ? (int64_t)pm[j] : j;
-                const double v[3] = {st.xyz[3 * i], st.xyz[3 * i + 1], st.xyz[3 * i + 2]};
-                dx[j] = v[0]; dy[j] = v[1]; dz[j] = v[2];
-                for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], v[a]); b[3 + a] = std::max(b[3 + a], v[a]); }
-            }
-        }
-    });
-    for (size_t s = 0; s < S; ++s)
-        if (!perms[s].empty()) std::memcpy(h + o_perm + (size_t)perm_off[s] * 4, perms[s].data(), perms[s].size() * 4);
+    parallel_for((int)S, [&](int si) { nn_plan_stage_set(sets, pl, (size_t)si, hx + soff[(size_t)si], hy + soff[(size_t)si], hz + soff[(size_t)si]); });
+    for (size_t k = 0; k < pl.perms.size(); ++k)
+        std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
 
-    auto box_lb2 = [](const double* a, const double* b) {   // squared distance between two boxes, never overstated
-        double s2 = 0.0;
-        for (int ax = 0; ax < 3; ++ax) {
-            const double gap = std::max(0.0, std::max(a[ax] - b[3 + ax], b[ax] - a[3 + ax]));
-            s2 += gap * gap;
-        }
-        return s2 * (1.0 - 1e-12);
-    };
-    const int gpc = std::max(1, ch / g);
     std::vector<std::vector<NnWorkH>> lw(hp.size());
-    parallel_for((int)hp.size(), [&](int ii) {
-        const size_t i = (size_t)ii;
-        const int32_t q = pr[(size_t)owner[i]][0], p = pr[(size_t)owner[i]][1];
-        const int64_t nq = hp[i].nq, np = hp[i].np, n_chunks = (np + ch - 1) / ch;
-        for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb) {
-            const double* bq = box.data() + (size_t)(goff[(size_t)q] + qb) * 6;
-            for (int64_t c = 0; c < n_chunks; ++c) {
-                double lb2 = DBL_MAX;
-                for (int64_t gi = c * gpc; gi < std::min<int64_t>((c + 1) * gpc, goff[(size_t)p + 1] - goff[(size_t)p]); ++gi)
-                    lb2 = std::min(lb2, box_lb2(bq, box.data() + (size_t)(goff[(size_t)p] + gi) * 6));
-                if (lb2 <= r2) lw[i].push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)(c * ch), 1, lb2});
-            }
-        }
-    });
+    parallel_for((int)hp.size(), [&](int ii) { nn_plan_count_items(pl, pr, (size_t)ii, r2, lw[(size_t)ii]); });
     std::vector<NnWorkH> work;
     for (auto& v : lw) work.insert(work.end(), v.begin(), v.end());
     if (work.size() > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "radius counts: too many work items");
@@ -926,6 +938,60 @@ int mm_nn_min_sq_batch(mm_engine* h, int n_sets, const int64_t* set_off, const d
     if ((rc = nn_batch(e, sets, pr, mins))) return rc;
     for (int k = 0; k < n_pairs; ++k)
         if (!mins[(size_t)k].empty()) std::memcpy(out + out_off[k], mins[(size_t)k].data(), mins[(size_t)k].size() * 8);
+    return MM_OK;
+}
+
+// The work lists of one nearest-neighbour batch and of one radius count, as the launch paths build them, without an
+// engine.  A test hook for the pruning claims; nothing in the product calls it.
+int mm_nn_plan(int n_sets, const int64_t* set_off, const double* xyz, const double* unit, const uint8_t* has,
+               const uint8_t* derived, const double* adj, const int32_t* order_like, int n_pairs, const int32_t* q_set,
+               const int32_t* p_set, double r2, int32_t* perm, int64_t* info, int32_t* items, double* item_lb2, int64_t cap)
+{
+    if (n_sets < 0 || n_pairs < 0 || cap < 0 || !info || (n_sets > 0 && !set_off) || (n_pairs > 0 && (!q_set || !p_set)) ||
+        (cap > 0 && (!items || !item_lb2)))
+        return set_error(MM_ERR_INVALID, "mm_nn_plan: bad arguments");
+    std::vector<Set3> sets((size_t)n_sets);
+    for (int s = 0; s < n_sets; ++s) {
+        const int64_t n = set_off[s + 1] - set_off[s];
+        if (set_off[s] < 0 || n < 0 || n > INT32_MAX || (n > 0 && !xyz)) return set_error(MM_ERR_INVALID, "mm_nn_plan: bad set extent");
+        sets[(size_t)s] = Set3{xyz ? xyz + 3 * set_off[s] : nullptr, n};
+        if (derived && derived[s] && n > 0) {
+            if (!unit || !has || !adj) return set_error(MM_ERR_INVALID, "mm_nn_plan: a derived set needs unit, has and adj");
+            sets[(size_t)s] = Set3{xyz + 3 * set_off[s], n, unit + 3 * set_off[s], has + set_off[s], adj[s]};
+        }
+    }
+    if (n_sets > 0 && set_off[n_sets] > 0 && !perm) return set_error(MM_ERR_INVALID, "mm_nn_plan: perm == NULL");
+    std::vector<std::array<int32_t, 2>> pr((size_t)n_pairs);
+    for (int k = 0; k < n_pairs; ++k) pr[(size_t)k] = {q_set[k], p_set[k]};
+    std::vector<int32_t> ol;
+    if (order_like) ol.assign(order_like, order_like + n_sets);
+    NnPlan pl;
+    int rc = nn_plan_pairs(sets, pr, order_like ? &ol : nullptr, "mm_nn_plan", pl);
+    if (rc) return rc;
+    for (size_t s = 0; s < sets.size(); ++s) {
+        nn_plan_stage_set(sets, pl, s, nullptr, nullptr, nullptr);
+        int32_t* dst = perm + set_off[s];
+        if (pl.perm_of[s] >= 0) std::memcpy(dst, pl.perms[(size_t)pl.perm_of[s]].data(), (size_t)sets[s].n * 4);
+        else for (int64_t j = 0; j < sets[s].n; ++j) dst[j] = (int32_t)j;
+    }
+    std::vector<NnWorkH> lists[3];   // pass A, pass B, radius count
+    for (size_t i = 0; i < pl.hp.size(); ++i) {
+        nn_plan_min_items(pl, pr, i, lists[0], lists[1]);
+        nn_plan_count_items(pl, pr, i, r2, lists[2]);
+    }
+    int64_t k = 0;
+    for (int l = 0; l < 3; ++l) {
+        info[l] = (int64_t)lists[l].size();
+        for (const NnWorkH& w : lists[l]) {
+            if (k < cap) {
+                int32_t* it = items + 5 * k;
+                it[0] = l; it[1] = pl.owner[(size_t)w.pair]; it[2] = w.q0; it[3] = w.c0; it[4] = w.n_chunks;
+                item_lb2[k] = w.lb2;
+            }
+            ++k;
+        }
+    }
+    info[3] = pl.qpb; info[4] = pl.ch; info[5] = pl.span;
     return MM_OK;
 }
 

@@ -944,11 +944,12 @@ static int hausdorff_large(Engine* e, const std::vector<SetRef>& sets, const std
 // Needs every pair on the streaming kernel (both sets beyond the LDS kernel's budget) and no empty set;
 // otherwise, and for short lists, everything is evaluated.
 int hausdorff_sets_first_min(Engine* e, const std::vector<SetRef>& sets, const std::vector<std::array<int32_t, 2>>& pr,
-                             int32_t* best, double* best_cost, int64_t* n_exact)
+                             int32_t* best, double* best_cost, int64_t* n_exact, FirstMinState* st)
 {
     const int P = (int)pr.size();
     *best = -1; *best_cost = INFINITY;
     if (n_exact) *n_exact = 0;
+    if (st) *st = FirstMinState{false, std::vector<double>((size_t)P, NAN), -1, NAN, std::vector<uint8_t>((size_t)P, 0)};
     if (P == 0) return MM_OK;
     const int cap = max_target_points_f64();
     bool all_large = P >= 8;
@@ -959,10 +960,11 @@ int hausdorff_sets_first_min(Engine* e, const std::vector<SetRef>& sets, const s
         all_large = sets[ia].n > cap && sets[ib].n > cap;
     }
     std::vector<double> cost((size_t)P, INFINITY);
+    int64_t ne = P;   // pairs evaluated exactly
     if (!all_large) {
         int rc = hausdorff_sets(e, sets, pr, cost.data());
         if (rc) return rc;
-        if (n_exact) *n_exact = P;
+        if (st) st->exact.assign((size_t)P, 1);
     } else {
         std::vector<int> all((size_t)P);
         for (int p = 0; p < P; ++p) all[(size_t)p] = p;
@@ -982,10 +984,18 @@ int hausdorff_sets_first_min(Engine* e, const std::vector<SetRef>& sets, const s
         std::vector<double> res(rest.size());
         if ((rc = lb.run(pr, rest, true, 1, res.data()))) return rc;
         for (size_t k = 0; k < rest.size(); ++k) cost[(size_t)rest[k]] = res[k];
-        if (n_exact) *n_exact = 1 + (int64_t)rest.size();
+        ne = 1 + (int64_t)rest.size();
+        if (st) {
+            st->pruned = true; st->bound = bound; st->pick = pick; st->ub = ub;
+            st->exact[(size_t)pick] = 1;
+            for (int p : rest) st->exact[(size_t)p] = 1;
+        }
     }
     for (int p = 0; p < P; ++p)
         if (cost[(size_t)p] < *best_cost) { *best_cost = cost[(size_t)p]; *best = p; }
+    if (n_exact) *n_exact = ne;
+    e->first_min_pairs += P;
+    e->first_min_exact += ne;
     return MM_OK;
 }
 
@@ -1211,6 +1221,14 @@ int mm_engine_set_bound_matrix(mm_engine* h, int on)
         if ((qt != 1 && qt != 2) || (nc != 1 && nc != 2)) return set_error(MM_ERR_INVALID, "mm_engine_set_bound_matrix: variant must be 11, 12, 21 or 22");
         e->screen_opts.bound_matrix_qt = qt; e->screen_opts.bound_matrix_nc = nc;
     }
+    return MM_OK;
+}
+
+int mm_engine_first_min_stats(mm_engine* h, int64_t out[2])
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e || !out) return set_error(MM_ERR_INVALID, "engine or out == NULL");
+    out[0] = e->first_min_pairs; out[1] = e->first_min_exact;
     return MM_OK;
 }
 
@@ -1481,17 +1499,10 @@ int mm_hausdorff_2d(mm_engine* h, const double* ax, const double* ay, int na,
     return mm_hausdorff_batch(h, 1, ao, ax, ay, bo, bx, by, out, nullptr);
 }
 
-int mm_hausdorff_batch(mm_engine* h, int n_pairs, const int64_t* a_off, const double* ax, const double* ay,
-                       const int64_t* b_off, const double* bx, const double* by, double* out, int32_t* first_min)
+// the pairs of mm_hausdorff_batch's arguments: sets 2p and 2p + 1 for pair p
+static int batch_pairs(int n_pairs, const int64_t* a_off, const double* ax, const double* ay, const int64_t* b_off,
+                       const double* bx, const double* by, std::vector<SetRef>& sets, std::vector<std::array<int32_t, 2>>& pr)
 {
-    Engine* e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    if (n_pairs < 0 || (n_pairs > 0 && !out)) return set_error(MM_ERR_INVALID, "mm_hausdorff_batch: bad arguments");
-    if (first_min) *first_min = -1;
-    if (n_pairs == 0) return MM_OK;
-    MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets;
-    std::vector<std::array<int32_t, 2>> pr;
     sets.reserve(2 * (size_t)n_pairs); pr.reserve((size_t)n_pairs);
     if (!a_off || !b_off) return set_error(MM_ERR_INVALID, "mm_hausdorff_batch: offsets == NULL");
     for (int p = 0; p < n_pairs; ++p) {
@@ -1503,13 +1514,53 @@ int mm_hausdorff_batch(mm_engine* h, int n_pairs, const int64_t* a_off, const do
         sets.push_back(SetRef{bx + b_off[p], by + b_off[p], (int32_t)nb, 0.0, 0.0});
         pr.push_back({2 * p, 2 * p + 1});
     }
-    int rc = hausdorff_sets(e, sets, pr, out);
+    return MM_OK;
+}
+
+int mm_hausdorff_batch(mm_engine* h, int n_pairs, const int64_t* a_off, const double* ax, const double* ay,
+                       const int64_t* b_off, const double* bx, const double* by, double* out, int32_t* first_min)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    if (n_pairs < 0 || (n_pairs > 0 && !out)) return set_error(MM_ERR_INVALID, "mm_hausdorff_batch: bad arguments");
+    if (first_min) *first_min = -1;
+    if (n_pairs == 0) return MM_OK;
+    MM_HIP(hipSetDevice(e->device));
+    std::vector<SetRef> sets;
+    std::vector<std::array<int32_t, 2>> pr;
+    int rc = batch_pairs(n_pairs, a_off, ax, ay, b_off, bx, by, sets, pr);
+    if (rc) return rc;
+    rc = hausdorff_sets(e, sets, pr, out);
     if (rc) return rc;
     int32_t best = -1;
     double best_cost = INFINITY;   // f64::MAX in the reference; costs are finite
     for (int p = 0; p < n_pairs; ++p)
         if (out[p] < best_cost) { best_cost = out[p]; best = p; }
     if (first_min) *first_min = best;
+    return MM_OK;
+}
+
+// The winner-only selection of refine_alignment_hausdorff (hausdorff_sets_first_min) on mm_hausdorff_batch's pairs, with
+// what it did along the way.  A test hook for its claims; nothing in the product calls it.
+int mm_hausdorff_first_min_state(mm_engine* h, int n_pairs, const int64_t* a_off, const double* ax, const double* ay,
+                                 const int64_t* b_off, const double* bx, const double* by, int32_t* pruned, double* bound,
+                                 int32_t* pick, double* ub, uint8_t* exact, int32_t* best, double* best_cost, int64_t* n_exact)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    if (n_pairs < 0 || !pruned || !pick || !ub || !best || !best_cost || !n_exact || (n_pairs > 0 && (!bound || !exact)))
+        return set_error(MM_ERR_INVALID, "mm_hausdorff_first_min_state: bad arguments");
+    MM_HIP(hipSetDevice(e->device));
+    std::vector<SetRef> sets;
+    std::vector<std::array<int32_t, 2>> pr;
+    int rc = n_pairs > 0 ? batch_pairs(n_pairs, a_off, ax, ay, b_off, bx, by, sets, pr) : MM_OK;
+    if (rc) return rc;
+    FirstMinState st;
+    if ((rc = hausdorff_sets_first_min(e, sets, pr, best, best_cost, n_exact, &st))) return rc;
+    *pruned = st.pruned ? 1 : 0;
+    *pick = st.pick;
+    *ub = st.ub;
+    for (int p = 0; p < n_pairs; ++p) { bound[p] = st.bound[(size_t)p]; exact[p] = st.exact[(size_t)p]; }
     return MM_OK;
 }
 

@@ -88,6 +88,7 @@ struct Engine {
     // bounded screen (MM_PRECISION_F32_BOUNDED) while profiling: candidates offered / bounded in round 1 (host
     // counts), device accumulators [1] bounded in round 2, [2] fully screened
     int64_t bound_offered = 0, bound_round1 = 0;
+    int64_t first_min_pairs = 0, first_min_exact = 0;   // hausdorff_sets_first_min: pairs offered / evaluated exactly
     // the switches levels staged from now on take (mm_engine_set_*)
     ScreenOptions screen_opts;
     // candidates screened since the engine was created, by kernel: [0] direct-form f32, [1] packed FMA, [2] matrix pipe
@@ -206,7 +207,16 @@ int hausdorff_sets(Engine* e, const std::vector<SetRef>& sets, const std::vector
 
 // First index of minimal hausdorff_distance over the pairs (strict '<' in pair order) and its value, with
 // lower bounds ruling pairs out where every pair runs on the streaming kernel; n_exact = pairs evaluated.
+// st (nullable, a test hook's): what the selection did -- whether the bounds ran, each pair's bound (NaN where they did
+// not), the pick and its exact cost ub (-1 / NaN where they did not), and which pairs were evaluated exactly.
+struct FirstMinState {
+    bool pruned = false;
+    std::vector<double> bound;
+    int32_t pick = -1;
+    double ub = NAN;
+    std::vector<uint8_t> exact;
+};
 int hausdorff_sets_first_min(Engine* e, const std::vector<SetRef>& sets, const std::vector<std::array<int32_t, 2>>& pairs,
-                             int32_t* best, double* best_cost, int64_t* n_exact);
+                             int32_t* best, double* best_cost, int64_t* n_exact, FirstMinState* st = nullptr);
 
 }  // namespace mm

@@ -62,12 +62,16 @@ def test_refine_winner_only_prunes_and_agrees_on_large_sets(engine, mm):
                                               true_rotation_deg=-31.0, true_index=10, clutter_frac=0.05)
     aligned, rcl, idx0 = _aligned(mm, case)
     for rng_deg, step_deg, idx_range in ((12.0, 1.0, 2), (4.0, 0.5, 3)):
+        before = engine.first_min_stats()
         full = mm.centerline.refine_alignment_hausdorff(engine, [aligned], rcl, idx0, 0.0, case["points"],
                                                         math.radians(rng_deg), math.radians(step_deg), idx_range)
         win = mm.centerline.refine_alignment_hausdorff(engine, [aligned], rcl, idx0, 0.0, case["points"],
                                                        math.radians(rng_deg), math.radians(step_deg), idx_range,
                                                        return_costs=False)
         assert len(full[3]) >= 8 and win[:3] == full[:3]
+        after = engine.first_min_stats()             # the winner-only call: every pair offered, most ruled out
+        assert after["pairs"] - before["pairs"] == len(full[3])
+        assert 1 <= after["exact"] - before["exact"] < len(full[3])
         k = int(np.argmin(full[3]))
         assert full[2] == full[3][k]
 
