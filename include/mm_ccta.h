@@ -248,6 +248,85 @@ int     mm_trim_mesh(mm_engine* e, const double* vertices_xyz, int64_t nv, const
                      const uint8_t* region, int mode, int64_t target_n, double despike_cos, int64_t max_rounds,
                      double* out_vertices, int64_t* out_faces, int64_t* ring_len, int64_t* ring_idx, int64_t* counts);
 
+/* ---- stitching (multimodars/ccta/stitching.py:69-107, 355-481, 1148-1334; _converters.py:1018-1085;
+ *      src/ccta/binding/ccta_py.rs:596-700) ------------------------------------------------------------------------- */
+
+/* What mm_mesh_assemble did and what it left.  watertight <=> n_open_edges == 0 && n_nonmanifold_edges == 0. */
+typedef struct mm_assemble_report {
+    int64_t n_vertices, n_faces;             /* of the result                                                        */
+    int64_t n_welded_vertices;               /* referenced vertices merged into an earlier one                       */
+    int64_t n_unreferenced_vertices;         /* vertices no input face names: dropped                                */
+    int64_t n_degenerate_faces;              /* faces with a repeated index after the weld: dropped                  */
+    int64_t n_duplicate_faces;               /* faces whose vertex set an earlier face has: dropped                  */
+    int64_t n_flipped_faces;                 /* faces the winding stage reversed (not counting the inversion)        */
+    int64_t n_winding_conflicts;             /* edges owned twice whose faces still disagree: 0 for orientable input */
+    int64_t n_open_edges, n_nonmanifold_edges;   /* edges of the result owned by one face / by more than two         */
+    int64_t inverted;                        /* 1: volume < 0 and every face was reversed                            */
+    int64_t winding_rounds;                  /* launches of the winding stage's union-find: 1 hook + the pointer-    */
+                                             /* jumping rounds, at most 2 + ceil(log2(max(n_faces, 2)))               */
+    double  volume;                          /* signed volume before the inversion (0 without fix_inversion)         */
+} mm_assemble_report;
+
+/* fix_mesh_winding (ccta_py.rs:596-700) on the device, on a bare face list (indices in [0, 2^31), nf < 2^31).  Two
+ * faces are adjacent when they share an undirected edge owned by exactly two faces.  In every connected component the
+ * face with the smallest index keeps its corner order; every other face is reversed (a, b, c) -> (c, b, a) iff its
+ * parity to that face is odd (adjacent faces agree when they traverse the shared edge in opposite directions).  For an
+ * orientable component that is the reference's BFS whatever its hash-map order.  A component that is not orientable has
+ * no consistent answer: its flips are unspecified.  info[3] = {faces reversed, edges owned twice whose faces still
+ * disagree, winding_rounds}. */
+int     mm_fix_winding(mm_engine* e, const int64_t* faces, int64_t nf, int64_t* out_faces, int64_t* info);
+/* n_parts meshes concatenated, welded, cleaned and oriented on the device: one upload, one download.  Part p has the
+ * vertices vert_off[p] .. vert_off[p+1] of vertices_xyz and the faces face_off[p] .. face_off[p+1] of faces, whose
+ * indices are local to the part (checked against it before anything is allocated); the totals stay below 2^31.
+ *   weld     only vertices some face names take part.  key = rint(c * 10^merge_digits) per coordinate (one f64
+ *            multiply; rint rounds half to even; merge_digits in [0, 15]).  A vertex with a non-finite coordinate or a
+ *            scaled magnitude at or above 2^62 matches nothing.  Vertices with equal keys become the one with the
+ *            smallest index in concatenated order, coordinates bit for bit; survivors keep concatenated order.
+ *   faces    remapped through the weld; a face with a repeated index is dropped; of faces with the same vertex set the
+ *            one with the smallest index stays, with its own corner order; survivors keep input order.
+ *   winding  (fix_winding) as mm_fix_winding on the surviving faces.
+ *   inversion (fix_inversion) volume = (sum_f t_f) / 6 over the surviving faces after the winding stage, with, for the
+ *            corners p0 p1 p2 of f, unfused:  cx = p1y p2z - p1z p2y;  cy = p1z p2x - p1x p2z;  cz = p1x p2y - p1y p2x;
+ *            t_f = (p0x cx + p0y cy) + p0z cz.  The sum is the adjacent-pair tree over the faces in output order, padded
+ *            with +0.0 to a power of two.  volume < 0: every face is reversed.
+ * out_vertices (capacity: all vertices) and out_faces (capacity: all faces) receive the result. */
+int     mm_mesh_assemble(mm_engine* e, int n_parts, const double* vertices_xyz, const int64_t* vert_off,
+                         const int64_t* faces, const int64_t* face_off, int merge_digits, int fix_winding,
+                         int fix_inversion, double* out_vertices, int64_t* out_faces, mm_assemble_report* report);
+
+/* The seam, host only.  Rings are n xyz triples; sums run in index order; norms are sqrt((x x + y y) + z z). */
+
+/* _assign_rings_to_ends (stitching.py:69-107): ring r = points ring_off[r] .. ring_off[r+1]; its centroid is the
+ * sequential sum of its points divided by their number.  Over all ordered pairs (i, j), i != j, in loop order, the one
+ * with the smallest |c_i - prox| + |c_j - dist| (strict <: the first minimum wins) goes to pair[2].  Fewer than two
+ * rings or an empty ring is MM_ERR_INVALID. */
+int     mm_assign_rings_to_ends(const double* rings_xyz, const int64_t* ring_off, int64_t n_rings, const double prox[3],
+                                const double dist[3], int64_t pair[2]);
+/* The start index of a ring: mode 0 = _rotate_to_nearest_iv (:1154-1159), the first point nearest to iv_pt; mode 1 =
+ * _adjust_start_point_by_z (:1148-1151), the first point of largest z (iv_pt unused).  As numpy's argmin / argmax, the
+ * first NaN wins.  n < 1 is MM_ERR_INVALID. */
+int64_t mm_ring_start(const double* ring_xyz, int64_t n, int mode, const double* iv_pt);
+/* 1 where the ring is to be reversed behind its first point, else 0.  mode 0 = _fix_ring_direction_by_distance
+ * (:1213-1239) against every point_step-th IV point, the first n_b of them: reversed iff its summed distance is
+ * strictly smaller.  mode 1 = _fix_ring_direction_by_winding (:1242-1259): the Newell normal of the IV ring
+ * (_newell_normal :1194-1210; (0, 0, 1) when its length is not above 1e-10) and the ring's signed area projected on
+ * it (_signed_area_projected :1176-1191): reversed iff negative. */
+int     mm_ring_direction(const double* ring_xyz, int64_t n_b, const double* iv_xyz, int64_t n_iv, int mode,
+                          int64_t point_step);
+/* _stitch_rings (:1262-1334): the n_b + n_iv faces of the strip between a boundary ring (vertices 0 .. n_b - 1) and an
+ * IV ring (n_b .. n_b + n_iv - 1) by the two-pointer walk (the boundary advances while (i+1)/n_b <= (j+1)/n_iv in
+ * f64).  With outward (nullable) every face is reversed when the mean of the finite unit face normals (sequential sum
+ * in face order) has a negative dot product with it.  Returns 1 where it reversed, else 0; a ring of fewer than 3
+ * points is MM_ERR_INVALID. */
+int     mm_stitch_rings(const double* ring_xyz, int64_t n_b, const double* iv_xyz, int64_t n_iv, const double* outward,
+                        int64_t* faces);
+/* The tube of geometry_to_trimesh (_converters.py:1018-1085): n_contours contours of n_points points each give
+ * 2 (n_contours - 1) n_points faces [a, b, d], [b, c, d] per quad; every face is reversed when the first face's normal
+ * points towards centroid0 (the first contour's centroid).  Returns 1 where it reversed; fewer than 2 contours or 1
+ * point is MM_ERR_INVALID. */
+int     mm_tube_faces(const double* contours_xyz, int64_t n_contours, int64_t n_points, const double centroid0[3],
+                      int64_t* faces);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    label_anomalous_region, label_geometry, remove_occluded_points_ray_triangle, scale,
                    scale_region_centerline_morphing, sync_results_to_mesh, open_boundary_edges, order_boundary_rings,
                    clean_open_boundary, remove_labeled_points_from_mesh, keep_labeled_points_from_mesh,
-                   extract_region_with_border_faces, export_section_stl, build_adjacency_map)
+                   extract_region_with_border_faces, export_section_stl, build_adjacency_map,
+                   fix_mesh_winding, assemble_mesh, stitch_rings, stitch_ccta_to_intravascular, stitch)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -63,6 +64,7 @@ __all__ = [
     "sync_results_to_mesh", "scale", "open_boundary_edges", "order_boundary_rings", "clean_open_boundary",
     "remove_labeled_points_from_mesh", "keep_labeled_points_from_mesh", "extract_region_with_border_faces",
     "export_section_stl", "build_adjacency_map",
+    "fix_mesh_winding", "assemble_mesh", "stitch_rings", "stitch_ccta_to_intravascular", "stitch",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

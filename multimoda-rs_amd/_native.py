@@ -106,7 +106,17 @@ EXPORTS_CCTA = [
     "mm_slice_anchor_count", "mm_nearest_anchor_project", "mm_resample_closed_contour", "mm_discretize_vessel_batch",
     "mm_centerline_morph_batch", "mm_match_points", "mm_keep_largest_component",
     "mm_build_adjacency", "mm_boundary_rings", "mm_open_boundary_edges", "mm_clean_open_boundary", "mm_trim_mesh",
+    "mm_fix_winding", "mm_mesh_assemble", "mm_assign_rings_to_ends", "mm_ring_start", "mm_ring_direction",
+    "mm_stitch_rings", "mm_tube_faces",
 ]
+
+
+class MMAssembleReport(C.Structure):
+    """``mm_assemble_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_welded_vertices", "n_unreferenced_vertices", "n_degenerate_faces",
+        "n_duplicate_faces", "n_flipped_faces", "n_winding_conflicts", "n_open_edges", "n_nonmanifold_edges",
+        "inverted", "winding_rounds")] + [("volume", C.c_double)]
 
 
 class MMClGeometry(C.Structure):
@@ -467,6 +477,20 @@ def lib():
     L.mm_clean_open_boundary.argtypes = [P, P, I64, P, I64, P, I64, I64, D, I64, P, P, P, P]
     L.mm_trim_mesh.restype = I
     L.mm_trim_mesh.argtypes = [P, P, I64, P, I64, P, I, I64, D, I64, P, P, P, P, P]
+    L.mm_fix_winding.restype = I
+    L.mm_fix_winding.argtypes = [P, P, I64, P, P]
+    L.mm_mesh_assemble.restype = I
+    L.mm_mesh_assemble.argtypes = [P, I, P, P, P, P, I, I, I, P, P, C.POINTER(MMAssembleReport)]
+    L.mm_assign_rings_to_ends.restype = I
+    L.mm_assign_rings_to_ends.argtypes = [P, P, I64, P, P, P]
+    L.mm_ring_start.restype = I64
+    L.mm_ring_start.argtypes = [P, I64, I, P]
+    L.mm_ring_direction.restype = I
+    L.mm_ring_direction.argtypes = [P, I64, P, I64, I, I64]
+    L.mm_stitch_rings.restype = I
+    L.mm_stitch_rings.argtypes = [P, I64, P, I64, P, P]
+    L.mm_tube_faces.restype = I
+    L.mm_tube_faces.argtypes = [P, I64, I64, P, P]
     _lib = L
     return L
 

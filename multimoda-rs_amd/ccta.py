@@ -1049,3 +1049,251 @@ def export_section_stl(results: dict, type: str = "all", output_dir=None, engine
     path = os.path.join(out_dir, f"{type}.stl")
     write_stl(path, *_mesh_parts(sub))
     return path
+
+
+# ---- stitching (multimodars/ccta/stitching.py:69-107, 355-481, 1148-1334; ccta/__init__.py:261-338) -----------------
+
+ASSEMBLE_REPORT_KEYS = tuple(name for name, _ in N.MMAssembleReport._fields_)
+
+
+def fix_mesh_winding(faces, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """ccta_py.rs:596-700: ``faces`` with a consistent winding, ``(F, 3)`` int64.  Two faces are adjacent when they share
+    an edge that exactly two faces own; in every connected component the face with the smallest index keeps its corner
+    order and every other face is reversed ``(a, b, c) -> (c, b, a)`` iff its parity to that face is odd.  For an
+    orientable component that is the reference's BFS result; a component that is not orientable has no consistent
+    answer and its flips are unspecified.  Runs on the device (csrc/mm_weld_kernels.hip: a union-find with parity, a
+    logarithmic number of launches whatever the mesh's diameter)."""
+    return _fix_winding(faces, engine)[0]
+
+
+def _fix_winding(faces, engine):
+    f = _faces3(faces)
+    if f.size and (f.min() < 0 or f.max() >= 2 ** 31 - 1):
+        raise ValueError("face index out of range [0, 2^31 - 1)")
+    out = np.zeros_like(f)
+    info = np.zeros(3, dtype=np.int64)
+    N.check(N.lib().mm_fix_winding(_engine(engine).handle, N._ptr(f), f.shape[0], N._ptr(out), N._ptr(info)),
+            "fix_mesh_winding")
+    return out, {"n_flipped_faces": int(info[0]), "n_winding_conflicts": int(info[1]), "winding_rounds": int(info[2])}
+
+
+def assemble_mesh(parts, merge_digits: int = 3, fix_winding: bool = True, fix_inversion: bool = True,
+                  engine: Optional[N.Engine] = None):
+    """The tail of stitch_ccta_to_intravascular (stitching.py:455-468) on the device: ``parts`` (``(vertices, faces)``
+    pairs or meshes with ``.vertices`` / ``.faces``) concatenated, vertices welded where ``rint(c * 10**merge_digits)``
+    agrees in every coordinate (the smallest index of a group stays, bit for bit; vertices no face names are dropped),
+    faces with a repeated index and later repeats of a vertex set dropped, the winding made consistent
+    (fix_mesh_winding) and, where the signed volume is negative, every face reversed.  Returns ``(vertices, faces,
+    report)``; ``report`` holds ASSEMBLE_REPORT_KEYS and ``"watertight"``.  Holes are not filled: the report says
+    whether any are left.  include/mm_ccta.h states every rule."""
+    vs, fs = [], []
+    for part in parts:
+        pv, pf = _mesh_parts(part)
+        pv = _p3(pv)
+        vs.append(pv)
+        fs.append(_checked_faces(pf, pv.shape[0]))
+    voff = np.zeros(len(vs) + 1, dtype=np.int64)
+    foff = np.zeros(len(vs) + 1, dtype=np.int64)
+    if vs:
+        voff[1:] = np.cumsum([a.shape[0] for a in vs])
+        foff[1:] = np.cumsum([a.shape[0] for a in fs])
+    v = np.ascontiguousarray(np.concatenate(vs)) if vs else np.zeros((0, 3), dtype=np.float64)
+    f = np.ascontiguousarray(np.concatenate(fs)) if fs else np.zeros((0, 3), dtype=np.int64)
+    out_v, out_f = np.zeros_like(v), np.zeros_like(f)
+    rep = N.MMAssembleReport()
+    N.check(N.lib().mm_mesh_assemble(_engine(engine).handle, len(vs), N._ptr(v), N._ptr(voff), N._ptr(f), N._ptr(foff),
+                                     int(merge_digits), int(bool(fix_winding)), int(bool(fix_inversion)), N._ptr(out_v),
+                                     N._ptr(out_f), C.byref(rep)), "assemble_mesh")
+    report = {k: getattr(rep, k) for k in ASSEMBLE_REPORT_KEYS}
+    report["watertight"] = report["n_open_edges"] == 0 and report["n_nonmanifold_edges"] == 0
+    return out_v[:rep.n_vertices].copy(), out_f[:rep.n_faces].copy(), report
+
+
+def assign_rings_to_ends(rings, prox_centroid, dist_centroid):
+    """stitching.py:69-107: ``(i, j, leftover)``: the ring for the proximal end, the ring for the distal end (the
+    ordered pair of distinct rings with the smallest summed centroid distance, the first minimum in loop order) and the
+    indices of the other rings."""
+    rs = [_p3(r) for r in rings]
+    off = np.zeros(len(rs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([r.shape[0] for r in rs])
+    flat = np.ascontiguousarray(np.concatenate(rs)) if rs else np.zeros((0, 3), dtype=np.float64)
+    pair = np.zeros(2, dtype=np.int64)
+    p, d = _p3(prox_centroid), _p3(dist_centroid)
+    N.check(N.lib().mm_assign_rings_to_ends(N._ptr(flat), N._ptr(off), len(rs), N._ptr(p), N._ptr(d), N._ptr(pair)),
+            "assign_rings_to_ends")
+    i, j = int(pair[0]), int(pair[1])
+    return i, j, [k for k in range(len(rs)) if k not in (i, j)]
+
+
+def rotate_ring_start(boundary_pts, mode: str = "nearest_iv", iv_pt=None) -> np.ndarray:
+    """_rotate_to_nearest_iv (stitching.py:1154-1159) / _adjust_start_point_by_z (:1148-1151): the ring rotated so that
+    the first point nearest to ``iv_pt`` (``"nearest_iv"``) or the first point of largest z (``"highest_z"``) leads."""
+    b = _p3(boundary_pts)
+    if mode not in ("nearest_iv", "highest_z"):
+        raise ValueError(f"unknown start mode {mode!r}")
+    q = _p3(iv_pt) if mode == "nearest_iv" else None
+    k = N.lib().mm_ring_start(N._ptr(b), b.shape[0], 0 if mode == "nearest_iv" else 1, N._ptr(q))
+    if k < 0:
+        N.check(int(k), "rotate_ring_start")
+    return np.concatenate([b[k:], b[:k]])
+
+
+def fix_ring_direction(boundary_pts, iv_pts, mode: str = "distance", point_step: int = 1) -> np.ndarray:
+    """_fix_ring_direction_by_distance (stitching.py:1213-1239, ``mode="distance"``) / _fix_ring_direction_by_winding
+    (:1242-1259, ``mode="winding"``): the ring as it is or reversed behind its first point."""
+    b, iv = _p3(boundary_pts), _p3(iv_pts)
+    if mode not in ("distance", "winding"):
+        raise ValueError(f"unknown direction mode {mode!r}")
+    rc = N.lib().mm_ring_direction(N._ptr(b), b.shape[0], N._ptr(iv), iv.shape[0], 0 if mode == "distance" else 1,
+                                   int(point_step))
+    if rc < 0:
+        N.check(rc, "fix_ring_direction")
+    return np.concatenate([b[:1], b[:0:-1]]) if rc else b
+
+
+def stitch_rings(boundary_pts, iv_pts, outward_direction=None):
+    """_stitch_rings (stitching.py:1262-1334): the closed strip between a boundary ring and an IV ring,
+    ``(vertices, faces)`` with the boundary vertices first and exactly ``n_b + n_iv`` faces; the whole strip is reversed
+    when its mean unit face normal points against ``outward_direction``."""
+    b, iv = _p3(boundary_pts), _p3(iv_pts)
+    if b.shape[0] < 3 or iv.shape[0] < 3:
+        raise ValueError(f"Need at least 3 points per ring to stitch (got boundary={b.shape[0]}, iv={iv.shape[0]}).")
+    faces = np.zeros((b.shape[0] + iv.shape[0], 3), dtype=np.int64)
+    o = None if outward_direction is None else _p3(outward_direction)
+    rc = N.lib().mm_stitch_rings(N._ptr(b), b.shape[0], N._ptr(iv), iv.shape[0], N._ptr(o), N._ptr(faces))
+    if rc < 0:
+        N.check(rc, "stitch_rings")
+    return np.concatenate([b, iv]), faces
+
+
+def _downsample_geometry(g: G.FlatGeometry, n: int):
+    """PyGeometry.downsample (py_geometry.rs:394, contour.rs:47-58) of the lumen contours: a contour of more than ``n``
+    points keeps the points ``int(i * (len / n))``.  Returns the list of per-frame ``(k, 3)`` arrays."""
+    out = []
+    for i in range(g.n_frames):
+        pts = g.frame_lumen(i)
+        if pts.shape[0] > n:
+            idx = (np.arange(n, dtype=np.float64) * (pts.shape[0] / float(n))).astype(np.int64)
+            pts = pts[idx]
+        out.append(np.ascontiguousarray(pts, dtype=np.float64))
+    return out
+
+
+def geometry_tube(contours, centroid0):
+    """geometry_to_trimesh (_converters.py:1018-1085): ``(vertices, faces)`` of the tube through ``contours`` (equally
+    many points each), one quad strip per adjacent pair, reversed as a whole when its first face looks at
+    ``centroid0``."""
+    cs = [_p3(c) for c in contours]
+    if len(cs) < 2:
+        raise ValueError("Need at least two contours to build a mesh.")
+    n = cs[0].shape[0]
+    if n < 1 or any(c.shape[0] != n for c in cs):
+        raise ValueError("every contour needs the same, positive number of points")
+    v = np.ascontiguousarray(np.concatenate(cs))
+    faces = np.zeros((2 * (len(cs) - 1) * n, 3), dtype=np.int64)
+    rc = N.lib().mm_tube_faces(N._ptr(v), len(cs), n, N._ptr(_p3(centroid0)), N._ptr(faces))
+    if rc < 0:
+        N.check(rc, "geometry_tube")
+    return v, faces
+
+
+def _result_rings(results: dict, mesh, engine) -> list:
+    """_boundary_rings (stitching.py:40-66): the rings under ``boundary_points_<n>``, or, failing that, those of the
+    mesh's open edges that hold a point of the flat ``boundary_points``."""
+    rings = []
+    n = 1
+    while f"{BOUNDARY_RING_PREFIX}{n}" in results:
+        r = _p3(results[f"{BOUNDARY_RING_PREFIX}{n}"])
+        if r.shape[0]:
+            rings.append(r)
+        n += 1
+    if rings:
+        return rings
+    flat = _p3(results.get("boundary_points", ()) if results.get("boundary_points", None) is not None else ())
+    if flat.shape[0] == 0:
+        return []
+    v, f = _mesh_parts(mesh)
+    v = _p3(v)
+    idx = _match(v, flat)
+    seeds = set(int(i) for i in idx[idx >= 0])
+    return [v[r] for r in order_boundary_rings(f, v, seeds, engine=engine)]
+
+
+def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dict, n_points_iv_cont: int = 100,
+                                 prox_start_mode: str = "nearest_iv", dist_start_mode: str = "nearest_iv",
+                                 condition_rims: bool = False, engine: Optional[N.Engine] = None) -> dict:
+    """stitching.py:355-481 without the rim conditioning of _prepare_prox_dist_boundary_pts (:484-1060: plane
+    flattening, smoothing, respacing, ostium clamp, densification), which this package does not have yet:
+    ``condition_rims=True`` raises NotImplementedError, and the arguments that only steer it (``proximal_is_ostium``,
+    ``clamp_overshoot``, ``boundary_point_ratio``) are not accepted.  The lumen contours are downsampled to
+    ``n_points_iv_cont`` points, the two rims (``boundary_points_<n>`` of ``results``, else the mesh's open edges) are
+    assigned to the ends as whole rings, rotated to their start (``"nearest_iv"`` | ``"highest_z"``; ``"highest_z"``
+    also rotates every frame so that the first frame's highest point leads, the last of equal ones, as the reference's
+    sort_frame_points does) and given the IV ring's direction, both strips are stitched, and ``[mesh, proximal strip,
+    distal strip, IV tube]`` are assembled on the device (assemble_mesh).  Returns a new dict with the reference's keys
+    ``prox_boundary_points``, ``dist_boundary_points``, ``anomalous_points``, ``rca_points``, ``mesh`` and
+    ``stitch_report`` (the assembly's report; holes are not filled)."""
+    if condition_rims:
+        raise NotImplementedError("condition_rims=True: the rim conditioning of _prepare_prox_dist_boundary_pts "
+                                  "(stitching.py:484-1060) is not part of this package yet")
+    for m in (prox_start_mode, dist_start_mode):
+        if m not in ("nearest_iv", "highest_z"):
+            raise ValueError(f"unknown start mode {m!r}")
+    frames = _downsample_geometry(iv_geometry, int(n_points_iv_cont))
+    if len(frames) < 2:
+        raise ValueError("Need at least two contours to build a mesh.")
+    iv_points = np.concatenate(frames)
+    prox_c, dist_c = iv_geometry.centroids[0].copy(), iv_geometry.centroids[-1].copy()
+    prox_outward, dist_outward = prox_c - dist_c, dist_c - prox_c
+
+    rings = _result_rings(results, mesh, engine)
+    if len(rings) < 2:
+        raise ValueError(f"Stitching needs a proximal and a distal boundary ring, but {len(rings)} were found. Re-run "
+                         f"the removal with target_boundaries=2 so both rims are kept as separate rings.")
+    i, j, _ = assign_rings_to_ends(rings, prox_c, dist_c)
+    prox_b, dist_b = rings[i], rings[j]
+    prox_step = max(1, frames[0].shape[0] // prox_b.shape[0])
+    dist_step = max(1, frames[-1].shape[0] // dist_b.shape[0])
+
+    if "highest_z" in (prox_start_mode, dist_start_mode):                  # sort_frame_points (geometry.rs:257-276)
+        z = frames[0][:, 2]
+        shift = int(z.shape[0] - 1 - np.argmax(z[::-1]))                   # max_by: the last of equal maxima
+        frames = [np.concatenate([f[shift % f.shape[0]:], f[:shift % f.shape[0]]]) if f.shape[0] else f for f in frames]
+    ends = ((prox_b, frames[0], prox_start_mode, prox_step), (dist_b, frames[-1], dist_start_mode, dist_step))
+    fixed = []
+    for ring, iv, mode, step in ends:
+        ring = rotate_ring_start(ring, mode, iv[0])
+        fixed.append(fix_ring_direction(ring, iv, "winding", 1) if mode == "highest_z"
+                     else fix_ring_direction(ring, iv, "distance", step))
+    prox_b, dist_b = fixed
+    prox_patch = stitch_rings(prox_b, frames[0], prox_outward)
+    dist_patch = stitch_rings(dist_b, frames[-1], dist_outward)
+    lc = iv_geometry.lumen_centroids
+    c0 = lc[0] if lc is not None and (iv_geometry.has_lumen_centroid is None or iv_geometry.has_lumen_centroid[0]) \
+        else iv_geometry.centroids[0]
+    tube = geometry_tube(frames, c0)
+    mv, mf = _mesh_parts(mesh)
+    new_v, new_f, report = assemble_mesh([(mv, mf), prox_patch, dist_patch, tube], engine=engine)
+
+    out = dict(results)
+    out["prox_boundary_points"] = prox_b
+    out["dist_boundary_points"] = dist_b
+    out["anomalous_points"] = iv_points
+    out["rca_points"] = np.concatenate([iv_points, _p3(results.get("distal_points", ())),
+                                        _p3(results.get("proximal_points", ()))])
+    out["mesh"] = _with_mesh(mesh, new_v, new_f)
+    out["stitch_report"] = report
+    return out
+
+
+def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
+           prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
+           engine: Optional[N.Engine] = None) -> dict:
+    """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
+    to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
+    default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  No
+    post-processing and no hole filling: ``stitch_report`` says whether the result is watertight."""
+    keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
+    updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
+    return stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
+                                        dist_start_mode=dist_start_mode, engine=engine)

@@ -203,6 +203,34 @@ hipError_t launch_trim_scan(const uint8_t* flag, long long n, long long* tile_su
 hipError_t launch_trim_compact(const double* v, long long nv, const int32_t* vidx, const int32_t* face, long long nf,
                                const int32_t* fidx, double* out_v, int32_t* out_f, hipStream_t s);
 hipError_t launch_trim_clear(const int32_t* idx, long long n, uint8_t* mask, hipStream_t s);
+// mesh assembly (mm_weld_kernels.hip): face = int32 triples.  weld_vertices: rep[v] = the smallest vertex with v's key
+// (v itself without a key, -1 unreferenced) through an int32 table of 2^log2_cap slots (at least twice nv), keep[v] =
+// rep[v] == v, counts[0] += unreferenced; weld_faces: vmap[v] = vidx[rep[v]] (vidx: the scan of keep), the faces read through it, fkeep = neither
+// degenerate nor a later repeat of a vertex set (table: at least twice nf), counts[0..1] += degenerate, repeated;
+// weld_edges: the edge table (keys 8 B, counts 4 B, two owners 8 B a slot; at least 6 nf slots, never fewer than 256);
+// weld_hook: link = parity union-find over the edges owned twice; weld_jump: one pointer-jumping round, *changed set
+// where a link moved; weld_flip: the faces of odd parity reversed, *n_flipped += their number; weld_edge_report:
+// counts[0..2] += open, non-manifold, conflicting edges (link nullable: no flips); weld_volume: *out = the adjacent-pair
+// tree of the per-face terms (a: nf doubles, b: weld_sum_scratch(nf)); weld_reverse: every face reversed
+hipError_t launch_weld_vertices(const double* v, long long nv, const int32_t* face, long long nf, double scale,
+                                uint8_t* ref, int32_t* table, int log2_cap, int32_t* rep, uint8_t* keep,
+                                unsigned long long* counts, hipStream_t s);
+hipError_t launch_weld_faces(const int32_t* face, long long nf, long long nv, const int32_t* rep, const int32_t* vidx,
+                             int32_t* vmap, int32_t* table, int log2_cap, int32_t* frep, uint8_t* fkeep,
+                             unsigned long long* counts, hipStream_t s);
+hipError_t launch_weld_edges(const int32_t* face, long long nf, unsigned long long* keys, unsigned int* cnt,
+                             unsigned int* own, int log2_cap, hipStream_t s);
+hipError_t launch_weld_hook(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
+                            int log2_cap, unsigned int* link, long long nf, hipStream_t s);
+hipError_t launch_weld_jump(unsigned int* link, long long nf, unsigned int* changed, hipStream_t s);
+hipError_t launch_weld_flip(int32_t* face, long long nf, const unsigned int* link, unsigned long long* n_flipped,
+                            hipStream_t s);
+hipError_t launch_weld_edge_report(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
+                                   int log2_cap, const unsigned int* link, unsigned long long* counts, hipStream_t s);
+size_t     weld_sum_scratch(long long nf);
+hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
+                              hipStream_t s);
+hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s);
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers

@@ -1,0 +1,484 @@
+// mm_weld_kernels.hip -- the data-parallel part of CCTA stitching, for gfx950: welding the vertices of concatenated
+// meshes, dropping repeated and degenerate faces, making the winding consistent and summing the signed volume.
+//
+// stitch_ccta_to_intravascular (multimodars/ccta/stitching.py:455-468: concatenate, merge_vertices, unique_faces,
+// nondegenerate_faces, remove_unreferenced_vertices, _fast_fix_normals) and fix_mesh_winding
+// (src/ccta/binding/ccta_py.rs:596-700).  Faces are int32 index triples checked on the host; every stage has an exact,
+// order-free answer (include/mm_ccta.h states the rules), so the output does not depend on scheduling.
+//
+//   k_weld_mark          ref[v] = 1 for every corner of every face (plain byte stores, benign races).
+//   k_weld_vertex_insert one lane per referenced vertex with a key (the integer triple rint(c * scale)): an
+//                        open-addressing table of int32 slots, each holding the SMALLEST vertex index seen with the
+//                        slot's key.  A slot is claimed with a 32-bit atomicCAS from empty; a lane that finds a slot
+//                        taken re-derives the holder's key from the immutable coordinates (every holder of a slot has
+//                        the same key, so it does not matter which one it reads) and either lowers the slot with
+//                        atomicMin or probes on.  The lane remembers its slot in rep[v].
+//   k_weld_vertex_rep    rep[v] = the slot's final value (v itself without a key, -1 unreferenced), keep[v] = rep[v] == v.
+//   k_weld_vmap / k_weld_face_insert   vmap[v] = the new index of v's representative; a face with a repeated index
+//                        after the weld is dropped, the others go through the same kind of table keyed by their
+//                        sorted new index triple.
+//   k_weld_face_rep      fkeep[f] = the face is the smallest index of its vertex set.
+//   k_weld_edge_insert   the three undirected edges of every face into the 64-bit CAS table of the trimming, with a
+//                        count and the first two owners (face << 1 | traverses it from the smaller to the larger end).
+//   k_weld_hook          union-find with parity over the edges owned by exactly two faces: link[f] = parent << 1 |
+//                        parity to the parent.  A root hooks under a smaller root with one atomicCAS (parents only
+//                        ever get smaller: no cycle, and the root of a component ends as its smallest face); finds halve
+//                        their path as they go.  Lock-free: a lane only retries after another lane's hook landed.
+//   k_weld_jump          one round of pointer jumping, link[f] -> its grandparent with the parities added.
+//   k_weld_flip          a face of odd parity to its root is reversed (a, b, c) -> (c, b, a); counted per wave.
+//   k_weld_edge_report   open, non-manifold and winding-conflict edges of the table, one integer atomicAdd per wave each.
+//   k_weld_terms / k_weld_pair_sum   the per-face volume terms and their adjacent-pair tree (a wave's xor-butterfly,
+//                        then the four waves through LDS), 256 to 1 per launch.  No float atomics anywhere.
+//   k_weld_reverse       every face reversed (the inversion).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mm_device.h"
+
+namespace mm {
+
+static constexpr int kWeldThreads = 256;
+static constexpr int32_t kWeldEmpty = -1;
+static constexpr unsigned long long kEdgeEmpty = ~0ull;               // no key: both ends < 2^31 never give it
+
+static __device__ __forceinline__ long long weld_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
+static __device__ __forceinline__ long long weld_stride() { return (long long)gridDim.x * blockDim.x; }
+
+static __device__ __forceinline__ unsigned long long weld_mix(unsigned long long h, unsigned long long k)
+{
+    h ^= k + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+    h *= 0xBF58476D1CE4E5B9ull;
+    return h ^ (h >> 31);
+}
+
+// the weld key of one vertex; false where it matches nothing (a non-finite coordinate or a scaled magnitude >= 2^62)
+static __device__ __forceinline__ bool weld_key(const double* __restrict__ v, long long i, double scale, long long k[3])
+{
+    bool ok = true;
+    for (int c = 0; c < 3; ++c) {
+        const double s = v[3 * i + c] * scale;
+        ok = ok && (fabs(s) < 4611686018427387904.0);                 // false for NaN as well
+        k[c] = ok ? (long long)rint(s) : 0;
+    }
+    return ok;
+}
+
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_mark(const int32_t* __restrict__ face, long long nf, uint8_t* __restrict__ ref)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        ref[face[3 * f]] = 1;
+        ref[face[3 * f + 1]] = 1;
+        ref[face[3 * f + 2]] = 1;
+    }
+}
+
+// rep[v] = the slot of v's key, -2 for a referenced vertex without a key, -1 unreferenced
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_vertex_insert(const double* __restrict__ v, long long nv, const uint8_t* __restrict__ ref, double scale,
+                     int32_t* __restrict__ table, unsigned long long mask, int shift, int32_t* __restrict__ rep)
+{
+    for (long long i = weld_tid(); i < nv; i += weld_stride()) {
+        if (!ref[i]) { rep[i] = -1; continue; }
+        long long k[3];
+        if (!weld_key(v, i, scale, k)) { rep[i] = -2; continue; }
+        unsigned long long s = weld_mix(weld_mix(weld_mix(0, (unsigned long long)k[0]), (unsigned long long)k[1]),
+                                        (unsigned long long)k[2]) >> shift;
+        for (;;) {
+            int32_t o = atomicCAS(&table[s], kWeldEmpty, (int32_t)i);
+            if (o != kWeldEmpty) {
+                long long q[3];
+                weld_key(v, o, scale, q);                              // a holder always has a key
+                if (q[0] != k[0] || q[1] != k[1] || q[2] != k[2]) { s = (s + 1) & mask; continue; }
+                if ((int32_t)i < o) atomicMin(&table[s], (int32_t)i);
+            }
+            rep[i] = (int32_t)s;
+            break;
+        }
+    }
+}
+
+// counts[0] += the unreferenced vertices (one atomicAdd per wave); nv_padded is a multiple of the workgroup
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_vertex_rep(long long nv_padded, long long nv, const int32_t* __restrict__ table, int32_t* __restrict__ rep,
+                  uint8_t* __restrict__ keep, unsigned long long* __restrict__ counts)
+{
+    const int lane = (int)__lane_id();
+    for (long long i = weld_tid(); i < nv_padded; i += weld_stride()) {
+        bool unref = false;
+        if (i < nv) {
+            const int32_t s = rep[i];
+            const int32_t r = s >= 0 ? table[s] : (s == -2 ? (int32_t)i : -1);
+            rep[i] = r;
+            keep[i] = r == (int32_t)i;
+            unref = r < 0;
+        }
+        const unsigned long long b = __ballot(unref);
+        if (lane == 0 && b) atomicAdd(&counts[0], (unsigned long long)__popcll(b));
+    }
+}
+
+static __device__ __forceinline__ void weld_sort3(int32_t a, int32_t b, int32_t c, int32_t k[3])
+{
+    int32_t t;
+    if (a > b) { t = a; a = b; b = t; }
+    if (b > c) { t = b; b = c; c = t; }
+    if (a > b) { t = a; a = b; b = t; }
+    k[0] = a; k[1] = b; k[2] = c;
+}
+
+// vmap[v] = the new index of the vertex v was welded into (-1 unreferenced): vidx is the scan of keep
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_vmap(long long nv, const int32_t* __restrict__ rep, const int32_t* __restrict__ vidx, int32_t* __restrict__ vmap)
+{
+    for (long long i = weld_tid(); i < nv; i += weld_stride()) vmap[i] = rep[i] >= 0 ? vidx[rep[i]] : -1;
+}
+
+// frep[f] = the slot of f's vertex set in the welded numbering, -1 when two corners coincide there
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_face_insert(const int32_t* __restrict__ face, long long nf, const int32_t* __restrict__ vmap,
+                   int32_t* __restrict__ table, unsigned long long mask, int shift, int32_t* __restrict__ frep)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        const int32_t a = vmap[face[3 * f]], b = vmap[face[3 * f + 1]], c = vmap[face[3 * f + 2]];
+        if (a == b || b == c || a == c) { frep[f] = -1; continue; }
+        int32_t k[3];
+        weld_sort3(a, b, c, k);
+        unsigned long long s = weld_mix(weld_mix(0, ((unsigned long long)k[0] << 32) | (unsigned long long)k[1]),
+                                        (unsigned long long)k[2]) >> shift;
+        for (;;) {
+            int32_t o = atomicCAS(&table[s], kWeldEmpty, (int32_t)f);
+            if (o != kWeldEmpty) {
+                int32_t q[3];
+                weld_sort3(vmap[face[3 * (long long)o]], vmap[face[3 * (long long)o + 1]],
+                           vmap[face[3 * (long long)o + 2]], q);
+                if (q[0] != k[0] || q[1] != k[1] || q[2] != k[2]) { s = (s + 1) & mask; continue; }
+                if ((int32_t)f < o) atomicMin(&table[s], (int32_t)f);
+            }
+            frep[f] = (int32_t)s;
+            break;
+        }
+    }
+}
+
+// fkeep[f] = 1 for the survivors; counts[0] += degenerate faces, counts[1] += repeated faces (one atomicAdd per wave)
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_face_rep(long long nf_padded, long long nf, const int32_t* __restrict__ table, const int32_t* __restrict__ frep,
+                uint8_t* __restrict__ fkeep, unsigned long long* __restrict__ counts)
+{
+    const int lane = (int)__lane_id();
+    for (long long f = weld_tid(); f < nf_padded; f += weld_stride()) {
+        bool degenerate = false, repeated = false;
+        if (f < nf) {
+            const int32_t s = frep[f];
+            degenerate = s < 0;
+            repeated = !degenerate && table[s] != (int32_t)f;
+            fkeep[f] = !degenerate && !repeated;
+        }
+        const unsigned long long bd = __ballot(degenerate), br = __ballot(repeated);
+        if (lane == 0 && bd) atomicAdd(&counts[0], (unsigned long long)__popcll(bd));
+        if (lane == 0 && br) atomicAdd(&counts[1], (unsigned long long)__popcll(br));
+    }
+}
+
+static __device__ __forceinline__ void weld_edge(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
+                                                 unsigned int* __restrict__ own, unsigned long long mask, int shift,
+                                                 int32_t u, int32_t v, unsigned int f)
+{
+    const unsigned long long lo = (unsigned long long)(u < v ? u : v), hi = (unsigned long long)(u < v ? v : u);
+    const unsigned long long key = (lo << 32) | hi;
+    unsigned long long s = (key * 0x9E3779B97F4A7C15ull) >> shift;
+    for (;;) {
+        const unsigned long long prev = atomicCAS(&keys[s], kEdgeEmpty, key);
+        if (prev == kEdgeEmpty || prev == key) {
+            const unsigned int p = atomicAdd(&cnt[s], 1u);
+            if (p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
+            return;
+        }
+        s = (s + 1) & mask;
+    }
+}
+
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_edge_insert(const int32_t* __restrict__ face, long long nf, unsigned long long* __restrict__ keys,
+                   unsigned int* __restrict__ cnt, unsigned int* __restrict__ own, unsigned long long mask, int shift)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
+        weld_edge(keys, cnt, own, mask, shift, a, b, (unsigned int)f);
+        weld_edge(keys, cnt, own, mask, shift, b, c, (unsigned int)f);
+        weld_edge(keys, cnt, own, mask, shift, c, a, (unsigned int)f);
+    }
+}
+
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_link_init(unsigned int* __restrict__ link, long long nf)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) link[f] = (unsigned int)f << 1;
+}
+
+static __device__ __forceinline__ unsigned int weld_load(const unsigned int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// the root of x and, xor-ed into *par, x's parity to it; every step moves x's link to its grandparent (any ancestor with
+// the parities added is a valid link, whichever lane writes it last)
+static __device__ __forceinline__ unsigned int weld_find(unsigned int* __restrict__ link, unsigned int x, unsigned int* par)
+{
+    unsigned int wx = weld_load(&link[x]);
+    while ((wx >> 1) != x) {
+        const unsigned int p = wx >> 1;
+        const unsigned int wp = weld_load(&link[p]);
+        if ((wp >> 1) != p) __atomic_store_n(&link[x], (wp & ~1u) | ((wx ^ wp) & 1u), __ATOMIC_RELAXED);
+        *par ^= wx & 1u;
+        x = p;
+        wx = wp;
+    }
+    return x;
+}
+
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_hook(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
+            const unsigned int* __restrict__ own, unsigned long long cap, unsigned int* __restrict__ link)
+{
+    for (unsigned long long s = (unsigned long long)weld_tid(); s < cap; s += (unsigned long long)weld_stride()) {
+        if (keys[s] == kEdgeEmpty || cnt[s] != 2u) continue;
+        const unsigned int oa = own[2 * s], ob = own[2 * s + 1];
+        unsigned int a = oa >> 1, b = ob >> 1;
+        if (a == b) continue;
+        unsigned int pa = 0, pb = 0;
+        const unsigned int e = ((oa ^ ob) & 1u) ^ 1u;                   // same direction: the two faces differ by a flip
+        for (;;) {
+            a = weld_find(link, a, &pa);
+            b = weld_find(link, b, &pb);
+            if (a == b) break;                                          // joined already (or not orientable)
+            const unsigned int hi = a < b ? b : a, lo = a < b ? a : b;
+            if (atomicCAS(&link[hi], hi << 1, (lo << 1) | (pa ^ pb ^ e)) == hi << 1) break;
+        }
+    }
+}
+
+// one round of pointer jumping; *changed = 1 where a link moved
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_jump(unsigned int* __restrict__ link, long long nf, unsigned int* __restrict__ changed)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        const unsigned int wx = weld_load(&link[f]);
+        const unsigned int p = wx >> 1;
+        const unsigned int wp = weld_load(&link[p]);
+        if ((wp >> 1) != p) {
+            __atomic_store_n(&link[f], (wp & ~1u) | ((wx ^ wp) & 1u), __ATOMIC_RELAXED);
+            *changed = 1u;
+        }
+    }
+}
+
+// links are flat (every parent a root): reverse the faces of odd parity; *n_flipped += their number
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_flip(int32_t* __restrict__ face, long long nf_padded, long long nf, const unsigned int* __restrict__ link,
+            unsigned long long* __restrict__ n_flipped)
+{
+    const int lane = (int)__lane_id();
+    for (long long f = weld_tid(); f < nf_padded; f += weld_stride()) {
+        const bool flip = f < nf && (link[f] & 1u);
+        if (flip) {
+            const int32_t a = face[3 * f], c = face[3 * f + 2];
+            face[3 * f] = c;
+            face[3 * f + 2] = a;
+        }
+        const unsigned long long b = __ballot(flip);
+        if (lane == 0 && b) atomicAdd(n_flipped, (unsigned long long)__popcll(b));
+    }
+}
+
+// counts[0] += edges owned once, counts[1] += edges owned more than twice, counts[2] += edges owned twice whose faces
+// (with the flips of `link`, flat) traverse them in the same direction.  cap is a multiple of kWeldThreads.
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_edge_report(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
+                   const unsigned int* __restrict__ own, unsigned long long cap, const unsigned int* __restrict__ link,
+                   unsigned long long* __restrict__ counts)
+{
+    const int lane = (int)__lane_id();
+    for (unsigned long long s = (unsigned long long)weld_tid(); s < cap; s += (unsigned long long)weld_stride()) {
+        const bool used = keys[s] != kEdgeEmpty;
+        const unsigned int c = used ? cnt[s] : 0u;
+        bool conflict = false;
+        if (c == 2u) {
+            const unsigned int oa = own[2 * s], ob = own[2 * s + 1];
+            const unsigned int fa = link ? (link[oa >> 1] & 1u) : 0u, fb = link ? (link[ob >> 1] & 1u) : 0u;
+            conflict = (((oa ^ fa) ^ (ob ^ fb)) & 1u) == 0u;
+        }
+        const unsigned long long b1 = __ballot(c == 1u), b3 = __ballot(c > 2u), bc = __ballot(conflict);
+        if (lane == 0 && b1) atomicAdd(&counts[0], (unsigned long long)__popcll(b1));
+        if (lane == 0 && b3) atomicAdd(&counts[1], (unsigned long long)__popcll(b3));
+        if (lane == 0 && bc) atomicAdd(&counts[2], (unsigned long long)__popcll(bc));
+    }
+}
+
+// term[f] = v0 . (v1 x v2), unfused, in the order include/mm_ccta.h states
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_terms(const double* __restrict__ v, const int32_t* __restrict__ face, long long nf, double* __restrict__ term)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        const double* p0 = v + 3 * (long long)face[3 * f];
+        const double* p1 = v + 3 * (long long)face[3 * f + 1];
+        const double* p2 = v + 3 * (long long)face[3 * f + 2];
+        const double cx = p1[1] * p2[2] - p1[2] * p2[1];
+        const double cy = p1[2] * p2[0] - p1[0] * p2[2];
+        const double cz = p1[0] * p2[1] - p1[1] * p2[0];
+        term[f] = (p0[0] * cx + p0[1] * cy) + p0[2] * cz;
+    }
+}
+
+// out[b] = the adjacent-pair tree over in[256 b .. 256 b + 255], entries at or beyond n reading +0.0.  `levels` (1..8)
+// of the tree are summed: fewer than 8 only in the last launch, where the padded length is below 256 (the result is
+// then in out[0]; the lanes beyond 2^levels hold other sub-trees and are not read).
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_pair_sum(const double* __restrict__ in, long long n, int levels, double* __restrict__ out)
+{
+    __shared__ double s_wave[kWeldThreads / 64];
+    const long long i = (long long)blockIdx.x * kWeldThreads + threadIdx.x;
+    double x = i < n ? in[i] : 0.0;
+    for (int l = 0; l < 6 && l < levels; ++l) x = x + __shfl_xor(x, 1 << l);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = s_wave[0];
+        if (levels > 6) r = s_wave[0] + s_wave[1];
+        if (levels > 7) r = r + (s_wave[2] + s_wave[3]);
+        out[blockIdx.x] = r;
+    }
+}
+
+__global__ void __launch_bounds__(kWeldThreads)
+k_weld_reverse(int32_t* __restrict__ face, long long nf)
+{
+    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+        const int32_t a = face[3 * f], c = face[3 * f + 2];
+        face[3 * f] = c;
+        face[3 * f + 2] = a;
+    }
+}
+
+static unsigned weld_grid(long long n)
+{
+    const long long b = (n + kWeldThreads - 1) / kWeldThreads;
+    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
+static long long weld_pad(long long n) { return (n + kWeldThreads - 1) / kWeldThreads * kWeldThreads; }
+
+#define WELD_LAUNCH(kernel, n, ...)                                                                        \
+    do {                                                                                                   \
+        hipLaunchKernelGGL(kernel, dim3(weld_grid(n)), dim3(kWeldThreads), 0, s, __VA_ARGS__);             \
+        const hipError_t he__ = hipGetLastError();                                                         \
+        if (he__ != hipSuccess) return he__;                                                               \
+    } while (0)
+
+hipError_t launch_weld_vertices(const double* v, long long nv, const int32_t* face, long long nf, double scale,
+                                uint8_t* ref, int32_t* table, int log2_cap, int32_t* rep, uint8_t* keep,
+                                unsigned long long* counts, hipStream_t s)
+{
+    const unsigned long long cap = 1ull << log2_cap;
+    hipError_t he;
+    if ((he = hipMemsetAsync(table, 0xFF, cap * 4, s)) != hipSuccess) return he;
+    if (nv <= 0) return hipSuccess;
+    if ((he = hipMemsetAsync(ref, 0, (size_t)nv, s)) != hipSuccess) return he;
+    if (nf > 0) WELD_LAUNCH(k_weld_mark, nf, face, nf, ref);
+    WELD_LAUNCH(k_weld_vertex_insert, nv, v, nv, ref, scale, table, cap - 1, 64 - log2_cap, rep);
+    WELD_LAUNCH(k_weld_vertex_rep, nv, weld_pad(nv), nv, table, rep, keep, counts);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_faces(const int32_t* face, long long nf, long long nv, const int32_t* rep, const int32_t* vidx,
+                             int32_t* vmap, int32_t* table, int log2_cap, int32_t* frep, uint8_t* fkeep,
+                             unsigned long long* counts, hipStream_t s)
+{
+    const unsigned long long cap = 1ull << log2_cap;
+    hipError_t he;
+    if ((he = hipMemsetAsync(table, 0xFF, cap * 4, s)) != hipSuccess) return he;
+    if (nf <= 0) return hipSuccess;
+    WELD_LAUNCH(k_weld_vmap, nv, nv, rep, vidx, vmap);
+    WELD_LAUNCH(k_weld_face_insert, nf, face, nf, vmap, table, cap - 1, 64 - log2_cap, frep);
+    WELD_LAUNCH(k_weld_face_rep, nf, weld_pad(nf), nf, table, frep, fkeep, counts);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_edges(const int32_t* face, long long nf, unsigned long long* keys, unsigned int* cnt,
+                             unsigned int* own, int log2_cap, hipStream_t s)
+{
+    const unsigned long long cap = 1ull << log2_cap;
+    hipError_t he;
+    if ((he = hipMemsetAsync(keys, 0xFF, cap * 8, s)) != hipSuccess) return he;
+    if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
+    if (nf > 0) WELD_LAUNCH(k_weld_edge_insert, nf, face, nf, keys, cnt, own, cap - 1, 64 - log2_cap);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_hook(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
+                            int log2_cap, unsigned int* link, long long nf, hipStream_t s)
+{
+    if (nf <= 0) return hipSuccess;
+    const unsigned long long cap = 1ull << log2_cap;
+    WELD_LAUNCH(k_weld_link_init, nf, link, nf);
+    WELD_LAUNCH(k_weld_hook, (long long)cap, keys, cnt, own, cap, link);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_jump(unsigned int* link, long long nf, unsigned int* changed, hipStream_t s)
+{
+    hipError_t he;
+    if ((he = hipMemsetAsync(changed, 0, 4, s)) != hipSuccess) return he;
+    if (nf > 0) WELD_LAUNCH(k_weld_jump, nf, link, nf, changed);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_flip(int32_t* face, long long nf, const unsigned int* link, unsigned long long* n_flipped,
+                            hipStream_t s)
+{
+    if (nf > 0) WELD_LAUNCH(k_weld_flip, nf, face, weld_pad(nf), nf, link, n_flipped);
+    return hipSuccess;
+}
+
+hipError_t launch_weld_edge_report(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
+                                   int log2_cap, const unsigned int* link, unsigned long long* counts, hipStream_t s)
+{
+    const unsigned long long cap = 1ull << log2_cap;                   // at least kWeldThreads (the host sizes it)
+    WELD_LAUNCH(k_weld_edge_report, (long long)cap, keys, cnt, own, cap, link, counts);
+    return hipSuccess;
+}
+
+size_t weld_sum_scratch(long long nf) { return (size_t)((nf + kWeldThreads - 1) / kWeldThreads) + 1; }
+
+// *out = the adjacent-pair tree of the nf volume terms (padded with +0.0 to a power of two); a and b are scratch of nf
+// and weld_sum_scratch(nf) doubles
+hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
+                              hipStream_t s)
+{
+    if (nf <= 0) return hipMemsetAsync(out, 0, 8, s);
+    WELD_LAUNCH(k_weld_terms, nf, v, face, nf, a);
+    int levels = 0;                                                    // the padded length is 2^levels
+    while ((1ll << levels) < nf) ++levels;
+    long long n = nf;
+    double* in = a;
+    double* to = b;
+    for (;;) {
+        const int now = levels >= 8 ? 8 : levels;
+        const long long blocks = (n + kWeldThreads - 1) / kWeldThreads;
+        const bool last = levels <= 8;
+        hipLaunchKernelGGL(k_weld_pair_sum, dim3((unsigned)blocks), dim3(kWeldThreads), 0, s, in, n, now, last ? out : to);
+        const hipError_t he = hipGetLastError();
+        if (he != hipSuccess) return he;
+        if (last) return hipSuccess;
+        levels -= 8;
+        n = blocks;
+        double* t = in; in = to; to = t;
+    }
+}
+
+hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s)
+{
+    if (nf > 0) WELD_LAUNCH(k_weld_reverse, nf, face, nf);
+    return hipSuccess;
+}
+
+}  // namespace mm
