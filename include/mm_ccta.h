@@ -21,6 +21,7 @@
  *   src/ccta/discretizing/resampling.rs:11-229       create_uniform_contours, resample_spline
  *   src/ccta/discretizing.rs:13-22, discretizing/vessel_tree.rs:21-83  discretize_vessel_rs, from_results_dict
  *   src/ccta/binding/ccta_py.rs:541-580, label_coronary.rs:428-455  keep_largest_connected_component
+ *   multimodars/ccta/labeling.py:415-487           label_branches
  * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481, 724-920 (discretize_vessel,
  * discretize_vessel_tree)
  * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
@@ -36,7 +37,8 @@
  * nearest-anchor assignment and plane projection run on the device in exact f64 (mm_slice_kernels.hip); its anchors
  * and spline resampling are host f64.  The mesh morphing's nearest-centerline search and radial move run on the device
  * in exact f64 (mm_morph_kernels.hip).  The mesh trimming's face membership, open-edge counting and compaction run on the
- * device (mm_trim_kernels.hip); its ring logic on the rim is host C++.
+ * device (mm_trim_kernels.hip); its ring logic on the rim is host C++.  The branch labelling's membership masks are one device
+ * pass in exact f64 (mm_branch_kernels.hip); its lists are read off the masks on the host.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -326,6 +328,35 @@ int     mm_stitch_rings(const double* ring_xyz, int64_t n_b, const double* iv_xy
  * point is MM_ERR_INVALID. */
 int     mm_tube_faces(const double* contours_xyz, int64_t n_contours, int64_t n_points, const double centroid0[3],
                       int64_t* faces);
+
+/* ---- branch labelling (multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
+
+#define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */
+
+/* masks_out[i] bit b = 1 iff some centerline point with branch_id b lies within squared distance <= radius * radius of
+ * point i: the test of mm_centerline_bounded_points (the same operands in the same order, exact f64), so the mask equals
+ * one call of that function per branch, bit for bit, from one upload and one launch (mm_branch_kernels.hip).  An empty
+ * point set or centerline, like a NULL array, is MM_ERR_INVALID. */
+int     mm_branch_masks(mm_engine* e, const mm_clpoint* cl, int64_t ncl, const double* pts_xyz, int64_t n, double radius,
+                        uint64_t* masks_out);
+/* Centerline points of one LDS tile of that kernel (a longer centerline is staged tile after tile). */
+int     mm_branch_tile_points(void);
+/* The lists of label_branches from n masks, host only.  MAIN = the bits of main_ids (n_main of them, each below
+ * MM_BRANCH_MASK_BITS).  main_idx: the points with mask & MAIN != 0; side_idx: all others; both in input order, capacity
+ * n, nullable.  side_k of branch k (0 <= k < n_branches <= MM_BRANCH_MASK_BITS): the side points with bit k, in input
+ * order, at side_k_idx[side_k_off[k] .. side_k_off[k + 1]) (side_k_off: n_branches + 1 entries; a main branch's range is
+ * empty; a point near several side branches is in each of their lists).  counts[3] = {main, side, all side_k entries};
+ * side_k_idx (nullable) is written only where counts[2] <= side_k_cap. */
+int     mm_branch_select(const uint64_t* masks, int64_t n, const uint32_t* main_ids, int64_t n_main, int64_t n_branches,
+                         int64_t* main_idx, int64_t* side_idx, int64_t* side_k_off, int64_t* side_k_idx, int64_t side_k_cap,
+                         int64_t* counts);
+/* label_branches (labeling.py:453-487) in one launch: mm_branch_masks into masks_out (n entries), then mm_branch_select
+ * on them.  Equal to the reference's sequence of per-branch searches and set differences, duplicated points included:
+ * points with equal coordinates have equal masks. */
+int     mm_label_branches(mm_engine* e, const mm_clpoint* cl, int64_t ncl, const double* pts_xyz, int64_t n, double radius,
+                          const uint32_t* main_ids, int64_t n_main, int64_t n_branches, uint64_t* masks_out,
+                          int64_t* main_idx, int64_t* side_idx, int64_t* side_k_off, int64_t* side_k_idx, int64_t side_k_cap,
+                          int64_t* counts);
 
 #ifdef __cplusplus
 }

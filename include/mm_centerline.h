@@ -69,6 +69,51 @@ int64_t mm_centerline_find_ref_idx(const mm_clpoint* cl, int64_t n, const double
 int64_t mm_centerline_preprocess(const mm_clpoint* cl, int64_t n, const mm_geometry* ref_mesh,
                                  mm_clpoint* out, int64_t cap, double* spacing);
 
+/* ---- branch structure (centerline.rs:64-937), host f64 in the reference's operation order (mm_cl_branches.cpp).
+ * A branch is a maximal run of consecutive points with one branch_id (the reference's branch_start_indices are the
+ * first indices of those runs); `branch` arguments count runs from 0, which is the branch_id wherever one of these
+ * functions has numbered them.  ContourPoint.point_index is the position in the array.  Every function writes a new
+ * centerline into out (never the input array) and returns its number of points, or a negative error; branch ids are
+ * renumbered 0, 1, ... and tangents recomputed inside branches (recompute_tangents, :377-391) wherever the reference
+ * rebuilds, and the input is copied unchanged wherever the reference returns early. */
+
+/* calculate_branches (:78-155): the branches of a centerline whose segments were written one after the other.  Gaps
+ * above p95(consecutive spacing) * spacing_tolerance start a segment; segments are joined by one edge at their closest
+ * pair where that is within the threshold; the longest path by arc length (double BFS from point 0) becomes branch 0,
+ * the remaining components side branches in descending size (ties: discovery order), each walked as a chain; components
+ * of fewer than 5 points are dropped.  out holds n points.  A coordinate that is not finite is MM_ERR_INVALID (the
+ * reference's sort of the spacings has no defined order then). */
+int64_t mm_centerline_calculate_branches(const mm_clpoint* cl, int64_t n, double spacing_tolerance, mm_clpoint* out);
+/* find_sharp_angles (:436-466): the positions of the interior points of the branch whose opening angle has
+ * cos > cos_threshold (both legs at least 1e-10 long), ascending, into out_idx (capacity n).  An absent branch: 0. */
+int64_t mm_centerline_find_sharp_angles(const mm_clpoint* cl, int64_t n, uint32_t branch, double cos_threshold,
+                                        int64_t* out_idx);
+/* split_branch (:474-505) at position point_index, which both pieces keep; branches re-sorted by descending number of
+ * points (stable).  out holds n + 1 points.  An absent branch, a position outside it or at one of its ends: unchanged. */
+int64_t mm_centerline_split_branch(const mm_clpoint* cl, int64_t n, uint32_t branch, int64_t point_index, mm_clpoint* out);
+/* merge_branches (:512-553): the two branches joined at their closest pair of ends (the first of the four pairings
+ * within 1e-12 of the smallest distance, in the order last-first, last-last, first-first, first-last), re-sorted as
+ * above.  out holds n points.  Equal or absent branches: unchanged. */
+int64_t mm_centerline_merge_branches(const mm_clpoint* cl, int64_t n, uint32_t branch_a, uint32_t branch_b, mm_clpoint* out);
+/* orient_by_max_z (:570-587): branch 0 reversed unless its point of largest z (the LAST of equal maxima) is its first;
+ * every other branch reversed where its last point is nearer to branch 0 (as it then stands) than its first. */
+int64_t mm_centerline_orient_by_max_z(const mm_clpoint* cl, int64_t n, mm_clpoint* out);
+/* orient_to_reference (:599-615): every branch reversed where its last point is strictly nearer than its first to the
+ * reference's first branch (minimum over its points).  An empty reference reverses nothing. */
+int64_t mm_centerline_orient_to_reference(const mm_clpoint* cl, int64_t n, const mm_clpoint* reference, int64_t n_ref,
+                                          mm_clpoint* out);
+/* remove_branch_overlap (:681-692, 877-913): from every side branch, in order, the leading points within branch 0's mean
+ * spacing of a point of branch 0 or of an earlier, already trimmed branch are removed but the last of them (the
+ * junction); a branch wholly within is dropped. */
+int64_t mm_centerline_remove_branch_overlap(const mm_clpoint* cl, int64_t n, mm_clpoint* out);
+/* trim_start (:698-708, 917-937): the first points of branch 0 up to the last whose arc length from the start is
+ * <= mm_len are removed; mm_len <= 0: unchanged. */
+int64_t mm_centerline_trim_start(const mm_clpoint* cl, int64_t n, double mm_len, mm_clpoint* out);
+/* smooth (:798-866): positions replaced by a Gaussian mean over the points with the same branch_id, sigma in points,
+ * truncated at ceil(3 sigma) and at the nearer end of the branch on BOTH sides alike; tangents recomputed; branch ids
+ * kept.  sigma < 1e-12: unchanged. */
+int64_t mm_centerline_smooth(const mm_clpoint* cl, int64_t n, double sigma, mm_clpoint* out);
+
 /* Contour::sort_contour_points (contour.rs:368-405) on n xyz triples, in place. */
 int     mm_sort_contour_points(double* xyz, int64_t n);
 /* Geometry::rotate_geometry (geometry.rs:241-250): every frame about its own centroid, then

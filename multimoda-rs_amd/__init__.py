@@ -20,7 +20,7 @@ from .api import (GeometryPair, align_frames_in_geometries, from_array_doublepai
                   from_array_single, from_array_singlepair, from_file_doublepair, from_file_full,
                   from_file_single, from_file_singlepair)
 from .centerline import (Centerline, align_combined, align_manual, align_three_point, numpy_to_centerline, read_centerline_vtp,
-                         preprocess_centerline)
+                         preprocess_centerline, load_centerline, prepare_centerline)
 from . import centerline
 from . import ccta
 from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_simple, clean_outlier_points,
@@ -32,7 +32,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    scale_region_centerline_morphing, sync_results_to_mesh, open_boundary_edges, order_boundary_rings,
                    clean_open_boundary, remove_labeled_points_from_mesh, keep_labeled_points_from_mesh,
                    extract_region_with_border_faces, export_section_stl, build_adjacency_map,
-                   fix_mesh_winding, assemble_mesh, stitch_rings, stitch_ccta_to_intravascular, stitch)
+                   fix_mesh_winding, assemble_mesh, stitch_rings, stitch_ccta_to_intravascular, stitch, branch_masks,
+                   label_branches, label_branches_pair, find_sharp_angles, label)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -65,6 +66,8 @@ __all__ = [
     "remove_labeled_points_from_mesh", "keep_labeled_points_from_mesh", "extract_region_with_border_faces",
     "export_section_stl", "build_adjacency_map",
     "fix_mesh_winding", "assemble_mesh", "stitch_rings", "stitch_ccta_to_intravascular", "stitch",
+    "load_centerline", "prepare_centerline", "branch_masks", "label_branches", "label_branches_pair", "find_sharp_angles",
+    "label",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

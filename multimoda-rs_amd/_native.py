@@ -51,6 +51,9 @@ EXPORTS_CENTERLINE = [
     "mm_centerline_from_points", "mm_centerline_find_ref_idx", "mm_centerline_preprocess",
     "mm_sort_contour_points", "mm_rotate_geometry", "mm_apply_transformations", "mm_best_rotation_three_point",
     "mm_refine_alignment_hausdorff", "mm_align_three_point", "mm_align_manual", "mm_align_combined", "mm_align_walls",
+    "mm_centerline_calculate_branches", "mm_centerline_find_sharp_angles", "mm_centerline_split_branch",
+    "mm_centerline_merge_branches", "mm_centerline_orient_by_max_z", "mm_centerline_orient_to_reference",
+    "mm_centerline_remove_branch_overlap", "mm_centerline_trim_start", "mm_centerline_smooth",
 ]
 
 
@@ -108,6 +111,7 @@ EXPORTS_CCTA = [
     "mm_build_adjacency", "mm_boundary_rings", "mm_open_boundary_edges", "mm_clean_open_boundary", "mm_trim_mesh",
     "mm_fix_winding", "mm_mesh_assemble", "mm_assign_rings_to_ends", "mm_ring_start", "mm_ring_direction",
     "mm_stitch_rings", "mm_tube_faces",
+    "mm_branch_masks", "mm_branch_tile_points", "mm_branch_select", "mm_label_branches",
 ]
 
 
@@ -384,6 +388,24 @@ def lib():
     L.mm_refine_alignment_hausdorff.restype = I
     L.mm_refine_alignment_hausdorff.argtypes = [P, P, I, P, I64, I64, D, P, I64, D, D, I64, C.POINTER(D),
                                                 C.POINTER(I64), C.POINTER(D), P, I64, C.POINTER(I64)]
+    L.mm_centerline_calculate_branches.restype = I64
+    L.mm_centerline_calculate_branches.argtypes = [P, I64, D, P]
+    L.mm_centerline_find_sharp_angles.restype = I64
+    L.mm_centerline_find_sharp_angles.argtypes = [P, I64, U32, D, P]
+    L.mm_centerline_split_branch.restype = I64
+    L.mm_centerline_split_branch.argtypes = [P, I64, U32, I64, P]
+    L.mm_centerline_merge_branches.restype = I64
+    L.mm_centerline_merge_branches.argtypes = [P, I64, U32, U32, P]
+    L.mm_centerline_orient_by_max_z.restype = I64
+    L.mm_centerline_orient_by_max_z.argtypes = [P, I64, P]
+    L.mm_centerline_orient_to_reference.restype = I64
+    L.mm_centerline_orient_to_reference.argtypes = [P, I64, P, I64, P]
+    L.mm_centerline_remove_branch_overlap.restype = I64
+    L.mm_centerline_remove_branch_overlap.argtypes = [P, I64, P]
+    L.mm_centerline_trim_start.restype = I64
+    L.mm_centerline_trim_start.argtypes = [P, I64, D, P]
+    L.mm_centerline_smooth.restype = I64
+    L.mm_centerline_smooth.argtypes = [P, I64, D, P]
     L.mm_align_three_point.restype = I
     L.mm_align_three_point.argtypes = [P, I64, P, I, U32, P, P, P, D, I, C.POINTER(D), C.POINTER(D)]
     L.mm_align_walls.restype = I
@@ -491,6 +513,14 @@ def lib():
     L.mm_stitch_rings.argtypes = [P, I64, P, I64, P, P]
     L.mm_tube_faces.restype = I
     L.mm_tube_faces.argtypes = [P, I64, I64, P, P]
+    L.mm_branch_masks.restype = I
+    L.mm_branch_masks.argtypes = [P, P, I64, P, I64, D, P]
+    L.mm_branch_tile_points.restype = I
+    L.mm_branch_tile_points.argtypes = []
+    L.mm_branch_select.restype = I
+    L.mm_branch_select.argtypes = [P, I64, P, I64, I64, P, P, P, P, I64, P]
+    L.mm_label_branches.restype = I
+    L.mm_label_branches.argtypes = [P, P, I64, P, I64, D, P, I64, I64, P, P, P, P, P, I64, P]
     _lib = L
     return L
 

@@ -14,7 +14,10 @@ csrc/mm_nn_kernels.hip); there is no CPU fallback.  The vessel discretisation mi
 multimodars/ccta/discretization_map.py:104-205; implementation src/ccta/discretizing).  The mesh morphing mirrors
 ``label_anomalous_region`` (multimodars/ccta/labeling.py:283-389), ``scale_region_centerline_morphing`` /
 ``sync_results_to_mesh`` (multimodars/ccta/scaling.py:16-80, 301-351) and ``scale`` (multimodars/ccta/__init__.py:171-258);
-its nearest-centerline search runs on the device (csrc/mm_morph_kernels.hip).
+its nearest-centerline search runs on the device (csrc/mm_morph_kernels.hip).  The branch labelling mirrors
+``label_branches`` (multimodars/ccta/labeling.py:415-487), ``label_branches_pair`` / ``find_sharp_angles``
+(multimodars/ccta/discretization_map.py:216-306) and ``label`` (multimodars/ccta/__init__.py:22-168); which branches
+reach a point comes from one launch (csrc/mm_branch_kernels.hip).
 """
 from __future__ import annotations
 
@@ -418,6 +421,122 @@ def label_geometry(mesh, centerline_aorta: Centerline, centerline_rca: Centerlin
     aorta, rca, lca, rca_rm, lca_rm = final_reclassification(v, f, rca_pts, lca_pts, rca_removed, lca_removed)
     return {"mesh": mesh, "aorta_points": aorta, "rca_points": rca, "lca_points": lca, "rca_removed_points": rca_rm,
             "lca_removed_points": lca_rm}
+
+
+# ---- branch labelling (multimodars/ccta/labeling.py:415-487, discretization_map.py:216-306, __init__.py:22-168) -------
+
+_EMPTY_SEARCH = "find_centerline_bounded_points failed because `Centerline` is empty"
+
+
+def branch_masks(centerline: Centerline, points, radius: float, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """One uint64 per point: bit b is set iff some point of ``centerline`` with ``branch_id`` b lies within ``radius``
+    (squared distance <= radius * radius, the test of ``find_centerline_bounded_points_simple``): what one call of that
+    function per branch answers, from one upload and one launch (csrc/mm_branch_kernels.hip).  An empty point set or
+    centerline raises ValueError, as that function does; a ``branch_id`` of 64 or more raises RuntimeError."""
+    p = _p3(points)
+    if p.shape[0] == 0 or len(centerline) == 0:
+        raise ValueError(_EMPTY_SEARCH)
+    masks = np.zeros(p.shape[0], dtype=np.uint64)
+    N.check(N.lib().mm_branch_masks(_engine(engine).handle, N._ptr(centerline.points), len(centerline), N._ptr(p),
+                                    p.shape[0], float(radius), N._ptr(masks)), "branch_masks")
+    return masks
+
+
+def label_branches(centerline: Centerline, results: dict, results_key: str = "rca_points", branch_id=0,
+                   bounding_sphere_radius_mm: float = 3.0, engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/labeling.py:415-487: split ``results[results_key]`` into ``"{key}_main"`` (the points within
+    ``bounding_sphere_radius_mm`` of a main branch: ``branch_id``, an int or a list of ints), ``"{key}_side"`` (all
+    others) and ``"{key}_side_{k}"`` for every other branch k of ``centerline`` (the side points within the radius of
+    branch k; a point near two side branches is in both), all in input order with duplicates kept, as ``(n, 3)``
+    arrays.  The reference searches the points once per branch; here every point's branches come from one launch
+    (``branch_masks``) and the lists are read off the masks.  Mutates and returns ``results``.  Raises what the
+    reference's sequence raises: ValueError for a branch the centerline does not have and for an empty point list or an
+    empty remainder when a search would run on it (the keys written before that stay)."""
+    branch_ids = [int(branch_id)] if isinstance(branch_id, (int, np.integer)) else [int(b) for b in branch_id]
+    p = _p3(results[results_key])
+    present = set(int(b) for b in np.unique(centerline.points["branch_id"]))
+
+    def need(b):
+        if b not in present:
+            raise ValueError(f"branch_id {b} not found in centerline")        # get_branch
+
+    for b in branch_ids:
+        need(b)
+        if p.shape[0] == 0:
+            raise ValueError(_EMPTY_SEARCH)
+    n, n_branches = p.shape[0], len(centerline.branch_start_indices)
+    side_ids = [k for k in range(n_branches) if k not in set(branch_ids)]
+    nb = min(n_branches, 64)
+    main_idx, side_idx = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    off, counts = np.zeros(nb + 1, dtype=np.int64), np.zeros(3, dtype=np.int64)
+    side_k = np.zeros(2 * n, dtype=np.int64)
+    if n:
+        ids = np.array(branch_ids, dtype=np.uint32)
+        masks = np.zeros(n, dtype=np.uint64)
+        L = N.lib()
+        N.check(L.mm_label_branches(_engine(engine).handle, N._ptr(centerline.points), len(centerline), N._ptr(p), n,
+                                    float(bounding_sphere_radius_mm), N._ptr(ids), len(ids), nb, N._ptr(masks),
+                                    N._ptr(main_idx), N._ptr(side_idx), N._ptr(off), N._ptr(side_k), side_k.shape[0],
+                                    N._ptr(counts)), "label_branches")
+        if int(counts[2]) > side_k.shape[0]:                # many points near several side branches: fill from the masks
+            side_k = np.zeros(int(counts[2]), dtype=np.int64)
+            N.check(L.mm_branch_select(N._ptr(masks), n, N._ptr(ids), len(ids), nb, None, None, N._ptr(off),
+                                       N._ptr(side_k), side_k.shape[0], N._ptr(counts)), "label_branches")
+    main_points, side_points = p[main_idx[:int(counts[0])]], p[side_idx[:int(counts[1])]]
+    results[f"{results_key}_main"] = main_points
+    results[f"{results_key}_side"] = side_points
+    print(f"\nBranch labeling for '{results_key}' (branch_ids={branch_ids}):")
+    print(f"  {results_key}_main: {len(main_points)}")
+    print(f"  {results_key}_side: {len(side_points)}")
+    for k in side_ids:
+        need(k)
+        if side_points.shape[0] == 0:
+            raise ValueError(_EMPTY_SEARCH)
+        pts_k = p[side_k[int(off[k]):int(off[k + 1])]]
+        results[f"{results_key}_side_{k}"] = pts_k
+        print(f"  {results_key}_side_{k}: {len(pts_k)}")
+    return results
+
+
+def label_branches_pair(rca_cl: Centerline, lca_cl: Centerline, results_dict: dict, control_plot: bool = False,
+                        engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/discretization_map.py:216-263: ``label_branches`` for ``"rca_points"`` along ``rca_cl``, then
+    for ``"lca_points"`` along ``lca_cl`` (branch 0 the main vessel, radius 3 mm): the keys ``discretize_vessel_tree``
+    reads.  The centerlines are expected prepared (``prepare_centerline``).  ``control_plot`` is accepted and ignored."""
+    results_dict = label_branches(rca_cl, results_dict, engine=engine)
+    results_dict = label_branches(lca_cl, results_dict, results_key="lca_points", engine=engine)
+    return results_dict
+
+
+def find_sharp_angles(cl: Centerline, branch_id: int, cos_threshold: float = 0.0, control_plot: bool = False) -> list:
+    """multimodars/ccta/discretization_map.py:266-306: ``cl.find_sharp_angles`` with the reference's log line; the
+    global point indices ``split_branch`` takes.  ``control_plot`` is accepted and ignored."""
+    positions = cl.find_sharp_angles(branch_id, cos_threshold)
+    print(f"Branch {branch_id}: {len(positions)} sharp angle(s) at point_index {positions}")
+    return positions
+
+
+def label(mesh, path_centerline_aorta, path_centerline_rca, path_centerline_lca, aligned_frames,
+          acute_takeoff_rca: bool = False, acute_takeoff_lca: bool = False, range_mm_takeoff_rca: float = 60.0,
+          range_mm_takeoff_lca: float = 60.0, step_size_mm: float = 1.0, bounding_sphere_radius_mm_rca: float = 3.0,
+          bounding_sphere_radius_mm_lca: float = 3.0, tolerance_float: float = 1e-6, control_plot: bool = True,
+          engine: Optional[N.Engine] = None) -> dict:
+    """multimodars/ccta/__init__.py:22-168: load the three centerlines (``load_centerline``: a Centerline, an array, a
+    ``.vtp`` or a comma-delimited file), orient the aorta by its highest point and the coronaries towards the aorta,
+    ``label_geometry``, then ``label_anomalous_region`` along the RCA if its take-off is acute, else along the LCA if
+    that one is.  ``mesh`` is what ``label_geometry`` takes (no mesh file is read); ``aligned_frames`` what
+    ``label_anomalous_region`` takes; ``control_plot`` is accepted and ignored."""
+    from .centerline import load_centerline
+    ao_cl = load_centerline(path_centerline_aorta, "Aorta").orient_by_max_z()
+    rca_cl = load_centerline(path_centerline_rca, "RCA").orient_to_reference(ao_cl)
+    lca_cl = load_centerline(path_centerline_lca, "LCA").orient_to_reference(ao_cl)
+    results = label_geometry(mesh, ao_cl, rca_cl, lca_cl, acute_takeoff_rca, acute_takeoff_lca, range_mm_takeoff_rca,
+                             range_mm_takeoff_lca, step_size_mm, bounding_sphere_radius_mm_rca,
+                             bounding_sphere_radius_mm_lca, tolerance_float, control_plot, engine=engine)
+    if acute_takeoff_rca or acute_takeoff_lca:
+        key, cl = ("rca_points", rca_cl) if acute_takeoff_rca else ("lca_points", lca_cl)
+        results = label_anomalous_region(cl, aligned_frames, results, results_key=key, engine=engine)
+    return results
 
 
 # ---- vessel discretisation (src/ccta/discretizing) ------------------------------------------------------------------

@@ -157,6 +157,71 @@ class Centerline:
         r = np.ascontiguousarray(np.asarray(reference_point, dtype=np.float64).reshape(3))
         return int(N.lib().mm_centerline_find_ref_idx(N._ptr(self.points), len(self), N._ptr(r)))
 
+    # -- branch structure (centerline.rs:64-937; csrc/mm_cl_branches.cpp).  Every method returns a new centerline, as
+    #    the reference's PyCenterline methods do (py_centerline.rs); `branch_id` counts branches from 0 ---------------
+    def _derive(self, fn, *args, extra: int = 0, what: str = "") -> "Centerline":
+        out = np.zeros(len(self) + extra, dtype=CL_DTYPE)
+        n = fn(N._ptr(self.points), len(self), *args, N._ptr(out))
+        if n < 0:
+            N.check(int(n), what)
+        return Centerline(out[:int(n)].copy())
+
+    def calculate_branches(self, spacing_tolerance: float) -> "Centerline":
+        """Centerline::calculate_branches (centerline.rs:78-155): find the branches of a centerline whose vessel segments
+        were written one after the other (a CSV export).  Consecutive gaps above ``spacing_tolerance`` times the 95th
+        percentile spacing start a segment; segments are joined at their closest point pair; the longest path by arc
+        length becomes branch 0, the other components side branches in descending size; components of fewer than 5
+        points are dropped.  Non-finite coordinates raise RuntimeError."""
+        return self._derive(N.lib().mm_centerline_calculate_branches, float(spacing_tolerance), what="calculate_branches")
+
+    def find_sharp_angles(self, branch_id: int, cos_threshold: float) -> list:
+        """Centerline::find_sharp_angles (:436-466): the global indices of the interior points of ``branch_id`` whose
+        opening angle has a cosine above ``cos_threshold`` (0.0: below 90 degrees, 0.5: below 60)."""
+        if branch_id < 0 or branch_id > 0xFFFFFFFF:
+            raise OverflowError("branch_id must fit an unsigned 32-bit integer")
+        idx = np.zeros(max(len(self), 1), dtype=np.int64)
+        n = N.lib().mm_centerline_find_sharp_angles(N._ptr(self.points), len(self), int(branch_id), float(cos_threshold),
+                                                    N._ptr(idx))
+        if n < 0:
+            N.check(int(n), "find_sharp_angles")
+        return [int(i) for i in idx[:int(n)]]
+
+    def split_branch(self, branch_id: int, point_index: int) -> "Centerline":
+        """Centerline::split_branch (:474-505): ``branch_id`` cut at the global ``point_index`` (kept by both pieces);
+        branches re-sorted by descending number of points.  A position outside the branch or at its ends changes
+        nothing."""
+        return self._derive(N.lib().mm_centerline_split_branch, int(branch_id), int(point_index), extra=1,
+                            what="split_branch")
+
+    def merge_branches(self, branch_id_a: int, branch_id_b: int) -> "Centerline":
+        """Centerline::merge_branches (:512-553): the two branches joined at their closest ends, branches re-sorted."""
+        return self._derive(N.lib().mm_centerline_merge_branches, int(branch_id_a), int(branch_id_b), what="merge_branches")
+
+    def orient_by_max_z(self) -> "Centerline":
+        """Centerline::orient_by_max_z (:570-587): branch 0 starts at its highest point, side branches at the end nearer
+        to branch 0.  For a centerline with nothing to orient against (the aorta)."""
+        return self._derive(N.lib().mm_centerline_orient_by_max_z, what="orient_by_max_z")
+
+    def orient_to_reference(self, reference: "Centerline") -> "Centerline":
+        """Centerline::orient_to_reference (:599-615): every branch starts at its end nearer to ``reference``'s branch 0
+        (for a coronary: the aorta)."""
+        return self._derive(N.lib().mm_centerline_orient_to_reference, N._ptr(reference.points), len(reference),
+                            what="orient_to_reference")
+
+    def remove_branch_overlap(self) -> "Centerline":
+        """Centerline::remove_branch_overlap (:681-692): drop the prefix every side branch of a VTP export shares with
+        the vessel it leaves, keeping the junction point; a branch that never leaves is dropped."""
+        return self._derive(N.lib().mm_centerline_remove_branch_overlap, what="remove_branch_overlap")
+
+    def trim_start(self, mm: float) -> "Centerline":
+        """Centerline::trim_start (:698-708): ``mm`` of arc length off the start of branch 0."""
+        return self._derive(N.lib().mm_centerline_trim_start, float(mm), what="trim_start")
+
+    def smooth(self, sigma: float) -> "Centerline":
+        """Centerline::smooth (:798-866): Gaussian smoothing of the positions inside every branch (``sigma`` in points,
+        truncated symmetrically at ceil(3 sigma) and at the branch ends), tangents recomputed."""
+        return self._derive(N.lib().mm_centerline_smooth, float(sigma), what="smooth")
+
 
 def numpy_to_centerline(arr) -> Centerline:
     """multimodars/_converters.py:605-686: (N,3) array -> centerline; NaNs are interpolated along the
@@ -290,6 +355,60 @@ def read_centerline_vtp(file_path: str) -> Centerline:
             out[k] = (x, y, z, t[0], t[1], t[2], radii[pi], branch_id, 0)
             k += 1
     return Centerline(out)
+
+
+def load_centerline(source, name: str) -> Centerline:
+    """multimodars/ccta/centerline_prep.py:10-51: a centerline from a ``Centerline`` (returned as it is), an ``(N, 3)``
+    array, a ``.vtp`` path (``read_centerline_vtp``) or a comma-delimited text file whose rows are x, y, z
+    (``numpy.genfromtxt`` then ``numpy_to_centerline``, which like the reference's takes exactly three columns).
+    ``name`` labels the log line.  The result is unprepared: pass it to ``prepare_centerline``."""
+    if isinstance(source, Centerline):
+        cl = source
+        print(f"Using provided {name} centerline: {len(cl.points)} points")
+    elif isinstance(source, np.ndarray):
+        cl = numpy_to_centerline(source)
+        print(f"Using provided {name} centerline: {len(cl.points)} points")
+    elif str(source).lower().endswith(".vtp"):
+        try:
+            cl = read_centerline_vtp(str(source))
+            print(f"Loaded {name} centerline from VTP: {len(cl.points)} points")
+        except Exception as e:
+            print(f"Error reading {name} centerline from {source}: {e}")
+            raise
+    else:
+        try:
+            cl = numpy_to_centerline(np.genfromtxt(source, delimiter=","))
+            print(f"Loaded {name} centerline: {len(cl.points)} points")
+        except Exception as e:
+            print(f"Error reading {name} centerline from {source}: {e}")
+            raise
+    return cl
+
+
+def prepare_centerline(centerline: Centerline, ref_centerline: Optional[Centerline] = None,
+                       spacing_mm: Optional[float] = None, branch_spacing_tolerance: float = 2.0,
+                       rm_start_mm: float = 0.0, smooth_sigma: float = 2.5) -> Centerline:
+    """multimodars/ccta/centerline_prep.py:54-134, in its order: ``calculate_branches(branch_spacing_tolerance)`` only
+    for a coronary (``ref_centerline`` given) that carries no branch structure yet (at most one branch);
+    ``remove_branch_overlap()``; ``trim_start(rm_start_mm)`` if positive; ``resample(spacing_mm)`` if given (and not 0);
+    ``orient_to_reference(ref_centerline)``, or ``orient_by_max_z()`` without a reference (the aorta, which is never
+    branched); ``smooth(smooth_sigma)`` if positive."""
+    if ref_centerline is not None and len(centerline.branch_start_indices) <= 1:
+        cl = centerline.calculate_branches(branch_spacing_tolerance)
+    else:
+        cl = centerline
+    cl = cl.remove_branch_overlap()
+    if rm_start_mm > 0:
+        cl = cl.trim_start(rm_start_mm)
+    if spacing_mm:
+        cl = cl.resample(spacing_mm)
+    if ref_centerline is not None:
+        cl = cl.orient_to_reference(ref_centerline)
+    else:
+        cl = cl.orient_by_max_z()
+    if smooth_sigma > 0:
+        cl = cl.smooth(smooth_sigma)
+    return cl
 
 
 def preprocess_centerline(centerline: Centerline, ref_mesh: G.FlatGeometry) -> Tuple[Centerline, float]:

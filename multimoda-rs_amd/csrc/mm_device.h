@@ -231,6 +231,13 @@ size_t     weld_sum_scratch(long long nf);
 hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
                               hipStream_t s);
 hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s);
+// branch masks (mm_branch_kernels.hip): pts = n xyz triples; cl = m packed centerline points of branch_cl_point_bytes()
+// each (x, y, z, 1 << branch_id), staged through LDS branch_tile_points() at a time; mask[i] = the bits of the centerline
+// points within squared distance r2 of point i
+hipError_t launch_branch_mask(const double* pts, long long n, const void* cl, int m, double r2, unsigned long long* mask,
+                              hipStream_t s);
+int        branch_cl_point_bytes();
+int        branch_tile_points();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
 // kernel is a 512-thread blit that starves beside another stream's screen launch); 16-byte aligned pointers
