@@ -22,6 +22,9 @@
  *   src/ccta/discretizing.rs:13-22, discretizing/vessel_tree.rs:21-83  discretize_vessel_rs, from_results_dict
  *   src/ccta/binding/ccta_py.rs:541-580, label_coronary.rs:428-455  keep_largest_connected_component
  *   multimodars/ccta/labeling.py:415-487           label_branches
+ *   multimodars/ccta/fixing_functions.py:13-49     manual_hole_fill
+ *   multimodars/ccta/__init__.py:432-499           create_wall_mesh (composed in Python from the pieces here)
+ *   src/ccta/binding/ccta_py.rs:743-814            smooth_mesh_labels
  * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481, 724-920 (discretize_vessel,
  * discretize_vessel_tree)
  * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
@@ -39,6 +42,8 @@
  * in exact f64 (mm_morph_kernels.hip).  The mesh trimming's face membership, open-edge counting and compaction run on the
  * device (mm_trim_kernels.hip); its ring logic on the rim is host C++.  The branch labelling's membership masks are one device
  * pass in exact f64 (mm_branch_kernels.hip); its lists are read off the masks on the host.
+ * The mesh closing's edge table, winding, open half-edges, fans, volume and label votes run on the device
+ * (mm_weld_kernels.hip, mm_close_kernels.hip); its walk over the rim is host C++.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -329,7 +334,74 @@ int     mm_stitch_rings(const double* ring_xyz, int64_t n_b, const double* iv_xy
 int     mm_tube_faces(const double* contours_xyz, int64_t n_contours, int64_t n_points, const double centroid0[3],
                       int64_t* faces);
 
-/* ---- branch labelling (multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
+/* ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, multimodars/ccta/__init__.py:432-499;
+ *      src/ccta/binding/ccta_py.rs:743-814) ------------------------------------------------------------------------- */
+
+/* What mm_fill_holes did and what it left.  watertight <=> n_open_edges == 0 && n_nonmanifold_edges == 0. */
+typedef struct mm_fill_report {
+    int64_t n_vertices, n_faces;             /* of the result: nv + n_loops_filled, nf + n_fan_faces                 */
+    int64_t n_loops_filled, n_fan_faces;     /* loops of at least 3 vertices, and the faces of their fans            */
+    int64_t n_open_edges_before;             /* open edges of the input (after the winding stage)                    */
+    int64_t n_short_loops;                   /* loops of fewer than 3 vertices: skipped, their edges stay open       */
+    int64_t n_irregular_components;          /* rim components with a vertex that is not regular: left open          */
+    int64_t n_irregular_edges;               /* the open edges they hold                                             */
+    int64_t n_open_edges, n_nonmanifold_edges;   /* edges of the result owned by one face / by more than two         */
+    int64_t n_flipped_faces;                 /* faces the winding stage reversed (not counting the inversion)        */
+    int64_t winding_rounds;                  /* as mm_assemble_report: at most 2 + ceil(log2(max(nf, 2)))            */
+    int64_t inverted;                        /* 1: volume < 0 and every face of the result was reversed              */
+    double  volume;                          /* signed volume of the result before the inversion (0 without          */
+                                             /* fix_normals)                                                         */
+} mm_fill_report;
+
+/* The walk over the rim, host only (no engine, no device).  half_edges: ne (a, b) pairs, the open edges as their owner
+ * traverses them, in any order; indices in [0, nv).  succ(a) = b.  A vertex is regular iff exactly one half-edge leaves
+ * it and exactly one enters it.  The half-edges fall into components (two half-edges with a common vertex belong
+ * together).  A component all of whose vertices are regular is one cycle of succ: a loop.  Loops are reported in
+ * increasing order of their smallest vertex, start at it and follow succ; a loop of fewer than 3 vertices
+ * (fixing_functions.py:27) is counted and skipped.  Every other component is irregular (a pinch vertex, faces that
+ * disagree in direction along the rim, a non-manifold edge nearby): counted and skipped.  Loop k's centroid is the sum
+ * of its points in walk order, per coordinate, sequential, divided by their number (f64, unfused).
+ * loop_len (capacity ne), loop_idx (capacity ne) and centroids (capacity ne doubles: 3 per loop; nullable, as is
+ * vertices_xyz then) receive the loops back to back.  counts[5] = {loops, loop vertices, irregular components,
+ * irregular edges, short loops}. */
+int     mm_hole_loops(const int64_t* half_edges, int64_t ne, const double* vertices_xyz, int64_t nv, int64_t* loop_len,
+                      int64_t* loop_idx, double* centroids, int64_t* counts);
+/* manual_hole_fill (fixing_functions.py:13-49): every regular loop of the open rim closed by a fan about its centroid.
+ * One upload of the mesh, one download of the result; everything proportional to nf runs on the device
+ * (mm_weld_kernels.hip, mm_close_kernels.hip), the walk of mm_hole_loops on the host.  nv, nf < 2^31 and face indices
+ * in [0, nv), checked before anything is allocated.
+ *   winding   (fix_normals != 0) the faces first go through the winding stage exactly as mm_fix_winding defines it.
+ *   open half-edges  an undirected edge owned by exactly one face is open; its owner traverses it a -> b.
+ *   loops     as mm_hole_loops on the open half-edges.
+ *   fill      loop k (of at least 3 vertices) gets the new vertex nv + k, its centroid.  For each half-edge a -> b of
+ *             the loop, in walk order, the face (b, a, nv + k) is appended: it crosses the shared edge against the
+ *             owner, so the fan agrees with the mesh around it.  New faces follow all input faces, loop after loop;
+ *             input vertices keep their index and their bits.
+ *   orientation  (fix_normals != 0) the inversion stage of mm_mesh_assemble on the result: the same t_f, the same
+ *             adjacent-pair tree over the faces of the result in output order, volume < 0 reverses every face.
+ * Bounds: loops <= open edges / 3, fan faces <= open edges <= 3 nf.  When vert_cap < nv + loops or face_cap < nf + fan
+ * faces, nothing but the report is written and the call returns MM_ERR_TOO_LARGE; n_vertices and n_faces of the report
+ * then hold the capacities needed (the counts found so far are filled in, those of the result are 0). */
+int     mm_fill_holes(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                      int fix_normals, int64_t vert_cap, int64_t face_cap, double* out_vertices, int64_t* out_faces,
+                      mm_fill_report* report);
+/* smooth_mesh_labels (ccta_py.rs:743-814) on the device.  One iteration reads the labels of the previous one only.  A
+ * vertex with at least one neighbour, all of whose neighbours carry the same label L != its own, becomes L; everything
+ * else stays.  Only unanimous votes flip, so the result is exact and free of any order.  An iteration that flips
+ * nothing ends the run.  The labels stay on the device across iterations: one upload, one download, at most two
+ * launches per iteration.  info[4] = {iterations run, flips in total, flips of the last iteration run, kernel launches}.
+ * A flip count above zero is no sign of progress: two vertices that are each other's only neighbour swap for ever.
+ *   _faces  the neighbours of a vertex are those of mm_build_adjacency: every other corner of every face that names it,
+ *           and itself where a face repeats a corner.  Face indices in [0, nv).
+ *   _csr    the neighbours of vertex i are nb[off[i] .. off[i + 1]) as given (off: nv + 1 ascending entries from 0; the
+ *           lists need not be symmetric, sorted or free of repeats).  A neighbour outside [0, nv) is MM_ERR_INVALID.
+ * nv, nf and off[nv] stay below 2^31; iterations < 0 is MM_ERR_INVALID; on an error out_labels is not written. */
+int     mm_smooth_labels_faces(mm_engine* e, const uint8_t* labels, int64_t nv, const int64_t* faces, int64_t nf,
+                               int64_t iterations, uint8_t* out_labels, int64_t* info);
+int     mm_smooth_labels_csr(mm_engine* e, const uint8_t* labels, int64_t nv, const int64_t* off, const int64_t* nb,
+                             int64_t iterations, uint8_t* out_labels, int64_t* info);
+
+/* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */
 

@@ -111,6 +111,7 @@ EXPORTS_CCTA = [
     "mm_build_adjacency", "mm_boundary_rings", "mm_open_boundary_edges", "mm_clean_open_boundary", "mm_trim_mesh",
     "mm_fix_winding", "mm_mesh_assemble", "mm_assign_rings_to_ends", "mm_ring_start", "mm_ring_direction",
     "mm_stitch_rings", "mm_tube_faces",
+    "mm_hole_loops", "mm_fill_holes", "mm_smooth_labels_faces", "mm_smooth_labels_csr",
     "mm_branch_masks", "mm_branch_tile_points", "mm_branch_select", "mm_label_branches",
 ]
 
@@ -121,6 +122,14 @@ class MMAssembleReport(C.Structure):
         "n_vertices", "n_faces", "n_welded_vertices", "n_unreferenced_vertices", "n_degenerate_faces",
         "n_duplicate_faces", "n_flipped_faces", "n_winding_conflicts", "n_open_edges", "n_nonmanifold_edges",
         "inverted", "winding_rounds")] + [("volume", C.c_double)]
+
+
+class MMFillReport(C.Structure):
+    """``mm_fill_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_loops_filled", "n_fan_faces", "n_open_edges_before", "n_short_loops",
+        "n_irregular_components", "n_irregular_edges", "n_open_edges", "n_nonmanifold_edges", "n_flipped_faces",
+        "winding_rounds", "inverted")] + [("volume", C.c_double)]
 
 
 class MMClGeometry(C.Structure):
@@ -503,6 +512,14 @@ def lib():
     L.mm_fix_winding.argtypes = [P, P, I64, P, P]
     L.mm_mesh_assemble.restype = I
     L.mm_mesh_assemble.argtypes = [P, I, P, P, P, P, I, I, I, P, P, C.POINTER(MMAssembleReport)]
+    L.mm_hole_loops.restype = I
+    L.mm_hole_loops.argtypes = [P, I64, P, I64, P, P, P, P]
+    L.mm_fill_holes.restype = I
+    L.mm_fill_holes.argtypes = [P, P, I64, P, I64, I, I64, I64, P, P, C.POINTER(MMFillReport)]
+    L.mm_smooth_labels_faces.restype = I
+    L.mm_smooth_labels_faces.argtypes = [P, P, I64, P, I64, I64, P, P]
+    L.mm_smooth_labels_csr.restype = I
+    L.mm_smooth_labels_csr.argtypes = [P, P, I64, P, P, I64, P, P]
     L.mm_assign_rings_to_ends.restype = I
     L.mm_assign_rings_to_ends.argtypes = [P, P, I64, P, P, P]
     L.mm_ring_start.restype = I64

@@ -1407,12 +1407,195 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
-           engine: Optional[N.Engine] = None) -> dict:
+           engine: Optional[N.Engine] = None, fill_holes: bool = False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  No
-    post-processing and no hole filling: ``stitch_report`` says whether the result is watertight."""
+    post-processing.  The reference always ends with ``manual_hole_fill`` (:330); here that is ``fill_holes=True``: the
+    stitched mesh goes through ``manual_hole_fill`` and the result carries ``fill_report`` beside ``stitch_report``.
+    The default leaves the holes open, and ``stitch_report`` says whether the result is watertight."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
-    return stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
-                                        dist_start_mode=dist_start_mode, engine=engine)
+    out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
+                                       dist_start_mode=dist_start_mode, engine=engine)
+    if fill_holes:
+        v, f = _mesh_parts(out["mesh"])
+        new_v, new_f, report = _fill(v, f, True, engine)
+        out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
+        out["fill_report"] = report
+    return out
+
+
+# ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
+
+MM_ERR_TOO_LARGE = -3                    # include/mm_hausdorff.h
+FILL_REPORT_KEYS = ("n_vertices", "n_faces", "n_loops_filled", "n_fan_faces", "n_open_edges_before", "n_short_loops",
+                    "n_irregular_components", "n_irregular_edges", "n_open_edges", "n_nonmanifold_edges",
+                    "n_flipped_faces", "winding_rounds", "inverted", "volume")
+
+
+def hole_loops(half_edges, vertices):
+    """The host walk of the hole filling on a list of open half-edges ``(a, b)`` (no device): ``(loops, centroids,
+    info)``, the regular loops of at least 3 vertices as int64 index arrays in increasing order of their smallest
+    vertex, each starting there and following the half-edges, their centroids ``(L, 3)``, and ``info`` with
+    ``n_irregular_components``, ``n_irregular_edges`` and ``n_short_loops``.  include/mm_ccta.h states the rules."""
+    e = np.ascontiguousarray(np.asarray(half_edges, dtype=np.int64).reshape(-1, 2))
+    v = _p3(vertices)
+    ne = e.shape[0]
+    loop_len, loop_idx = np.zeros(ne + 1, dtype=np.int64), np.zeros(ne + 1, dtype=np.int64)
+    centroids = np.zeros(ne + 3, dtype=np.float64)
+    counts = np.zeros(5, dtype=np.int64)
+    rc = N.lib().mm_hole_loops(N._ptr(e), ne, N._ptr(v), v.shape[0], N._ptr(loop_len), N._ptr(loop_idx),
+                               N._ptr(centroids), N._ptr(counts))
+    if rc == -2 and e.size and (e.min() < 0 or e.max() >= v.shape[0]):
+        raise ValueError("half-edge end out of range")
+    N.check(rc, "hole_loops")
+    info = {"n_irregular_components": int(counts[2]), "n_irregular_edges": int(counts[3]), "n_short_loops": int(counts[4])}
+    return _rings(loop_len, loop_idx, int(counts[0])), centroids[:3 * counts[0]].reshape(-1, 3).copy(), info
+
+
+def fill_holes(vertices, faces, fix_normals: bool = True, engine: Optional[N.Engine] = None):
+    """manual_hole_fill (fixing_functions.py:13-49) on arrays: every hole whose rim is a regular loop is closed by a fan
+    about the loop's centroid.  Returns ``(vertices, faces, report)``: the input vertices followed by one centroid per
+    loop, the input faces (after the winding stage of fix_mesh_winding when ``fix_normals``) followed by the fans, and
+    ``report`` with FILL_REPORT_KEYS and ``"watertight"`` (no open and no non-manifold edge, as assemble_mesh defines
+    it).  An edge owned by one face is open and is followed the way its owner traverses it; a rim vertex is regular
+    when one open half-edge leaves and one enters it; a loop runs through regular vertices only, starts at its
+    smallest vertex, and loops come in increasing order of that vertex; loop ``k`` gets vertex ``nv + k`` and the
+    faces ``(b, a, nv + k)`` for its half-edges ``a -> b``.  Rims with a pinch vertex, with faces that disagree in
+    direction (possible only with ``fix_normals=False``) or beside a non-manifold edge are left open and counted
+    (``n_irregular_components``, ``n_irregular_edges``).  With ``fix_normals`` the result is reversed as a whole when
+    its signed volume is negative (the reference's closing ``fix_normals()``).
+
+    Where this differs from the reference: that takes its loops from trimesh's outline entities, re-orders each by a
+    walk over the mesh adjacency restricted to the loop's points (which can cut across a chord) with an angle sort
+    as fall-back, and finds vertices by coordinate (the last duplicate wins).  This one follows the rim itself and
+    works on indices; on a loop the reference walks without a chord the fan is the same set of triangles.  Everything
+    proportional to the mesh runs on the device (csrc/mm_weld_kernels.hip, csrc/mm_close_kernels.hip); the walk over
+    the rim is host code.  The outputs are allocated for a small rim first and, where that is too small, once more
+    with the exact sizes the first call reports."""
+    return _fill(vertices, faces, fix_normals, engine)
+
+
+def _fill(vertices, faces, fix_normals, engine):
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    nv, nf = v.shape[0], f.shape[0]
+    h = _engine(engine).handle
+    rep = N.MMFillReport()
+    vert_cap, face_cap = nv + 16, nf + 1024
+    for attempt in (0, 1):
+        out_v = np.zeros((vert_cap, 3), dtype=np.float64)
+        out_f = np.zeros((face_cap, 3), dtype=np.int64)
+        rc = N.lib().mm_fill_holes(h, N._ptr(v), nv, N._ptr(f), nf, int(bool(fix_normals)), vert_cap, face_cap,
+                                   N._ptr(out_v), N._ptr(out_f), C.byref(rep))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and (rep.n_vertices > vert_cap or rep.n_faces > face_cap):
+            vert_cap, face_cap = int(rep.n_vertices), int(rep.n_faces)
+            continue
+        N.check(rc, "fill_holes")
+        break
+    report = {k: getattr(rep, k) for k in FILL_REPORT_KEYS}
+    report["watertight"] = report["n_open_edges"] == 0 and report["n_nonmanifold_edges"] == 0
+    return out_v[:rep.n_vertices].copy(), out_f[:rep.n_faces].copy(), report
+
+
+def manual_hole_fill(mesh, fix_normals: bool = True, engine: Optional[N.Engine] = None):
+    """fixing_functions.py:13-49: ``mesh`` (a ``(vertices, faces)`` tuple or an object with ``.vertices`` / ``.faces``)
+    with every regular hole closed by a fan about its centroid, as a new mesh of the kind given; the input is not
+    modified.  ``fill_holes`` states the rules and the differences from the reference, and returns the report too."""
+    v, f = _mesh_parts(mesh)
+    new_v, new_f, _ = _fill(v, f, fix_normals, engine)
+    return _with_mesh(mesh, new_v, new_f)
+
+
+def smooth_mesh_labels_info(labels, adjacency_map=None, iterations: int = 1, faces=None,
+                            engine: Optional[N.Engine] = None):
+    """smooth_mesh_labels with what the run did: ``(labels, info)``, ``info`` holding ``iterations_run``,
+    ``n_flips``, ``n_flips_last`` and ``launches`` (the kernels the call launched)."""
+    lab = np.ascontiguousarray(np.asarray(labels, dtype=np.uint8).reshape(-1))
+    if (adjacency_map is None) == (faces is None):
+        raise ValueError("give exactly one of adjacency_map and faces")
+    if int(iterations) < 0:
+        raise ValueError("iterations must not be negative")
+    nv = lab.shape[0]
+    out = np.zeros_like(lab)
+    info = np.zeros(4, dtype=np.int64)
+    h = _engine(engine).handle
+    if faces is not None:
+        f = _checked_faces(faces, nv)
+        rc = N.lib().mm_smooth_labels_faces(h, N._ptr(lab), nv, N._ptr(f), f.shape[0], int(iterations), N._ptr(out),
+                                            N._ptr(info))
+    else:
+        rows = [np.fromiter(adjacency_map.get(i, ()), dtype=np.int64) for i in range(nv)]
+        off = np.zeros(nv + 1, dtype=np.int64)
+        if nv:
+            off[1:] = np.cumsum([r.shape[0] for r in rows])
+        nb = np.ascontiguousarray(np.concatenate(rows)) if nv and off[-1] else np.zeros(0, dtype=np.int64)
+        if nb.size and (nb.min() < 0 or nb.max() >= nv):
+            raise ValueError(f"neighbour index out of range [0, {nv})")
+        rc = N.lib().mm_smooth_labels_csr(h, N._ptr(lab), nv, N._ptr(off), N._ptr(nb), int(iterations), N._ptr(out),
+                                          N._ptr(info))
+    N.check(rc, "smooth_mesh_labels")
+    return out, {"iterations_run": int(info[0]), "n_flips": int(info[1]), "n_flips_last": int(info[2]),
+                 "launches": int(info[3])}
+
+
+def smooth_mesh_labels(labels, adjacency_map=None, iterations: int = 1, faces=None,
+                       engine: Optional[N.Engine] = None) -> np.ndarray:
+    """ccta_py.rs:743-814: ``labels`` (one ``uint8`` per vertex) smoothed for ``iterations`` synchronous rounds: a
+    vertex with at least one neighbour, all of whose neighbours carry the same label different from its own, takes that
+    label; every round reads the labels of the round before only.  Only unanimous votes flip, so the reference's
+    hash-order tie never matters and the result is exact.  A round that flips nothing ends the run.  Give exactly one
+    of ``faces`` (recommended: the neighbours are those of build_adjacency_map, found on the device without building a
+    dict of sets) and ``adjacency_map`` (the dict of build_adjacency_map, the reference's positional signature; read
+    row by row as given, it need not be symmetric; a vertex without an entry has no neighbour).  The labels stay on
+    the device across the rounds (csrc/mm_close_kernels.hip).  Returns a new ``uint8`` array."""
+    return smooth_mesh_labels_info(labels, adjacency_map, iterations, faces, engine)[0]
+
+
+WALL_AORTA_KEYS = ("aorta_points", "rca_removed_points", "lca_removed_points")
+
+
+def _wall_sub_mesh(results: dict, keys, engine):
+    """keep_labeled_points_from_mesh for the wall mesh: an empty region or one that matches no vertex is an error
+    there (keep_labeled_points_from_mesh hands back its input, which would take the whole mesh as the sub-mesh)."""
+    sub = keep_labeled_points_from_mesh(results, list(keys), engine=engine)
+    if sub is results:
+        raise ValueError(f"create_wall_mesh: {' + '.join(keys)} is empty or matches no vertex of the mesh")
+    return sub
+
+
+def create_wall_mesh(geometry, cl_aorta: Centerline, cl_rca: Centerline, cl_lca: Centerline, results: dict,
+                     aortic_scaling: Optional[float] = None, coronary_scaling: float = 1.0,
+                     engine: Optional[N.Engine] = None) -> dict:
+    """ccta/__init__.py:432-499: a wall mesh from the labelled lumen mesh.  The aortic scaling is
+    ``find_aortic_wall_scaling(geometry, cl_aorta, results)`` where ``geometry`` is given, else ``aortic_scaling``
+    (both ``None``: ``ValueError("Either provide frames or aortic scaling")``, before anything else).  The aortic
+    sub-mesh (``aorta_points``, ``rca_removed_points``, ``lca_removed_points`` kept) has its ostia filled
+    (``manual_hole_fill``) and every vertex of the filled mesh, the new centres included, morphed about ``cl_aorta``;
+    the ``rca_points`` and ``lca_points`` sub-meshes are kept and morphed about their centerlines by
+    ``coronary_scaling``; the three are concatenated in that order without welding.  Returns a new dict (the input is
+    not modified) with ``"mesh"`` replaced and ``"wall_report"`` = ``{"aortic_scaling", "coronary_scaling",
+    "fill_report"}``.  A region that is empty or matches no vertex raises ``ValueError`` naming its key, where
+    keep_labeled_points_from_mesh would hand the whole mesh back as the sub-mesh (what the reference does in that case
+    was not checked)."""
+    if geometry is None and aortic_scaling is None:
+        raise ValueError("Either provide frames or aortic scaling")
+    scaling = float(find_aortic_wall_scaling(geometry, cl_aorta, results)) if geometry is not None else float(aortic_scaling)
+    mesh = results["mesh"]
+    aorta = _wall_sub_mesh(results, WALL_AORTA_KEYS, engine)
+    av, af = _mesh_parts(aorta["mesh"])
+    fv, ff, fill_report = _fill(av, af, True, engine)
+    parts = [(centerline_morph_batch([(cl_aorta, fv, scaling)], engine)[0][0], ff)]
+    for key, cl in (("rca_points", cl_rca), ("lca_points", cl_lca)):
+        sub = _wall_sub_mesh(results, (key,), engine)
+        moved = scale_region_centerline_morphing(sub["mesh"], sub[key], cl, float(coronary_scaling), engine)
+        pv, pf = _mesh_parts(moved)
+        parts.append((_p3(pv), _faces3(pf)))
+    off = np.concatenate([[0], np.cumsum([p[0].shape[0] for p in parts])]).astype(np.int64)
+    out = dict(results)
+    out["mesh"] = _with_mesh(mesh, np.ascontiguousarray(np.concatenate([p[0] for p in parts])),
+                             np.ascontiguousarray(np.concatenate([p[1] + o for p, o in zip(parts, off[:-1])])))
+    out["wall_report"] = {"aortic_scaling": scaling, "coronary_scaling": float(coronary_scaling),
+                          "fill_report": fill_report}
+    return out

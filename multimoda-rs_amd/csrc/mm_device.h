@@ -231,6 +231,20 @@ size_t     weld_sum_scratch(long long nf);
 hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
                               hipStream_t s);
 hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s);
+// mesh closing (mm_close_kernels.hip).  close_half_edges: the edges of weld_edges' table owned by one face, as that face
+// traverses them (link nullable: the flips of the winding stage), packed a << 32 | b into out in no fixed order, their
+// number in *n_out (cleared here); close_fan: face[nf + i] = (fan[3i+1], fan[3i], nv + fan[3i+2]); smooth_faces: one
+// iteration of the label smoothing over the faces (vote: nv words, zero before the first iteration and after every
+// one), next = the new labels, *n_flips += the changes, *launches += the kernels launched; smooth_csr: the same over
+// the rows of a CSR adjacency
+hipError_t launch_close_half_edges(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
+                                   int log2_cap, const unsigned int* link, unsigned long long* out,
+                                   unsigned long long out_cap, unsigned long long* n_out, hipStream_t s);
+hipError_t launch_close_fan(const int32_t* fan, long long n_fan, long long nv, int32_t* face, long long nf, hipStream_t s);
+hipError_t launch_smooth_faces(const int32_t* face, long long nf, long long nv, const uint8_t* cur, unsigned int* vote,
+                               uint8_t* next, unsigned long long* n_flips, int* launches, hipStream_t s);
+hipError_t launch_smooth_csr(const int32_t* off, const int32_t* nb, long long nv, const uint8_t* cur, uint8_t* next,
+                             unsigned long long* n_flips, int* launches, hipStream_t s);
 // branch masks (mm_branch_kernels.hip): pts = n xyz triples; cl = m packed centerline points of branch_cl_point_bytes()
 // each (x, y, z, 1 << branch_id), staged through LDS branch_tile_points() at a time; mask[i] = the bits of the centerline
 // points within squared distance r2 of point i

@@ -130,6 +130,14 @@ enum { kUnref = 0, kDegenerate = 1, kRepeated = 2, kFlipped = 3, kOpen = 4, kNon
 // winding of the nf faces at `face` (device, in place): the edge table, the union-find, the flips and the edge report
 int wind(Engine* e, WeldDev& d, int32_t* face, int64_t nf, bool fix, int64_t* rounds)
 {
+    const WindDev w{d.keys, d.cnt, d.own, d.link, d.changed, d.counts + kFlipped, d.counts + kOpen, d.log2_e};
+    return weld_wind(e, w, face, nf, fix, rounds);
+}
+
+}  // namespace
+
+int weld_wind(Engine* e, const WindDev& d, int32_t* face, int64_t nf, bool fix, int64_t* rounds)
+{
     *rounds = 0;
     MM_TRY_HIP(launch_weld_edges(face, nf, d.keys, d.cnt, d.own, d.log2_e, e->stream));
     if (fix && nf > 0) {
@@ -145,14 +153,13 @@ int wind(Engine* e, WeldDev& d, int32_t* face, int64_t nf, bool fix, int64_t* ro
             if (!hc[0]) break;
             if (*rounds > bound) return set_error(MM_ERR_HIP, "winding: pointer jumping did not settle");
         }
-        MM_TRY_HIP(launch_weld_flip(face, nf, d.link, d.counts + kFlipped, e->stream));
+        MM_TRY_HIP(launch_weld_flip(face, nf, d.link, d.n_flipped, e->stream));
     }
     MM_TRY_HIP(launch_weld_edge_report(d.keys, d.cnt, d.own, d.log2_e, fix && nf > 0 ? d.link : nullptr,
-                                       d.counts + kOpen, e->stream));
+                                       d.edge_counts, e->stream));
     return MM_OK;
 }
 
-}  // namespace
 }  // namespace mm
 
 using namespace mm;
