@@ -334,6 +334,129 @@ int     mm_stitch_rings(const double* ring_xyz, int64_t n_b, const double* iv_xy
 int     mm_tube_faces(const double* contours_xyz, int64_t n_contours, int64_t n_points, const double centroid0[3],
                       int64_t* faces);
 
+/* ---- rim conditioning (multimodars/ccta/stitching.py:484-1064: _prepare_prox_dist_boundary_pts and its helpers) ----- */
+
+/* The ring arithmetic, host only, f64, unfused.  Rings are n xyz triples; a mean over points is the sequential sum in
+ * index order divided by their number; dot products are (x x' + y y') + z z', norms sqrt((x x + y y) + z z).  A NULL
+ * array, a negative count or a non-finite input (the reference would hand NaN on) is MM_ERR_INVALID; rings of fewer
+ * than 3 points pass through where the reference passes them through. */
+
+/* The centroid and the direction of least variance of n >= 1 points (_plane_normal_svd :965-969, :659-662): the
+ * eigenvector of the smallest eigenvalue of the 3 x 3 scatter matrix by cyclic Jacobi, unit length, its component of
+ * largest magnitude positive.  numpy's SVD leaves the sign open and every use in the reference is indifferent to it; the
+ * direction agrees with LAPACK's to rounding only. */
+int     mm_ring_fit_plane(const double* ring_xyz, int64_t n, double origin[3], double normal[3]);
+/* origin == normal == NULL: _project_to_best_fit_plane (:648-665), the ring on its own plane.  Both given:
+ * _project_onto_plane (:775-782), p - ((p - origin) . normal) normal. */
+int     mm_ring_project_to_plane(const double* ring_xyz, int64_t n, const double* origin, const double* normal, double* out);
+/* _smooth_ring_preserving_size (:706-739): `iterations` passes of alpha p_i + (1 - alpha) (p_{i-1} + p_{i+1}) / 2, then
+ * scaled about the centroid back to the calibre (mean distance from the centroid) it had; a calibre of zero before or
+ * after leaves the smoothed ring as it is. */
+int     mm_ring_smooth_preserving_size(const double* ring_xyz, int64_t n, int64_t iterations, double alpha, double* out);
+/* _redistribute_ring_evenly (:742-772): n_out points (-1: n) at the arc lengths i * (perimeter / n_out) of the closed
+ * polyline; the segment of a target is the last one starting at or before it.  Index 0 keeps its bits.  n < 3, n_out < 3
+ * or a zero perimeter copies the ring.  out holds max(n, n_out) points; returns the number written. */
+int64_t mm_ring_redistribute(const double* ring_xyz, int64_t n, int64_t n_out, double* out);
+/* _shift_plane_clear_of (:785-813): the unit normal turned along `outward`, and the plane moved along it until every
+ * one of the n >= 1 points lies at least `overshoot` behind it.  *moved = the distance (0: it was clear already). */
+int     mm_plane_shift_clear_of(const double origin[3], const double normal[3], const double* pts_xyz, int64_t n,
+                                const double outward[3], double overshoot, double out_origin[3], double out_normal[3],
+                                double* moved);
+/* _clamp_to_plane (:978-1011): the side of the plane is the sign of the median distance (an even count: the mean of the
+ * middle two; sign(0) = 0); a point whose distance has another sign and is not 0 goes onto the plane; with overshoot > 0
+ * every point nearer than `overshoot` on the right side is then moved out to exactly that. */
+int     mm_ring_clamp_to_plane(const double* ring_xyz, int64_t n, const double origin[3], const double normal[3],
+                               double overshoot, double* out);
+/* The insert counts of _densify_boundary (:862-892): every ring edge i (point i to point i + 1, cyclic) receives
+ * (target_n - n) / n points and the (target_n - n) % n longest one more (of equal lengths the earlier edge first).
+ * Returns 1 with a plan, 0 where there is nothing to insert (n < 3 or target_n == n), 2 where n > target_n (the
+ * reference's warning); counts is zero then. */
+int     mm_ring_densify_plan(const double* ring_xyz, int64_t n, int64_t target_n, int64_t* counts);
+
+/* The three mesh-wide stages on the device (mm_rim_kernels.hip).  Indices on the device are int32: nv, nf < 2^31 and
+ * face indices in [0, nv), checked before anything is allocated.  Every stage has one answer whatever the scheduling. */
+
+/* The reference's {tuple(v): i} dict over the vertices (:826, :873): index[k] = the LAST vertex equal to point k by
+ * value (-0.0 equals 0.0, a row with a NaN equals nothing), -1 without one. */
+int     mm_mesh_locate_points(mm_engine* e, const double* vertices_xyz, int64_t nv, const double* pts_xyz, int64_t r,
+                              int64_t* index);
+/* Query points one LDS chunk of that kernel holds (more are staged chunk after chunk). */
+int     mm_rim_locate_chunk_points(void);
+/* _enforce_layer_gap_from_plane (:1014-1064).  out_layer[v] = 0 for a seed, k for a vertex whose shortest path to a
+ * seed over face edges has k <= n_rings edges, else -1.  A vertex p of layer k >= 1 moves, unfused and in this order:
+ *   d = ((px - ox) nx + (py - oy) ny) + (pz - oz) nz;  q = p - d n;  r = q - o;  rn = sqrt((rx rx + ry ry) + rz rz);
+ *   rn < 1e-10: it stays;  else p + ((k step) / rn) r.
+ * One launch marks the seeds, one finds each ring (the run ends behind a ring that finds no vertex), one pushes.
+ * info[3] = {kernel launches, rings run, vertices with a layer >= 1}. */
+int     mm_mesh_layer_push(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                           const int64_t* seeds, int64_t ns, const double origin[3], const double normal[3],
+                           double layer_step, int64_t n_rings, double* out_vertices, int32_t* out_layer, int64_t* info);
+/* The mesh side of _densify_boundary (:894-962) for a ring of n >= 3 distinct vertices (a repeated one is
+ * MM_ERR_INVALID; the reference would overwrite its own table) and counts[i] points for ring edge i.
+ *   vertices  the input vertices; then, edge after edge, the points pa + (j / (count + 1)) (pb - pa), j = 1 .. count;
+ *             then one centroid (the mean of the polygon's points) per face fanned about a centroid, in face order.
+ *   faces     a face is touched when one of its edges joins the two ends of a ring edge with count > 0, in either
+ *             direction.  The untouched faces come first, in input order.  Then, in ascending order of the touched
+ *             face, its fan: the face's polygon is its corners in order with the inserted points of each edge behind
+ *             the edge's first corner; about the first corner that is on no subdivided edge, (r0, r_i, r_i+1) over the
+ *             polygon rotated to start there; without such a corner about the centroid, (c, p_i, p_i+1) all round.
+ *             (The reference walks a Python set of touched faces: its order is CPython's.)
+ *   ring      out_ring_idx (n + sum(counts) entries): every ring vertex followed by its edge's inserted points.
+ * info[6] = {vertices, faces, points inserted, faces fanned, fans about a centroid, kernel launches}.  Where vert_cap
+ * or face_cap is too small nothing else is written, info[0..1] hold the sizes needed, and the call returns
+ * MM_ERR_TOO_LARGE. */
+int     mm_mesh_split_rim_edges(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                                const int64_t* ring_idx, int64_t n, const int64_t* counts, int64_t vert_cap,
+                                int64_t face_cap, double* out_vertices, int64_t* out_faces, int64_t* out_ring_idx,
+                                int64_t* info);
+
+typedef struct mm_rim_params {
+    int64_t proximal_is_ostium;              /* != 0: _condition_ostium_ring on the proximal ring                      */
+    int64_t target_n;                        /* points of a densified ring; 0: no densification (the reference's None) */
+    int64_t smooth_iterations, n_rings;      /* the reference's 5 and 2                                                */
+    int64_t vert_cap, face_cap, ring_cap;    /* capacities of out_vertices, out_faces and of each ring                 */
+    double  smooth_alpha;                    /* 0.5                                                                    */
+    double  angle_threshold_deg;             /* 45                                                                     */
+    double  clamp_overshoot;                 /* mm                                                                     */
+    double  layer_step_mm;                   /* 0.1                                                                    */
+} mm_rim_params;
+
+/* What mm_condition_rims did.  The reference's printed warnings are the ring_* flags. */
+typedef struct mm_rim_report {
+    int64_t n_vertices, n_faces;             /* of the result                                                          */
+    int64_t n_prox, n_dist;                  /* points of the returned rings                                           */
+    int64_t n_moved_prox, n_moved_dist;      /* mesh vertices the first write-back of each ring moved                  */
+    int64_t n_moved_ostium;                  /* ... and the write-back of the ostium stage                             */
+    int64_t clamped;                         /* 1: the planes met at the threshold angle or above, the clamp ran       */
+    int64_t n_layer_vertices[2];             /* vertices of layer 1 and 2 behind a clamped ring                        */
+    int64_t n_inserted_prox, n_inserted_dist;
+    int64_t n_fanned_faces, n_centroid_fans; /* faces replaced by a fan; those of them fanned about a centroid         */
+    int64_t ring_over_target[2];             /* the ring has more points than target_n: left as it is                  */
+    int64_t ring_off_mesh[2];                /* a point of the ring is no mesh vertex: not densified                   */
+    int64_t n_launches;                      /* kernels launched                                                       */
+    int64_t bytes_uploaded, bytes_downloaded;/* all copies of the call: the mesh once each way, the rest ring-sized    */
+    double  plane_shift_mm;                  /* how far the ostium plane moved (0: it was clear, or no ostium stage)   */
+    double  plane_angle_deg;                 /* the angle between ring plane and IV plane (0 without the ostium stage) */
+} mm_rim_report;
+
+/* _prepare_prox_dist_boundary_pts (:505-556) for the two rings already assigned to the ends: one upload of the mesh, one
+ * download, the mesh resident in between.  Both rings: project, smooth, redistribute, written back to the vertices they
+ * are located at (a ring that gives one vertex two different targets is MM_ERR_INVALID; the reference keeps the last).
+ * With proximal_is_ostium, n_iv > 0 and n_prox >= 3 the ostium stage (:582-645): towards = the mean of aorta_xyz minus
+ * the ring's centroid, or prox_outward (nullable) where that is zero or na == 0; the plane shift, the clamp against the
+ * IV plane through prox_centroid where the angle reaches the threshold, the write-back, and behind a clamped ring the
+ * layer push of mm_mesh_layer_push from the moved vertices.  Then, with target_n > 0, both rings densified
+ * (mm_ring_densify_plan, mm_mesh_locate_points, mm_mesh_split_rim_edges), proximal first.
+ * Launches: 1 to locate a ring, 1 to write it (none where no point sits on the mesh); 1 + rings run + 1 for the layer
+ * push; to split, 3 (positions, ring coordinates, touched faces) and 4 more (scan, compaction) where a face is touched.
+ * Capacities as mm_fill_holes: too small, the call returns MM_ERR_TOO_LARGE and n_vertices / n_faces of the report hold
+ * sizes that suffice for a rim whose edges have one owner each (n_prox / n_dist the ring sizes). */
+int     mm_condition_rims(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                          const double* prox_ring, int64_t n_prox, const double* dist_ring, int64_t n_dist,
+                          const double* iv_frame, int64_t n_iv, const double prox_centroid[3], const double* prox_outward,
+                          const double* aorta_xyz, int64_t na, const mm_rim_params* params, double* out_vertices,
+                          int64_t* out_faces, double* out_prox, double* out_dist, mm_rim_report* report);
+
 /* ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, multimodars/ccta/__init__.py:432-499;
  *      src/ccta/binding/ccta_py.rs:743-814) ------------------------------------------------------------------------- */
 

@@ -113,6 +113,9 @@ EXPORTS_CCTA = [
     "mm_stitch_rings", "mm_tube_faces",
     "mm_hole_loops", "mm_fill_holes", "mm_smooth_labels_faces", "mm_smooth_labels_csr",
     "mm_branch_masks", "mm_branch_tile_points", "mm_branch_select", "mm_label_branches",
+    "mm_ring_fit_plane", "mm_ring_project_to_plane", "mm_ring_smooth_preserving_size", "mm_ring_redistribute",
+    "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
+    "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
 ]
 
 
@@ -130,6 +133,24 @@ class MMFillReport(C.Structure):
         "n_vertices", "n_faces", "n_loops_filled", "n_fan_faces", "n_open_edges_before", "n_short_loops",
         "n_irregular_components", "n_irregular_edges", "n_open_edges", "n_nonmanifold_edges", "n_flipped_faces",
         "winding_rounds", "inverted")] + [("volume", C.c_double)]
+
+
+class MMRimParams(C.Structure):
+    """``mm_rim_params`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "proximal_is_ostium", "target_n", "smooth_iterations", "n_rings", "vert_cap", "face_cap", "ring_cap")] + \
+               [(name, C.c_double) for name in ("smooth_alpha", "angle_threshold_deg", "clamp_overshoot", "layer_step_mm")]
+
+
+class MMRimReport(C.Structure):
+    """``mm_rim_report`` (include/mm_ccta.h)."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_prox", C.c_int64), ("n_dist", C.c_int64),
+                ("n_moved_prox", C.c_int64), ("n_moved_dist", C.c_int64), ("n_moved_ostium", C.c_int64),
+                ("clamped", C.c_int64), ("n_layer_vertices", C.c_int64 * 2), ("n_inserted_prox", C.c_int64),
+                ("n_inserted_dist", C.c_int64), ("n_fanned_faces", C.c_int64), ("n_centroid_fans", C.c_int64),
+                ("ring_over_target", C.c_int64 * 2), ("ring_off_mesh", C.c_int64 * 2), ("n_launches", C.c_int64),
+                ("bytes_uploaded", C.c_int64), ("bytes_downloaded", C.c_int64), ("plane_shift_mm", C.c_double),
+                ("plane_angle_deg", C.c_double)]
 
 
 class MMClGeometry(C.Structure):
@@ -538,6 +559,31 @@ def lib():
     L.mm_branch_select.argtypes = [P, I64, P, I64, I64, P, P, P, P, I64, P]
     L.mm_label_branches.restype = I
     L.mm_label_branches.argtypes = [P, P, I64, P, I64, D, P, I64, I64, P, P, P, P, P, I64, P]
+    L.mm_ring_fit_plane.restype = I
+    L.mm_ring_fit_plane.argtypes = [P, I64, P, P]
+    L.mm_ring_project_to_plane.restype = I
+    L.mm_ring_project_to_plane.argtypes = [P, I64, P, P, P]
+    L.mm_ring_smooth_preserving_size.restype = I
+    L.mm_ring_smooth_preserving_size.argtypes = [P, I64, I64, D, P]
+    L.mm_ring_redistribute.restype = I64
+    L.mm_ring_redistribute.argtypes = [P, I64, I64, P]
+    L.mm_plane_shift_clear_of.restype = I
+    L.mm_plane_shift_clear_of.argtypes = [P, P, P, I64, P, D, P, P, P]
+    L.mm_ring_clamp_to_plane.restype = I
+    L.mm_ring_clamp_to_plane.argtypes = [P, I64, P, P, D, P]
+    L.mm_ring_densify_plan.restype = I
+    L.mm_ring_densify_plan.argtypes = [P, I64, I64, P]
+    L.mm_mesh_locate_points.restype = I
+    L.mm_mesh_locate_points.argtypes = [P, P, I64, P, I64, P]
+    L.mm_rim_locate_chunk_points.restype = I
+    L.mm_rim_locate_chunk_points.argtypes = []
+    L.mm_mesh_layer_push.restype = I
+    L.mm_mesh_layer_push.argtypes = [P, P, I64, P, I64, P, I64, P, P, D, I64, P, P, P]
+    L.mm_mesh_split_rim_edges.restype = I
+    L.mm_mesh_split_rim_edges.argtypes = [P, P, I64, P, I64, P, I64, P, I64, I64, P, P, P, P]
+    L.mm_condition_rims.restype = I
+    L.mm_condition_rims.argtypes = [P, P, I64, P, I64, P, I64, P, I64, P, I64, P, P, P, I64, C.POINTER(MMRimParams), P, P,
+                                    P, P, C.POINTER(MMRimReport)]
     _lib = L
     return L
 

@@ -1341,10 +1341,13 @@ def _result_rings(results: dict, mesh, engine) -> list:
 def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dict, n_points_iv_cont: int = 100,
                                  prox_start_mode: str = "nearest_iv", dist_start_mode: str = "nearest_iv",
                                  condition_rims: bool = False, engine: Optional[N.Engine] = None) -> dict:
-    """stitching.py:355-481 without the rim conditioning of _prepare_prox_dist_boundary_pts (:484-1060: plane
-    flattening, smoothing, respacing, ostium clamp, densification), which this package does not have yet:
-    ``condition_rims=True`` raises NotImplementedError, and the arguments that only steer it (``proximal_is_ostium``,
-    ``clamp_overshoot``, ``boundary_point_ratio``) are not accepted.  The lumen contours are downsampled to
+    """stitching.py:355-481 behind the rim conditioning: this function sews the rings it is given as they are.  The
+    conditioning of _prepare_prox_dist_boundary_pts (:484-1064: plane flattening, smoothing, respacing, ostium clamp,
+    densification) is a step of its own, ``condition_boundary_rings``, whose result goes straight in here as ``mesh`` and
+    ``results``; ``stitch_conditioned`` runs the whole line.  ``condition_rims=True`` still raises NotImplementedError
+    and the arguments that only steer the conditioning (``proximal_is_ostium``, ``clamp_overshoot``,
+    ``boundary_point_ratio``) are not accepted here: they belong to ``condition_boundary_rings``.  The lumen contours are
+    downsampled to
     ``n_points_iv_cont`` points, the two rims (``boundary_points_<n>`` of ``results``, else the mesh's open edges) are
     assigned to the ends as whole rings, rotated to their start (``"nearest_iv"`` | ``"highest_z"``; ``"highest_z"``
     also rotates every frame so that the first frame's highest point leads, the last of equal ones, as the reference's
@@ -1426,9 +1429,320 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     return out
 
 
+MM_ERR_TOO_LARGE = -3                    # include/mm_hausdorff.h
+
+
+# ---- rim conditioning (multimodars/ccta/stitching.py:484-1064) -----------------------------------------------------------
+
+RIM_REPORT_KEYS = ("n_vertices", "n_faces", "n_prox", "n_dist", "n_moved_prox", "n_moved_dist", "n_moved_ostium", "clamped",
+                   "n_layer_vertices", "n_inserted_prox", "n_inserted_dist", "n_fanned_faces", "n_centroid_fans",
+                   "ring_over_target", "ring_off_mesh", "n_launches", "bytes_uploaded", "bytes_downloaded",
+                   "plane_shift_mm", "plane_angle_deg")
+
+
+def _ring_call(rc: int, what: str):
+    """MM_ERR_INVALID of a ring function is a ValueError (a NaN, a repeated ring vertex); everything else as check."""
+    if rc == -2:
+        raise ValueError(f"{what}: {N.last_error()}")
+    if rc < 0:
+        N.check(int(rc), what)
+    return rc
+
+
+def fit_ring_plane(points):
+    """_plane_normal_svd (stitching.py:965-969): ``(centroid, normal)`` of the best-fit plane; the normal is the
+    direction of least variance with its largest component positive (numpy leaves the sign to LAPACK)."""
+    p = _p3(points)
+    o, n = np.zeros(3), np.zeros(3)
+    _ring_call(N.lib().mm_ring_fit_plane(N._ptr(p), p.shape[0], N._ptr(o), N._ptr(n)), "fit_ring_plane")
+    return o, n
+
+
+def project_to_best_fit_plane(points, origin=None, normal=None) -> np.ndarray:
+    """_project_to_best_fit_plane (stitching.py:648-665); with ``origin`` and ``normal`` _project_onto_plane (:775-782)."""
+    p = _p3(points)
+    out = np.zeros_like(p)
+    o = None if origin is None else _p3(origin)
+    n = None if normal is None else _p3(normal)
+    _ring_call(N.lib().mm_ring_project_to_plane(N._ptr(p), p.shape[0], N._ptr(o), N._ptr(n), N._ptr(out)),
+               "project_to_best_fit_plane")
+    return out
+
+
+def smooth_ring_preserving_size(points, iterations: int = 5, alpha: float = 0.5) -> np.ndarray:
+    """_smooth_ring_preserving_size (stitching.py:706-739): Laplacian smoothing of a closed ring, scaled back to the
+    calibre it had."""
+    p = _p3(points)
+    out = np.zeros_like(p)
+    _ring_call(N.lib().mm_ring_smooth_preserving_size(N._ptr(p), p.shape[0], int(iterations), float(alpha), N._ptr(out)),
+               "smooth_ring_preserving_size")
+    return out
+
+
+def redistribute_ring_evenly(points, n_out: Optional[int] = None) -> np.ndarray:
+    """_redistribute_ring_evenly (stitching.py:742-772): ``n_out`` points (default: as many as given) at equal arc
+    lengths of the closed polyline; index 0 stays where it is."""
+    p = _p3(points)
+    if n_out is not None and int(n_out) < 0:
+        raise ValueError("n_out must not be negative")
+    k = -1 if n_out is None else int(n_out)
+    out = np.zeros((max(p.shape[0], k, 1), 3), dtype=np.float64)
+    m = _ring_call(N.lib().mm_ring_redistribute(N._ptr(p), p.shape[0], k, N._ptr(out)), "redistribute_ring_evenly")
+    return out[:m].copy()
+
+
+def shift_plane_clear_of(origin, normal, points, outward, overshoot: float):
+    """_shift_plane_clear_of (stitching.py:785-813): ``(origin, normal, moved)`` of the plane turned along ``outward``
+    and moved until every point lies ``overshoot`` behind it."""
+    o, n, p, w = _p3(origin), _p3(normal), _p3(points), _p3(outward)
+    so, sn, moved = np.zeros(3), np.zeros(3), C.c_double(0.0)
+    _ring_call(N.lib().mm_plane_shift_clear_of(N._ptr(o), N._ptr(n), N._ptr(p), p.shape[0], N._ptr(w), float(overshoot),
+                                               N._ptr(so), N._ptr(sn), C.byref(moved)), "shift_plane_clear_of")
+    return so, sn, float(moved.value)
+
+
+def clamp_to_plane(points, plane_origin, plane_normal, overshoot: float = 0.0) -> np.ndarray:
+    """_clamp_to_plane (stitching.py:978-1011)."""
+    p, o, n = _p3(points), _p3(plane_origin), _p3(plane_normal)
+    out = np.zeros_like(p)
+    _ring_call(N.lib().mm_ring_clamp_to_plane(N._ptr(p), p.shape[0], N._ptr(o), N._ptr(n), float(overshoot), N._ptr(out)),
+               "clamp_to_plane")
+    return out
+
+
+def densify_plan(ring, target_n: int):
+    """The insert counts of _densify_boundary (stitching.py:862-892): ``(counts, status)``, status 1 with a plan, 0 where
+    nothing is to insert, 2 where the ring has more than ``target_n`` points."""
+    p = _p3(ring)
+    counts = np.zeros(max(p.shape[0], 1), dtype=np.int64)
+    st = _ring_call(N.lib().mm_ring_densify_plan(N._ptr(p), p.shape[0], int(target_n), N._ptr(counts)), "densify_plan")
+    return counts[:p.shape[0]].copy(), int(st)
+
+
+def locate_points(vertices, points, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """The reference's ``{tuple(v): i}`` lookup on the device (csrc/mm_rim_kernels.hip): for every point the index of the
+    last vertex equal to it by value (-0.0 equals 0.0; a NaN equals nothing), -1 without one."""
+    v, p = _p3(vertices), _p3(points)
+    idx = np.full(max(p.shape[0], 1), -1, dtype=np.int64)
+    N.check(N.lib().mm_mesh_locate_points(_engine(engine).handle, N._ptr(v), v.shape[0], N._ptr(p), p.shape[0], N._ptr(idx)),
+            "locate_points")
+    return idx[:p.shape[0]].copy()
+
+
+def write_ring_to_mesh(mesh, old_pts, new_pts, engine: Optional[N.Engine] = None):
+    """_write_ring_to_mesh (stitching.py:816-834): ``(mesh, moved)``, the mesh with the vertices at ``old_pts`` moved to
+    ``new_pts`` and the sorted indices that moved.  The vertices are found on the device (locate_points)."""
+    v, f = _mesh_parts(mesh)
+    v = _p3(v).copy()
+    new = _p3(new_pts)
+    idx = locate_points(v, old_pts, engine)
+    order = np.argsort(idx, kind="stable")
+    for a, b in zip(order[:-1], order[1:]):
+        if idx[a] >= 0 and idx[a] == idx[b] and new[a].tobytes() != new[b].tobytes():
+            raise ValueError("two ring points with different targets sit on one mesh vertex")
+    hit = idx >= 0
+    v[idx[hit]] = new[hit]
+    return _with_mesh(mesh, v, np.asarray(f)), sorted(set(idx[hit].tolist()))
+
+
+def enforce_layer_gap_from_plane(mesh, seed_indices, plane_origin, plane_normal, layer_step_mm: float = 0.1,
+                                 n_rings: int = 2, engine: Optional[N.Engine] = None, return_info: bool = False):
+    """_enforce_layer_gap_from_plane (stitching.py:1014-1064) on the device: the vertices ``k <= n_rings`` edges away
+    from the seeds move ``k * layer_step_mm`` along their radial direction in the plane.  ``return_info`` adds
+    ``(layer, info)``: the layer of every vertex (-1 beyond ``n_rings``) and ``launches`` / ``rings_run`` /
+    ``n_layer_vertices``."""
+    v, f = _mesh_parts(mesh)
+    v = _p3(v)
+    f = _checked_faces(f, v.shape[0])
+    seeds = np.ascontiguousarray(sorted(set(int(i) for i in seed_indices)), dtype=np.int64)
+    if seeds.size and (seeds[0] < 0 or seeds[-1] >= v.shape[0]):
+        raise ValueError("seed index out of range")
+    out = np.zeros((max(v.shape[0], 1), 3), dtype=np.float64)
+    layer = np.full(max(v.shape[0], 1), -1, dtype=np.int32)
+    info = np.zeros(3, dtype=np.int64)
+    o, n = _p3(plane_origin), _p3(plane_normal)
+    N.check(N.lib().mm_mesh_layer_push(_engine(engine).handle, N._ptr(v), v.shape[0], N._ptr(f), f.shape[0], N._ptr(seeds),
+                                       seeds.shape[0], N._ptr(o), N._ptr(n), float(layer_step_mm), int(n_rings),
+                                       N._ptr(out), N._ptr(layer), N._ptr(info)), "enforce_layer_gap_from_plane")
+    new = _with_mesh(mesh, out[:v.shape[0]].copy(), np.asarray(f))
+    if not return_info:
+        return new
+    return new, layer[:v.shape[0]].copy(), {"launches": int(info[0]), "rings_run": int(info[1]),
+                                            "n_layer_vertices": int(info[2])}
+
+
+def split_rim_edges(vertices, faces, ring_idx, counts, engine: Optional[N.Engine] = None, vert_cap: Optional[int] = None,
+                    face_cap: Optional[int] = None):
+    """The mesh side of _densify_boundary (stitching.py:894-962) on the device for a ring of vertex indices and the
+    points each ring edge receives: ``(vertices, faces, dense_ring_idx, info)``.  include/mm_ccta.h states the order
+    of everything appended.  ``vert_cap`` / ``face_cap`` are the first sizes tried; too small, the call is repeated once
+    with the sizes the first one reports."""
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    ring = np.ascontiguousarray(np.asarray(ring_idx, dtype=np.int64).ravel())
+    cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64).ravel())
+    if ring.shape[0] != cnt.shape[0]:
+        raise ValueError("one count per ring edge")
+    if ring.shape[0] < 3:
+        raise ValueError("a ring needs at least 3 vertices")
+    if cnt.size and cnt.min() < 0:
+        raise ValueError("insert counts must not be negative")
+    total = int(cnt.sum())
+    vert_cap = v.shape[0] + total + 8 if vert_cap is None else int(vert_cap)
+    face_cap = f.shape[0] + total + 8 if face_cap is None else int(face_cap)
+    dense = np.zeros(ring.shape[0] + total, dtype=np.int64)
+    info = np.zeros(6, dtype=np.int64)
+    for attempt in (0, 1):
+        out_v = np.zeros((max(vert_cap, 1), 3), dtype=np.float64)
+        out_f = np.zeros((max(face_cap, 1), 3), dtype=np.int64)
+        rc = N.lib().mm_mesh_split_rim_edges(_engine(engine).handle, N._ptr(v), v.shape[0], N._ptr(f), f.shape[0],
+                                             N._ptr(ring), ring.shape[0], N._ptr(cnt), vert_cap, face_cap, N._ptr(out_v),
+                                             N._ptr(out_f), N._ptr(dense), N._ptr(info))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and (info[0] > vert_cap or info[1] > face_cap):
+            vert_cap, face_cap = int(info[0]), int(info[1])
+            continue
+        _ring_call(rc, "split_rim_edges")
+        break
+    rep = {"n_vertices": int(info[0]), "n_faces": int(info[1]), "n_inserted": int(info[2]), "n_fanned_faces": int(info[3]),
+           "n_centroid_fans": int(info[4]), "launches": int(info[5]), "attempts": attempt + 1}
+    return out_v[:info[0]].copy(), out_f[:info[1]].copy(), dense, rep
+
+
+def densify_boundary(mesh, ring, target_n: int, engine: Optional[N.Engine] = None):
+    """_densify_boundary (stitching.py:837-962): ``(mesh, dense_ring, info)``; the ring gets ``target_n`` points, the
+    extra ones on its longest edges first, and every face that owns a subdivided edge becomes a fan.  A ring above the
+    target or off the mesh comes back as it is (``info["over_target"]`` / ``info["off_mesh"]``)."""
+    r = _p3(ring)
+    v, f = _mesh_parts(mesh)
+    v = _p3(v)
+    info = {"n_inserted": 0, "n_fanned_faces": 0, "n_centroid_fans": 0, "over_target": 0, "off_mesh": 0, "launches": 0}
+    counts, status = densify_plan(r, target_n)
+    info["over_target"] = int(status == 2)
+    if status != 1:
+        return mesh, r.copy(), info
+    idx = locate_points(v, r, engine)
+    info["launches"] = 1
+    if (idx < 0).any():
+        info["off_mesh"] = 1
+        return mesh, r.copy(), info
+    nv, nf, dense, rep = split_rim_edges(v, f, idx, counts, engine)
+    for k in ("n_inserted", "n_fanned_faces", "n_centroid_fans"):
+        info[k] = rep[k]
+    info["launches"] += rep["launches"]
+    return _with_mesh(mesh, nv, nf), nv[dense], info
+
+
+def _condition(v, f, prox_ring, dist_ring, iv_frame, prox_centroid, prox_outward, aorta, params: dict, engine,
+               vert_cap=None, face_cap=None):
+    """mm_condition_rims with the capacity retry: ``(vertices, faces, prox, dist, report)``."""
+    v = _p3(v)
+    f = _checked_faces(f, v.shape[0])
+    pr, dr, iv, ao = _p3(prox_ring), _p3(dist_ring), _p3(iv_frame), _p3(aorta if aorta is not None else ())
+    pc = _p3(prox_centroid)
+    po = None if prox_outward is None else _p3(prox_outward)
+    target = int(params["target_n"])
+    ring_cap = max(pr.shape[0], dr.shape[0], target, 1)
+    P = N.MMRimParams(int(bool(params["proximal_is_ostium"])), target, int(params.get("smooth_iterations", 5)),
+                      int(params.get("n_rings", 2)), 0, 0, ring_cap, float(params.get("smooth_alpha", 0.5)),
+                      float(params["angle_threshold_deg"]), float(params["clamp_overshoot"]),
+                      float(params.get("layer_step_mm", 0.1)))
+    vert_cap = v.shape[0] + 2 * target + 64 if vert_cap is None else int(vert_cap)
+    face_cap = f.shape[0] + 4 * target + 64 if face_cap is None else int(face_cap)
+    rep = N.MMRimReport()
+    h = _engine(engine).handle
+    attempts = 0
+    while True:
+        attempts += 1
+        P.vert_cap, P.face_cap = vert_cap, face_cap
+        out_v = np.zeros((max(vert_cap, 1), 3), dtype=np.float64)
+        out_f = np.zeros((max(face_cap, 1), 3), dtype=np.int64)
+        out_p, out_d = np.zeros((ring_cap, 3), dtype=np.float64), np.zeros((ring_cap, 3), dtype=np.float64)
+        rc = N.lib().mm_condition_rims(h, N._ptr(v), v.shape[0], N._ptr(f), f.shape[0], N._ptr(pr), pr.shape[0], N._ptr(dr),
+                                       dr.shape[0], N._ptr(iv), iv.shape[0], N._ptr(pc), N._ptr(po), N._ptr(ao), ao.shape[0],
+                                       C.byref(P), N._ptr(out_v), N._ptr(out_f), N._ptr(out_p), N._ptr(out_d), C.byref(rep))
+        if rc == MM_ERR_TOO_LARGE and attempts < 4 and (rep.n_vertices > vert_cap or rep.n_faces > face_cap):
+            vert_cap, face_cap = max(vert_cap, int(rep.n_vertices)), max(face_cap, int(rep.n_faces))
+            continue
+        _ring_call(rc, "condition_boundary_rings")
+        break
+    report = {}
+    for k in RIM_REPORT_KEYS:
+        x = getattr(rep, k)
+        report[k] = x if isinstance(x, (int, float)) else [int(y) for y in x]
+    report["attempts"] = attempts
+    return (out_v[:rep.n_vertices].copy(), out_f[:rep.n_faces].copy(), out_p[:rep.n_prox].copy(), out_d[:rep.n_dist].copy(),
+            report)
+
+
+def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n_points_iv_cont: int = 100,
+                             proximal_is_ostium: bool = True, clamp_overshoot: float = 0.5,
+                             boundary_point_ratio: float = 1.0, ostium_angle_threshold_deg: float = 45.0,
+                             engine: Optional[N.Engine] = None) -> dict:
+    """_prepare_prox_dist_boundary_pts (stitching.py:484-556), the first stage of the reference's
+    stitch_ccta_to_intravascular, as a step of its own: both rims of the cut mesh are flattened onto their best-fit
+    plane, smoothed without shrinking, respaced evenly and written back into the mesh; an ostial proximal ring has its
+    plane slid clear of the first IV frame, is clamped against the IV plane where the two meet at
+    ``ostium_angle_threshold_deg`` or more (``clamp_overshoot`` mm of clearance; the two vertex layers behind a clamped
+    ring move out by 0.1 and 0.2 mm); and both rims are densified to ``max(3, round(boundary_point_ratio * n))`` points,
+    ``n`` the points of the first downsampled IV contour, every CCTA face on a subdivided rim edge being replaced by a
+    fan, so that the strip of the stitch is point for point and the mesh has no T-junction.
+
+    The rings are those the stitch would use (``boundary_points_<n>`` of ``results``, else the mesh's open edges) and are
+    assigned to the ends as it assigns them.  Returns a new dict: ``mesh`` replaced (the same kind of container),
+    ``boundary_points_1`` / ``boundary_points_2`` the conditioned proximal and distal ring, ``boundary_points`` both,
+    ``rim_report`` what was done (RIM_REPORT_KEYS, ``n_leftover_rings``, ``target_n``).  It goes into
+    ``stitch_ccta_to_intravascular(iv_geometry, out["mesh"], out, ...)`` unchanged.  The mesh makes one trip to the
+    device and back (csrc/mm_rim.cpp, csrc/mm_rim_kernels.hip); include/mm_ccta.h states every rule."""
+    frames = _downsample_geometry(iv_geometry, int(n_points_iv_cont))
+    if not frames:
+        raise ValueError("Need at least two contours to build a mesh.")
+    prox_c, dist_c = iv_geometry.centroids[0].copy(), iv_geometry.centroids[-1].copy()
+    rings = _result_rings(results, mesh, engine)
+    if len(rings) < 2:
+        raise ValueError(f"Stitching needs a proximal and a distal boundary ring, but {len(rings)} were found. Re-run "
+                         f"the removal with target_boundaries=2 so both rims are kept as separate rings.")
+    i, j, leftover = assign_rings_to_ends(rings, prox_c, dist_c)
+    target_n = max(3, round(boundary_point_ratio * frames[0].shape[0]))
+    params = {"proximal_is_ostium": proximal_is_ostium, "target_n": target_n,
+              "angle_threshold_deg": ostium_angle_threshold_deg, "clamp_overshoot": clamp_overshoot}
+    v, f = _mesh_parts(mesh)
+    aorta = results.get("aorta_points", None)
+    new_v, new_f, prox, dist, report = _condition(v, f, rings[i], rings[j], frames[0], prox_c, prox_c - dist_c, aorta,
+                                                  params, engine)
+    report["n_leftover_rings"] = len(leftover)
+    report["target_n"] = target_n
+    out = {k: val for k, val in results.items() if not k.startswith(BOUNDARY_RING_PREFIX)}
+    out["mesh"] = _with_mesh(mesh, new_v, new_f)
+    out[f"{BOUNDARY_RING_PREFIX}1"] = prox
+    out[f"{BOUNDARY_RING_PREFIX}2"] = dist
+    out["boundary_points"] = np.concatenate([prox, dist])
+    out["rim_report"] = report
+    return out
+
+
+def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
+                       prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
+                       engine: Optional[N.Engine] = None, **conditioning) -> dict:
+    """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
+    (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
+    ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
+    carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``)."""
+    keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
+    updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
+    cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
+    n_iv = int(conditioning.get("n_points_iv_cont", 100))
+    out = stitch_ccta_to_intravascular(geometry, cond["mesh"], cond, n_points_iv_cont=n_iv, prox_start_mode=prox_start_mode,
+                                       dist_start_mode=dist_start_mode, engine=engine)
+    if fill_holes:
+        v, f = _mesh_parts(out["mesh"])
+        new_v, new_f, report = _fill(v, f, True, engine)
+        out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
+        out["fill_report"] = report
+    return out
+
+
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
 
-MM_ERR_TOO_LARGE = -3                    # include/mm_hausdorff.h
 FILL_REPORT_KEYS = ("n_vertices", "n_faces", "n_loops_filled", "n_fan_faces", "n_open_edges_before", "n_short_loops",
                     "n_irregular_components", "n_irregular_edges", "n_open_edges", "n_nonmanifold_edges",
                     "n_flipped_faces", "winding_rounds", "inverted", "volume")

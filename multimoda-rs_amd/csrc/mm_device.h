@@ -245,6 +245,24 @@ hipError_t launch_smooth_faces(const int32_t* face, long long nf, long long nv, 
                                uint8_t* next, unsigned long long* n_flips, int* launches, hipStream_t s);
 hipError_t launch_smooth_csr(const int32_t* off, const int32_t* nb, long long nv, const uint8_t* cur, uint8_t* next,
                              unsigned long long* n_flips, int* launches, hipStream_t s);
+// rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
+// rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
+// rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers
+// (layer: -1 unvisited), *n_new += the vertices set; rim_push: the vertices of layer k >= 1 pushed by k * step;
+// rim_gather: out[i] = v[index[i]]; rim_edge_faces: keep[f] = 0 and (f, a, b, c) appended to list (list_cap entries;
+// *n_list counts all) for the faces with an edge between ring neighbours (pos: ring position or -1) whose ring edge has
+// counts > 0; rim_face_gather: out[fidx[f]] = face f where fidx[f] >= 0 (fidx: launch_trim_scan of keep)
+int        rim_locate_chunk_points();
+hipError_t launch_rim_locate(const double* v, long long nv, const unsigned long long* q, int r, int32_t* index, hipStream_t s);
+hipError_t launch_rim_write(const int32_t* index, const double* pts, int n, double* v, hipStream_t s);
+hipError_t launch_rim_mark(const int32_t* index, int n, int by_position, int32_t* arr, hipStream_t s);
+hipError_t launch_rim_layer(const int32_t* face, long long nf, int32_t* layer, int32_t k, unsigned int* n_new, hipStream_t s);
+hipError_t launch_rim_push(double* v, long long nv, const int32_t* layer, const double o[3], const double n[3], double step,
+                           hipStream_t s);
+hipError_t launch_rim_gather(const double* v, const int32_t* index, int n, double* out, hipStream_t s);
+hipError_t launch_rim_edge_faces(const int32_t* face, long long nf, const int32_t* pos, const int32_t* counts, int n,
+                                 uint8_t* keep, int32_t* list, unsigned int list_cap, unsigned int* n_list, hipStream_t s);
+hipError_t launch_rim_face_gather(const int32_t* face, long long nf, const int32_t* fidx, int32_t* out, hipStream_t s);
 // branch masks (mm_branch_kernels.hip): pts = n xyz triples; cl = m packed centerline points of branch_cl_point_bytes()
 // each (x, y, z, 1 << branch_id), staged through LDS branch_tile_points() at a time; mask[i] = the bits of the centerline
 // points within squared distance r2 of point i
