@@ -524,6 +524,67 @@ int     mm_smooth_labels_faces(mm_engine* e, const uint8_t* labels, int64_t nv, 
 int     mm_smooth_labels_csr(mm_engine* e, const uint8_t* labels, int64_t nv, const int64_t* off, const int64_t* nb,
                              int64_t iterations, uint8_t* out_labels, int64_t* info);
 
+/* ---- mesh smoothing (multimodars/ccta/fixing_functions.py:52-92: the filter_taubin that ends the post-processing;
+ *      trimesh.smoothing.filter_taubin / filter_laplacian with equal weights; the isotropic remesh in front of it is not
+ *      part of this project) ----------------------------------------------------------------------------------------
+ *
+ * Adjacency.  The neighbours of vertex v are the distinct vertices w != v that share a corner pair with v in some face.
+ * A face (a, a, b) gives only a-b; repeated faces add nothing.  Row v lists its neighbours in ascending index order;
+ * deg(v) is the row's length, and a vertex with deg == 0 is isolated.  (Not mm_build_adjacency, which keeps self entries
+ * and no order.)
+ *
+ * One step with factor f.  All arithmetic is f64 and unfused.  Per coordinate x of a vertex v with deg > 0:
+ *     w = 1.0 / deg;  acc = +0.0;  for the neighbours j ascending: acc = acc + w * x_j  (the product rounded, then the
+ *     sum);  d = acc - x;  x' = x + f * d.
+ * Every step reads the coordinates of the step before only.  Isolated and pinned vertices keep their bits; pinned
+ * vertices still feed their neighbours' averages.  Non-finite coordinates propagate by IEEE.
+ *
+ * Schedules.  filter_taubin(lamb, nu, iterations) is the factors lamb, -nu, lamb, -nu, ... (step 0 takes lamb; x - nu d
+ * and x + (-nu) d are the same bits); filter_laplacian(lamb, iterations) is lamb every step.  The C ABI takes the
+ * factor array itself.
+ *
+ * trimesh.  This is trimesh's operator (laplacian_calculation with equal weights, L V - V) with the row order fixed;
+ * trimesh's own row order follows a graph library's insertion order, so parity with it holds up to the order of the sum
+ * only.  trimesh pulls an unreferenced vertex towards the origin (an empty row makes L v = 0); here it stays, counted.
+ *
+ * Ring distance.  ring[v] = the fewest edges of the adjacency from v to any seed vertex, 0 at a seed; -1 where that is
+ * more than max_ring or no seed is reachable.
+ *
+ * Report.  volume_before / volume_after: the signed volume of mm_mesh_assemble (the same t_f, the same adjacent-pair
+ * tree over the faces in input order, divided by 6) on the input and the output coordinates.  max_displacement_sq: the
+ * largest (dx dx + dy dy) + dz dz over the vertices, d = output - input; unspecified where a coordinate is not finite.
+ *
+ * Device indices are int32: nv, nf < 2^31 and face indices in [0, nv), checked before anything is allocated
+ * (MM_ERR_INVALID); the rows hold at most 6 nf entries, which must stay below 2^31 as well (MM_ERR_TOO_LARGE).
+ * Launches.  The adjacency is 7 kernels: the edge table of mm_mesh_assemble (1), the degrees (1), their exclusive scan
+ * (3), the fill (1), the sort inside each row (1).  A volume is 1 + max(1, ceil(ceil(log2 nf) / 8)).  With nv == 0 or
+ * nf == 0 nothing is launched: every vertex is isolated, the volumes are 0. */
+
+typedef struct mm_smooth_report {
+    int64_t n_vertices, n_faces, n_edges;    /* n_edges: distinct undirected edges between distinct vertices          */
+    int64_t n_isolated, n_pinned, max_degree;/* n_pinned: nonzero entries of the mask                                 */
+    int64_t steps_run, launches;             /* launches: adjacency + n_steps + two volumes + 1 (the displacement)    */
+    double  volume_before, volume_after, max_displacement_sq;
+} mm_smooth_report;
+
+/* The adjacency as CSR.  off: nv + 1 entries; nb: capacity nb_cap (6 nf always suffices).  info[4] = {entries, longest
+ * row, isolated vertices, kernel launches}.  Where nb_cap is too small, info is filled (info[0] = the capacity needed),
+ * off and nb are not written and the call returns MM_ERR_TOO_LARGE. */
+int     mm_mesh_adjacency_csr(mm_engine* e, const int64_t* faces, int64_t nf, int64_t nv, int64_t nb_cap, int64_t* off,
+                              int64_t* nb, int64_t* info);
+/* n_steps steps with factors[0 .. n_steps) on the device (mm_smooth_kernels.hip): one upload of vertices, faces and mask,
+ * the coordinates resident in two buffers in between, one download of the vertices and the report's numbers.  pinned
+ * (nullable): nv bytes, nonzero = the vertex does not move.  n_steps == 0 copies the input bit for bit, with the report
+ * filled and the volumes equal; n_steps < 0 is MM_ERR_INVALID.  out_vertices may be vertices_xyz. */
+int     mm_mesh_smooth(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                       const double* factors, int64_t n_steps, const uint8_t* pinned, double* out_vertices,
+                       mm_smooth_report* report);
+/* ring_out[v] (nv entries) = the ring distance from the n_seeds seeds, cut at max_ring: one launch marks the seeds, one
+ * finds each ring; the run stops at max_ring or behind a ring that reaches nothing.  info[3] = {vertices with a ring
+ * >= 0, ring launches run, kernel launches}.  max_ring < 0 or a seed outside [0, nv) is MM_ERR_INVALID. */
+int     mm_mesh_vertex_rings(mm_engine* e, const int64_t* faces, int64_t nf, int64_t nv, const int64_t* seeds,
+                             int64_t n_seeds, int64_t max_ring, int32_t* ring_out, int64_t* info);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

@@ -34,7 +34,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    extract_region_with_border_faces, export_section_stl, build_adjacency_map,
                    fix_mesh_winding, assemble_mesh, stitch_rings, stitch_ccta_to_intravascular, stitch, branch_masks,
                    label_branches, label_branches_pair, find_sharp_angles, label, manual_hole_fill, fill_holes,
-                   smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned)
+                   smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned, smooth_mesh,
+                   filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -70,6 +71,7 @@ __all__ = [
     "load_centerline", "prepare_centerline", "branch_masks", "label_branches", "label_branches_pair", "find_sharp_angles",
     "label", "manual_hole_fill", "fill_holes", "smooth_mesh_labels", "create_wall_mesh",
     "condition_boundary_rings", "stitch_conditioned",
+    "smooth_mesh", "filter_taubin", "filter_laplacian", "mesh_adjacency_csr", "vertex_rings", "postprocess_stitched_mesh",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

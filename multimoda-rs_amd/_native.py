@@ -116,6 +116,7 @@ EXPORTS_CCTA = [
     "mm_ring_fit_plane", "mm_ring_project_to_plane", "mm_ring_smooth_preserving_size", "mm_ring_redistribute",
     "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
+    "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
 ]
 
 
@@ -133,6 +134,13 @@ class MMFillReport(C.Structure):
         "n_vertices", "n_faces", "n_loops_filled", "n_fan_faces", "n_open_edges_before", "n_short_loops",
         "n_irregular_components", "n_irregular_edges", "n_open_edges", "n_nonmanifold_edges", "n_flipped_faces",
         "winding_rounds", "inverted")] + [("volume", C.c_double)]
+
+
+class MMSmoothReport(C.Structure):
+    """``mm_smooth_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_edges", "n_isolated", "n_pinned", "max_degree", "steps_run", "launches")] + \
+               [(name, C.c_double) for name in ("volume_before", "volume_after", "max_displacement_sq")]
 
 
 class MMRimParams(C.Structure):
@@ -541,6 +549,12 @@ def lib():
     L.mm_smooth_labels_faces.argtypes = [P, P, I64, P, I64, I64, P, P]
     L.mm_smooth_labels_csr.restype = I
     L.mm_smooth_labels_csr.argtypes = [P, P, I64, P, P, I64, P, P]
+    L.mm_mesh_adjacency_csr.restype = I
+    L.mm_mesh_adjacency_csr.argtypes = [P, P, I64, I64, I64, P, P, P]
+    L.mm_mesh_smooth.restype = I
+    L.mm_mesh_smooth.argtypes = [P, P, I64, P, I64, P, I64, P, P, C.POINTER(MMSmoothReport)]
+    L.mm_mesh_vertex_rings.restype = I
+    L.mm_mesh_vertex_rings.argtypes = [P, P, I64, I64, P, I64, I64, P, P]
     L.mm_assign_rings_to_ends.restype = I
     L.mm_assign_rings_to_ends.argtypes = [P, P, I64, P, P, P]
     L.mm_ring_start.restype = I64

@@ -1410,13 +1410,17 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
-           engine: Optional[N.Engine] = None, fill_holes: bool = False) -> dict:
+           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
-    default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  No
-    post-processing.  The reference always ends with ``manual_hole_fill`` (:330); here that is ``fill_holes=True``: the
+    default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
+    reference always ends with ``manual_hole_fill`` (:330); here that is ``fill_holes=True``: the
     stitched mesh goes through ``manual_hole_fill`` and the result carries ``fill_report`` beside ``stitch_report``.
-    The default leaves the holes open, and ``stitch_report`` says whether the result is watertight."""
+    The default leaves the holes open, and ``stitch_report`` says whether the result is watertight.  ``smooth=True``, or
+    a dict of ``smooth_mesh`` keywords (``band``, ``pinned``, ``iterations`` ...), then runs the smoothing half of the
+    reference's post-processing (``smooth_mesh``; the remesh is not part of this package) on the mesh: the point lists
+    follow the moved vertices (``sync_results_to_mesh``) and the result carries ``smooth_report``.  The default
+    ``smooth=False`` changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1426,6 +1430,19 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
+    return _smooth_result(out, smooth, engine)
+
+
+def _smooth_result(out: dict, smooth, engine) -> dict:
+    """The ``smooth`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of smooth_mesh keywords."""
+    if smooth is False or smooth is None:
+        return out
+    kw = dict(smooth) if isinstance(smooth, dict) else {}
+    kw.setdefault("engine", engine)
+    old = out["mesh"]
+    new, report = smooth_mesh(old, **kw)
+    out = sync_results_to_mesh(out, old, new)
+    out["smooth_report"] = report
     return out
 
 
@@ -1722,11 +1739,12 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
-                       engine: Optional[N.Engine] = None, **conditioning) -> dict:
+                       engine: Optional[N.Engine] = None, smooth=False, **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
-    carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``)."""
+    carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``smooth`` as in ``stitch``: the smoothing
+    runs last and adds ``smooth_report``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
@@ -1738,7 +1756,7 @@ def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return out
+    return _smooth_result(out, smooth, engine)
 
 
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
@@ -1913,3 +1931,161 @@ def create_wall_mesh(geometry, cl_aorta: Centerline, cl_rca: Centerline, cl_lca:
     out["wall_report"] = {"aortic_scaling": scaling, "coronary_scaling": float(coronary_scaling),
                           "fill_report": fill_report}
     return out
+
+
+# ---- mesh smoothing (multimodars/ccta/fixing_functions.py:52-92; trimesh.smoothing.filter_taubin / filter_laplacian) ---
+
+SMOOTH_REPORT_KEYS = ("n_vertices", "n_faces", "n_edges", "n_isolated", "n_pinned", "max_degree", "steps_run", "launches",
+                      "volume_before", "volume_after", "max_displacement_sq")
+
+
+def _n_vertices(faces: np.ndarray, n_vertices) -> int:
+    nv = (int(faces.max()) + 1 if faces.size else 0) if n_vertices is None else int(n_vertices)
+    if nv < 0:
+        raise ValueError("n_vertices must not be negative")
+    return nv
+
+
+def mesh_adjacency_csr(faces, n_vertices=None, engine: Optional[N.Engine] = None):
+    """The vertex adjacency the smoothing runs over, built on the device (csrc/mm_smooth_kernels.hip): ``(off, nb,
+    info)``.  Row ``v`` = ``nb[off[v]:off[v + 1]]`` = the distinct vertices other than ``v`` that share a corner pair
+    with it in some face, ascending (a face ``(a, a, b)`` gives ``a-b`` only; repeated faces add nothing).
+    ``n_vertices`` defaults to the largest index + 1.  ``info``: ``entries``, ``max_degree``, ``n_isolated``,
+    ``launches``.  Unlike ``build_adjacency_map`` there are no self entries and the order is fixed."""
+    f = _faces3(faces)
+    nv = _n_vertices(f, n_vertices)
+    f = _checked_faces(f, nv)
+    h = _engine(engine).handle
+    off = np.zeros(nv + 1, dtype=np.int64)
+    info = np.zeros(4, dtype=np.int64)
+    cap = 3 * f.shape[0] + 64                                             # a closed surface needs 3 nf
+    for attempt in (0, 1):
+        nb = np.zeros(max(cap, 1), dtype=np.int64)
+        rc = N.lib().mm_mesh_adjacency_csr(h, N._ptr(f), f.shape[0], nv, cap, N._ptr(off), N._ptr(nb), N._ptr(info))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and info[0] > cap:
+            cap = int(info[0])
+            continue
+        N.check(rc, "mesh_adjacency_csr")
+        break
+    return off, nb[:info[0]].copy(), {"entries": int(info[0]), "max_degree": int(info[1]), "n_isolated": int(info[2]),
+                                      "launches": int(info[3])}
+
+
+def vertex_rings_info(faces, seeds, max_ring: int, n_vertices=None, engine: Optional[N.Engine] = None):
+    """``vertex_rings`` with what the run did: ``(ring, info)``, ``info`` holding ``reached``, ``rounds``, ``launches``."""
+    f = _faces3(faces)
+    nv = _n_vertices(f, n_vertices)
+    f = _checked_faces(f, nv)
+    s = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).reshape(-1))
+    if s.size and (s.min() < 0 or s.max() >= nv):
+        raise ValueError(f"seed index out of range [0, {nv})")
+    if int(max_ring) < 0:
+        raise ValueError("max_ring must not be negative")
+    ring = np.full(nv, -1, dtype=np.int32)
+    info = np.zeros(3, dtype=np.int64)
+    N.check(N.lib().mm_mesh_vertex_rings(_engine(engine).handle, N._ptr(f), f.shape[0], nv, N._ptr(s), s.shape[0],
+                                         int(max_ring), N._ptr(ring), N._ptr(info)), "vertex_rings")
+    return ring, {"reached": int(info[0]), "rounds": int(info[1]), "launches": int(info[2])}
+
+
+def vertex_rings(faces, seeds, max_ring: int, n_vertices=None, engine: Optional[N.Engine] = None) -> np.ndarray:
+    """``ring[v]`` (int32) = the fewest mesh edges from vertex ``v`` to any of the seed vertices ``seeds`` (indices), 0 at
+    a seed; -1 for a vertex farther than ``max_ring`` edges or not connected to a seed.  A level-synchronous search on
+    the device over the adjacency of ``mesh_adjacency_csr``."""
+    return vertex_rings_info(faces, seeds, max_ring, n_vertices, engine)[0]
+
+
+def _seed_indices(seeds, vertices: np.ndarray) -> np.ndarray:
+    """Seeds given as vertex indices (an integer array) or as xyz points (matched to the vertices by value as
+    sync_results_to_mesh matches; a point that is no vertex is dropped)."""
+    a = np.asarray(seeds)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.bool_):
+        return np.flatnonzero(a) if a.dtype == np.bool_ else a.astype(np.int64).reshape(-1)
+    idx = _match(vertices, a)
+    return np.unique(idx[idx >= 0])
+
+
+def smooth_mesh(mesh, factors=None, *, lamb: float = 0.5, nu: float = 0.5, iterations: int = 10, pinned=None, band=None,
+                engine: Optional[N.Engine] = None):
+    """Laplacian / Taubin smoothing of ``mesh`` (a ``(vertices, faces)`` tuple or an object with ``.vertices`` /
+    ``.faces``) on the device: ``(mesh, report)``, the mesh of the kind given with new vertices and the same faces; the
+    input is not modified.  One step with factor ``f`` moves every vertex with a neighbour by ``f`` times the difference
+    between the equal-weight mean of its neighbours and itself; ``factors`` lists the steps' factors, and where it is
+    None the Taubin schedule ``lamb, -nu, lamb, ...`` of ``iterations`` steps is used
+    (trimesh.smoothing.filter_taubin, as fixing_functions.py:52-92 ends the post-processing).  The neighbours are summed
+    in ascending index order in unfused f64 (include/mm_ccta.h, "mesh smoothing"), so the result has one bit pattern
+    whatever the scheduling; against trimesh, whose row order is a graph library's insertion order, it agrees up to the
+    order of that sum.  A vertex without a face stays where it is (trimesh pulls it towards the origin).
+
+    ``pinned``: a bool mask over the vertices or an array of indices that do not move (they still pull their
+    neighbours).  ``band=(seeds, k)`` frees only the vertices within ``k`` edges of the seed vertices (indices, or xyz
+    points matched to the vertices by value) and pins everything else; with both, a vertex pinned by either stays.
+    ``report``: SMOOTH_REPORT_KEYS (``launches``: the kernels of the call; ``volume_before`` / ``volume_after``: the
+    signed volume assemble_mesh reports, before and after) and ``volume_ratio``."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    if factors is None:
+        if int(iterations) < 0:
+            raise ValueError("iterations must not be negative")
+        factors = [float(lamb) if i % 2 == 0 else -float(nu) for i in range(int(iterations))]
+    fac = np.ascontiguousarray(np.asarray(factors, dtype=np.float64).reshape(-1))
+    mask = None
+    if pinned is not None:
+        p = np.asarray(pinned)
+        if p.dtype == np.bool_:
+            if p.reshape(-1).shape[0] != nv:
+                raise ValueError("a pinned mask has one entry per vertex")
+            mask = p.reshape(-1).copy()
+        else:
+            p = p.astype(np.int64).reshape(-1)
+            if p.size and (p.min() < 0 or p.max() >= nv):
+                raise ValueError(f"pinned index out of range [0, {nv})")
+            mask = np.zeros(nv, dtype=bool)
+            mask[p] = True
+    if band is not None:
+        seeds, k = band
+        ring = vertex_rings(f, _seed_indices(seeds, v), int(k), nv, engine)
+        mask = (ring < 0) if mask is None else (mask | (ring < 0))
+    m8 = None if mask is None else np.ascontiguousarray(mask.astype(np.uint8))
+    out = np.zeros_like(v)
+    rep = N.MMSmoothReport()
+    N.check(N.lib().mm_mesh_smooth(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), f.shape[0], N._ptr(fac),
+                                   fac.shape[0], N._ptr(m8), N._ptr(out), C.byref(rep)), "smooth_mesh")
+    report = {k: getattr(rep, k) for k in SMOOTH_REPORT_KEYS}
+    report["volume_ratio"] = report["volume_after"] / report["volume_before"] if report["volume_before"] != 0.0 \
+        else float("nan")
+    return _with_vertices(mesh, out), report
+
+
+def filter_taubin(mesh, lamb: float = 0.5, nu: float = 0.5, iterations: int = 10, **kw):
+    """trimesh.smoothing.filter_taubin with equal weights: ``iterations`` steps alternating ``lamb`` and ``-nu``
+    (step 0 takes ``lamb``).  Returns the new mesh only; keywords as ``smooth_mesh`` (``pinned``, ``band``,
+    ``engine``)."""
+    return smooth_mesh(mesh, None, lamb=lamb, nu=nu, iterations=iterations, **kw)[0]
+
+
+def filter_laplacian(mesh, lamb: float = 0.5, iterations: int = 10, **kw):
+    """trimesh.smoothing.filter_laplacian with equal weights and without volume constraint: ``iterations`` steps of
+    factor ``lamb``.  Returns the new mesh only; keywords as ``smooth_mesh``."""
+    if int(iterations) < 0:
+        raise ValueError("iterations must not be negative")
+    return smooth_mesh(mesh, [float(lamb)] * int(iterations), **kw)[0]
+
+
+def postprocess_stitched_mesh(mesh, *, postprocessing: bool = False, lamb: float = 0.5, nu: float = 0.5,
+                              iterations: int = 10, **kw):
+    """fixing_functions.py:52-92 by the reference's name and flag.  ``postprocessing=False`` hands the mesh back as it
+    is.  ``True`` runs the Taubin smoothing that ends the reference's post-processing (``filter_taubin``); its repair
+    and isotropic remesh in front are MeshLab's and not part of this project, so ``target_edge_length_mm`` or
+    ``remesh_iterations`` raise NotImplementedError.  Other keywords go to ``smooth_mesh``."""
+    for name in ("target_edge_length_mm", "remesh_iterations"):
+        if name in kw:
+            raise NotImplementedError(f"{name}: the isotropic remesh of the reference's post-processing is not part of "
+                                      "this project; only its Taubin smoothing runs here")
+    if not postprocessing:
+        return mesh
+    return filter_taubin(mesh, lamb, nu, iterations, **kw)

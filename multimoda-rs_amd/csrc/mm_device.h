@@ -245,6 +245,24 @@ hipError_t launch_smooth_faces(const int32_t* face, long long nf, long long nv, 
                                uint8_t* next, unsigned long long* n_flips, int* launches, hipStream_t s);
 hipError_t launch_smooth_csr(const int32_t* off, const int32_t* nb, long long nv, const uint8_t* cur, uint8_t* next,
                              unsigned long long* n_flips, int* launches, hipStream_t s);
+// mesh smoothing (mm_smooth_kernels.hip).  Every launcher adds the kernels it launched to *launches.  mesh_csr: from
+// weld_edges' table (keys) the sorted adjacency off (nv + 1), nb (as many entries as off[nv]: twice the edges between
+// different vertices, at most 6 nf); deg (nv words) and tile_sum (mesh_csr_tiles(nv) + 1) are scratch; counts[0..2] =
+// those edges, the vertices without a neighbour, the longest row.  mesh_step: out = one step with factor f over in (two
+// buffers of nv xyz triples; pinned nullable).  mesh_ring_seed: ring = -1 everywhere, 0 at the seeds, *reached = the
+// distinct seeds; mesh_ring: ring r >= 1 of the level-synchronous search, *reached += the vertices it set.  mesh_disp:
+// *max_bits = the bits of the largest squared distance between a and b
+size_t     mesh_csr_tiles(long long nv);
+hipError_t launch_mesh_csr(const unsigned long long* keys, int log2_cap, long long nv, int32_t* deg, int32_t* off,
+                           long long* tile_sum, int32_t* nb, unsigned long long* counts, int* launches, hipStream_t s);
+hipError_t launch_mesh_step(const int32_t* off, const int32_t* nb, const double* in, double* out, long long nv, double f,
+                            const uint8_t* pinned, int* launches, hipStream_t s);
+hipError_t launch_mesh_ring_seed(const int32_t* seeds, long long n, int32_t* ring, long long nv,
+                                 unsigned long long* reached, int* launches, hipStream_t s);
+hipError_t launch_mesh_ring(const int32_t* off, const int32_t* nb, long long nv, int32_t* ring, int32_t r,
+                            unsigned long long* reached, int* launches, hipStream_t s);
+hipError_t launch_mesh_disp(const double* a, const double* b, long long nv, unsigned long long* max_bits, int* launches,
+                            hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

@@ -1,0 +1,306 @@
+// mm_smooth.cpp -- CCTA mesh finishing (include/mm_ccta.h, "mesh smoothing"): the sorted vertex adjacency, Laplacian /
+// Taubin smoothing with a pin mask, ring distances from seed vertices.  Reference: multimodars/ccta/fixing_functions.py:
+// 52-92 (the filter_taubin that ends the post-processing).  The host checks the arguments, narrows the faces to int32,
+// lays the device buffers out and reads the report back; everything over the mesh runs on the device
+// (mm_weld_kernels.hip for the edge table and the volume, mm_smooth_kernels.hip for the rest).
+//
+// mm_mesh_smooth keeps the input coordinates (v0) for the displacement and ping-pongs between two buffers (vA, vB): step
+// 0 reads v0 and writes vA, every later step swaps vA and vB.  The report's numbers sit between vA and vB, so whichever
+// of the two holds the result comes down together with them in one copy.
+#include <algorithm>
+#include <climits>
+#include <cstring>
+
+#include "../../include/mm_ccta.h"
+#include "mm_engine.h"
+
+namespace mm {
+namespace {
+
+#define MM_TRY_HIP(call)                                          \
+    do {                                                          \
+        const hipError_t e__ = (call);                            \
+        if (e__ != hipSuccess) return hip_error(e__, #call);      \
+    } while (0)
+
+inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+
+constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
+
+int engine_of(mm_engine* h, Engine*& e)
+{
+    e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    const hipError_t he = hipSetDevice(e->device);
+    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
+    return MM_OK;
+}
+
+int log2_at_least(unsigned long long n)
+{
+    int l = 8;
+    while ((1ull << l) < n) ++l;
+    return l;
+}
+
+// the checks every entry point shares; the faces are read once here
+int mesh_args(const int64_t* faces, int64_t nf, int64_t nv, const char* who)
+{
+    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (nf > 0 && !faces))
+        return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
+    for (int64_t k = 0; k < 3 * nf; ++k)
+        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, std::string(who) + ": face index out of range");
+    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
+    return MM_OK;
+}
+
+// The adjacency's device buffers, laid out behind whatever the caller placed first.  nb takes the place of the edge
+// table's owner words (8 bytes a slot, at least 6 nf slots): the fill runs behind the insertion, which alone writes them.
+struct CsrDev {
+    size_t o_keys, o_cnt, o_own, o_deg, o_off, o_tile, o_counts;
+    int log2_e;
+    unsigned long long* keys; unsigned int *cnt, *own;
+    int32_t *deg, *off, *nb;
+    long long* tile;
+    unsigned long long* counts;           // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
+
+    template <class Take> void plan(Take&& take, int64_t nf, int64_t nv)
+    {
+        log2_e = log2_at_least(6ull * (unsigned long long)nf);
+        const size_t cap = (size_t)1 << log2_e;
+        o_keys = take(cap * 8); o_cnt = take(cap * 4); o_own = take(cap * 8);
+        o_deg = take((size_t)nv * 4); o_off = take(((size_t)nv + 1) * 4);
+        o_tile = take((mesh_csr_tiles(nv) + 1) * 8);
+    }
+    void bind(unsigned char* b, unsigned long long* counts_at)
+    {
+        keys = (unsigned long long*)(b + o_keys); cnt = (unsigned int*)(b + o_cnt); own = (unsigned int*)(b + o_own);
+        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)own;
+        tile = (long long*)(b + o_tile);
+        counts = counts_at;
+    }
+};
+
+int csr_build(Engine* e, const CsrDev& d, const int32_t* face, int64_t nf, int64_t nv, int* launches)
+{
+    MM_TRY_HIP(launch_weld_edges(face, nf, d.keys, d.cnt, d.own, d.log2_e, e->stream));
+    ++*launches;                                                       // nf > 0: the insertion ran
+    MM_TRY_HIP(launch_mesh_csr(d.keys, d.log2_e, nv, d.deg, d.off, d.tile, d.nb, d.counts, launches, e->stream));
+    return MM_OK;
+}
+
+// the kernels of launch_weld_volume: the terms, then the pair tree 8 levels a launch
+int volume_launches(int64_t nf)
+{
+    int levels = 0;
+    while ((1ll << levels) < nf) ++levels;
+    return 1 + std::max(1, (levels + 7) / 8);
+}
+
+}  // namespace
+}  // namespace mm
+
+using namespace mm;
+
+extern "C" {
+
+int mm_mesh_adjacency_csr(mm_engine* h, const int64_t* faces, int64_t nf, int64_t nv, int64_t nb_cap, int64_t* off,
+                          int64_t* nb, int64_t* info)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (nb_cap < 0 || !off || !info || (nb_cap > 0 && !nb)) return set_error(MM_ERR_INVALID, "mm_mesh_adjacency_csr: bad arguments");
+    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_adjacency_csr"))) return rc;
+    std::memset(info, 0, 4 * sizeof(int64_t));
+    if (nv == 0 || nf == 0) {
+        for (int64_t i = 0; i <= nv; ++i) off[i] = 0;
+        info[2] = nv;
+        return MM_OK;
+    }
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
+    const size_t o_face = take((size_t)nf * 12);
+    CsrDev d;
+    d.plan(take, nf, nv);
+    const size_t o_counts = take(4 * 8);
+    if ((rc = e->ensure(e->host_pts, (size_t)nf * 12 + 512, true))) return rc;
+    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    unsigned char* hb = (unsigned char*)e->host_pts.p;
+    unsigned char* b = (unsigned char*)e->dev_pts.p;
+    d.bind(b, (unsigned long long*)(b + o_counts));
+    int32_t* hf = (int32_t*)hb;
+    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    const int32_t* d_face = (const int32_t*)(b + o_face);
+    int launches = 0;
+    MM_TRY_HIP(hipMemcpyAsync(b + o_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
+    if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
+    MM_TRY_HIP(hipMemcpyAsync(hb, d.counts, 4 * 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    const unsigned long long* c = (const unsigned long long*)hb;
+    const int64_t entries = 2 * (int64_t)c[0];
+    if (entries < 0 || entries > 6 * nf) return set_error(MM_ERR_HIP, "mm_mesh_adjacency_csr: entry count out of range");
+    info[0] = entries; info[1] = (int64_t)c[2]; info[2] = (int64_t)c[1]; info[3] = launches;
+    if (entries > nb_cap) return set_error(MM_ERR_TOO_LARGE, "mm_mesh_adjacency_csr: nb_cap too small (info[0] holds the size)");
+    const size_t h_nb = up256(((size_t)nv + 1) * 4);
+    if ((rc = e->ensure(e->host_pts, h_nb + (size_t)entries * 4 + 512, true))) return rc;
+    hb = (unsigned char*)e->host_pts.p;
+    MM_TRY_HIP(hipMemcpyAsync(hb, d.off, ((size_t)nv + 1) * 4, hipMemcpyDeviceToHost, e->stream));
+    if (entries > 0) MM_TRY_HIP(hipMemcpyAsync(hb + h_nb, d.nb, (size_t)entries * 4, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    const int32_t* ho = (const int32_t*)hb;
+    const int32_t* hn = (const int32_t*)(hb + h_nb);
+    if (ho[nv] != entries) return set_error(MM_ERR_HIP, "mm_mesh_adjacency_csr: the scan and the edge count disagree");
+    for (int64_t i = 0; i <= nv; ++i) off[i] = ho[i];
+    for (int64_t k = 0; k < entries; ++k) nb[k] = hn[k];
+    return MM_OK;
+}
+
+int mm_mesh_smooth(mm_engine* h, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                   const double* factors, int64_t n_steps, const uint8_t* pinned, double* out_vertices,
+                   mm_smooth_report* report)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (!report || n_steps < 0 || (n_steps > 0 && !factors) || (nv > 0 && (!vertices_xyz || !out_vertices)))
+        return set_error(MM_ERR_INVALID, "mm_mesh_smooth: bad arguments");
+    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_smooth"))) return rc;
+    std::memset(report, 0, sizeof(*report));
+    report->n_vertices = nv;
+    report->n_faces = nf;
+    report->steps_run = n_steps;
+    if (pinned)
+        for (int64_t i = 0; i < nv; ++i) report->n_pinned += pinned[i] != 0;
+    if (nv == 0 || nf == 0) {                                           // no edge: nothing moves
+        report->n_isolated = nv;
+        if (nv > 0) std::memmove(out_vertices, vertices_xyz, (size_t)nv * 24);
+        return MM_OK;
+    }
+
+    // device: [faces | mask | v0] (the upload), vA, the report's numbers, vB, the adjacency, the volume's scratch
+    const size_t vbytes = (size_t)nv * 24;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
+    const size_t o_face = take((size_t)nf * 12), o_mask = take(pinned ? (size_t)nv : 0), o_v0 = take(vbytes);
+    const size_t up_bytes = o_v0 + vbytes;
+    const size_t o_va = take(vbytes), o_num = take(256), o_vb = take(vbytes);
+    CsrDev d;
+    d.plan(take, nf, nv);
+    const size_t o_sa = take((size_t)nf * 8), o_sb = take(weld_sum_scratch(nf) * 8);
+    const size_t down_bytes = o_vb + vbytes - o_va;
+    if ((rc = e->ensure(e->host_pts, std::max(up_bytes, down_bytes) + 512, true))) return rc;
+    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    unsigned char* hb = (unsigned char*)e->host_pts.p;
+    unsigned char* b = (unsigned char*)e->dev_pts.p;
+    enum { kVolBefore = 0, kVolAfter = 1, kDisp = 2, kCounts = 3 };    // 8-byte words of the numbers block
+    double* d_num = (double*)(b + o_num);
+    d.bind(b, (unsigned long long*)(d_num + kCounts));
+    int32_t* hf = (int32_t*)(hb + o_face);
+    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    if (pinned) std::memcpy(hb + o_mask, pinned, (size_t)nv);
+    std::memcpy(hb + o_v0, vertices_xyz, vbytes);
+    const int32_t* d_face = (const int32_t*)(b + o_face);
+    const uint8_t* d_mask = pinned ? (const uint8_t*)(b + o_mask) : nullptr;
+    const double* v0 = (const double*)(b + o_v0);
+    double *va = (double*)(b + o_va), *vb = (double*)(b + o_vb);
+    double *sa = (double*)(b + o_sa), *sb = (double*)(b + o_sb);
+    int launches = 0;
+    MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
+    MM_TRY_HIP(launch_weld_volume(v0, d_face, nf, sa, sb, d_num + kVolBefore, e->stream));
+    const double* cur = v0;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        double* next = cur == va ? vb : va;
+        MM_TRY_HIP(launch_mesh_step(d.off, d.nb, cur, next, nv, factors[i], d_mask, &launches, e->stream));
+        cur = next;
+    }
+    MM_TRY_HIP(launch_weld_volume(cur, d_face, nf, sa, sb, d_num + kVolAfter, e->stream));
+    launches += 2 * volume_launches(nf);
+    MM_TRY_HIP(launch_mesh_disp(v0, cur, nv, (unsigned long long*)(d_num + kDisp), &launches, e->stream));
+    // one copy down: [vA | numbers] or [numbers | vB], whichever holds the result; the numbers alone without a step
+    const size_t from = cur == va ? o_va : o_num;
+    const size_t bytes = cur == va ? o_num + 256 - o_va : (cur == vb ? o_vb + vbytes - o_num : 256);
+    MM_TRY_HIP(hipMemcpyAsync(hb, b + from, bytes, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    const double* num = (const double*)(hb + (o_num - from));
+    if (cur == v0) std::memmove(out_vertices, vertices_xyz, vbytes);
+    else std::memcpy(out_vertices, hb + ((cur == va ? o_va : o_vb) - from), vbytes);
+    unsigned long long c[4];
+    std::memcpy(c, num + kCounts, sizeof(c));
+    report->n_edges = (int64_t)c[0];
+    report->n_isolated = (int64_t)c[1];
+    report->max_degree = (int64_t)c[2];
+    report->launches = launches;
+    report->volume_before = num[kVolBefore] / 6.0;
+    report->volume_after = num[kVolAfter] / 6.0;
+    report->max_displacement_sq = num[kDisp];
+    return MM_OK;
+}
+
+int mm_mesh_vertex_rings(mm_engine* h, const int64_t* faces, int64_t nf, int64_t nv, const int64_t* seeds,
+                         int64_t n_seeds, int64_t max_ring, int32_t* ring_out, int64_t* info)
+{
+    Engine* e;
+    int rc = engine_of(h, e);
+    if (rc) return rc;
+    if (!info || n_seeds < 0 || n_seeds > kMaxIndex || max_ring < 0 || (n_seeds > 0 && !seeds) || (nv > 0 && !ring_out))
+        return set_error(MM_ERR_INVALID, "mm_mesh_vertex_rings: bad arguments");
+    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_vertex_rings"))) return rc;
+    for (int64_t k = 0; k < n_seeds; ++k)
+        if (seeds[k] < 0 || seeds[k] >= nv) return set_error(MM_ERR_INVALID, "mm_mesh_vertex_rings: seed out of range");
+    std::memset(info, 0, 3 * sizeof(int64_t));
+    if (nv == 0) return MM_OK;
+    if (nf == 0 || n_seeds == 0) {                                      // no edge or no seed: the seeds alone
+        for (int64_t i = 0; i < nv; ++i) ring_out[i] = -1;
+        for (int64_t k = 0; k < n_seeds; ++k) {
+            info[0] += ring_out[seeds[k]] == -1;
+            ring_out[seeds[k]] = 0;
+        }
+        return MM_OK;
+    }
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
+    const size_t o_face = take((size_t)nf * 12), o_seed = take((size_t)n_seeds * 4);
+    const size_t up_bytes = o_seed + (size_t)n_seeds * 4;
+    CsrDev d;
+    d.plan(take, nf, nv);
+    const size_t o_ring = take((size_t)nv * 4), o_counts = take(4 * 8), o_reached = take(8);
+    const size_t h_flag = up256(std::max(up_bytes, (size_t)nv * 4));   // the round's count, behind upload and download
+    if ((rc = e->ensure(e->host_pts, h_flag + 512, true))) return rc;
+    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    unsigned char* hb = (unsigned char*)e->host_pts.p;
+    unsigned char* b = (unsigned char*)e->dev_pts.p;
+    d.bind(b, (unsigned long long*)(b + o_counts));
+    int32_t* hf = (int32_t*)(hb + o_face);
+    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    int32_t* hs = (int32_t*)(hb + o_seed);
+    for (int64_t k = 0; k < n_seeds; ++k) hs[k] = (int32_t)seeds[k];
+    const int32_t* d_face = (const int32_t*)(b + o_face);
+    int32_t* d_ring = (int32_t*)(b + o_ring);
+    unsigned long long* d_reached = (unsigned long long*)(b + o_reached);
+    const unsigned long long* h_reached = (const unsigned long long*)(hb + h_flag);
+    int launches = 0;
+    MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
+    if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
+    MM_TRY_HIP(launch_mesh_ring_seed((const int32_t*)(b + o_seed), n_seeds, d_ring, nv, d_reached, &launches, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hb + h_flag, d_reached, 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    int64_t reached = (int64_t)h_reached[0], rounds = 0;
+    for (int64_t r = 1; r <= max_ring; ++r) {                           // a round that reaches nothing is the last
+        MM_TRY_HIP(launch_mesh_ring(d.off, d.nb, nv, d_ring, (int32_t)r, d_reached, &launches, e->stream));
+        MM_TRY_HIP(hipMemcpyAsync(hb + h_flag, d_reached, 8, hipMemcpyDeviceToHost, e->stream));
+        MM_TRY_HIP(hipStreamSynchronize(e->stream));
+        ++rounds;
+        const int64_t now = (int64_t)h_reached[0];
+        if (now == reached) break;
+        reached = now;
+    }
+    MM_TRY_HIP(hipMemcpyAsync(hb, d_ring, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    std::memcpy(ring_out, hb, (size_t)nv * 4);
+    info[0] = reached; info[1] = rounds; info[2] = launches;
+    return MM_OK;
+}
+
+}  // extern "C"
