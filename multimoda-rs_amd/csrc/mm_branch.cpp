@@ -8,29 +8,12 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
 
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct BranchClPointH { double x, y, z; uint64_t bit; };   // BranchClPoint in mm_branch_kernels.hip
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
 
 int branch_masks(mm_engine* h, const mm_clpoint* cl, int64_t ncl, const double* pts, int64_t n, double radius,
                  uint64_t* masks, const char* who)

@@ -14,7 +14,7 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_adjacency.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 #include "mm_pool.h"
 #include "mm_trace.h"
 
@@ -34,14 +34,6 @@ struct Set3 {
     }
 };
 struct NnMorphH { int32_t dst_off, n, aux_off, pad; double adj; };   // device: pool[dst_off + j] = aux point j moved by adj
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
 
 // Slab order of a point set: points sorted by their coordinate along the longest axis of the set's bounding
 // box (quantised to 20 bits, stable LSD radix sort), so that groups of consecutive points are slabs.
@@ -599,15 +591,6 @@ int clean_up_points(Engine* e, const double* cleanup, int64_t nc, const double* 
             to_ref[(size_t)i] = ratio >= min_ratio ? 1 : 0;
         }
     }
-    return MM_OK;
-}
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
     return MM_OK;
 }
 
@@ -1202,8 +1185,7 @@ int64_t mm_faces_near_points(mm_engine* h, const double* vertices, int64_t nv, c
         return set_error(MM_ERR_INVALID, "mm_faces_near_points: bad arguments");
     if (nf > 0) std::memset(face_selected, 0, (size_t)nf);
     if (n == 0 || nv == 0 || nf == 0) return 0;                                                   // :248-250
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_faces_near_points: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_faces_near_points"))) return rc;
     std::vector<std::vector<uint32_t>> cnt;
     if ((rc = radius_counts(e, {Set3{vertices, nv}, Set3{pts, n}}, {{0, 1}}, tol * tol, cnt))) return rc;   // :259-273
     int64_t k = 0;
@@ -1257,8 +1239,7 @@ int mm_final_reclassification(const double* vertices, int64_t nv, const int64_t*
     if (nv < 0 || nf < 0 || nr < 0 || nl < 0 || nrr < 0 || nlr < 0 || (nv > 0 && (!vertices || !label)) ||
         (nf > 0 && !faces) || (nr > 0 && !rca) || (nl > 0 && !lca) || (nrr > 0 && !rca_rm) || (nlr > 0 && !lca_rm))
         return set_error(MM_ERR_INVALID, "mm_final_reclassification: bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_final_reclassification: face index out of range");
+    if (const int rc = faces_in_range(faces, nf, nv, "mm_final_reclassification")) return rc;
     std::unordered_map<BitsKey, int64_t, BitsHash> idx;                                   // :353-358 the last index wins
     idx.reserve((size_t)nv);
     for (int64_t i = 0; i < nv; ++i) idx[bits_key(vertices + 3 * i)] = i;

@@ -16,36 +16,10 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
-
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
-
-int log2_at_least(unsigned long long n)
-{
-    int l = 8;
-    while ((1ull << l) < n) ++l;
-    return l;
-}
 
 // ---- the walk over the rim (host) -------------------------------------------------------------------------------------
 
@@ -206,8 +180,7 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
     if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || !report || vert_cap < 0 || face_cap < 0 ||
         (nv > 0 && !vertices_xyz) || (nf > 0 && !faces) || (vert_cap > 0 && !out_vertices) || (face_cap > 0 && !out_faces))
         return set_error(MM_ERR_INVALID, "mm_fill_holes: bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_fill_holes: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_fill_holes"))) return rc;
     std::memset(report, 0, sizeof(*report));
     const bool fix = fix_normals != 0;
     if (nf == 0) {                                                    // no face, no rim
@@ -219,31 +192,31 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
 
     // ---- phase 1 (dev_pts): faces up, winding, open half-edges down
     enum { kFlipped = 0, kOpen = 1, kNonManifold = 2, kConflict = 3, kOpen2 = 4, kNonManifold2 = 5, kConflict2 = 6, kCounts = 8 };
-    const int log2_e = log2_at_least(6ull * (unsigned long long)nf);
-    const size_t cap_e = (size_t)1 << log2_e;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_keys = take(cap_e * 8), o_cnt = take(cap_e * 4), o_own = take(cap_e * 8);
-    const size_t o_link = take((size_t)nf * 4), o_list = take((size_t)nf * 24), o_nlist = take(8);
-    const size_t o_counts = take(kCounts * 8), o_changed = take(4);
+    Carve lay;
+    EdgeTable t;
+    const size_t o_face = lay.take((size_t)nf * 12);
+    t.plan(lay, nf);
+    const size_t o_link = lay.take((size_t)nf * 4), o_list = lay.take((size_t)nf * 24), o_nlist = lay.take(8);
+    const size_t o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 24 + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)hb;
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
+    t.bind(b);
     int32_t* d_face = (int32_t*)(b + o_face);
     unsigned long long* d_counts = (unsigned long long*)(b + o_counts);
     unsigned long long* d_list = (unsigned long long*)(b + o_list);
     unsigned long long* d_nlist = (unsigned long long*)(b + o_nlist);
-    WindDev w{(unsigned long long*)(b + o_keys), (unsigned int*)(b + o_cnt), (unsigned int*)(b + o_own),
-              (unsigned int*)(b + o_link), (unsigned int*)(b + o_changed), d_counts + kFlipped, d_counts + kOpen, log2_e};
+    WindDev w{t.keys, t.cnt, t.own, (unsigned int*)(b + o_link), (unsigned int*)(b + o_changed), d_counts + kFlipped,
+              d_counts + kOpen, t.log2_e};
     MM_TRY_HIP(hipMemcpyAsync(d_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemsetAsync(d_counts, 0, kCounts * 8, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));                      // the pinned buffer takes the round flags next
     int64_t rounds = 0;
     if ((rc = weld_wind(e, w, d_face, nf, fix, &rounds))) return rc;
-    MM_TRY_HIP(launch_close_half_edges(w.keys, w.cnt, w.own, log2_e, fix ? w.link : nullptr, d_list,
+    MM_TRY_HIP(launch_close_half_edges(w.keys, w.cnt, w.own, w.log2_e, fix ? w.link : nullptr, d_list,
                                        3ull * (unsigned long long)nf, d_nlist, e->stream));
     unsigned long long* h_n = (unsigned long long*)hb;
     MM_TRY_HIP(hipMemcpyAsync(h_n, d_nlist, 8, hipMemcpyDeviceToHost, e->stream));
@@ -286,15 +259,16 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         return set_error(MM_ERR_TOO_LARGE, "mm_fill_holes: vert_cap / face_cap too small (the report holds the sizes)");
 
     // ---- phase 2 (dev_lvl): sized by the result
-    const int log2_e2 = log2_at_least(6ull * (unsigned long long)nf2);
-    const size_t cap_e2 = (size_t)1 << log2_e2;
-    o = 0;
-    const size_t p_fan = take((size_t)n_fan * 12), p_vert = take(fix ? (size_t)nv2 * 24 : 0);
-    const size_t up_bytes = o;
-    const size_t p_face = take((size_t)nf2 * 12), p_keys = take(cap_e2 * 8), p_cnt = take(cap_e2 * 4), p_own = take(cap_e2 * 8);
-    const size_t p_sa = take(fix ? (size_t)nf2 * 8 : 0), p_sb = take(fix ? weld_sum_scratch(nf2) * 8 : 0), p_vol = take(8);
+    Carve lay2;
+    EdgeTable t2;
+    const size_t p_fan = lay2.take((size_t)n_fan * 12), p_vert = lay2.take(fix ? (size_t)nv2 * 24 : 0);
+    const size_t up_bytes = lay2.size();
+    const size_t p_face = lay2.take((size_t)nf2 * 12);
+    t2.plan(lay2, nf2);
+    const size_t p_sa = lay2.take(fix ? (size_t)nf2 * 8 : 0), p_sb = lay2.take(fix ? weld_sum_scratch(nf2) * 8 : 0);
+    const size_t p_vol = lay2.take(8);
     if ((rc = e->ensure(e->host_pts, std::max(up_bytes, (size_t)nf2 * 12) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_lvl, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_lvl, lay2.size(), false))) return rc;
     hb = (unsigned char*)e->host_pts.p;
     unsigned char* b2 = (unsigned char*)e->dev_lvl.p;
     int32_t* h_fan = (int32_t*)(hb + p_fan);
@@ -317,13 +291,12 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         if (n_loops > 0) std::memcpy(hb + p_vert + (size_t)nv * 24, centroids.data(), (size_t)n_loops * 24);
     }
     int32_t* d_face2 = (int32_t*)(b2 + p_face);
-    unsigned long long* keys2 = (unsigned long long*)(b2 + p_keys);
-    unsigned int *cnt2 = (unsigned int*)(b2 + p_cnt), *own2 = (unsigned int*)(b2 + p_own);
+    t2.bind(b2);
     if (up_bytes > 0) MM_TRY_HIP(hipMemcpyAsync(b2, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(d_face2, d_face, (size_t)nf * 12, hipMemcpyDeviceToDevice, e->stream));
     MM_TRY_HIP(launch_close_fan((const int32_t*)(b2 + p_fan), n_fan, nv, d_face2, nf, e->stream));
-    MM_TRY_HIP(launch_weld_edges(d_face2, nf2, keys2, cnt2, own2, log2_e2, e->stream));
-    MM_TRY_HIP(launch_weld_edge_report(keys2, cnt2, own2, log2_e2, nullptr, d_counts + kOpen2, e->stream));
+    MM_TRY_HIP(launch_weld_edges(d_face2, nf2, t2.keys, t2.cnt, t2.own, t2.log2_e, e->stream));
+    MM_TRY_HIP(launch_weld_edge_report(t2.keys, t2.cnt, t2.own, t2.log2_e, nullptr, d_counts + kOpen2, e->stream));
     double volume = 0.0;
     int inverted = 0;
     if (fix) {
@@ -344,7 +317,7 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
     MM_TRY_HIP(hipMemcpyAsync(hb + h_counts, d_counts, kCounts * 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     const int32_t* f32 = (const int32_t*)hb;
-    for (int64_t k = 0; k < 3 * nf2; ++k) out_faces[k] = f32[k];
+    widen_faces(out_faces, f32, 3 * nf2);
     if (nv > 0) std::memcpy(out_vertices, vertices_xyz, (size_t)nv * 24);
     if (n_loops > 0) std::memcpy(out_vertices + 3 * nv, centroids.data(), (size_t)n_loops * 24);
     const unsigned long long* c = (const unsigned long long*)(hb + h_counts);
@@ -362,15 +335,14 @@ int mm_smooth_labels_faces(mm_engine* h, const uint8_t* labels, int64_t nv, cons
     int rc = smooth_args(h, e, labels, nv, iterations, out_labels, info, "mm_smooth_labels_faces");
     if (rc) return rc;
     if (nf < 0 || nf > kMaxIndex || (nf > 0 && !faces)) return set_error(MM_ERR_INVALID, "mm_smooth_labels_faces: bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, "mm_smooth_labels_faces: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_smooth_labels_faces"))) return rc;
     std::memset(info, 0, 4 * sizeof(int64_t));
     if (nv == 0) return MM_OK;
     if (iterations == 0) { std::memmove(out_labels, labels, (size_t)nv); return MM_OK; }
     const size_t topo = (size_t)nf * 12;
     if ((rc = e->ensure(e->host_pts, up256(up256(topo) + (size_t)nv) + 512, true))) return rc;
     int32_t* hf = (int32_t*)e->host_pts.p;
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     return smooth_run(e, labels, nv, topo, false, nf, iterations, out_labels, info);
 }
 

@@ -228,6 +228,7 @@ hipError_t launch_weld_flip(int32_t* face, long long nf, const unsigned int* lin
 hipError_t launch_weld_edge_report(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
                                    int log2_cap, const unsigned int* link, unsigned long long* counts, hipStream_t s);
 size_t     weld_sum_scratch(long long nf);
+int        weld_volume_launches(long long nf);   // the kernels launch_weld_volume launches for nf faces
 hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
                               hipStream_t s);
 hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s);

@@ -219,16 +219,4 @@ struct FirstMinState {
 int hausdorff_sets_first_min(Engine* e, const std::vector<SetRef>& sets, const std::vector<std::array<int32_t, 2>>& pairs,
                              int32_t* best, double* best_cost, int64_t* n_exact, FirstMinState* st = nullptr);
 
-// The winding stage of the mesh assembly (mm_stitch.cpp; mm_close.cpp runs it too), on nf int32 faces on the device, in
-// place: the edge table (keys, cnt, own: 2^log2_e slots, at least 6 nf), with `fix` the parity union-find (link: nf
-// words; changed: one) and the flips (*n_flipped += their number), then the edge report (edge_counts[0..2] += open,
-// non-manifold, conflicting edges).  The table and link stay as built: own's directions are those before the flips.
-// The first word of e->host_pts takes the round flags.  *rounds = the union-find's launches.
-struct WindDev {
-    unsigned long long* keys; unsigned int *cnt, *own, *link, *changed;
-    unsigned long long *n_flipped, *edge_counts;
-    int log2_e;
-};
-int weld_wind(Engine* e, const WindDev& d, int32_t* face, int64_t nf, bool fix, int64_t* rounds);
-
 }  // namespace mm

@@ -34,6 +34,7 @@
 #include <cstdio>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 #include "../../include/mm_hausdorff.h"
 
 namespace mm {
@@ -140,17 +141,7 @@ static __device__ __forceinline__ T wave_max(T v)
 //   R      reference points (rows) per lane held in registers
 //   NLI    row lanes per workgroup (threads = 16 * NLI)
 //   EXACT  reference operation order, absolute coordinates, angle==0 shortcut
-// XCD-aware work order.  Workgroups are dealt round-robin over the 8 XCDs (observed, not contractual:
-// b and b+8 share an XCD and its private 4 MiB L2), while the work list is pair-major (all candidate
-// blocks of a pair are adjacent).  With the identity mapping every pair's point sets and tables are
-// pulled into all eight L2s; this bijective remap hands each XCD one contiguous eighth of the list, so
-// a pair is fetched from HBM by one XCD (or two, at a boundary).  Speed/traffic only, never correctness.
-static __device__ __forceinline__ int xcd_work_index(int b, int n)
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-
+// Work order: xcd_work_index (mm_xcd.h).
 // Work items come either from a host-built table (n_work_dev == nullptr) or from the
 // device shortlist queue (count read from *n_work_dev); workgroups stride over them, so
 // every wave terminates whatever the queue length is.

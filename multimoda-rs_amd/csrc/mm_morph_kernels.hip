@@ -22,6 +22,7 @@
 #include <cfloat>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 
 namespace mm {
 
@@ -31,12 +32,6 @@ static constexpr int kMorphLanes = 256;   // points per work item
 struct MorphJob { int32_t p_off, np, c_off, nc; double adj; };   // points [p_off, p_off + np), centerline [c_off, c_off + nc)
 struct MorphWork { int32_t job, p0; };
 
-static __device__ __forceinline__ int morph_xcd_work_index(int b, int n)   // see xcd_work_index in mm_kernels.hip
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-
 // pts, cl, out: xyz triples; nearest / out at the point's position
 __global__ void __launch_bounds__(256)
 k_cl_morph(const MorphJob* __restrict__ jobs, const MorphWork* __restrict__ work, int n_work,
@@ -45,7 +40,7 @@ k_cl_morph(const MorphJob* __restrict__ jobs, const MorphWork* __restrict__ work
 {
     __shared__ double4 s_c[kMorphTile];
     const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_work ? morph_xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
         const MorphWork w = work[wi];
         const MorphJob jb = jobs[w.job];

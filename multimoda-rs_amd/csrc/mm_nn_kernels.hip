@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 
 namespace mm {
 
@@ -35,12 +36,6 @@ struct NnWork { int32_t pair, q0, c0, n_chunks; double lb2; };
 
 static constexpr int kNnChunk = 512;
 static constexpr int kNnSpan = 10;
-
-static __device__ __forceinline__ int nn_xcd_work_index(int b, int n)   // see xcd_work_index in mm_kernels.hip
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
 
 __global__ void __launch_bounds__(256)
 k_nn3_fill(unsigned long long* __restrict__ out, long long n)
@@ -81,7 +76,7 @@ k_nn3_min(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int
     __shared__ double4 s_p[CH];
     __shared__ unsigned long long s_max;
     const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_work ? nn_xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
         const NnWork w = work[wi];
         const NnPair pd = pairs[w.pair];
@@ -154,7 +149,7 @@ k_nn3_count(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, i
     constexpr int NT = 256, CH = kNnChunk;
     __shared__ double4 s_p[CH];
     const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_work ? nn_xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
         const NnWork w = work[wi];
         const NnPair pd = pairs[w.pair];

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 
 namespace mm {
 
@@ -27,12 +28,6 @@ static constexpr int kRayChunk = 256;   // faces per LDS chunk (9 x 256 doubles 
 static constexpr int kRayLanes = 256;   // rays per work item
 
 struct RayPartial { int32_t count, face; double t; };   // hits of one ray in one chunk, closest (t, face)
-
-static __device__ __forceinline__ int ray_xcd_work_index(int b, int n)   // see xcd_work_index in mm_kernels.hip
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
 
 // ray: 6 planes of n_rays doubles (origin xyz, direction xyz); tri: 9 planes of n_faces doubles (v0 xyz, e1 xyz, e2 xyz)
 __global__ void __launch_bounds__(256)
@@ -42,7 +37,7 @@ k_ray_tri(const double* __restrict__ ray, int n_rays, const double* __restrict__
     __shared__ double s_f[9][kRayChunk];
     const int tid = threadIdx.x;
     const size_t nr = (size_t)n_rays, nf = (size_t)n_faces;
-    for (int wi = (int)gridDim.x == n_work ? ray_xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
         const int chunk = wi / n_rblk, rb = wi - chunk * n_rblk;
         const int f0 = chunk * kRayChunk;

@@ -12,20 +12,11 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
 
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
 constexpr int64_t kMaxRing = 1 << 20;      // ring points of one call
 
 bool all_finite(const double* p, int64_t count)
@@ -372,15 +363,6 @@ struct Rim {
     int64_t need_v = 0, need_f = 0;                                    // set where a stage passes v_cap / f_cap
 };
 
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
-
 int h2d(Rim& R, void* dst, const void* src, size_t bytes)
 {
     if (bytes == 0) return MM_OK;
@@ -407,19 +389,19 @@ int rim_open(Rim& R, Engine* e, const double* v, int64_t nv, const int64_t* face
     if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || v_cap > kMaxIndex || f_cap > kMaxIndex || r_cap > kMaxRing ||
         (nv > 0 && !v) || (nf > 0 && !faces))
         return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, std::string(who) + ": face index out of range");
+    if (const int bad = faces_in_range(faces, nf, nv, who)) return bad;
     R.e = e;
     R.nv = nv; R.nf = nf;
     R.v_cap = std::max(v_cap, nv); R.f_cap = std::max(f_cap, nf); R.r_cap = std::max<int64_t>(r_cap, 1);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
+    Carve lay;
     const size_t vc = (size_t)R.v_cap, fc = (size_t)R.f_cap, rc = (size_t)R.r_cap;
-    const size_t o_v = take(vc * 24), o_f = take(fc * 12), o_f2 = take(fc * 12), o_layer = take(vc * 4), o_fidx = take(fc * 4);
-    const size_t o_list = take(fc * 16), o_keep = take(fc), o_tile = take((trim_scan_tiles((long long)fc) + 1) * 8);
-    const size_t o_q = take(rc * 24), o_index = take(rc * 4), o_counts = take(rc * 4), o_pts = take(rc * 24), o_counter = take(8);
+    const size_t o_v = lay.take(vc * 24), o_f = lay.take(fc * 12), o_f2 = lay.take(fc * 12), o_layer = lay.take(vc * 4);
+    const size_t o_fidx = lay.take(fc * 4), o_list = lay.take(fc * 16), o_keep = lay.take(fc);
+    const size_t o_tile = lay.take((trim_scan_tiles((long long)fc) + 1) * 8);
+    const size_t o_q = lay.take(rc * 24), o_index = lay.take(rc * 4), o_counts = lay.take(rc * 4), o_pts = lay.take(rc * 24);
+    const size_t o_counter = lay.take(8);
     int rc_;
-    if ((rc_ = e->ensure(e->dev_pts, o, false))) return rc_;
+    if ((rc_ = e->ensure(e->dev_pts, lay.size(), false))) return rc_;
     if ((rc_ = e->ensure(e->host_pts, std::max((size_t)R.v_cap * 24, (size_t)R.f_cap * 12) + 256, true))) return rc_;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     R.v = (double*)(b + o_v);
@@ -435,7 +417,7 @@ int rim_open(Rim& R, Engine* e, const double* v, int64_t nv, const int64_t* face
     }
     if (nf > 0) {
         int32_t* hf = (int32_t*)hb;
-        for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+        narrow_faces(hf, faces, 3 * nf);
         if ((rc_ = h2d(R, R.face, hb, (size_t)nf * 12))) return rc_;
     }
     return MM_OK;
@@ -453,7 +435,7 @@ int rim_close(Rim& R, double* out_v, int64_t* out_f)
     if (R.nf > 0 && out_f) {
         if ((rc = d2h(R, hb, R.face, (size_t)R.nf * 12))) return rc;
         const int32_t* hf = (const int32_t*)hb;
-        for (int64_t k = 0; k < 3 * R.nf; ++k) out_f[k] = hf[k];
+        widen_faces(out_f, hf, 3 * R.nf);
     }
     return MM_OK;
 }

@@ -11,30 +11,13 @@
 #include <vector>
 
 #include "../../include/mm_build.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 #include "mm_pool.h"
 
 namespace mm {
 namespace {
 
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct ShapeJobH { int64_t off; int32_t n; int32_t pad; };
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
 
 // find_closest_opposite (contour.rs:247-273): the centre is the stored centroid, else the sequential mean of the
 // points; theta = atan2(y - cy, x - cx), + 2 pi below 0

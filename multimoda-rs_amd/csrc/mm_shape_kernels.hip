@@ -33,6 +33,7 @@
 #include <climits>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 
 namespace mm {
 
@@ -41,12 +42,6 @@ static constexpr int kShapeLds = 1024;   // points staged in LDS: 4 arrays x 102
 static constexpr double kPi = 3.14159265358979323846;
 
 struct ShapeJob { int64_t off; int32_t n; int32_t pad; };   // points [off, off + n)
-
-static __device__ __forceinline__ int shape_xcd_work_index(int b, int n)   // see xcd_work_index in mm_kernels.hip
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
 
 struct LdsPts {
     const double *x, *y, *z, *t;
@@ -212,7 +207,7 @@ k_contour_measures(const ShapeJob* __restrict__ jobs, int n_jobs, const double* 
     __shared__ double s_x[kShapeLds], s_y[kShapeLds], s_z[kShapeLds], s_t[kShapeLds];
     __shared__ ShapeRed s_red;
     const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_jobs ? shape_xcd_work_index(blockIdx.x, n_jobs) : (int)blockIdx.x; wi < n_jobs;
+    for (int wi = (int)gridDim.x == n_jobs ? xcd_work_index(blockIdx.x, n_jobs) : (int)blockIdx.x; wi < n_jobs;
          wi += gridDim.x) {
         const ShapeJob jb = jobs[wi];
         const double* p = xyz + 3 * (size_t)jb.off;

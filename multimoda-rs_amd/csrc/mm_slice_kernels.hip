@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_xcd.h"
 
 namespace mm {
 
@@ -26,12 +27,6 @@ static constexpr int kSliceLanes = 256;   // points per work item
 struct SliceJob { int32_t p_off, np, a_off, na; };   // points [p_off, p_off + np), anchors [a_off, a_off + na)
 struct SliceWork { int32_t job, p0; };
 
-static __device__ __forceinline__ int slice_xcd_work_index(int b, int n)   // see xcd_work_index in mm_kernels.hip
-{
-    const int q = n >> 3, r = n & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
-
 // pts: xyz triples; anc: 6 doubles per anchor (x, y, z, nx, ny, nz); idx / proj: per point, at the point's position
 __global__ void __launch_bounds__(256)
 k_slice_nearest(const SliceJob* __restrict__ jobs, const SliceWork* __restrict__ work, int n_work,
@@ -40,7 +35,7 @@ k_slice_nearest(const SliceJob* __restrict__ jobs, const SliceWork* __restrict__
 {
     __shared__ double4 s_a[kSliceTile];
     const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_work ? slice_xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
+    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
         const SliceWork w = work[wi];
         const SliceJob jb = jobs[w.job];

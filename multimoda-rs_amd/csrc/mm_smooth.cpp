@@ -12,44 +12,17 @@
 #include <cstring>
 
 #include "../../include/mm_ccta.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
-
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
-
-int log2_at_least(unsigned long long n)
-{
-    int l = 8;
-    while ((1ull << l) < n) ++l;
-    return l;
-}
 
 // the checks every entry point shares; the faces are read once here
 int mesh_args(const int64_t* faces, int64_t nf, int64_t nv, const char* who)
 {
     if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (nf > 0 && !faces))
         return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return set_error(MM_ERR_INVALID, std::string(who) + ": face index out of range");
+    if (const int rc = faces_in_range(faces, nf, nv, who)) return rc;
     if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
     return MM_OK;
 }
@@ -57,25 +30,22 @@ int mesh_args(const int64_t* faces, int64_t nf, int64_t nv, const char* who)
 // The adjacency's device buffers, laid out behind whatever the caller placed first.  nb takes the place of the edge
 // table's owner words (8 bytes a slot, at least 6 nf slots): the fill runs behind the insertion, which alone writes them.
 struct CsrDev {
-    size_t o_keys, o_cnt, o_own, o_deg, o_off, o_tile, o_counts;
-    int log2_e;
-    unsigned long long* keys; unsigned int *cnt, *own;
+    EdgeTable edges;
+    size_t o_deg, o_off, o_tile;
     int32_t *deg, *off, *nb;
     long long* tile;
     unsigned long long* counts;           // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
 
-    template <class Take> void plan(Take&& take, int64_t nf, int64_t nv)
+    void plan(Carve& lay, int64_t nf, int64_t nv)
     {
-        log2_e = log2_at_least(6ull * (unsigned long long)nf);
-        const size_t cap = (size_t)1 << log2_e;
-        o_keys = take(cap * 8); o_cnt = take(cap * 4); o_own = take(cap * 8);
-        o_deg = take((size_t)nv * 4); o_off = take(((size_t)nv + 1) * 4);
-        o_tile = take((mesh_csr_tiles(nv) + 1) * 8);
+        edges.plan(lay, nf);
+        o_deg = lay.take((size_t)nv * 4); o_off = lay.take(((size_t)nv + 1) * 4);
+        o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8);
     }
     void bind(unsigned char* b, unsigned long long* counts_at)
     {
-        keys = (unsigned long long*)(b + o_keys); cnt = (unsigned int*)(b + o_cnt); own = (unsigned int*)(b + o_own);
-        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)own;
+        edges.bind(b);
+        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)edges.own;
         tile = (long long*)(b + o_tile);
         counts = counts_at;
     }
@@ -83,18 +53,11 @@ struct CsrDev {
 
 int csr_build(Engine* e, const CsrDev& d, const int32_t* face, int64_t nf, int64_t nv, int* launches)
 {
-    MM_TRY_HIP(launch_weld_edges(face, nf, d.keys, d.cnt, d.own, d.log2_e, e->stream));
+    const EdgeTable& t = d.edges;
+    MM_TRY_HIP(launch_weld_edges(face, nf, t.keys, t.cnt, t.own, t.log2_e, e->stream));
     ++*launches;                                                       // nf > 0: the insertion ran
-    MM_TRY_HIP(launch_mesh_csr(d.keys, d.log2_e, nv, d.deg, d.off, d.tile, d.nb, d.counts, launches, e->stream));
+    MM_TRY_HIP(launch_mesh_csr(t.keys, t.log2_e, nv, d.deg, d.off, d.tile, d.nb, d.counts, launches, e->stream));
     return MM_OK;
-}
-
-// the kernels of launch_weld_volume: the terms, then the pair tree 8 levels a launch
-int volume_launches(int64_t nf)
-{
-    int levels = 0;
-    while ((1ll << levels) < nf) ++levels;
-    return 1 + std::max(1, (levels + 7) / 8);
 }
 
 }  // namespace
@@ -118,19 +81,18 @@ int mm_mesh_adjacency_csr(mm_engine* h, const int64_t* faces, int64_t nf, int64_
         info[2] = nv;
         return MM_OK;
     }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12);
     CsrDev d;
-    d.plan(take, nf, nv);
-    const size_t o_counts = take(4 * 8);
+    d.plan(lay, nf, nv);
+    const size_t o_counts = lay.take(4 * 8);
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 12 + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     d.bind(b, (unsigned long long*)(b + o_counts));
     int32_t* hf = (int32_t*)hb;
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     const int32_t* d_face = (const int32_t*)(b + o_face);
     int launches = 0;
     MM_TRY_HIP(hipMemcpyAsync(b + o_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
@@ -180,24 +142,23 @@ int mm_mesh_smooth(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
 
     // device: [faces | mask | v0] (the upload), vA, the report's numbers, vB, the adjacency, the volume's scratch
     const size_t vbytes = (size_t)nv * 24;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_mask = take(pinned ? (size_t)nv : 0), o_v0 = take(vbytes);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12), o_mask = lay.take(pinned ? (size_t)nv : 0), o_v0 = lay.take(vbytes);
     const size_t up_bytes = o_v0 + vbytes;
-    const size_t o_va = take(vbytes), o_num = take(256), o_vb = take(vbytes);
+    const size_t o_va = lay.take(vbytes), o_num = lay.take(256), o_vb = lay.take(vbytes);
     CsrDev d;
-    d.plan(take, nf, nv);
-    const size_t o_sa = take((size_t)nf * 8), o_sb = take(weld_sum_scratch(nf) * 8);
+    d.plan(lay, nf, nv);
+    const size_t o_sa = lay.take((size_t)nf * 8), o_sb = lay.take(weld_sum_scratch(nf) * 8);
     const size_t down_bytes = o_vb + vbytes - o_va;
     if ((rc = e->ensure(e->host_pts, std::max(up_bytes, down_bytes) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     enum { kVolBefore = 0, kVolAfter = 1, kDisp = 2, kCounts = 3 };    // 8-byte words of the numbers block
     double* d_num = (double*)(b + o_num);
     d.bind(b, (unsigned long long*)(d_num + kCounts));
     int32_t* hf = (int32_t*)(hb + o_face);
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     if (pinned) std::memcpy(hb + o_mask, pinned, (size_t)nv);
     std::memcpy(hb + o_v0, vertices_xyz, vbytes);
     const int32_t* d_face = (const int32_t*)(b + o_face);
@@ -216,7 +177,7 @@ int mm_mesh_smooth(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
         cur = next;
     }
     MM_TRY_HIP(launch_weld_volume(cur, d_face, nf, sa, sb, d_num + kVolAfter, e->stream));
-    launches += 2 * volume_launches(nf);
+    launches += 2 * weld_volume_launches(nf);
     MM_TRY_HIP(launch_mesh_disp(v0, cur, nv, (unsigned long long*)(d_num + kDisp), &launches, e->stream));
     // one copy down: [vA | numbers] or [numbers | vB], whichever holds the result; the numbers alone without a step
     const size_t from = cur == va ? o_va : o_num;
@@ -259,21 +220,20 @@ int mm_mesh_vertex_rings(mm_engine* h, const int64_t* faces, int64_t nf, int64_t
         }
         return MM_OK;
     }
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_seed = take((size_t)n_seeds * 4);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12), o_seed = lay.take((size_t)n_seeds * 4);
     const size_t up_bytes = o_seed + (size_t)n_seeds * 4;
     CsrDev d;
-    d.plan(take, nf, nv);
-    const size_t o_ring = take((size_t)nv * 4), o_counts = take(4 * 8), o_reached = take(8);
+    d.plan(lay, nf, nv);
+    const size_t o_ring = lay.take((size_t)nv * 4), o_counts = lay.take(4 * 8), o_reached = lay.take(8);
     const size_t h_flag = up256(std::max(up_bytes, (size_t)nv * 4));   // the round's count, behind upload and download
     if ((rc = e->ensure(e->host_pts, h_flag + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     d.bind(b, (unsigned long long*)(b + o_counts));
     int32_t* hf = (int32_t*)(hb + o_face);
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     int32_t* hs = (int32_t*)(hb + o_seed);
     for (int64_t k = 0; k < n_seeds; ++k) hs[k] = (int32_t)seeds[k];
     const int32_t* d_face = (const int32_t*)(b + o_face);

@@ -15,36 +15,10 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
-
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
-
-int log2_at_least(unsigned long long n)
-{
-    int l = 8;
-    while ((1ull << l) < n) ++l;
-    return l;
-}
 
 // ---- the seam (host) ------------------------------------------------------------------------------------------------
 
@@ -120,9 +94,10 @@ struct WeldDev {
     double *vert = nullptr, *out_v = nullptr, *sum_a = nullptr, *sum_b = nullptr, *volume = nullptr;
     uint8_t *ref = nullptr, *keep = nullptr, *fkeep = nullptr;
     long long *vtile = nullptr, *ftile = nullptr;
-    unsigned long long *keys = nullptr, *counts = nullptr;   // counts: unreferenced, degenerate, repeated, flipped,
-    unsigned int *cnt = nullptr, *own = nullptr, *link = nullptr, *changed = nullptr;   // open, non-manifold, conflicts
-    int log2_v = 8, log2_f = 8, log2_e = 8;
+    EdgeTable edges;
+    unsigned long long* counts = nullptr;    // unreferenced, degenerate, repeated, flipped, open, non-manifold, conflicts
+    unsigned int *link = nullptr, *changed = nullptr;
+    int log2_v = 8, log2_f = 8;
 };
 
 enum { kUnref = 0, kDegenerate = 1, kRepeated = 2, kFlipped = 3, kOpen = 4, kNonManifold = 5, kConflict = 6, kCounts = 8 };
@@ -130,7 +105,8 @@ enum { kUnref = 0, kDegenerate = 1, kRepeated = 2, kFlipped = 3, kOpen = 4, kNon
 // winding of the nf faces at `face` (device, in place): the edge table, the union-find, the flips and the edge report
 int wind(Engine* e, WeldDev& d, int32_t* face, int64_t nf, bool fix, int64_t* rounds)
 {
-    const WindDev w{d.keys, d.cnt, d.own, d.link, d.changed, d.counts + kFlipped, d.counts + kOpen, d.log2_e};
+    const EdgeTable& t = d.edges;
+    const WindDev w{t.keys, t.cnt, t.own, d.link, d.changed, d.counts + kFlipped, d.counts + kOpen, t.log2_e};
     return weld_wind(e, w, face, nf, fix, rounds);
 }
 
@@ -173,24 +149,21 @@ int mm_fix_winding(mm_engine* h, const int64_t* faces, int64_t nf, int64_t* out_
     if (rc) return rc;
     if (nf < 0 || nf > kMaxIndex || !info || (nf > 0 && (!faces || !out_faces)))
         return set_error(MM_ERR_INVALID, "mm_fix_winding: bad arguments");
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] > kMaxIndex) return set_error(MM_ERR_INVALID, "mm_fix_winding: face index out of range");
+    if ((rc = faces_in_range(faces, nf, kMaxIndex + 1, "mm_fix_winding"))) return rc;   // no nv: what an int32 holds
     std::memset(info, 0, 3 * sizeof(int64_t));
     if (nf == 0) return MM_OK;
     WeldDev d;
-    d.log2_e = log2_at_least(6ull * (unsigned long long)nf);
-    const size_t cap = (size_t)1 << d.log2_e;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_keys = take(cap * 8), o_cnt = take(cap * 4), o_own = take(cap * 8);
-    const size_t o_link = take((size_t)nf * 4), o_counts = take(kCounts * 8), o_changed = take(4);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12);
+    d.edges.plan(lay, nf);
+    const size_t o_link = lay.take((size_t)nf * 4), o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 12 + 256, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)e->host_pts.p;
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     d.face = (int32_t*)(b + o_face);
-    d.keys = (unsigned long long*)(b + o_keys); d.cnt = (unsigned int*)(b + o_cnt); d.own = (unsigned int*)(b + o_own);
+    d.edges.bind(b);
     d.link = (unsigned int*)(b + o_link); d.counts = (unsigned long long*)(b + o_counts);
     d.changed = (unsigned int*)(b + o_changed);
     MM_TRY_HIP(hipMemcpyAsync(d.face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
@@ -202,7 +175,7 @@ int mm_fix_winding(mm_engine* h, const int64_t* faces, int64_t nf, int64_t* out_
     MM_TRY_HIP(hipMemcpyAsync(hf, d.face, (size_t)nf * 12, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(hcnt, d.counts, kCounts * 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    for (int64_t k = 0; k < 3 * nf; ++k) out_faces[k] = hf[k];
+    widen_faces(out_faces, hf, 3 * nf);
     info[0] = (int64_t)hcnt[kFlipped];
     info[1] = (int64_t)hcnt[kConflict];
     info[2] = rounds;
@@ -229,11 +202,10 @@ int mm_mesh_assemble(mm_engine* h, int n_parts, const double* vertices_xyz, cons
     const int64_t nv = vert_off[n_parts], nf = face_off[n_parts];
     if ((nv > 0 && (!vertices_xyz || !out_vertices)) || (nf > 0 && (!faces || !out_faces)))
         return set_error(MM_ERR_INVALID, "mm_mesh_assemble: bad arguments");
-    for (int p = 0; p < n_parts; ++p) {
-        const int64_t n = vert_off[p + 1] - vert_off[p];
-        for (int64_t k = 3 * face_off[p]; k < 3 * face_off[p + 1]; ++k)
-            if (faces[k] < 0 || faces[k] >= n) return set_error(MM_ERR_INVALID, "mm_mesh_assemble: face index out of range");
-    }
+    for (int p = 0; p < n_parts; ++p)
+        if ((rc = faces_in_range(faces + 3 * face_off[p], face_off[p + 1] - face_off[p], vert_off[p + 1] - vert_off[p],
+                                 "mm_mesh_assemble")))
+            return rc;
     if (nf == 0) { report->n_unreferenced_vertices = nv; return MM_OK; }   // no face names a vertex
 
     double scale = 1.0;
@@ -242,35 +214,34 @@ int mm_mesh_assemble(mm_engine* h, int n_parts, const double* vertices_xyz, cons
     WeldDev d;
     d.log2_v = log2_at_least(2ull * (unsigned long long)nv);
     d.log2_f = log2_at_least(2ull * (unsigned long long)nf);
-    d.log2_e = log2_at_least(6ull * (unsigned long long)nf);
-    const size_t cap_t = (size_t)1 << std::max(d.log2_v, d.log2_f), cap_e = (size_t)1 << d.log2_e;
+    const size_t cap_t = (size_t)1 << std::max(d.log2_v, d.log2_f);
     const size_t nvt = trim_scan_tiles(nv) + 1, nft = trim_scan_tiles(nf) + 1;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_vert = take((size_t)nv * 24);
-    const size_t in_bytes = o;
-    const size_t o_ref = take((size_t)nv), o_keep = take((size_t)nv), o_rep = take((size_t)nv * 4);
-    const size_t o_vidx = take((size_t)nv * 4), o_vmap = take((size_t)nv * 4), o_vt = take(nvt * 8);
-    const size_t o_table = take(cap_t * 4), o_frep = take((size_t)nf * 4), o_fkeep = take((size_t)nf);
-    const size_t o_fidx = take((size_t)nf * 4), o_ft = take(nft * 8);
-    const size_t o_ov = take((size_t)nv * 24), o_of = take((size_t)nf * 12);
-    const size_t o_keys = take(cap_e * 8), o_cnt = take(cap_e * 4), o_own = take(cap_e * 8), o_link = take((size_t)nf * 4);
-    const size_t o_sa = take((size_t)nf * 8), o_sb = take(weld_sum_scratch(nf) * 8), o_vol = take(8);
-    const size_t o_counts = take(kCounts * 8), o_changed = take(4);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12), o_vert = lay.take((size_t)nv * 24);
+    const size_t in_bytes = lay.size();
+    const size_t o_ref = lay.take((size_t)nv), o_keep = lay.take((size_t)nv), o_rep = lay.take((size_t)nv * 4);
+    const size_t o_vidx = lay.take((size_t)nv * 4), o_vmap = lay.take((size_t)nv * 4), o_vt = lay.take(nvt * 8);
+    const size_t o_table = lay.take(cap_t * 4), o_frep = lay.take((size_t)nf * 4), o_fkeep = lay.take((size_t)nf);
+    const size_t o_fidx = lay.take((size_t)nf * 4), o_ft = lay.take(nft * 8);
+    const size_t o_ov = lay.take((size_t)nv * 24), o_of = lay.take((size_t)nf * 12);
+    d.edges.plan(lay, nf);
+    const size_t o_link = lay.take((size_t)nf * 4);
+    const size_t o_sa = lay.take((size_t)nf * 8), o_sb = lay.take(weld_sum_scratch(nf) * 8), o_vol = lay.take(8);
+    const size_t o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
     if ((rc = e->ensure(e->host_pts, std::max(in_bytes, (size_t)nv * 24 + (size_t)nf * 12 + 512), true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)hb;
     for (int p = 0; p < n_parts; ++p)
-        for (int64_t k = 3 * face_off[p]; k < 3 * face_off[p + 1]; ++k) hf[k] = (int32_t)(faces[k] + vert_off[p]);
+        narrow_faces(hf + 3 * face_off[p], faces + 3 * face_off[p], 3 * (face_off[p + 1] - face_off[p]), vert_off[p]);
     if (nv > 0) std::memcpy(hb + o_vert, vertices_xyz, (size_t)nv * 24);
     d.face = (int32_t*)(b + o_face); d.vert = (double*)(b + o_vert);
     d.ref = b + o_ref; d.keep = b + o_keep; d.rep = (int32_t*)(b + o_rep); d.vidx = (int32_t*)(b + o_vidx);
     d.vmap = (int32_t*)(b + o_vmap); d.vtile = (long long*)(b + o_vt); d.table = (int32_t*)(b + o_table);
     d.frep = (int32_t*)(b + o_frep); d.fkeep = b + o_fkeep; d.fidx = (int32_t*)(b + o_fidx);
     d.ftile = (long long*)(b + o_ft); d.out_v = (double*)(b + o_ov); d.out_f = (int32_t*)(b + o_of);
-    d.keys = (unsigned long long*)(b + o_keys); d.cnt = (unsigned int*)(b + o_cnt); d.own = (unsigned int*)(b + o_own);
+    d.edges.bind(b);
     d.link = (unsigned int*)(b + o_link); d.sum_a = (double*)(b + o_sa); d.sum_b = (double*)(b + o_sb);
     d.volume = (double*)(b + o_vol); d.counts = (unsigned long long*)(b + o_counts);
     d.changed = (unsigned int*)(b + o_changed);
@@ -286,12 +257,8 @@ int mm_mesh_assemble(mm_engine* h, int n_parts, const double* vertices_xyz, cons
     MM_TRY_HIP(launch_trim_scan(d.fkeep, nf, d.ftile, d.fidx, e->stream));
     MM_TRY_HIP(launch_trim_compact(d.vert, nv, d.vidx, d.face, 0, d.fidx, d.out_v, d.out_f, e->stream));   // vertices
     MM_TRY_HIP(launch_trim_compact(d.vert, 0, d.vmap, d.face, nf, d.fidx, d.out_v, d.out_f, e->stream));    // faces
-    long long* ht = (long long*)hb;
-    MM_TRY_HIP(hipMemcpyAsync(ht, d.vtile + trim_scan_tiles(nv), 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(ht + 1, d.ftile + trim_scan_tiles(nf), 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    const long long kv = ht[0], kf = ht[1];
-    if (kv < 0 || kv > nv || kf < 0 || kf > nf) return set_error(MM_ERR_HIP, "mm_mesh_assemble: compaction count out of range");
+    long long kv, kf;
+    if ((rc = scan_totals(e, d.vtile, nv, d.ftile, nf, &kv, &kf, "mm_mesh_assemble"))) return rc;
 
     int64_t rounds = 0;
     if ((rc = wind(e, d, d.out_f, kf, fix_winding != 0, &rounds))) return rc;
@@ -315,7 +282,7 @@ int mm_mesh_assemble(mm_engine* h, int n_parts, const double* vertices_xyz, cons
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     std::memcpy(out_vertices, hb, (size_t)kv * 24);
     const int32_t* f32 = (const int32_t*)(hb + h_faces);
-    for (long long k = 0; k < 3 * kf; ++k) out_faces[k] = f32[k];
+    widen_faces(out_faces, f32, 3 * kf);
     const unsigned long long* c = (const unsigned long long*)(hb + h_counts);
     report->n_vertices = kv;
     report->n_faces = kf;

@@ -18,29 +18,10 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_adjacency.h"
-#include "mm_engine.h"
+#include "mm_mesh_stage.h"
 
 namespace mm {
 namespace {
-
-#define MM_TRY_HIP(call)                                          \
-    do {                                                          \
-        const hipError_t e__ = (call);                            \
-        if (e__ != hipSuccess) return hip_error(e__, #call);      \
-    } while (0)
-
-inline size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-
-constexpr int64_t kMaxIndex = INT32_MAX;   // device indices are int32: nv and nf stay below 2^31
-
-int engine_of(mm_engine* h, Engine*& e)
-{
-    e = reinterpret_cast<Engine*>(h);
-    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
-    const hipError_t he = hipSetDevice(e->device);
-    if (he != hipSuccess) return hip_error(he, "hipSetDevice");
-    return MM_OK;
-}
 
 // ---- ring logic on the rim (host) -----------------------------------------------------------------------------------
 
@@ -226,8 +207,8 @@ void rim_pass(const int64_t* edges, int64_t ne, const std::vector<int64_t>& seed
 
 // ---- device part -----------------------------------------------------------------------------------------------------
 
-// The device buffers of one trim, carved out of the engine's grow-only device buffer.  The hash table has 2^log2_cap
-// slots, at least twice the 3 nf insertions of a pass (12 bytes a slot).
+// The device buffers of one trim, carved out of the engine's grow-only device buffer.  The hash table has the slots of
+// the edge table (EdgeTable::log2_slots) without the owner plane: 12 bytes a slot.
 struct TrimDev {
     int32_t* face = nullptr;
     double* vert = nullptr;
@@ -240,37 +221,30 @@ struct TrimDev {
     int log2_cap = 8;
 };
 
-int table_log2(int64_t nf)
-{
-    int l = 8;
-    while ((1ull << l) < (unsigned long long)(6 * nf)) ++l;
-    return l;
-}
-
 // Device layout for nv vertices and nf faces (vertices only where with_vertices); the faces, converted to int32, and
 // the vertices (with_vertices) go up in one copy from the pinned buffer, which is left sized for every download.
 int trim_alloc(Engine* e, const double* v, int64_t nv, const int64_t* faces, int64_t nf, bool with_vertices, TrimDev& d)
 {
-    d.log2_cap = table_log2(nf);
+    d.log2_cap = EdgeTable::log2_slots(nf);
     const size_t cap = (size_t)1 << d.log2_cap;
     const size_t nvt = trim_scan_tiles(nv) + 1, nft = trim_scan_tiles(nf) + 1;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; };
-    const size_t o_face = take((size_t)nf * 12), o_vert = take(with_vertices ? (size_t)nv * 24 : 0);
-    const size_t in_bytes = o;
-    const size_t o_in = take((size_t)nv), o_fk = take((size_t)nf), o_mark = take((size_t)nv);
-    const size_t o_keys = take(cap * 8), o_cnt = take(cap * 4), o_open = take((size_t)nf * 24), o_nopen = take(8);
-    const size_t o_vidx = take((size_t)nv * 4), o_fidx = take((size_t)nf * 4), o_drop = take((size_t)nv * 4);
-    const size_t o_vt = take(nvt * 8), o_ft = take(nft * 8);
-    const size_t o_ov = take(with_vertices ? (size_t)nv * 24 : 0), o_of = take((size_t)nf * 12);
+    Carve lay;
+    const size_t o_face = lay.take((size_t)nf * 12), o_vert = lay.take(with_vertices ? (size_t)nv * 24 : 0);
+    const size_t in_bytes = lay.size();
+    const size_t o_in = lay.take((size_t)nv), o_fk = lay.take((size_t)nf), o_mark = lay.take((size_t)nv);
+    const size_t o_keys = lay.take(cap * 8), o_cnt = lay.take(cap * 4);
+    const size_t o_open = lay.take((size_t)nf * 24), o_nopen = lay.take(8);
+    const size_t o_vidx = lay.take((size_t)nv * 4), o_fidx = lay.take((size_t)nf * 4), o_drop = lay.take((size_t)nv * 4);
+    const size_t o_vt = lay.take(nvt * 8), o_ft = lay.take(nft * 8);
+    const size_t o_ov = lay.take(with_vertices ? (size_t)nv * 24 : 0), o_of = lay.take((size_t)nf * 12);
     const size_t host_bytes = std::max({in_bytes, (size_t)nf * 24, (size_t)nv * 24 + (size_t)nf * 12, (size_t)nv + 256});
     int rc = e->ensure(e->host_pts, host_bytes, true);
     if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, o, false))) return rc;
+    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)h;
-    for (int64_t k = 0; k < 3 * nf; ++k) hf[k] = (int32_t)faces[k];
+    narrow_faces(hf, faces, 3 * nf);
     if (with_vertices && nv > 0) std::memcpy(h + o_vert, v, (size_t)nv * 24);
     d.face = (int32_t*)(b + o_face);
     d.vert = (double*)(b + o_vert);
@@ -339,13 +313,6 @@ int clean_loop(Engine* e, TrimDev& d, int64_t nf, const double* v, std::vector<i
     return MM_OK;
 }
 
-bool faces_ok(const int64_t* faces, int64_t nf, int64_t nv)
-{
-    for (int64_t k = 0; k < 3 * nf; ++k)
-        if (faces[k] < 0 || faces[k] >= nv) return false;
-    return true;
-}
-
 int write_rings(const std::vector<Ring>& rings, int64_t* ring_len, int64_t* ring_idx, int64_t* n_rings, int64_t* n_idx)
 {
     int64_t k = 0;
@@ -394,7 +361,7 @@ int mm_build_adjacency(const int64_t* faces, int64_t nf, int64_t nv, int64_t* of
 {
     if (nf < 0 || nv < 0 || (nf > 0 && (!faces || !nb)) || !off)
         return set_error(MM_ERR_INVALID, "mm_build_adjacency: bad arguments");
-    if (!faces_ok(faces, nf, nv)) return set_error(MM_ERR_INVALID, "mm_build_adjacency: face index out of range");
+    if (const int rc = faces_in_range(faces, nf, nv, "mm_build_adjacency")) return rc;
     Adjacency adj;
     build_adjacency(faces, nf, nv, adj);
     std::copy(adj.off.begin(), adj.off.end(), off);
@@ -409,7 +376,7 @@ int64_t mm_open_boundary_edges(mm_engine* h, const int64_t* faces, int64_t nf, i
     if (rc) return rc;
     if (nf < 0 || nv < 0 || nf > kMaxIndex || nv > kMaxIndex || (nf > 0 && (!faces || !edges)))
         return set_error(MM_ERR_INVALID, "mm_open_boundary_edges: bad arguments");
-    if (!faces_ok(faces, nf, nv)) return set_error(MM_ERR_INVALID, "mm_open_boundary_edges: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_open_boundary_edges"))) return rc;
     if (nf == 0) return 0;
     TrimDev d;
     if ((rc = trim_alloc(e, nullptr, nv, faces, nf, false, d))) return rc;
@@ -431,7 +398,7 @@ int mm_clean_open_boundary(mm_engine* h, const int64_t* faces, int64_t nf, const
         (nv > 0 && (!vertices_xyz || !drop || !ring_len || !ring_idx)) || (ns > 0 && !seeds) ||
         (target_n < 1 && target_n != -1))
         return set_error(MM_ERR_INVALID, "mm_clean_open_boundary: bad arguments");
-    if (!faces_ok(faces, nf, nv)) return set_error(MM_ERR_INVALID, "mm_clean_open_boundary: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_clean_open_boundary"))) return rc;
     std::memset(counts, 0, 3 * sizeof(int64_t));
     if (nf == 0) return MM_OK;                         // no open edge: no rim, nothing dropped
     TrimDev d;
@@ -458,7 +425,7 @@ int mm_trim_mesh(mm_engine* h, const double* vertices_xyz, int64_t nv, const int
         (nf > 0 && (!faces || !out_faces)) || (nv > 0 && (!vertices_xyz || !region || !out_vertices)) ||
         (mode != 2 && nv > 0 && (!ring_len || !ring_idx)) || (target_n < 1 && target_n != -1))
         return set_error(MM_ERR_INVALID, "mm_trim_mesh: bad arguments");
-    if (!faces_ok(faces, nf, nv)) return set_error(MM_ERR_INVALID, "mm_trim_mesh: face index out of range");
+    if ((rc = faces_in_range(faces, nf, nv, "mm_trim_mesh"))) return rc;
     std::memset(counts, 0, 4 * sizeof(int64_t));
     if (nv == 0) return MM_OK;
     TrimDev d;
@@ -489,19 +456,15 @@ int mm_trim_mesh(mm_engine* h, const double* vertices_xyz, int64_t nv, const int
     MM_TRY_HIP(launch_trim_scan(vmask, nv, d.vtile, d.vidx, e->stream));
     MM_TRY_HIP(launch_trim_scan(d.fk, nf, d.ftile, d.fidx, e->stream));
     MM_TRY_HIP(launch_trim_compact(d.vert, nv, d.vidx, d.face, nf, d.fidx, d.out_v, d.out_f, e->stream));
-    long long* ht = (long long*)e->host_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(ht, d.vtile + trim_scan_tiles(nv), 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(ht + 1, d.ftile + trim_scan_tiles(nf), 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    const long long kv = ht[0], kf = ht[1];
-    if (kv < 0 || kv > nv || kf < 0 || kf > nf) return set_error(MM_ERR_HIP, "mm_trim_mesh: compaction count out of range");
+    long long kv, kf;
+    if ((rc = scan_totals(e, d.vtile, nv, d.ftile, nf, &kv, &kf, "mm_trim_mesh"))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     if (kv) MM_TRY_HIP(hipMemcpyAsync(hb, d.out_v, (size_t)kv * 24, hipMemcpyDeviceToHost, e->stream));
     if (kf) MM_TRY_HIP(hipMemcpyAsync(hb + (size_t)kv * 24, d.out_f, (size_t)kf * 12, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     std::memcpy(out_vertices, hb, (size_t)kv * 24);
     const int32_t* f32 = (const int32_t*)(hb + (size_t)kv * 24);
-    for (long long k = 0; k < 3 * kf; ++k) out_faces[k] = f32[k];
+    widen_faces(out_faces, f32, 3 * kf);
     counts[0] = kv;
     counts[1] = kf;
     return write_rings(rings, ring_len, ring_idx, counts + 2, counts + 3);

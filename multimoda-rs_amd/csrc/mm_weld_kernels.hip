@@ -449,6 +449,18 @@ hipError_t launch_weld_edge_report(const unsigned long long* keys, const unsigne
 
 size_t weld_sum_scratch(long long nf) { return (size_t)((nf + kWeldThreads - 1) / kWeldThreads) + 1; }
 
+// the pair tree over the nf volume terms: the padded length is 2^levels, and a launch sums 8 levels of it
+static int weld_tree_levels(long long nf)
+{
+    int levels = 0;
+    while ((1ll << levels) < nf) ++levels;
+    return levels;
+}
+static int weld_tree_launches(int levels) { return levels <= 8 ? 1 : (levels + 7) / 8; }
+
+// the kernels launch_weld_volume launches: the terms, then the tree
+int weld_volume_launches(long long nf) { return nf <= 0 ? 0 : 1 + weld_tree_launches(weld_tree_levels(nf)); }
+
 // *out = the adjacent-pair tree of the nf volume terms (padded with +0.0 to a power of two); a and b are scratch of nf
 // and weld_sum_scratch(nf) doubles
 hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf, double* a, double* b, double* out,
@@ -456,23 +468,23 @@ hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf
 {
     if (nf <= 0) return hipMemsetAsync(out, 0, 8, s);
     WELD_LAUNCH(k_weld_terms, nf, v, face, nf, a);
-    int levels = 0;                                                    // the padded length is 2^levels
-    while ((1ll << levels) < nf) ++levels;
+    int levels = weld_tree_levels(nf);
+    const int launches = weld_tree_launches(levels);
     long long n = nf;
     double* in = a;
     double* to = b;
-    for (;;) {
+    for (int k = 1; k <= launches; ++k) {
         const int now = levels >= 8 ? 8 : levels;
         const long long blocks = (n + kWeldThreads - 1) / kWeldThreads;
-        const bool last = levels <= 8;
-        hipLaunchKernelGGL(k_weld_pair_sum, dim3((unsigned)blocks), dim3(kWeldThreads), 0, s, in, n, now, last ? out : to);
+        hipLaunchKernelGGL(k_weld_pair_sum, dim3((unsigned)blocks), dim3(kWeldThreads), 0, s, in, n, now,
+                           k == launches ? out : to);
         const hipError_t he = hipGetLastError();
         if (he != hipSuccess) return he;
-        if (last) return hipSuccess;
         levels -= 8;
         n = blocks;
         double* t = in; in = to; to = t;
     }
+    return hipSuccess;
 }
 
 hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s)
