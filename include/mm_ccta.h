@@ -614,6 +614,39 @@ int     mm_label_branches(mm_engine* e, const mm_clpoint* cl, int64_t ncl, const
                           int64_t* main_idx, int64_t* side_idx, int64_t* side_k_off, int64_t* side_k_idx, int64_t side_k_cap,
                           int64_t* counts);
 
+/* ---- B-spline contours (multimodars/ccta/discretization_map.py:16-101) --------------------------------------------- */
+
+/* Most points one contour of mm_bspline_fit_closed_batch may have.  The fit keeps a contour's whole problem in one
+ * block's LDS: 39 (m + 10) + 11 m doubles at degree 5, about 102 KB at m = 256, inside the 160 KB a gfx950 block may
+ * take. */
+#define MM_BSPLINE_MAX_POINTS 256
+
+/* out_status of mm_bspline_fit_closed_batch */
+enum mm_bspline_status {
+    MM_BSPLINE_FITTED               = 0,  /* |fp - s| <= 1e-3 s (FITPACK ier 0)                                  */
+    MM_BSPLINE_INTERPOLATED         = 1,  /* s = 0, or the knots grew to the interpolation set (ier -1)          */
+    MM_BSPLINE_COLLAPSED            = 2,  /* the best constant already has fp0 - s < 1e-3 s: one point (ier -2)  */
+    MM_BSPLINE_UNCHANGED_SHORT      = 3,  /* fewer than degree + 1 points: returned as it is                     */
+    MM_BSPLINE_UNCHANGED_ZERO_CHORD = 4,  /* two consecutive points coincide (ier 10): returned as it is         */
+    MM_BSPLINE_UNCHANGED_NONFINITE  = 5,  /* a non-finite coordinate, or a singular system: returned as it is    */
+    MM_BSPLINE_ITERATION_LIMIT      = 6   /* the search for p stopped early (ier 1, 2, 3): the result is used    */
+};
+
+/* Replace each of n_contours contours (CSR: contour j = points offsets[j] .. offsets[j + 1] of xyz) by m points on its
+ * closed smoothing B-spline of the given degree (1..5) and smoothing s >= 0: scipy's splprep(s, k, per=True) followed by
+ * splev at u = i / m, restated.  The last point of a contour is replaced by its first before the fit, as
+ * splprep does.  out_xyz: as many points as xyz; out_centroid: 3 per contour, np.mean of each output coordinate in
+ * numpy's pairwise order; out_status: one mm_bspline_status; out_fp: the residual sum of squares; out_nknots: the knot
+ * count (0 for an unchanged contour).  Every contour is fitted in one launch (mm_bspline_kernels.hip), bit for bit the
+ * arithmetic of tests/mm_checkers/bspline.py.  A degree outside 1..5, a negative or non-finite smoothing, or a contour of
+ * more than MM_BSPLINE_MAX_POINTS points is MM_ERR_INVALID for the whole call, and no output is written; so is
+ * MM_ERR_TOO_LARGE on a device whose LDS per block cannot hold the longest contour's system. */
+int     mm_bspline_fit_closed_batch(mm_engine* e, int64_t n_contours, const double* xyz, const int64_t* offsets,
+                                    double smoothing, int degree, double* out_xyz, double* out_centroid,
+                                    int32_t* out_status, double* out_fp, int32_t* out_nknots);
+/* MM_BSPLINE_MAX_POINTS */
+int     mm_bspline_max_points(void);
+
 #ifdef __cplusplus
 }
 #endif

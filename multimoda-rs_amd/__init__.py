@@ -25,6 +25,8 @@ from . import centerline
 from . import ccta
 from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_simple, clean_outlier_points,
                    discretize_vessel, discretize_vessel_tree, final_reclassification,
+                   BSplineReport, discretize_vessel_tree_bspline, fit_bspline_contour, fit_bspline_contours,
+                   replace_contours_with_bsplines,
                    find_aorta_scaling, find_aortic_points, find_aortic_scaling, find_aortic_wall_scaling,
                    find_centerline_bounded_points_simple, find_distal_and_proximal_scaling, find_faces_near_points,
                    find_points_by_cl_region, find_proximal_distal_scaling, keep_largest_connected_component,
@@ -63,6 +65,8 @@ __all__ = [
     "find_centerline_bounded_points_simple", "find_faces_near_points", "remove_occluded_points_ray_triangle",
     "find_aortic_points", "final_reclassification", "label_geometry",
     "discretize_vessel", "discretize_vessel_tree", "DiscretizedVesselTree",
+    "BSplineReport", "discretize_vessel_tree_bspline", "fit_bspline_contour", "fit_bspline_contours",
+    "replace_contours_with_bsplines",
     "keep_largest_connected_component", "label_anomalous_region", "scale_region_centerline_morphing",
     "sync_results_to_mesh", "scale", "open_boundary_edges", "order_boundary_rings", "clean_open_boundary",
     "remove_labeled_points_from_mesh", "keep_labeled_points_from_mesh", "extract_region_with_border_faces",

@@ -117,6 +117,7 @@ EXPORTS_CCTA = [
     "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
+    "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
 
@@ -598,6 +599,10 @@ def lib():
     L.mm_condition_rims.restype = I
     L.mm_condition_rims.argtypes = [P, P, I64, P, I64, P, I64, P, I64, P, I64, P, P, P, I64, C.POINTER(MMRimParams), P, P,
                                     P, P, C.POINTER(MMRimReport)]
+    L.mm_bspline_fit_closed_batch.restype = I
+    L.mm_bspline_fit_closed_batch.argtypes = [P, I64, P, P, D, I, P, P, P, P, P]
+    L.mm_bspline_max_points.restype = I
+    L.mm_bspline_max_points.argtypes = []
     _lib = L
     return L
 

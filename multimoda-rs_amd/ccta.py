@@ -749,15 +749,124 @@ def discretize_vessel_tree(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Center
                            control_plot: bool = False, engine: Optional[N.Engine] = None) -> DiscretizedVesselTree:
     """multimodars/ccta/discretization_map.py:117-205: discretise the aorta (``aorta_points`` + ``rca_removed_points``),
     the main vessels (``rca_points_main`` / ``lca_points_main``) and the side branches (``rca_points_side_1``, ...) of
-    a labelled results dict, with reference points.  B-spline contours are not implemented (``b_spline=True`` raises
-    NotImplementedError); ``control_plot`` is accepted and ignored."""
+    a labelled results dict, with reference points.  ``b_spline=True`` raises NotImplementedError here: the B-spline
+    path is ``discretize_vessel_tree_bspline``; ``control_plot`` is accepted and ignored."""
     if b_spline:
-        raise NotImplementedError("discretize_vessel_tree: b_spline contours are not implemented")
+        raise NotImplementedError("discretize_vessel_tree: b_spline contours are not implemented on this entry point; "
+                                  "call discretize_vessel_tree_bspline")
     points_ao = np.concatenate([_p3(results_dict["aorta_points"]), _p3(results_dict["rca_removed_points"])])
     return discretize_vessel_tree_raw(ao_cl, rca_cl, lca_cl, points_ao, results_dict["rca_points_main"],
                                       results_dict["lca_points_main"], _extract_side_branches(results_dict, "rca_points"),
                                       _extract_side_branches(results_dict, "lca_points"), branch_id_rca, branch_id_lca,
                                       step_size, n_points, calculate_ref_pts=True, engine=engine)
+
+
+# ---- closed B-spline contours (multimodars/ccta/discretization_map.py:16-101) ----------------------------------------
+BSPLINE_STATUS = ("fitted", "interpolated", "collapsed", "unchanged_short", "unchanged_zero_chord",
+                  "unchanged_nonfinite", "iteration_limit")
+
+
+@dataclass
+class BSplineReport:
+    """What mm_bspline_fit_closed_batch says about one contour: ``status`` (a name of BSPLINE_STATUS; ``code`` its
+    number), the residual sum of squares ``fp`` and the knot count (0 for an unchanged contour)."""
+    status: str
+    code: int
+    fp: float
+    n_knots: int
+
+
+def bspline_max_points() -> int:
+    """MM_BSPLINE_MAX_POINTS: the most points one contour of fit_bspline_contours may have."""
+    return int(N.lib().mm_bspline_max_points())
+
+
+def _bspline_batch(arrays, smoothing: float, degree: int, engine: Optional[N.Engine]):
+    """(n, 3) arrays -> (new arrays, centroids (n, 3), reports) from one call of mm_bspline_fit_closed_batch"""
+    nc = len(arrays)
+    off = np.zeros(nc + 1, dtype=np.int64)
+    if nc:
+        off[1:] = np.cumsum([a.shape[0] for a in arrays])
+    xyz = np.ascontiguousarray(np.concatenate(arrays)) if nc and off[-1] else np.zeros((0, 3))
+    out = np.zeros_like(xyz)
+    cen = np.zeros((nc, 3))
+    status = np.zeros(nc, dtype=np.int32)
+    fp = np.zeros(nc)
+    nk = np.zeros(nc, dtype=np.int32)
+    N.check(N.lib().mm_bspline_fit_closed_batch(_engine(engine).handle, nc, N._ptr(xyz), N._ptr(off), float(smoothing),
+                                                int(degree), N._ptr(out), N._ptr(cen), N._ptr(status), N._ptr(fp),
+                                                N._ptr(nk)), "fit_bspline_contours")
+    new = [out[int(off[j]):int(off[j + 1])].copy() for j in range(nc)]
+    reports = [BSplineReport(BSPLINE_STATUS[int(status[j])], int(status[j]), float(fp[j]), int(nk[j])) for j in range(nc)]
+    return new, cen, reports
+
+
+def fit_bspline_contours(contours, smoothing: float = 0.0, degree: int = 3, engine: Optional[N.Engine] = None):
+    """_fit_bspline_contour (discretization_map.py:16-83) for a list of contours in one device pass
+    (csrc/mm_bspline_kernels.hip): each contour is replaced by as many points on its closed smoothing B-spline --
+    scipy's ``splprep(s=smoothing, k=degree, per=True)`` and ``splev`` at ``linspace(0, 1, n, endpoint=False)``,
+    restated in exact f64.  ``contours``: ``(n, 3)`` arrays or ``frames.Contour`` objects.  Returns ``(new, reports)``:
+    arrays for arrays; for Contour objects new Contour objects with the fitted points, the centroid ``np.mean`` of
+    them, and id, original_frame, thicknesses, kind and aortic flags carried over.  ``reports[i]`` is a BSplineReport.
+    A contour of fewer than ``degree + 1`` points, with two coinciding consecutive points or with a non-finite
+    coordinate comes back with its own points and its status says why.  A degree outside 1..5 or more than
+    ``bspline_max_points()`` points raises RuntimeError."""
+    from .frames import Contour
+    contours = list(contours)
+    arrays = [_p3(c.points if isinstance(c, Contour) else c) for c in contours]
+    new, cen, reports = _bspline_batch(arrays, smoothing, degree, engine)
+    out = []
+    for c, a, ce, r in zip(contours, new, cen, reports):
+        if isinstance(c, Contour):
+            if r.status.startswith("unchanged"):
+                out.append(c)                                   # the reference returns the contour itself
+            else:
+                out.append(Contour(c.id, c.original_frame, a, _t3(ce), c.aortic_thickness, c.pulmonary_thickness, c.kind,
+                                   None if c.aortic is None else c.aortic.copy()))
+        else:
+            out.append(a)
+    return out, reports
+
+
+def fit_bspline_contour(contour, smoothing: float = 0.0, degree: int = 3, engine: Optional[N.Engine] = None):
+    """One contour through fit_bspline_contours: ``(new contour, report)``."""
+    new, reports = fit_bspline_contours([contour], smoothing, degree, engine)
+    return new[0], reports[0]
+
+
+def replace_contours_with_bsplines(tree: "DiscretizedVesselTree", smoothing: float = 0.0, degree: int = 3,
+                                   engine: Optional[N.Engine] = None) -> "DiscretizedVesselTree":
+    """_replace_contours_with_bsplines (discretization_map.py:86-101): every contour of the aorta, both main vessels and
+    every side branch replaced by its closed B-spline fit, all of them in ONE device pass.  In place; returns the tree.
+    The reference points are not recomputed (call ``calculate_ref_pts``)."""
+    groups = [tree.discretized_aorta, tree.discretized_rca_main, tree.discretized_lca_main]
+    groups += list(tree.rca_branches) + list(tree.lca_branches)
+    flat = [c for g in groups for c in g]
+    new, _ = fit_bspline_contours(flat, smoothing, degree, engine)
+    it = iter(new)
+    fitted = [[next(it) for _ in g] for g in groups]
+    nr = len(tree.rca_branches)
+    tree.discretized_aorta, tree.discretized_rca_main, tree.discretized_lca_main = fitted[0], fitted[1], fitted[2]
+    tree.rca_branches = fitted[3:3 + nr]
+    tree.lca_branches = fitted[3 + nr:]
+    return tree
+
+
+def discretize_vessel_tree_bspline(ao_cl: Centerline, rca_cl: Centerline, lca_cl: Centerline, results_dict: dict,
+                                   branch_id_rca: int = 0, branch_id_lca: int = 0, step_size: float = 1.0,
+                                   n_points: int = 100, bspline_smoothing: float = 100.0, bspline_degree: int = 3,
+                                   control_plot: bool = False, engine: Optional[N.Engine] = None) -> DiscretizedVesselTree:
+    """The ``b_spline=True`` path of multimodars/ccta/discretization_map.py:117-205: discretise without reference
+    points, replace every contour by its closed B-spline fit, then ``calculate_ref_pts``.  The defaults are the
+    reference's (``bspline_smoothing=100`` collapses a contour whose squared distances to its mean sum to less than
+    100 -- every coronary-sized contour of fewer than about 30 points -- to that mean, as the reference does)."""
+    points_ao = np.concatenate([_p3(results_dict["aorta_points"]), _p3(results_dict["rca_removed_points"])])
+    tree = discretize_vessel_tree_raw(ao_cl, rca_cl, lca_cl, points_ao, results_dict["rca_points_main"],
+                                      results_dict["lca_points_main"], _extract_side_branches(results_dict, "rca_points"),
+                                      _extract_side_branches(results_dict, "lca_points"), branch_id_rca, branch_id_lca,
+                                      step_size, n_points, calculate_ref_pts=False, engine=engine)
+    replace_contours_with_bsplines(tree, bspline_smoothing, bspline_degree, engine)
+    return tree.calculate_ref_pts()
 
 
 # ---- mesh morphing (src/ccta/adjust_mesh/scale_coronary.rs:218-260, multimodars/ccta/{labeling,scaling,__init__}.py) --

@@ -319,4 +319,11 @@ size_t     lds_bytes_f64(int nbp);
 int        max_target_points_f32();
 int        max_target_points_f64();
 
+// closed smoothing B-spline contours (mm_bspline_kernels.hip): jobs = n_jobs BsplJob records (first point, count), one
+// wave each, the work arrays of a contour in lds_bytes = 8 * bspline_work_doubles(longest m, k) of dynamic LDS.
+// out_xyz is indexed like xyz; status / fp / nknots per job.
+size_t     bspline_work_doubles(int m, int k);
+hipError_t launch_bspline_fit(const void* jobs, int n_jobs, const double* xyz, int k, double s, size_t lds_bytes,
+                              double* out_xyz, int32_t* status, double* fp, int32_t* nknots, hipStream_t st);
+
 }  // namespace mm
