@@ -3,8 +3,8 @@
 //
 // manual_hole_fill (multimodars/ccta/fixing_functions.py:13-49) and smooth_mesh_labels
 // (src/ccta/binding/ccta_py.rs:743-814).  include/mm_ccta.h states the rules; every stage has an exact, order-free
-// answer, so the output does not depend on scheduling.  The edge table, the winding and the volume are those of
-// mm_weld_kernels.hip.
+// answer, so the output does not depend on scheduling.  The edge table is that of mm_mesh_device.h as
+// mm_weld_kernels.hip fills it; the winding and the volume are those of mm_weld_kernels.hip.
 //
 //   k_close_half_edges   one lane per slot of the edge table: a slot owned by exactly one face gives the half-edge
 //                        a -> b as that face traverses it (with the flip of the winding stage where it ran), packed
@@ -25,49 +25,37 @@
 #include <cstdint>
 
 #include "mm_device.h"
+#include "mm_mesh_device.h"
 
 namespace mm {
 
-static constexpr int kCloseThreads = 256;
-static constexpr unsigned long long kCloseEdgeEmpty = ~0ull;          // kEdgeEmpty of mm_weld_kernels.hip
 static constexpr unsigned int kSmoothMixed = 0x7FFFFFFFu;
 
-static __device__ __forceinline__ long long close_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-static __device__ __forceinline__ long long close_stride() { return (long long)gridDim.x * blockDim.x; }
-
-// cap is a multiple of kCloseThreads: every lane of a wave runs the same number of rounds (the ballots need it)
-__global__ void __launch_bounds__(kCloseThreads)
+// cap is a multiple of kMeshThreads: every lane of a wave runs the same number of rounds (the ballots need it)
+__global__ void __launch_bounds__(kMeshThreads)
 k_close_half_edges(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
                    const unsigned int* __restrict__ own, unsigned long long cap, const unsigned int* __restrict__ link,
                    unsigned long long* __restrict__ out, unsigned long long out_cap, unsigned long long* __restrict__ n_out)
 {
-    const int lane = (int)__lane_id();
-    for (unsigned long long s = (unsigned long long)close_tid(); s < cap; s += (unsigned long long)close_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         const unsigned long long key = keys[s];
-        const bool open = key != kCloseEdgeEmpty && cnt[s] == 1u;
+        const bool open = key != kEdgeEmpty && cnt[s] == 1u;
         unsigned long long he = 0;
         if (open) {
             const unsigned int o = own[2 * s];
             const unsigned int dir = (o ^ (link ? link[o >> 1] : 0u)) & 1u;      // 1: from the smaller to the larger end
-            const unsigned long long lo = key >> 32, hi = key & 0xFFFFFFFFull;
-            he = dir ? key : ((hi << 32) | lo);
+            he = dir ? key : (((unsigned long long)edge_hi(key) << 32) | edge_lo(key));
         }
-        const unsigned long long b = __ballot(open);
-        unsigned long long base = 0;
-        if (lane == 0 && b) base = atomicAdd(n_out, (unsigned long long)__popcll(b));
-        base = __shfl(base, 0);
-        if (open) {
-            const unsigned long long at = base + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
-            if (at < out_cap) out[at] = he;                                       // never beyond: open edges <= 3 nf
-        }
+        const unsigned long long at = wave_append(open, n_out);
+        if (open && at < out_cap) out[at] = he;                                   // never beyond: open edges <= 3 nf
     }
 }
 
 // fan[3 i .. 3 i + 2] = (a, b, loop) of the i-th half-edge of the loops in walk order
-__global__ void __launch_bounds__(kCloseThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_close_fan(const int32_t* __restrict__ fan, long long n_fan, int32_t nv, int32_t* __restrict__ face, long long nf)
 {
-    for (long long i = close_tid(); i < n_fan; i += close_stride()) {
+    for (long long i = mesh_tid(); i < n_fan; i += mesh_stride()) {
         int32_t* f = face + 3 * (nf + i);
         f[0] = fan[3 * i + 1];
         f[1] = fan[3 * i];
@@ -90,10 +78,10 @@ static __device__ __forceinline__ void smooth_vote(unsigned int* __restrict__ w,
     atomicMax(w, kSmoothMixed);
 }
 
-__global__ void __launch_bounds__(kCloseThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_vote(const int32_t* __restrict__ face, long long nf, const uint8_t* __restrict__ cur, unsigned int* __restrict__ vote)
 {
-    for (long long f = close_tid(); f < nf; f += close_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
         const unsigned int la = cur[a], lb = cur[b], lc = cur[c];
         if (lb == lc) smooth_vote(&vote[a], lb); else smooth_mixed(&vote[a]);
@@ -103,12 +91,11 @@ k_smooth_vote(const int32_t* __restrict__ face, long long nf, const uint8_t* __r
 }
 
 // nv_padded is a multiple of the workgroup; *n_flips += the vertices that changed (one atomicAdd per wave)
-__global__ void __launch_bounds__(kCloseThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_apply(long long nv_padded, long long nv, const uint8_t* __restrict__ cur, unsigned int* __restrict__ vote,
                uint8_t* __restrict__ next, unsigned long long* __restrict__ n_flips)
 {
-    const int lane = (int)__lane_id();
-    for (long long v = close_tid(); v < nv_padded; v += close_stride()) {
+    for (long long v = mesh_tid(); v < nv_padded; v += mesh_stride()) {
         bool flip = false;
         if (v < nv) {
             const unsigned int w = vote[v];
@@ -117,17 +104,15 @@ k_smooth_apply(long long nv_padded, long long nv, const uint8_t* __restrict__ cu
             next[v] = flip ? (uint8_t)(w - 1u) : own;
             if (w != 0u) vote[v] = 0u;
         }
-        const unsigned long long b = __ballot(flip);
-        if (lane == 0 && b) atomicAdd(n_flips, (unsigned long long)__popcll(b));
+        wave_count(flip, n_flips);
     }
 }
 
-__global__ void __launch_bounds__(kCloseThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_csr(long long nv_padded, long long nv, const int32_t* __restrict__ off, const int32_t* __restrict__ nb,
              const uint8_t* __restrict__ cur, uint8_t* __restrict__ next, unsigned long long* __restrict__ n_flips)
 {
-    const int lane = (int)__lane_id();
-    for (long long v = close_tid(); v < nv_padded; v += close_stride()) {
+    for (long long v = mesh_tid(); v < nv_padded; v += mesh_stride()) {
         bool flip = false;
         if (v < nv) {
             const int32_t lo = off[v], hi = off[v + 1];
@@ -142,40 +127,24 @@ k_smooth_csr(long long nv_padded, long long nv, const int32_t* __restrict__ off,
             flip = to != own;
             next[v] = to;
         }
-        const unsigned long long b = __ballot(flip);
-        if (lane == 0 && b) atomicAdd(n_flips, (unsigned long long)__popcll(b));
+        wave_count(flip, n_flips);
     }
 }
-
-static unsigned close_grid(long long n)
-{
-    const long long b = (n + kCloseThreads - 1) / kCloseThreads;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-static long long close_pad(long long n) { return (n + kCloseThreads - 1) / kCloseThreads * kCloseThreads; }
-
-#define CLOSE_LAUNCH(kernel, n, ...)                                                                       \
-    do {                                                                                                   \
-        hipLaunchKernelGGL(kernel, dim3(close_grid(n)), dim3(kCloseThreads), 0, s, __VA_ARGS__);           \
-        const hipError_t he__ = hipGetLastError();                                                         \
-        if (he__ != hipSuccess) return he__;                                                               \
-    } while (0)
 
 hipError_t launch_close_half_edges(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
                                    int log2_cap, const unsigned int* link, unsigned long long* out,
                                    unsigned long long out_cap, unsigned long long* n_out, hipStream_t s)
 {
-    const unsigned long long cap = 1ull << log2_cap;                   // at least kCloseThreads (the host sizes it)
+    const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
     hipError_t he;
     if ((he = hipMemsetAsync(n_out, 0, 8, s)) != hipSuccess) return he;
-    CLOSE_LAUNCH(k_close_half_edges, (long long)cap, keys, cnt, own, cap, link, out, out_cap, n_out);
+    MESH_LAUNCH(k_close_half_edges, mesh_grid((long long)cap), keys, cnt, own, cap, link, out, out_cap, n_out);
     return hipSuccess;
 }
 
 hipError_t launch_close_fan(const int32_t* fan, long long n_fan, long long nv, int32_t* face, long long nf, hipStream_t s)
 {
-    if (n_fan > 0) CLOSE_LAUNCH(k_close_fan, n_fan, fan, n_fan, (int32_t)nv, face, nf);
+    if (n_fan > 0) MESH_LAUNCH(k_close_fan, mesh_grid(n_fan), fan, n_fan, (int32_t)nv, face, nf);
     return hipSuccess;
 }
 
@@ -183,10 +152,10 @@ hipError_t launch_smooth_faces(const int32_t* face, long long nf, long long nv, 
                                uint8_t* next, unsigned long long* n_flips, int* launches, hipStream_t s)
 {
     if (nf > 0) {
-        CLOSE_LAUNCH(k_smooth_vote, nf, face, nf, cur, vote);
+        MESH_LAUNCH(k_smooth_vote, mesh_grid(nf), face, nf, cur, vote);
         ++*launches;
     }
-    CLOSE_LAUNCH(k_smooth_apply, nv, close_pad(nv), nv, cur, vote, next, n_flips);
+    MESH_LAUNCH(k_smooth_apply, mesh_grid(nv), mesh_pad(nv), nv, cur, vote, next, n_flips);
     ++*launches;
     return hipSuccess;
 }
@@ -194,7 +163,7 @@ hipError_t launch_smooth_faces(const int32_t* face, long long nf, long long nv, 
 hipError_t launch_smooth_csr(const int32_t* off, const int32_t* nb, long long nv, const uint8_t* cur, uint8_t* next,
                              unsigned long long* n_flips, int* launches, hipStream_t s)
 {
-    CLOSE_LAUNCH(k_smooth_csr, nv, close_pad(nv), nv, off, nb, cur, next, n_flips);
+    MESH_LAUNCH(k_smooth_csr, mesh_grid(nv), mesh_pad(nv), nv, off, nb, cur, next, n_flips);
     ++*launches;
     return hipSuccess;
 }

@@ -20,21 +20,18 @@
 //   k_rim_gather      out[i] = v[index[i]].
 //   k_rim_edge_faces  keep[f] = 0 and (f, a, b, c) appended to a list when an edge of f joins ring neighbours whose
 //                     ring edge receives points; keep[f] = 1 otherwise.
-//   k_rim_face_gather the kept faces compacted in input order through the scan of the trimming (launch_trim_scan).
+//   k_rim_face_gather the kept faces compacted in input order through launch_trim_scan (the scan of mm_mesh_device.h).
 // The only atomics are integer atomics.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "mm_device.h"
+#include "mm_mesh_device.h"
 
 namespace mm {
 
-static constexpr int kRimThreads = 256;
 static constexpr int kRimChunk = 1024;                                 // query points per LDS chunk: 24 KB
-
-static __device__ __forceinline__ long long rim_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-static __device__ __forceinline__ long long rim_stride() { return (long long)gridDim.x * blockDim.x; }
 
 static __device__ __forceinline__ unsigned long long rim_bits(double x)
 {
@@ -42,12 +39,12 @@ static __device__ __forceinline__ unsigned long long rim_bits(double x)
 }
 
 // q: r query points as 3 r bit patterns (x, y, z interleaved), folded; index: r entries, -1 before the launch
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_locate(const double* __restrict__ v, long long nv, const unsigned long long* __restrict__ q, int r,
              int32_t* __restrict__ index)
 {
     __shared__ unsigned long long s_q[3 * kRimChunk];
-    for (long long base = (long long)blockIdx.x * kRimThreads; base < nv; base += (long long)gridDim.x * kRimThreads) {
+    for (long long base = (long long)blockIdx.x * kMeshThreads; base < nv; base += (long long)gridDim.x * kMeshThreads) {
         const long long i = base + threadIdx.x;                        // the trip count is uniform over the block
         bool ok = i < nv;
         unsigned long long bx = 0, by = 0, bz = 0;
@@ -59,7 +56,7 @@ k_rim_locate(const double* __restrict__ v, long long nv, const unsigned long lon
         for (int c0 = 0; c0 < r; c0 += kRimChunk) {
             const int m = r - c0 < kRimChunk ? r - c0 : kRimChunk;
             __syncthreads();
-            for (int k = threadIdx.x; k < 3 * m; k += kRimThreads) s_q[k] = q[3 * (long long)c0 + k];
+            for (int k = threadIdx.x; k < 3 * m; k += kMeshThreads) s_q[k] = q[3 * (long long)c0 + k];
             __syncthreads();
             if (!ok) continue;
             for (int k = 0; k < m; ++k)
@@ -68,10 +65,10 @@ k_rim_locate(const double* __restrict__ v, long long nv, const unsigned long lon
     }
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_write(const int32_t* __restrict__ index, const double* __restrict__ pts, int n, double* __restrict__ v)
 {
-    for (long long i = rim_tid(); i < n; i += rim_stride()) {
+    for (long long i = mesh_tid(); i < n; i += mesh_stride()) {
         const long long k = index[i];
         if (k < 0) continue;
         v[3 * k] = pts[3 * i];
@@ -80,18 +77,18 @@ k_rim_write(const int32_t* __restrict__ index, const double* __restrict__ pts, i
     }
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_mark(const int32_t* __restrict__ index, int n, int by_position, int32_t* __restrict__ arr)
 {
-    for (long long i = rim_tid(); i < n; i += rim_stride())
+    for (long long i = mesh_tid(); i < n; i += mesh_stride())
         if (index[i] >= 0) arr[index[i]] = by_position ? (int32_t)i : 0;
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_layer(const int32_t* __restrict__ face, long long nf, int32_t* __restrict__ layer, int32_t k,
             unsigned int* __restrict__ n_new)
 {
-    for (long long f = rim_tid(); f < nf; f += rim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t c[3] = {face[3 * f], face[3 * f + 1], face[3 * f + 2]};
         int32_t l[3];
         for (int j = 0; j < 3; ++j) l[j] = __atomic_load_n(&layer[c[j]], __ATOMIC_RELAXED);
@@ -103,11 +100,11 @@ k_rim_layer(const int32_t* __restrict__ face, long long nf, int32_t* __restrict_
     }
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_push(double* __restrict__ v, long long nv, const int32_t* __restrict__ layer, double ox, double oy, double oz,
            double nx, double ny, double nz, double step)
 {
-    for (long long i = rim_tid(); i < nv; i += rim_stride()) {
+    for (long long i = mesh_tid(); i < nv; i += mesh_stride()) {
         const int32_t k = layer[i];
         if (k < 1) continue;
         const double px = v[3 * i], py = v[3 * i + 1], pz = v[3 * i + 2];
@@ -122,10 +119,10 @@ k_rim_push(double* __restrict__ v, long long nv, const int32_t* __restrict__ lay
     }
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_gather(const double* __restrict__ v, const int32_t* __restrict__ index, int n, double* __restrict__ out)
 {
-    for (long long i = rim_tid(); i < n; i += rim_stride()) {
+    for (long long i = mesh_tid(); i < n; i += mesh_stride()) {
         const long long k = index[i];
         if (k < 0) continue;
         out[3 * i] = v[3 * k];
@@ -143,12 +140,12 @@ static __device__ __forceinline__ bool rim_edge_splits(int32_t pa, int32_t pb, i
 }
 
 // list: list_cap entries of 4 words; *n_list counts every touched face, also those beyond list_cap
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_edge_faces(const int32_t* __restrict__ face, long long nf, const int32_t* __restrict__ pos,
                  const int32_t* __restrict__ counts, int n, uint8_t* __restrict__ keep, int32_t* __restrict__ list,
                  unsigned int list_cap, unsigned int* __restrict__ n_list)
 {
-    for (long long f = rim_tid(); f < nf; f += rim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
         const int32_t pa = pos[a], pb = pos[b], pc = pos[c];
         const bool touched = rim_edge_splits(pa, pb, n, counts) || rim_edge_splits(pb, pc, n, counts) ||
@@ -164,10 +161,10 @@ k_rim_edge_faces(const int32_t* __restrict__ face, long long nf, const int32_t* 
     }
 }
 
-__global__ void __launch_bounds__(kRimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_rim_face_gather(const int32_t* __restrict__ face, long long nf, const int32_t* __restrict__ fidx, int32_t* __restrict__ out)
 {
-    for (long long f = rim_tid(); f < nf; f += rim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const long long k = fidx[f];
         if (k < 0) continue;
         out[3 * k] = face[3 * f];
@@ -176,60 +173,56 @@ k_rim_face_gather(const int32_t* __restrict__ face, long long nf, const int32_t*
     }
 }
 
-static unsigned rim_grid(long long n)
-{
-    const long long b = (n + kRimThreads - 1) / kRimThreads;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-#define RIM_LAUNCH(kernel, n, ...)                                                                        \
-    do {                                                                                                  \
-        hipLaunchKernelGGL(kernel, dim3(rim_grid(n)), dim3(kRimThreads), 0, s, __VA_ARGS__);              \
-        return hipGetLastError();                                                                         \
-    } while (0)
-
 int rim_locate_chunk_points() { return kRimChunk; }
 
 hipError_t launch_rim_locate(const double* v, long long nv, const unsigned long long* q, int r, int32_t* index, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_locate, nv, v, nv, q, r, index);
+    MESH_LAUNCH(k_rim_locate, mesh_grid(nv), v, nv, q, r, index);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_write(const int32_t* index, const double* pts, int n, double* v, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_write, n, index, pts, n, v);
+    MESH_LAUNCH(k_rim_write, mesh_grid(n), index, pts, n, v);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_mark(const int32_t* index, int n, int by_position, int32_t* arr, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_mark, n, index, n, by_position, arr);
+    MESH_LAUNCH(k_rim_mark, mesh_grid(n), index, n, by_position, arr);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_layer(const int32_t* face, long long nf, int32_t* layer, int32_t k, unsigned int* n_new, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_layer, nf, face, nf, layer, k, n_new);
+    MESH_LAUNCH(k_rim_layer, mesh_grid(nf), face, nf, layer, k, n_new);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_push(double* v, long long nv, const int32_t* layer, const double o[3], const double n[3], double step,
                            hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_push, nv, v, nv, layer, o[0], o[1], o[2], n[0], n[1], n[2], step);
+    MESH_LAUNCH(k_rim_push, mesh_grid(nv), v, nv, layer, o[0], o[1], o[2], n[0], n[1], n[2], step);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_gather(const double* v, const int32_t* index, int n, double* out, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_gather, n, v, index, n, out);
+    MESH_LAUNCH(k_rim_gather, mesh_grid(n), v, index, n, out);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_edge_faces(const int32_t* face, long long nf, const int32_t* pos, const int32_t* counts, int n,
                                  uint8_t* keep, int32_t* list, unsigned int list_cap, unsigned int* n_list, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_edge_faces, nf, face, nf, pos, counts, n, keep, list, list_cap, n_list);
+    MESH_LAUNCH(k_rim_edge_faces, mesh_grid(nf), face, nf, pos, counts, n, keep, list, list_cap, n_list);
+    return hipSuccess;
 }
 
 hipError_t launch_rim_face_gather(const int32_t* face, long long nf, const int32_t* fidx, int32_t* out, hipStream_t s)
 {
-    RIM_LAUNCH(k_rim_face_gather, nf, face, nf, fidx, out);
+    MESH_LAUNCH(k_rim_face_gather, mesh_grid(nf), face, nf, fidx, out);
+    return hipSuccess;
 }
 
 }  // namespace mm

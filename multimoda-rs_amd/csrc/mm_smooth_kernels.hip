@@ -5,11 +5,11 @@
 // its post-processing, with the row order fixed: include/mm_ccta.h ("mesh smoothing") states the rules, every one of
 // which has a single answer whatever the scheduling.
 //
-//   k_smooth_degree      one lane per slot of the edge table of mm_weld_kernels.hip (each undirected edge once): an edge
+//   k_smooth_degree      one lane per slot of the edge table of mm_mesh_device.h (each undirected edge once): an edge
 //                        between two different vertices adds one to the degree of both ends (integer atomics) and is
 //                        counted, one atomicAdd per wave.
 //   k_smooth_scan_count / k_smooth_scan_tiles / k_smooth_scan_offsets   the exclusive scan of the int32 degrees in the
-//                        three passes of the trimming's scan (tiles of 4096): off[v], off[nv] = the entries; the degree
+//                        three passes of mm_mesh_device.h's scan (tiles of 4096): off[v], off[nv] = the entries; the degree
 //                        array becomes the fill cursor in place.  The last pass also counts the isolated vertices and
 //                        takes the largest degree (one integer atomic per wave each).
 //   k_smooth_fill        every edge writes each end into the other's row through the atomic cursor: the order inside a
@@ -30,109 +30,70 @@
 #include <cstdint>
 
 #include "mm_device.h"
+#include "mm_mesh_device.h"
 
 namespace mm {
 
-static constexpr int kSmoothThreads = 256;
-static constexpr int kSmoothScanItems = 16;                                    // degrees per lane in the scan
-static constexpr int kSmoothScanTile = kSmoothThreads * kSmoothScanItems;     // 4096 per workgroup
 static constexpr int kSmoothInsertion = 24;                                    // rows up to here: insertion sort
-static constexpr unsigned long long kSmoothEdgeEmpty = ~0ull;                  // kEdgeEmpty of mm_weld_kernels.hip
 
-static __device__ __forceinline__ long long smooth_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-static __device__ __forceinline__ long long smooth_stride() { return (long long)gridDim.x * blockDim.x; }
-
-// counts[0] += the edges between different vertices.  cap is a multiple of kSmoothThreads, as is the stride.
-__global__ void __launch_bounds__(kSmoothThreads)
+// counts[0] += the edges between different vertices.  cap is a multiple of kMeshThreads, as is the stride.
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_degree(const unsigned long long* __restrict__ keys, unsigned long long cap, int32_t* __restrict__ deg,
                 unsigned long long* __restrict__ counts)
 {
-    const int lane = (int)__lane_id();
-    for (unsigned long long s = (unsigned long long)smooth_tid(); s < cap; s += (unsigned long long)smooth_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         const unsigned long long k = keys[s];
-        const int32_t lo = (int32_t)(k >> 32), hi = (int32_t)(k & 0xFFFFFFFFull);
-        const bool edge = k != kSmoothEdgeEmpty && lo != hi;
+        const int32_t lo = (int32_t)edge_lo(k), hi = (int32_t)edge_hi(k);
+        const bool edge = k != kEdgeEmpty && lo != hi;
         if (edge) {
             atomicAdd(&deg[lo], 1);
             atomicAdd(&deg[hi], 1);
         }
-        const unsigned long long b = __ballot(edge);
-        if (lane == 0 && b) atomicAdd(&counts[0], (unsigned long long)__popcll(b));
+        wave_count(edge, &counts[0]);
     }
-}
-
-// inclusive sum over the workgroup of one value per lane; returns the lane's exclusive prefix, *total the sum
-static __device__ __forceinline__ long long smooth_block_exclusive(long long x, long long* total)
-{
-    __shared__ long long s_wave[kSmoothThreads / 64];
-    const int lane = (int)__lane_id(), wave = threadIdx.x >> 6;
-    long long inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(inc, d);
-        if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (int w = 0; w < kSmoothThreads / 64; ++w) {
-        const long long t = s_wave[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - x;
 }
 
 // tile_sum[t] = the sum of the degrees of tile t; grid = the number of tiles
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_scan_count(const int32_t* __restrict__ deg, long long n, long long* __restrict__ tile_sum)
 {
-    const long long i0 = (long long)blockIdx.x * kSmoothScanTile + (long long)threadIdx.x * kSmoothScanItems;
+    const long long i0 = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
     long long c = 0;
-    for (int j = 0; j < kSmoothScanItems; ++j)
+    for (int j = 0; j < kScanItems; ++j)
         if (i0 + j < n) c += deg[i0 + j];
     long long total;
-    smooth_block_exclusive(c, &total);
+    block_exclusive<kMeshThreads>(c, &total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
 // one workgroup: tile_sum -> exclusive offsets in place; off[n] = the total
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_scan_tiles(long long* __restrict__ tile_sum, long long n_tiles, int32_t* __restrict__ off, long long n)
 {
-    long long carry = 0;
-    for (long long t0 = 0; t0 < n_tiles; t0 += kSmoothThreads) {
-        const long long t = t0 + threadIdx.x;
-        const long long x = t < n_tiles ? tile_sum[t] : 0;
-        long long total;
-        const long long ex = smooth_block_exclusive(x, &total);
-        if (t < n_tiles) tile_sum[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) off[n] = (int32_t)carry;
+    const long long total = scan_tile_sums(tile_sum, n_tiles);
+    if (threadIdx.x == 0) off[n] = (int32_t)total;
 }
 
 // off[i] = the sum of the degrees before i; deg[i] becomes the same (the fill cursor of row i); counts[1] += the
 // vertices of degree 0, counts[2] = max(counts[2], the largest degree)
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_scan_offsets(int32_t* __restrict__ deg, long long n, const long long* __restrict__ tile_off,
                       int32_t* __restrict__ off, unsigned long long* __restrict__ counts)
 {
-    const long long i0 = (long long)blockIdx.x * kSmoothScanTile + (long long)threadIdx.x * kSmoothScanItems;
-    int32_t d[kSmoothScanItems];
+    const long long i0 = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
+    int32_t d[kScanItems];
     long long c = 0;
     int isolated = 0;
     int32_t longest = 0;
-    for (int j = 0; j < kSmoothScanItems; ++j) {
+    for (int j = 0; j < kScanItems; ++j) {
         d[j] = i0 + j < n ? deg[i0 + j] : -1;
         if (d[j] > 0) c += d[j];
         isolated += d[j] == 0;
         longest = d[j] > longest ? d[j] : longest;
     }
     long long total;
-    long long at = tile_off[blockIdx.x] + smooth_block_exclusive(c, &total);
-    for (int j = 0; j < kSmoothScanItems; ++j) {
+    long long at = tile_off[blockIdx.x] + block_exclusive<kMeshThreads>(c, &total);
+    for (int j = 0; j < kScanItems; ++j) {
         if (d[j] >= 0) {
             off[i0 + j] = (int32_t)at;
             deg[i0 + j] = (int32_t)at;
@@ -150,14 +111,14 @@ k_smooth_scan_offsets(int32_t* __restrict__ deg, long long n, const long long* _
     }
 }
 
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_fill(const unsigned long long* __restrict__ keys, unsigned long long cap, int32_t* __restrict__ cursor,
               int32_t* __restrict__ nb)
 {
-    for (unsigned long long s = (unsigned long long)smooth_tid(); s < cap; s += (unsigned long long)smooth_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         const unsigned long long k = keys[s];
-        const int32_t lo = (int32_t)(k >> 32), hi = (int32_t)(k & 0xFFFFFFFFull);
-        if (k == kSmoothEdgeEmpty || lo == hi) continue;
+        const int32_t lo = (int32_t)edge_lo(k), hi = (int32_t)edge_hi(k);
+        if (k == kEdgeEmpty || lo == hi) continue;
         nb[atomicAdd(&cursor[lo], 1)] = hi;
         nb[atomicAdd(&cursor[hi], 1)] = lo;
     }
@@ -178,10 +139,10 @@ static __device__ __forceinline__ void smooth_sift(int32_t* __restrict__ r, int3
 }
 
 // row v of nb ascending, in place (the entries of a row are distinct)
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_row_sort(const int32_t* __restrict__ off, int32_t* __restrict__ nb, long long nv)
 {
-    for (long long v = smooth_tid(); v < nv; v += smooth_stride()) {
+    for (long long v = mesh_tid(); v < nv; v += mesh_stride()) {
         int32_t* r = nb + off[v];
         const int32_t n = off[v + 1] - off[v];
         if (n <= kSmoothInsertion) {
@@ -204,11 +165,11 @@ k_smooth_row_sort(const int32_t* __restrict__ off, int32_t* __restrict__ nb, lon
 }
 
 // one step with factor f: out = the coordinates after it, in = those before (never the same buffer)
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_step(const int32_t* __restrict__ off, const int32_t* __restrict__ nb, const double* __restrict__ in,
               double* __restrict__ out, long long nv, double f, const uint8_t* __restrict__ pinned)
 {
-    for (long long v = smooth_tid(); v < nv; v += smooth_stride()) {
+    for (long long v = mesh_tid(); v < nv; v += mesh_stride()) {
         const int32_t b = off[v], e = off[v + 1];
         const double x = in[3 * v], y = in[3 * v + 1], z = in[3 * v + 2];
         double nx = x, ny = y, nz = z;
@@ -232,44 +193,40 @@ k_smooth_step(const int32_t* __restrict__ off, const int32_t* __restrict__ nb, c
 }
 
 // ring (all -1 before) = 0 at the seeds; *reached += the distinct seeds
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_ring_seed(const int32_t* __restrict__ seeds, long long n_padded, long long n, int32_t* __restrict__ ring,
                    unsigned long long* __restrict__ reached)
 {
-    const int lane = (int)__lane_id();
-    for (long long i = smooth_tid(); i < n_padded; i += smooth_stride()) {
+    for (long long i = mesh_tid(); i < n_padded; i += mesh_stride()) {
         const bool first = i < n && atomicExch(&ring[seeds[i]], 0) == -1;
-        const unsigned long long b = __ballot(first);
-        if (lane == 0 && b) atomicAdd(reached, (unsigned long long)__popcll(b));
+        wave_count(first, reached);
     }
 }
 
 // ring r (>= 1): a vertex holding -1 with a neighbour holding r - 1 takes r.  A neighbour written in this very launch
 // reads as -1 or r, neither of which is r - 1.  *reached += the vertices set.
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_ring(const int32_t* __restrict__ off, const int32_t* __restrict__ nb, long long nv_padded, long long nv,
               int32_t* __restrict__ ring, int32_t r, unsigned long long* __restrict__ reached)
 {
-    const int lane = (int)__lane_id();
-    for (long long v = smooth_tid(); v < nv_padded; v += smooth_stride()) {
+    for (long long v = mesh_tid(); v < nv_padded; v += mesh_stride()) {
         bool take = false;
         if (v < nv && __atomic_load_n(&ring[v], __ATOMIC_RELAXED) == -1) {
             for (int32_t k = off[v], e = off[v + 1]; k < e && !take; ++k)
                 take = __atomic_load_n(&ring[nb[k]], __ATOMIC_RELAXED) == r - 1;
             if (take) __atomic_store_n(&ring[v], r, __ATOMIC_RELAXED);
         }
-        const unsigned long long b = __ballot(take);
-        if (lane == 0 && b) atomicAdd(reached, (unsigned long long)__popcll(b));
+        wave_count(take, reached);
     }
 }
 
 // *max_bits = max(*max_bits, the bits of (dx dx + dy dy) + dz dz) over the vertices, d = b - a
-__global__ void __launch_bounds__(kSmoothThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_smooth_disp(const double* __restrict__ a, const double* __restrict__ b, long long nv,
               unsigned long long* __restrict__ max_bits)
 {
     unsigned long long m = 0;
-    for (long long v = smooth_tid(); v < nv; v += smooth_stride()) {
+    for (long long v = mesh_tid(); v < nv; v += mesh_stride()) {
         const double dx = b[3 * v] - a[3 * v], dy = b[3 * v + 1] - a[3 * v + 1], dz = b[3 * v + 2] - a[3 * v + 2];
         const unsigned long long q = (unsigned long long)__double_as_longlong((dx * dx + dy * dy) + dz * dz);
         m = q > m ? q : m;
@@ -281,45 +238,32 @@ k_smooth_disp(const double* __restrict__ a, const double* __restrict__ b, long l
     if (__lane_id() == 0 && m) atomicMax(max_bits, m);
 }
 
-static unsigned smooth_grid(long long n)
-{
-    const long long b = (n + kSmoothThreads - 1) / kSmoothThreads;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
+// every launcher here counts the kernels it launched
+#define SMOOTH_LAUNCH(kernel, blocks, ...) do { MESH_LAUNCH(kernel, blocks, __VA_ARGS__); ++*launches; } while (0)
 
-static long long smooth_pad(long long n) { return (n + kSmoothThreads - 1) / kSmoothThreads * kSmoothThreads; }
-
-#define SMOOTH_LAUNCH(kernel, blocks, ...)                                                                 \
-    do {                                                                                                   \
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kSmoothThreads), 0, s, __VA_ARGS__);                 \
-        const hipError_t he__ = hipGetLastError();                                                         \
-        if (he__ != hipSuccess) return he__;                                                               \
-        ++*launches;                                                                                       \
-    } while (0)
-
-size_t mesh_csr_tiles(long long nv) { return (size_t)((nv + kSmoothScanTile - 1) / kSmoothScanTile); }
+size_t mesh_csr_tiles(long long nv) { return scan_tiles(nv); }
 
 hipError_t launch_mesh_csr(const unsigned long long* keys, int log2_cap, long long nv, int32_t* deg, int32_t* off,
                            long long* tile_sum, int32_t* nb, unsigned long long* counts, int* launches, hipStream_t s)
 {
-    const unsigned long long cap = 1ull << log2_cap;                   // at least kSmoothThreads (the host sizes it)
-    const long long tiles = (long long)mesh_csr_tiles(nv);
+    const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
+    const long long tiles = (long long)scan_tiles(nv);
     hipError_t he;
     if ((he = hipMemsetAsync(deg, 0, (size_t)nv * 4, s)) != hipSuccess) return he;
     if ((he = hipMemsetAsync(counts, 0, 4 * 8, s)) != hipSuccess) return he;
-    SMOOTH_LAUNCH(k_smooth_degree, smooth_grid((long long)cap), keys, cap, deg, counts);
+    SMOOTH_LAUNCH(k_smooth_degree, mesh_grid((long long)cap), keys, cap, deg, counts);
     SMOOTH_LAUNCH(k_smooth_scan_count, (unsigned)tiles, deg, nv, tile_sum);
     SMOOTH_LAUNCH(k_smooth_scan_tiles, 1u, tile_sum, tiles, off, nv);
     SMOOTH_LAUNCH(k_smooth_scan_offsets, (unsigned)tiles, deg, nv, tile_sum, off, counts);
-    SMOOTH_LAUNCH(k_smooth_fill, smooth_grid((long long)cap), keys, cap, deg, nb);
-    SMOOTH_LAUNCH(k_smooth_row_sort, smooth_grid(nv), off, nb, nv);
+    SMOOTH_LAUNCH(k_smooth_fill, mesh_grid((long long)cap), keys, cap, deg, nb);
+    SMOOTH_LAUNCH(k_smooth_row_sort, mesh_grid(nv), off, nb, nv);
     return hipSuccess;
 }
 
 hipError_t launch_mesh_step(const int32_t* off, const int32_t* nb, const double* in, double* out, long long nv, double f,
                             const uint8_t* pinned, int* launches, hipStream_t s)
 {
-    SMOOTH_LAUNCH(k_smooth_step, smooth_grid(nv), off, nb, in, out, nv, f, pinned);
+    SMOOTH_LAUNCH(k_smooth_step, mesh_grid(nv), off, nb, in, out, nv, f, pinned);
     return hipSuccess;
 }
 
@@ -329,14 +273,14 @@ hipError_t launch_mesh_ring_seed(const int32_t* seeds, long long n, int32_t* rin
     hipError_t he;
     if ((he = hipMemsetAsync(ring, 0xFF, (size_t)nv * 4, s)) != hipSuccess) return he;
     if ((he = hipMemsetAsync(reached, 0, 8, s)) != hipSuccess) return he;
-    if (n > 0) SMOOTH_LAUNCH(k_smooth_ring_seed, smooth_grid(n), seeds, smooth_pad(n), n, ring, reached);
+    if (n > 0) SMOOTH_LAUNCH(k_smooth_ring_seed, mesh_grid(n), seeds, mesh_pad(n), n, ring, reached);
     return hipSuccess;
 }
 
 hipError_t launch_mesh_ring(const int32_t* off, const int32_t* nb, long long nv, int32_t* ring, int32_t r,
                             unsigned long long* reached, int* launches, hipStream_t s)
 {
-    SMOOTH_LAUNCH(k_smooth_ring, smooth_grid(nv), off, nb, smooth_pad(nv), nv, ring, r, reached);
+    SMOOTH_LAUNCH(k_smooth_ring, mesh_grid(nv), off, nb, mesh_pad(nv), nv, ring, r, reached);
     return hipSuccess;
 }
 
@@ -345,7 +289,7 @@ hipError_t launch_mesh_disp(const double* a, const double* b, long long nv, unsi
 {
     const hipError_t he = hipMemsetAsync(max_bits, 0, 8, s);
     if (he != hipSuccess) return he;
-    SMOOTH_LAUNCH(k_smooth_disp, smooth_grid(nv), a, b, nv, max_bits);
+    SMOOTH_LAUNCH(k_smooth_disp, mesh_grid(nv), a, b, nv, max_bits);
     return hipSuccess;
 }
 

@@ -10,14 +10,15 @@
 //                        also has a corner outside `in` are marked (the rim seeds).  any-mode: keep = some corner in
 //                        `in`; every corner of a kept face is marked (the used vertices).  Marks are plain byte stores
 //                        of 1 from any number of lanes: the races are benign.
-//   k_trim_edge_insert   every kept face inserts its three undirected edge keys (min << 32 | max) into an open-addressing
-//                        table (multiplicative hash, linear probing, 64-bit atomicCAS on the key, 32-bit atomicAdd on
-//                        its count).  The table holds at least twice as many slots as insertions, so a probe ends.
-//   k_trim_edge_compact  the keys of count 1, appended through one returning atomicAdd per wave (ballot, then the
-//                        lane's rank in the ballot).  The order depends on scheduling; the host sorts the keys, so the
-//                        result is the set, independent of it.  No float atomics anywhere.
+//   k_trim_edge_insert   every kept face inserts its three undirected edge keys (min << 32 | max) into the edge table
+//                        of mm_mesh_device.h (edge_insert without owners: 64-bit atomicCAS on the key, 32-bit atomicAdd
+//                        on its count).  The table holds at least twice as many slots as insertions, so a probe ends.
+//   k_trim_edge_compact  the keys of count 1, appended through one returning atomicAdd per wave (wave_append: ballot,
+//                        then the lane's rank in the ballot).  The order depends on scheduling; the host sorts the keys,
+//                        so the result is the set, independent of it.  No float atomics anywhere.
 //   k_trim_tile_count / k_trim_tile_scan / k_trim_index   exclusive scan of a mask (hand-written, three passes: tile
-//                        counts, one workgroup scanning the tile counts, per-element indices), -1 where the mask is 0.
+//                        counts, one workgroup scanning the tile counts (scan_tile_sums of mm_mesh_device.h), per-element
+//                        indices), -1 where the mask is 0.
 //   k_trim_gather / k_trim_remap   the kept vertices to their new slots, the kept faces remapped to the new indices.
 //   k_trim_clear         mask[idx[i]] = 0 for the vertices a cleaning round culls.
 #include <hip/hip_runtime.h>
@@ -25,22 +26,15 @@
 #include <cstdint>
 
 #include "mm_device.h"
+#include "mm_mesh_device.h"
 
 namespace mm {
 
-static constexpr int kTrimThreads = 256;
-static constexpr int kScanItems = 16;                                  // mask bytes per lane in the scan
-static constexpr int kScanTile = kTrimThreads * kScanItems;            // 4096 per workgroup
-static constexpr unsigned long long kTrimEmpty = ~0ull;                // no key: both ends < 2^31 never give it
-
-static __device__ __forceinline__ long long trim_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-static __device__ __forceinline__ long long trim_stride() { return (long long)gridDim.x * blockDim.x; }
-
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_faces(const int32_t* __restrict__ face, long long nf, const uint8_t* __restrict__ in, int any_mode,
              uint8_t* __restrict__ fkeep, uint8_t* __restrict__ mark)
 {
-    for (long long f = trim_tid(); f < nf; f += trim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
         const uint8_t ia = in[a], ib = in[b], ic = in[c];
         if (any_mode) {
@@ -59,79 +53,35 @@ k_trim_faces(const int32_t* __restrict__ face, long long nf, const uint8_t* __re
     }
 }
 
-static __device__ __forceinline__ void trim_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
-                                                   unsigned long long mask, int shift, int32_t u, int32_t v)
-{
-    const unsigned long long lo = (unsigned long long)(u < v ? u : v), hi = (unsigned long long)(u < v ? v : u);
-    const unsigned long long key = (lo << 32) | hi;
-    unsigned long long s = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (;;) {
-        const unsigned long long prev = atomicCAS(&keys[s], kTrimEmpty, key);
-        if (prev == kTrimEmpty || prev == key) {
-            atomicAdd(&cnt[s], 1u);
-            return;
-        }
-        s = (s + 1) & mask;
-    }
-}
-
-// table: cap = mask + 1 slots (a power of two), slot of a key = its multiplicative hash >> shift (64 - log2 cap)
-__global__ void __launch_bounds__(kTrimThreads)
+// the edge table of mm_mesh_device.h without owners: cap = mask + 1 slots, shift = 64 - log2 cap
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_edge_insert(const int32_t* __restrict__ face, long long nf, const uint8_t* __restrict__ fkeep,
                    unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt, unsigned long long mask, int shift)
 {
-    for (long long f = trim_tid(); f < nf; f += trim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         if (!fkeep[f]) continue;
         const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
-        trim_insert(keys, cnt, mask, shift, a, b);
-        trim_insert(keys, cnt, mask, shift, b, c);
-        trim_insert(keys, cnt, mask, shift, c, a);
+        edge_insert<false>(keys, cnt, nullptr, mask, shift, a, b, 0u);
+        edge_insert<false>(keys, cnt, nullptr, mask, shift, b, c, 0u);
+        edge_insert<false>(keys, cnt, nullptr, mask, shift, c, a, 0u);
     }
 }
 
-// cap is a multiple of kTrimThreads and the stride a multiple of it: every wave runs the loop with all 64 lanes
-__global__ void __launch_bounds__(kTrimThreads)
+// cap is a multiple of kMeshThreads and the stride a multiple of it: every wave runs the loop with all 64 lanes
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_edge_compact(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
                     unsigned long long cap, unsigned long long* __restrict__ out, unsigned long long* __restrict__ n_out)
 {
-    const int lane = (int)__lane_id();
-    const unsigned long long below = (1ull << lane) - 1;                 // the lanes before this one
-    for (unsigned long long s = (unsigned long long)trim_tid(); s < cap; s += (unsigned long long)trim_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         const unsigned long long k = keys[s];
-        const bool open = k != kTrimEmpty && cnt[s] == 1u;
-        const unsigned long long ballot = __ballot(open);
-        unsigned long long base = 0;
-        if (lane == 0 && ballot) base = atomicAdd(n_out, (unsigned long long)__popcll(ballot));
-        base = __shfl(base, 0);
-        if (open) out[base + (unsigned long long)__popcll(ballot & below)] = k;
+        const bool open = k != kEdgeEmpty && cnt[s] == 1u;
+        const unsigned long long at = wave_append(open, n_out);
+        if (open) out[at] = k;
     }
-}
-
-// inclusive sum over the workgroup of one value per lane; returns the lane's exclusive prefix, *total the sum
-static __device__ __forceinline__ long long trim_block_exclusive(long long x, long long* total)
-{
-    __shared__ long long s_wave[kTrimThreads / 64];
-    const int lane = (int)__lane_id(), wave = threadIdx.x >> 6;
-    long long inc = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long y = __shfl_up(inc, d);
-        if (lane >= d) inc += y;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-    for (int w = 0; w < kTrimThreads / 64; ++w) {
-        const long long t = s_wave[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    *total = all;
-    return before + inc - x;
 }
 
 // tile_sum[t] = the number of nonzero flags in tile t (kScanTile flags); grid = the number of tiles
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_tile_count(const uint8_t* __restrict__ flag, long long n, long long* __restrict__ tile_sum)
 {
     const long long i0 = (long long)blockIdx.x * kScanTile + (long long)threadIdx.x * kScanItems;
@@ -139,28 +89,20 @@ k_trim_tile_count(const uint8_t* __restrict__ flag, long long n, long long* __re
     for (int j = 0; j < kScanItems; ++j)
         if (i0 + j < n) c += flag[i0 + j] != 0;
     long long total;
-    trim_block_exclusive(c, &total);
+    block_exclusive<kMeshThreads>(c, &total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
 // one workgroup: tile_sum -> exclusive offsets in place, tile_sum[n_tiles] = the total
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_tile_scan(long long* __restrict__ tile_sum, long long n_tiles)
 {
-    long long carry = 0;
-    for (long long t0 = 0; t0 < n_tiles; t0 += kTrimThreads) {
-        const long long t = t0 + threadIdx.x;
-        const long long x = t < n_tiles ? tile_sum[t] : 0;
-        long long total;
-        const long long ex = trim_block_exclusive(x, &total);
-        if (t < n_tiles) tile_sum[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) tile_sum[n_tiles] = carry;
+    const long long total = scan_tile_sums(tile_sum, n_tiles);
+    if (threadIdx.x == 0) tile_sum[n_tiles] = total;
 }
 
 // idx[i] = the number of nonzero flags before i where flag[i] != 0, else -1
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_index(const uint8_t* __restrict__ flag, long long n, const long long* __restrict__ tile_off,
              int32_t* __restrict__ idx)
 {
@@ -169,7 +111,7 @@ k_trim_index(const uint8_t* __restrict__ flag, long long n, const long long* __r
     for (int j = 0; j < kScanItems; ++j)
         if (i0 + j < n) c += flag[i0 + j] != 0;
     long long total;
-    long long at = tile_off[blockIdx.x] + trim_block_exclusive(c, &total);
+    long long at = tile_off[blockIdx.x] + block_exclusive<kMeshThreads>(c, &total);
     for (int j = 0; j < kScanItems; ++j) {
         if (i0 + j >= n) break;
         if (flag[i0 + j]) idx[i0 + j] = (int32_t)at++;
@@ -177,10 +119,10 @@ k_trim_index(const uint8_t* __restrict__ flag, long long n, const long long* __r
     }
 }
 
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_gather(const double* __restrict__ v, long long nv, const int32_t* __restrict__ vidx, double* __restrict__ out)
 {
-    for (long long i = trim_tid(); i < nv; i += trim_stride()) {
+    for (long long i = mesh_tid(); i < nv; i += mesh_stride()) {
         const int32_t k = vidx[i];
         if (k < 0) continue;
         out[3 * (long long)k] = v[3 * i];
@@ -189,11 +131,11 @@ k_trim_gather(const double* __restrict__ v, long long nv, const int32_t* __restr
     }
 }
 
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_remap(const int32_t* __restrict__ face, long long nf, const int32_t* __restrict__ fidx,
              const int32_t* __restrict__ vidx, int32_t* __restrict__ out)
 {
-    for (long long f = trim_tid(); f < nf; f += trim_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t k = fidx[f];
         if (k < 0) continue;
         out[3 * (long long)k] = vidx[face[3 * f]];
@@ -202,24 +144,17 @@ k_trim_remap(const int32_t* __restrict__ face, long long nf, const int32_t* __re
     }
 }
 
-__global__ void __launch_bounds__(kTrimThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_trim_clear(const int32_t* __restrict__ idx, long long n, uint8_t* __restrict__ mask)
 {
-    for (long long i = trim_tid(); i < n; i += trim_stride()) mask[idx[i]] = 0;
-}
-
-static unsigned trim_grid(long long n)
-{
-    const long long b = (n + kTrimThreads - 1) / kTrimThreads;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+    for (long long i = mesh_tid(); i < n; i += mesh_stride()) mask[idx[i]] = 0;
 }
 
 hipError_t launch_trim_faces(const int32_t* face, long long nf, const uint8_t* in, int any_mode, uint8_t* fkeep,
                              uint8_t* mark, hipStream_t s)
 {
-    if (nf <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_trim_faces, dim3(trim_grid(nf)), dim3(kTrimThreads), 0, s, face, nf, in, any_mode, fkeep, mark);
-    return hipGetLastError();
+    if (nf > 0) MESH_LAUNCH(k_trim_faces, mesh_grid(nf), face, nf, in, any_mode, fkeep, mark);
+    return hipSuccess;
 }
 
 hipError_t launch_trim_open_edges(const int32_t* face, long long nf, const uint8_t* fkeep, unsigned long long* keys,
@@ -232,49 +167,35 @@ hipError_t launch_trim_open_edges(const int32_t* face, long long nf, const uint8
     if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
     if ((he = hipMemsetAsync(n_out, 0, 8, s)) != hipSuccess) return he;
     if (nf <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_trim_edge_insert, dim3(trim_grid(nf)), dim3(kTrimThreads), 0, s, face, nf, fkeep, keys, cnt,
-                       cap - 1, 64 - log2_cap);
-    if ((he = hipGetLastError()) != hipSuccess) return he;
-    hipLaunchKernelGGL(k_trim_edge_compact, dim3(trim_grid((long long)cap)), dim3(kTrimThreads), 0, s, keys, cnt, cap,
-                       out, n_out);
-    return hipGetLastError();
+    MESH_LAUNCH(k_trim_edge_insert, mesh_grid(nf), face, nf, fkeep, keys, cnt, cap - 1, 64 - log2_cap);
+    MESH_LAUNCH(k_trim_edge_compact, mesh_grid((long long)cap), keys, cnt, cap, out, n_out);
+    return hipSuccess;
 }
 
-size_t trim_scan_tiles(long long n) { return (size_t)((n + kScanTile - 1) / kScanTile); }
+size_t trim_scan_tiles(long long n) { return scan_tiles(n); }
 
 hipError_t launch_trim_scan(const uint8_t* flag, long long n, long long* tile_sum, int32_t* idx, hipStream_t s)
 {
-    const long long tiles = (long long)trim_scan_tiles(n);
+    const long long tiles = (long long)scan_tiles(n);
     if (tiles == 0) return hipMemsetAsync(tile_sum, 0, 8, s);
-    hipLaunchKernelGGL(k_trim_tile_count, dim3((unsigned)tiles), dim3(kTrimThreads), 0, s, flag, n, tile_sum);
-    hipError_t he;
-    if ((he = hipGetLastError()) != hipSuccess) return he;
-    hipLaunchKernelGGL(k_trim_tile_scan, dim3(1), dim3(kTrimThreads), 0, s, tile_sum, tiles);
-    if ((he = hipGetLastError()) != hipSuccess) return he;
-    hipLaunchKernelGGL(k_trim_index, dim3((unsigned)tiles), dim3(kTrimThreads), 0, s, flag, n, tile_sum, idx);
-    return hipGetLastError();
+    MESH_LAUNCH(k_trim_tile_count, (unsigned)tiles, flag, n, tile_sum);
+    MESH_LAUNCH(k_trim_tile_scan, 1u, tile_sum, tiles);
+    MESH_LAUNCH(k_trim_index, (unsigned)tiles, flag, n, tile_sum, idx);
+    return hipSuccess;
 }
 
 hipError_t launch_trim_compact(const double* v, long long nv, const int32_t* vidx, const int32_t* face, long long nf,
                                const int32_t* fidx, double* out_v, int32_t* out_f, hipStream_t s)
 {
-    if (nv > 0) {
-        hipLaunchKernelGGL(k_trim_gather, dim3(trim_grid(nv)), dim3(kTrimThreads), 0, s, v, nv, vidx, out_v);
-        const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return he;
-    }
-    if (nf > 0) {
-        hipLaunchKernelGGL(k_trim_remap, dim3(trim_grid(nf)), dim3(kTrimThreads), 0, s, face, nf, fidx, vidx, out_f);
-        return hipGetLastError();
-    }
+    if (nv > 0) MESH_LAUNCH(k_trim_gather, mesh_grid(nv), v, nv, vidx, out_v);
+    if (nf > 0) MESH_LAUNCH(k_trim_remap, mesh_grid(nf), face, nf, fidx, vidx, out_f);
     return hipSuccess;
 }
 
 hipError_t launch_trim_clear(const int32_t* idx, long long n, uint8_t* mask, hipStream_t s)
 {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_trim_clear, dim3(trim_grid(n)), dim3(kTrimThreads), 0, s, idx, n, mask);
-    return hipGetLastError();
+    if (n > 0) MESH_LAUNCH(k_trim_clear, mesh_grid(n), idx, n, mask);
+    return hipSuccess;
 }
 
 }  // namespace mm

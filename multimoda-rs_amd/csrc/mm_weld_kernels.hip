@@ -18,7 +18,7 @@
 //                        after the weld is dropped, the others go through the same kind of table keyed by their
 //                        sorted new index triple.
 //   k_weld_face_rep      fkeep[f] = the face is the smallest index of its vertex set.
-//   k_weld_edge_insert   the three undirected edges of every face into the 64-bit CAS table of the trimming, with a
+//   k_weld_edge_insert   the three undirected edges of every face into the edge table of mm_mesh_device.h, with a
 //                        count and the first two owners (face << 1 | traverses it from the smaller to the larger end).
 //   k_weld_hook          union-find with parity over the edges owned by exactly two faces: link[f] = parent << 1 |
 //                        parity to the parent.  A root hooks under a smaller root with one atomicCAS (parents only
@@ -35,15 +35,11 @@
 #include <cstdint>
 
 #include "mm_device.h"
+#include "mm_mesh_device.h"
 
 namespace mm {
 
-static constexpr int kWeldThreads = 256;
 static constexpr int32_t kWeldEmpty = -1;
-static constexpr unsigned long long kEdgeEmpty = ~0ull;               // no key: both ends < 2^31 never give it
-
-static __device__ __forceinline__ long long weld_tid() { return (long long)blockIdx.x * blockDim.x + threadIdx.x; }
-static __device__ __forceinline__ long long weld_stride() { return (long long)gridDim.x * blockDim.x; }
 
 static __device__ __forceinline__ unsigned long long weld_mix(unsigned long long h, unsigned long long k)
 {
@@ -64,10 +60,10 @@ static __device__ __forceinline__ bool weld_key(const double* __restrict__ v, lo
     return ok;
 }
 
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_mark(const int32_t* __restrict__ face, long long nf, uint8_t* __restrict__ ref)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         ref[face[3 * f]] = 1;
         ref[face[3 * f + 1]] = 1;
         ref[face[3 * f + 2]] = 1;
@@ -75,11 +71,11 @@ k_weld_mark(const int32_t* __restrict__ face, long long nf, uint8_t* __restrict_
 }
 
 // rep[v] = the slot of v's key, -2 for a referenced vertex without a key, -1 unreferenced
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_vertex_insert(const double* __restrict__ v, long long nv, const uint8_t* __restrict__ ref, double scale,
                      int32_t* __restrict__ table, unsigned long long mask, int shift, int32_t* __restrict__ rep)
 {
-    for (long long i = weld_tid(); i < nv; i += weld_stride()) {
+    for (long long i = mesh_tid(); i < nv; i += mesh_stride()) {
         if (!ref[i]) { rep[i] = -1; continue; }
         long long k[3];
         if (!weld_key(v, i, scale, k)) { rep[i] = -2; continue; }
@@ -100,12 +96,11 @@ k_weld_vertex_insert(const double* __restrict__ v, long long nv, const uint8_t* 
 }
 
 // counts[0] += the unreferenced vertices (one atomicAdd per wave); nv_padded is a multiple of the workgroup
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_vertex_rep(long long nv_padded, long long nv, const int32_t* __restrict__ table, int32_t* __restrict__ rep,
                   uint8_t* __restrict__ keep, unsigned long long* __restrict__ counts)
 {
-    const int lane = (int)__lane_id();
-    for (long long i = weld_tid(); i < nv_padded; i += weld_stride()) {
+    for (long long i = mesh_tid(); i < nv_padded; i += mesh_stride()) {
         bool unref = false;
         if (i < nv) {
             const int32_t s = rep[i];
@@ -114,8 +109,7 @@ k_weld_vertex_rep(long long nv_padded, long long nv, const int32_t* __restrict__
             keep[i] = r == (int32_t)i;
             unref = r < 0;
         }
-        const unsigned long long b = __ballot(unref);
-        if (lane == 0 && b) atomicAdd(&counts[0], (unsigned long long)__popcll(b));
+        wave_count(unref, &counts[0]);
     }
 }
 
@@ -129,18 +123,18 @@ static __device__ __forceinline__ void weld_sort3(int32_t a, int32_t b, int32_t 
 }
 
 // vmap[v] = the new index of the vertex v was welded into (-1 unreferenced): vidx is the scan of keep
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_vmap(long long nv, const int32_t* __restrict__ rep, const int32_t* __restrict__ vidx, int32_t* __restrict__ vmap)
 {
-    for (long long i = weld_tid(); i < nv; i += weld_stride()) vmap[i] = rep[i] >= 0 ? vidx[rep[i]] : -1;
+    for (long long i = mesh_tid(); i < nv; i += mesh_stride()) vmap[i] = rep[i] >= 0 ? vidx[rep[i]] : -1;
 }
 
 // frep[f] = the slot of f's vertex set in the welded numbering, -1 when two corners coincide there
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_face_insert(const int32_t* __restrict__ face, long long nf, const int32_t* __restrict__ vmap,
                    int32_t* __restrict__ table, unsigned long long mask, int shift, int32_t* __restrict__ frep)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = vmap[face[3 * f]], b = vmap[face[3 * f + 1]], c = vmap[face[3 * f + 2]];
         if (a == b || b == c || a == c) { frep[f] = -1; continue; }
         int32_t k[3];
@@ -163,12 +157,11 @@ k_weld_face_insert(const int32_t* __restrict__ face, long long nf, const int32_t
 }
 
 // fkeep[f] = 1 for the survivors; counts[0] += degenerate faces, counts[1] += repeated faces (one atomicAdd per wave)
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_face_rep(long long nf_padded, long long nf, const int32_t* __restrict__ table, const int32_t* __restrict__ frep,
                 uint8_t* __restrict__ fkeep, unsigned long long* __restrict__ counts)
 {
-    const int lane = (int)__lane_id();
-    for (long long f = weld_tid(); f < nf_padded; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf_padded; f += mesh_stride()) {
         bool degenerate = false, repeated = false;
         if (f < nf) {
             const int32_t s = frep[f];
@@ -176,46 +169,27 @@ k_weld_face_rep(long long nf_padded, long long nf, const int32_t* __restrict__ t
             repeated = !degenerate && table[s] != (int32_t)f;
             fkeep[f] = !degenerate && !repeated;
         }
-        const unsigned long long bd = __ballot(degenerate), br = __ballot(repeated);
-        if (lane == 0 && bd) atomicAdd(&counts[0], (unsigned long long)__popcll(bd));
-        if (lane == 0 && br) atomicAdd(&counts[1], (unsigned long long)__popcll(br));
+        wave_count(degenerate, &counts[0]);
+        wave_count(repeated, &counts[1]);
     }
 }
 
-static __device__ __forceinline__ void weld_edge(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
-                                                 unsigned int* __restrict__ own, unsigned long long mask, int shift,
-                                                 int32_t u, int32_t v, unsigned int f)
-{
-    const unsigned long long lo = (unsigned long long)(u < v ? u : v), hi = (unsigned long long)(u < v ? v : u);
-    const unsigned long long key = (lo << 32) | hi;
-    unsigned long long s = (key * 0x9E3779B97F4A7C15ull) >> shift;
-    for (;;) {
-        const unsigned long long prev = atomicCAS(&keys[s], kEdgeEmpty, key);
-        if (prev == kEdgeEmpty || prev == key) {
-            const unsigned int p = atomicAdd(&cnt[s], 1u);
-            if (p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
-            return;
-        }
-        s = (s + 1) & mask;
-    }
-}
-
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_edge_insert(const int32_t* __restrict__ face, long long nf, unsigned long long* __restrict__ keys,
                    unsigned int* __restrict__ cnt, unsigned int* __restrict__ own, unsigned long long mask, int shift)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = face[3 * f], b = face[3 * f + 1], c = face[3 * f + 2];
-        weld_edge(keys, cnt, own, mask, shift, a, b, (unsigned int)f);
-        weld_edge(keys, cnt, own, mask, shift, b, c, (unsigned int)f);
-        weld_edge(keys, cnt, own, mask, shift, c, a, (unsigned int)f);
+        edge_insert<true>(keys, cnt, own, mask, shift, a, b, (unsigned int)f);
+        edge_insert<true>(keys, cnt, own, mask, shift, b, c, (unsigned int)f);
+        edge_insert<true>(keys, cnt, own, mask, shift, c, a, (unsigned int)f);
     }
 }
 
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_link_init(unsigned int* __restrict__ link, long long nf)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) link[f] = (unsigned int)f << 1;
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) link[f] = (unsigned int)f << 1;
 }
 
 static __device__ __forceinline__ unsigned int weld_load(const unsigned int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
@@ -236,11 +210,11 @@ static __device__ __forceinline__ unsigned int weld_find(unsigned int* __restric
     return x;
 }
 
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_hook(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
             const unsigned int* __restrict__ own, unsigned long long cap, unsigned int* __restrict__ link)
 {
-    for (unsigned long long s = (unsigned long long)weld_tid(); s < cap; s += (unsigned long long)weld_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         if (keys[s] == kEdgeEmpty || cnt[s] != 2u) continue;
         const unsigned int oa = own[2 * s], ob = own[2 * s + 1];
         unsigned int a = oa >> 1, b = ob >> 1;
@@ -258,10 +232,10 @@ k_weld_hook(const unsigned long long* __restrict__ keys, const unsigned int* __r
 }
 
 // one round of pointer jumping; *changed = 1 where a link moved
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_jump(unsigned int* __restrict__ link, long long nf, unsigned int* __restrict__ changed)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const unsigned int wx = weld_load(&link[f]);
         const unsigned int p = wx >> 1;
         const unsigned int wp = weld_load(&link[p]);
@@ -273,32 +247,29 @@ k_weld_jump(unsigned int* __restrict__ link, long long nf, unsigned int* __restr
 }
 
 // links are flat (every parent a root): reverse the faces of odd parity; *n_flipped += their number
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_flip(int32_t* __restrict__ face, long long nf_padded, long long nf, const unsigned int* __restrict__ link,
             unsigned long long* __restrict__ n_flipped)
 {
-    const int lane = (int)__lane_id();
-    for (long long f = weld_tid(); f < nf_padded; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf_padded; f += mesh_stride()) {
         const bool flip = f < nf && (link[f] & 1u);
         if (flip) {
             const int32_t a = face[3 * f], c = face[3 * f + 2];
             face[3 * f] = c;
             face[3 * f + 2] = a;
         }
-        const unsigned long long b = __ballot(flip);
-        if (lane == 0 && b) atomicAdd(n_flipped, (unsigned long long)__popcll(b));
+        wave_count(flip, n_flipped);
     }
 }
 
 // counts[0] += edges owned once, counts[1] += edges owned more than twice, counts[2] += edges owned twice whose faces
-// (with the flips of `link`, flat) traverse them in the same direction.  cap is a multiple of kWeldThreads.
-__global__ void __launch_bounds__(kWeldThreads)
+// (with the flips of `link`, flat) traverse them in the same direction.  cap is a multiple of kMeshThreads.
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_edge_report(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
                    const unsigned int* __restrict__ own, unsigned long long cap, const unsigned int* __restrict__ link,
                    unsigned long long* __restrict__ counts)
 {
-    const int lane = (int)__lane_id();
-    for (unsigned long long s = (unsigned long long)weld_tid(); s < cap; s += (unsigned long long)weld_stride()) {
+    for (unsigned long long s = (unsigned long long)mesh_tid(); s < cap; s += (unsigned long long)mesh_stride()) {
         const bool used = keys[s] != kEdgeEmpty;
         const unsigned int c = used ? cnt[s] : 0u;
         bool conflict = false;
@@ -307,18 +278,17 @@ k_weld_edge_report(const unsigned long long* __restrict__ keys, const unsigned i
             const unsigned int fa = link ? (link[oa >> 1] & 1u) : 0u, fb = link ? (link[ob >> 1] & 1u) : 0u;
             conflict = (((oa ^ fa) ^ (ob ^ fb)) & 1u) == 0u;
         }
-        const unsigned long long b1 = __ballot(c == 1u), b3 = __ballot(c > 2u), bc = __ballot(conflict);
-        if (lane == 0 && b1) atomicAdd(&counts[0], (unsigned long long)__popcll(b1));
-        if (lane == 0 && b3) atomicAdd(&counts[1], (unsigned long long)__popcll(b3));
-        if (lane == 0 && bc) atomicAdd(&counts[2], (unsigned long long)__popcll(bc));
+        wave_count(c == 1u, &counts[0]);
+        wave_count(c > 2u, &counts[1]);
+        wave_count(conflict, &counts[2]);
     }
 }
 
 // term[f] = v0 . (v1 x v2), unfused, in the order include/mm_ccta.h states
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_terms(const double* __restrict__ v, const int32_t* __restrict__ face, long long nf, double* __restrict__ term)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const double* p0 = v + 3 * (long long)face[3 * f];
         const double* p1 = v + 3 * (long long)face[3 * f + 1];
         const double* p2 = v + 3 * (long long)face[3 * f + 2];
@@ -332,11 +302,11 @@ k_weld_terms(const double* __restrict__ v, const int32_t* __restrict__ face, lon
 // out[b] = the adjacent-pair tree over in[256 b .. 256 b + 255], entries at or beyond n reading +0.0.  `levels` (1..8)
 // of the tree are summed: fewer than 8 only in the last launch, where the padded length is below 256 (the result is
 // then in out[0]; the lanes beyond 2^levels hold other sub-trees and are not read).
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_pair_sum(const double* __restrict__ in, long long n, int levels, double* __restrict__ out)
 {
-    __shared__ double s_wave[kWeldThreads / 64];
-    const long long i = (long long)blockIdx.x * kWeldThreads + threadIdx.x;
+    __shared__ double s_wave[kMeshThreads / 64];
+    const long long i = (long long)blockIdx.x * kMeshThreads + threadIdx.x;
     double x = i < n ? in[i] : 0.0;
     for (int l = 0; l < 6 && l < levels; ++l) x = x + __shfl_xor(x, 1 << l);
     if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = x;
@@ -349,30 +319,15 @@ k_weld_pair_sum(const double* __restrict__ in, long long n, int levels, double* 
     }
 }
 
-__global__ void __launch_bounds__(kWeldThreads)
+__global__ void __launch_bounds__(kMeshThreads)
 k_weld_reverse(int32_t* __restrict__ face, long long nf)
 {
-    for (long long f = weld_tid(); f < nf; f += weld_stride()) {
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
         const int32_t a = face[3 * f], c = face[3 * f + 2];
         face[3 * f] = c;
         face[3 * f + 2] = a;
     }
 }
-
-static unsigned weld_grid(long long n)
-{
-    const long long b = (n + kWeldThreads - 1) / kWeldThreads;
-    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-static long long weld_pad(long long n) { return (n + kWeldThreads - 1) / kWeldThreads * kWeldThreads; }
-
-#define WELD_LAUNCH(kernel, n, ...)                                                                        \
-    do {                                                                                                   \
-        hipLaunchKernelGGL(kernel, dim3(weld_grid(n)), dim3(kWeldThreads), 0, s, __VA_ARGS__);             \
-        const hipError_t he__ = hipGetLastError();                                                         \
-        if (he__ != hipSuccess) return he__;                                                               \
-    } while (0)
 
 hipError_t launch_weld_vertices(const double* v, long long nv, const int32_t* face, long long nf, double scale,
                                 uint8_t* ref, int32_t* table, int log2_cap, int32_t* rep, uint8_t* keep,
@@ -383,9 +338,9 @@ hipError_t launch_weld_vertices(const double* v, long long nv, const int32_t* fa
     if ((he = hipMemsetAsync(table, 0xFF, cap * 4, s)) != hipSuccess) return he;
     if (nv <= 0) return hipSuccess;
     if ((he = hipMemsetAsync(ref, 0, (size_t)nv, s)) != hipSuccess) return he;
-    if (nf > 0) WELD_LAUNCH(k_weld_mark, nf, face, nf, ref);
-    WELD_LAUNCH(k_weld_vertex_insert, nv, v, nv, ref, scale, table, cap - 1, 64 - log2_cap, rep);
-    WELD_LAUNCH(k_weld_vertex_rep, nv, weld_pad(nv), nv, table, rep, keep, counts);
+    if (nf > 0) MESH_LAUNCH(k_weld_mark, mesh_grid(nf), face, nf, ref);
+    MESH_LAUNCH(k_weld_vertex_insert, mesh_grid(nv), v, nv, ref, scale, table, cap - 1, 64 - log2_cap, rep);
+    MESH_LAUNCH(k_weld_vertex_rep, mesh_grid(nv), mesh_pad(nv), nv, table, rep, keep, counts);
     return hipSuccess;
 }
 
@@ -397,9 +352,9 @@ hipError_t launch_weld_faces(const int32_t* face, long long nf, long long nv, co
     hipError_t he;
     if ((he = hipMemsetAsync(table, 0xFF, cap * 4, s)) != hipSuccess) return he;
     if (nf <= 0) return hipSuccess;
-    WELD_LAUNCH(k_weld_vmap, nv, nv, rep, vidx, vmap);
-    WELD_LAUNCH(k_weld_face_insert, nf, face, nf, vmap, table, cap - 1, 64 - log2_cap, frep);
-    WELD_LAUNCH(k_weld_face_rep, nf, weld_pad(nf), nf, table, frep, fkeep, counts);
+    MESH_LAUNCH(k_weld_vmap, mesh_grid(nv), nv, rep, vidx, vmap);
+    MESH_LAUNCH(k_weld_face_insert, mesh_grid(nf), face, nf, vmap, table, cap - 1, 64 - log2_cap, frep);
+    MESH_LAUNCH(k_weld_face_rep, mesh_grid(nf), mesh_pad(nf), nf, table, frep, fkeep, counts);
     return hipSuccess;
 }
 
@@ -410,7 +365,7 @@ hipError_t launch_weld_edges(const int32_t* face, long long nf, unsigned long lo
     hipError_t he;
     if ((he = hipMemsetAsync(keys, 0xFF, cap * 8, s)) != hipSuccess) return he;
     if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
-    if (nf > 0) WELD_LAUNCH(k_weld_edge_insert, nf, face, nf, keys, cnt, own, cap - 1, 64 - log2_cap);
+    if (nf > 0) MESH_LAUNCH(k_weld_edge_insert, mesh_grid(nf), face, nf, keys, cnt, own, cap - 1, 64 - log2_cap);
     return hipSuccess;
 }
 
@@ -419,8 +374,8 @@ hipError_t launch_weld_hook(const unsigned long long* keys, const unsigned int* 
 {
     if (nf <= 0) return hipSuccess;
     const unsigned long long cap = 1ull << log2_cap;
-    WELD_LAUNCH(k_weld_link_init, nf, link, nf);
-    WELD_LAUNCH(k_weld_hook, (long long)cap, keys, cnt, own, cap, link);
+    MESH_LAUNCH(k_weld_link_init, mesh_grid(nf), link, nf);
+    MESH_LAUNCH(k_weld_hook, mesh_grid((long long)cap), keys, cnt, own, cap, link);
     return hipSuccess;
 }
 
@@ -428,26 +383,26 @@ hipError_t launch_weld_jump(unsigned int* link, long long nf, unsigned int* chan
 {
     hipError_t he;
     if ((he = hipMemsetAsync(changed, 0, 4, s)) != hipSuccess) return he;
-    if (nf > 0) WELD_LAUNCH(k_weld_jump, nf, link, nf, changed);
+    if (nf > 0) MESH_LAUNCH(k_weld_jump, mesh_grid(nf), link, nf, changed);
     return hipSuccess;
 }
 
 hipError_t launch_weld_flip(int32_t* face, long long nf, const unsigned int* link, unsigned long long* n_flipped,
                             hipStream_t s)
 {
-    if (nf > 0) WELD_LAUNCH(k_weld_flip, nf, face, weld_pad(nf), nf, link, n_flipped);
+    if (nf > 0) MESH_LAUNCH(k_weld_flip, mesh_grid(nf), face, mesh_pad(nf), nf, link, n_flipped);
     return hipSuccess;
 }
 
 hipError_t launch_weld_edge_report(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own,
                                    int log2_cap, const unsigned int* link, unsigned long long* counts, hipStream_t s)
 {
-    const unsigned long long cap = 1ull << log2_cap;                   // at least kWeldThreads (the host sizes it)
-    WELD_LAUNCH(k_weld_edge_report, (long long)cap, keys, cnt, own, cap, link, counts);
+    const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
+    MESH_LAUNCH(k_weld_edge_report, mesh_grid((long long)cap), keys, cnt, own, cap, link, counts);
     return hipSuccess;
 }
 
-size_t weld_sum_scratch(long long nf) { return (size_t)((nf + kWeldThreads - 1) / kWeldThreads) + 1; }
+size_t weld_sum_scratch(long long nf) { return (size_t)((nf + kMeshThreads - 1) / kMeshThreads) + 1; }
 
 // the pair tree over the nf volume terms: the padded length is 2^levels, and a launch sums 8 levels of it
 static int weld_tree_levels(long long nf)
@@ -467,7 +422,7 @@ hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf
                               hipStream_t s)
 {
     if (nf <= 0) return hipMemsetAsync(out, 0, 8, s);
-    WELD_LAUNCH(k_weld_terms, nf, v, face, nf, a);
+    MESH_LAUNCH(k_weld_terms, mesh_grid(nf), v, face, nf, a);
     int levels = weld_tree_levels(nf);
     const int launches = weld_tree_launches(levels);
     long long n = nf;
@@ -475,11 +430,8 @@ hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf
     double* to = b;
     for (int k = 1; k <= launches; ++k) {
         const int now = levels >= 8 ? 8 : levels;
-        const long long blocks = (n + kWeldThreads - 1) / kWeldThreads;
-        hipLaunchKernelGGL(k_weld_pair_sum, dim3((unsigned)blocks), dim3(kWeldThreads), 0, s, in, n, now,
-                           k == launches ? out : to);
-        const hipError_t he = hipGetLastError();
-        if (he != hipSuccess) return he;
+        const long long blocks = (n + kMeshThreads - 1) / kMeshThreads;
+        MESH_LAUNCH(k_weld_pair_sum, (unsigned)blocks, in, n, now, k == launches ? out : to);
         levels -= 8;
         n = blocks;
         double* t = in; in = to; to = t;
@@ -489,7 +441,7 @@ hipError_t launch_weld_volume(const double* v, const int32_t* face, long long nf
 
 hipError_t launch_weld_reverse(int32_t* face, long long nf, hipStream_t s)
 {
-    if (nf > 0) WELD_LAUNCH(k_weld_reverse, nf, face, nf);
+    if (nf > 0) MESH_LAUNCH(k_weld_reverse, mesh_grid(nf), face, nf);
     return hipSuccess;
 }
 

@@ -14,7 +14,7 @@ from hypothesis import HealthCheck, given, settings, strategies as st
 from mm_checkers import close_mesh as CM
 from mm_checkers import smooth_mesh as SMO
 from mm_checkers import stitch_mesh as SM
-from test_trim_host import octahedron, capped_tube
+from test_trim_host import octahedron, capped_tube, CARRY_NV, band_across_the_carry
 from test_close_host import open_box
 from test_smooth_host import tetrahedron, noisy_icosphere, same_bits
 from test_gpu_stitch import takeoff_case
@@ -88,6 +88,15 @@ def test_one_vertex_past_a_workgroup_and_past_a_scan_tile(engine, n_around, n_ri
     ring, info = ccta.vertex_rings_info(f, [len(v) - 2], 10 ** 6, len(v), engine=engine)
     wring, winfo = SMO.rings(f, len(v), [len(v) - 2], 10 ** 6)
     assert np.array_equal(ring, wring) and info == winfo and info["reached"] == len(v)
+
+
+def test_more_tiles_than_one_round_of_the_tile_scan(engine):
+    """258 tiles of degrees: the one-workgroup scan of the tile sums (256 a round) carries into a second round, and the
+    rows beyond vertex 2^20 start at offsets that come from the carry."""
+    _, f, _, _ = band_across_the_carry()
+    off, nb, info = same_csr(f, CARRY_NV, engine)
+    assert off[2 ** 20 + 1] > 0 and off[2 ** 20 + 1] < off[-1] == len(nb)
+    assert info["n_isolated"] == CARRY_NV - 300 and info["max_degree"] == 4
 
 
 def messy():

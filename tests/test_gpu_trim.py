@@ -8,6 +8,7 @@ import pytest
 
 from mm_checkers import trim_mesh as TM
 from test_trim_host import grid_with_hole, full_grid, octahedron, capped_tube, traces_real_edges
+from test_trim_host import CARRY_NV, band_across_the_carry
 
 import multimoda_rs_amd as mm
 
@@ -181,6 +182,25 @@ def test_a_million_faces(engine):
     same_results(got, TM.remove_labeled_points_from_mesh(dict(res), "anomalous_points"))
     assert len(got["boundary_points_1"]) > 0
     assert np.array_equal(mm.open_boundary_edges(f, engine=engine), TM.open_boundary_edges(f))
+
+
+def test_more_tiles_than_one_round_of_the_tile_scan(engine):
+    """258 tiles of vertices: the one-workgroup scan of the tile counts (256 a round) carries into a second round.  The
+    band's faces hold 0, 4095, 4096, 2^20 - 1, 2^20 and nv - 1; the region takes a band vertex and isolated vertices on
+    each side of 2^20, so the kept vertices beyond it get their new index from the carry."""
+    v, f, lower, _ = band_across_the_carry()
+    nv = len(v)
+    assert nv == CARRY_NV and {0, 4095, 4096, 2 ** 20 - 1, 2 ** 20, nv - 1} <= set(f.ravel().tolist())
+    region = np.concatenate([lower[[10, 90]], np.arange(5000, 6000), np.arange(2 ** 20 + 1000, 2 ** 20 + 1100)])
+    assert (region < 2 ** 20).sum() == 1002 and (region > 2 ** 20).sum() == 100
+    res = {"mesh": (v, f), "anomalous_points": v[region]}
+    got = mm.remove_labeled_points_from_mesh(dict(res), "anomalous_points", engine=engine)
+    want = TM.remove_labeled_points_from_mesh(dict(res), "anomalous_points")
+    same_results(got, want)
+    gv, gf = got["mesh"]
+    assert len(gv) <= nv - len(region) and len(gv) > 2 ** 20 and len(gf) > 0
+    assert gf.min() < 4096 and gf.max() == len(gv) - 1 and same_points(gv[-1], v[-1])
+    assert len(got["boundary_points_1"]) > 0
 
 
 # ---- pipeline ----------------------------------------------------------------------------------------------------------

@@ -55,6 +55,27 @@ def capped_tube(n_around=8, n_rings=5):
     return v, np.concatenate([f, np.array(caps)])
 
 
+CARRY_NV = 256 * 4096 + 4097                    # 258 scan tiles: the one-workgroup tile scan takes a second round
+
+
+def band_across_the_carry(nv=CARRY_NV):
+    """A closed band of 300 faces (two rows of 150 vertices on a circle of radius 10, one unit apart in z) whose 300
+    vertices sit at the indices around 0, the first scan tile's end (4095 | 4096), the first round's end of the tile scan
+    (2^20 - 1 | 2^20) and nv - 1; every other vertex is isolated, at distinct coordinates far away.  Returns
+    (vertices, faces, lower row, upper row): column j of the band is (lower[j], upper[j])."""
+    ids = np.concatenate([np.arange(50), np.arange(4046, 4146), np.arange(2 ** 20 - 50, 2 ** 20 + 50),
+                          np.arange(nv - 50, nv)])
+    lower, upper = ids[0::2], ids[1::2]
+    m = len(lower)
+    v = 1000.0 + np.arange(3 * nv, dtype=np.float64).reshape(nv, 3)
+    a = 2.0 * np.pi * np.arange(m) / m
+    v[lower] = np.column_stack([10.0 * np.cos(a), 10.0 * np.sin(a), np.zeros(m)])
+    v[upper] = v[lower] + [0.0, 0.0, 1.0]
+    j, k = np.arange(m), (np.arange(m) + 1) % m
+    f = np.concatenate([np.column_stack([lower[j], lower[k], upper[j]]), np.column_stack([lower[k], upper[k], upper[j]])])
+    return v, f.astype(np.int64), lower, upper
+
+
 def open_edge_degrees(faces):
     deg = {}
     for a, b in TM.open_boundary_edges(faces).tolist():
