@@ -585,6 +585,79 @@ int     mm_mesh_smooth(mm_engine* e, const double* vertices_xyz, int64_t nv, con
 int     mm_mesh_vertex_rings(mm_engine* e, const int64_t* faces, int64_t nf, int64_t nv, const int64_t* seeds,
                              int64_t n_seeds, int64_t max_ring, int32_t* ring_out, int64_t* info);
 
+/* ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: fix_and_remesh_stitched_mesh brings the coarse CCTA
+ *      triangles down to the intravascular resolution with MeshLab's isotropic remesh; of that filter this is the edge
+ *      split alone -- no collapse, no flip, no tangential relaxation, no reprojection, no repair) --------------------------
+ *
+ * One pass on vertices v (f64) and triangles, with thr2 = (ratio target_len) (ratio target_len) computed once in f64:
+ *   marked     the undirected edge lo < hi is marked when ((dx dx + dy dy) + dz dz) > thr2, d = v[hi] - v[lo] per
+ *              component, unfused f64.  An (a, a) edge is never marked; a NaN length marks nothing.
+ *   numbering  marked edges are numbered in order of first appearance: the faces ascending, in each the corners j = 0, 1,
+ *              2 for the edges (c0, c1), (c1, c2), (c2, c0).  The k-th marked edge gets vertex nv + k, its coordinates
+ *              (v[lo] + v[hi]) * 0.5 per component, its parents (lo, hi).
+ *   children   every face (a, b, c) is replaced, in place and in face order, by children of its winding; m0, m1, m2 are
+ *              the midpoints of (a, b), (b, c), (c, a).
+ *                none marked   the face itself
+ *                one           rotated so that the marked edge is (a, b): (a, m0, c), (m0, b, c)
+ *                two           rotated so that the unmarked edge is (c, a): (m0, b, m1), then the quad a, m0, m1, c cut by
+ *                              its shorter diagonal: |m0 - c|^2 < |a - m1|^2 (the squared length above, on the stored
+ *                              midpoints) gives (a, m0, c), (m0, m1, c); otherwise, ties included, (a, m0, m1), (a, m1, c)
+ *                three         (a, m0, m2), (m0, b, m1), (m2, m1, c), (m0, m1, m2)
+ * The rule is per edge, so every owner of an edge sees the same midpoint: a third owner of a non-manifold edge, both
+ * corners of a degenerate (a, b, a) face.  No existing vertex moves or changes its index.  Passes repeat on the result
+ * until one marks nothing (converged), max_passes have run, or one would bring the vertices above max_vertices: that
+ * pass is not run (stopped_by_cap) and the result of the passes before it is returned.
+ *
+ * Edges of the report: n_edges counts the distinct undirected edges between different vertices, longest_sq is the largest
+ * squared length among them that is not NaN; an edge (an (a, a) edge too) with one owning corner is open, with more than
+ * two non-manifold, as mm_fill_holes counts them.  The volumes are those of mm_mesh_assemble (the same t_f, the same
+ * adjacent-pair tree over the faces in their order, divided by 6).
+ *
+ * Device indices are int32: nv, nf < 2^31 and indices in [0, nv) (MM_ERR_INVALID), 6 nf < 2^31 for the input and for
+ * every pass's result, and a result below 2^31 vertices (MM_ERR_TOO_LARGE).  The mesh is uploaded once, stays on the
+ * device in two buffers that take turns and grow there, and comes down once together with the parents; each pass reads
+ * 80 bytes of counters back.  bytes_uploaded = 24 nv + 12 nf; bytes_downloaded = 24 nv' + 12 nf' + 8 (nv' - nv).
+ * Launches (mm_refine_kernels.hip; all integer atomics, no float atomics): a pass that splits is 6 -- the edge table
+ * with each edge's first corner (1), the marks and the edge counts (1), the children and new vertices per face with
+ * their tile sums (1), the scan of the tile sums (1), the offsets with the midpoints and parents (1), the children (1).
+ * A pass that marks nothing or is stopped by max_vertices ends behind the scan: 4.  Where max_passes passes have run,
+ * the edge counts of the result cost 2 more.  The two volumes: 1 + max(1, ceil(ceil(log2 nf) / 8)) each.  With nv == 0
+ * or nf == 0 nothing is launched and the input is returned. */
+
+#define MM_REFINE_SPLIT_SLOTS 16
+
+typedef struct mm_refine_report {
+    int64_t n_vertices, n_faces;             /* of the result (the capacities needed where they were too small)       */
+    int64_t n_edges_before, n_edges_after;
+    int64_t passes_run;                      /* passes whose marks were taken: the last may have marked nothing       */
+    int64_t splits_per_pass[MM_REFINE_SPLIT_SLOTS];   /* marked edges of pass k; passes beyond 16 add into the last   */
+    int64_t faces_by_template[4];            /* faces of all passes run, by their number of marked corners            */
+    int64_t converged;                       /* 1: the last pass run marked nothing                                   */
+    int64_t stopped_by_cap;                  /* 1: the next pass would have passed max_vertices and was not run       */
+    int64_t n_open_edges_before, n_open_edges_after;
+    int64_t n_nonmanifold_edges_before, n_nonmanifold_edges_after;
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    double  longest_sq_before, longest_sq_after;
+    double  volume_before, volume_after;
+} mm_refine_report;
+
+/* The first half of a pass made public: the distinct undirected edges between different vertices in order of first
+ * appearance (out_edges: lo, hi per edge) with their squared lengths as the marking computes them.  info[4] = {edges,
+ * open edges, non-manifold edges, kernel launches (the 4 of a stopped pass, 1 more for the list)}.  Where edge_cap is
+ * too small, info is filled (the list was not launched), nothing else is written and the call returns MM_ERR_TOO_LARGE. */
+int     mm_mesh_edge_lengths(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                             int64_t edge_cap, int64_t* out_edges, double* out_len_sq, int64_t* info);
+/* The passes above.  target_len and ratio finite and > 0, with a threshold that neither overflows nor underflows to 0;
+ * max_passes >= 0 (0 returns the input, with the edge counts and volumes of the report filled); max_vertices >= 0.
+ * out_vertices: vert_cap triples, out_tris: face_cap triples, out_parents: 2 per new vertex, capacity vert_cap - nv
+ * pairs.  Capacities as mm_fill_holes: where vert_cap or face_cap is too small, nothing but the report is written (all of
+ * it: n_vertices and n_faces are the capacities needed) and the call returns MM_ERR_TOO_LARGE.  On any other error the
+ * outputs are not written. */
+int     mm_mesh_refine(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                       double target_len, double ratio, int64_t max_passes, int64_t max_vertices, int64_t vert_cap,
+                       int64_t face_cap, double* out_vertices, int64_t* out_tris, int64_t* out_parents,
+                       mm_refine_report* report);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

@@ -37,7 +37,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    fix_mesh_winding, assemble_mesh, stitch_rings, stitch_ccta_to_intravascular, stitch, branch_masks,
                    label_branches, label_branches_pair, find_sharp_angles, label, manual_hole_fill, fill_holes,
                    smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned, smooth_mesh,
-                   filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh)
+                   filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh,
+                   mesh_edge_lengths, edge_length_target, refine_mesh)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -76,6 +77,7 @@ __all__ = [
     "label", "manual_hole_fill", "fill_holes", "smooth_mesh_labels", "create_wall_mesh",
     "condition_boundary_rings", "stitch_conditioned",
     "smooth_mesh", "filter_taubin", "filter_laplacian", "mesh_adjacency_csr", "vertex_rings", "postprocess_stitched_mesh",
+    "mesh_edge_lengths", "edge_length_target", "refine_mesh",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

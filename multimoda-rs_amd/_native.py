@@ -117,6 +117,7 @@ EXPORTS_CCTA = [
     "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
+    "mm_mesh_edge_lengths", "mm_mesh_refine",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -142,6 +143,18 @@ class MMSmoothReport(C.Structure):
     _fields_ = [(name, C.c_int64) for name in (
         "n_vertices", "n_faces", "n_edges", "n_isolated", "n_pinned", "max_degree", "steps_run", "launches")] + \
                [(name, C.c_double) for name in ("volume_before", "volume_after", "max_displacement_sq")]
+
+
+class MMRefineReport(C.Structure):
+    """``mm_refine_report`` (include/mm_ccta.h)."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("n_edges_before", C.c_int64),
+                ("n_edges_after", C.c_int64), ("passes_run", C.c_int64), ("splits_per_pass", C.c_int64 * 16),
+                ("faces_by_template", C.c_int64 * 4), ("converged", C.c_int64), ("stopped_by_cap", C.c_int64),
+                ("n_open_edges_before", C.c_int64), ("n_open_edges_after", C.c_int64),
+                ("n_nonmanifold_edges_before", C.c_int64), ("n_nonmanifold_edges_after", C.c_int64),
+                ("n_launches", C.c_int64), ("bytes_uploaded", C.c_int64), ("bytes_downloaded", C.c_int64),
+                ("longest_sq_before", C.c_double), ("longest_sq_after", C.c_double), ("volume_before", C.c_double),
+                ("volume_after", C.c_double)]
 
 
 class MMRimParams(C.Structure):
@@ -556,6 +569,10 @@ def lib():
     L.mm_mesh_smooth.argtypes = [P, P, I64, P, I64, P, I64, P, P, C.POINTER(MMSmoothReport)]
     L.mm_mesh_vertex_rings.restype = I
     L.mm_mesh_vertex_rings.argtypes = [P, P, I64, I64, P, I64, I64, P, P]
+    L.mm_mesh_edge_lengths.restype = I
+    L.mm_mesh_edge_lengths.argtypes = [P, P, I64, P, I64, I64, P, P, P]
+    L.mm_mesh_refine.restype = I
+    L.mm_mesh_refine.argtypes = [P, P, I64, P, I64, D, D, I64, I64, I64, I64, P, P, P, C.POINTER(MMRefineReport)]
     L.mm_assign_rings_to_ends.restype = I
     L.mm_assign_rings_to_ends.argtypes = [P, P, I64, P, P, P]
     L.mm_ring_start.restype = I64

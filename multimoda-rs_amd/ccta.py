@@ -1519,7 +1519,7 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
-           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False) -> dict:
+           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1529,7 +1529,10 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     a dict of ``smooth_mesh`` keywords (``band``, ``pinned``, ``iterations`` ...), then runs the smoothing half of the
     reference's post-processing (``smooth_mesh``; the remesh is not part of this package) on the mesh: the point lists
     follow the moved vertices (``sync_results_to_mesh``) and the result carries ``smooth_report``.  The default
-    ``smooth=False`` changes nothing."""
+    ``smooth=False`` changes nothing.  ``refine=True``, or a dict of ``refine_mesh`` keywords, splits the long edges
+    (``refine_mesh``, the edge split of the reference's remesh) behind the hole fill and in front of the smoothing: a
+    new vertex joins, in ascending order, every point list that holds both its parents, and the result carries
+    ``refine_report``.  The default ``refine=False`` changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1539,7 +1542,34 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(out, smooth, engine)
+    return _smooth_result(_refine_result(out, refine, engine), smooth, engine)
+
+
+def _refine_result(out: dict, refine, engine) -> dict:
+    """The ``refine`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of refine_mesh keywords.  A
+    new vertex is appended, in ascending vertex order, to every point list (SYNC_KEYS, ``boundary_points_*``) that holds
+    both its parents by value; parents that are new vertices themselves count once they have joined."""
+    if refine is False or refine is None:
+        return out
+    kw = dict(refine) if isinstance(refine, dict) else {}
+    kw.setdefault("engine", engine)
+    old = out["mesh"]
+    new, parents, report = refine_mesh(old, **kw)
+    nv0 = _p3(_mesh_parts(old)[0]).shape[0]
+    v = _p3(_mesh_parts(new)[0])
+    out = dict(out)
+    out["mesh"] = new
+    out["refine_report"] = report
+    for key in SYNC_KEYS + tuple(sorted(k for k in out if k.startswith("boundary_points_"))):
+        pts = out.get(key)
+        if pts is None or len(pts) == 0 or parents.shape[0] == 0:
+            continue
+        member = np.zeros(v.shape[0], dtype=bool)
+        member[:nv0] = _match(_p3(pts), v[:nv0]) >= 0
+        for k in range(parents.shape[0]):                                # ascending: a parent's own membership is known
+            member[nv0 + k] = member[parents[k, 0]] and member[parents[k, 1]]
+        out[key] = np.concatenate([_p3(pts), v[nv0:][member[nv0:]]])
+    return out
 
 
 def _smooth_result(out: dict, smooth, engine) -> dict:
@@ -1848,12 +1878,13 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
-                       engine: Optional[N.Engine] = None, smooth=False, **conditioning) -> dict:
+                       engine: Optional[N.Engine] = None, smooth=False, refine=False, **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
-    carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``smooth`` as in ``stitch``: the smoothing
-    runs last and adds ``smooth_report``."""
+    carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``refine`` and ``smooth`` as in ``stitch``:
+    the refinement runs behind the hole fill and adds ``refine_report``, the smoothing runs last and adds
+    ``smooth_report``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
@@ -1865,7 +1896,7 @@ def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(out, smooth, engine)
+    return _smooth_result(_refine_result(out, refine, engine), smooth, engine)
 
 
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
@@ -2185,12 +2216,121 @@ def filter_laplacian(mesh, lamb: float = 0.5, iterations: int = 10, **kw):
     return smooth_mesh(mesh, [float(lamb)] * int(iterations), **kw)[0]
 
 
+# ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: the edge split of the isotropic remesh) -----------
+
+REFINE_REPORT_KEYS = ("n_vertices", "n_faces", "n_edges_before", "n_edges_after", "passes_run", "converged",
+                      "stopped_by_cap", "n_open_edges_before", "n_open_edges_after", "n_nonmanifold_edges_before",
+                      "n_nonmanifold_edges_after", "n_launches", "bytes_uploaded", "bytes_downloaded", "longest_sq_before",
+                      "longest_sq_after", "volume_before", "volume_after")
+
+
+def _edge_lengths_sq(v: np.ndarray, f: np.ndarray, engine):
+    nv, nf = v.shape[0], f.shape[0]
+    h = _engine(engine).handle
+    info = np.zeros(4, dtype=np.int64)
+    cap = 3 * nf // 2 + 64                                                # a closed surface has 3 nf / 2 edges
+    for attempt in (0, 1):
+        edges = np.zeros((max(cap, 1), 2), dtype=np.int64)
+        len_sq = np.zeros(max(cap, 1), dtype=np.float64)
+        rc = N.lib().mm_mesh_edge_lengths(h, N._ptr(v), nv, N._ptr(f), nf, cap, N._ptr(edges), N._ptr(len_sq), N._ptr(info))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and info[0] > cap:
+            cap = int(info[0])
+            continue
+        N.check(rc, "mesh_edge_lengths")
+        break
+    return edges[:info[0]].copy(), len_sq[:info[0]].copy(), info
+
+
+def mesh_edge_lengths(mesh, engine: Optional[N.Engine] = None):
+    """``(edges, lengths)`` of ``mesh`` (a ``(vertices, faces)`` tuple or an object with ``.vertices`` / ``.faces``):
+    the distinct undirected edges ``(lo, hi)`` between different vertices, in the order in which a walk over the faces
+    (corners 0, 1, 2 for the edges (c0, c1), (c1, c2), (c2, c0)) first meets them, and their lengths, the ``sqrt`` of
+    the squares the device computes as ``refine_mesh`` marks with them (csrc/mm_refine_kernels.hip)."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    edges, len_sq, _ = _edge_lengths_sq(v, f, engine)
+    return edges, np.sqrt(len_sq)
+
+
+def edge_length_target(mesh, q: float = 25.0, engine: Optional[N.Engine] = None) -> float:
+    """The reference's automatic ``target_edge_length_mm`` (fixing_functions.py:161-162): the ``q``-th percentile of
+    the unique edge lengths, 25 keeping the fine intravascular resolution."""
+    lengths = mesh_edge_lengths(mesh, engine)[1]
+    if lengths.size == 0:
+        raise ValueError("a mesh without an edge has no edge length target")
+    return float(np.percentile(lengths, q))
+
+
+def refine_mesh(mesh, target_edge_length_mm: Optional[float] = None, *, ratio: float = 4.0 / 3.0, passes: int = 10,
+                max_vertices: Optional[int] = None, engine: Optional[N.Engine] = None):
+    """Split every edge of ``mesh`` longer than ``ratio * target_edge_length_mm`` at its midpoint, pass after pass,
+    on the device: ``(mesh, parents, report)``, the mesh of the kind given, the input not modified.  This is the edge
+    split of the isotropic remesh with which the reference's post-processing (fixing_functions.py:114-239, MeshLab)
+    brings the coarse CCTA triangles down to the intravascular resolution; its collapse, flip, tangential relaxation,
+    reprojection and repair steps are not part of this project.  No existing vertex moves or changes its index: new
+    vertices follow the old ones, ``parents[k]`` = the ends ``(lo, hi)`` of the edge whose midpoint vertex
+    ``nv + k`` is, and every face is replaced in place by 1 to 4 children of its winding (include/mm_ccta.h, "mesh
+    refinement", states the rule; it has one bit pattern whatever the scheduling).  A closed manifold mesh stays closed
+    and manifold, and its volume changes by rounding only.
+
+    ``target_edge_length_mm=None`` takes ``edge_length_target(mesh)``, the 25th percentile of the edge lengths as the
+    reference does; ``ratio`` = 4/3 is the split threshold of Botsch and Kobbelt and of MeshLab's filter.  At most
+    ``passes`` passes run (the reference's ``remesh_iterations``); they end on their own once no edge is too long
+    (``converged``).  A pass that would bring the vertices above ``max_vertices`` is not run (``stopped_by_cap``).
+    ``report``: REFINE_REPORT_KEYS, ``splits_per_pass`` (16 entries), ``faces_by_template`` (faces by their number of
+    split edges, 0 .. 3, over all passes), ``target_edge_length_mm``, ``threshold_mm`` and ``watertight`` (no open and no
+    non-manifold edge afterwards).  The outputs are allocated for a fourfold mesh first and, where that is too small,
+    once more with the sizes the first call reports."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    nf = f.shape[0]
+    if int(passes) < 0:
+        raise ValueError("passes must not be negative")
+    if max_vertices is not None and int(max_vertices) < 0:
+        raise ValueError("max_vertices must not be negative")
+    if target_edge_length_mm is None:
+        lengths = np.sqrt(_edge_lengths_sq(v, f, engine)[1])
+        if lengths.size == 0:
+            raise ValueError("a mesh without an edge has no edge length target")
+        target_edge_length_mm = float(np.percentile(lengths, 25.0))
+    target, ratio = float(target_edge_length_mm), float(ratio)
+    if not (np.isfinite(target) and target > 0.0 and np.isfinite(ratio) and ratio > 0.0):
+        raise ValueError("target_edge_length_mm and ratio must be finite and greater than 0")
+    h = _engine(engine).handle
+    rep = N.MMRefineReport()
+    cap_v = 2 ** 31 - 1 if max_vertices is None else int(max_vertices)
+    vert_cap, face_cap = 4 * nv + 64, 4 * nf + 64
+    for attempt in (0, 1):
+        out_v = np.zeros((vert_cap, 3), dtype=np.float64)
+        out_f = np.zeros((face_cap, 3), dtype=np.int64)
+        out_p = np.zeros((max(vert_cap - nv, 1), 2), dtype=np.int64)
+        rc = N.lib().mm_mesh_refine(h, N._ptr(v), nv, N._ptr(f), nf, target, ratio, int(passes), cap_v, vert_cap, face_cap,
+                                    N._ptr(out_v), N._ptr(out_f), N._ptr(out_p), C.byref(rep))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and (rep.n_vertices > vert_cap or rep.n_faces > face_cap):
+            vert_cap, face_cap = int(rep.n_vertices), int(rep.n_faces)
+            continue
+        N.check(rc, "refine_mesh")
+        break
+    report = {k: getattr(rep, k) for k in REFINE_REPORT_KEYS}
+    report["splits_per_pass"] = list(rep.splits_per_pass)
+    report["faces_by_template"] = list(rep.faces_by_template)
+    report["target_edge_length_mm"] = target
+    report["threshold_mm"] = ratio * target
+    report["watertight"] = report["n_open_edges_after"] == 0 and report["n_nonmanifold_edges_after"] == 0
+    new = _with_mesh(mesh, out_v[:rep.n_vertices].copy(), out_f[:rep.n_faces].copy())
+    return new, out_p[:rep.n_vertices - nv].copy(), report
+
+
 def postprocess_stitched_mesh(mesh, *, postprocessing: bool = False, lamb: float = 0.5, nu: float = 0.5,
                               iterations: int = 10, **kw):
     """fixing_functions.py:52-92 by the reference's name and flag.  ``postprocessing=False`` hands the mesh back as it
     is.  ``True`` runs the Taubin smoothing that ends the reference's post-processing (``filter_taubin``); its repair
     and isotropic remesh in front are MeshLab's and not part of this project, so ``target_edge_length_mm`` or
-    ``remesh_iterations`` raise NotImplementedError.  Other keywords go to ``smooth_mesh``."""
+    ``remesh_iterations`` raise NotImplementedError.  Other keywords go to ``smooth_mesh``.  The edge split of that
+    remesh is ``refine_mesh``, to be called in front of this function."""
     for name in ("target_edge_length_mm", "remesh_iterations"):
         if name in kw:
             raise NotImplementedError(f"{name}: the isotropic remesh of the reference's post-processing is not part of "

@@ -264,6 +264,32 @@ hipError_t launch_mesh_ring(const int32_t* off, const int32_t* nb, long long nv,
                             unsigned long long* reached, int* launches, hipStream_t s);
 hipError_t launch_mesh_disp(const double* a, const double* b, long long nv, unsigned long long* max_bits, int* launches,
                             hipStream_t s);
+// mesh refinement (mm_refine_kernels.hip): face = int32 triples, the edge table as weld_edges sizes it.  refine_edges:
+// the table with own[2 s] = the smallest corner id 3 f + j of the slot's edge, slot[3 f + j] = the slot of corner j;
+// refine_marks: own[2 s + 1] = 0 where the edge is marked (longer than thr2; with `all` every edge between different
+// vertices), ~0 where not; counts (refine_counters() words, cleared here) [0..4] = edges between different vertices,
+// open, non-manifold, the bits of the longest squared length, marked; refine_counts: code (nf bytes), tile_sum
+// (refine_tiles(nf) entries) -> exclusive packed offsets, counts[5..7] += faces with 1, 2, 3 marked corners, counts[8..9]
+// = new vertices, children; refine_offsets: foff[f] = the first child of f, the midpoints nv, nv + 1 ... into v_out,
+// their parents into par at (id - nv0), own[2 s + 1] = the midpoint's vertex; refine_edge_list: the marked edges and
+// their squared lengths in order instead; refine_children: out = the children (v: the coordinates with the midpoints)
+size_t     refine_tiles(long long nf);
+int        refine_counters();
+hipError_t launch_refine_edges(const int32_t* face, long long nf, unsigned long long* keys, unsigned int* cnt,
+                               unsigned int* own, int log2_cap, unsigned int* slot, hipStream_t s);
+hipError_t launch_refine_marks(const unsigned long long* keys, const unsigned int* cnt, unsigned int* own, int log2_cap,
+                               const double* v, double thr2, int all, unsigned long long* counts, hipStream_t s);
+hipError_t launch_refine_counts(const unsigned int* slot, const unsigned int* own, long long nf, uint8_t* code,
+                                long long* tile_sum, unsigned long long* counts, hipStream_t s);
+hipError_t launch_refine_offsets(const uint8_t* code, long long nf, const long long* tile_off, const unsigned int* slot,
+                                 const unsigned long long* keys, unsigned int* own, const double* v, long long nv,
+                                 long long nv0, int32_t* foff, double* v_out, int32_t* par, hipStream_t s);
+hipError_t launch_refine_edge_list(const uint8_t* code, long long nf, const long long* tile_off, const unsigned int* slot,
+                                   const unsigned long long* keys, const double* v, int32_t* edges, double* len_sq,
+                                   hipStream_t s);
+hipError_t launch_refine_children(const int32_t* face, long long nf, const uint8_t* code, const int32_t* foff,
+                                  const unsigned int* slot, const unsigned int* own, const double* v, int32_t* out,
+                                  hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

@@ -1,6 +1,6 @@
-// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim _kernels.hip)
-// share, the device-side counterpart of mm_mesh_stage.h: the launch geometry, the 64-bit edge table (the weld and trim
-// files insert, the close and smooth files read, EdgeTable of mm_mesh_stage.h sizes it), the workgroup scan and the two
+// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine
+// _kernels.hip) share, the device-side counterpart of mm_mesh_stage.h: the launch geometry, the 64-bit edge table (the weld, trim
+// and refine files insert, the close and smooth files read, EdgeTable of mm_mesh_stage.h sizes it), the workgroup scan and the two
 // per-wave ballot idioms.  Header-only; internal.
 #pragma once
 
@@ -58,24 +58,29 @@ static __device__ __forceinline__ unsigned long long edge_slot(unsigned long lon
 static __device__ __forceinline__ unsigned int edge_lo(unsigned long long key) { return (unsigned int)(key >> 32); }
 static __device__ __forceinline__ unsigned int edge_hi(unsigned long long key) { return (unsigned int)(key & 0xFFFFFFFFull); }
 
-// the edge u - v of face f: 64-bit atomicCAS on the key, 32-bit atomicAdd on its count; with owners, the first two to
-// arrive leave f << 1 | (f traverses the edge from the smaller to the larger end)
-template <bool kOwners>
-static __device__ __forceinline__ void edge_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
-                                                   unsigned int* __restrict__ own, unsigned long long mask, int shift,
-                                                   int32_t u, int32_t v, unsigned int f)
+// the slot of the undirected edge u - v, taken with a 64-bit atomicCAS on the key where no lane held it yet
+static __device__ __forceinline__ unsigned long long edge_claim(unsigned long long* __restrict__ keys,
+                                                                unsigned long long mask, int shift, int32_t u, int32_t v)
 {
     const unsigned long long key = edge_key(u, v);
     unsigned long long s = edge_slot(key, shift);
     for (;;) {
         const unsigned long long prev = atomicCAS(&keys[s], kEdgeEmpty, key);
-        if (prev == kEdgeEmpty || prev == key) {
-            const unsigned int p = atomicAdd(&cnt[s], 1u);
-            if (kOwners && p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
-            return;
-        }
+        if (prev == kEdgeEmpty || prev == key) return s;
         s = (s + 1) & mask;
     }
+}
+
+// the edge u - v of face f: its slot claimed, 32-bit atomicAdd on its count; with owners, the first two to arrive leave
+// f << 1 | (f traverses the edge from the smaller to the larger end)
+template <bool kOwners>
+static __device__ __forceinline__ void edge_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
+                                                   unsigned int* __restrict__ own, unsigned long long mask, int shift,
+                                                   int32_t u, int32_t v, unsigned int f)
+{
+    const unsigned long long s = edge_claim(keys, mask, shift, u, v);
+    const unsigned int p = atomicAdd(&cnt[s], 1u);
+    if (kOwners && p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
 }
 
 // ---- scans ----
