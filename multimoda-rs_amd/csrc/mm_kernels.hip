@@ -986,21 +986,30 @@ int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 //   2. every other tile, unless thr(I, J) >= max(Umax_I, Vmax_J), with Umax_I the largest row minimum of row tile I and
 //      Vmax_J the largest column minimum of column tile J after phase 1 (integer order on the f32 bits, as every minimum
 //      here is taken).  A row tile with nothing left after phase 1 is final: its largest row minimum is Umax_I.
-// The bookkeeping has no serial cross-lane step per row tile: thr of all tile pairs is computed one pair per lane into a
-// wave-private table; lane I then builds row tile I's two masks in-lane from that table, from its row minima in the row
-// store and from the column maxima published in LDS; the phase loops only read the wave-uniform mask of a row tile
-// (v_readlane) and run its tiles, the next row tile's A fragment already requested.
+// The bookkeeping has no serial cross-lane step per row tile: lane (h, J) computes thr of column tile J (its centre rotated
+// once) against the row tiles 2 p + h, two row tiles per pass, into a wave-private table; a pass's close tiles (thr <= 0)
+// are one ballot whose halves are the phase-1 masks of its two row tiles, and each lane keeps its column's nearest row
+// tile on the way (the two halves meet once).  Lane I then builds row tile I's phase-2 mask in-lane from its table row,
+// from its row minima in the row store and from the column maxima published in LDS.  The phase loops read the
+// wave-uniform mask of a row tile (v_readlane) and visit its SET bits only (s_ff1), the next row tile's A fragment already
+// requested; the column tile's B fragment and running minimum are reached by the uniform index (an indexed register
+// move, s_set_gpr_idx), so a tile that is not computed costs nothing.
 // Why the value is bit-identical to the full kernel's: a skipped tile's values v are >= thr > 0; every row r of tile I has
 // a current minimum m_r <= Umax_I <= thr <= v (minima only decrease, so the phase-1 maximum stays an upper bound), so v
 // cannot become r's minimum, and the same for every column of J with Vmax_J.  Every row and column minimum is therefore
 // the minimum over all 32 x NCT (resp. 32 x nrt) values, which is what the full kernel computes, and so is their maximum.
 // (A positive f32 compares like its bits as an integer; a negative minimum -- rounding below 0 for coincident points --
 // is below every positive threshold in that order too.)  The mask of a row tile is wave-uniform (one candidate per
-// wave): a scalar bit test and a branch per tile.
+// wave): one scalar loop over its set bits.
 // -------------------------------------------------------------------------------------
 typedef float f16x16 __attribute__((ext_vector_type(16)));
 
 static constexpr int MXC_ROW_TILES_MAX = 17;
+// Column tiles from which the culled screen loops over the set mask bits; below it keeps the bit-test chain and one tile
+// pair per lane.  The static budget (profiles/r6_cull_isa_budget.txt) has the loop cheaper from 9 column tiles on (a register
+// vector of fewer is indexed by compare and select) and dearer below; on the device it was measured to win at 17 and to lose
+// on the small launches at 16 (profiles/r6_config3_cull_kernel_stats.csv), so only 17 takes it.
+static constexpr int MXC_SETBIT_MIN_NCT = 17;
 
 static __device__ __forceinline__ int min3i(int a, int b, int c) { return min(a, min(b, c)); }
 
@@ -1032,16 +1041,55 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
     return r0 > r1 ? r0 : r1;
 }
 
-// the tiles of `mask` for one row tile (A fragment af): their column minima into cm, their row minima into rmin -- per tile
+// Section marks for tools/count_cull_isa.py: a comment line in the assembly, no instruction.  "<name>:<trips>" -- the
+// section's instructions run once per <trips> (1, nrt, rows2, half, tiles; "tile" is a computed tile's own body).
+#define MXC_MARK(s) __asm__ volatile("; mxc:" s)
+#define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
+
+// one register per column tile, indexed by the wave-uniform tile index (a uniform index into a register vector is an
+// indexed register move, no branch per tile)
+template <int N> struct mxc_regs { typedef int type __attribute__((ext_vector_type(N))); };
+typedef int mxc_i4 __attribute__((ext_vector_type(4)));
+
+// the tiles of `mask` for one row tile (A fragment af): their column minima into cm, their row minima into rmin -- a loop
+// over the SET bits of the wave-uniform mask (its cost is per computed tile, not per column tile); per tile D = A.B and
+// D' = B.A, both MFMAs in flight before the minima.  (blo, bhi): the two dwords of every column tile's B fragment.
+template <int NCT, int PH>
+static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, const typename mxc_regs<NCT>::type& blo,
+                                                 const typename mxc_regs<NCT>::type& bhi, typename mxc_regs<NCT>::type& cm, int& rmin)
+{
+    const f16x16 z = {};
+    while (mask) {
+        MXC_MARK("tloop:tiles");
+        const int t = __builtin_ctz(mask);
+        mask &= mask - 1;
+        // a column fragment's K slots 4..7 repeat its slots 0..3 (mx_col_coords / mx_col_norm): kept as 8 bytes, widened here
+        const int lo = blo[t], hi = bhi[t];
+        const h8v b = __builtin_bit_cast(h8v, mxc_i4{lo, hi, lo, hi});
+        int c0 = cm[t];
+        MXC_MARK_V("tile", c0);
+        const f16x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, z, 0, 0, 0);
+        const f16x16 e = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, af, z, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        int c1 = mxc_fold(c0, d);
+        rmin = mxc_fold(rmin, e);
+        MXC_MARK_V("tloop:tiles", c1);
+        cm[t] = c1;
+    }
+    if constexpr (PH == 1) MXC_MARK_V("p1_row:nrt", rmin); else MXC_MARK_V("p2_row:rows2", rmin);
+}
+
+// the same by a bit test and a branch per column tile in front of NCT unrolled bodies (A fragment af): their column minima into cm, their row minima into rmin -- per tile
 // D = A.B and D' = B.A, both MFMAs in flight before the minima
-template <int NCT>
-static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, const h4v (&bh)[NCT], int (&cm)[NCT], int& rmin)
+template <int NCT, int PH>
+static __device__ __forceinline__ void mxc_tiles_chain(unsigned mask, const h8v& af, const h4v (&bh)[NCT], int (&cm)[NCT], int& rmin)
 {
     const f16x16 z = {};
 #pragma unroll
     for (int t = 0; t < NCT; ++t) {
         if ((mask >> t) & 1) {
             // a column fragment's K slots 4..7 repeat its slots 0..3 (mx_col_coords / mx_col_norm): kept as 8 bytes, widened here
+            MXC_MARK("tile");
             const h4v v = bh[t];
             const h8v b = h8v{v[0], v[1], v[2], v[3], v[0], v[1], v[2], v[3]};
             const f16x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, z, 0, 0, 0);
@@ -1049,6 +1097,7 @@ static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, c
             __builtin_amdgcn_sched_barrier(0);
             cm[t] = mxc_fold(cm[t], d);
             rmin = mxc_fold(rmin, e);
+            if constexpr (PH == 1) MXC_MARK("p1_row:nrt"); else MXC_MARK("p2_row:rows2");
         }
     }
 }
@@ -1065,7 +1114,8 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                  const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
                  const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done)
 {
-    constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128;
+    constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128, VM = 40, NT4 = (NCT + 3) / 4;
+    typedef typename mxc_regs<NCT>::type regs_t;
     extern __shared__ __align__(16) unsigned char smem[];
     h8v* s_a = reinterpret_cast<h8v*>(smem);                          // [a_cap][64] row fragments of the pair (all waves)
     h4v* s_bw = reinterpret_cast<h4v*>(s_a + a_cap * 64);            // [WAVES][NCT][64] column fragments of the wave's candidate
@@ -1122,125 +1172,300 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
         for (int k = wave; k < w.cnt; k += WAVES) {
             const float c = s_cs[2 * k], s = s_cs[2 * k + 1];
             const int a = s_ci[k];
+            if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
+                MXC_MARK("setup:1");
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int j = lane + 64 * q;
-                if (j < NB) {
-                    const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
-                    const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
-                    s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                for (int q = 0; q < NQ; ++q) {
+                    const int j = lane + 64 * q;
+                    if (j < NB) {
+                        const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
+                        const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
+                        s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                    }
                 }
-            }
-            // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
-            __asm__ volatile("" ::: "memory");
-            h4v bf[NCT];
+                // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
+                __asm__ volatile("" ::: "memory");
+                regs_t blo, bhi;
 #pragma unroll
-            for (int t = 0; t < NCT; ++t) bf[t] = s_b[t * 64 + lane];
-            __asm__ volatile("" ::: "memory");
+                for (int t = 0; t < NCT; ++t) {
+                    const int2 v = reinterpret_cast<const int2*>(s_b)[t * 64 + lane];
+                    blo[t] = v.x; bhi[t] = v.y;
+                }
+                __asm__ volatile("" ::: "memory");
 
-            // ---- thr(I, J) of every tile pair, one pair per lane (no cross-lane step, the loads of a pass issued together) ----
-            for (int p = lane; p < nrt * NCT; p += 64) {
-                const int I = p / NCT, J = p - I * NCT;
-                const float4 rc = s_circ[NCT + I], cc = s_circ[J];
-                const float bx = __builtin_fmaf(cc.x, c, -(cc.y * s)), by = __builtin_fmaf(cc.x, s, cc.y * c);
-                s_th[I * 32 + J] = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, bx, by, cc.z), e2s);
-            }
-            __asm__ volatile("" ::: "memory");
-            // lane I (< nrt): phase-1 mask of row tile I -- every tile with thr <= 0, else the one with the smallest thr.
-            // lane 32 + J (J < NCT): column tile J's nearest row tile when none of its tiles has thr <= 0
-            unsigned m1 = 0;
-            int lone_i = -1;
-            if (lane < nrt) {
-                float best = __builtin_inff();
-                int bj = 0;
-#pragma unroll
-                for (int J = 0; J < NCT; ++J) {
-                    const float t = s_th[lane * 32 + J];
-                    if (!(t > 0.0f)) m1 |= 1u << J;
-                    if (t < best) { best = t; bj = J; }
+                // ---- thr(I, J) of every tile pair: lane (h, J) takes column tile J (its centre rotated once) against the row
+                // tiles 2 p + h, two row tiles per pass (the next pass's row circle already requested).  A pass's close tiles
+                // (thr <= 0) are one ballot: its two halves are the phase-1 masks of row tiles 2 p and 2 p + 1, kept by lanes
+                // 2 p and 2 p + 1.  Each lane keeps its column's nearest row tile on the way (no second sweep over the table).
+                MXC_MARK("thr:1");
+                const int hw = lane >> 5;
+                const bool jok = l32 < NCT;
+                const float4 cc = s_circ[jok ? l32 : NCT - 1];
+                const float cbx = __builtin_fmaf(cc.x, c, -(cc.y * s)), cby = __builtin_fmaf(cc.x, s, cc.y * c);
+                unsigned m1 = 0;
+                float ckey = __builtin_inff();                               // the column's smallest thr so far, -1 once a tile is close
+                int cbi = 0;
+                float4 rc = s_circ[NCT + (hw < nrt ? hw : nrt - 1)];
+                for (int p = 0; 2 * p < nrt; ++p) {
+                    MXC_MARK("thr_pass:half");
+                    const int I = 2 * p + hw;
+                    const float4 rn = s_circ[NCT + (I + 2 < nrt ? I + 2 : nrt - 1)];
+                    const bool ok = jok && I < nrt;
+                    const float t = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, cbx, cby, cc.z), e2s);
+                    if (ok) s_th[I * 32 + l32] = t;
+                    const bool close = ok && !(t > 0.0f);
+                    const unsigned long long bal = __builtin_amdgcn_ballot_w64(close);
+                    m1 = lane == 2 * p ? (unsigned)bal : lane == 2 * p + 1 ? (unsigned)(bal >> 32) : m1;
+                    if (close) ckey = -1.0f;
+                    else if (ok && t < ckey) { ckey = t; cbi = I; }         // (ascending I, strict: the smallest I of equal thr)
+                    rc = rn;
                 }
-                if (!m1) m1 = 1u << bj;
-            } else if (lane >= 32 && lane - 32 < NCT) {
-                const int J = lane - 32;
-                bool cov = false;
-                float best = __builtin_inff();
-                int bi = 0;
+                MXC_MARK("m1:1");
+                __asm__ volatile("" ::: "memory");
+                // lane I (< nrt) without a close tile: the tile with the smallest thr of its row
+                if (lane < nrt && !m1) {
+                    const float4* q = reinterpret_cast<const float4*>(s_th + lane * 32);
+                    float th[NT4 * 4];
+#pragma unroll
+                    for (int u = 0; u < NT4; ++u) { const float4 w4 = q[u]; th[4 * u] = w4.x; th[4 * u + 1] = w4.y; th[4 * u + 2] = w4.z; th[4 * u + 3] = w4.w; }
+                    float best = __builtin_inff();
+                    int bj = 0;
+#pragma unroll
+                    for (int J = 0; J < NCT; ++J)
+                        if (th[J] < best) { best = th[J]; bj = J; }
+                    m1 = 1u << bj;
+                }
+                // column tile J without a close tile: its nearest row tile.  The halves (even and odd row tiles) meet; both
+                // halves of lane pair J then hold the same answer, the lower half's lanes report it
+                int lone_i = -1;
+                {
+                    const auto kk = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(ckey), (unsigned)__float_as_int(ckey), false, false);
+                    const auto ii = __builtin_amdgcn_permlane32_swap((unsigned)cbi, (unsigned)cbi, false, false);
+                    const float k0 = __int_as_float((int)kk[0]), k1 = __int_as_float((int)kk[1]);
+                    const int i0 = (int)ii[0], i1 = (int)ii[1];
+                    if (lane < NCT && k0 > 0.0f && k1 > 0.0f) lone_i = k1 < k0 ? i1 : k1 == k0 ? min(i0, i1) : i0;
+                }
+                for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
+                    const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
+                    if (lane == I) m1 |= 1u << L;
+                }
+
+                // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
+                MXC_MARK("p1_init:1");
+                regs_t cm;
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
+                h8v af = s_a[lane];
                 for (int I = 0; I < nrt; ++I) {
-                    const float t = s_th[I * 32 + J];
-                    cov = cov || !(t > 0.0f);
-                    if (t < best) { best = t; bi = I; }
+                    MXC_MARK("p1_row:nrt");
+                    const unsigned mask = __builtin_amdgcn_readlane(m1, I);
+                    const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
+                    int rmin = 0x7f800000;
+                    mxc_tiles<NCT, 1>(mask, af, blo, bhi, cm, rmin);
+                    rmin = mxc_meet(rmin);
+                    if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                    done += __builtin_popcount(mask);
+                    af = an;
                 }
-                lone_i = cov ? -1 : bi;
-            }
-            for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
-                const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
-                if (lane == I) m1 |= 1u << (L - 32);
-            }
-
-            // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
-            int cm[NCT];
+                // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
+                MXC_MARK("vmax:1");
 #pragma unroll
-            for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
-            h8v af = s_a[lane];
-            for (int I = 0; I < nrt; ++I) {
-                const unsigned mask = __builtin_amdgcn_readlane(m1, I);
-                const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
-                int rmin = 0x7f800000;
-                mxc_tiles<NCT>(mask, af, bf, cm, rmin);
-                rmin = mxc_meet(rmin);
-                if (lane < 32) s_rs[I * 32 + lane] = rmin;
-                done += __builtin_popcount(mask);
-                af = an;
-            }
-            // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
-#pragma unroll
-            for (int t = 0; t < NCT; ++t) {
-                cm[t] = mxc_meet(cm[t]);
-                if (lane < 32) s_v[t * VS + lane] = cm[t];
-            }
-            __asm__ volatile("" ::: "memory");
-            if (lane < NCT) {
-                const int4* q = reinterpret_cast<const int4*>(s_v + lane * VS);
-                int v = (int)0x80000000;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; v = max(v, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
-                s_v[lane * VS + 40] = v;                                  // (inside the coordinate half, past the 32 minima)
-            }
-            __asm__ volatile("" ::: "memory");
-            // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
-            unsigned m2 = 0;
-            int rowmax = 0;
-            if (lane < nrt) {
-                const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
-                int umax = (int)0x80000000;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
-#pragma unroll
-                for (int J = 0; J < NCT; ++J) {
-                    const float t = s_th[lane * 32 + J];
-                    const int lim = max(umax, s_v[J * VS + 40]);
-                    if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
+                for (int t = 0; t < NCT; ++t) {
+                    cm[t] = mxc_meet(cm[t]);
+                    if (lane < 32) s_v[t * VS + lane] = cm[t];
                 }
-                m2 &= ~m1;
-                if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
-            }
-
-            // ---- phase 2: only the row tiles with tiles left ----
-            for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
-                const int I = __builtin_ctzll(rows);
-                const unsigned mask = __builtin_amdgcn_readlane(m2, I);
-                const h8v ai = s_a[I * 64 + lane];
-                int rmin = s_rs[I * 32 + l32];
-                mxc_tiles<NCT>(mask, ai, bf, cm, rmin);
-                rmin = mxc_meet(rmin);
-                done += __builtin_popcount(mask);
-                rowmax = max(rowmax, rmin);
-            }
-            int m = rowmax;
+                __asm__ volatile("" ::: "memory");
+                if (lane < NCT) {
+                    const int4* q = reinterpret_cast<const int4*>(s_v + lane * VS);
+                    int v = (int)0x80000000;
 #pragma unroll
-            for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
-            m = wave_max_i32_dpp(m);
-            if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                    for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; v = max(v, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+                    s_v[VM + lane] = v;                                       // (column tile 0's coordinate half, past its 32 minima)
+                }
+                __asm__ volatile("" ::: "memory");
+                // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
+                MXC_MARK("m2:1");
+                unsigned m2 = 0;
+                int rowmax = 0;
+                if (lane < nrt) {
+                    const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
+                    int umax = (int)0x80000000;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+                    const float4* qt = reinterpret_cast<const float4*>(s_th + lane * 32);
+                    const int4* qv = reinterpret_cast<const int4*>(s_v + VM);
+                    float th[NT4 * 4];
+                    int vm[NT4 * 4];
+#pragma unroll
+                    for (int u = 0; u < NT4; ++u) {
+                        const float4 w4 = qt[u]; th[4 * u] = w4.x; th[4 * u + 1] = w4.y; th[4 * u + 2] = w4.z; th[4 * u + 3] = w4.w;
+                        const int4 v4 = qv[u]; vm[4 * u] = v4.x; vm[4 * u + 1] = v4.y; vm[4 * u + 2] = v4.z; vm[4 * u + 3] = v4.w;
+                    }
+#pragma unroll
+                    for (int J = 0; J < NCT; ++J) {
+                        const float t = th[J];
+                        const int lim = max(umax, vm[J]);
+                        if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
+                    }
+                    m2 &= ~m1;
+                    if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
+                }
+
+                // ---- phase 2: only the row tiles with tiles left ----
+                for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
+                    MXC_MARK("p2_row:rows2");
+                    const int I = __builtin_ctzll(rows);
+                    const unsigned mask = __builtin_amdgcn_readlane(m2, I);
+                    const h8v ai = s_a[I * 64 + lane];
+                    int rmin = s_rs[I * 32 + l32];
+                    mxc_tiles<NCT, 2>(mask, ai, blo, bhi, cm, rmin);
+                    rmin = mxc_meet(rmin);
+                    done += __builtin_popcount(mask);
+                    rowmax = max(rowmax, rmin);
+                }
+                MXC_MARK("final:1");
+                int m = rowmax;
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
+                m = wave_max_i32_dpp(m);
+                if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                MXC_MARK("end:0");
+            } else {
+                // fewer column tiles: the bit-test chain in front of unrolled tile bodies and one tile pair per lane are
+                // cheaper there (profiles/r6_cull_isa_budget.txt)
+                MXC_MARK("setup:1");
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const int j = lane + 64 * q;
+                    if (j < NB) {
+                        const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
+                        const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
+                        s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                    }
+                }
+                // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
+                __asm__ volatile("" ::: "memory");
+                h4v bf[NCT];
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) bf[t] = s_b[t * 64 + lane];
+                __asm__ volatile("" ::: "memory");
+
+                // ---- thr(I, J) of every tile pair, one pair per lane (no cross-lane step, the loads of a pass issued together) ----
+                MXC_MARK("thr:1");
+                for (int p = lane; p < nrt * NCT; p += 64) {
+                    MXC_MARK("thr_pass:pairs64");
+                    const int I = p / NCT, J = p - I * NCT;
+                    const float4 rc = s_circ[NCT + I], cc = s_circ[J];
+                    const float bx = __builtin_fmaf(cc.x, c, -(cc.y * s)), by = __builtin_fmaf(cc.x, s, cc.y * c);
+                    s_th[I * 32 + J] = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, bx, by, cc.z), e2s);
+                }
+                __asm__ volatile("" ::: "memory");
+                // lane I (< nrt): phase-1 mask of row tile I -- every tile with thr <= 0, else the one with the smallest thr.
+                // lane 32 + J (J < NCT): column tile J's nearest row tile when none of its tiles has thr <= 0
+                MXC_MARK("m1:1");
+                unsigned m1 = 0;
+                int lone_i = -1;
+                if (lane < nrt) {
+                    float best = __builtin_inff();
+                    int bj = 0;
+#pragma unroll
+                    for (int J = 0; J < NCT; ++J) {
+                        const float t = s_th[lane * 32 + J];
+                        if (!(t > 0.0f)) m1 |= 1u << J;
+                        if (t < best) { best = t; bj = J; }
+                    }
+                    if (!m1) m1 = 1u << bj;
+                } else if (lane >= 32 && lane - 32 < NCT) {
+                    const int J = lane - 32;
+                    bool cov = false;
+                    float best = __builtin_inff();
+                    int bi = 0;
+                    for (int I = 0; I < nrt; ++I) {
+                        MXC_MARK("lone_loop:nrt");
+                        const float t = s_th[I * 32 + J];
+                        cov = cov || !(t > 0.0f);
+                        if (t < best) { best = t; bi = I; }
+                    }
+                    MXC_MARK("m1:1");
+                    lone_i = cov ? -1 : bi;
+                }
+                for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
+                    const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
+                    if (lane == I) m1 |= 1u << (L - 32);
+                }
+
+                // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
+                MXC_MARK("p1_init:1");
+                int cm[NCT];
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
+                h8v af = s_a[lane];
+                for (int I = 0; I < nrt; ++I) {
+                    MXC_MARK("p1_row:nrt");
+                    const unsigned mask = __builtin_amdgcn_readlane(m1, I);
+                    const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
+                    int rmin = 0x7f800000;
+                    mxc_tiles_chain<NCT, 1>(mask, af, bf, cm, rmin);
+                    rmin = mxc_meet(rmin);
+                    if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                    done += __builtin_popcount(mask);
+                    af = an;
+                }
+                MXC_MARK("vmax:1");
+                // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    cm[t] = mxc_meet(cm[t]);
+                    if (lane < 32) s_v[t * VS + lane] = cm[t];
+                }
+                __asm__ volatile("" ::: "memory");
+                if (lane < NCT) {
+                    const int4* q = reinterpret_cast<const int4*>(s_v + lane * VS);
+                    int v = (int)0x80000000;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; v = max(v, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+                    s_v[lane * VS + 40] = v;                                  // (inside the coordinate half, past the 32 minima)
+                }
+                __asm__ volatile("" ::: "memory");
+                // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
+                MXC_MARK("m2:1");
+                unsigned m2 = 0;
+                int rowmax = 0;
+                if (lane < nrt) {
+                    const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
+                    int umax = (int)0x80000000;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+#pragma unroll
+                    for (int J = 0; J < NCT; ++J) {
+                        const float t = s_th[lane * 32 + J];
+                        const int lim = max(umax, s_v[J * VS + 40]);
+                        if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
+                    }
+                    m2 &= ~m1;
+                    if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
+                }
+
+                // ---- phase 2: only the row tiles with tiles left ----
+                for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
+                    MXC_MARK("p2_row:rows2");
+                    const int I = __builtin_ctzll(rows);
+                    const unsigned mask = __builtin_amdgcn_readlane(m2, I);
+                    const h8v ai = s_a[I * 64 + lane];
+                    int rmin = s_rs[I * 32 + l32];
+                    mxc_tiles_chain<NCT, 2>(mask, ai, bf, cm, rmin);
+                    rmin = mxc_meet(rmin);
+                    done += __builtin_popcount(mask);
+                    rowmax = max(rowmax, rmin);
+                }
+                MXC_MARK("final:1");
+                int m = rowmax;
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
+                m = wave_max_i32_dpp(m);
+                if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                MXC_MARK("end:0");
+            }
         }
     }
     if (tiles_done && lane == 0 && done) atomicAdd(tiles_done, done);

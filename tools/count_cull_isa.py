@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Static instruction budget of k_screen_mx_cull<NCT>, counted from the compiler's assembly (no GPU).
+
+    hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -Imultimoda-rs_amd/csrc \\
+          --cuda-device-only -S multimoda-rs_amd/csrc/mm_kernels.hip -o mm_kernels.s
+    python tools/count_cull_isa.py mm_kernels.s --nct 17 --nrt 17 --tiles 60
+
+The kernel's candidate loop carries section marks, comment lines `; mxc:<name>:<trips>` that emit no instruction.  Every
+instruction line after a mark belongs to that section, in the TEXT order of the assembly (the compiler may place a block
+away from its source position: a few instructions land in a neighbouring section; the sums are not affected).  <trips> says
+how often the section runs per candidate:
+
+    1        once                       nrt      once per row tile            half     once per two row tiles
+    rows2    once per row tile that has tiles left in phase 2 (--rows2, default nrt: the upper bound)
+    pairs64  once per 64 tile pairs     tiles    once per computed tile (summed over the copies, divided by their number)
+    0        not in the candidate loop
+
+and a section named `tile` is a computed tile's own body (its copies are averaged; every v_mfma counts to it).  A section
+ends at the next mark or at an unconditional branch; instructions between such a branch and the next mark are listed as
+`unmarked` and not charged.  Instructions are classified by the
+mnemonic's prefix only: v_mfma, other v_, s_, ds_, global_/flat_/buffer_.  The estimate counts every instruction of a section
+as executed, also those a branch skips (rare paths are charged in full), and leaves out the `unmarked` blocks, some of which
+the compiler moved out of the candidate loop's text (register-vector copies at a loop exit, for instance): it is a count for
+comparing two builds of the kernel section by section, neither a bound nor a time.
+"""
+import argparse
+import re
+import sys
+from collections import OrderedDict
+
+CLASSES = ("mfma", "valu", "salu", "lds", "vmem", "other")
+
+
+def classify(mn):
+    if mn.startswith("v_mfma"):
+        return "mfma"
+    if mn.startswith("v_"):
+        return "valu"
+    if mn.startswith("s_"):
+        return "salu"
+    if mn.startswith("ds_"):
+        return "lds"
+    if mn.startswith(("global_", "flat_", "buffer_")):
+        return "vmem"
+    return "other"
+
+
+def kernels(text):
+    """{NCT: (body lines, info lines)} of every k_screen_mx_cull<NCT> in the assembly."""
+    out = {}
+    lines = text.splitlines()
+    i = 0
+    head = re.compile(r"^(_Z\w*k_screen_mx_cullILi(\d+)E\w*):")
+    while i < len(lines):
+        m = head.match(lines[i])
+        if not m:
+            i += 1
+            continue
+        nct = int(m.group(2))
+        j = i + 1
+        while j < len(lines) and not lines[j].startswith(".Lfunc_end"):
+            j += 1
+        k = j
+        while k < len(lines) and k < j + 400 and not head.match(lines[k]) and not lines[k].startswith("; Occupancy"):
+            k += 1
+        k = min(k + 1, len(lines))
+        out[nct] = (lines[i + 1:j], lines[j:k])
+        i = k
+    return out
+
+
+def info(lines, key):
+    for ln in lines:
+        m = re.match(r"^;\s*" + re.escape(key) + r":\s*(\d+)", ln)
+        if m:
+            return int(m.group(1))
+    return None
+
+
+def sections(body):
+    """OrderedDict name -> {"trips": str, "entries": int, class: count}; the code before the first mark is `item`."""
+    secs = OrderedDict()
+
+    def sec(name, trips):
+        if name not in secs:
+            secs[name] = dict(trips=trips, entries=0, **{c: 0 for c in CLASSES})
+        return secs[name]
+
+    cur = sec("item", "0")
+    for ln in body:
+        m = re.search(r";\s*mxc:([A-Za-z0-9_]+)(?::([A-Za-z0-9_]+))?", ln)
+        if m:
+            cur = sec(m.group(1), m.group(2) or ("tile" if m.group(1) == "tile" else "1"))
+            cur["entries"] += 1
+            continue
+        m = re.match(r"^\s+([a-z][a-z0-9_]*)\b", ln)
+        if not m or ln.lstrip().startswith((".", ";")):
+            continue
+        mn, cl = m.group(1), classify(m.group(1))
+        (sec("tile", "tile") if cl == "mfma" else cur)[cl] += 1      # (the scheduler may lift a tile's MFMAs above its mark)
+        if mn in ("s_branch", "s_endpgm") or mn.startswith("s_setpc"):
+            cur = sec("unmarked", "0")                               # no fall-through: what follows is another block
+    return secs
+
+
+def report(nct, body, inf, nrt, tiles, rows2, out):
+    secs = sections(body)
+    copies = max(1, secs["tile"]["entries"]) if "tile" in secs else 1
+    trips = {"0": 0.0, "1": 1.0, "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
+             "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles / copies, "tile": tiles / copies}
+    out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (
+        nct, info(inf, "NumVgprs"), info(inf, "NumAgprs"), info(inf, "ScratchSize"), info(inf, "Occupancy")))
+    out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g; tile bodies in the code: %d\n" % (
+        nrt, nct, tiles, rows2, copies))
+    out.write("  %-10s %-8s %6s %6s %6s %6s %6s %6s %7s %9s\n" % ("section", "trips", "mfma", "valu", "salu", "lds", "vmem",
+                                                                  "other", "static", "executed"))
+    tot_tile = tot_rest = 0.0
+    for name, s in secs.items():
+        static = sum(s[c] for c in CLASSES)
+        if s["trips"] not in trips:
+            raise SystemExit("unknown trip count %r in mark %r" % (s["trips"], name))
+        ex = static * trips[s["trips"]]
+        if name == "tile":
+            tot_tile += ex
+        else:
+            tot_rest += ex
+        out.write("  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.0f\n" % (name, s["trips"], s["mfma"], s["valu"], s["salu"], s["lds"],
+                                                                       s["vmem"], s["other"], static, ex))
+    if "tile" in secs:
+        out.write("  a computed tile's body: %.1f instructions\n" % (sum(secs["tile"][c] for c in CLASSES) / copies))
+    out.write("  executed per candidate: tiles %.0f, everything else %.0f\n\n" % (tot_tile, tot_rest))
+    return tot_tile, tot_rest
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("asm", help="assembly of mm_kernels.hip (hipcc ... -S --cuda-device-only)")
+    ap.add_argument("--nct", type=int, default=17, help="column tiles: which k_screen_mx_cull<NCT> (0: all)")
+    ap.add_argument("--nrt", type=int, default=17, help="row tiles of the pair")
+    ap.add_argument("--tiles", type=float, default=60, help="tiles computed per candidate")
+    ap.add_argument("--rows2", type=float, default=None, help="row tiles with tiles left in phase 2 (default: nrt)")
+    a = ap.parse_args(argv)
+    with open(a.asm) as f:
+        ks = kernels(f.read())
+    if not ks:
+        raise SystemExit("no k_screen_mx_cull in " + a.asm)
+    for nct in sorted(ks):
+        if a.nct and nct != a.nct:
+            continue
+        body, inf = ks[nct]
+        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout)
+
+
+if __name__ == "__main__":
+    main()
