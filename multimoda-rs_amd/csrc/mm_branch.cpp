@@ -8,12 +8,10 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {
-
-struct BranchClPointH { double x, y, z; uint64_t bit; };   // BranchClPoint in mm_branch_kernels.hip
 
 int branch_masks(mm_engine* h, const mm_clpoint* cl, int64_t ncl, const double* pts, int64_t n, double radius,
                  uint64_t* masks, const char* who)
@@ -28,26 +26,20 @@ int branch_masks(mm_engine* h, const mm_clpoint* cl, int64_t ncl, const double* 
         if (cl[k].branch_id >= MM_BRANCH_MASK_BITS)
             return set_error(MM_ERR_INVALID, std::string(who) + ": branch_id " + std::to_string(cl[k].branch_id) +
                                                  " does not fit a mask of " + std::to_string(MM_BRANCH_MASK_BITS) + " branches");
-    if ((size_t)branch_cl_point_bytes() != sizeof(BranchClPointH))
-        return set_error(MM_ERR_INVALID, std::string(who) + ": packed centerline point size mismatch");
-    const size_t o_cl = up256((size_t)n * 24), in_bytes = up256(o_cl + (size_t)ncl * sizeof(BranchClPointH));
-    const size_t o_mask = in_bytes, total = up256(o_mask + (size_t)n * 8);
-    if ((rc = e->ensure(e->host_pts, std::max(in_bytes, (size_t)n * 8), true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* hp = (unsigned char*)e->host_pts.p;
-    std::memcpy(hp, pts, (size_t)n * 24);
-    BranchClPointH* hc = (BranchClPointH*)(hp + o_cl);
-    for (int64_t k = 0; k < ncl; ++k) hc[k] = BranchClPointH{cl[k].x, cl[k].y, cl[k].z, (uint64_t)1 << cl[k].branch_id};
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->profile_begin(e->stream))) return rc;
-    const hipError_t he = launch_branch_mask((const double*)d, n, d + o_cl, (int)ncl, radius * radius,   // label_coronary.rs:226
-                                             (unsigned long long*)(d + o_mask), e->stream);
-    if (he != hipSuccess) return hip_error(he, "branch mask launch");
-    if ((rc = e->profile_end(e->stream, (double)n * (double)ncl, 0))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(hp, d + o_mask, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    std::memcpy(masks, hp, (size_t)n * 8);
+    StagedPass sp;
+    const size_t o_pts = sp.in.take((size_t)n * 24), o_cl = sp.in.take((size_t)ncl * sizeof(BranchClPoint));
+    const size_t o_mask = sp.out.take((size_t)n * 8);
+    if ((rc = sp.reserve(e))) return rc;
+    std::memcpy(sp.host<double>(o_pts), pts, (size_t)n * 24);
+    BranchClPoint* hc = sp.host<BranchClPoint>(o_cl);
+    for (int64_t k = 0; k < ncl; ++k) hc[k] = BranchClPoint{cl[k].x, cl[k].y, cl[k].z, 1ull << cl[k].branch_id};
+    rc = sp.run((double)n * (double)ncl, "branch mask launch", [&] {
+        return launch_branch_mask(sp.dev_in<double>(o_pts), n, sp.dev_in<BranchClPoint>(o_cl), (int)ncl,
+                                  radius * radius,   // label_coronary.rs:226
+                                  sp.dev_out<unsigned long long>(o_mask), e->stream);
+    });
+    if (rc) return rc;
+    std::memcpy(masks, sp.host<uint64_t>(o_mask), (size_t)n * 8);
     return MM_OK;
 }
 

@@ -28,8 +28,6 @@ namespace mm {
 static constexpr int kBranchTile = 1024;    // centerline points per LDS tile (1024 x 32 B = 32 KiB)
 static constexpr int kBranchLanes = 256;    // mesh points per block
 
-struct alignas(32) BranchClPoint { double x, y, z; unsigned long long bit; };
-
 // pts: n xyz triples; cl: m packed centerline points; mask: n words
 __global__ void __launch_bounds__(256)
 k_branch_mask(const double* __restrict__ pts, long long n, const BranchClPoint* __restrict__ cl, int m, double r2,
@@ -57,15 +55,14 @@ k_branch_mask(const double* __restrict__ pts, long long n, const BranchClPoint* 
     if (i < n) mask[i] = acc;
 }
 
-int branch_cl_point_bytes() { return (int)sizeof(BranchClPoint); }
 int branch_tile_points() { return kBranchTile; }
 
-hipError_t launch_branch_mask(const double* pts, long long n, const void* cl, int m, double r2, unsigned long long* mask,
-                              hipStream_t s)
+hipError_t launch_branch_mask(const double* pts, long long n, const BranchClPoint* cl, int m, double r2,
+                              unsigned long long* mask, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_branch_mask, dim3((unsigned)((n + kBranchLanes - 1) / kBranchLanes)), dim3(kBranchLanes), 0, s,
-                       pts, n, (const BranchClPoint*)cl, m, r2, mask);
+                       pts, n, cl, m, r2, mask);
     return hipGetLastError();
 }
 

@@ -9,12 +9,10 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_device.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {
-
-struct BsplJobH { int32_t p_off, m; };   // BsplJob in mm_bspline_kernels.hip
 
 // numpy's pairwise sum of n doubles `stride` apart: fewer than 8 one after the other; up to 128 in eight accumulators
 // combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the rest one after the other; longer arrays split at n/2 rounded down
@@ -82,7 +80,7 @@ int mm_bspline_fit_closed_batch(mm_engine* h, int64_t n_contours, const double* 
         return set_error(MM_ERR_TOO_LARGE, "mm_bspline_fit_closed_batch: the longest contour's system does not fit the "
                                            "device's LDS per block");
     // from here on the outputs are written.  Unchanged contours: the input, fp 0, no knots.
-    std::vector<BsplJobH> jobs;
+    std::vector<BsplJob> jobs;
     std::vector<int> job_of;                       // contour of each job
     for (int j = 0; j < nc; ++j) {
         const int64_t lo = offsets[j], m = offsets[j + 1] - lo;
@@ -94,44 +92,35 @@ int mm_bspline_fit_closed_batch(mm_engine* h, int64_t n_contours, const double* 
         for (int64_t i = 3 * lo; i < 3 * (lo + m); ++i) finite = finite && std::isfinite(xyz[i]);
         if (!finite) { out_status[j] = MM_BSPLINE_UNCHANGED_NONFINITE; continue; }
         out_status[j] = MM_BSPLINE_FITTED;
-        jobs.push_back(BsplJobH{(int32_t)lo, (int32_t)m});
+        jobs.push_back(BsplJob{(int32_t)lo, (int32_t)m});
         job_of.push_back(j);
     }
     if (!jobs.empty()) {
         const int nj = (int)jobs.size();
-        Carve cv;
-        const size_t o_xyz = cv.take((size_t)NP * 24), o_jobs = cv.take((size_t)nj * sizeof(BsplJobH)), in_bytes = cv.size();
-        const size_t o_out = cv.take((size_t)NP * 24), o_fp = cv.take((size_t)nj * 8), o_st = cv.take((size_t)nj * 4);
-        const size_t o_nk = cv.take((size_t)nj * 4), out_end = cv.size();
-        if ((rc = e->ensure(e->host_pts, std::max(in_bytes, out_end - o_out), true))) return rc;
-        if ((rc = e->ensure(e->dev_pts, cv.size(), false))) return rc;
-        unsigned char* hp = (unsigned char*)e->host_pts.p;
-        unsigned char* d = (unsigned char*)e->dev_pts.p;
-        std::memcpy(hp + o_xyz, xyz, (size_t)NP * 24);
-        std::memcpy(hp + o_jobs, jobs.data(), (size_t)nj * sizeof(BsplJobH));
-        MM_TRY_HIP(hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, e->stream));
-        if ((rc = e->profile_begin(e->stream))) return rc;
-        const hipError_t he = launch_bspline_fit(d + o_jobs, nj, (const double*)(d + o_xyz), degree, smoothing,
-                                                 wd * 8, (double*)(d + o_out), (int32_t*)(d + o_st), (double*)(d + o_fp),
-                                                 (int32_t*)(d + o_nk), e->stream);
-        if (he != hipSuccess) return hip_error(he, "B-spline fit launch");
-        if ((rc = e->profile_end(e->stream, (double)NP, 0))) return rc;
-        MM_TRY_HIP(hipMemcpyAsync(hp, d + o_out, out_end - o_out, hipMemcpyDeviceToHost, e->stream));
-        MM_TRY_HIP(hipStreamSynchronize(e->stream));
-        const double* r_out = (const double*)hp;
-        const double* r_fp = (const double*)(hp + (o_fp - o_out));
-        const int32_t* r_st = (const int32_t*)(hp + (o_st - o_out));
-        const int32_t* r_nk = (const int32_t*)(hp + (o_nk - o_out));
+        StagedPass sp;
+        const size_t o_xyz = sp.in.take((size_t)NP * 24), o_jobs = sp.in.take((size_t)nj * sizeof(BsplJob));
+        const size_t o_out = sp.out.take((size_t)NP * 24), o_fp = sp.out.take((size_t)nj * 8);
+        const size_t o_st = sp.out.take((size_t)nj * 4), o_nk = sp.out.take((size_t)nj * 4);
+        if ((rc = sp.reserve(e))) return rc;
+        std::memcpy(sp.host<double>(o_xyz), xyz, (size_t)NP * 24);
+        std::memcpy(sp.host<BsplJob>(o_jobs), jobs.data(), (size_t)nj * sizeof(BsplJob));
+        rc = sp.run((double)NP, "B-spline fit launch", [&] {
+            return launch_bspline_fit(sp.dev_in<BsplJob>(o_jobs), nj, sp.dev_in<double>(o_xyz), degree, smoothing, wd * 8,
+                                      sp.dev_out<double>(o_out), sp.dev_out<int32_t>(o_st), sp.dev_out<double>(o_fp),
+                                      sp.dev_out<int32_t>(o_nk), e->stream);
+        });
+        if (rc) return rc;
         for (int q = 0; q < nj; ++q) {
             const int j = job_of[(size_t)q];
-            const int32_t st = r_st[q];
+            const int32_t st = sp.host<int32_t>(o_st)[q];
             out_status[j] = st;
             if (st == MM_BSPLINE_UNCHANGED_SHORT || st == MM_BSPLINE_UNCHANGED_ZERO_CHORD || st == MM_BSPLINE_UNCHANGED_NONFINITE)
                 continue;
             if (st < 0 || st > MM_BSPLINE_ITERATION_LIMIT) return set_error(MM_ERR_HIP, "mm_bspline_fit_closed_batch: bad status from the device");
-            out_fp[j] = r_fp[q];
-            out_nknots[j] = r_nk[q];
-            std::memcpy(out_xyz + 3 * (size_t)jobs[(size_t)q].p_off, r_out + 3 * (size_t)jobs[(size_t)q].p_off, (size_t)jobs[(size_t)q].m * 24);
+            out_fp[j] = sp.host<double>(o_fp)[q];
+            out_nknots[j] = sp.host<int32_t>(o_nk)[q];
+            const size_t lo = (size_t)jobs[(size_t)q].p_off;
+            std::memcpy(out_xyz + 3 * lo, sp.host<double>(o_out) + 3 * lo, (size_t)jobs[(size_t)q].m * 24);
         }
     }
     for (int j = 0; j < nc; ++j) {                 // np.mean of each coordinate of the contour as returned

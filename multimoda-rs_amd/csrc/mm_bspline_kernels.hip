@@ -15,8 +15,6 @@
 
 namespace mm {
 
-struct BsplJob { int32_t p_off, m; };   // first point and point count of one contour (BsplJobH in mm_bspline.cpp)
-
 __global__ void __launch_bounds__(64)
 k_bspline_fit(const BsplJob* __restrict__ jobs, int n_jobs, const double* __restrict__ xyz, int k, double s,
               double* __restrict__ out_xyz, int32_t* __restrict__ status, double* __restrict__ fp,
@@ -59,7 +57,7 @@ k_bspline_fit(const BsplJob* __restrict__ jobs, int n_jobs, const double* __rest
 
 size_t bspline_work_doubles(int m, int k) { return bspl::work_doubles(m, k); }
 
-hipError_t launch_bspline_fit(const void* jobs, int n_jobs, const double* xyz, int k, double s, size_t lds_bytes,
+hipError_t launch_bspline_fit(const BsplJob* jobs, int n_jobs, const double* xyz, int k, double s, size_t lds_bytes,
                               double* out_xyz, int32_t* status, double* fp, int32_t* nknots, hipStream_t st)
 {
     if (n_jobs <= 0) return hipSuccess;
@@ -68,7 +66,7 @@ hipError_t launch_bspline_fit(const void* jobs, int n_jobs, const double* xyz, i
                                                  (int)lds_bytes);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_bspline_fit, dim3((unsigned)n_jobs), dim3(64), lds_bytes, st, (const BsplJob*)jobs, n_jobs, xyz, k,
+    hipLaunchKernelGGL(k_bspline_fit, dim3((unsigned)n_jobs), dim3(64), lds_bytes, st, jobs, n_jobs, xyz, k,
                        s, out_xyz, status, fp, nknots);
     return hipGetLastError();
 }

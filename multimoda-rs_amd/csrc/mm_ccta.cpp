@@ -14,15 +14,13 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_adjacency.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 #include "mm_pool.h"
 #include "mm_trace.h"
 
 namespace mm {
 namespace {
 
-struct NnPairH { int32_t q_off, nq, p_off, np, out_off, qperm_off; };
-struct NnWorkH { int32_t pair, q0, c0, n_chunks; double lb2; };
 // AoS triples.  A derived set (unit != nullptr) is xyz moved by adj along per-point unit vectors where has[i]
 // (centerline_based_diameter_morphing, scale_coronary.rs:236-239): it is never materialised on the host --
 // the device computes it from the base points and the unit vectors staged once for all scalings.
@@ -33,7 +31,6 @@ struct Set3 {
         return (unit && has[i]) ? xyz[3 * i + a] + unit[3 * i + a] * adj : xyz[3 * i + a];   // :236 p + unit * x
     }
 };
-struct NnMorphH { int32_t dst_off, n, aux_off, pad; double adj; };   // device: pool[dst_off + j] = aux point j moved by adj
 
 // Slab order of a point set: points sorted by their coordinate along the longest axis of the set's bounding
 // box (quantised to 20 bits, stable LSD radix sort), so that groups of consecutive points are slabs.
@@ -82,7 +79,7 @@ struct NnPlan {
     std::vector<int32_t> perm_of;              // set -> its entry of perms (-1: staged in original order)
     std::vector<std::vector<int32_t>> perms;   // slab orders, one per distinct base set
     std::vector<int64_t> perm_off;             // offset of every entry of perms in the permutation pool
-    std::vector<NnPairH> hp;                   // device pairs: both sets non-empty
+    std::vector<NnPair> hp;                   // device pairs: both sets non-empty
     std::vector<int> owner;                    // device pair -> caller's pair
     int64_t nout = 0;
     std::vector<int64_t> goff;                 // first group of every set
@@ -130,7 +127,7 @@ int nn_plan_pairs(const std::vector<Set3>& sets, const std::vector<std::array<in
         const int32_t q = pr[k][0], p = pr[k][1];
         const int64_t nq = sets[(size_t)q].n, np = sets[(size_t)p].n;
         if (nq == 0 || np == 0) continue;
-        pl.hp.push_back(NnPairH{(int32_t)pl.soff[(size_t)q], (int32_t)nq, (int32_t)pl.soff[(size_t)p], (int32_t)np, (int32_t)pl.nout,
+        pl.hp.push_back(NnPair{(int32_t)pl.soff[(size_t)q], (int32_t)nq, (int32_t)pl.soff[(size_t)p], (int32_t)np, (int32_t)pl.nout,
                                 pl.perm_of[(size_t)q] >= 0 ? (int32_t)pl.perm_off[(size_t)pl.perm_of[(size_t)q]] : -1});
         pl.owner.push_back((int)k);
         pl.nout += nq;
@@ -186,8 +183,8 @@ inline double chunk_lb2(const NnPlan& pl, int32_t q, int64_t qb, int32_t p, int6
 // Device pair i's items of k_nn3_min: pass A (wa) runs for every query block the chunk with the smallest lb2, pass B
 // (wb) every other chunk with its lb2.  Pairs that are not both sorted, or that have at most 2 chunks, scan everything
 // in pass A, span chunks per item.
-void nn_plan_min_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2>>& pr, size_t i, std::vector<NnWorkH>& wa,
-                       std::vector<NnWorkH>& wb)
+void nn_plan_min_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2>>& pr, size_t i, std::vector<NnWork>& wa,
+                       std::vector<NnWork>& wb)
 {
     const int qpb = pl.qpb, ch = pl.ch, gpc = ch / qpb;   // groups per chunk
     const int32_t q = pr[(size_t)pl.owner[i]][0], p = pr[(size_t)pl.owner[i]][1];
@@ -197,22 +194,22 @@ void nn_plan_min_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2
     if (!prune) {
         for (int64_t q0 = 0; q0 < nq; q0 += qpb)
             for (int64_t c0 = 0; c0 < np; c0 += (int64_t)pl.span * ch)
-                wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)c0, pl.span, 0.0});
+                wa.push_back(NnWork{(int32_t)i, (int32_t)q0, (int32_t)c0, pl.span, 0.0});
         return;
     }
     std::vector<std::pair<double, int32_t>> cand((size_t)n_chunks);
     for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb) {
         for (int64_t c = 0; c < n_chunks; ++c) cand[(size_t)c] = {chunk_lb2(pl, q, qb, p, c, gpc), (int32_t)c};
         std::sort(cand.begin(), cand.end());   // nearest chunks first: they tighten the minima the others check
-        wa.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[0].second * ch, 1, 0.0});
+        wa.push_back(NnWork{(int32_t)i, (int32_t)q0, cand[0].second * ch, 1, 0.0});
         for (size_t c = 1; c < cand.size(); ++c)
-            wb.push_back(NnWorkH{(int32_t)i, (int32_t)q0, cand[c].second * ch, 1, cand[c].first});
+            wb.push_back(NnWork{(int32_t)i, (int32_t)q0, cand[c].second * ch, 1, cand[c].first});
     }
 }
 
 // Device pair i's items of k_nn3_count: the (query block, chunk) combinations whose boxes come within r2
 void nn_plan_count_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2>>& pr, size_t i, double r2,
-                         std::vector<NnWorkH>& w)
+                         std::vector<NnWork>& w)
 {
     const int qpb = pl.qpb, ch = pl.ch, gpc = std::max(1, ch / qpb);
     const int32_t q = pr[(size_t)pl.owner[i]][0], p = pr[(size_t)pl.owner[i]][1];
@@ -220,7 +217,7 @@ void nn_plan_count_items(const NnPlan& pl, const std::vector<std::array<int32_t,
     for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb)
         for (int64_t c = 0; c < n_chunks; ++c) {
             const double lb2 = chunk_lb2(pl, q, qb, p, c, gpc);
-            if (lb2 <= r2) w.push_back(NnWorkH{(int32_t)i, (int32_t)q0, (int32_t)(c * ch), 1, lb2});
+            if (lb2 <= r2) w.push_back(NnWork{(int32_t)i, (int32_t)q0, (int32_t)(c * ch), 1, lb2});
         }
 }
 
@@ -250,11 +247,6 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     if (rc) return rc;
     for (size_t k = 0; k < pr.size(); ++k) view[k].n = sets[(size_t)pr[k][0]].n;   // fold(INFINITY, min) over an empty set: all +inf
     if (pl.hp.empty()) return MM_OK;
-    const std::vector<NnPairH>& hp = pl.hp;
-    const std::vector<int>& owner = pl.owner;
-    const std::vector<int64_t>& soff = pl.soff;
-    const std::vector<int32_t>& perm_of = pl.perm_of;
-    const std::vector<int64_t>& perm_off = pl.perm_off;
     const int64_t npts = pl.npts(), nout = pl.nout;
 
     // ---- stage the points (permuted where sorted) and the bounding box of every group of qpb points ---
@@ -269,17 +261,18 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
         if (!st.unit || st.n == 0) continue;
         size_t k = 0;
         for (; k < aux.size(); ++k)
-            if (aux[k].xyz == st.xyz && aux[k].unit == st.unit && aux[k].has == st.has && aux[k].perm == perm_of[s] && aux[k].n == st.n) break;
-        if (k == aux.size()) { aux.push_back(Aux{st.xyz, st.unit, st.has, perm_of[s], st.n, naux}); naux += st.n; }
+            if (aux[k].xyz == st.xyz && aux[k].unit == st.unit && aux[k].has == st.has && aux[k].perm == pl.perm_of[s] && aux[k].n == st.n) break;
+        if (k == aux.size()) { aux.push_back(Aux{st.xyz, st.unit, st.has, pl.perm_of[s], st.n, naux}); naux += st.n; }
         aux_of[s] = (int32_t)k;
     }
-    std::vector<NnMorphH> morphs;
+    std::vector<NnMorph> morphs;
     for (size_t s = 0; s < S; ++s)
-        if (aux_of[s] >= 0) morphs.push_back(NnMorphH{(int32_t)soff[s], (int32_t)sets[s].n, (int32_t)aux[(size_t)aux_of[s]].off, 0, sets[s].adj});
-    const size_t o_x = 0, o_y = up256((size_t)npts * 8), o_z = up256(o_y + (size_t)npts * 8);
-    const size_t o_perm = up256(o_z + (size_t)npts * 8), o_aux = up256(o_perm + (size_t)perm_off.back() * 4);
-    const size_t o_morph = up256(o_aux + (size_t)naux * 7 * 8), o_pairs = up256(o_morph + morphs.size() * sizeof(NnMorphH));
-    const size_t pts_bytes = o_pairs;   // the work lists follow once they are known
+        if (aux_of[s] >= 0) morphs.push_back(NnMorph{(int32_t)pl.soff[s], (int32_t)sets[s].n, (int32_t)aux[(size_t)aux_of[s]].off, 0, sets[s].adj});
+    Carve cv;
+    const size_t o_x = cv.take((size_t)npts * 8), o_y = cv.take((size_t)npts * 8), o_z = cv.take((size_t)npts * 8);
+    const size_t o_perm = cv.take((size_t)pl.perm_off.back() * 4), o_aux = cv.take((size_t)naux * 7 * 8);
+    const size_t o_morph = cv.take(morphs.size() * sizeof(NnMorph));
+    const size_t pts_bytes = cv.size();   // the pairs and the work lists follow once they are known
     if ((rc = e->ensure(e->host_pts, pts_bytes, true))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
     double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
@@ -301,39 +294,39 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
         }
         const size_t si = (size_t)job;
         const bool derived = aux_of[si] >= 0;
-        nn_plan_stage_set(sets, pl, si, derived ? nullptr : hx + soff[si], hy + soff[si], hz + soff[si]);
+        nn_plan_stage_set(sets, pl, si, derived ? nullptr : hx + pl.soff[si], hy + pl.soff[si], hz + pl.soff[si]);
     });
     }
     for (size_t k = 0; k < pl.perms.size(); ++k)
-        std::memcpy(h + o_perm + (size_t)perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
-    if (!morphs.empty()) std::memcpy(h + o_morph, morphs.data(), morphs.size() * sizeof(NnMorphH));
+        std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
+    if (!morphs.empty()) std::memcpy(h + o_morph, morphs.data(), morphs.size() * sizeof(NnMorph));
 
     // ---- work lists -------------------------------------------------------------------------------
     TraceTimer tt_wl("nn: work lists");
-    std::vector<std::vector<NnWorkH>> la(hp.size()), lb(hp.size());   // per pair, built over the worker pool
-    parallel_for((int)hp.size(), [&](int ii) { nn_plan_min_items(pl, pr, (size_t)ii, la[(size_t)ii], lb[(size_t)ii]); });
-    std::vector<NnWorkH> wa, wb;
+    std::vector<std::vector<NnWork>> la(pl.hp.size()), lb(pl.hp.size());   // per pair, built over the worker pool
+    parallel_for((int)pl.hp.size(), [&](int ii) { nn_plan_min_items(pl, pr, (size_t)ii, la[(size_t)ii], lb[(size_t)ii]); });
+    std::vector<NnWork> wa, wb;
     {
         size_t na_ = 0, nb_ = 0;
-        for (size_t i = 0; i < hp.size(); ++i) { na_ += la[i].size(); nb_ += lb[i].size(); }
+        for (size_t i = 0; i < pl.hp.size(); ++i) { na_ += la[i].size(); nb_ += lb[i].size(); }
         wa.reserve(na_); wb.reserve(nb_);
-        for (size_t i = 0; i < hp.size(); ++i) { wa.insert(wa.end(), la[i].begin(), la[i].end()); wb.insert(wb.end(), lb[i].begin(), lb[i].end()); }
+        for (size_t i = 0; i < pl.hp.size(); ++i) { wa.insert(wa.end(), la[i].begin(), la[i].end()); wb.insert(wb.end(), lb[i].begin(), lb[i].end()); }
     }
     if (wa.size() + wb.size() > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "nn batch exceeds 2^30 work items");
     tt_wl.stop();
     TraceTimer tt_dev("nn: copies + kernels");
 
-    const size_t o_wa = up256(o_pairs + hp.size() * sizeof(NnPairH)), o_wb = up256(o_wa + wa.size() * sizeof(NnWorkH));
-    const size_t in_bytes = up256(o_wb + wb.size() * sizeof(NnWorkH));
-    const size_t o_out = in_bytes, o_sums = up256(o_out + (size_t)nout * 8), total = up256(o_sums + hp.size() * 8);
+    const size_t o_pairs = cv.take(pl.hp.size() * sizeof(NnPair)), o_wa = cv.take(wa.size() * sizeof(NnWork));
+    const size_t o_wb = cv.take(wb.size() * sizeof(NnWork)), in_bytes = cv.size();
+    const size_t o_out = cv.take((size_t)nout * 8), o_sums = cv.take(pl.hp.size() * 8), total = cv.size();
     // descriptors and results go through the level buffers (the point staging above is still in flight-free
     // pinned memory of its own), so nothing staged so far moves
     if ((rc = e->ensure(e->host_lvl, std::max(in_bytes - o_pairs, (size_t)nout * 8), true))) return rc;
     if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
     unsigned char* hl = (unsigned char*)e->host_lvl.p;
-    std::memcpy(hl, hp.data(), hp.size() * sizeof(NnPairH));
-    std::memcpy(hl + (o_wa - o_pairs), wa.data(), wa.size() * sizeof(NnWorkH));
-    std::memcpy(hl + (o_wb - o_pairs), wb.data(), wb.size() * sizeof(NnWorkH));
+    std::memcpy(hl, pl.hp.data(), pl.hp.size() * sizeof(NnPair));
+    std::memcpy(hl + (o_wa - o_pairs), wa.data(), wa.size() * sizeof(NnWork));
+    std::memcpy(hl + (o_wb - o_pairs), wb.data(), wb.size() * sizeof(NnWork));
     unsigned char* d = (unsigned char*)e->dev_pts.p;
     if (morphs.empty()) {
         MM_TRY_HIP(hipMemcpyAsync(d, h, pts_bytes, hipMemcpyHostToDevice, e->stream));
@@ -342,31 +335,32 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
         for (size_t s2 = 0; s2 < S; ++s2) {
             if (aux_of[s2] >= 0 || sets[s2].n == 0) continue;
             for (size_t o : {o_x, o_y, o_z})
-                MM_TRY_HIP(hipMemcpyAsync(d + o + (size_t)soff[s2] * 8, h + o + (size_t)soff[s2] * 8, (size_t)sets[s2].n * 8,
+                MM_TRY_HIP(hipMemcpyAsync(d + o + (size_t)pl.soff[s2] * 8, h + o + (size_t)pl.soff[s2] * 8, (size_t)sets[s2].n * 8,
                                           hipMemcpyHostToDevice, e->stream));
         }
         MM_TRY_HIP(hipMemcpyAsync(d + o_perm, h + o_perm, o_pairs - o_perm, hipMemcpyHostToDevice, e->stream));
-        const hipError_t hm = launch_nn3_morph(d + o_morph, (int)morphs.size(), (const double*)(d + o_aux), naux,
+        const hipError_t hm = launch_nn3_morph((const NnMorph*)(d + o_morph), (int)morphs.size(), (const double*)(d + o_aux), naux,
                                                (double*)(d + o_x), (double*)(d + o_y), (double*)(d + o_z), e->stream);
         if (hm != hipSuccess) return hip_error(hm, "morph launch");
     }
     MM_TRY_HIP(hipMemcpyAsync(d + o_pairs, hl, in_bytes - o_pairs, hipMemcpyHostToDevice, e->stream));
-    const hipError_t he = launch_nn3_min(d + o_pairs, d + o_wa, (int)wa.size(), d + o_wb, (int)wb.size(),
-                                         (const double*)(d + o_x), (const double*)(d + o_y), (const double*)(d + o_z),
+    const NnPair* d_pairs = (const NnPair*)(d + o_pairs);
+    const hipError_t he = launch_nn3_min(d_pairs, (const NnWork*)(d + o_wa), (int)wa.size(), (const NnWork*)(d + o_wb),
+                                         (int)wb.size(), (const double*)(d + o_x), (const double*)(d + o_y), (const double*)(d + o_z),
                                          (const int32_t*)(d + o_perm), (double*)(d + o_out), nout, e->stream);
     if (he != hipSuccess) return hip_error(he, "nearest-neighbour launch");
     if (sums) {
-        const hipError_t hs = launch_nn3_sums(d + o_pairs, (int)hp.size(), (const double*)(d + o_out), (double*)(d + o_sums), e->stream);
+        const hipError_t hs = launch_nn3_sums(d_pairs, (int)pl.hp.size(), (const double*)(d + o_out), (double*)(d + o_sums), e->stream);
         if (hs != hipSuccess) return hip_error(hs, "sum launch");
-        MM_TRY_HIP(hipMemcpyAsync(hl, d + o_sums, hp.size() * 8, hipMemcpyDeviceToHost, e->stream));
+        MM_TRY_HIP(hipMemcpyAsync(hl, d + o_sums, pl.hp.size() * 8, hipMemcpyDeviceToHost, e->stream));
         MM_TRY_HIP(hipStreamSynchronize(e->stream));
-        for (size_t i = 0; i < hp.size(); ++i) (*sums)[(size_t)owner[i]] = ((const double*)hl)[i];
+        for (size_t i = 0; i < pl.hp.size(); ++i) (*sums)[(size_t)pl.owner[i]] = ((const double*)hl)[i];
         return MM_OK;
     }
     MM_TRY_HIP(hipMemcpyAsync(hl, d + o_out, (size_t)nout * 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     const double* res = (const double*)hl;
-    for (size_t i = 0; i < hp.size(); ++i) view[(size_t)owner[i]].p = res + hp[i].out_off;
+    for (size_t i = 0; i < pl.hp.size(); ++i) view[(size_t)pl.owner[i]].p = res + pl.hp[i].out_off;
     return MM_OK;
 }
 
@@ -527,47 +521,45 @@ int radius_counts(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     if (rc) return rc;
     for (size_t k = 0; k < pr.size(); ++k) counts[k].assign((size_t)sets[(size_t)pr[k][0]].n, 0u);
     if (pl.hp.empty()) return MM_OK;
-    const std::vector<NnPairH>& hp = pl.hp;
-    const std::vector<int>& owner = pl.owner;
-    const std::vector<int64_t>& soff = pl.soff;
     const int64_t npts = pl.npts(), nout = pl.nout;
 
     // staged points (slab order where sorted) + bounding boxes of groups of qpb points (a chunk's box is the union of
     // its ch / qpb groups)
-    const size_t o_x = 0, o_y = up256((size_t)npts * 8), o_z = up256(o_y + (size_t)npts * 8);
-    const size_t o_perm = up256(o_z + (size_t)npts * 8), o_pairs = up256(o_perm + (size_t)pl.perm_off.back() * 4);
+    Carve cv;
+    const size_t o_x = cv.take((size_t)npts * 8), o_y = cv.take((size_t)npts * 8), o_z = cv.take((size_t)npts * 8);
+    const size_t o_perm = cv.take((size_t)pl.perm_off.back() * 4), o_pairs = cv.take(pl.hp.size() * sizeof(NnPair));
     if ((rc = e->ensure(e->host_pts, o_pairs, true))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
     double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
-    parallel_for((int)S, [&](int si) { nn_plan_stage_set(sets, pl, (size_t)si, hx + soff[(size_t)si], hy + soff[(size_t)si], hz + soff[(size_t)si]); });
+    parallel_for((int)S, [&](int si) { nn_plan_stage_set(sets, pl, (size_t)si, hx + pl.soff[(size_t)si], hy + pl.soff[(size_t)si], hz + pl.soff[(size_t)si]); });
     for (size_t k = 0; k < pl.perms.size(); ++k)
         std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
 
-    std::vector<std::vector<NnWorkH>> lw(hp.size());
-    parallel_for((int)hp.size(), [&](int ii) { nn_plan_count_items(pl, pr, (size_t)ii, r2, lw[(size_t)ii]); });
-    std::vector<NnWorkH> work;
+    std::vector<std::vector<NnWork>> lw(pl.hp.size());
+    parallel_for((int)pl.hp.size(), [&](int ii) { nn_plan_count_items(pl, pr, (size_t)ii, r2, lw[(size_t)ii]); });
+    std::vector<NnWork> work;
     for (auto& v : lw) work.insert(work.end(), v.begin(), v.end());
     if (work.size() > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "radius counts: too many work items");
 
-    const size_t o_work = up256(o_pairs + hp.size() * sizeof(NnPairH)), in_bytes = up256(o_work + work.size() * sizeof(NnWorkH));
-    const size_t o_out = in_bytes, total = up256(o_out + (size_t)nout * 4);
+    const size_t o_work = cv.take(work.size() * sizeof(NnWork)), in_bytes = cv.size();
+    const size_t o_out = cv.take((size_t)nout * 4), total = cv.size();
     if ((rc = e->ensure(e->host_lvl, std::max(in_bytes - o_pairs, (size_t)nout * 4), true))) return rc;
     if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
     unsigned char* hl = (unsigned char*)e->host_lvl.p;
-    std::memcpy(hl, hp.data(), hp.size() * sizeof(NnPairH));
-    if (!work.empty()) std::memcpy(hl + (o_work - o_pairs), work.data(), work.size() * sizeof(NnWorkH));
+    std::memcpy(hl, pl.hp.data(), pl.hp.size() * sizeof(NnPair));
+    if (!work.empty()) std::memcpy(hl + (o_work - o_pairs), work.data(), work.size() * sizeof(NnWork));
     unsigned char* d = (unsigned char*)e->dev_pts.p;
     MM_TRY_HIP(hipMemcpyAsync(d, h, o_pairs, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(d + o_pairs, hl, in_bytes - o_pairs, hipMemcpyHostToDevice, e->stream));
-    const hipError_t he = launch_nn3_count(d + o_pairs, d + o_work, (int)work.size(), (const double*)(d + o_x), (const double*)(d + o_y),
+    const hipError_t he = launch_nn3_count((const NnPair*)(d + o_pairs), (const NnWork*)(d + o_work), (int)work.size(), (const double*)(d + o_x), (const double*)(d + o_y),
                                            (const double*)(d + o_z), (const int32_t*)(d + o_perm), r2, (unsigned int*)(d + o_out), nout,
                                            e->stream);
     if (he != hipSuccess) return hip_error(he, "radius-count launch");
     MM_TRY_HIP(hipMemcpyAsync(hl, d + o_out, (size_t)nout * 4, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     const uint32_t* res = (const uint32_t*)hl;
-    for (size_t i = 0; i < hp.size(); ++i)
-        std::memcpy(counts[(size_t)owner[i]].data(), res + hp[i].out_off, (size_t)hp[i].nq * 4);
+    for (size_t i = 0; i < pl.hp.size(); ++i)
+        std::memcpy(counts[(size_t)pl.owner[i]].data(), res + pl.hp[i].out_off, (size_t)pl.hp[i].nq * 4);
     return MM_OK;
 }
 
@@ -654,17 +646,16 @@ int occluded_points(Engine* e, const mm_clpoint* cc, int64_t ncc, const mm_clpoi
     if (R == 0) return MM_OK;
     const int ch = ray_chunk_faces(), rb = ray_block_rays();
     const int64_t n_chunks = (nf + ch - 1) / ch, n_rblk = (R + rb - 1) / rb;
-    const size_t part_bytes = ray_partial_bytes() * (size_t)R * (size_t)n_chunks;
+    const size_t part_bytes = sizeof(RayPartial) * (size_t)R * (size_t)n_chunks;
     if (R > INT32_MAX / 8 || nf > INT32_MAX / 16 || n_chunks * n_rblk > INT32_MAX || part_bytes > ((size_t)4 << 30))
         return set_error(MM_ERR_TOO_LARGE, "mm_occluded_points: too many rays x faces for one pass");
-    const size_t o_tri = up256((size_t)R * 6 * 8), in_bytes = up256(o_tri + (size_t)nf * 9 * 8);
-    const size_t o_part = in_bytes, o_cl = up256(o_part + part_bytes), total = up256(o_cl + (size_t)R * 4);
-    int rc = e->ensure(e->host_pts, std::max(in_bytes, (size_t)R * 4), true);
+    StagedPass sp;
+    const size_t o_ray = sp.in.take((size_t)R * 6 * 8), o_tri = sp.in.take((size_t)nf * 9 * 8);
+    const size_t o_cl = sp.out.take((size_t)R * 4), o_part = sp.scratch.take(part_bytes);
+    int rc = sp.reserve(e);
     if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    double* hr = (double*)h;
-    double* ht = (double*)(h + o_tri);
+    double* hr = sp.host<double>(o_ray);
+    double* ht = sp.host<double>(o_tri);
     const int64_t nc = (int64_t)cor.size();
     for (int64_t a = 0; a < nca; ++a)
         for (int64_t k = 0; k < nc; ++k) {
@@ -682,16 +673,12 @@ int occluded_points(Engine* e, const mm_clpoint* cc, int64_t ncc, const mm_clpoi
             ht[(size_t)(6 + ax) * nf + f] = t[6 + ax] - t[ax];                                       // edge2 = v2 - v0 (:39)
         }
     }
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->profile_begin(e->stream))) return rc;
-    const hipError_t he = launch_ray_tri((const double*)d, (int)R, (const double*)(d + o_tri), (int)nf, d + o_part,
-                                         (int32_t*)(d + o_cl), e->stream);
-    if (he != hipSuccess) return hip_error(he, "ray-triangle launch");
-    if ((rc = e->profile_end(e->stream, (double)R * (double)nf, 0))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(h, d + o_cl, (size_t)R * 4, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    const int32_t* closest = (const int32_t*)h;
+    rc = sp.run((double)R * (double)nf, "ray-triangle launch", [&] {
+        return launch_ray_tri(sp.dev_in<double>(o_ray), (int)R, sp.dev_in<double>(o_tri), (int)nf,
+                              sp.dev_scratch<RayPartial>(o_part), sp.dev_out<int32_t>(o_cl), e->stream);
+    });
+    if (rc) return rc;
+    const int32_t* closest = sp.host<int32_t>(o_cl);
     for (int64_t r = 0; r < R; ++r)
         if (closest[r] >= 0) excluded[(size_t)closest[r]] = 1;
     // :143-183 a point goes iff a vertex of an excluded face lies within squared distance 0.5
@@ -839,9 +826,6 @@ void restore_removed(const Adjacency& adj, const std::vector<uint8_t>& labels, s
 
 // ---- centerline morphing (scale_coronary.rs:218-260) on the device ----------------------------------------------
 
-struct MorphJobH { int32_t p_off, np, c_off, nc; double adj; };   // MorphJob in mm_morph_kernels.hip
-struct MorphWorkH { int32_t job, p0; };
-
 // every point of every job moved about its nearest centerline point of that job (k_cl_morph); every job with points
 // has a centerline point (checked by the caller)
 int cl_morph(Engine* e, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off, const double* pts,
@@ -851,41 +835,15 @@ int cl_morph(Engine* e, int n_jobs, const mm_clpoint* cl, const int64_t* cl_off,
     if (NP == 0) return MM_OK;
     if (NP > INT32_MAX / 4 || NC > INT32_MAX / 4)
         return set_error(MM_ERR_TOO_LARGE, "centerline morphing: too many points for one pass");
-    std::vector<MorphJobH> jobs((size_t)n_jobs);
-    std::vector<MorphWorkH> work;
-    double evals = 0.0;
-    const int bp = morph_block_points();
-    for (int j = 0; j < n_jobs; ++j) {
-        const int64_t np = pt_off[j + 1] - pt_off[j], nc = cl_off[j + 1] - cl_off[j];
-        jobs[(size_t)j] = MorphJobH{(int32_t)pt_off[j], (int32_t)np, (int32_t)cl_off[j], (int32_t)nc, adj[j]};
-        for (int64_t p0 = 0; p0 < np; p0 += bp) work.push_back(MorphWorkH{j, (int32_t)p0});
-        evals += (double)np * (double)nc;
-    }
-    const size_t o_cl = up256((size_t)NP * 24), o_jobs = up256(o_cl + (size_t)NC * 24);
-    const size_t o_work = up256(o_jobs + jobs.size() * sizeof(MorphJobH)), in_bytes = up256(o_work + work.size() * sizeof(MorphWorkH));
-    const size_t o_idx = in_bytes, o_out = up256(o_idx + (size_t)NP * 4), total = up256(o_out + (size_t)NP * 24);
-    int rc = e->ensure(e->host_pts, std::max(in_bytes, total - o_idx), true);
-    if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    std::memcpy(h, pts, (size_t)NP * 24);
-    double* hc = (double*)(h + o_cl);
-    for (int64_t k = 0; k < NC; ++k) { hc[3 * k] = cl[k].x; hc[3 * k + 1] = cl[k].y; hc[3 * k + 2] = cl[k].z; }
-    std::memcpy(h + o_jobs, jobs.data(), jobs.size() * sizeof(MorphJobH));
-    std::memcpy(h + o_work, work.data(), work.size() * sizeof(MorphWorkH));
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->profile_begin(e->stream))) return rc;
-    const hipError_t he = launch_cl_morph(d + o_jobs, d + o_work, (int)work.size(), (const double*)d,
-                                          (const double*)(d + o_cl), (int32_t*)(d + o_idx), (double*)(d + o_out),
-                                          e->stream);
-    if (he != hipSuccess) return hip_error(he, "centerline morphing launch");
-    if ((rc = e->profile_end(e->stream, evals, 0))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(h, d + o_idx, total - o_idx, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    std::memcpy(nearest, h, (size_t)NP * 4);
-    std::memcpy(out, h + (o_out - o_idx), (size_t)NP * 24);
-    return MM_OK;
+    std::vector<MorphJob> jobs((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j)
+        jobs[(size_t)j] = MorphJob{(int32_t)pt_off[j], (int32_t)(pt_off[j + 1] - pt_off[j]), (int32_t)cl_off[j],
+                                   (int32_t)(cl_off[j + 1] - cl_off[j]), adj[j]};
+    auto fill_cl = [&](double* hc) {
+        for (int64_t k = 0; k < NC; ++k) { hc[3 * k] = cl[k].x; hc[3 * k + 1] = cl[k].y; hc[3 * k + 2] = cl[k].z; }
+    };
+    return nearest_pass(e, jobs, pt_off, pts, cl_off, 3, fill_cl, morph_block_points(), launch_cl_morph,
+                        "centerline morphing launch", nearest, out);
 }
 
 }  // namespace
@@ -957,7 +915,7 @@ int mm_nn_plan(int n_sets, const int64_t* set_off, const double* xyz, const doub
         if (pl.perm_of[s] >= 0) std::memcpy(dst, pl.perms[(size_t)pl.perm_of[s]].data(), (size_t)sets[s].n * 4);
         else for (int64_t j = 0; j < sets[s].n; ++j) dst[j] = (int32_t)j;
     }
-    std::vector<NnWorkH> lists[3];   // pass A, pass B, radius count
+    std::vector<NnWork> lists[3];   // pass A, pass B, radius count
     for (size_t i = 0; i < pl.hp.size(); ++i) {
         nn_plan_min_items(pl, pr, i, lists[0], lists[1]);
         nn_plan_count_items(pl, pr, i, r2, lists[2]);
@@ -965,7 +923,7 @@ int mm_nn_plan(int n_sets, const int64_t* set_off, const double* xyz, const doub
     int64_t k = 0;
     for (int l = 0; l < 3; ++l) {
         info[l] = (int64_t)lists[l].size();
-        for (const NnWorkH& w : lists[l]) {
+        for (const NnWork& w : lists[l]) {
             if (k < cap) {
                 int32_t* it = items + 5 * k;
                 it[0] = l; it[1] = pl.owner[(size_t)w.pair]; it[2] = w.q0; it[3] = w.c0; it[4] = w.n_chunks;

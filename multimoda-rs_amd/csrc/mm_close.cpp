@@ -16,7 +16,7 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {

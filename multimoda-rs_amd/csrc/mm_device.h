@@ -1,9 +1,11 @@
-// mm_device.h -- structures shared by the HIP kernels (mm_kernels.hip) and the host
-// engine (mm_engine.cpp).  Internal; the public boundary is include/mm_hausdorff.h.
+// mm_device.h -- shared by the HIP kernel files (mm_*_kernels.hip) and the host files that drive them: the search engine's
+// structures and every file's launchers; the CCTA point kernels' records are in mm_point_records.h.  Internal.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
+
+#include "mm_point_records.h"
 
 namespace mm {
 
@@ -141,52 +143,49 @@ hipError_t launch_hausdorff_large(const void* pairs, const void* work, int n_pai
 hipError_t launch_hausdorff_large_bound(const void* pairs, const void* work, int n_out, int n_work, const double* px,
                                         const double* py, void* rowmax, double* out, hipStream_t s);
 int        large_rows_per_block();
-// 3-D nearest-neighbour squared distances (mm_nn_kernels.hip); pairs/work are device arrays of the kernel's
-// NnPair {q_off, nq, p_off, np, out_off, qperm_off} / NnWork {pair, q0, c0, n_chunks, lb2 (f64)} records:
+// 3-D nearest-neighbour squared distances (mm_nn_kernels.hip); pairs / work are device arrays:
 // work_a always runs, work_b items first check their bound against their queries' current minima
-hipError_t launch_nn3_min(const void* pairs, const void* work_a, int n_a, const void* work_b, int n_b, const double* px,
-                          const double* py, const double* pz, const int32_t* qperm, double* out, long long n_out,
-                          hipStream_t s);
+hipError_t launch_nn3_min(const NnPair* pairs, const NnWork* work_a, int n_a, const NnWork* work_b, int n_b,
+                          const double* px, const double* py, const double* pz, const int32_t* qperm, double* out,
+                          long long n_out, hipStream_t s);
 // neighbour counts within a radius (same records; every work item runs): out[n_out] u32
-hipError_t launch_nn3_count(const void* pairs, const void* work, int n_work, const double* px, const double* py,
+hipError_t launch_nn3_count(const NnPair* pairs, const NnWork* work, int n_work, const double* px, const double* py,
                             const double* pz, const int32_t* qperm, double r2, unsigned int* out, long long n_out,
                             hipStream_t s);
-// derived sets (NnMorph {dst_off, n, aux_off, pad, adj (f64)}): base point + unit vector * adj where flagged,
-// from 7 planes of n_aux doubles (bx by bz ux uy uz flag), written into the SoA point pool
-hipError_t launch_nn3_morph(const void* items, int n_items, const double* aux, long long n_aux, double* px, double* py,
+// derived sets: base point + unit vector * adj where flagged, from 7 planes of n_aux doubles (bx by bz ux uy uz flag),
+// written into the SoA point pool
+hipError_t launch_nn3_morph(const NnMorph* items, int n_items, const double* aux, long long n_aux, double* px, double* py,
                             double* pz, hipStream_t s);
 // sums[p] = the minima of pair p added up in index order (sequential f64 fold)
-hipError_t launch_nn3_sums(const void* pairs, int n_pairs, const double* out, double* sums, hipStream_t s);
+hipError_t launch_nn3_sums(const NnPair* pairs, int n_pairs, const double* out, double* sums, hipStream_t s);
 int        nn_queries_per_block();
 int        nn_chunk_points();
 int        nn_span_chunks();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
-// xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = ray_partial_bytes() x n_rays x
-// ceil(n_faces / ray_chunk_faces()) bytes of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits
-// at least 3 faces, else -1
-hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int n_faces, void* part, int32_t* closest,
-                          hipStream_t s);
+// xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = n_rays x ceil(n_faces /
+// ray_chunk_faces()) records of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits at least 3
+// faces, else -1
+hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int n_faces, RayPartial* part,
+                          int32_t* closest, hipStream_t s);
 int        ray_chunk_faces();
 int        ray_block_rays();
-size_t     ray_partial_bytes();
-// nearest slice anchor and plane projection of the vessel discretisation (mm_slice_kernels.hip): jobs = SliceJob records
-// (point / anchor ranges), work = SliceWork records (job, first point) of slice_block_points() points each; pts = xyz
-// triples, anc = 6 doubles per anchor (position, unit normal); idx / proj at the point's position
-hipError_t launch_slice_nearest(const void* jobs, const void* work, int n_work, const double* pts, const double* anc,
-                                int32_t* idx, double* proj, hipStream_t s);
+// nearest slice anchor and plane projection of the vessel discretisation (mm_slice_kernels.hip): jobs = point / anchor
+// ranges, work = blocks of slice_block_points() points; pts = xyz triples, anc = 6 doubles per anchor (position, unit
+// normal); idx / proj at the point's position
+hipError_t launch_slice_nearest(const SliceJob* jobs, const PointWork* work, int n_work, const double* pts,
+                                const double* anc, int32_t* idx, double* proj, hipStream_t s);
 int        slice_block_points();
-// radial morphing about the nearest centerline point (mm_morph_kernels.hip): jobs = MorphJob records (point /
-// centerline ranges, adjustment), work = MorphWork records (job, first point) of morph_block_points() points each;
-// pts / cl = xyz triples; nearest (job-local centerline index) / out (moved xyz) at the point's position
-hipError_t launch_cl_morph(const void* jobs, const void* work, int n_work, const double* pts, const double* cl,
+// radial morphing about the nearest centerline point (mm_morph_kernels.hip): jobs = point / centerline ranges and the
+// adjustment, work = blocks of morph_block_points() points; pts / cl = xyz triples; nearest (job-local centerline
+// index) / out (moved xyz) at the point's position
+hipError_t launch_cl_morph(const MorphJob* jobs, const PointWork* work, int n_work, const double* pts, const double* cl,
                            int32_t* nearest, double* out, hipStream_t s);
 int        morph_block_points();
-// lumen morphometry (mm_shape_kernels.hip): jobs = n_jobs ShapeJob records of shape_job_bytes() each (first point,
-// point count); xyz = point rows; theta = one angle per point, read only when want2d; val = 5 doubles per contour
-// (area, major, minor 3-D, minor 2-D, elliptic ratio), idx = 6 per contour (the three pairs, contour-local)
-hipError_t launch_contour_measures(const void* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
+// lumen morphometry (mm_shape_kernels.hip): one job per contour; xyz = point rows; theta = one angle per point, read
+// only when want2d; val = 5 doubles per contour (area, major, minor 3-D, minor 2-D, elliptic ratio), idx = 6 per
+// contour (the three pairs, contour-local)
+hipError_t launch_contour_measures(const ShapeJob* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
                                    double* val, int64_t* idx, hipStream_t s);
-size_t     shape_job_bytes();
 // mesh trimming (mm_trim_kernels.hip): face = int32 triples, masks uint8 0 / 1.  trim_faces: fkeep per face (all corners
 // in `in`, or with any_mode some corner) and the corner marks (nullable); trim_open_edges: the edge keys (min << 32 | max)
 // used by exactly one kept face into out (capacity 3 nf), their number in *n_out, through a table of 2^log2_cap slots
@@ -308,12 +307,11 @@ hipError_t launch_rim_gather(const double* v, const int32_t* index, int n, doubl
 hipError_t launch_rim_edge_faces(const int32_t* face, long long nf, const int32_t* pos, const int32_t* counts, int n,
                                  uint8_t* keep, int32_t* list, unsigned int list_cap, unsigned int* n_list, hipStream_t s);
 hipError_t launch_rim_face_gather(const int32_t* face, long long nf, const int32_t* fidx, int32_t* out, hipStream_t s);
-// branch masks (mm_branch_kernels.hip): pts = n xyz triples; cl = m packed centerline points of branch_cl_point_bytes()
-// each (x, y, z, 1 << branch_id), staged through LDS branch_tile_points() at a time; mask[i] = the bits of the centerline
-// points within squared distance r2 of point i
-hipError_t launch_branch_mask(const double* pts, long long n, const void* cl, int m, double r2, unsigned long long* mask,
-                              hipStream_t s);
-int        branch_cl_point_bytes();
+// branch masks (mm_branch_kernels.hip): pts = n xyz triples; cl = m packed centerline points (x, y, z, 1 << branch_id),
+// staged through LDS branch_tile_points() at a time; mask[i] = the bits of the centerline points within squared
+// distance r2 of point i
+hipError_t launch_branch_mask(const double* pts, long long n, const BranchClPoint* cl, int m, double r2,
+                              unsigned long long* mask, hipStream_t s);
 int        branch_tile_points();
 hipError_t launch_exact_all(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
 // bytes between HBM and pinned host memory by a 256-thread kernel (see k_copy_small: a runtime copy behind a
@@ -345,11 +343,11 @@ size_t     lds_bytes_f64(int nbp);
 int        max_target_points_f32();
 int        max_target_points_f64();
 
-// closed smoothing B-spline contours (mm_bspline_kernels.hip): jobs = n_jobs BsplJob records (first point, count), one
-// wave each, the work arrays of a contour in lds_bytes = 8 * bspline_work_doubles(longest m, k) of dynamic LDS.
+// closed smoothing B-spline contours (mm_bspline_kernels.hip): one job per contour (first point, count), one wave
+// each, the work arrays of a contour in lds_bytes = 8 * bspline_work_doubles(longest m, k) of dynamic LDS.
 // out_xyz is indexed like xyz; status / fp / nknots per job.
 size_t     bspline_work_doubles(int m, int k);
-hipError_t launch_bspline_fit(const void* jobs, int n_jobs, const double* xyz, int k, double s, size_t lds_bytes,
+hipError_t launch_bspline_fit(const BsplJob* jobs, int n_jobs, const double* xyz, int k, double s, size_t lds_bytes,
                               double* out_xyz, int32_t* status, double* fp, int32_t* nknots, hipStream_t st);
 
 }  // namespace mm

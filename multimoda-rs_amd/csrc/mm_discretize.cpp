@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 #include "mm_pool.h"
 
 namespace mm {
@@ -184,9 +184,6 @@ int resample(const double* pts, int64_t n, V3 c, int64_t n_points, double* out)
 
 // ---- device pass ----------------------------------------------------------------------------------------------------
 
-struct SliceJobH { int32_t p_off, np, a_off, na; };   // SliceJob in mm_slice_kernels.hip
-struct SliceWorkH { int32_t job, p0; };
-
 // nearest anchor and plane projection of every point of every job (voronoi_partition, projecting.rs:62-104).
 // pt_off / a_off: n_jobs + 1 offsets into pts (xyz) and anc (6 doubles each).  idx = -1 and proj = p where a job has
 // no anchor (the reference drops such points).
@@ -197,52 +194,16 @@ int nearest_project(Engine* e, int n_jobs, const int64_t* pt_off, const double* 
     if (NP == 0) return MM_OK;
     if (NP > INT32_MAX / 4 || NA > INT32_MAX / 8)
         return set_error(MM_ERR_TOO_LARGE, "discretize: too many points or anchors for one pass");
-    std::vector<SliceJobH> jobs((size_t)n_jobs);
-    std::vector<SliceWorkH> work;
-    double evals = 0.0;
-    const int bp = slice_block_points();
+    std::vector<SliceJob> jobs((size_t)n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         const int64_t np = pt_off[j + 1] - pt_off[j], na = a_off[j + 1] - a_off[j];
-        jobs[(size_t)j] = SliceJobH{(int32_t)pt_off[j], (int32_t)np, (int32_t)a_off[j], (int32_t)na};
-        if (na == 0) {
-            for (int64_t i = pt_off[j]; i < pt_off[j + 1]; ++i) {
-                idx[i] = -1;
-                proj[3 * i] = pts[3 * i]; proj[3 * i + 1] = pts[3 * i + 1]; proj[3 * i + 2] = pts[3 * i + 2];
-            }
-            continue;
-        }
-        for (int64_t p0 = 0; p0 < np; p0 += bp) work.push_back(SliceWorkH{j, (int32_t)p0});
-        evals += (double)np * (double)na;
+        jobs[(size_t)j] = SliceJob{(int32_t)pt_off[j], (int32_t)np, (int32_t)a_off[j], (int32_t)na};
+        if (na) continue;
+        std::fill(idx + pt_off[j], idx + pt_off[j + 1], -1);
+        std::memcpy(proj + 3 * pt_off[j], pts + 3 * pt_off[j], (size_t)np * 24);
     }
-    if (work.empty()) return MM_OK;
-    const size_t o_anc = up256((size_t)NP * 24), o_jobs = up256(o_anc + (size_t)NA * 48);
-    const size_t o_work = up256(o_jobs + jobs.size() * sizeof(SliceJobH)), in_bytes = up256(o_work + work.size() * sizeof(SliceWorkH));
-    const size_t o_idx = in_bytes, o_proj = up256(o_idx + (size_t)NP * 4), total = up256(o_proj + (size_t)NP * 24);
-    int rc = e->ensure(e->host_pts, std::max(in_bytes, total - o_idx), true);
-    if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    std::memcpy(h, pts, (size_t)NP * 24);
-    if (NA) std::memcpy(h + o_anc, anc, (size_t)NA * 48);
-    std::memcpy(h + o_jobs, jobs.data(), jobs.size() * sizeof(SliceJobH));
-    std::memcpy(h + o_work, work.data(), work.size() * sizeof(SliceWorkH));
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->profile_begin(e->stream))) return rc;
-    const hipError_t he = launch_slice_nearest(d + o_jobs, d + o_work, (int)work.size(), (const double*)d,
-                                               (const double*)(d + o_anc), (int32_t*)(d + o_idx), (double*)(d + o_proj),
-                                               e->stream);
-    if (he != hipSuccess) return hip_error(he, "nearest-anchor launch");
-    if ((rc = e->profile_end(e->stream, evals, 0))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(h, d + o_idx, total - o_idx, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    for (int j = 0; j < n_jobs; ++j) {
-        if (a_off[j + 1] == a_off[j]) continue;
-        const int64_t lo = pt_off[j], hi = pt_off[j + 1];
-        std::memcpy(idx + lo, h + (size_t)lo * 4, (size_t)(hi - lo) * 4);
-        std::memcpy(proj + 3 * lo, h + (o_proj - o_idx) + (size_t)lo * 24, (size_t)(hi - lo) * 24);
-    }
-    return MM_OK;
+    return nearest_pass(e, jobs, pt_off, pts, a_off, 6, [&](double* ha) { if (NA) std::memcpy(ha, anc, (size_t)NA * 48); },
+                        slice_block_points(), launch_slice_nearest, "nearest-anchor launch", idx, proj);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine
-// _kernels.hip) share, the device-side counterpart of mm_mesh_stage.h: the launch geometry, the 64-bit edge table (the weld, trim
-// and refine files insert, the close and smooth files read, EdgeTable of mm_mesh_stage.h sizes it), the workgroup scan and the two
+// _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim
+// and refine files insert, the close and smooth files read, EdgeTable of mm_stage.h sizes it), the workgroup scan and the two
 // per-wave ballot idioms.  Header-only; internal.
 #pragma once
 

@@ -13,59 +13,35 @@
 // the divisions are hipcc's correctly rounded expansions (v_rsq_f64 + refinement, v_div_scale/fmas/fixup).
 //
 // Mapping: one work item = one job x 256 consecutive points (one per lane).  Each lane folds its own point over the
-// job's whole centerline range in order, so the tie and NaN rules hold without a cross-lane merge and no atomics are
-// needed.  Centerline points are staged through LDS in tiles of kMorphTile as (x, y, z, pad): every lane reads the
-// same address (broadcast, conflict-free).  Many jobs share one launch; work items are job-major and dealt to the
-// XCDs in contiguous eighths.
+// job's whole centerline range in order (nearest_fold, mm_point_device.h: centerline points staged through LDS in
+// tiles), so the tie and NaN rules hold without a cross-lane merge and no atomics are needed.  Many jobs share one
+// launch; work items are job-major and dealt to the XCDs in contiguous eighths.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 
 #include "mm_device.h"
+#include "mm_point_device.h"
 #include "mm_xcd.h"
 
 namespace mm {
 
-static constexpr int kMorphTile = 512;    // centerline points per LDS tile (512 x 32 B = 16 KiB)
-static constexpr int kMorphLanes = 256;   // points per work item
-
-struct MorphJob { int32_t p_off, np, c_off, nc; double adj; };   // points [p_off, p_off + np), centerline [c_off, c_off + nc)
-struct MorphWork { int32_t job, p0; };
-
 // pts, cl, out: xyz triples; nearest / out at the point's position
 __global__ void __launch_bounds__(256)
-k_cl_morph(const MorphJob* __restrict__ jobs, const MorphWork* __restrict__ work, int n_work,
+k_cl_morph(const MorphJob* __restrict__ jobs, const PointWork* __restrict__ work, int n_work,
            const double* __restrict__ pts, const double* __restrict__ cl, int32_t* __restrict__ nearest,
            double* __restrict__ out)
 {
-    __shared__ double4 s_c[kMorphTile];
     const int tid = threadIdx.x;
     for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
-        const MorphWork w = work[wi];
+        const PointWork w = work[wi];
         const MorphJob jb = jobs[w.job];
         const int i = w.p0 + tid;
         const size_t pi = (size_t)jb.p_off + (size_t)(i < jb.np ? i : jb.np - 1);   // lanes past the end recompute the last point
         const double px = pts[3 * pi], py = pts[3 * pi + 1], pz = pts[3 * pi + 2];
         const double* c0 = cl + 3 * (size_t)jb.c_off;
-        double best = DBL_MAX;
-        int bi = 0;
-        for (int t0 = 0; t0 < jb.nc; t0 += kMorphTile) {
-            const int n = jb.nc - t0 < kMorphTile ? jb.nc - t0 : kMorphTile;
-            __syncthreads();   // the previous tile is fully consumed
-            for (int j = tid; j < n; j += kMorphLanes) {
-                const double* c = c0 + 3 * (size_t)(t0 + j);
-                s_c[j] = make_double4(c[0], c[1], c[2], 0.0);
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int j = 0; j < n; ++j) {
-                const double4 c = s_c[j];
-                const double dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-                const double d = dx * dx + dy * dy + dz * dz;
-                if (d < best) { best = d; bi = t0 + j; }
-            }
-        }
+        const int bi = nearest_fold<3>(c0, jb.nc, px, py, pz, DBL_MAX);       // the start: no d_j below DBL_MAX keeps index 0
         if (i < jb.np) {
             const double* c = c0 + 3 * (size_t)bi;
             const double vx = px - c[0], vy = py - c[1], vz = pz - c[2];
@@ -84,14 +60,13 @@ k_cl_morph(const MorphJob* __restrict__ jobs, const MorphWork* __restrict__ work
     }
 }
 
-int morph_block_points() { return kMorphLanes; }
+int morph_block_points() { return kNearestLanes; }
 
-hipError_t launch_cl_morph(const void* jobs, const void* work, int n_work, const double* pts, const double* cl,
+hipError_t launch_cl_morph(const MorphJob* jobs, const PointWork* work, int n_work, const double* pts, const double* cl,
                            int32_t* nearest, double* out, hipStream_t s)
 {
     if (n_work <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_cl_morph, dim3((unsigned)n_work), dim3(256), 0, s, (const MorphJob*)jobs,
-                       (const MorphWork*)work, n_work, pts, cl, nearest, out);
+    hipLaunchKernelGGL(k_cl_morph, dim3((unsigned)n_work), dim3(256), 0, s, jobs, work, n_work, pts, cl, nearest, out);
     return hipGetLastError();
 }
 

@@ -28,12 +28,6 @@
 
 namespace mm {
 
-// q_off / p_off: into the point pool; out_off: into the output; qperm_off: into the permutation pool (the
-// staged position j of the query set holds original point qperm[qperm_off + j]; -1 = staged in original order)
-struct NnPair { int32_t q_off, nq, p_off, np, out_off, qperm_off; };
-// queries [q0, q0 + 256 QPT) x points [c0, c0 + n_chunks CH); lb2: see "Pruning" above (pass B only)
-struct NnWork { int32_t pair, q0, c0, n_chunks; double lb2; };
-
 static constexpr int kNnChunk = 512;
 static constexpr int kNnSpan = 10;
 
@@ -44,11 +38,10 @@ k_nn3_fill(unsigned long long* __restrict__ out, long long n)
     if (i < n) out[i] = 0x7ff0000000000000ull;   // +inf
 }
 
-// A derived set: pool[dst_off + j] = base point j moved by adj along its unit vector where its flag is set,
+// A derived set (NnMorph): pool[dst_off + j] = base point j moved by adj along its unit vector where its flag is set,
 // p + unit * x with one rounding for the product and one for the sum (no contraction: this file is built
 // with -ffp-contract=off), exactly centerline_based_diameter_morphing (scale_coronary.rs:236-239).
 // aux: 7 planes of n_aux doubles -- bx by bz ux uy uz flag.
-struct NnMorph { int32_t dst_off, n, aux_off, pad; double adj; };
 
 __global__ void __launch_bounds__(256)
 k_nn3_morph(const NnMorph* __restrict__ items, const double* __restrict__ aux, long long n_aux,
@@ -225,25 +218,25 @@ k_nn3_sums(const NnPair* __restrict__ pairs, int n_pairs, const double* __restri
     if (threadIdx.x == 0) sums[blockIdx.x] = s;
 }
 
-hipError_t launch_nn3_sums(const void* pairs, int n_pairs, const double* out, double* sums, hipStream_t s)
+hipError_t launch_nn3_sums(const NnPair* pairs, int n_pairs, const double* out, double* sums, hipStream_t s)
 {
     if (n_pairs <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_nn3_sums, dim3((unsigned)n_pairs), dim3(64), 0, s, (const NnPair*)pairs, n_pairs, out, sums);
+    hipLaunchKernelGGL(k_nn3_sums, dim3((unsigned)n_pairs), dim3(64), 0, s, pairs, n_pairs, out, sums);
     return hipGetLastError();
 }
 
-hipError_t launch_nn3_morph(const void* items, int n_items, const double* aux, long long n_aux, double* px, double* py,
+hipError_t launch_nn3_morph(const NnMorph* items, int n_items, const double* aux, long long n_aux, double* px, double* py,
                             double* pz, hipStream_t s)
 {
     if (n_items <= 0) return hipSuccess;
     // grid.x covers the largest set; blocks past a set's end exit
     hipLaunchKernelGGL(k_nn3_morph, dim3((unsigned)((n_aux + 255) / 256), (unsigned)n_items), dim3(256), 0, s,
-                       (const NnMorph*)items, aux, n_aux, px, py, pz);
+                       items, aux, n_aux, px, py, pz);
     return hipGetLastError();
 }
 
 // out[n_out] (u32, zeroed here) += neighbours within sqrt(r2) over the work items
-hipError_t launch_nn3_count(const void* pairs, const void* work, int n_work, const double* px, const double* py,
+hipError_t launch_nn3_count(const NnPair* pairs, const NnWork* work, int n_work, const double* px, const double* py,
                             const double* pz, const int32_t* qperm, double r2, unsigned int* out, long long n_out,
                             hipStream_t s)
 {
@@ -252,25 +245,25 @@ hipError_t launch_nn3_count(const void* pairs, const void* work, int n_work, con
         if (e != hipSuccess) return e;
     }
     if (n_work > 0)
-        hipLaunchKernelGGL((k_nn3_count<kNnQpt>), dim3((unsigned)n_work), dim3(256), 0, s, (const NnPair*)pairs,
-                           (const NnWork*)work, n_work, px, py, pz, qperm, r2, out);
+        hipLaunchKernelGGL((k_nn3_count<kNnQpt>), dim3((unsigned)n_work), dim3(256), 0, s, pairs, work, n_work,
+                           px, py, pz, qperm, r2, out);
     return hipGetLastError();
 }
 
 // work_a: items that always run (n_a of them); work_b: items that first check their bound (n_b)
-hipError_t launch_nn3_min(const void* pairs, const void* work_a, int n_a, const void* work_b, int n_b, const double* px,
-                          const double* py, const double* pz, const int32_t* qperm, double* out, long long n_out,
-                          hipStream_t s)
+hipError_t launch_nn3_min(const NnPair* pairs, const NnWork* work_a, int n_a, const NnWork* work_b, int n_b,
+                          const double* px, const double* py, const double* pz, const int32_t* qperm, double* out,
+                          long long n_out, hipStream_t s)
 {
     if (n_out > 0)
         hipLaunchKernelGGL(k_nn3_fill, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s,
                            (unsigned long long*)out, n_out);
     if (n_a > 0)
-        hipLaunchKernelGGL((k_nn3_min<kNnQpt, false>), dim3((unsigned)n_a), dim3(256), 0, s, (const NnPair*)pairs,
-                           (const NnWork*)work_a, n_a, px, py, pz, qperm, (unsigned long long*)out);
+        hipLaunchKernelGGL((k_nn3_min<kNnQpt, false>), dim3((unsigned)n_a), dim3(256), 0, s, pairs, work_a, n_a,
+                           px, py, pz, qperm, (unsigned long long*)out);
     if (n_b > 0)
-        hipLaunchKernelGGL((k_nn3_min<kNnQpt, true>), dim3((unsigned)n_b), dim3(256), 0, s, (const NnPair*)pairs,
-                           (const NnWork*)work_b, n_b, px, py, pz, qperm, (unsigned long long*)out);
+        hipLaunchKernelGGL((k_nn3_min<kNnQpt, true>), dim3((unsigned)n_b), dim3(256), 0, s, pairs, work_b, n_b,
+                           px, py, pz, qperm, (unsigned long long*)out);
     return hipGetLastError();
 }
 

@@ -27,8 +27,6 @@ namespace mm {
 static constexpr int kRayChunk = 256;   // faces per LDS chunk (9 x 256 doubles = 18 KiB)
 static constexpr int kRayLanes = 256;   // rays per work item
 
-struct RayPartial { int32_t count, face; double t; };   // hits of one ray in one chunk, closest (t, face)
-
 // ray: 6 planes of n_rays doubles (origin xyz, direction xyz); tri: 9 planes of n_faces doubles (v0 xyz, e1 xyz, e2 xyz)
 __global__ void __launch_bounds__(256)
 k_ray_tri(const double* __restrict__ ray, int n_rays, const double* __restrict__ tri, int n_faces, int n_rblk,
@@ -97,10 +95,9 @@ k_ray_fold(const RayPartial* __restrict__ part, int n_rays, int n_chunks, int32_
 
 int ray_chunk_faces() { return kRayChunk; }
 int ray_block_rays() { return kRayLanes; }
-size_t ray_partial_bytes() { return sizeof(RayPartial); }
 
-hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int n_faces, void* part, int32_t* closest,
-                          hipStream_t s)
+hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int n_faces, RayPartial* part,
+                          int32_t* closest, hipStream_t s)
 {
     if (n_rays <= 0) return hipSuccess;
     const int n_rblk = (n_rays + kRayLanes - 1) / kRayLanes;
@@ -109,9 +106,8 @@ hipError_t launch_ray_tri(const double* ray, int n_rays, const double* tri, int 
     if (n_work > 0x7fffffffLL) return hipErrorInvalidValue;
     if (n_work > 0)
         hipLaunchKernelGGL(k_ray_tri, dim3((unsigned)n_work), dim3(256), 0, s, ray, n_rays, tri, n_faces, n_rblk,
-                           (int)n_work, (RayPartial*)part);
-    hipLaunchKernelGGL(k_ray_fold, dim3((unsigned)n_rblk), dim3(256), 0, s, (const RayPartial*)part, n_rays, n_chunks,
-                       closest);
+                           (int)n_work, part);
+    hipLaunchKernelGGL(k_ray_fold, dim3((unsigned)n_rblk), dim3(256), 0, s, part, n_rays, n_chunks, closest);
     return hipGetLastError();
 }
 

@@ -14,7 +14,7 @@
 #include <cstring>
 
 #include "../../include/mm_ccta.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {

@@ -11,13 +11,11 @@
 #include <vector>
 
 #include "../../include/mm_build.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 #include "mm_pool.h"
 
 namespace mm {
 namespace {
-
-struct ShapeJobH { int64_t off; int32_t n; int32_t pad; };
 
 // find_closest_opposite (contour.rs:247-273): the centre is the stored centroid, else the sequential mean of the
 // points; theta = atan2(y - cy, x - cx), + 2 pi below 0
@@ -44,24 +42,22 @@ int contour_measures(Engine* e, int64_t nc, const int64_t* off, const double* xy
                      const double* centroid, bool want2d, double* out_val, int64_t* out_idx)
 {
     const int64_t NP = off[nc];
-    if (shape_job_bytes() != sizeof(ShapeJobH)) return set_error(MM_ERR_INVALID, "contour measures: job layout");
-    std::vector<ShapeJobH> jobs((size_t)nc);
+    std::vector<ShapeJob> jobs((size_t)nc);
     double evals = 0.0;
     for (int64_t c = 0; c < nc; ++c) {
         const int64_t n = off[c + 1] - off[c];
-        jobs[(size_t)c] = ShapeJobH{off[c], (int32_t)n, 0};
+        jobs[(size_t)c] = ShapeJob{off[c], (int32_t)n, 0};
         evals += 0.5 * (double)n * (double)(n > 0 ? n - 1 : 0) + (want2d ? (double)n * (double)n : 0.0);
     }
-    const size_t o_t = up256((size_t)NP * 24), o_jobs = up256(o_t + (want2d ? (size_t)NP * 8 : 0));
-    const size_t in_bytes = up256(o_jobs + (size_t)nc * sizeof(ShapeJobH));
-    const size_t o_val = in_bytes, o_idx = up256(o_val + (size_t)nc * 40), total = up256(o_idx + (size_t)nc * 48);
-    int rc = e->ensure(e->host_pts, std::max(in_bytes, total - o_val), true);
+    StagedPass sp;
+    const size_t o_xyz = sp.in.take((size_t)NP * 24), o_t = sp.in.take(want2d ? (size_t)NP * 8 : 0);
+    const size_t o_jobs = sp.in.take((size_t)nc * sizeof(ShapeJob));
+    const size_t o_val = sp.out.take((size_t)nc * 40), o_idx = sp.out.take((size_t)nc * 48);
+    int rc = sp.reserve(e);
     if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    if (NP) std::memcpy(h, xyz, (size_t)NP * 24);
+    if (NP) std::memcpy(sp.host<double>(o_xyz), xyz, (size_t)NP * 24);
     if (want2d) {
-        double* th = (double*)(h + o_t);
+        double* th = sp.host<double>(o_t);
         WorkerPool::instance().parallel_for((int)nc, [&](int c) {
             const int64_t n = off[c + 1] - off[c];
             if (n < 3) return;                                                     // the 2-D pass needs n > 2
@@ -69,19 +65,15 @@ int contour_measures(Engine* e, int64_t nc, const int64_t* off, const double* xy
             opposite_angles(xyz + 3 * off[c], n, own ? centroid + 3 * (size_t)c : nullptr, th + off[c]);
         });
     }
-    std::memcpy(h + o_jobs, jobs.data(), jobs.size() * sizeof(ShapeJobH));
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, e->stream));
-    if ((rc = e->profile_begin(e->stream))) return rc;
-    const hipError_t he = launch_contour_measures(d + o_jobs, (int)nc, (const double*)d,
-                                                  want2d ? (const double*)(d + o_t) : nullptr, want2d ? 1 : 0,
-                                                  (double*)(d + o_val), (int64_t*)(d + o_idx), e->stream);
-    if (he != hipSuccess) return hip_error(he, "contour measures launch");
-    if ((rc = e->profile_end(e->stream, evals, 0))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(h, d + o_val, total - o_val, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    std::memcpy(out_val, h, (size_t)nc * 40);
-    std::memcpy(out_idx, h + (o_idx - o_val), (size_t)nc * 48);
+    std::memcpy(sp.host<ShapeJob>(o_jobs), jobs.data(), jobs.size() * sizeof(ShapeJob));
+    rc = sp.run(evals, "contour measures launch", [&] {
+        return launch_contour_measures(sp.dev_in<ShapeJob>(o_jobs), (int)nc, sp.dev_in<double>(o_xyz),
+                                       want2d ? sp.dev_in<double>(o_t) : nullptr, want2d ? 1 : 0,
+                                       sp.dev_out<double>(o_val), sp.dev_out<int64_t>(o_idx), e->stream);
+    });
+    if (rc) return rc;
+    std::memcpy(out_val, sp.host<double>(o_val), (size_t)nc * 40);
+    std::memcpy(out_idx, sp.host<int64_t>(o_idx), (size_t)nc * 48);
     return MM_OK;
 }
 

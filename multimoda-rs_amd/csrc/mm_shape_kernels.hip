@@ -41,8 +41,6 @@ static constexpr int kShapeLanes = 256;
 static constexpr int kShapeLds = 1024;   // points staged in LDS: 4 arrays x 1024 x 8 B = 32 KiB
 static constexpr double kPi = 3.14159265358979323846;
 
-struct ShapeJob { int64_t off; int32_t n; int32_t pad; };   // points [off, off + n)
-
 struct LdsPts {
     const double *x, *y, *z, *t;
     __device__ __forceinline__ double X(int j) const { return x[j]; }
@@ -228,15 +226,13 @@ k_contour_measures(const ShapeJob* __restrict__ jobs, int n_jobs, const double* 
     }
 }
 
-size_t shape_job_bytes() { return sizeof(ShapeJob); }
-
-hipError_t launch_contour_measures(const void* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
+hipError_t launch_contour_measures(const ShapeJob* jobs, int n_jobs, const double* xyz, const double* theta, int want2d,
                                    double* val, int64_t* idx, hipStream_t s)
 {
     if (n_jobs <= 0) return hipSuccess;
     const int grid = n_jobs < (1 << 20) ? n_jobs : (1 << 20);
-    hipLaunchKernelGGL(k_contour_measures, dim3((unsigned)grid), dim3(kShapeLanes), 0, s, (const ShapeJob*)jobs,
-                       n_jobs, xyz, theta, want2d, val, (long long*)idx);
+    hipLaunchKernelGGL(k_contour_measures, dim3((unsigned)grid), dim3(kShapeLanes), 0, s, jobs, n_jobs,
+                       xyz, theta, want2d, val, (long long*)idx);
     return hipGetLastError();
 }
 

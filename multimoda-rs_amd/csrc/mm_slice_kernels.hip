@@ -10,61 +10,35 @@
 // No contraction (the file is built with -ffp-contract=off), so every value is the reference's bit for bit.
 //
 // Mapping: one work item = one job x 256 consecutive points (one per lane).  Each lane folds its own point over the
-// job's whole anchor range in anchor order, so the tie and NaN rules hold without a cross-lane merge and no atomics
-// are needed.  Anchors are staged through LDS in tiles of kSliceTile as (x, y, z, pad): every lane reads the same
-// address (broadcast, conflict-free).  Many jobs (aorta, main vessels, side branches) share one launch; work items
-// are job-major and dealt to the XCDs in contiguous eighths.
+// job's whole anchor range in anchor order (nearest_fold, mm_point_device.h: anchors staged through LDS in tiles), so the
+// tie and NaN rules hold without a cross-lane merge and no atomics are needed.  Many jobs (aorta, main vessels, side
+// branches) share one launch; work items are job-major and dealt to the XCDs in contiguous eighths.
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_point_device.h"
 #include "mm_xcd.h"
 
 namespace mm {
 
-static constexpr int kSliceTile = 512;    // anchors per LDS tile (512 x 32 B = 16 KiB)
-static constexpr int kSliceLanes = 256;   // points per work item
-
-struct SliceJob { int32_t p_off, np, a_off, na; };   // points [p_off, p_off + np), anchors [a_off, a_off + na)
-struct SliceWork { int32_t job, p0; };
-
 // pts: xyz triples; anc: 6 doubles per anchor (x, y, z, nx, ny, nz); idx / proj: per point, at the point's position
 __global__ void __launch_bounds__(256)
-k_slice_nearest(const SliceJob* __restrict__ jobs, const SliceWork* __restrict__ work, int n_work,
+k_slice_nearest(const SliceJob* __restrict__ jobs, const PointWork* __restrict__ work, int n_work,
                 const double* __restrict__ pts, const double* __restrict__ anc, int32_t* __restrict__ idx,
                 double* __restrict__ proj)
 {
-    __shared__ double4 s_a[kSliceTile];
     const int tid = threadIdx.x;
     for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
-        const SliceWork w = work[wi];
+        const PointWork w = work[wi];
         const SliceJob jb = jobs[w.job];
         const int i = w.p0 + tid;
         const size_t pi = (size_t)jb.p_off + (size_t)(i < jb.np ? i : jb.np - 1);   // lanes past the end recompute the last point
         const double px = pts[3 * pi], py = pts[3 * pi + 1], pz = pts[3 * pi + 2];
         const double* a0 = anc + 6 * (size_t)jb.a_off;
-        double best;
-        {
-            const double dx = px - a0[0], dy = py - a0[1], dz = pz - a0[2];
-            best = dx * dx + dy * dy + dz * dz;                               // the fold's start: anchor 0
-        }
-        int bi = 0;
-        for (int t0 = 0; t0 < jb.na; t0 += kSliceTile) {
-            const int n = jb.na - t0 < kSliceTile ? jb.na - t0 : kSliceTile;
-            __syncthreads();   // the previous tile is fully consumed
-            for (int j = tid; j < n; j += kSliceLanes) {
-                const double* a = a0 + 6 * (size_t)(t0 + j);
-                s_a[j] = make_double4(a[0], a[1], a[2], 0.0);
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int j = 0; j < n; ++j) {
-                const double4 a = s_a[j];
-                const double dx = px - a.x, dy = py - a.y, dz = pz - a.z;
-                const double d = dx * dx + dy * dy + dz * dz;
-                if (best > d) { best = d; bi = t0 + j; }                      // anchor 0 against itself: never
-            }
-        }
+        const double dx = px - a0[0], dy = py - a0[1], dz = pz - a0[2];
+        // the fold's start: d_0, which anchor 0 itself never beats
+        const int bi = nearest_fold<6>(a0, jb.na, px, py, pz, dx * dx + dy * dy + dz * dz);
         if (i < jb.np) {
             const double* a = a0 + 6 * (size_t)bi;
             const double cx = a[0], cy = a[1], cz = a[2], nx = a[3], ny = a[4], nz = a[5];
@@ -77,16 +51,13 @@ k_slice_nearest(const SliceJob* __restrict__ jobs, const SliceWork* __restrict__
     }
 }
 
-int slice_block_points() { return kSliceLanes; }
-size_t slice_job_bytes() { return sizeof(SliceJob); }
-size_t slice_work_bytes() { return sizeof(SliceWork); }
+int slice_block_points() { return kNearestLanes; }
 
-hipError_t launch_slice_nearest(const void* jobs, const void* work, int n_work, const double* pts, const double* anc,
-                                int32_t* idx, double* proj, hipStream_t s)
+hipError_t launch_slice_nearest(const SliceJob* jobs, const PointWork* work, int n_work, const double* pts,
+                                const double* anc, int32_t* idx, double* proj, hipStream_t s)
 {
     if (n_work <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_slice_nearest, dim3((unsigned)n_work), dim3(256), 0, s, (const SliceJob*)jobs,
-                       (const SliceWork*)work, n_work, pts, anc, idx, proj);
+    hipLaunchKernelGGL(k_slice_nearest, dim3((unsigned)n_work), dim3(256), 0, s, jobs, work, n_work, pts, anc, idx, proj);
     return hipGetLastError();
 }
 

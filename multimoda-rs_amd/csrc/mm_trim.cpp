@@ -18,7 +18,7 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_adjacency.h"
-#include "mm_mesh_stage.h"
+#include "mm_stage.h"
 
 namespace mm {
 namespace {
