@@ -25,6 +25,7 @@
  *   multimodars/ccta/fixing_functions.py:13-49     manual_hole_fill
  *   multimodars/ccta/__init__.py:432-499           create_wall_mesh (composed in Python from the pieces here)
  *   src/ccta/binding/ccta_py.rs:743-814            smooth_mesh_labels
+ *   multimodars/ccta/fixing_functions.py:196-219   checksurfdist / maxsurfdist (measured here: mm_point_mesh_distance)
  * Python entry points that bind them: src/ccta/binding/ccta_py.rs:52-481, 724-920 (discretize_vessel,
  * discretize_vessel_tree)
  * (find_centerline_bounded_points_simple, remove_occluded_points_ray_triangle, find_faces_near_points,
@@ -44,6 +45,8 @@
  * pass in exact f64 (mm_branch_kernels.hip); its lists are read off the masks on the host.
  * The mesh closing's edge table, winding, open half-edges, fans, volume and label votes run on the device
  * (mm_weld_kernels.hip, mm_close_kernels.hip); its walk over the rim is host C++.
+ * The surface distance's point-to-triangle minima, winning faces and closest points are computed on the device in exact
+ * f64 (mm_tri_kernels.hip); the staging order and the pruning bounds are host C++, its means are summed in Python.
  */
 #ifndef MM_CCTA_H
 #define MM_CCTA_H
@@ -657,6 +660,59 @@ int     mm_mesh_refine(mm_engine* e, const double* vertices_xyz, int64_t nv, con
                        double target_len, double ratio, int64_t max_passes, int64_t max_vertices, int64_t vert_cap,
                        int64_t face_cap, double* out_vertices, int64_t* out_tris, int64_t* out_parents,
                        mm_refine_report* report);
+
+/* ---- surface distance ---------------------------------------------------------------------------------------------
+ * How far a point lies from a triangle mesh: the quantity the reference bounds inside MeshLab while it remeshes
+ * (multimodars/ccta/fixing_functions.py:196-219, checksurfdist / maxsurfdist) and this project measures instead.
+ * tests/mm_checkers/surface_distance.py is the executable form of the rule.
+ *
+ * For a query p and a face (a, b, c), all arithmetic unfused f64, dot(u, v) = (ux*vx + uy*vy) + uz*vz, u + e*t one
+ * product and one sum per component, every quotient a true IEEE division.
+ *
+ * Proper faces take Ericson's closest point (Real-Time Collision Detection 5.1.5); the first test that holds wins:
+ *   1. ab = b-a, ac = c-a, ap = p-a; d1 = dot(ab,ap), d2 = dot(ac,ap).  d1 <= 0 && d2 <= 0: a (region 1).
+ *   2. bp = p-b; d3 = dot(ab,bp), d4 = dot(ac,bp).  d3 >= 0 && d4 <= d3: b (region 2).
+ *   3. vc = d1*d4 - d3*d2.  vc <= 0 && d1 >= 0 && d3 <= 0: a + ab*(d1/(d1-d3)) (edge ab, region 4).
+ *   4. cp = p-c; d5 = dot(ab,cp), d6 = dot(ac,cp).  d6 >= 0 && d5 <= d6: c (region 3).
+ *   5. vb = d5*d2 - d1*d6.  vb <= 0 && d2 >= 0 && d6 <= 0: a + ac*(d2/(d2-d6)) (edge ca, region 6).
+ *   6. va = d3*d6 - d5*d4.  va <= 0 && (d4-d3) >= 0 && (d5-d6) >= 0: b + (c-b)*((d4-d3)/((d4-d3)+(d5-d6))) (edge bc,
+ *      region 5).
+ *   7. otherwise s = (va+vb)+vc and the point is (a + ab*(vb/s)) + ac*(vc/s) (interior, region 0).
+ * d2(p, face) = dot(p-q, p-q) for the closest point q.
+ *
+ * Degenerate faces -- a repeated index, or every component of ab x ac = (aby*acz - abz*acy, abz*acx - abx*acz,
+ * abx*acy - aby*acx) exactly 0.0 -- take the smallest d2 over the segments ab, bc, ca in that order with strict <.  For a
+ * segment (u, v): e = v-u; l = dot(e,e); t = 0 where l == 0, else dot(p-u,e)/l, replaced by 0 where it is < 0 and by 1
+ * where it is > 1; the point is u + e*t.  The region is 4, 5 or 6 for the winning segment.
+ *
+ * The fold over faces is exact: face f replaces the best iff its d2 < best, so equal d2 keeps the lowest face index and a
+ * NaN d2 is never chosen; a query that no face beat returns +inf, face -1, closest NaN, region -1.  The result has one
+ * bit pattern whatever the chunking, the order or the pruning.  The device computes every d2 (mm_tri_kernels.hip). */
+
+typedef struct mm_surface_report {
+    int64_t items_pass_a;     /* (query block, face chunk) items that always run: one per query block */
+    int64_t items_pass_b;     /* the others, which first check their lower bound against the block's minima */
+    int64_t items_skipped;    /* those of pass B that the check skipped */
+    int64_t n_launches;
+    int64_t bytes_uploaded, bytes_downloaded;
+} mm_surface_report;
+
+/* out_sq[i] = the smallest d2 of query i over the nf faces; out_face (nullable) the winning face, out_closest (nullable,
+ * 3 per query) its closest point, out_region (nullable) the region.  nf == 0 or nq == 0 is valid.  MM_ERR_INVALID: a
+ * non-finite coordinate in vertices or queries, a face index out of range, nv, nf or nq of 2^31 or more; MM_ERR_TOO_LARGE:
+ * more than 2^31 - 1 (query block, chunk) items.  On an error the outputs are not written. */
+int     mm_point_mesh_distance(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                               const double* queries_xyz, int64_t nq, double* out_sq, int64_t* out_face,
+                               double* out_closest, int32_t* out_region, mm_surface_report* report);
+/* TEST HOOK (nothing in the product calls it; no engine, no device): the host side of mm_point_mesh_distance.
+ * face_order[j] = the face staged at position j, query_perm[j] = the query staged at position j (slabs across the longest
+ * axis of the faces' corners, faces by the sum of their corners: ascending up to one cell of a 20-bit quantisation of
+ * the range).  items (3 int32 each: 0 = pass A, 1 = pass B; first staged query q0; first staged face c0) and item_lb2 (the item's lower bound of every d2 between its queries and its
+ * faces) receive at most cap items, pass A first.  info[4] = {items of pass A, of pass B, queries per block, faces per
+ * chunk}.  Errors as mm_point_mesh_distance. */
+int     mm_tri_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf, const double* queries_xyz,
+                    int64_t nq, int32_t* face_order, int32_t* query_perm, int64_t* info, int32_t* items, double* item_lb2,
+                    int64_t cap);
 
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 

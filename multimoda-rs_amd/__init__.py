@@ -39,6 +39,9 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned, smooth_mesh,
                    filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh,
                    mesh_edge_lengths, edge_length_target, refine_mesh)
+from . import surface
+from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport, point_mesh_distance,
+                      sample_mesh_surface, surface_distance)
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -78,6 +81,8 @@ __all__ = [
     "condition_boundary_rings", "stitch_conditioned",
     "smooth_mesh", "filter_taubin", "filter_laplacian", "mesh_adjacency_csr", "vertex_rings", "postprocess_stitched_mesh",
     "mesh_edge_lengths", "edge_length_target", "refine_mesh",
+    "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
+    "DirectedDistance", "SurfaceDistanceReport",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

@@ -117,7 +117,7 @@ EXPORTS_CCTA = [
     "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
-    "mm_mesh_edge_lengths", "mm_mesh_refine",
+    "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -155,6 +155,12 @@ class MMRefineReport(C.Structure):
                 ("n_launches", C.c_int64), ("bytes_uploaded", C.c_int64), ("bytes_downloaded", C.c_int64),
                 ("longest_sq_before", C.c_double), ("longest_sq_after", C.c_double), ("volume_before", C.c_double),
                 ("volume_after", C.c_double)]
+
+
+class MMSurfaceReport(C.Structure):
+    """``mm_surface_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "items_pass_a", "items_pass_b", "items_skipped", "n_launches", "bytes_uploaded", "bytes_downloaded")]
 
 
 class MMRimParams(C.Structure):
@@ -573,6 +579,10 @@ def lib():
     L.mm_mesh_edge_lengths.argtypes = [P, P, I64, P, I64, I64, P, P, P]
     L.mm_mesh_refine.restype = I
     L.mm_mesh_refine.argtypes = [P, P, I64, P, I64, D, D, I64, I64, I64, I64, P, P, P, C.POINTER(MMRefineReport)]
+    L.mm_point_mesh_distance.restype = I
+    L.mm_point_mesh_distance.argtypes = [P, P, I64, P, I64, P, I64, P, P, P, P, C.POINTER(MMSurfaceReport)]
+    L.mm_tri_plan.restype = I
+    L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I
     L.mm_assign_rings_to_ends.argtypes = [P, P, I64, P, P, P]
     L.mm_ring_start.restype = I64

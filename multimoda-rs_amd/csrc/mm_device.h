@@ -161,6 +161,16 @@ hipError_t launch_nn3_sums(const NnPair* pairs, int n_pairs, const double* out, 
 int        nn_queries_per_block();
 int        nn_chunk_points();
 int        nn_span_chunks();
+// point-to-triangle distances (mm_tri_kernels.hip).  tri12: nf staged faces of 12 doubles (a, b, c as x y z w; a.w = the
+// bits of the degenerate flag, b.w = those of the original face index); qxyz: nq staged queries; work: n_a items of pass
+// A, then n_b of pass B.  sq: the minima's bits; key: original face << 32 | staged face of the winner (~0: none); closest:
+// 3 per query; region: one; counters[0] = items pass B skipped.  All outputs per query in staged order.
+hipError_t launch_tri_distance(const TriWork* work, int n_a, int n_b, const double* tri12, int nf, const double* qxyz, int nq,
+                               unsigned long long* sq, unsigned long long* key, double* closest, int32_t* region,
+                               unsigned long long* counters, hipStream_t s);
+int        tri_launches(int n_b);
+int        tri_queries_per_block();
+int        tri_chunk_faces();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
 // xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = n_rays x ceil(n_faces /
 // ray_chunk_faces()) records of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits at least 3

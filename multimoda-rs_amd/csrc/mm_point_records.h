@@ -1,6 +1,7 @@
-// mm_point_records.h -- the device records of the CCTA point kernels (mm_nn, mm_ray, mm_slice, mm_morph, mm_shape,
-// mm_branch, mm_bspline _kernels.hip), declared once for those kernels and for the host files that fill them (mm_ccta,
-// mm_discretize, mm_shape, mm_branch, mm_bspline .cpp); mm_device.h's launchers take them by type.  Plain C++; internal.
+// mm_point_records.h -- the device records of the CCTA point kernels (mm_nn, mm_tri, mm_ray, mm_slice, mm_morph,
+// mm_shape, mm_branch, mm_bspline _kernels.hip), declared once for those kernels and for the host files that fill them
+// (mm_ccta, mm_surface, mm_discretize, mm_shape, mm_branch, mm_bspline .cpp); mm_device.h's launchers take them by type.
+// Plain C++; internal.
 #pragma once
 
 #include <cstdint>
@@ -15,6 +16,9 @@ struct NnPair { int32_t q_off, nq, p_off, np, out_off, qperm_off; };
 struct NnWork { int32_t pair, q0, c0, n_chunks; double lb2; };
 // A derived set: pool[dst_off + j] = aux point aux_off + j moved by adj along its unit vector where its flag is set
 struct NnMorph { int32_t dst_off, n, aux_off, pad; double adj; };
+// mm_tri_kernels.hip: queries [q0, q0 + tri_queries_per_block()) x faces [c0, c0 + tri_chunk_faces()), both in staged
+// order; lb2: a lower bound of the squared distance between the two (pass B and the who pass of k_tri_min)
+struct TriWork { int32_t q0, c0; double lb2; };
 // mm_ray_kernels.hip: hits of one ray in one chunk of faces, closest (t, face)
 struct RayPartial { int32_t count, face; double t; };
 // mm_slice_kernels.hip, mm_morph_kernels.hip: points [p0, p0 + *_block_points()) of job `job`
@@ -30,6 +34,7 @@ struct BsplJob { int32_t p_off, m; };
 
 static_assert(sizeof(NnPair) == 24 && alignof(NnPair) == 4, "NnPair layout");
 static_assert(sizeof(NnWork) == 24 && alignof(NnWork) == 8, "NnWork layout");
+static_assert(sizeof(TriWork) == 16 && alignof(TriWork) == 8, "TriWork layout");
 static_assert(sizeof(NnMorph) == 24 && alignof(NnMorph) == 8, "NnMorph layout");
 static_assert(sizeof(RayPartial) == 16 && alignof(RayPartial) == 8, "RayPartial layout");
 static_assert(sizeof(PointWork) == 8 && alignof(PointWork) == 4, "PointWork layout");
