@@ -14,6 +14,7 @@
 
 #include "../../include/mm_ccta.h"
 #include "mm_adjacency.h"
+#include "mm_prune.h"
 #include "mm_stage.h"
 #include "mm_pool.h"
 #include "mm_trace.h"
@@ -32,40 +33,18 @@ struct Set3 {
     }
 };
 
-// Slab order of a point set: points sorted by their coordinate along the longest axis of the set's bounding
-// box (quantised to 20 bits, stable LSD radix sort), so that groups of consecutive points are slabs.
-// The sets here are vessel surfaces -- thin shells around a centerline -- and their nearest neighbours are
-// radial, i.e. in the same or the next slab; boxes of compact 3-D patches (k-d leaves, Morton runs) overlap
-// their neighbours and the opposite wall and prune far less (measured on the bench case: pass B 6.1 ms
-// with Morton runs, 3.5 ms with k-d leaves, 2.5 ms with slabs).  Any permutation gives the same minima.
+// Slab order of a point set (mm_prune.h, slab_permutation) along the longest axis of its bounding box.  The sets here are
+// vessel surfaces -- thin shells around a centerline -- and their nearest neighbours are radial, i.e. in the same or the
+// next slab; boxes of compact 3-D patches (k-d leaves, Morton runs) overlap their neighbours and the opposite wall and
+// prune far less (measured on the bench case: pass B 6.1 ms with Morton runs, 3.5 ms with k-d leaves, 2.5 ms with slabs).
 void slab_order(const Set3& st, std::vector<int32_t>& perm)
 {
-    const int64_t n = st.n;
-    perm.resize((size_t)n);
-    double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-    for (int64_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) { const double v = st.at(i, a); lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
-    int ax = 0;
-    for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[ax] - lo[ax]) ax = a;
-    const double sc = hi[ax] > lo[ax] ? 1048575.0 / (hi[ax] - lo[ax]) : 0.0;
-    std::vector<uint32_t> key((size_t)n), key2((size_t)n);
-    std::vector<int32_t> idx2((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const double t = (st.at(i, ax) - lo[ax]) * sc;
-        key[(size_t)i] = t > 0.0 ? (t < 1048575.0 ? (uint32_t)t : 1048575u) : 0u;   // NaN-safe clamp
-        perm[(size_t)i] = (int32_t)i;
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int sh = 10 * pass;
-        uint32_t cnt[1025] = {0};
-        for (int64_t i = 0; i < n; ++i) ++cnt[((key[(size_t)i] >> sh) & 1023u) + 1];
-        for (int b = 0; b < 1024; ++b) cnt[b + 1] += cnt[b];
-        for (int64_t i = 0; i < n; ++i) {
-            const uint32_t d = cnt[(key[(size_t)i] >> sh) & 1023u]++;
-            key2[d] = key[(size_t)i]; idx2[d] = perm[(size_t)i];
-        }
-        key.swap(key2); perm.swap(idx2);
-    }
+    Box3 all;
+    for (int64_t i = 0; i < st.n; ++i) { const double v[3] = {st.at(i, 0), st.at(i, 1), st.at(i, 2)}; all.add(v); }
+    const int ax = all.longest_axis();
+    std::vector<double> key((size_t)st.n);
+    for (int64_t i = 0; i < st.n; ++i) key[(size_t)i] = st.at(i, ax);
+    slab_permutation(key, perm);
 }
 
 // The host side of a nearest-neighbour batch, shared by the launch paths (nn_batch_view, radius_counts) and the
@@ -83,7 +62,7 @@ struct NnPlan {
     std::vector<int> owner;                    // device pair -> caller's pair
     int64_t nout = 0;
     std::vector<int64_t> goff;                 // first group of every set
-    std::vector<double> box;                   // lo xyz, hi xyz of every group (filled by nn_plan_stage_set)
+    std::vector<Box3> box;                     // of every group (filled by nn_plan_stage_set)
     int64_t npts() const { return soff.back(); }
 };
 
@@ -136,7 +115,7 @@ int nn_plan_pairs(const std::vector<Set3>& sets, const std::vector<std::array<in
         return set_error(MM_ERR_TOO_LARGE, std::string(what) + ": batch exceeds 2^30 points");
     pl.goff.assign(S + 1, 0);
     for (size_t s = 0; s < S; ++s) pl.goff[s + 1] = pl.goff[s] + (sets[s].n + pl.qpb - 1) / pl.qpb;
-    pl.box.assign((size_t)pl.goff.back() * 6, 0.0);
+    pl.box.assign((size_t)pl.goff.back(), Box3{});
     return MM_OK;
 }
 
@@ -147,36 +126,24 @@ void nn_plan_stage_set(const std::vector<Set3>& sets, NnPlan& pl, size_t si, dou
     const Set3& st = sets[si];
     const int32_t* pm = pl.perm_of[si] >= 0 ? pl.perms[(size_t)pl.perm_of[si]].data() : nullptr;
     for (int64_t g0 = 0, g = pl.goff[si]; g0 < st.n; g0 += pl.qpb, ++g) {
-        double* b = pl.box.data() + (size_t)g * 6;
-        b[0] = b[1] = b[2] = DBL_MAX; b[3] = b[4] = b[5] = -DBL_MAX;
+        Box3& b = pl.box[(size_t)g] = Box3{};
         for (int64_t j = g0; j < std::min<int64_t>(st.n, g0 + pl.qpb); ++j) {
             const int64_t i = pm ? (int64_t)pm[j] : j;
             const double v[3] = {st.at(i, 0), st.at(i, 1), st.at(i, 2)};
             if (dx) { dx[j] = v[0]; dy[j] = v[1]; dz[j] = v[2]; }
-            for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], v[a]); b[3 + a] = std::max(b[3 + a], v[a]); }
+            b.add(v);
         }
     }
 }
 
-// squared distance between two boxes, shaved so that rounding can never overstate it
-inline double box_lb2(const double* a, const double* b)
-{
-    double s = 0.0;
-    for (int ax = 0; ax < 3; ++ax) {
-        const double gap = std::max(0.0, std::max(a[ax] - b[3 + ax], b[ax] - a[3 + ax]));
-        s += gap * gap;
-    }
-    return s * (1.0 - 1e-12);
-}
-
 // lb2 of query block qb of set q against chunk c of set p: a chunk's box is the union of its groups', so the smallest
-// of their distances
+// of their bounds (mm_prune.h, box_lb2; the points lie in their boxes exactly: no slack)
 inline double chunk_lb2(const NnPlan& pl, int32_t q, int64_t qb, int32_t p, int64_t c, int gpc)
 {
-    const double* bq = pl.box.data() + (size_t)(pl.goff[(size_t)q] + qb) * 6;
+    const Box3& bq = pl.box[(size_t)(pl.goff[(size_t)q] + qb)];
     double lb2 = DBL_MAX;
     for (int64_t g = c * gpc; g < std::min<int64_t>((c + 1) * gpc, pl.goff[(size_t)p + 1] - pl.goff[(size_t)p]); ++g)
-        lb2 = std::min(lb2, box_lb2(bq, pl.box.data() + (size_t)(pl.goff[(size_t)p] + g) * 6));
+        lb2 = std::min(lb2, box_lb2(bq, pl.box[(size_t)(pl.goff[(size_t)p] + g)], 0.0));
     return lb2;
 }
 
@@ -197,10 +164,9 @@ void nn_plan_min_items(const NnPlan& pl, const std::vector<std::array<int32_t, 2
                 wa.push_back(NnWork{(int32_t)i, (int32_t)q0, (int32_t)c0, pl.span, 0.0});
         return;
     }
-    std::vector<std::pair<double, int32_t>> cand((size_t)n_chunks);
+    std::vector<std::pair<double, int32_t>> cand;
     for (int64_t q0 = 0, qb = 0; q0 < nq; q0 += qpb, ++qb) {
-        for (int64_t c = 0; c < n_chunks; ++c) cand[(size_t)c] = {chunk_lb2(pl, q, qb, p, c, gpc), (int32_t)c};
-        std::sort(cand.begin(), cand.end());   // nearest chunks first: they tighten the minima the others check
+        nearest_first(n_chunks, [&](int64_t c) { return chunk_lb2(pl, q, qb, p, c, gpc); }, cand);
         wa.push_back(NnWork{(int32_t)i, (int32_t)q0, cand[0].second * ch, 1, 0.0});
         for (size_t c = 1; c < cand.size(); ++c)
             wb.push_back(NnWork{(int32_t)i, (int32_t)q0, cand[c].second * ch, 1, cand[c].first});
@@ -221,15 +187,85 @@ void nn_plan_count_items(const NnPlan& pl, const std::vector<std::array<int32_t,
         }
 }
 
+// The staging both nearest-neighbour launches share, through the engine's two pinned buffers: the point pool (x, y, z
+// planes, the permutations, then what the caller carves behind them) in host_pts; pairs and work lists in host_lvl,
+// which also receives the results, so that nothing in host_pts moves.  dev_pts holds them in that order, outputs last.
+struct NnStage {
+    Carve cv;
+    size_t o_x, o_y, o_z, o_perm, o_pairs = 0, o_work[2] = {0, 0}, n_work[2] = {0, 0}, in_bytes = 0, o_out = 0, o_out2 = 0;
+    unsigned char *h = nullptr, *hl = nullptr, *d = nullptr;
+
+    explicit NnStage(const NnPlan& pl)
+        : o_x(cv.take((size_t)pl.npts() * 8)), o_y(cv.take((size_t)pl.npts() * 8)), o_z(cv.take((size_t)pl.npts() * 8)),
+          o_perm(cv.take((size_t)pl.perm_off.back() * 4)) {}
+    template <class T> T* dev(size_t off) const { return (T*)(d + off); }
+
+    // Pins host_pts for everything carved so far and fills the group boxes of every set, the staged coordinates of the
+    // sets that exist on the host (the device writes a derived set's) and the permutations; extra(k), k < n_extra, runs
+    // on the same worker pool.
+    template <class Extra>
+    int points(Engine* e, const std::vector<Set3>& sets, NnPlan& pl, size_t n_extra, Extra extra)
+    {
+        if (const int rc = e->ensure(e->host_pts, cv.size(), true)) return rc;
+        h = (unsigned char*)e->host_pts.p;
+        double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
+        const size_t S = sets.size();
+        parallel_for((int)(S + n_extra), [&](int job) {
+            const size_t si = (size_t)job;
+            if (si >= S) return extra(si - S);
+            nn_plan_stage_set(sets, pl, si, sets[si].unit ? nullptr : hx + pl.soff[si], hy + pl.soff[si], hz + pl.soff[si]);
+        });
+        for (size_t k = 0; k < pl.perms.size(); ++k)
+            std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
+        return MM_OK;
+    }
+    // Builds the work lists over the worker pool (items(i, w0, w1) appends device pair i's; each list is pair-major),
+    // carves pairs, lists and the two outputs behind the points, sizes host_lvl and dev_pts, fills host_lvl.
+    template <class Items>
+    int work(Engine* e, const NnPlan& pl, Items items, const char* too_many, size_t out_bytes, size_t out2_bytes)
+    {
+        const size_t P = pl.hp.size();
+        std::vector<std::vector<NnWork>> per[2] = {std::vector<std::vector<NnWork>>(P), std::vector<std::vector<NnWork>>(P)};
+        { TraceTimer tt("nn: work lists");
+        parallel_for((int)P, [&](int i) { items((size_t)i, per[0][(size_t)i], per[1][(size_t)i]); });
+        }
+        o_pairs = cv.take(P * sizeof(NnPair));
+        for (int l = 0; l < 2; ++l) {
+            for (const auto& v : per[l]) n_work[l] += v.size();
+            o_work[l] = cv.take(n_work[l] * sizeof(NnWork));
+        }
+        if (n_work[0] + n_work[1] > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, too_many);
+        in_bytes = cv.size();
+        o_out = cv.take(out_bytes); o_out2 = cv.take(out2_bytes);
+        if (const int rc = e->ensure(e->host_lvl, std::max(in_bytes - o_pairs, out_bytes), true)) return rc;
+        if (const int rc = e->ensure(e->dev_pts, cv.size(), false)) return rc;
+        hl = (unsigned char*)e->host_lvl.p; d = (unsigned char*)e->dev_pts.p;
+        std::memcpy(hl, pl.hp.data(), P * sizeof(NnPair));
+        for (int l = 0; l < 2; ++l) {
+            NnWork* dst = (NnWork*)(hl + (o_work[l] - o_pairs));
+            for (const auto& v : per[l]) dst = std::copy(v.begin(), v.end(), dst);
+        }
+        return MM_OK;
+    }
+    int send(Engine* e, bool pool = true) const   // the point pool (unless the caller sent its parts), then pairs and lists
+    {
+        if (pool) MM_TRY_HIP(hipMemcpyAsync(d, h, o_pairs, hipMemcpyHostToDevice, e->stream));
+        MM_TRY_HIP(hipMemcpyAsync(d + o_pairs, hl, in_bytes - o_pairs, hipMemcpyHostToDevice, e->stream));
+        return MM_OK;
+    }
+    int fetch(Engine* e, size_t off, size_t bytes) const   // device output at `off` into host_lvl; synchronises
+    {
+        MM_TRY_HIP(hipMemcpyAsync(hl, d + off, bytes, hipMemcpyDeviceToHost, e->stream));
+        MM_TRY_HIP(hipStreamSynchronize(e->stream));
+        return MM_OK;
+    }
+};
+
 // Per-query minima of every pair (sets[q] against sets[p]); one upload, two launches, one download.
 // view[k] = {pointer, count}: pair k's minima, in the query set's ORIGINAL order, inside the engine's pinned
 // staging buffer (valid until the next call on this engine); pointer == nullptr means "all +inf" (an empty
 // point set) or no queries.
-// order_like (nullable, one entry per set): the set whose spatial order this one shares -- a morphed copy of
-// a set moves every point by at most a few mm, so the 41 scalings of a search reuse one sort.  Large sets
-// are staged in slab order and every (query block, chunk) item carries the squared distance between the
-// two bounding boxes; the kernel skips items that cannot lower any of their queries' minima.  Minima are
-// exact and order-independent: pruned or not, sorted or not, the results are the same bits.
+// order_like: as nn_plan_pairs takes it.  Pruned or not, sorted or not, the results are the same bits.
 struct MinView { const double* p; int64_t n; };
 
 // sums (nullable): if given, only the per-pair sums of the minima (sequential, index order) come back
@@ -247,9 +283,7 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     if (rc) return rc;
     for (size_t k = 0; k < pr.size(); ++k) view[k].n = sets[(size_t)pr[k][0]].n;   // fold(INFINITY, min) over an empty set: all +inf
     if (pl.hp.empty()) return MM_OK;
-    const int64_t npts = pl.npts(), nout = pl.nout;
-
-    // ---- stage the points (permuted where sorted) and the bounding box of every group of qpb points ---
+    const int64_t nout = pl.nout;
     // derived sets: only their boxes are computed here; their coordinates are produced on the device from
     // an auxiliary pool (base point, unit vector, flag per point; one entry per distinct base + order)
     struct Aux { const double* xyz; const double* unit; const uint8_t* has; int32_t perm; int64_t n, off; };
@@ -268,98 +302,58 @@ int nn_batch_view(Engine* e, const std::vector<Set3>& sets, const std::vector<st
     std::vector<NnMorph> morphs;
     for (size_t s = 0; s < S; ++s)
         if (aux_of[s] >= 0) morphs.push_back(NnMorph{(int32_t)pl.soff[s], (int32_t)sets[s].n, (int32_t)aux[(size_t)aux_of[s]].off, 0, sets[s].adj});
-    Carve cv;
-    const size_t o_x = cv.take((size_t)npts * 8), o_y = cv.take((size_t)npts * 8), o_z = cv.take((size_t)npts * 8);
-    const size_t o_perm = cv.take((size_t)pl.perm_off.back() * 4), o_aux = cv.take((size_t)naux * 7 * 8);
-    const size_t o_morph = cv.take(morphs.size() * sizeof(NnMorph));
-    const size_t pts_bytes = cv.size();   // the pairs and the work lists follow once they are known
-    if ((rc = e->ensure(e->host_pts, pts_bytes, true))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
-    double* haux = (double*)(h + o_aux);   // 7 planes of naux: bx by bz ux uy uz flag
+    NnStage st(pl);
+    const size_t o_aux = st.cv.take((size_t)naux * 7 * 8), o_morph = st.cv.take(morphs.size() * sizeof(NnMorph));
     { TraceTimer tt("nn: stage points + boxes");
-    parallel_for((int)(S + aux.size()), [&](int job) {
-        if ((size_t)job >= S) {   // one auxiliary pool entry
-            const Aux& ax = aux[(size_t)job - S];
-            const int32_t* pm = ax.perm >= 0 ? pl.perms[(size_t)ax.perm].data() : nullptr;
-            for (int64_t j = 0; j < ax.n; ++j) {
-                const int64_t i = pm ? (int64_t)pm[j] : j;
-                for (int a = 0; a < 3; ++a) {
-                    haux[(size_t)a * (size_t)naux + (size_t)(ax.off + j)] = ax.xyz[3 * i + a];
-                    haux[(size_t)(3 + a) * (size_t)naux + (size_t)(ax.off + j)] = ax.unit[3 * i + a];
-                }
-                haux[(size_t)6 * (size_t)naux + (size_t)(ax.off + j)] = ax.has[i] ? 1.0 : 0.0;
+    rc = st.points(e, sets, pl, aux.size(), [&](size_t k) {   // one auxiliary pool entry: 7 planes of naux, bx by bz ux uy uz flag
+        double* haux = (double*)(st.h + o_aux);
+        const Aux& ax = aux[k];
+        const int32_t* pm = ax.perm >= 0 ? pl.perms[(size_t)ax.perm].data() : nullptr;
+        for (int64_t j = 0; j < ax.n; ++j) {
+            const int64_t i = pm ? (int64_t)pm[j] : j;
+            for (int a = 0; a < 3; ++a) {
+                haux[(size_t)a * (size_t)naux + (size_t)(ax.off + j)] = ax.xyz[3 * i + a];
+                haux[(size_t)(3 + a) * (size_t)naux + (size_t)(ax.off + j)] = ax.unit[3 * i + a];
             }
-            return;
+            haux[(size_t)6 * (size_t)naux + (size_t)(ax.off + j)] = ax.has[i] ? 1.0 : 0.0;
         }
-        const size_t si = (size_t)job;
-        const bool derived = aux_of[si] >= 0;
-        nn_plan_stage_set(sets, pl, si, derived ? nullptr : hx + pl.soff[si], hy + pl.soff[si], hz + pl.soff[si]);
     });
+    if (rc) return rc;
     }
-    for (size_t k = 0; k < pl.perms.size(); ++k)
-        std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
-    if (!morphs.empty()) std::memcpy(h + o_morph, morphs.data(), morphs.size() * sizeof(NnMorph));
+    if (!morphs.empty()) std::memcpy(st.h + o_morph, morphs.data(), morphs.size() * sizeof(NnMorph));
 
-    // ---- work lists -------------------------------------------------------------------------------
-    TraceTimer tt_wl("nn: work lists");
-    std::vector<std::vector<NnWork>> la(pl.hp.size()), lb(pl.hp.size());   // per pair, built over the worker pool
-    parallel_for((int)pl.hp.size(), [&](int ii) { nn_plan_min_items(pl, pr, (size_t)ii, la[(size_t)ii], lb[(size_t)ii]); });
-    std::vector<NnWork> wa, wb;
-    {
-        size_t na_ = 0, nb_ = 0;
-        for (size_t i = 0; i < pl.hp.size(); ++i) { na_ += la[i].size(); nb_ += lb[i].size(); }
-        wa.reserve(na_); wb.reserve(nb_);
-        for (size_t i = 0; i < pl.hp.size(); ++i) { wa.insert(wa.end(), la[i].begin(), la[i].end()); wb.insert(wb.end(), lb[i].begin(), lb[i].end()); }
-    }
-    if (wa.size() + wb.size() > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "nn batch exceeds 2^30 work items");
-    tt_wl.stop();
+    // pass A and pass B lists (nn_plan_min_items), the minima and the per-pair sums behind them
+    rc = st.work(e, pl, [&](size_t i, std::vector<NnWork>& wa, std::vector<NnWork>& wb) { nn_plan_min_items(pl, pr, i, wa, wb); },
+                 "nn batch exceeds 2^30 work items", (size_t)nout * 8, pl.hp.size() * 8);
+    if (rc) return rc;
     TraceTimer tt_dev("nn: copies + kernels");
-
-    const size_t o_pairs = cv.take(pl.hp.size() * sizeof(NnPair)), o_wa = cv.take(wa.size() * sizeof(NnWork));
-    const size_t o_wb = cv.take(wb.size() * sizeof(NnWork)), in_bytes = cv.size();
-    const size_t o_out = cv.take((size_t)nout * 8), o_sums = cv.take(pl.hp.size() * 8), total = cv.size();
-    // descriptors and results go through the level buffers (the point staging above is still in flight-free
-    // pinned memory of its own), so nothing staged so far moves
-    if ((rc = e->ensure(e->host_lvl, std::max(in_bytes - o_pairs, (size_t)nout * 8), true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* hl = (unsigned char*)e->host_lvl.p;
-    std::memcpy(hl, pl.hp.data(), pl.hp.size() * sizeof(NnPair));
-    std::memcpy(hl + (o_wa - o_pairs), wa.data(), wa.size() * sizeof(NnWork));
-    std::memcpy(hl + (o_wb - o_pairs), wb.data(), wb.size() * sizeof(NnWork));
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    if (morphs.empty()) {
-        MM_TRY_HIP(hipMemcpyAsync(d, h, pts_bytes, hipMemcpyHostToDevice, e->stream));
-    } else {
+    if (!morphs.empty()) {
         // only the sets that exist on the host travel; the derived ones are written by the device
         for (size_t s2 = 0; s2 < S; ++s2) {
             if (aux_of[s2] >= 0 || sets[s2].n == 0) continue;
-            for (size_t o : {o_x, o_y, o_z})
-                MM_TRY_HIP(hipMemcpyAsync(d + o + (size_t)pl.soff[s2] * 8, h + o + (size_t)pl.soff[s2] * 8, (size_t)sets[s2].n * 8,
-                                          hipMemcpyHostToDevice, e->stream));
+            for (size_t o : {st.o_x + (size_t)pl.soff[s2] * 8, st.o_y + (size_t)pl.soff[s2] * 8, st.o_z + (size_t)pl.soff[s2] * 8})
+                MM_TRY_HIP(hipMemcpyAsync(st.d + o, st.h + o, (size_t)sets[s2].n * 8, hipMemcpyHostToDevice, e->stream));
         }
-        MM_TRY_HIP(hipMemcpyAsync(d + o_perm, h + o_perm, o_pairs - o_perm, hipMemcpyHostToDevice, e->stream));
-        const hipError_t hm = launch_nn3_morph((const NnMorph*)(d + o_morph), (int)morphs.size(), (const double*)(d + o_aux), naux,
-                                               (double*)(d + o_x), (double*)(d + o_y), (double*)(d + o_z), e->stream);
+        MM_TRY_HIP(hipMemcpyAsync(st.d + st.o_perm, st.h + st.o_perm, st.o_pairs - st.o_perm, hipMemcpyHostToDevice, e->stream));
+        const hipError_t hm = launch_nn3_morph(st.dev<const NnMorph>(o_morph), (int)morphs.size(), st.dev<const double>(o_aux), naux,
+                                               st.dev<double>(st.o_x), st.dev<double>(st.o_y), st.dev<double>(st.o_z), e->stream);
         if (hm != hipSuccess) return hip_error(hm, "morph launch");
     }
-    MM_TRY_HIP(hipMemcpyAsync(d + o_pairs, hl, in_bytes - o_pairs, hipMemcpyHostToDevice, e->stream));
-    const NnPair* d_pairs = (const NnPair*)(d + o_pairs);
-    const hipError_t he = launch_nn3_min(d_pairs, (const NnWork*)(d + o_wa), (int)wa.size(), (const NnWork*)(d + o_wb),
-                                         (int)wb.size(), (const double*)(d + o_x), (const double*)(d + o_y), (const double*)(d + o_z),
-                                         (const int32_t*)(d + o_perm), (double*)(d + o_out), nout, e->stream);
+    if ((rc = st.send(e, morphs.empty()))) return rc;
+    const NnPair* d_pairs = st.dev<const NnPair>(st.o_pairs);
+    const hipError_t he = launch_nn3_min(d_pairs, st.dev<const NnWork>(st.o_work[0]), (int)st.n_work[0], st.dev<const NnWork>(st.o_work[1]),
+                                         (int)st.n_work[1], st.dev<const double>(st.o_x), st.dev<const double>(st.o_y), st.dev<const double>(st.o_z),
+                                         st.dev<const int32_t>(st.o_perm), st.dev<double>(st.o_out), nout, e->stream);
     if (he != hipSuccess) return hip_error(he, "nearest-neighbour launch");
     if (sums) {
-        const hipError_t hs = launch_nn3_sums(d_pairs, (int)pl.hp.size(), (const double*)(d + o_out), (double*)(d + o_sums), e->stream);
+        const hipError_t hs = launch_nn3_sums(d_pairs, (int)pl.hp.size(), st.dev<const double>(st.o_out), st.dev<double>(st.o_out2), e->stream);
         if (hs != hipSuccess) return hip_error(hs, "sum launch");
-        MM_TRY_HIP(hipMemcpyAsync(hl, d + o_sums, pl.hp.size() * 8, hipMemcpyDeviceToHost, e->stream));
-        MM_TRY_HIP(hipStreamSynchronize(e->stream));
-        for (size_t i = 0; i < pl.hp.size(); ++i) (*sums)[(size_t)pl.owner[i]] = ((const double*)hl)[i];
+        if ((rc = st.fetch(e, st.o_out2, pl.hp.size() * 8))) return rc;
+        for (size_t i = 0; i < pl.hp.size(); ++i) (*sums)[(size_t)pl.owner[i]] = ((const double*)st.hl)[i];
         return MM_OK;
     }
-    MM_TRY_HIP(hipMemcpyAsync(hl, d + o_out, (size_t)nout * 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    const double* res = (const double*)hl;
+    if ((rc = st.fetch(e, st.o_out, (size_t)nout * 8))) return rc;
+    const double* res = (const double*)st.hl;
     for (size_t i = 0; i < pl.hp.size(); ++i) view[(size_t)pl.owner[i]].p = res + pl.hp[i].out_off;
     return MM_OK;
 }
@@ -509,55 +503,27 @@ int region_points(Engine* e, const double* an, int64_t n, const double* ref, int
 
 // ---- neighbour counts within a radius (clean_up_non_section_points, scale_coronary.rs:342-409) ------------
 // counts[k][i] = #{p in sets[pr[k][1]] : |q_i - p|^2 <= r2} for every query q_i of sets[pr[k][0]], exact f64 on
-// the device (k_nn3_count).  Large sets are staged in slab order and only the (query block, chunk) combinations
-// whose bounding boxes come within the radius are launched; a count does not depend on the order.
+// the device (k_nn3_count) over the items of nn_plan_count_items; a count does not depend on the order.
 int radius_counts(Engine* e, const std::vector<Set3>& sets, const std::vector<std::array<int32_t, 2>>& pr, double r2,
                   std::vector<std::vector<uint32_t>>& counts)
 {
     counts.assign(pr.size(), {});
-    const size_t S = sets.size();
     NnPlan pl;
     int rc = nn_plan_pairs(sets, pr, nullptr, "radius counts", pl);
     if (rc) return rc;
     for (size_t k = 0; k < pr.size(); ++k) counts[k].assign((size_t)sets[(size_t)pr[k][0]].n, 0u);
     if (pl.hp.empty()) return MM_OK;
-    const int64_t npts = pl.npts(), nout = pl.nout;
-
-    // staged points (slab order where sorted) + bounding boxes of groups of qpb points (a chunk's box is the union of
-    // its ch / qpb groups)
-    Carve cv;
-    const size_t o_x = cv.take((size_t)npts * 8), o_y = cv.take((size_t)npts * 8), o_z = cv.take((size_t)npts * 8);
-    const size_t o_perm = cv.take((size_t)pl.perm_off.back() * 4), o_pairs = cv.take(pl.hp.size() * sizeof(NnPair));
-    if ((rc = e->ensure(e->host_pts, o_pairs, true))) return rc;
-    unsigned char* h = (unsigned char*)e->host_pts.p;
-    double *hx = (double*)(h + o_x), *hy = (double*)(h + o_y), *hz = (double*)(h + o_z);
-    parallel_for((int)S, [&](int si) { nn_plan_stage_set(sets, pl, (size_t)si, hx + pl.soff[(size_t)si], hy + pl.soff[(size_t)si], hz + pl.soff[(size_t)si]); });
-    for (size_t k = 0; k < pl.perms.size(); ++k)
-        std::memcpy(h + o_perm + (size_t)pl.perm_off[k] * 4, pl.perms[k].data(), pl.perms[k].size() * 4);
-
-    std::vector<std::vector<NnWork>> lw(pl.hp.size());
-    parallel_for((int)pl.hp.size(), [&](int ii) { nn_plan_count_items(pl, pr, (size_t)ii, r2, lw[(size_t)ii]); });
-    std::vector<NnWork> work;
-    for (auto& v : lw) work.insert(work.end(), v.begin(), v.end());
-    if (work.size() > (size_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "radius counts: too many work items");
-
-    const size_t o_work = cv.take(work.size() * sizeof(NnWork)), in_bytes = cv.size();
-    const size_t o_out = cv.take((size_t)nout * 4), total = cv.size();
-    if ((rc = e->ensure(e->host_lvl, std::max(in_bytes - o_pairs, (size_t)nout * 4), true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, total, false))) return rc;
-    unsigned char* hl = (unsigned char*)e->host_lvl.p;
-    std::memcpy(hl, pl.hp.data(), pl.hp.size() * sizeof(NnPair));
-    if (!work.empty()) std::memcpy(hl + (o_work - o_pairs), work.data(), work.size() * sizeof(NnWork));
-    unsigned char* d = (unsigned char*)e->dev_pts.p;
-    MM_TRY_HIP(hipMemcpyAsync(d, h, o_pairs, hipMemcpyHostToDevice, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(d + o_pairs, hl, in_bytes - o_pairs, hipMemcpyHostToDevice, e->stream));
-    const hipError_t he = launch_nn3_count((const NnPair*)(d + o_pairs), (const NnWork*)(d + o_work), (int)work.size(), (const double*)(d + o_x), (const double*)(d + o_y),
-                                           (const double*)(d + o_z), (const int32_t*)(d + o_perm), r2, (unsigned int*)(d + o_out), nout,
-                                           e->stream);
+    NnStage st(pl);
+    if ((rc = st.points(e, sets, pl, 0, [](size_t) {}))) return rc;
+    rc = st.work(e, pl, [&](size_t i, std::vector<NnWork>& w, std::vector<NnWork>&) { nn_plan_count_items(pl, pr, i, r2, w); },
+                 "radius counts: too many work items", (size_t)pl.nout * 4, 0);
+    if (rc || (rc = st.send(e))) return rc;
+    const hipError_t he = launch_nn3_count(st.dev<const NnPair>(st.o_pairs), st.dev<const NnWork>(st.o_work[0]), (int)st.n_work[0],
+                                           st.dev<const double>(st.o_x), st.dev<const double>(st.o_y), st.dev<const double>(st.o_z),
+                                           st.dev<const int32_t>(st.o_perm), r2, st.dev<unsigned int>(st.o_out), pl.nout, e->stream);
     if (he != hipSuccess) return hip_error(he, "radius-count launch");
-    MM_TRY_HIP(hipMemcpyAsync(hl, d + o_out, (size_t)nout * 4, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    const uint32_t* res = (const uint32_t*)hl;
+    if ((rc = st.fetch(e, st.o_out, (size_t)pl.nout * 4))) return rc;
+    const uint32_t* res = (const uint32_t*)st.hl;
     for (size_t i = 0; i < pl.hp.size(); ++i)
         std::memcpy(counts[(size_t)pl.owner[i]].data(), res + pl.hp[i].out_off, (size_t)pl.hp[i].nq * 4);
     return MM_OK;

@@ -9,21 +9,16 @@
 //
 // Mapping: one work item = 256 lanes x QPT queries of one pair against a SPAN of chunks of CH points; a
 // chunk is staged in LDS as (x, y, z, 0) so that a point is two ds_read broadcasts (all lanes read the
-// same address: conflict-free).  The span minima are merged into the output with a 64-bit atomicMin on the
-// bit pattern (order-preserving for values >= 0; the output is pre-filled with +inf).
-// Per (query, point): 3 sub + 3 mul + 2 add + 1 min = 9 fp64 VALU operations against 2/QPT LDS reads
-// -> fp64-VALU bound.  Sets are SoA f64 in HBM (L2-resident: a set is a few hundred KB).
-//
-// Pruning (large sets, staged in slabs across their longest axis by the host so that a block of queries and a chunk of points
-// are each spatially compact): the host hands every (query block, chunk) item a lower bound lb2 of the
-// squared distance between their bounding boxes.  Pass A runs, per query block, the chunk with the smallest
-// bound; pass B runs all the others, and an item starts by reading its queries' current minima: if none
-// exceeds lb2, no point of the chunk can lower any of them and the item is skipped.  The minimum is exact
-// and order-independent, so the result is bit-identical to scanning everything; only work is saved.
+// same address: conflict-free).  Per (query, point): 3 sub + 3 mul + 2 add + 1 min = 9 fp64 VALU operations
+// against 2/QPT LDS reads -> fp64-VALU bound.  Sets are SoA f64 in HBM (L2-resident: a set is a few hundred KB).
 // The work lists are pair-major and dealt to the XCDs in contiguous eighths (as in mm_kernels.hip).
+//
+// Pruning (mm_prune.h, mm_prune_device.h): large sets are staged in slabs and an item of pass B
+// (k_nn3_min<.., true>) is one (query block, chunk) with its bound; the others scan a span unchecked.
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_prune_device.h"
 #include "mm_xcd.h"
 
 namespace mm {
@@ -35,7 +30,7 @@ __global__ void __launch_bounds__(256)
 k_nn3_fill(unsigned long long* __restrict__ out, long long n)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = 0x7ff0000000000000ull;   // +inf
+    if (i < n) out[i] = kInfBits;
 }
 
 // A derived set (NnMorph): pool[dst_off + j] = base point j moved by adj along its unit vector where its flag is set,
@@ -59,15 +54,17 @@ k_nn3_morph(const NnMorph* __restrict__ items, const double* __restrict__ aux, l
     pz[it.dst_off + j] = mv ? bz + uz * it.adj : bz;
 }
 
-template <int QPT, bool CHECK>
-__global__ void __launch_bounds__(256)
-k_nn3_min(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int n_work,
-          const double* __restrict__ px, const double* __restrict__ py, const double* __restrict__ pz,
-          const int32_t* __restrict__ qperm, unsigned long long* __restrict__ out)
+// The body of k_nn3_min and k_nn3_count: every work item's queries against its span of chunks.  What a lane keeps of a
+// query's squared distances v is the fold: acc = step(acc, v) from `start`, then merge(&out[query], acc).
+// CHECK (pass B of the minimum): an item first reads its queries' current minima and is skipped if its bound says so.
+template <int QPT, bool CHECK, class Acc, class Step, class Merge, class Out>
+__device__ __forceinline__ void nn3_scan(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int n_work,
+                                         const double* __restrict__ px, const double* __restrict__ py,
+                                         const double* __restrict__ pz, const int32_t* __restrict__ qperm, Acc start,
+                                         Step step, Merge merge, Out* __restrict__ out)
 {
     constexpr int NT = 256, CH = kNnChunk;
     __shared__ double4 s_p[CH];
-    __shared__ unsigned long long s_max;
     const int tid = threadIdx.x;
     for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
          wi += gridDim.x) {
@@ -79,26 +76,22 @@ k_nn3_min(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int
             const int q = w.q0 + k * NT + tid;
             oi[k] = q < pd.nq ? (pd.qperm_off >= 0 ? qperm[pd.qperm_off + q] : q) : -1;
         }
-        if (CHECK) {
-            // largest current minimum of this block's queries (a stale, larger value only costs work)
+        if constexpr (CHECK) {
+            __shared__ unsigned long long s_max;
             unsigned long long mx = 0ull;
 #pragma unroll
             for (int k = 0; k < QPT; ++k)
                 if (oi[k] >= 0) { const unsigned long long v = out[pd.out_off + oi[k]]; mx = v > mx ? v : mx; }
-            __syncthreads();   // s_max of the previous item is no longer read
-            if (tid == 0) s_max = 0ull;
-            __syncthreads();
-            atomicMax(&s_max, mx);
-            __syncthreads();
-            if (w.lb2 >= __longlong_as_double((long long)s_max)) continue;   // uniform: nothing here can improve
+            if (skip_item(Skip::cannot_lower, w.lb2, __longlong_as_double((long long)block_max(mx, &s_max)))) continue;
         }
-        double qx[QPT], qy[QPT], qz[QPT], m[QPT];
+        double qx[QPT], qy[QPT], qz[QPT];
+        Acc acc[QPT];
 #pragma unroll
         for (int k = 0; k < QPT; ++k) {
             const int q = w.q0 + k * NT + tid;
             const int qc = q < pd.nq ? q : pd.nq - 1;   // lanes past the end recompute the last query, never stored
             qx[k] = px[pd.q_off + qc]; qy[k] = py[pd.q_off + qc]; qz[k] = pz[pd.q_off + qc];
-            m[k] = __builtin_inf();
+            acc[k] = start;
         }
         const int c_end = pd.np - w.c0 < w.n_chunks * CH ? pd.np : w.c0 + w.n_chunks * CH;
         for (int c0 = w.c0; c0 < c_end; c0 += CH) {
@@ -114,19 +107,25 @@ k_nn3_min(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int
                 for (int k = 0; k < QPT; ++k) {
                     const double dx = qx[k] - p.x, dy = qy[k] - p.y, dz = qz[k] - p.z;
                     const double v = dx * dx + dy * dy + dz * dz;
-                    m[k] = __builtin_fmin(m[k], v);
+                    acc[k] = step(acc[k], v);
                 }
             }
         }
-        // the stored values only ever decrease, so a (possibly stale) plain read that is already <= ours
-        // proves the atomic would change nothing: most chunks of pass B improve few of their queries
 #pragma unroll
         for (int k = 0; k < QPT; ++k)
-            if (oi[k] >= 0) {
-                const unsigned long long v = (unsigned long long)__double_as_longlong(m[k]);
-                if (v < out[pd.out_off + oi[k]]) atomicMin(&out[pd.out_off + oi[k]], v);
-            }
+            if (oi[k] >= 0) merge(&out[pd.out_off + oi[k]], acc[k]);
     }
+}
+
+template <int QPT, bool CHECK>
+__global__ void __launch_bounds__(256)
+k_nn3_min(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, int n_work,
+          const double* __restrict__ px, const double* __restrict__ py, const double* __restrict__ pz,
+          const int32_t* __restrict__ qperm, unsigned long long* __restrict__ out)
+{
+    nn3_scan<QPT, CHECK>(pairs, work, n_work, px, py, pz, qperm, __builtin_inf(),
+                         [](double m, double v) { return __builtin_fmin(m, v); },   // a NaN v is never taken
+                         [](unsigned long long* o, double m) { merge_min(o, (unsigned long long)__double_as_longlong(m)); }, out);
 }
 
 // Radius counts: cnt[q] += #{p in the chunk : |q - p|^2 <= r2}, the same squared distance, exact f64 -- the
@@ -139,46 +138,9 @@ k_nn3_count(const NnPair* __restrict__ pairs, const NnWork* __restrict__ work, i
             const double* __restrict__ px, const double* __restrict__ py, const double* __restrict__ pz,
             const int32_t* __restrict__ qperm, double r2, unsigned int* __restrict__ out)
 {
-    constexpr int NT = 256, CH = kNnChunk;
-    __shared__ double4 s_p[CH];
-    const int tid = threadIdx.x;
-    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work;
-         wi += gridDim.x) {
-        const NnWork w = work[wi];
-        const NnPair pd = pairs[w.pair];
-        int oi[QPT];
-        double qx[QPT], qy[QPT], qz[QPT];
-        unsigned int c[QPT];
-#pragma unroll
-        for (int k = 0; k < QPT; ++k) {
-            const int q = w.q0 + k * NT + tid;
-            oi[k] = q < pd.nq ? (pd.qperm_off >= 0 ? qperm[pd.qperm_off + q] : q) : -1;
-            const int qc = q < pd.nq ? q : pd.nq - 1;
-            qx[k] = px[pd.q_off + qc]; qy[k] = py[pd.q_off + qc]; qz[k] = pz[pd.q_off + qc];
-            c[k] = 0u;
-        }
-        const int c_end = pd.np - w.c0 < w.n_chunks * CH ? pd.np : w.c0 + w.n_chunks * CH;
-        for (int c0 = w.c0; c0 < c_end; c0 += CH) {
-            const int n = c_end - c0 < CH ? c_end - c0 : CH;
-            __syncthreads();
-            for (int j = tid; j < n; j += NT)
-                s_p[j] = make_double4(px[pd.p_off + c0 + j], py[pd.p_off + c0 + j], pz[pd.p_off + c0 + j], 0.0);
-            __syncthreads();
-#pragma unroll 4
-            for (int j = 0; j < n; ++j) {
-                const double4 p = s_p[j];
-#pragma unroll
-                for (int k = 0; k < QPT; ++k) {
-                    const double dx = qx[k] - p.x, dy = qy[k] - p.y, dz = qz[k] - p.z;
-                    const double v = dx * dx + dy * dy + dz * dz;
-                    c[k] += v <= r2 ? 1u : 0u;
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < QPT; ++k)
-            if (oi[k] >= 0 && c[k]) atomicAdd(&out[pd.out_off + oi[k]], c[k]);
-    }
+    nn3_scan<QPT, false>(pairs, work, n_work, px, py, pz, qperm, 0u,
+                         [r2](unsigned int c, double v) { return c + (v <= r2 ? 1u : 0u); },
+                         [](unsigned int* o, unsigned int c) { if (c) atomicAdd(o, c); }, out);
 }
 
 // queries per lane: 1..4 measured within 5 % of each other on MI355X (10.9 / 10.4 / 10.4 / 10.3 ms for the

@@ -11,13 +11,13 @@ namespace mm {
 // mm_nn_kernels.hip.  q_off / p_off: into the point pool; out_off: into the output; qperm_off: into the permutation pool (the
 // staged position j of the query set holds original point qperm[qperm_off + j]; -1 = staged in original order)
 struct NnPair { int32_t q_off, nq, p_off, np, out_off, qperm_off; };
-// queries [q0, q0 + nn_queries_per_block()) x points [c0, c0 + n_chunks nn_chunk_points()); lb2: a lower bound of the
-// squared distance between the two (pass B of k_nn3_min only)
+// queries [q0, q0 + nn_queries_per_block()) x points [c0, c0 + n_chunks nn_chunk_points()); lb2: the bound of
+// mm_prune.h (box_lb2) between the two; pass B of k_nn3_min reads it, pass A stores 0
 struct NnWork { int32_t pair, q0, c0, n_chunks; double lb2; };
 // A derived set: pool[dst_off + j] = aux point aux_off + j moved by adj along its unit vector where its flag is set
 struct NnMorph { int32_t dst_off, n, aux_off, pad; double adj; };
 // mm_tri_kernels.hip: queries [q0, q0 + tri_queries_per_block()) x faces [c0, c0 + tri_chunk_faces()), both in staged
-// order; lb2: a lower bound of the squared distance between the two (pass B and the who pass of k_tri_min)
+// order; lb2: the bound of mm_prune.h (box_lb2) between the two (pass B and the who pass of k_tri_min read it)
 struct TriWork { int32_t q0, c0; double lb2; };
 // mm_ray_kernels.hip: hits of one ray in one chunk of faces, closest (t, face)
 struct RayPartial { int32_t count, face; double t; };

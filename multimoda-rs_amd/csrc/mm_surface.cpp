@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/mm_ccta.h"
+#include "mm_prune.h"
 #include "mm_stage.h"
 #include "mm_trace.h"
 
@@ -44,56 +45,11 @@ int plan_args(const double* vertices, int64_t nv, const int64_t* faces, int64_t 
     return MM_OK;
 }
 
-// Slab order, as the nearest-neighbour staging takes it (mm_ccta.cpp, slab_order): indices 0 .. n-1 by their key quantised
-// to 20 bits of the keys' range, equal cells by index (a stable LSD radix sort, two passes of 10 bits).  Any permutation
-// gives the same distances; this one costs two linear passes where a full sort took most of the call's host time.
-void order_by(const std::vector<double>& key, std::vector<int32_t>& order)
-{
-    const size_t n = key.size();
-    order.resize(n);
-    if (n == 0) return;
-    const auto mm = std::minmax_element(key.begin(), key.end());
-    const double lo = *mm.first, width = *mm.second - lo;               // finite keys; the width may overflow to inf
-    const double sc = width > 0.0 ? 1048575.0 / width : 0.0;
-    std::vector<uint32_t> cell(n), cell2(n);
-    std::vector<int32_t> idx2(n);
-    for (size_t i = 0; i < n; ++i) {
-        const double t = (key[i] - lo) * sc;
-        cell[i] = t > 0.0 ? (t < 1048575.0 ? (uint32_t)t : 1048575u) : 0u;   // NaN-safe clamp
-        order[i] = (int32_t)i;
-    }
-    for (int sh = 0; sh < 20; sh += 10) {
-        uint32_t cnt[1025] = {0};
-        for (size_t i = 0; i < n; ++i) ++cnt[((cell[i] >> sh) & 1023u) + 1];
-        for (int b = 0; b < 1024; ++b) cnt[b + 1] += cnt[b];
-        for (size_t i = 0; i < n; ++i) {
-            const uint32_t d = cnt[(cell[i] >> sh) & 1023u]++;
-            cell2[d] = cell[i]; idx2[d] = order[i];
-        }
-        cell.swap(cell2); order.swap(idx2);
-    }
-}
-
-struct Box {
-    double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-    void add(const double* p) { for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
-    double largest() const { double m = 0.0; for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs(lo[a]), std::fabs(hi[a]))); return m; }
-};
-
-// A lower bound of every squared distance the device computes between a query in q and a face with its corners in c.
-// The closest point the rule computes, u + e t or (a + ab v) + ac w with factors that rounding keeps within a few ulp
-// of [0, 1], lies within a few ulp of the largest coordinate of the triangle's own box, hence of the chunk's; each gap is
-// narrowed by 64 such ulp, and the sum shaved for the roundings of the squared distance itself.
-double box_lb2(const Box& q, const Box& c)
-{
-    const double slack = 64.0 * DBL_EPSILON * std::max(q.largest(), c.largest());
-    double s = 0.0;
-    for (int a = 0; a < 3; ++a) {
-        const double gap = std::max(0.0, std::max(q.lo[a] - c.hi[a], c.lo[a] - q.hi[a]) - slack);
-        s += gap * gap;
-    }
-    return s * (1.0 - 1e-12);
-}
+// The slack of the bound (mm_prune.h, box_lb2) between a query block q and a chunk's corners c.  The closest point the
+// rule computes, u + e t or (a + ab v) + ac w with factors that rounding keeps within a few ulp of [0, 1], lies within a
+// few ulp of the largest coordinate of the triangle's own box, hence of the chunk's: each gap is narrowed by 64 such ulp
+// (DESIGN 4.19).
+double tri_slack(const Box3& q, const Box3& c) { return 64.0 * DBL_EPSILON * std::max(q.largest(), c.largest()); }
 
 // every component of ab x ac exactly 0, or a repeated index
 bool is_degenerate(const double* a, const double* b, const double* c, const int64_t* f)
@@ -111,16 +67,15 @@ int build_plan(const double* v, const int64_t* f, int64_t nf, const double* q, i
     pl.qpb = tri_queries_per_block();
     pl.ch = tri_chunk_faces();
     TraceTimer t_order("tri: slab order");
-    Box all;
+    Box3 all;
     for (int64_t k = 0; k < 3 * nf; ++k) all.add(v + 3 * f[k]);
-    int ax = 0;
-    for (int a = 1; a < 3; ++a) if (all.hi[a] - all.lo[a] > all.hi[ax] - all.lo[ax]) ax = a;
+    const int ax = all.longest_axis();
     std::vector<double> key((size_t)nf);
     for (int64_t i = 0; i < nf; ++i) key[(size_t)i] = (v[3 * f[3 * i] + ax] + v[3 * f[3 * i + 1] + ax]) + v[3 * f[3 * i + 2] + ax];
-    order_by(key, pl.forder);
+    slab_permutation(key, pl.forder);
     key.resize((size_t)nq);
     for (int64_t i = 0; i < nq; ++i) key[(size_t)i] = q[3 * i + ax];
-    order_by(key, pl.qperm);
+    slab_permutation(key, pl.qperm);
     pl.degenerate.resize((size_t)nf);
     for (int64_t j = 0; j < nf; ++j) {
         const int64_t* t = f + 3 * (int64_t)pl.forder[(size_t)j];
@@ -133,17 +88,17 @@ int build_plan(const double* v, const int64_t* f, int64_t nf, const double* q, i
     if (nq == 0 || nf == 0) return MM_OK;
     const int64_t nqb = (nq + pl.qpb - 1) / pl.qpb, nch = (nf + pl.ch - 1) / pl.ch;
     if (nqb * nch > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": more than 2^31 work items");
-    std::vector<Box> qbox((size_t)nqb), cbox((size_t)nch);
+    std::vector<Box3> qbox((size_t)nqb), cbox((size_t)nch);
     for (int64_t j = 0; j < nq; ++j) qbox[(size_t)(j / pl.qpb)].add(q + 3 * (int64_t)pl.qperm[(size_t)j]);
     for (int64_t j = 0; j < nf; ++j)
         for (int k = 0; k < 3; ++k) cbox[(size_t)(j / pl.ch)].add(v + 3 * f[3 * (int64_t)pl.forder[(size_t)j] + k]);
     pl.n_a = nqb;
     pl.n_b = nqb * (nch - 1);
     pl.work.resize((size_t)(pl.n_a + pl.n_b));
-    std::vector<std::pair<double, int32_t>> cand((size_t)nch);
+    std::vector<std::pair<double, int32_t>> cand;
     for (int64_t b = 0; b < nqb; ++b) {
-        for (int64_t c = 0; c < nch; ++c) cand[(size_t)c] = {box_lb2(qbox[(size_t)b], cbox[(size_t)c]), (int32_t)c};
-        std::sort(cand.begin(), cand.end());   // nearest chunks first: they tighten the minima the others check
+        const Box3& qb = qbox[(size_t)b];
+        nearest_first(nch, [&](int64_t c) { return box_lb2(qb, cbox[(size_t)c], tri_slack(qb, cbox[(size_t)c])); }, cand);
         const int32_t q0 = (int32_t)(b * pl.qpb);
         pl.work[(size_t)b] = TriWork{q0, cand[0].second * pl.ch, cand[0].first};
         for (int64_t c = 1; c < nch; ++c)

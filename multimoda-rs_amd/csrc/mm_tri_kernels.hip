@@ -4,34 +4,30 @@
 // (the file is built with -ffp-contract=off), every quotient a true division.  min is exact, so the result does not
 // depend on the traversal order.
 //
-// Mapping (that of mm_nn_kernels.hip): one work item = 256 lanes x QPT queries against one chunk of CH faces; a chunk is
-// staged in LDS as three double4 per face (corner a, b, c), so that a corner is two ds_read broadcasts (all lanes read
-// the same address: conflict-free).  a.w carries the bits of the face's degenerate flag, b.w those of its original index;
-// both are the same for all lanes and are made scalar with readfirstlane, so the degenerate branch is uniform.  The
-// minima merge into the output with a 64-bit atomicMin on the bit pattern (order-preserving for values >= +0; the output
-// is pre-filled with +inf; a NaN never enters: the lane's own fold takes v only where v < m).
+// Mapping: one work item = 256 lanes x QPT queries against one chunk of CH faces; a chunk is staged in LDS as three
+// double4 per face (corner a, b, c), so that a corner is two ds_read broadcasts (all lanes read the same address:
+// conflict-free).  a.w carries the bits of the face's degenerate flag, b.w those of its original index; both are the
+// same for all lanes and are made scalar with readfirstlane, so the degenerate branch is uniform.
 // Per (query, face): 9 sub, 6 dots (30), 3 cross terms (9), then the branch of the query's region -- a vertex (nothing),
 // an edge (1 division, 3 mul-add pairs) or the interior (2 divisions, 6 pairs) -- and the squared distance (8): about 60
 // fp64 VALU operations and at most 2 divisions against 6/QPT LDS reads -> fp64-VALU bound.  The divisions stay inside
 // their branches: lanes of other regions are masked off while they run.
 //
-// Pruning: queries and faces are staged in slabs across the mesh's longest axis by the host, which hands every (query
-// block, chunk) item a lower bound lb2 of the squared distance between the block's box and the chunk's box.  Pass A
-// (k_tri_min<.., false, false>) runs each block's smallest-bound chunk, pass B (<.., true, false>) every other one, and an item of
-// pass B starts by reading its queries' current minima: if none exceeds lb2 the item is skipped (and counted).
-// The winner: the who pass (k_tri_min<.., false, true>) takes, over the items with lb2 <= the block's largest final minimum, the lowest original face
-// index whose d2 equals the query's final minimum, by a 64-bit atomicMin on (original index << 32 | staged position);
-// k_tri_closest then recomputes closest point and region of that face, one lane per query.
+// Pruning (mm_prune.h, mm_prune_device.h): pass A is k_tri_min<.., false, false>, pass B <.., true, false>,
+// which counts the items it skips.  Particular to this kernel is the winner: the who pass (<.., false, true>) takes, over
+// the items whose bound does not exceed the block's largest final minimum, the lowest original face index whose d2 equals
+// the query's final minimum, by the same merge on (original index << 32 | staged position); k_tri_closest then
+// recomputes closest point and region of that face, one lane per query.
 #include <hip/hip_runtime.h>
 
 #include "mm_device.h"
+#include "mm_prune_device.h"
 #include "mm_xcd.h"
 
 namespace mm {
 
 static constexpr int kTriChunk = 256;   // 256 faces x 3 double4 = 24 KiB of LDS: 6 blocks a CU by LDS
 static constexpr int kTriQpt = 2;
-static constexpr unsigned long long kInfBits = 0x7ff0000000000000ull;
 
 struct V3 { double x, y, z; };
 
@@ -120,17 +116,6 @@ k_tri_fill(unsigned long long* __restrict__ sq, unsigned long long* __restrict__
     if (i == 0) counters[0] = 0ull;
 }
 
-// the largest of the block's values v (one per lane), through s_max; uniform
-__device__ __forceinline__ unsigned long long block_max(unsigned long long v, unsigned long long* s_max)
-{
-    __syncthreads();   // s_max of the previous item is no longer read
-    if (threadIdx.x == 0) *s_max = 0ull;
-    __syncthreads();
-    atomicMax(s_max, v);
-    __syncthreads();
-    return *s_max;
-}
-
 // WHO = false: the minima (CHECK: pass B).  WHO = true: the winners' keys, from the final minima in sq.
 template <int QPT, bool CHECK, bool WHO>
 __global__ void __launch_bounds__(256)
@@ -157,8 +142,7 @@ k_tri_min(const TriWork* __restrict__ work, int n_work, const double4* __restric
                 fin[k] = q < nq && v != kInfBits ? __longlong_as_double((long long)v) : __builtin_nan("");
             }
             const double top = __longlong_as_double((long long)block_max(mx, &s_max));
-            // uniform: nothing here can improve (pass B) / equal (who) any of the block's minima
-            if (WHO ? w.lb2 > top : w.lb2 >= top) {
+            if (skip_item(WHO ? Skip::cannot_equal : Skip::cannot_lower, w.lb2, top)) {   // uniform
                 if (CHECK && tid == 0) atomicAdd(&counters[0], 1ull);
                 continue;
             }
@@ -191,18 +175,12 @@ k_tri_min(const TriWork* __restrict__ work, int n_work, const double4* __restric
                 else m[k] = v < m[k] ? v : m[k];
             }
         }
-        // the stored values only ever decrease, so a (possibly stale) plain read that is already <= ours proves the
-        // atomic would change nothing
 #pragma unroll
         for (int k = 0; k < QPT; ++k) {
             const int q = w.q0 + k * NT + tid;
             if (q >= nq) continue;
-            if (WHO) {
-                if (best[k] < key[q]) atomicMin(&key[q], best[k]);
-            } else {
-                const unsigned long long v = (unsigned long long)__double_as_longlong(m[k]);
-                if (v < sq[q]) atomicMin(&sq[q], v);
-            }
+            if (WHO) merge_min(&key[q], best[k]);
+            else merge_min(&sq[q], (unsigned long long)__double_as_longlong(m[k]));
         }
     }
 }

@@ -1,8 +1,8 @@
 """Surface distance on the device (csrc/mm_tri_kernels.hip, csrc/mm_surface.cpp) against the checker
 (tests/mm_checkers/surface_distance.py): bit-identical squared distances and closest points, equal faces and regions,
 equal integer report fields (items, launches, bytes).  Cases: the seven regions, the small solids, the ties, the
-degenerate faces, one face past a chunk and one query past a block, a long tube whose pass B must skip items, shuffled
-faces, random meshes, empty inputs, the argument checks; then surface_distance, and the line label -> remove ->
+degenerate faces, one face past a chunk and one query past a block, a long tube whose pass B must skip items, an equal
+distance in a chunk that pass B skips, shuffled faces, random meshes, empty inputs, the argument checks; then surface_distance, and the line label -> remove ->
 stitch(fill_holes=True, refine=True, smooth=True) measured against its unrefined, unsmoothed self."""
 import ctypes as C
 import os
@@ -15,8 +15,8 @@ from mm_checkers import surface_distance as S
 from test_trim_host import octahedron
 from test_smooth_host import tetrahedron
 from test_refine_host import same_bits, jitter, wound_tube
-from test_surface_host import (ACCURACY_TOL, REGION_QUERIES, REGIONS, TRIANGLE, degenerate_faces, long_tube, must_skip,
-                               two_coplanar)
+from test_surface_host import (ACCURACY_TOL, REGION_QUERIES, REGIONS, TRIANGLE, degenerate_faces,
+                               far_face_touching_the_first_chunk, long_tube, must_skip, two_coplanar)
 from test_gpu_stitch import takeoff_case
 
 import multimoda_rs_amd as mm
@@ -93,6 +93,16 @@ def test_long_tube_skips_what_the_plan_says_it_must(engine):
     got = same_as_checker(fine, v, f, engine)                             # the checker's scan is unpruned
     print(f"long tube: pass B {got.report['items_pass_b']} items, skipped {got.report['items_skipped']}, must_skip {n}")
     assert got.report["items_skipped"] >= n > 0
+
+
+def test_an_equal_distance_in_a_chunk_pass_b_skips_still_wins_on_face_index(engine):
+    """Every minimum of the one query block is 0 after pass A, so pass B skips both its items (lb2 >= 0), the far chunk
+    with bound 0.0 among them; the who pass must still run that chunk (lb2 > 0 is false): face 0, staged there, touches
+    the first query and has the lowest index.  The layout is checked on the host in tests/test_surface_host.py."""
+    v, f, q = far_face_touching_the_first_chunk()
+    got = same_as_checker(q, v, f, engine)
+    assert got.face.tolist() == [0, 6, 101] and (got.sq_distance == 0.0).all()
+    assert got.report["items_pass_a"] == 1 and got.report["items_pass_b"] == 2 and got.report["items_skipped"] == 2
 
 
 def test_shuffled_faces(engine):

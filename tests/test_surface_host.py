@@ -59,6 +59,22 @@ def long_tube():
     return v, f, jitter(v, 41)
 
 
+def far_face_touching_the_first_chunk():
+    """513 faces (three chunks): 512 small ones in a row along x, and face 0, a long triangle whose corner sum stages it
+    last -- alone in the third chunk -- while its corner (0, 0, 0) is also a corner of the first small face.  The three
+    queries are that shared vertex and two more vertices of small faces of the first chunk: every minimum is exactly 0."""
+    v = [[0.0, 0.0, 0.0], [2000.0, 1.0, 0.0], [2000.0, -1.0, 0.0]]
+    f = [[0, 1, 2]]
+    for i in range(512):
+        a = 0 if i == 0 else len(v)
+        if i:
+            v.append([float(i), 0.25, 0.5])
+        v += [[i + 0.5, 0.25, 0.5], [float(i), 0.75, 0.5]]
+        f.append([a, len(v) - 2, len(v) - 1])
+    v, f = np.array(v), np.array(f)
+    return v, f, np.array([v[0], v[f[6, 0]], v[f[101, 0]]])
+
+
 def must_skip(plan, points, v, f):
     """Items of pass B whose lower bound is not below the largest minimum pass A leaves in their block: whatever the
     order in which the device runs pass B, it skips at least these."""
@@ -314,6 +330,21 @@ def test_plan_of_the_long_tube_has_items_pass_b_must_skip():
     n = must_skip(plan, fine, v, f)
     print(f"long tube: {len(plan['b'])} items in pass B, must_skip = {n}")
     assert n > 0
+
+
+def test_plan_of_the_far_face_touching_the_first_chunk():
+    """The layout tests/test_gpu_surface.py relies on for the who pass's `lb2 > top`: face 0 is staged in another chunk
+    than the small face it touches, and the item of its chunk carries the bound 0.0."""
+    v, f, q = far_face_touching_the_first_chunk()
+    assert len(f) == 513 and f[0, 0] == f[1, 0] and same_bits(q[0], v[f[0, 0]])
+    plan = surface.tri_plan(q, (v, f))
+    where = np.argsort(plan["face_order"])                                 # face -> staged position
+    assert where[0] // plan["chunk"] == 2 and where[1] // plan["chunk"] == 0
+    assert (where[[6, 101]] // plan["chunk"] == 0).all()                  # pass A alone brings every minimum to 0
+    assert plan["a"].tolist() == [[0, 0]] and sorted(plan["b"][:, 1].tolist()) == [256, 512]
+    far = plan["b_lb2"][plan["b"][:, 1] == 512]
+    assert len(far) == 1 and same_bits(far, np.array([0.0]))
+    assert S.scan(q, v, f)[1].tolist() == [0, 6, 101] and (S.scan(q, v, f)[0] == 0.0).all()
 
 
 def test_plan_argument_checks():

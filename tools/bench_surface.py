@@ -2,13 +2,14 @@
 tools/bench_mesh_refine.py against its refined and Taubin-smoothed self, at a few sizes.  Whole-call wall times (the
 lattice samples in numpy, the host staging and work items, both uploads, every launch of both directions, both
 downloads, the means), with the distances and, per direction, the items of pass A and pass B, the items pass B skipped,
-the launches and the bytes each way.  No time is promised and there is no baseline: the call is new, and the checker
-(tests/mm_checkers/surface_distance.py) is numpy, a yardstick for bits and not for speed.  Prints one JSON line and
-writes it to profiles/bench_surface.json.
+the launches and the bytes each way, and a sha256 over every figure of the report but the skipped items.  No time is
+promised and there is no baseline: the call is new, and the checker (tests/mm_checkers/surface_distance.py) is numpy, a
+yardstick for bits and not for speed.  Prints one JSON line and writes it to profiles/bench_surface.json.
 
     python tools/bench_surface.py [--sizes 100x50,200x100,400x125] [--stretch 4] [--samples 1] [--reps 5]
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -26,6 +27,16 @@ from bench_mesh_refine import _best, capped_tube  # noqa: E402
 
 def _direction(d):
     return {"n": d.n, "max": d.max, "mean": d.mean, "rms": d.rms, **d.report}
+
+
+def _digest(rep):
+    """sha256 over every figure of both directions, floats by their bits"""
+    h = hashlib.sha256()
+    for d in (rep.a_to_b, rep.b_to_a):
+        h.update(np.array([d.max, d.mean, d.rms, *d.closest], dtype=np.float64).tobytes())
+        counts = {k: n for k, n in d.report.items() if k != "items_skipped"}   # what pass B skips depends on its schedule
+        h.update(json.dumps([d.argmax, d.sample_face, d.face, d.n, counts], sort_keys=True).encode())
+    return h.hexdigest()
 
 
 def main():
@@ -53,7 +64,7 @@ def main():
                                  "ms_min": t_min, "ms_median": t_median, "sampling_ms": sample_ms,
                                  "hausdorff": rep.hausdorff, "a_to_b": _direction(rep.a_to_b), "b_to_a": _direction(rep.b_to_a),
                                  "n_launches": rep.n_launches, "bytes_uploaded": rep.bytes_uploaded,
-                                 "bytes_downloaded": rep.bytes_downloaded})
+                                 "bytes_downloaded": rep.bytes_downloaded, "sha256": _digest(rep)})
     line = json.dumps(out)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
