@@ -714,6 +714,78 @@ int     mm_tri_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris,
                     int64_t nq, int32_t* face_order, int32_t* query_perm, int64_t* info, int32_t* items, double* item_lb2,
                     int64_t cap);
 
+/* ---- mesh relaxation (multimodars/ccta/fixing_functions.py:192-219: of MeshLab's isotropic remesh the tangential
+ *      smoothing and the reprojection, smoothflag / reprojectflag / checksurfdist; collapse, flip and repair stay out) ----
+ * Slides the free vertices of a mesh (v, faces) along a reference surface (rv, rfaces; the mesh's own input where none is
+ * given) and puts every one of them back on it exactly.  tests/mm_checkers/relax_mesh.py is the executable form.  All
+ * arithmetic is unfused f64 in the order written; dot, the cross components and the closest point are those of "surface
+ * distance", the average is that of "mesh smoothing".
+ *
+ * Free.  A vertex is free iff it has a neighbour in the adjacency of mm_mesh_adjacency_csr, its mask byte is 0 (or there
+ * is no mask), and it ends no edge whose owner count is not 2 -- every corner pair of every face owns its undirected
+ * edge, an (a, a) pair too, as mm_fill_holes and mm_mesh_refine count.  The ends of such edges are the border vertices
+ * (n_border, whatever their mask byte).  A vertex that is not free keeps its input bits and still feeds its neighbours'
+ * averages.  A free vertex with ref_nf == 0 is MM_ERR_INVALID.
+ *
+ * Projection.  P(p), F(p), D(p): closest point, winning face and d2 of the surface distance on the reference -- the
+ * lowest face on ties, a degenerate face as its segments.  Where no face beats +inf (F = -1) the vertex is not moved,
+ * then or later.
+ *
+ * Step 0 (always, n_iterations == 0 too).  For every free v:  x_v = P(v_in), F_v = F(v_in);  initial_distance_sq is the
+ * largest D(v_in).
+ *
+ * One iteration, reading only the state before it.  For a free v with neighbours j ascending:
+ *     w = 1.0 / deg;  acc = +0.0;  acc = acc + w * x_j;  d = acc - x   (per component)
+ *     n = ab x ac of reference face F_v = (aby*acz - abz*acy, abz*acx - abx*acz, abx*acy - aby*acx);  nn = dot(n, n)
+ *     nn > 0 and finite:  s = dot(n, d) / nn;  t = d - n*s  (one product, one difference);  otherwise t = d
+ *     c = x + lambda*t  (product, then sum).  A c with a non-finite component is not used: the vertex stays and counts
+ *     as reverted.  Otherwise  x'_v = P(c), F'_v = F(c);  F(c) == -1 reverts as well.
+ * Guard, one round an iteration, not cascading.  For every mesh face (i, j, k) of three distinct indices:
+ *     m_old = (x_j - x_i) x (x_k - x_i),  m_new the same on x';  where dot(m_old, m_old) > 0 and not
+ *     dot(m_old, m_new) > 0, the face's free corners take back x and F.
+ * n_reverted sums the vertices reverted over the iterations (each once an iteration).  n_flipped_faces counts the faces
+ * of three distinct indices with dot(m_in, m_in) > 0 and dot(m_in, m_out) <= 0, m_in on the input, m_out on the output:
+ * one guard round promises no flip-free result.
+ *
+ * The minimum over faces is exact, so the result has one bit pattern whatever the chunking, the order or the pruning.
+ *
+ * Device.  One upload: the faces (int32), the input vertices and, where a vertex is free, the reference's staged faces
+ * (96 bytes each, slab order), the free vertices' input positions as queries in slab order (24), their vertex indices
+ * (4), the (query block, chunk) items (16) and the chunks' boxes (48).  The mask is used on the host only.  One download:
+ * the vertices, one key per query, 256 bytes of numbers.  Every buffer is rounded up to 256 bytes.  Nothing crosses in
+ * between: per iteration the device recomputes each query block's box from the candidates and every item's lower bound
+ * from it with the functions the host used (mm_prune.h: box_lb2, tri_slack), seeds each query's minimum with the d2 to
+ * its previous face and runs every item checked.  items_run + items_skipped = items * (1 + n_iterations);
+ * items_skipped - items_skipped_step0 are the skips of the iterations, on the refreshed bounds.
+ * Launches, with T = 4 + (more than one chunk), V = 1 + max(1, ceil(ceil(log2 nf) / 8)), I = n_iterations:
+ *     n_launches = 2 V + 2  +  [n_free > 0] (T + 1 + 6 I)  +  [n_free > 0 and I > 0] 7
+ * -- two volumes, the flipped faces, the displacement; step 0 and its acceptance; per iteration the candidates with
+ * seeds and bounds, the checked minima, the winners, the closest points, the guard, the acceptance; the adjacency.  With
+ * nv == 0 or nf == 0 nothing is launched, the input is returned and the volumes are 0.
+ *
+ * Limits as mm_point_mesh_distance for both meshes (sizes below 2^31, finite coordinates, indices in range:
+ * MM_ERR_INVALID; more than 2^31 - 1 items: MM_ERR_TOO_LARGE), 6 nf < 2^31 (MM_ERR_TOO_LARGE); n_iterations < 0 or a
+ * non-finite lambda: MM_ERR_INVALID.  On an error no output is written. */
+
+typedef struct mm_relax_report {
+    int64_t n_vertices, n_faces, n_ref_faces;
+    int64_t n_free, n_pinned, n_border, n_isolated;   /* n_pinned: nonzero mask bytes; n_isolated: no neighbour        */
+    int64_t iterations_run, n_reverted, n_flipped_faces;
+    int64_t items_run, items_skipped;                 /* (query block, chunk) items of the minima passes               */
+    int64_t items_skipped_step0;                      /* those of items_skipped that step 0 skipped, on the host's bounds */
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    double  initial_distance_sq, max_displacement_sq; /* the latter as mm_smooth_report                                */
+    double  volume_before, volume_after;              /* as mm_smooth_report                                           */
+} mm_relax_report;                                    /* 160 bytes */
+
+/* ref_vertices == NULL: the mesh itself is the reference (ref_nv, ref_tris, ref_nf are ignored).  pinned (nullable): nv
+ * bytes.  out_vertices: nv triples (may be vertices_xyz); out_ref_face: nv entries, the reference face each free vertex
+ * lies on, -1 where the vertex is not free. */
+int     mm_mesh_relax(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                      const double* ref_vertices, int64_t ref_nv, const int64_t* ref_tris, int64_t ref_nf,
+                      const uint8_t* pinned, int64_t n_iterations, double factor, double* out_vertices,
+                      int64_t* out_ref_face, mm_relax_report* report);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

@@ -117,7 +117,7 @@ EXPORTS_CCTA = [
     "mm_plane_shift_clear_of", "mm_ring_clamp_to_plane", "mm_ring_densify_plan", "mm_mesh_locate_points",
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
-    "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan",
+    "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan", "mm_mesh_relax",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -161,6 +161,16 @@ class MMSurfaceReport(C.Structure):
     """``mm_surface_report`` (include/mm_ccta.h)."""
     _fields_ = [(name, C.c_int64) for name in (
         "items_pass_a", "items_pass_b", "items_skipped", "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMRelaxReport(C.Structure):
+    """``mm_relax_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_ref_faces", "n_free", "n_pinned", "n_border", "n_isolated", "iterations_run",
+        "n_reverted", "n_flipped_faces", "items_run", "items_skipped", "items_skipped_step0", "n_launches",
+        "bytes_uploaded", "bytes_downloaded")] + \
+               [(name, C.c_double) for name in ("initial_distance_sq", "max_displacement_sq", "volume_before",
+                                                "volume_after")]
 
 
 class MMRimParams(C.Structure):
@@ -581,6 +591,8 @@ def lib():
     L.mm_mesh_refine.argtypes = [P, P, I64, P, I64, D, D, I64, I64, I64, I64, P, P, P, C.POINTER(MMRefineReport)]
     L.mm_point_mesh_distance.restype = I
     L.mm_point_mesh_distance.argtypes = [P, P, I64, P, I64, P, I64, P, P, P, P, C.POINTER(MMSurfaceReport)]
+    L.mm_mesh_relax.restype = I
+    L.mm_mesh_relax.argtypes = [P, P, I64, P, I64, P, I64, P, I64, P, I64, D, P, P, C.POINTER(MMRelaxReport)]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

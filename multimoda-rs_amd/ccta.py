@@ -1519,7 +1519,7 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
-           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False) -> dict:
+           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1532,7 +1532,10 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     ``smooth=False`` changes nothing.  ``refine=True``, or a dict of ``refine_mesh`` keywords, splits the long edges
     (``refine_mesh``, the edge split of the reference's remesh) behind the hole fill and in front of the smoothing: a
     new vertex joins, in ascending order, every point list that holds both its parents, and the result carries
-    ``refine_report``.  The default ``refine=False`` changes nothing."""
+    ``refine_report``.  The default ``refine=False`` changes nothing.  ``relax=True``, or a dict of ``relax_mesh``
+    keywords, evens the vertices out on the surface (``relax_mesh`` against the mesh itself) behind the refinement and in
+    front of the smoothing: the point lists follow and the result carries ``relax_report``.  The default ``relax=False``
+    changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1542,7 +1545,7 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_refine_result(out, refine, engine), smooth, engine)
+    return _smooth_result(_relax_result(_refine_result(out, refine, engine), relax, engine), smooth, engine)
 
 
 def _refine_result(out: dict, refine, engine) -> dict:
@@ -1569,6 +1572,19 @@ def _refine_result(out: dict, refine, engine) -> dict:
         for k in range(parents.shape[0]):                                # ascending: a parent's own membership is known
             member[nv0 + k] = member[parents[k, 0]] and member[parents[k, 1]]
         out[key] = np.concatenate([_p3(pts), v[nv0:][member[nv0:]]])
+    return out
+
+
+def _relax_result(out: dict, relax, engine) -> dict:
+    """The ``relax`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of relax_mesh keywords."""
+    if relax is False or relax is None:
+        return out
+    kw = dict(relax) if isinstance(relax, dict) else {}
+    kw.setdefault("engine", engine)
+    old = out["mesh"]
+    new, _, report = relax_mesh(old, kw.pop("reference", None), **kw)
+    out = sync_results_to_mesh(out, old, new)
+    out["relax_report"] = report
     return out
 
 
@@ -1878,13 +1894,14 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
-                       engine: Optional[N.Engine] = None, smooth=False, refine=False, **conditioning) -> dict:
+                       engine: Optional[N.Engine] = None, smooth=False, refine=False, relax=False,
+                       **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
     carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``refine`` and ``smooth`` as in ``stitch``:
     the refinement runs behind the hole fill and adds ``refine_report``, the smoothing runs last and adds
-    ``smooth_report``."""
+    ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
@@ -1896,7 +1913,7 @@ def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_refine_result(out, refine, engine), smooth, engine)
+    return _smooth_result(_relax_result(_refine_result(out, refine, engine), relax, engine), smooth, engine)
 
 
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
@@ -2147,6 +2164,29 @@ def _seed_indices(seeds, vertices: np.ndarray) -> np.ndarray:
     return np.unique(idx[idx >= 0])
 
 
+def _pin_mask(pinned, band, v: np.ndarray, f: np.ndarray, engine):
+    """The uint8 mask of ``smooth_mesh`` / ``relax_mesh`` from their ``pinned`` and ``band`` keywords (None: no mask)."""
+    nv = v.shape[0]
+    mask = None
+    if pinned is not None:
+        p = np.asarray(pinned)
+        if p.dtype == np.bool_:
+            if p.reshape(-1).shape[0] != nv:
+                raise ValueError("a pinned mask has one entry per vertex")
+            mask = p.reshape(-1).copy()
+        else:
+            p = p.astype(np.int64).reshape(-1)
+            if p.size and (p.min() < 0 or p.max() >= nv):
+                raise ValueError(f"pinned index out of range [0, {nv})")
+            mask = np.zeros(nv, dtype=bool)
+            mask[p] = True
+    if band is not None:
+        seeds, k = band
+        ring = vertex_rings(f, _seed_indices(seeds, v), int(k), nv, engine)
+        mask = (ring < 0) if mask is None else (mask | (ring < 0))
+    return None if mask is None else np.ascontiguousarray(mask.astype(np.uint8))
+
+
 def smooth_mesh(mesh, factors=None, *, lamb: float = 0.5, nu: float = 0.5, iterations: int = 10, pinned=None, band=None,
                 engine: Optional[N.Engine] = None):
     """Laplacian / Taubin smoothing of ``mesh`` (a ``(vertices, faces)`` tuple or an object with ``.vertices`` /
@@ -2173,24 +2213,7 @@ def smooth_mesh(mesh, factors=None, *, lamb: float = 0.5, nu: float = 0.5, itera
             raise ValueError("iterations must not be negative")
         factors = [float(lamb) if i % 2 == 0 else -float(nu) for i in range(int(iterations))]
     fac = np.ascontiguousarray(np.asarray(factors, dtype=np.float64).reshape(-1))
-    mask = None
-    if pinned is not None:
-        p = np.asarray(pinned)
-        if p.dtype == np.bool_:
-            if p.reshape(-1).shape[0] != nv:
-                raise ValueError("a pinned mask has one entry per vertex")
-            mask = p.reshape(-1).copy()
-        else:
-            p = p.astype(np.int64).reshape(-1)
-            if p.size and (p.min() < 0 or p.max() >= nv):
-                raise ValueError(f"pinned index out of range [0, {nv})")
-            mask = np.zeros(nv, dtype=bool)
-            mask[p] = True
-    if band is not None:
-        seeds, k = band
-        ring = vertex_rings(f, _seed_indices(seeds, v), int(k), nv, engine)
-        mask = (ring < 0) if mask is None else (mask | (ring < 0))
-    m8 = None if mask is None else np.ascontiguousarray(mask.astype(np.uint8))
+    m8 = _pin_mask(pinned, band, v, f, engine)
     out = np.zeros_like(v)
     rep = N.MMSmoothReport()
     N.check(N.lib().mm_mesh_smooth(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), f.shape[0], N._ptr(fac),
@@ -2214,6 +2237,64 @@ def filter_laplacian(mesh, lamb: float = 0.5, iterations: int = 10, **kw):
     if int(iterations) < 0:
         raise ValueError("iterations must not be negative")
     return smooth_mesh(mesh, [float(lamb)] * int(iterations), **kw)[0]
+
+
+# ---- mesh relaxation (multimodars/ccta/fixing_functions.py:192-219: smoothing and reprojection of the isotropic remesh) --
+
+RELAX_REPORT_KEYS = ("n_vertices", "n_faces", "n_ref_faces", "n_free", "n_pinned", "n_border", "n_isolated",
+                     "iterations_run", "n_reverted", "n_flipped_faces", "items_run", "items_skipped", "items_skipped_step0",
+                     "n_launches", "bytes_uploaded", "bytes_downloaded", "initial_distance_sq", "max_displacement_sq", "volume_before",
+                     "volume_after")
+
+
+def relax_mesh(mesh, reference=None, *, iterations: int = 5, lamb: float = 0.5, pinned=None, band=None,
+               engine: Optional[N.Engine] = None):
+    """Tangential relaxation of ``mesh`` reprojected onto ``reference`` (a mesh of either kind; None: ``mesh`` as it
+    comes in), on the device: ``(mesh, ref_face, report)``.  Every free vertex is first put on the closest point of the
+    reference; each of the ``iterations`` Jacobi steps then moves it by ``lamb`` times the part of (mean of its
+    neighbours - itself) that is tangent to the reference face it lies on, and puts it back on the closest point of
+    the reference; a step that would turn a face's normal is taken back at that face's vertices (include/mm_ccta.h,
+    "mesh relaxation").  The faces do not change and the result has one bit pattern.  Free are the vertices with a
+    neighbour that are neither pinned nor on a border or non-manifold edge; all others keep their bits.
+
+    ``pinned`` and ``band`` as in ``smooth_mesh``.  ``ref_face[v]``: the reference face vertex ``v`` lies on, -1 where it
+    is not free.  ``report``: RELAX_REPORT_KEYS and ``volume_ratio``; ``initial_distance_sq`` is the largest squared
+    distance a free vertex had from the reference, ``n_reverted`` the moves taken back, ``n_flipped_faces`` the faces
+    that ended turned against their input normal."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    if int(iterations) < 0:
+        raise ValueError("iterations must not be negative")
+    if not np.isfinite(float(lamb)):
+        raise ValueError("lamb must be finite")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex coordinate")
+    rv = rf = None
+    if reference is not None:
+        rvert, rfaces = _mesh_parts(reference)
+        rv = _p3(rvert)
+        rf = _checked_faces(rfaces, rv.shape[0])
+        if not np.isfinite(rv).all():
+            raise ValueError("non-finite reference coordinate")
+    m8 = _pin_mask(pinned, band, v, f, engine)
+    out = np.zeros_like(v)
+    ref_face = np.full(nv, -1, dtype=np.int64)
+    rep = N.MMRelaxReport()
+    N.check(N.lib().mm_mesh_relax(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), f.shape[0], N._ptr(rv),
+                                  0 if rv is None else rv.shape[0], N._ptr(rf), 0 if rf is None else rf.shape[0],
+                                  N._ptr(m8), int(iterations), float(lamb), N._ptr(out), N._ptr(ref_face), C.byref(rep)),
+            "relax_mesh")
+    report = {k: getattr(rep, k) for k in RELAX_REPORT_KEYS}
+    report["volume_ratio"] = report["volume_after"] / report["volume_before"] if report["volume_before"] != 0.0 \
+        else float("nan")
+    return _with_vertices(mesh, out), ref_face, report
+
+
+def project_to_mesh(mesh, reference, **kw):
+    """``mesh`` with every free vertex on the closest point of ``reference``: ``relax_mesh(..., iterations=0)``."""
+    return relax_mesh(mesh, reference, iterations=0, **kw)
 
 
 # ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: the edge split of the isotropic remesh) -----------

@@ -169,6 +169,12 @@ hipError_t launch_tri_distance(const TriWork* work, int n_a, int n_b, const doub
                                unsigned long long* sq, unsigned long long* key, double* closest, int32_t* region,
                                unsigned long long* counters, hipStream_t s);
 int        tri_launches(int n_b);
+// the same over minima seeded with the d2 to one face each (sq) and key = ~0: all n_work items checked, the who pass,
+// the closest points; counters[0] += the items skipped
+hipError_t launch_tri_seeded(const TriWork* work, int n_work, const double* tri12, int nf, const double* qxyz, int nq,
+                             unsigned long long* sq, unsigned long long* key, double* closest, int32_t* region,
+                             unsigned long long* counters, hipStream_t s);
+int        tri_seeded_launches();
 int        tri_queries_per_block();
 int        tri_chunk_faces();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
@@ -273,6 +279,31 @@ hipError_t launch_mesh_ring(const int32_t* off, const int32_t* nb, long long nv,
                             unsigned long long* reached, int* launches, hipStream_t s);
 hipError_t launch_mesh_disp(const double* a, const double* b, long long nv, unsigned long long* max_bits, int* launches,
                             hipStream_t s);
+// mesh relaxation (mm_relax_kernels.hip; include/mm_ccta.h, "mesh relaxation").  Queries are the free vertices in staged
+// order (qv: their vertex), blocks of tri_queries_per_block(); x: the nv current positions; fkey: each query's face as
+// k_tri_min's key (original << 32 | staged, ~0: none); state: nonzero = not moved this iteration; num: the numbers block
+// (relax_num_* words).  relax_accept: step 0 -- x, fkey from closest / key, vq[qv[j]] = j (vq: -1 before), the largest
+// d2.  relax_candidates: per query block the candidates (qxyz), their seeds (sq, key = ~0), state, the block's box and
+// the refreshed lb2 of the block's items (work: n_a items of pass A, then n_b of pass B, as build_plan lays them out;
+// cbox: six doubles a chunk).  relax_guard: state |= 2 at the free corners of the faces an iteration would flip.
+// relax_apply: x, fkey from closest / key where state == 0; num[reverted] += the others.  relax_flipped:
+// num[flipped] += the faces whose normal turned against v0's.
+enum { relax_num_vol_before = 0, relax_num_vol_after, relax_num_disp, relax_num_init, relax_num_skipped,
+       relax_num_reverted, relax_num_flipped, relax_num_skipped0, relax_num_csr, relax_num_words = relax_num_csr + 4 };
+hipError_t launch_relax_accept(const int32_t* qv, int nq, const double* closest, const unsigned long long* key,
+                               const unsigned long long* sq, double* x, unsigned long long* fkey, int32_t* vq,
+                               unsigned long long* num, hipStream_t s);
+hipError_t launch_relax_candidates(const int32_t* off, const int32_t* nb, const double* x, const int32_t* qv, int nq,
+                                   const unsigned long long* fkey, const double* tri12, double lambda, double* qxyz,
+                                   unsigned long long* sq, unsigned long long* key, unsigned int* state, TriWork* work,
+                                   int n_a, int n_b, const double* cbox, hipStream_t s);
+hipError_t launch_relax_guard(const int32_t* face, long long nf, const double* x, const double* closest,
+                              const unsigned long long* key, const int32_t* vq, unsigned int* state, hipStream_t s);
+hipError_t launch_relax_apply(const int32_t* qv, int nq, const double* closest, const unsigned long long* key,
+                              const unsigned int* state, double* x, unsigned long long* fkey, unsigned long long* num,
+                              hipStream_t s);
+hipError_t launch_relax_flipped(const int32_t* face, long long nf, const double* v0, const double* x,
+                                unsigned long long* num, hipStream_t s);
 // mesh refinement (mm_refine_kernels.hip): face = int32 triples, the edge table as weld_edges sizes it.  refine_edges:
 // the table with own[2 s] = the smallest corner id 3 f + j of the slot's edge, slot[3 f + j] = the slot of corner j;
 // refine_marks: own[2 s + 1] = 0 where the edge is marked (longer than thr2; with `all` every edge between different

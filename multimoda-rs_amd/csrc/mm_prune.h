@@ -2,8 +2,17 @@
 // to triangle: mm_surface.cpp / mm_tri_kernels.hip): the slab order both sides are staged in, the boxes of their groups,
 // the lower bound lb2 every (query block, chunk) item carries, and the order the items run in.  The device half is
 // mm_prune_device.h; the argument that pruning returns the bits of a full scan is DESIGN.md 4.20.  Plain C++17, no HIP
-// and no engine header: tests/prune_host.cpp includes it on its own.
+// and no engine header: tests/prune_host.cpp includes it on its own.  Box3, box_lb2 and tri_slack are MM_HD: a HIP
+// compiler also builds them for the device, where the mesh relaxation (mm_relax_kernels.hip) refreshes the bounds of
+// queries that move -- one formula on both sides.
 #pragma once
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MM_HD __host__ __device__
+#else
+#define MM_HD
+#endif
 
 #include <algorithm>
 #include <cfloat>
@@ -19,8 +28,8 @@ namespace mm {
 // ignored, and a group of nothing but NaN keeps (DBL_MAX, -DBL_MAX).  Six doubles: lo xyz, hi xyz.
 struct Box3 {
     double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-    void add(const double* p) { for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
-    double largest() const { double m = 0.0; for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs(lo[a]), std::fabs(hi[a]))); return m; }
+    MM_HD void add(const double* p) { for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); } }
+    MM_HD double largest() const { double m = 0.0; for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs(lo[a]), std::fabs(hi[a]))); return m; }
     int longest_axis() const { int ax = 0; for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] > hi[ax] - lo[ax]) ax = a; return ax; }
 };
 static_assert(sizeof(Box3) == 48, "Box3 is six doubles");
@@ -69,7 +78,7 @@ inline void slab_permutation(const std::vector<double>& key, std::vector<int32_t
 // NaN included), nor what std::max then does with a NaN (tests/golden/prune_plans.json holds the bits from before the
 // function was shared).  Point to triangle measures to a closest point that rounding may place a few ulp outside the
 // triangle's box: it passes tri_slack (mm_surface.cpp).
-inline double box_lb2(const Box3& a, const Box3& b, double slack)
+MM_HD inline double box_lb2(const Box3& a, const Box3& b, double slack)
 {
     double s = 0.0;
     for (int ax = 0; ax < 3; ++ax) {
@@ -78,6 +87,12 @@ inline double box_lb2(const Box3& a, const Box3& b, double slack)
     }
     return s * (1.0 - 1e-12);
 }
+
+// The slack of the bound between a query block q and a chunk's corners c, point to triangle.  The closest point the rule
+// computes, u + e t or (a + ab v) + ac w with factors that rounding keeps within a few ulp of [0, 1], lies within a few
+// ulp of the largest coordinate of the triangle's own box, hence of the chunk's: each gap is narrowed by 64 such ulp
+// (DESIGN 4.19).
+MM_HD inline double tri_slack(const Box3& q, const Box3& c) { return 64.0 * DBL_EPSILON * std::max(q.largest(), c.largest()); }
 
 // Nearest chunks first: (lb2, chunk) of a query block against chunks 0 .. nch-1, ascending, ties by chunk.  cand[0] is
 // the block's item of pass A -- it runs unchecked and tightens the minima the others are checked against -- and

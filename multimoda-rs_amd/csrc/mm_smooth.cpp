@@ -27,39 +27,6 @@ int mesh_args(const int64_t* faces, int64_t nf, int64_t nv, const char* who)
     return MM_OK;
 }
 
-// The adjacency's device buffers, laid out behind whatever the caller placed first.  nb takes the place of the edge
-// table's owner words (8 bytes a slot, at least 6 nf slots): the fill runs behind the insertion, which alone writes them.
-struct CsrDev {
-    EdgeTable edges;
-    size_t o_deg, o_off, o_tile;
-    int32_t *deg, *off, *nb;
-    long long* tile;
-    unsigned long long* counts;           // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
-
-    void plan(Carve& lay, int64_t nf, int64_t nv)
-    {
-        edges.plan(lay, nf);
-        o_deg = lay.take((size_t)nv * 4); o_off = lay.take(((size_t)nv + 1) * 4);
-        o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8);
-    }
-    void bind(unsigned char* b, unsigned long long* counts_at)
-    {
-        edges.bind(b);
-        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)edges.own;
-        tile = (long long*)(b + o_tile);
-        counts = counts_at;
-    }
-};
-
-int csr_build(Engine* e, const CsrDev& d, const int32_t* face, int64_t nf, int64_t nv, int* launches)
-{
-    const EdgeTable& t = d.edges;
-    MM_TRY_HIP(launch_weld_edges(face, nf, t.keys, t.cnt, t.own, t.log2_e, e->stream));
-    ++*launches;                                                       // nf > 0: the insertion ran
-    MM_TRY_HIP(launch_mesh_csr(t.keys, t.log2_e, nv, d.deg, d.off, d.tile, d.nb, d.counts, launches, e->stream));
-    return MM_OK;
-}
-
 }  // namespace
 }  // namespace mm
 

@@ -184,6 +184,40 @@ struct EdgeTable {
     }
 };
 
+// The sorted vertex adjacency of mm_smooth_kernels.hip (mm_smooth.cpp and mm_relax.cpp build it): its device buffers,
+// laid out behind whatever the caller placed first.  nb takes the place of the edge table's owner words (8 bytes a slot,
+// at least 6 nf slots): the fill runs behind the insertion, which alone writes them.
+struct CsrDev {
+    EdgeTable edges;
+    size_t o_deg, o_off, o_tile;
+    int32_t *deg, *off, *nb;
+    long long* tile;
+    unsigned long long* counts;           // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
+
+    void plan(Carve& lay, int64_t nf, int64_t nv)
+    {
+        edges.plan(lay, nf);
+        o_deg = lay.take((size_t)nv * 4); o_off = lay.take(((size_t)nv + 1) * 4);
+        o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8);
+    }
+    void bind(unsigned char* b, unsigned long long* counts_at)
+    {
+        edges.bind(b);
+        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)edges.own;
+        tile = (long long*)(b + o_tile);
+        counts = counts_at;
+    }
+};
+
+inline int csr_build(Engine* e, const CsrDev& d, const int32_t* face, int64_t nf, int64_t nv, int* launches)
+{
+    const EdgeTable& t = d.edges;
+    MM_TRY_HIP(launch_weld_edges(face, nf, t.keys, t.cnt, t.own, t.log2_e, e->stream));
+    ++*launches;                                                       // nf > 0: the insertion ran
+    MM_TRY_HIP(launch_mesh_csr(t.keys, t.log2_e, nv, d.deg, d.off, d.tile, d.nb, d.counts, launches, e->stream));
+    return MM_OK;
+}
+
 // The counts a compaction kept: the last entry of each launch_trim_scan tile array (vertices, then faces), through the
 // first 16 bytes of e->host_pts.  Synchronises the stream.
 inline int scan_totals(Engine* e, const long long* vtile, int64_t nv, const long long* ftile, int64_t nf, long long* kv,
