@@ -590,7 +590,8 @@ int     mm_mesh_vertex_rings(mm_engine* e, const int64_t* faces, int64_t nf, int
 
 /* ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: fix_and_remesh_stitched_mesh brings the coarse CCTA
  *      triangles down to the intravascular resolution with MeshLab's isotropic remesh; of that filter this is the edge
- *      split alone -- no collapse, no flip, no tangential relaxation, no reprojection, no repair) --------------------------
+ *      split alone; the flip is "mesh edge flips", the tangential relaxation and the reprojection "mesh relaxation" below;
+ *      no collapse, no repair) ---------------------------------------------------------------------------------------
  *
  * One pass on vertices v (f64) and triangles, with thr2 = (ratio target_len) (ratio target_len) computed once in f64:
  *   marked     the undirected edge lo < hi is marked when ((dx dx + dy dy) + dz dz) > thr2, d = v[hi] - v[lo] per
@@ -715,7 +716,8 @@ int     mm_tri_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris,
                     int64_t cap);
 
 /* ---- mesh relaxation (multimodars/ccta/fixing_functions.py:192-219: of MeshLab's isotropic remesh the tangential
- *      smoothing and the reprojection, smoothflag / reprojectflag / checksurfdist; collapse, flip and repair stay out) ----
+ *      smoothing and the reprojection, smoothflag / reprojectflag / checksurfdist; the flip is "mesh edge flips" below,
+ *      collapse and repair stay out) ------------------------------------------------------------------------------------
  * Slides the free vertices of a mesh (v, faces) along a reference surface (rv, rfaces; the mesh's own input where none is
  * given) and puts every one of them back on it exactly.  tests/mm_checkers/relax_mesh.py is the executable form.  All
  * arithmetic is unfused f64 in the order written; dot, the cross components and the closest point are those of "surface
@@ -785,6 +787,89 @@ int     mm_mesh_relax(mm_engine* e, const double* vertices_xyz, int64_t nv, cons
                       const double* ref_vertices, int64_t ref_nv, const int64_t* ref_tris, int64_t ref_nf,
                       const uint8_t* pinned, int64_t n_iterations, double factor, double* out_vertices,
                       int64_t* out_ref_face, mm_relax_report* report);
+
+/* ---- mesh edge flips (multimodars/ccta/fixing_functions.py:207-219: of MeshLab's isotropic remesh the swap, swapflag;
+ *      the collapse deletes vertices, needs a link condition and stays out) ---------------------------------------------
+ * Flips edges of a mesh (v, faces) until no single flip brings the valences closer to their targets.  No vertex moves, nv
+ * and nf never change.  tests/mm_checkers/flip_edges.py is the executable form.  All f64 is unfused, in the order written;
+ * len_sq is that of "mesh refinement", the cross components and dot are those of "surface distance".  One pass reads only
+ * the state before it.
+ *
+ * Edge table.  Every corner pair of every face owns its undirected edge, as mm_mesh_refine counts: an owner count, and
+ * first = the smallest corner id 3 f + j that names the edge.  deg[v] = the distinct edges lo != hi at v.  v is a border
+ * vertex when it ends an edge, an (a, a) edge too, whose owner count is not 2.  ex[v] = deg[v] - (border ? 4 : 6).  The
+ * deviation is the sum of ex[v] ex[v] over all vertices, an int64.
+ *
+ * Candidate.  An edge lo < hi is a candidate when all of these hold; they are tried in this order.
+ *   (a) its owner count is 2 and the owners traverse it in opposite directions: F+ runs lo -> hi, F- runs hi -> lo.  Two
+ *       owners of one direction make an inconsistent edge, which is counted and never flipped.
+ *   (b) both owners have three distinct indices, and the opposite corners c (of F+) and d (of F-) differ.
+ *   (c) mask[lo] == 0 and mask[hi] == 0, where a mask is given.
+ *   (d) g = 2 (ex[lo] + ex[hi] - ex[c] - ex[d]) - 4 > 0: the exact drop of the deviation if this flip alone is made.
+ *   (e) the edge c - d is not in the table.
+ *   (f) n0 = (hi-lo) x (c-lo), n1 = (lo-hi) x (d-hi), m0 = (d-lo) x (c-lo), m1 = (c-hi) x (d-hi): the normals of F+, F-
+ *       and of the two faces the flip would make.  dot(m0,n0), dot(m0,n1), dot(m1,n0), dot(m1,n1) are all > 0.
+ *   (g) dn = dot(n0,n1) > 0 and dn dn >= (crease_cos crease_cos) (dot(n0,n0) dot(n1,n1)).
+ *   (h) q(i,j,k; n) = dot(n,n) / (S S), S = (len_sq(i,j) + len_sq(j,k)) + len_sq(k,i), 0 where S == 0, a true division:
+ *       q0 = q(lo,d,c; m0), q1 = q(hi,c,d; m1), t0 = k2 q(lo,hi,c; n0), t1 = k2 q(hi,lo,d; n1) with k2 = quality_keep
+ *       quality_keep; q0 >= t0, q0 >= t1, q1 >= t0 and q1 >= t1 -- min(q0, q1) >= k2 min(q(n0), q(n1)), written so that a
+ *       NaN fails.
+ * A NaN fails whichever comparison it meets.  Of (e) .. (h) the first that fails is counted: blocked_existing, _normal,
+ * _crease, _quality, summed over the passes.
+ *
+ * Selection.  A candidate has the priority min(g, 2^20) << 32 | (0xFFFFFFFF - first): unique per edge, never 0.  best[v] =
+ * the largest priority among the candidates with v in {lo, hi, c, d}.  A candidate flips iff it is best at all four of
+ * its vertices.  So flipped edges share no vertex, hence no face: every g is exact and the deviation falls by the sum of
+ * the flipped g.  The largest priority of the mesh always flips, so a pass with a candidate flips something, and the
+ * deviation, a non-negative integer, ends the passes.  Nothing depends on an order of visits.
+ *
+ * Rewrite, in place: F+ <- (lo, d, c), F- <- (hi, c, d).  Every other face keeps its bits and its place.
+ *
+ * Passes repeat until one has no candidate (converged) or max_passes have run.  passes_run counts the passes whose
+ * candidates were sought: the last may have found none.
+ *
+ * Edges of the report, all of the input: n_edges between different vertices; open (one owner) and non-manifold (more than
+ * two), (a, a) edges too; inconsistent as in (a); masked = the edges between different vertices with a nonzero mask byte
+ * at either end.  The volumes are those of mm_refine_report.
+ *
+ * Device (mm_flip_kernels.hip; integer atomics only).  One upload: the vertices (24 nv), the faces as int32 (12 nf), the
+ * mask where given (nv): bytes_uploaded.  The faces are rewritten where they lie; per pass the 128 bytes of counters are
+ * read back.  One download: the faces and the counters, bytes_downloaded = 12 nf + 128.  Launches, with V = 1 + max(1,
+ * ceil(ceil(log2 nf) / 8)) for a volume: a pass is 5 -- the edge table with owners and first corners, the valences with
+ * the edge counts, the deviation, the candidates with their priorities, the flips.  Where no pass converged (max_passes
+ * == 0 too) the valences of the result cost 3 more:
+ *     n_launches = 2 V + 5 passes_run + (converged ? 0 : 3)
+ * With nv == 0 or nf == 0 nothing is launched, the input is returned and both deviations are 36 nv.
+ *
+ * Limits as mm_mesh_refine: int32 indices, nv, nf < 2^31 and indices in [0, nv) (MM_ERR_INVALID), 6 nf < 2^31
+ * (MM_ERR_TOO_LARGE).  crease_cos outside [0, 1], quality_keep outside [0, 1] or not finite, max_passes < 0:
+ * MM_ERR_INVALID.  On an error no output is written. */
+
+#define MM_FLIP_PASS_SLOTS 16
+
+typedef struct mm_flip_report {
+    int64_t n_vertices, n_faces;
+    int64_t n_edges, n_open_edges, n_nonmanifold_edges, n_inconsistent_edges, n_masked_edges;
+    int64_t passes_run, converged, n_flips;
+    int64_t flips_per_pass[MM_FLIP_PASS_SLOTS];        /* passes beyond 16 add into the last slot                      */
+    int64_t candidates_per_pass[MM_FLIP_PASS_SLOTS];
+    int64_t blocked_existing, blocked_normal, blocked_crease, blocked_quality;
+    int64_t deviation_before, deviation_after;
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    double  volume_before, volume_after;
+} mm_flip_report;                                      /* 424 bytes */
+
+/* The first half of a pass made public.  vertices_xyz is not read (nullable): the valences are the faces' alone.
+ * out_degree[v] = deg[v], out_border[v] = 1 for a border vertex.  info[6] = {edges, open edges, non-manifold edges,
+ * inconsistent edges, deviation, kernel launches (3)}.  With nv == 0 or nf == 0 nothing is launched. */
+int     mm_mesh_valence(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                        int32_t* out_degree, uint8_t* out_border, int64_t* info);
+/* The passes above.  mask (nullable): nv bytes.  crease_cos: the cosine of the largest angle between the normals of F+ and
+ * F- across which an edge still flips.  max_passes == 0 returns the input with the edge counts, deviations and volumes
+ * filled.  out_tris: nf triples (may be tris). */
+int     mm_mesh_flip_edges(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                           const uint8_t* mask, double crease_cos, double quality_keep, int64_t max_passes,
+                           int64_t* out_tris, mm_flip_report* report);
 
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 

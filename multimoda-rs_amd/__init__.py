@@ -38,7 +38,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    label_branches, label_branches_pair, find_sharp_angles, label, manual_hole_fill, fill_holes,
                    smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned, smooth_mesh,
                    filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh,
-                   mesh_edge_lengths, edge_length_target, refine_mesh, relax_mesh, project_to_mesh)
+                   mesh_edge_lengths, edge_length_target, refine_mesh, relax_mesh, project_to_mesh,
+                   mesh_valence, flip_edges)
 from . import surface
 from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport, point_mesh_distance,
                       sample_mesh_surface, surface_distance)
@@ -81,6 +82,7 @@ __all__ = [
     "condition_boundary_rings", "stitch_conditioned",
     "smooth_mesh", "filter_taubin", "filter_laplacian", "mesh_adjacency_csr", "vertex_rings", "postprocess_stitched_mesh",
     "mesh_edge_lengths", "edge_length_target", "refine_mesh", "relax_mesh", "project_to_mesh",
+    "mesh_valence", "flip_edges",
     "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
     "DirectedDistance", "SurfaceDistanceReport",
     "morphometry", "ContourMeasures", "contour_measures",

@@ -1519,7 +1519,8 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
-           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False) -> dict:
+           engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False,
+           flip=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1535,7 +1536,11 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     ``refine_report``.  The default ``refine=False`` changes nothing.  ``relax=True``, or a dict of ``relax_mesh``
     keywords, evens the vertices out on the surface (``relax_mesh`` against the mesh itself) behind the refinement and in
     front of the smoothing: the point lists follow and the result carries ``relax_report``.  The default ``relax=False``
-    changes nothing."""
+    changes nothing.  ``flip=True``, or a dict of ``flip_edges`` keywords, evens the valences the split left
+    (``flip_edges``) behind the refinement and in front of the relaxation, which is where it pays; no vertex moves, so
+    the point lists stay, and the result carries ``flip_report``.  Where ``pinned`` is not given, the vertices of the
+    intravascular lumen (``anomalous_points``) are pinned: its triangulation stays.  The default ``flip=False`` changes
+    nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1545,7 +1550,8 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_relax_result(_refine_result(out, refine, engine), relax, engine), smooth, engine)
+    return _smooth_result(_relax_result(_flip_result(_refine_result(out, refine, engine), flip, engine), relax, engine),
+                          smooth, engine)
 
 
 def _refine_result(out: dict, refine, engine) -> dict:
@@ -1572,6 +1578,22 @@ def _refine_result(out: dict, refine, engine) -> dict:
         for k in range(parents.shape[0]):                                # ascending: a parent's own membership is known
             member[nv0 + k] = member[parents[k, 0]] and member[parents[k, 1]]
         out[key] = np.concatenate([_p3(pts), v[nv0:][member[nv0:]]])
+    return out
+
+
+def _flip_result(out: dict, flip, engine) -> dict:
+    """The ``flip`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of flip_edges keywords.
+    Without ``pinned`` the vertices that are points of the intravascular lumen (``anomalous_points``) are pinned."""
+    if flip is False or flip is None:
+        return out
+    kw = dict(flip) if isinstance(flip, dict) else {}
+    kw.setdefault("engine", engine)
+    if "pinned" not in kw:
+        iv = out.get("anomalous_points")
+        at = _match(_p3(_mesh_parts(out["mesh"])[0]), _p3(iv)) if iv is not None and len(iv) else np.zeros(0, dtype=np.int64)
+        kw["pinned"] = np.unique(at[at >= 0])
+    out = dict(out)
+    out["mesh"], out["flip_report"] = flip_edges(out["mesh"], **kw)
     return out
 
 
@@ -1894,14 +1916,15 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
-                       engine: Optional[N.Engine] = None, smooth=False, refine=False, relax=False,
+                       engine: Optional[N.Engine] = None, smooth=False, refine=False, relax=False, flip=False,
                        **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
     carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``refine`` and ``smooth`` as in ``stitch``:
     the refinement runs behind the hole fill and adds ``refine_report``, the smoothing runs last and adds
-    ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``."""
+    ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``, and ``flip`` in front
+    of it, adding ``flip_report``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
@@ -1913,7 +1936,8 @@ def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_relax_result(_refine_result(out, refine, engine), relax, engine), smooth, engine)
+    return _smooth_result(_relax_result(_flip_result(_refine_result(out, refine, engine), flip, engine), relax, engine),
+                          smooth, engine)
 
 
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
@@ -2348,8 +2372,8 @@ def refine_mesh(mesh, target_edge_length_mm: Optional[float] = None, *, ratio: f
     """Split every edge of ``mesh`` longer than ``ratio * target_edge_length_mm`` at its midpoint, pass after pass,
     on the device: ``(mesh, parents, report)``, the mesh of the kind given, the input not modified.  This is the edge
     split of the isotropic remesh with which the reference's post-processing (fixing_functions.py:114-239, MeshLab)
-    brings the coarse CCTA triangles down to the intravascular resolution; its collapse, flip, tangential relaxation,
-    reprojection and repair steps are not part of this project.  No existing vertex moves or changes its index: new
+    brings the coarse CCTA triangles down to the intravascular resolution; its flip is ``flip_edges``, its tangential
+    relaxation and reprojection ``relax_mesh``, its collapse and repair steps are not part of this project.  No existing vertex moves or changes its index: new
     vertices follow the old ones, ``parents[k]`` = the ends ``(lo, hi)`` of the edge whose midpoint vertex
     ``nv + k`` is, and every face is replaced in place by 1 to 4 children of its winding (include/mm_ccta.h, "mesh
     refinement", states the rule; it has one bit pattern whatever the scheduling).  A closed manifold mesh stays closed
@@ -2403,6 +2427,76 @@ def refine_mesh(mesh, target_edge_length_mm: Optional[float] = None, *, ratio: f
     report["watertight"] = report["n_open_edges_after"] == 0 and report["n_nonmanifold_edges_after"] == 0
     new = _with_mesh(mesh, out_v[:rep.n_vertices].copy(), out_f[:rep.n_faces].copy())
     return new, out_p[:rep.n_vertices - nv].copy(), report
+
+
+# ---- mesh edge flips (multimodars/ccta/fixing_functions.py:207-219: the swap of the isotropic remesh) -----------------
+
+FLIP_REPORT_KEYS = ("n_vertices", "n_faces", "n_edges", "n_open_edges", "n_nonmanifold_edges", "n_inconsistent_edges",
+                    "n_masked_edges", "passes_run", "converged", "n_flips", "blocked_existing", "blocked_normal",
+                    "blocked_crease", "blocked_quality", "deviation_before", "deviation_after", "n_launches",
+                    "bytes_uploaded", "bytes_downloaded", "volume_before", "volume_after")
+
+
+def mesh_valence(mesh, *, engine: Optional[N.Engine] = None):
+    """``(degree, border, info)`` of ``mesh``: per vertex the number of distinct edges to other vertices and whether it
+    ends an edge that does not have exactly two owning corners, as ``flip_edges`` counts them (include/mm_ccta.h, "mesh
+    edge flips").  ``info``: ``n_edges``, ``n_open_edges``, ``n_nonmanifold_edges``, ``n_inconsistent_edges``,
+    ``deviation`` (the sum over the vertices of (degree - target)^2, the target 4 on the border and 6 elsewhere) and
+    ``n_launches``."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    deg = np.zeros(nv, dtype=np.int32)
+    border = np.zeros(nv, dtype=np.uint8)
+    info = np.zeros(6, dtype=np.int64)
+    N.check(N.lib().mm_mesh_valence(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), f.shape[0], N._ptr(deg), N._ptr(border),
+                                    N._ptr(info)), "mesh_valence")
+    names = ("n_edges", "n_open_edges", "n_nonmanifold_edges", "n_inconsistent_edges", "deviation", "n_launches")
+    return deg, border.astype(bool), dict(zip(names, info.tolist()))
+
+
+def flip_edges(mesh, *, crease_deg: float = 30.0, quality_keep: float = 0.5, passes: int = 50, pinned=None, band=None,
+               engine: Optional[N.Engine] = None):
+    """Flip the edges of ``mesh`` whose flip brings the valences of their four vertices closer to 6 (4 on a border),
+    pass after pass, on the device: ``(mesh, report)``, the mesh of the kind given with the same vertices and new faces,
+    the input not modified.  This is the swap of the isotropic remesh of the reference's post-processing
+    (fixing_functions.py:207-219); it runs behind ``refine_mesh``, whose midpoints have valence 4, and in front of
+    ``relax_mesh``.  A flip is made only where the new edge does not exist yet, no normal turns, the two faces meet at
+    less than ``crease_deg`` (30 degrees, MeshLab's default crease angle) and the worse of the two new triangles keeps
+    at least ``quality_keep``^2 of the quality of the worse old one.  In a pass the flips share no vertex, chosen by a
+    priority and no order of visits, so the result has one bit pattern (include/mm_ccta.h, "mesh edge flips"); every
+    pass lowers ``deviation`` and at most ``passes`` run.  No vertex moves; the other faces keep their place.
+
+    ``pinned`` and ``band`` as in ``smooth_mesh``: an edge with a pinned end does not flip.  ``report``:
+    FLIP_REPORT_KEYS, ``flips_per_pass`` and ``candidates_per_pass`` (16 entries each), ``crease_deg``,
+    ``quality_keep`` and ``volume_ratio``."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    if int(passes) < 0:
+        raise ValueError("passes must not be negative")
+    crease_deg, quality_keep = float(crease_deg), float(quality_keep)
+    if not 0.0 <= crease_deg <= 90.0:
+        raise ValueError("crease_deg must lie in [0, 90]")
+    if not 0.0 <= quality_keep <= 1.0:
+        raise ValueError("quality_keep must lie in [0, 1]")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex coordinate")
+    m8 = _pin_mask(pinned, band, v, f, engine)
+    out = np.zeros_like(f)
+    rep = N.MMFlipReport()
+    crease_cos = min(1.0, max(0.0, math.cos(math.radians(crease_deg))))
+    N.check(N.lib().mm_mesh_flip_edges(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), f.shape[0], N._ptr(m8), crease_cos,
+                                       quality_keep, int(passes), N._ptr(out), C.byref(rep)), "flip_edges")
+    report = {k: getattr(rep, k) for k in FLIP_REPORT_KEYS}
+    report["flips_per_pass"] = list(rep.flips_per_pass)
+    report["candidates_per_pass"] = list(rep.candidates_per_pass)
+    report["crease_deg"], report["quality_keep"] = crease_deg, quality_keep
+    report["volume_ratio"] = report["volume_after"] / report["volume_before"] if report["volume_before"] != 0.0 \
+        else float("nan")
+    return _with_mesh(mesh, v.copy(), out), report
 
 
 def postprocess_stitched_mesh(mesh, *, postprocessing: bool = False, lamb: float = 0.5, nu: float = 0.5,

@@ -330,6 +330,23 @@ hipError_t launch_refine_edge_list(const uint8_t* code, long long nf, const long
 hipError_t launch_refine_children(const int32_t* face, long long nf, const uint8_t* code, const int32_t* foff,
                                   const unsigned int* slot, const unsigned int* own, const double* v, int32_t* out,
                                   hipStream_t s);
+// mesh edge flips (mm_flip_kernels.hip; include/mm_ccta.h, "mesh edge flips"): face = int32 triples, rewritten in place;
+// the edge table as weld_edges sizes it, with first (4 bytes a slot) beside it; vw: one word a vertex, deg in the low 31
+// bits, the border flag in bit 31; counts: the flip_num_* words, the first flip_num_pass cleared by flip_valence.
+// flip_valence: the table, vw and counts[edges .. deviation] of the faces as they are (3 kernels).  flip_pass, behind it:
+// prio (8 bytes a slot) and opp (the two opposite corners, 8 bytes a slot) of the candidates, best (8 bytes a vertex),
+// counts[candidates .. quality]; then the flips, counts[flips] (2 kernels).  cc2, qk2: the squares of crease_cos and
+// quality_keep.
+enum { flip_num_edges = 0, flip_num_open, flip_num_nonmanifold, flip_num_inconsistent, flip_num_masked, flip_num_deviation,
+       flip_num_candidates, flip_num_existing, flip_num_normal, flip_num_crease, flip_num_quality, flip_num_flips,
+       flip_num_pass, flip_num_vol_before = 14, flip_num_vol_after, flip_num_words };
+hipError_t launch_flip_valence(const int32_t* face, long long nf, long long nv, const uint8_t* pin,
+                               unsigned long long* keys, unsigned int* cnt, unsigned int* own, unsigned int* first,
+                               int log2_cap, unsigned int* vw, unsigned long long* counts, hipStream_t s);
+hipError_t launch_flip_pass(int32_t* face, long long nv, const double* v, const uint8_t* pin, const unsigned long long* keys,
+                            const unsigned int* cnt, const unsigned int* own, const unsigned int* first, int log2_cap,
+                            const unsigned int* vw, double cc2, double qk2, unsigned long long* prio, int32_t* opp,
+                            unsigned long long* best, unsigned long long* counts, hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

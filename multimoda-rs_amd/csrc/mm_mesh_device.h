@@ -1,7 +1,7 @@
-// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine
-// _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim
-// and refine files insert, the close and smooth files read, EdgeTable of mm_stage.h sizes it), the workgroup scan and the two
-// per-wave ballot idioms.  Header-only; internal.
+// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_flip
+// _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
+// refine and flip files insert, the close, smooth and flip files read, EdgeTable of mm_stage.h sizes it), the workgroup scan
+// and the two per-wave ballot idioms.  Header-only; internal.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -67,6 +67,20 @@ static __device__ __forceinline__ unsigned long long edge_claim(unsigned long lo
     for (;;) {
         const unsigned long long prev = atomicCAS(&keys[s], kEdgeEmpty, key);
         if (prev == kEdgeEmpty || prev == key) return s;
+        s = (s + 1) & mask;
+    }
+}
+
+// the slot of the undirected edge u - v in a table nothing inserts into any more, kEdgeEmpty where it has none
+static __device__ __forceinline__ unsigned long long edge_find(const unsigned long long* __restrict__ keys,
+                                                               unsigned long long mask, int shift, int32_t u, int32_t v)
+{
+    const unsigned long long key = edge_key(u, v);
+    unsigned long long s = edge_slot(key, shift);
+    for (;;) {
+        const unsigned long long at = keys[s];
+        if (at == key) return s;
+        if (at == kEdgeEmpty) return kEdgeEmpty;
         s = (s + 1) & mask;
     }
 }
