@@ -145,7 +145,7 @@ int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
  * MM_PRECISION_F32_MATRIX chooses per PAIR: only pairs with a set of fewer than 64 or more than 2048 points (or a radius
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
-/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix and mm_engine_set_screen_cull apply to the levels staged
+/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull and mm_engine_set_screen_split apply to the levels staged
  * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
  * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
@@ -161,6 +161,11 @@ int  mm_engine_set_bound_matrix(mm_engine* e, int on);
  * provably hold no row or column minimum (default, on != 0; bit-identical screened values); on == 0 computes every tile
  * (the A/B switch). */
 int  mm_engine_set_screen_cull(mm_engine* e, int on);
+/* The culled screen cuts a set into tiles of 32 consecutive points.  A search set of two runs (lumen ++ catheter) gets a
+ * tile that straddles both and whose bounding circle no other tile is far from; with the switch on (default) each run
+ * starts a tile of its own wherever that adds no tile (ceil(main / 32) + ceil((n - main) / 32) == ceil(n / 32)): fewer
+ * tiles computed, bit-identical screened values.  on == 0: the points in order (the A/B switch). */
+int  mm_engine_set_screen_split(mm_engine* e, int on);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
@@ -196,11 +201,23 @@ int  mm_pick_minima(mm_engine* e, const double* rx, const double* ry, int nr, co
  * values.  Sets of 64 .. 544 points. */
 int  mm_screen_values(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                       double cx, double cy, const double* angles, int n_angles, int flags, int cull, float* out_sq2, double* e2);
+/* The same for sets of two runs: the first ref_main / tgt_main points, then the rest (0: one run), as a search set is
+ * lumen ++ catheter.  Whether a side is split is the engine's decision (mm_engine_set_screen_split). */
+int  mm_screen_values_split(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty,
+                            int nt, int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles,
+                            int flags, int cull, float* out_sq2, double* e2);
+/* TEST HOOK (host only): the culled screen's layout of a set of n points in two runs (main, n - main): out[j] = the point
+ * in slot j for j < slots, laid out as asked (main == 0: in order).  Returns the split the engine takes for (n, main):
+ * main where it adds no tile, else 0; < 0 on bad arguments. */
+int  mm_tile_slot_map(int n, int main, int slots, int32_t* out);
 /* TEST HOOK (host only): the culled screen's tile bound for f32 sets relative to the rotation centre, scaled by 2^e, the
  * target rotated by (c, s): circles[4 * (row tiles + column tiles)] (cx, cy, r, 0; column centres rotated) and
  * thr[row tiles * column tiles], below every screened squared distance of the tile pair when > 0 (error bound e2). */
 int  mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int e, float c,
                          float s, double e2, float* circles, float* thr);
+/* The same with either set laid out as two runs (ref_main / tgt_main as mm_tile_slot_map lays them out; 0: in order). */
+int  mm_tile_bound_probe_split(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt,
+                               int ref_main, int tgt_main, int e, float c, float s, double e2, float* circles, float* thr);
 
 /* ---- the metric: hausdorff_distance (process_utils.rs:78-82) ------------------------ */
 /* f64-exact on the device; empty set on either side -> 0.0 (process_utils.rs:86-88). */

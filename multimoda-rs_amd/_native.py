@@ -31,6 +31,7 @@ EXPORTS = [
     "mm_engine_profile", "mm_engine_profile_read", "mm_engine_profile_launches", "mm_engine_bound_stats", "mm_engine_first_min_stats", "mm_engine_screen_stats", "mm_engine_set_bound_matrix", "mm_lower_bounds", "mm_pick_minima",
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_screen_values", "mm_tile_bound_probe",
+    "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -326,6 +327,14 @@ def lib():
     L.mm_screen_values.argtypes = [P, P, P, I, P, P, I, D, D, P, I, I, I, P, P]
     L.mm_tile_bound_probe.restype = I
     L.mm_tile_bound_probe.argtypes = [P, P, I, P, P, I, I, C.c_float, C.c_float, D, P, P]
+    L.mm_engine_set_screen_split.restype = I
+    L.mm_engine_set_screen_split.argtypes = [P, I]
+    L.mm_screen_values_split.restype = I
+    L.mm_screen_values_split.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, P, P]
+    L.mm_tile_bound_probe_split.restype = I
+    L.mm_tile_bound_probe_split.argtypes = [P, P, I, P, P, I, I, I, I, C.c_float, C.c_float, D, P, P]
+    L.mm_tile_slot_map.restype = I
+    L.mm_tile_slot_map.argtypes = [I, I, I, P]
     L.mm_parse_contour_table.restype = I64
     L.mm_parse_contour_table.argtypes = [C.c_char_p, I64, C.c_char, P, I64]
     L.mm_engine_set_bound_min_candidates.restype = I
@@ -956,19 +965,32 @@ class Engine:
         """MM_PRECISION_F32_MATRIX: skip the tiles that provably hold no minimum (default) or compute every tile."""
         check(lib().mm_engine_set_screen_cull(self._h, int(on)), "mm_engine_set_screen_cull")
 
+    def set_screen_split(self, on: bool):
+        """Culled screen: a set of two runs (lumen ++ catheter) gets tiles per run where that adds no tile (default), or
+        tiles of consecutive points."""
+        check(lib().mm_engine_set_screen_split(self._h, int(on)), "mm_engine_set_screen_split")
+
     def screen_tiles(self):
         """Tiles of the culled screen since the engine was created: (computed, what the full screen computes)."""
         out = np.zeros(2, dtype=np.int64)
         check(lib().mm_engine_screen_tiles(self._h, _ptr(out)), "mm_engine_screen_tiles")
         return int(out[0]), int(out[1])
 
-    def screen_values(self, ref, tgt, angles, centre, cull=True, skip_zero=True):
-        """TEST HOOK (``mm_screen_values``): every candidate's screened squared value and e2, culled or full screen."""
+    def screen_values(self, ref, tgt, angles, centre, cull=True, skip_zero=True, split=None):
+        """TEST HOOK (``mm_screen_values``): every candidate's screened squared value and e2, culled or full screen.
+        ``split=(ref_main, tgt_main)``: the sets are two runs, the first of these lengths (0: one run), through
+        ``mm_screen_values_split``."""
         ref = np.ascontiguousarray(ref, dtype=np.float64); tgt = np.ascontiguousarray(tgt, dtype=np.float64)
         rx, ry = np.ascontiguousarray(ref[:, 0]), np.ascontiguousarray(ref[:, 1])
         tx, ty = np.ascontiguousarray(tgt[:, 0]), np.ascontiguousarray(tgt[:, 1])
         ang = np.ascontiguousarray(angles, dtype=np.float64)
         out, e2 = np.zeros(len(ang), dtype=np.float32), C.c_double(0.0)
+        if split is not None:
+            check(lib().mm_screen_values_split(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), int(split[0]),
+                                               int(split[1]), float(centre[0]), float(centre[1]), _ptr(ang), len(ang),
+                                               MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(cull)), _ptr(out), C.byref(e2)),
+                  "mm_screen_values_split")
+            return out, e2.value
         check(lib().mm_screen_values(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), float(centre[0]),
                                      float(centre[1]), _ptr(ang), len(ang), MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(cull)),
                                      _ptr(out), C.byref(e2)), "mm_screen_values")

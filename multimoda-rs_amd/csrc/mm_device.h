@@ -23,6 +23,8 @@ struct PairDesc {
     int32_t ang_begin;        // first candidate of the slice this plan owns
     int32_t n_slice;          // candidates in the slice (== n_ang, except for empty-set pairs: n_ang = 0 there)
     int32_t pad0;             // k_screen_mx: scale exponent e (coordinates are multiplied by 2^e); otherwise 0
+    int32_t ref_main, tgt_main;   // k_screen_mx_cull: > 0 -- the set is two runs (main points, then the rest) and each run
+                                  // starts a tile of its own (mm_tile_slot_point, mm_tile_bound.h); 0: the points in order
     double  cx, cy;           // rotation centre (exact kernel)
     double  delta;            // f32 screening error bound (same unit as the costs)
     double  tol2;             // candidates within tol2 of the exact minimum are reported as near-ties

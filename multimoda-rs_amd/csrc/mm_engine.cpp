@@ -151,6 +151,7 @@ int Plan::alloc_pool(Engine* e, const std::vector<int32_t>& lens, bool transient
     const size_t S = lens.size();
     set_off.assign(S, 0); set_len.assign(S, 0);
     set_rho.assign(S, 0.0);
+    set_main.assign(S, 0);
     n_points = 0;
     for (size_t s = 0; s < S; ++s) {
         if (lens[s] < 0) return set_error(MM_ERR_INVALID, "negative set size");
@@ -200,6 +201,7 @@ int Plan::stage_sets(Engine* e, const std::vector<SetRef>& sets, bool transient_
             if (r2 <= 1.0e300) rho2 = std::max(rho2, r2); else bad = true;
         }
         set_rho[s] = bad ? INFINITY : std::sqrt(rho2) * (1.0 + 1e-12);
+        set_main[s] = r.main > 0 && r.main < r.n ? r.main : 0;
     }
     if (pts_bytes) MM_HIP(upload(pts_blob, h, pts_bytes, transient, st));
     if (!transient) MM_HIP(hipStreamSynchronize(st));
@@ -527,6 +529,14 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
                 }
                 g.work_count = (int)(wstart[(size_t)q1] - wstart[(size_t)q]);
                 if (g.screen == Screen::Matrix && opts.screen_cull && mx_cull_takes(g.nct, g.multi, g.a_cap)) g.screen = Screen::MatrixCull;
+                // the culled screen lays a set of two runs out run by run where that adds no tile: per set, per pair side
+                if (g.screen == Screen::MatrixCull && opts.screen_split)
+                    for (int k = q; k < q1; ++k) {
+                        const int p = order[(size_t)k];
+                        PairDesc& d = host_pairs[p];
+                        d.ref_main = mm_tile_split_main(d.n_ref, set_main[(size_t)pairs[p].ref_set]);
+                        d.tgt_main = mm_tile_split_main(d.n_tgt, set_main[(size_t)pairs[p].tgt_set]);
+                    }
                 if (g.work_count > 0) groups.push_back(g);
                 q = q1;
             }
@@ -1253,6 +1263,14 @@ int mm_engine_set_screen_cull(mm_engine* h, int on)
     return MM_OK;
 }
 
+int mm_engine_set_screen_split(mm_engine* h, int on)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    e->screen_opts.screen_split = on != 0;
+    return MM_OK;
+}
+
 int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
 {
     Engine* e = reinterpret_cast<Engine*>(h);
@@ -1412,11 +1430,21 @@ int mm_pick_minima(mm_engine* h, const double* rx, const double* ry, int nr, con
 int mm_screen_values(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                      double cx, double cy, const double* angles, int n_angles, int flags, int cull, float* out_sq2, double* e2)
 {
+    return mm_screen_values_split(h, rx, ry, nr, tx, ty, nt, 0, 0, cx, cy, angles, n_angles, flags, cull, out_sq2, e2);
+}
+
+// The same for sets of two runs: the first ref_main / tgt_main points, then the rest (0: one run).  The culled screen takes
+// a split per side where the engine's switch (mm_engine_set_screen_split) is on and the split adds no tile.
+int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                           int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
+                           int cull, float* out_sq2, double* e2)
+{
     Engine* e = reinterpret_cast<Engine*>(h);
-    if (!e || !rx || !ry || !tx || !ty || !angles || !out_sq2 || nr <= 0 || nt <= 0 || n_angles <= 0)
+    if (!e || !rx || !ry || !tx || !ty || !angles || !out_sq2 || nr <= 0 || nt <= 0 || n_angles <= 0 || ref_main < 0 ||
+        tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
         return set_error(MM_ERR_INVALID, "mm_screen_values: bad arguments");
     MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
+    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy, ref_main}, SetRef{tx, ty, nt, cx, cy, tgt_main}};
     std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
     opts.bound_min_candidates = 0; opts.screen_cull = cull != 0;
@@ -1440,23 +1468,39 @@ int mm_screen_values(mm_engine* h, const double* rx, const double* ry, int nr, c
 // rotated by (c, s): circles[4 * (nrt + nct)] (row tiles, then column tiles, each cx, cy, r, 0; column centres rotated) and
 // thr[nrt * nct] (row-major), the threshold every screened squared distance of the tile is >= (when > 0) for an error
 // bound e2 (unscaled).
+int mm_tile_slot_map(int n, int main, int slots, int32_t* out)
+{
+    if (n <= 0 || main < 0 || main >= n || slots < 0 || (slots > 0 && !out)) return set_error(MM_ERR_INVALID, "mm_tile_slot_map: bad arguments");
+    for (int j = 0; j < slots; ++j) out[j] = mm_tile_slot_point(j, n, main);
+    return mm_tile_split_main(n, main);
+}
+
 int mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int e, float c,
                         float s, double e2, float* circles, float* thr)
 {
-    if (!rx || !ry || !tx || !ty || !circles || !thr || nr <= 0 || nt <= 0 || nr > 1 << 20 || nt > 1 << 20 || e < -126 || e > 126)
+    return mm_tile_bound_probe_split(rx, ry, nr, tx, ty, nt, 0, 0, e, c, s, e2, circles, thr);
+}
+
+// The same with either set laid out as two runs (mm_tile_slot_point; 0: one run), as the kernel lays out a pair whose
+// PairDesc carries ref_main / tgt_main.  The caller decides whether a split is taken (mm_tile_split_main).
+int mm_tile_bound_probe_split(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int ref_main,
+                              int tgt_main, int e, float c, float s, double e2, float* circles, float* thr)
+{
+    if (!rx || !ry || !tx || !ty || !circles || !thr || nr <= 0 || nt <= 0 || nr > 1 << 20 || nt > 1 << 20 || e < -126 || e > 126 ||
+        ref_main < 0 || tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
         return set_error(MM_ERR_INVALID, "mm_tile_bound_probe: bad arguments");
     const int nrt = (nr + 31) / 32, nct = (nt + 31) / 32;
     const float S = std::ldexp(1.0f, e);
     const float e2s = mm_tile_e2s(e2, e);
     for (int i = 0; i < nrt; ++i) {
         float* o = circles + 4 * i;
-        mm_tile_circle(rx, ry, 32 * i, nr, S, o, o + 1, o + 2);
+        mm_tile_circle(rx, ry, 32 * i, nr, S, o, o + 1, o + 2, ref_main);
         o[3] = 0.0f;
     }
     for (int j = 0; j < nct; ++j) {
         float* o = circles + 4 * (nrt + j);
         float ux, uy;
-        mm_tile_circle(tx, ty, 32 * j, nt, S, &ux, &uy, o + 2);
+        mm_tile_circle(tx, ty, 32 * j, nt, S, &ux, &uy, o + 2, tgt_main);
         o[0] = std::fma(ux, c, -(uy * s)); o[1] = std::fma(ux, s, uy * c); o[3] = 0.0f;
     }
     for (int i = 0; i < nrt; ++i)

@@ -34,6 +34,8 @@ struct ScreenOptions {
     bool bound_matrix = true;               // MM_PRECISION_F32_BOUNDED: bounds, picks and survivors on the matrix pipe
     int bound_matrix_qt = 1, bound_matrix_nc = 1;   // k_bound_mx's variant: query tiles per side, candidates per wave
     bool screen_cull = true;                // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull
+    bool screen_split = true;               // k_screen_mx_cull: a set of two runs (lumen ++ catheter) gives each run tiles of its
+                                            // own where that adds no tile (PairDesc::ref_main / tgt_main)
 };
 
 // One device + one stream + grow-only staging buffers (pinned host, device) reused by the
@@ -107,6 +109,7 @@ struct Engine {
 // ---- internal batch description (the C ABI wrappers translate into this) --------------
 struct SetRef {            // one point set: SoA f64 as given + the centre its f32 copy is relative to
     const double* x; const double* y; int32_t n; double cx, cy;
+    int32_t main = 0;      // > 0: the set is two runs, `main` points and then the rest (Plan::set_main)
 };
 struct PairSpec {          // one search
     int32_t ref_set, tgt_set;      // indices into the set list
@@ -139,6 +142,8 @@ struct Plan {
     // sets
     std::vector<int32_t> set_off, set_len;
     std::vector<double> set_rho;   // max distance of a point from the set's centre
+    std::vector<int32_t> set_main; // > 0: the set is two runs of consecutive points (lumen, then catheter), the first of this
+                                   // length; 0: one run.  What the culled screen may lay out tile by tile (ScreenOptions::screen_split)
     int64_t n_points = 0;
     unsigned char* pts_blob = nullptr; size_t pts_bytes = 0; bool own_pts = false; size_t pts_cap = 0;
     size_t o32x = 0, o32y = 0, o64x = 0, o64y = 0;   // planes of the pool inside pts_blob

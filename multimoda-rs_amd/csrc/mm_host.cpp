@@ -167,13 +167,17 @@ static SampleSpec sample_spec(const mm_geometry* g, int64_t sample_size)
     return s;
 }
 
-// align_within.rs:173-191
-static void frame_search_set(const mm_geometry* g, int32_t i, const SampleSpec& s, std::vector<double>& ox,
-                             std::vector<double>& oy)
+// align_within.rs:173-191.  Returns the set's split point: the lumen points in front of its catheter points (SetRef::main),
+// 0 for a set of one run.
+static int32_t frame_search_set(const mm_geometry* g, int32_t i, const SampleSpec& s, std::vector<double>& ox,
+                                std::vector<double>& oy)
 {
+    const size_t n0 = ox.size();
     downsample_append(g->lumen + 3 * g->lumen_off[i], g->lumen_off[i + 1] - g->lumen_off[i], s.lumen, ox, oy);
+    const size_t n1 = ox.size();
     if (s.has_cath && g->cath_off)
         downsample_append(g->cath + 3 * g->cath_off[i], g->cath_off[i + 1] - g->cath_off[i], s.cath, ox, oy);
+    return n1 > n0 && ox.size() > n1 && n1 - n0 < (size_t)INT32_MAX ? (int32_t)(n1 - n0) : 0;
 }
 
 // geometry.rs:42-69
@@ -193,6 +197,7 @@ static size_t ref_or_proximal(const mm_geometry* g)
 // -------------------------------------------------------------------------------------
 struct SearchJob {
     std::vector<double> rx, ry, tx, ty;
+    int32_t r_main = 0, t_main = 0;   // split points of the two sets (frame_search_set)
     double cx = 0.0, cy = 0.0;
     int32_t flags = 0;
     double result = 0.0;  // chosen angle (radians)
@@ -222,8 +227,8 @@ static int run_searches(Engine* e, std::vector<SearchJob>& jobs, double step_deg
         for (int j : active) {
             const SearchJob& sj = jobs[j];
             const int32_t sid = (int32_t)sets.size();
-            sets.push_back(SetRef{sj.rx.data(), sj.ry.data(), (int32_t)sj.rx.size(), sj.cx, sj.cy});
-            sets.push_back(SetRef{sj.tx.data(), sj.ty.data(), (int32_t)sj.tx.size(), sj.cx, sj.cy});
+            sets.push_back(SetRef{sj.rx.data(), sj.ry.data(), (int32_t)sj.rx.size(), sj.cx, sj.cy, sj.r_main});
+            sets.push_back(SetRef{sj.tx.data(), sj.ty.data(), (int32_t)sj.tx.size(), sj.cx, sj.cy, sj.t_main});
             pairs.push_back(PairSpec{sid, sid + 1, sj.cx, sj.cy, sj.flags, lists[j].data(), (int32_t)lists[j].size(), 0.0, 0.0});
             if (pose_evals) *pose_evals += (int64_t)lists[j].size();
         }
@@ -347,6 +352,7 @@ int WithinPlan::build_sets_host(int32_t n_sets)
 {
     sx.assign((size_t)n_sets, {}); sy.assign((size_t)n_sets, {});
     std::vector<double> set_scale((size_t)n_sets, 0.0);
+    std::vector<int32_t> set_main((size_t)n_sets, 0);
     std::vector<int> set_geom((size_t)n_sets);
     for (int g = 0; g < n_geoms; ++g)
         for (int32_t i = 0; i < geoms[g]->n_frames; ++i) set_geom[(size_t)(set_base[g] + i)] = g;
@@ -357,7 +363,7 @@ int WithinPlan::build_sets_host(int32_t n_sets)
             const int32_t i = s - set_base[g];
             const mm_geometry* G = geoms[g];
             std::vector<double>&x = sx[(size_t)s], &y = sy[(size_t)s];
-            frame_search_set(G, i, spec[g], x, y);
+            set_main[(size_t)s] = frame_search_set(G, i, spec[g], x, y);
             const double cx = G->centroid[3 * i], cy = G->centroid[3 * i + 1];
             double scale = 0.0;
             for (size_t k = 0; k < x.size(); ++k) {
@@ -375,7 +381,7 @@ int WithinPlan::build_sets_host(int32_t n_sets)
         eps[g] = std::ldexp(4.0 * scale + 1.0, -42);
     }
     std::vector<SetRef> sets(sx.size());
-    for (size_t s = 0; s < sx.size(); ++s) sets[s] = SetRef{sx[s].data(), sy[s].data(), (int32_t)sx[s].size(), 0.0, 0.0};
+    for (size_t s = 0; s < sx.size(); ++s) sets[s] = SetRef{sx[s].data(), sy[s].data(), (int32_t)sx[s].size(), 0.0, 0.0, set_main[s]};
     TraceTimer t("prepare: stage sets (host)");
     return plan.stage_sets(e, sets, /*transient=*/false, e->aux);   // staging: the high-priority side stream
 }
@@ -440,7 +446,12 @@ int WithinPlan::build_sets_device(int32_t n_sets)
     TraceTimer t_alloc("prepare:   descriptors + pool");
     int rc = plan.alloc_pool(e, lens, /*transient=*/false);
     if (rc) return rc;
-    for (int32_t s = 0; s < n_sets; ++s) src[(size_t)s].dst_off = plan.set_off[(size_t)s];
+    for (int32_t s = 0; s < n_sets; ++s) {
+        SetSrc& d = src[(size_t)s];
+        d.dst_off = plan.set_off[(size_t)s];
+        const int32_t lum = std::min(d.lum_len, d.lum_take);
+        plan.set_main[(size_t)s] = lum > 0 && lum < d.n ? lum : 0;      // lumen ++ catheter: the set's two runs
+    }
     t_alloc.stop();
 
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -930,8 +941,8 @@ int WithinPlan::walk(mm_alignlog** logs, int64_t* pose_evals, int64_t* n_unresol
                 if (pose_evals) *pose_evals += evals[j];
             } else {
                 SearchJob job;
-                frame_search_set(G, i, spec[g], job.tx, job.ty);      // :92-93
-                frame_search_set(G, i - 1, spec[g], job.rx, job.ry);  // :94-95
+                job.t_main = frame_search_set(G, i, spec[g], job.tx, job.ty);      // :92-93
+                job.r_main = frame_search_set(G, i - 1, spec[g], job.rx, job.ry);  // :94-95
                 job.cx = st.cx; job.cy = st.cy; job.flags = MM_SEARCH_SKIP_ZERO;
                 jobs.push_back(std::move(job));
                 job_owner.push_back((int)steps.size());
@@ -1235,8 +1246,8 @@ int mm_align_within(mm_engine* eh, int n_geoms, mm_geometry** geoms, double step
             const double tx = pcx - G->centroid[3 * i], ty = pcy - G->centroid[3 * i + 1];  // :84-88
             mm_frame_translate(G, i, tx, ty, 0.0);                                            // :90
             SearchJob job;
-            frame_search_set(G, i, spec[g], job.tx, job.ty);      // testing_points   :92-93
-            frame_search_set(G, i - 1, spec[g], job.rx, job.ry);  // reference_points :94-95
+            job.t_main = frame_search_set(G, i, spec[g], job.tx, job.ty);      // testing_points   :92-93
+            job.r_main = frame_search_set(G, i - 1, spec[g], job.rx, job.ry);  // reference_points :94-95
             job.cx = G->centroid[3 * i]; job.cy = G->centroid[3 * i + 1];
             job.flags = MM_SEARCH_SKIP_ZERO;
             jobs.push_back(std::move(job));

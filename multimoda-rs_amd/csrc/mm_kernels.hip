@@ -597,12 +597,13 @@ static __device__ __forceinline__ h8v mx_fragment(float X, float Y, int hi)
 
 typedef _Float16 h4v __attribute__((ext_vector_type(4)));
 
-// the n points at (px, py) as ntiles x 64 row fragments in LDS (padding rows duplicate the last point), by 256 threads.  Four
+// the n points at (px, py) as ntiles x 64 row fragments in LDS (padding rows duplicate the last point; main > 0: the two
+// runs of a split set tile by tile, mm_tile_slot_point), by 256 threads.  Four
 // slots per thread and pass: the loads of a pass are issued together -- fragment by fragment the loop exposed one global-memory
 // round trip per slot (8.5 of them for a 544-point set: ~25 us of a bound kernel's work item, more than its MFMAs)
 template <int NT = 256>
 static __device__ __forceinline__ void mx_stage_rows(h8v* __restrict__ s_dst, int ntiles, int n, const float* __restrict__ px,
-                                                     const float* __restrict__ py, float S, int tid)
+                                                     const float* __restrict__ py, float S, int tid, int main = 0)
 {
     constexpr int U = NT >= 256 ? 4 : 9;        // slots per thread and pass (one wave: 17 row tiles in two passes)
     const int total = ntiles * 64;
@@ -611,7 +612,7 @@ static __device__ __forceinline__ void mx_stage_rows(h8v* __restrict__ s_dst, in
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int slot = s0 + NT * u < total ? s0 + NT * u : total - 1;
-            const int row = (slot >> 6) * 32 + (slot & 31), rc = row < n ? row : n - 1;
+            const int row = (slot >> 6) * 32 + (slot & 31), rc = mm_tile_slot_point(row, n, main);
             x[u] = px[rc]; y[u] = py[rc];
         }
 #pragma unroll
@@ -1001,6 +1002,9 @@ int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 // (A positive f32 compares like its bits as an integer; a negative minimum -- rounding below 0 for coincident points --
 // is below every positive threshold in that order too.)  The mask of a row tile is wave-uniform (one candidate per
 // wave): one scalar loop over its set bits.
+// Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
+// -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
+// no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
 // -------------------------------------------------------------------------------------
 typedef float f16x16 __attribute__((ext_vector_type(16)));
 
@@ -1148,23 +1152,24 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
             s_cs[t] = (t & 1) ? sinv[pd.tab_off + a] : cosv[pd.tab_off + a];
             if (!(t & 1)) s_ci[t >> 1] = a;
         }
-        mx_stage_rows<64 * WAVES>(s_a, nrt, na, ptx + pd.ref_off, pty + pd.ref_off, S, tid);
+        // a split set (ref_main / tgt_main > 0, Plan::stage_level): its two runs tile by tile, here and in the circles
+        mx_stage_rows<64 * WAVES>(s_a, nrt, na, ptx + pd.ref_off, pty + pd.ref_off, S, tid, pd.ref_main);
         float tx[NQ], ty[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int j = lane + 64 * q;
-            const int jc = j < nb ? j : nb - 1;
+            const int jc = mm_tile_slot_point(j, nb, pd.tgt_main);
             tx[q] = S * ptx[pd.tgt_off + jc]; ty[q] = S * pty[pd.tgt_off + jc];
             if (j < NB) s_b[(j >> 5) * 64 + (j & 31) + 32] = mx_col_norm(tx[q], ty[q]);
         }
         // the circles: thread t < NCT column tile t, thread 64 + t row tile t
         if (tid < NCT) {
             float cx, cy, r;
-            mm_tile_circle(ptx + pd.tgt_off, pty + pd.tgt_off, tid * 32, nb, S, &cx, &cy, &r);
+            mm_tile_circle(ptx + pd.tgt_off, pty + pd.tgt_off, tid * 32, nb, S, &cx, &cy, &r, pd.tgt_main);
             s_circ[tid] = float4{cx, cy, r, 0.0f};
         } else if (tid >= 64 && tid < 64 + nrt) {
             float cx, cy, r;
-            mm_tile_circle(ptx + pd.ref_off, pty + pd.ref_off, (tid - 64) * 32, na, S, &cx, &cy, &r);
+            mm_tile_circle(ptx + pd.ref_off, pty + pd.ref_off, (tid - 64) * 32, na, S, &cx, &cy, &r, pd.ref_main);
             s_circ[NCT + tid - 64] = float4{cx, cy, r, 0.0f};
         }
         __syncthreads();

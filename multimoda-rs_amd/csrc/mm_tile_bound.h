@@ -1,6 +1,7 @@
-// Tile bound of the culled matrix-pipe screen (k_screen_mx_cull, mm_kernels.hip): a bounding circle per tile of 32
-// consecutive points and a lower bound of the squared distance between any two points of two tiles.  Shared by the kernel
-// and the host (mm_tile_bound_probe, the test hook that checks it against f64), so both run the same f32 operations.
+// Tile bound of the culled matrix-pipe screen (k_screen_mx_cull, mm_kernels.hip): the layout of a set in tiles of 32 slots
+// (mm_tile_slot_point: consecutive points, or the two runs of a split set tile by tile), a bounding circle per tile and a
+// lower bound of the squared distance between any two points of two tiles.  Shared by the kernel and the host
+// (mm_tile_bound_probe, the test hook that checks it against f64), so both run the same f32 operations.
 //
 // Units are the screen's scaled units (x = 2^e * coordinate, every point of the pair within 512 of the rotation centre:
 // every coordinate, centre and radius below 2^10 in magnitude, every distance below 2^11).
@@ -24,23 +25,45 @@ MM_TB_HD inline float mm_tb_sqrt(float x)
 #endif
 }
 
-// Bounding circle of the points (S * px[k], S * py[k]), k = base .. base + 31, indices clamped to n - 1 (the padding rows
-// and columns of a tile duplicate the set's last point, as the screen's fragments do).  Centre: middle of the bounding box.
+// The point in slot j (>= 0) of a set of n points laid out in tiles of 32 slots.  main == 0: the points in order, the slots
+// from n on duplicate the last point.  0 < main < n: the set is two runs, `main` points and then n - main (lumen and
+// catheter of a search set), and each run starts a tile of its own: the first run fills ceil(main / 32) tiles, padded with
+// its last point, the second run the slots behind them, padded with the set's last point.  Every point has a slot and a
+// padding slot duplicates a point of its own run, so the multiset of values a screen takes minima over gains nothing new.
+MM_TB_HD inline int mm_tile_slot_point(int j, int n, int main)
+{
+    if (main <= 0 || main >= n) return j < n ? j : n - 1;
+    const int edge = ((main + 31) >> 5) << 5;
+    if (j < edge) return j < main ? j : main - 1;
+    const int k = j - edge, m = n - main;
+    return main + (k < m ? k : m - 1);
+}
+
+// The split a set of n points in two runs (main, n - main) may take: it must add no tile.  Else 0 (no split).
+MM_TB_HD inline int mm_tile_split_main(int n, int main)
+{
+    if (main <= 0 || main >= n) return 0;
+    return ((main + 31) >> 5) + ((n - main + 31) >> 5) == ((n + 31) >> 5) ? main : 0;
+}
+
+// Bounding circle of the points (S * px[i], S * py[i]) in the slots base .. base + 31 of the set (mm_tile_slot_point: the
+// padding rows and columns of a tile duplicate a point, as the screen's fragments do).  Centre: middle of the bounding box.
 // Radius: rounded UP -- the computed distance of a point from the centre carries at most 5 roundings of relative size 2^-24
 // (difference, square, fma, sqrt), the factor 1 + 2^-18 covers 64 of them and 2^-10 covers the f32 underflow of squares of
 // differences below 2^-60 -- so every point of the tile lies inside the circle, exactly.
-MM_TB_HD inline void mm_tile_circle(const float* px, const float* py, int base, int n, float S, float* cx, float* cy, float* r)
+MM_TB_HD inline void mm_tile_circle(const float* px, const float* py, int base, int n, float S, float* cx, float* cy, float* r,
+                                    int main = 0)
 {
     float x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
     for (int k = 0; k < 32; ++k) {
-        const int i = base + k < n ? base + k : n - 1;
+        const int i = mm_tile_slot_point(base + k, n, main);
         const float x = S * px[i], y = S * py[i];
         x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
     }
     const float mx = 0.5f * (x0 + x1), my = 0.5f * (y0 + y1);
     float m = 0.0f;
     for (int k = 0; k < 32; ++k) {
-        const int i = base + k < n ? base + k : n - 1;
+        const int i = mm_tile_slot_point(base + k, n, main);
         const float dx = S * px[i] - mx, dy = S * py[i] - my;
         m = fmaxf(m, fmaf(dx, dx, dy * dy));
     }
