@@ -145,7 +145,8 @@ int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
  * MM_PRECISION_F32_MATRIX chooses per PAIR: only pairs with a set of fewer than 64 or more than 2048 points (or a radius
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
-/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull and mm_engine_set_screen_split apply to the levels staged
+/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull, mm_engine_set_screen_split and
+ * mm_engine_set_screen_group apply to the levels staged
  * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
  * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
@@ -166,6 +167,13 @@ int  mm_engine_set_screen_cull(mm_engine* e, int on);
  * starts a tile of its own wherever that adds no tile (ceil(main / 32) + ceil((n - main) / 32) == ceil(n / 32)): fewer
  * tiles computed, bit-identical screened values.  on == 0: the points in order (the A/B switch). */
 int  mm_engine_set_screen_split(mm_engine* e, int on);
+/* The culled screen of 17 column tiles builds its tile bound and phase-1 masks once per GROUP of consecutive candidates
+ * of a pair, from circles that hold a tile under every rotation of the group, and hands the first candidate's phase-2
+ * tiles to the others: less bookkeeping per candidate for a few more tiles, bit-identical screened values whatever the
+ * angles are.  group == 0 (default): per pair the largest of 8, 4, 2 whose span, (group - 1) x the median step of the
+ * pair's list, is at most 3.5 degrees, and never more than a quarter of a work item; 1: off (the A/B switch); 2, 4, 8:
+ * forced, with work items of at least four groups.  Other values: MM_ERR_INVALID. */
+int  mm_engine_set_screen_group(mm_engine* e, int group);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
@@ -206,6 +214,15 @@ int  mm_screen_values(mm_engine* e, const double* rx, const double* ry, int nr, 
 int  mm_screen_values_split(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty,
                             int nt, int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles,
                             int flags, int cull, float* out_sq2, double* e2);
+/* The same with the group size of the culled screen given (mm_engine_set_screen_group's values; the two hooks above
+ * screen with group 1).  items (nullable, items_cap triples): the work items as (first candidate, candidates, group
+ * size), *n_items (nullable) their number: a wave takes the groups of its item in turn. */
+int  mm_screen_values_group(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty,
+                            int nt, int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles,
+                            int flags, int cull, int group, float* out_sq2, double* e2, int32_t* items, int items_cap,
+                            int* n_items);
+/* TEST HOOK (host only): the group size chosen for a candidate list (radians) when the switch is automatic. */
+int  mm_screen_group_auto(const double* angles, int n);
 /* TEST HOOK (host only): the culled screen's layout of a set of n points in two runs (main, n - main): out[j] = the point
  * in slot j for j < slots, laid out as asked (main == 0: in order).  Returns the split the engine takes for (n, main):
  * main where it adds no tile, else 0; < 0 on bad arguments. */
@@ -218,6 +235,11 @@ int  mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* 
 /* The same with either set laid out as two runs (ref_main / tgt_main as mm_tile_slot_map lays them out; 0: in order). */
 int  mm_tile_bound_probe_split(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt,
                                int ref_main, int tgt_main, int e, float c, float s, double e2, float* circles, float* thr);
+/* The same for a group of n rotations (cs: n pairs cos, sin): the column circles hold their tile under every rotation of
+ * the group, thr is below every screened squared distance of the tile pair under each of them.  n == 1: the hook above. */
+int  mm_tile_bound_probe_group(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt,
+                               int ref_main, int tgt_main, int e, const float* cs, int n, double e2, float* circles,
+                               float* thr);
 
 /* ---- the metric: hausdorff_distance (process_utils.rs:78-82) ------------------------ */
 /* f64-exact on the device; empty set on either side -> 0.0 (process_utils.rs:86-88). */

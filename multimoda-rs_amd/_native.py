@@ -32,6 +32,7 @@ EXPORTS = [
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
+    "mm_engine_set_screen_group", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -333,6 +334,14 @@ def lib():
     L.mm_screen_values_split.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, P, P]
     L.mm_tile_bound_probe_split.restype = I
     L.mm_tile_bound_probe_split.argtypes = [P, P, I, P, P, I, I, I, I, C.c_float, C.c_float, D, P, P]
+    L.mm_engine_set_screen_group.restype = I
+    L.mm_engine_set_screen_group.argtypes = [P, I]
+    L.mm_screen_values_group.restype = I
+    L.mm_screen_values_group.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, I, P, P, P, I, P]
+    L.mm_tile_bound_probe_group.restype = I
+    L.mm_tile_bound_probe_group.argtypes = [P, P, I, P, P, I, I, I, I, P, I, D, P, P]
+    L.mm_screen_group_auto.restype = I
+    L.mm_screen_group_auto.argtypes = [P, I]
     L.mm_tile_slot_map.restype = I
     L.mm_tile_slot_map.argtypes = [I, I, I, P]
     L.mm_parse_contour_table.restype = I64
@@ -969,6 +978,26 @@ class Engine:
         """Culled screen: a set of two runs (lumen ++ catheter) gets tiles per run where that adds no tile (default), or
         tiles of consecutive points."""
         check(lib().mm_engine_set_screen_split(self._h, int(on)), "mm_engine_set_screen_split")
+
+    def set_screen_group(self, group: int):
+        """Culled screen: consecutive candidates of a pair that share one tile bound and mask set.  0: chosen per pair from
+        its candidate list (default); 1: off; 2, 4, 8: forced."""
+        check(lib().mm_engine_set_screen_group(self._h, int(group)), "mm_engine_set_screen_group")
+
+    def screen_values_group(self, ref, tgt, angles, centre, group, cull=True, skip_zero=True, split=(0, 0)):
+        """TEST HOOK (``mm_screen_values_group``): ``screen_values`` with the group size given; returns the values, e2 and
+        the work items as rows (first candidate, candidates, group size)."""
+        ref = np.ascontiguousarray(ref, dtype=np.float64); tgt = np.ascontiguousarray(tgt, dtype=np.float64)
+        rx, ry = np.ascontiguousarray(ref[:, 0]), np.ascontiguousarray(ref[:, 1])
+        tx, ty = np.ascontiguousarray(tgt[:, 0]), np.ascontiguousarray(tgt[:, 1])
+        ang = np.ascontiguousarray(angles, dtype=np.float64)
+        out, e2 = np.zeros(len(ang), dtype=np.float32), C.c_double(0.0)
+        items, n_items = np.zeros((len(ang), 3), dtype=np.int32), C.c_int(0)
+        check(lib().mm_screen_values_group(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), int(split[0]),
+                                           int(split[1]), float(centre[0]), float(centre[1]), _ptr(ang), len(ang),
+                                           MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(cull)), int(group), _ptr(out),
+                                           C.byref(e2), _ptr(items), len(ang), C.byref(n_items)), "mm_screen_values_group")
+        return out, e2.value, items[:n_items.value].copy()
 
     def screen_tiles(self):
         """Tiles of the culled screen since the engine was created: (computed, what the full screen computes)."""

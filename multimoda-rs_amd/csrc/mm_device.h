@@ -46,7 +46,7 @@ struct SetSrc {
 
 // One workgroup's share: `cnt` consecutive candidates of one pair.
 struct WorkItem {
-    int32_t pair, a0, cnt, pad;
+    int32_t pair, a0, cnt, pad;   // pad: the bound kernels' candidate step; k_screen_mx_cull: candidates per group (0: 1)
 };
 
 static constexpr int kMaxNear = 8;  // near-tie slots per pair (MM_MAX_NEAR)
@@ -108,6 +108,7 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
                                  hipStream_t s);
 bool       mx_cull_takes(int nct, int multi, int a_cap);
+int        mx_cull_group_max(int nct);   // candidates per group (WorkItem::pad) the culled screen of nct column tiles takes
 hipError_t launch_screen_none(const BatchDev& b, int work_begin, int n_work, hipStream_t s);   // screened value 0 for every candidate
 void       mx_variant(int n_tgt, int* nct, int* multi);
 size_t     lds_bytes_mx(int nct, bool multi, int a_cap, int waves);

@@ -484,6 +484,34 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
         const int64_t per_wave = std::min<int64_t>(16, std::max<int64_t>(2, (2312 + tiles - 1) / tiles));
         return (int)std::max<int64_t>(apb, std::min<int64_t>(4 * per_wave, apb_fill));
     };
+    // The culled screen's groups (ScreenOptions::screen_group): per pair the candidates that share one tile bound.  A forced
+    // size asks for work items of four groups, one per wave; the automatic one follows the pair's list and never takes more
+    // than a quarter of the item the batch gives the pair, so that a small batch keeps a candidate per wave.
+    std::vector<int> pair_group((size_t)P, 1);
+    if (use_mx && opts.screen_cull && opts.screen_group != 1) {
+        int32_t seen_tab = -1, seen_n = -1; int seen_g = 1;
+        for (int p = 0; p < P; ++p) {
+            const PairScreen& c = screen[(size_t)p];
+            const PairDesc& d = host_pairs[p];
+            if (c.screen != Screen::Matrix || c.multi || d.n_ang < 2) continue;
+            const int gmax = mx_cull_group_max(c.nct);
+            if (gmax < 2) continue;
+            int g = opts.screen_group;
+            if (g == 0) {
+                if (d.tab_off != seen_tab || d.n_ang != seen_n) {
+                    seen_g = mm_tile_group_auto(host_tables.data() + d.tab_off, d.n_ang);
+                    seen_tab = d.tab_off; seen_n = d.n_ang;
+                }
+                g = seen_g;
+                while (g > 1 && 4 * g > apb_of(p)) g >>= 1;
+            }
+            pair_group[(size_t)p] = std::min(g, gmax);
+        }
+    }
+    auto apb_grouped = [&](int p) {
+        const int g = pair_group[(size_t)p];
+        return g > 1 ? std::max(apb_of(p), 4 * g) : apb_of(p);
+    };
     groups.clear();
     {
         // balanced chunks: ceil(n / apb) workgroups whose sizes differ by at most one (a 90-candidate
@@ -496,7 +524,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
         if (use_mx) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return screen[(size_t)x].key() < screen[(size_t)y].key(); });
         std::vector<int64_t> wstart((size_t)P + 1, 0);
         for (int q = 0; q < P; ++q) {
-            const int ap = apb_of(order[(size_t)q]);
+            const int ap = apb_grouped(order[(size_t)q]);
             wstart[(size_t)q + 1] = wstart[(size_t)q] + (host_pairs[order[(size_t)q]].n_ang + ap - 1) / ap;
         }
         if (wstart[(size_t)P] > INT32_MAX) return set_error(MM_ERR_TOO_LARGE, "too many work items");
@@ -511,7 +539,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
                 WorkItem* o = hw + wstart[(size_t)q];
                 for (int k = 0; k < nw; ++k) {
                     const int a0 = (int)((int64_t)d.n_ang * k / nw), a1 = (int)((int64_t)d.n_ang * (k + 1) / nw);
-                    o[k] = WorkItem{p, a0, a1 - a0, 0};
+                    o[k] = WorkItem{p, a0, a1 - a0, pair_group[(size_t)p] > 1 ? pair_group[(size_t)p] : 0};
                 }
             }
         });
@@ -1271,6 +1299,16 @@ int mm_engine_set_screen_split(mm_engine* h, int on)
     return MM_OK;
 }
 
+int mm_engine_set_screen_group(mm_engine* h, int group)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    if (group != 0 && group != 1 && group != 2 && group != 4 && group != 8)
+        return set_error(MM_ERR_INVALID, "mm_engine_set_screen_group: 0 (automatic), 1 (off), 2, 4 or 8");
+    e->screen_opts.screen_group = group;
+    return MM_OK;
+}
+
 int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
 {
     Engine* e = reinterpret_cast<Engine*>(h);
@@ -1439,6 +1477,19 @@ int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int
                            int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
                            int cull, float* out_sq2, double* e2)
 {
+    return mm_screen_values_group(h, rx, ry, nr, tx, ty, nt, ref_main, tgt_main, cx, cy, angles, n_angles, flags, cull, 1, out_sq2,
+                                  e2, nullptr, 0, nullptr);
+}
+
+// The same with the culled screen's group size given (1, 2, 4, 8; 0: the engine's choice for this list): the two hooks above
+// screen candidate by candidate (group 1).  items (nullable, room for items_cap triples): the plan's work items as
+// (first candidate, candidates, group size) -- what the kernel's waves split into groups; *n_items: their number.
+int mm_screen_values_group(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                           int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
+                           int cull, int group, float* out_sq2, double* e2, int32_t* items, int items_cap, int* n_items)
+{
+    if (group != 0 && group != 1 && group != 2 && group != 4 && group != 8)
+        return set_error(MM_ERR_INVALID, "mm_screen_values_group: group must be 0, 1, 2, 4 or 8");
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e || !rx || !ry || !tx || !ty || !angles || !out_sq2 || nr <= 0 || nt <= 0 || n_angles <= 0 || ref_main < 0 ||
         tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
@@ -1447,11 +1498,16 @@ int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int
     std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy, ref_main}, SetRef{tx, ty, nt, cx, cy, tgt_main}};
     std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
-    opts.bound_min_candidates = 0; opts.screen_cull = cull != 0;
+    opts.bound_min_candidates = 0; opts.screen_cull = cull != 0; opts.screen_group = group;
     Plan plan;
     int rc = plan.stage_sets(e, sets, true);
     if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_MATRIX, 0, INT32_MAX, false, nullptr, &opts);
     if (rc) return rc;
+    if (n_items) *n_items = plan.W;
+    for (int k = 0; items && k < plan.W && k < items_cap; ++k) {
+        const WorkItem& w = plan.host_work[(size_t)k];
+        items[3 * k] = w.a0; items[3 * k + 1] = w.cnt; items[3 * k + 2] = std::max(w.pad, 1);
+    }
     bool ok = plan.A == n_angles && !plan.groups.empty();
     for (const Plan::ScreenGroup& g : plan.groups)
         ok = ok && (g.screen == Screen::Matrix || g.screen == Screen::MatrixCull) && mx_cull_takes(g.nct, g.multi, g.a_cap);
@@ -1461,6 +1517,14 @@ int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int
     MM_HIP(hipStreamSynchronize(plan.stream));
     if (e2) *e2 = plan.host_pairs[0].e2;
     return MM_OK;
+}
+
+// TEST HOOK (host only): the group size the engine chooses for a candidate list in radians (mm_tile_group_auto), before
+// the cap a small batch's work items put on it.
+int mm_screen_group_auto(const double* angles, int n)
+{
+    if (!angles || n < 1) return set_error(MM_ERR_INVALID, "mm_screen_group_auto: bad arguments");
+    return mm_tile_group_auto(angles, n);
 }
 
 // TEST HOOK (host only, no device): the culled screen's tile bound (mm_tile_bound.h) for the f32 point sets (rx, ry) and
@@ -1486,6 +1550,16 @@ int mm_tile_bound_probe(const float* rx, const float* ry, int nr, const float* t
 int mm_tile_bound_probe_split(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int ref_main,
                               int tgt_main, int e, float c, float s, double e2, float* circles, float* thr)
 {
+    const float cs[2] = {c, s};
+    return mm_tile_bound_probe_group(rx, ry, nr, tx, ty, nt, ref_main, tgt_main, e, cs, 1, e2, circles, thr);
+}
+
+// The same for a GROUP of n rotations, cs = their (cos, sin) pairs: the column circles are the ones that hold the tile
+// under every rotation of the group (mm_tile_group_circle), thr the table the kernel builds once for the group.
+int mm_tile_bound_probe_group(const float* rx, const float* ry, int nr, const float* tx, const float* ty, int nt, int ref_main,
+                              int tgt_main, int e, const float* cs, int n, double e2, float* circles, float* thr)
+{
+    if (!cs || n < 1 || n > 64) return set_error(MM_ERR_INVALID, "mm_tile_bound_probe_group: a group is 1 .. 64 rotations");
     if (!rx || !ry || !tx || !ty || !circles || !thr || nr <= 0 || nt <= 0 || nr > 1 << 20 || nt > 1 << 20 || e < -126 || e > 126 ||
         ref_main < 0 || tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
         return set_error(MM_ERR_INVALID, "mm_tile_bound_probe: bad arguments");
@@ -1499,9 +1573,10 @@ int mm_tile_bound_probe_split(const float* rx, const float* ry, int nr, const fl
     }
     for (int j = 0; j < nct; ++j) {
         float* o = circles + 4 * (nrt + j);
-        float ux, uy;
-        mm_tile_circle(tx, ty, 32 * j, nt, S, &ux, &uy, o + 2, tgt_main);
-        o[0] = std::fma(ux, c, -(uy * s)); o[1] = std::fma(ux, s, uy * c); o[3] = 0.0f;
+        float ux, uy, ur;
+        mm_tile_circle(tx, ty, 32 * j, nt, S, &ux, &uy, &ur, tgt_main);
+        mm_tile_group_circle(ux, uy, ur, cs, n, o, o + 1, o + 2);
+        o[3] = 0.0f;
     }
     for (int i = 0; i < nrt; ++i)
         for (int j = 0; j < nct; ++j) {

@@ -36,6 +36,9 @@ struct ScreenOptions {
     bool screen_cull = true;                // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull
     bool screen_split = true;               // k_screen_mx_cull: a set of two runs (lumen ++ catheter) gives each run tiles of its
                                             // own where that adds no tile (PairDesc::ref_main / tgt_main)
+    int screen_group = 0;                   // k_screen_mx_cull: consecutive candidates that share one tile bound and mask set
+                                            // (WorkItem::pad).  0: chosen per pair from its list (mm_tile_group_auto), never
+                                            // more than a quarter of a work item; 1: off; 2 | 4 | 8: forced
 };
 
 // One device + one stream + grow-only staging buffers (pinned host, device) reused by the

@@ -1002,6 +1002,14 @@ int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 // (A positive f32 compares like its bits as an integer; a negative minimum -- rounding below 0 for coincident points --
 // is below every positive threshold in that order too.)  The mask of a row tile is wave-uniform (one candidate per
 // wave): one scalar loop over its set bits.
+// Groups (set-bit variant, WorkItem::pad = G > 1): a wave takes G consecutive candidates and builds thr and the phase-1 masks
+// once for them, from one circle per column tile that holds the tile under EVERY rotation of the group
+// (mm_tile_group_circle: centre of the middle rotation, the radius widened by the farthest of the others).  thr(I, J) is
+// then below every screened value of tile (I, J) for every candidate of the group, and the argument above holds candidate by
+// candidate: it asks for a valid lower bound and for a tile per row tile and column tile in phase 1, for nothing else --
+// not for rotations that are close, ordered or evenly spaced (far ones only cost tiles).  The group's first candidate runs
+// as described; the others take its phase-2 tiles into phase 1 (a superset there only lowers Umax and Vmax) and clear them
+// from their own phase-2 masks.  G = 1: the rule per candidate, from the same circle bit for bit.
 // Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
 // -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
 // no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
@@ -1046,7 +1054,8 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
 }
 
 // Section marks for tools/count_cull_isa.py: a comment line in the assembly, no instruction.  "<name>:<trips>" -- the
-// section's instructions run once per <trips> (1, nrt, rows2, half, tiles; "tile" is a computed tile's own body).
+// section's instructions run once per <trips> (1, nrt, rows2, half, tiles; group and ghalf: once, and once per two row tiles,
+// per GROUP of candidates; "tile" is a computed tile's own body).
 #define MXC_MARK(s) __asm__ volatile("; mxc:" s)
 #define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
 
@@ -1174,7 +1183,75 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
         }
         __syncthreads();
 
-        for (int k = wave; k < w.cnt; k += WAVES) {
+        // A wave takes runs of G consecutive candidates (group q = candidates [q G, (q + 1) G) of the item, wave w the groups w,
+        // w + 4, ...; G = WorkItem::pad, 1 | 2 | 4 | 8, chosen per pair at staging): the thresholds and the phase-1 masks are
+        // built once per group, and the group's first candidate hands its phase-2 masks on (see below).  G = 1 is the rule per
+        // candidate; the chain variant knows no other.
+        const int G = NCT >= MXC_SETBIT_MIN_NCT ? min(max(w.pad, 1), 8) : 1;
+        for (int k0 = wave * G; k0 < w.cnt; k0 += WAVES * G) {
+          const int k1 = min(k0 + G, w.cnt);
+          unsigned m1 = 0, carry = 0;
+          if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
+            // ---- thr(I, J) of every tile pair, once per GROUP: lane (h, J) takes column tile J (one circle that holds the
+            // tile under every rotation of the group, mm_tile_group_circle; a group of one: its centre rotated) against the
+            // row tiles 2 p + h, two row tiles per pass (the next pass's row circle already requested).  A pass's close tiles
+            // (thr <= 0) are one ballot: its two halves are the phase-1 masks of row tiles 2 p and 2 p + 1, kept by lanes
+            // 2 p and 2 p + 1.  Each lane keeps its column's nearest row tile on the way (no second sweep over the table).
+            MXC_MARK("thr:group");
+            const int hw = lane >> 5;
+            const bool jok = l32 < NCT;
+            float4 cc = s_circ[jok ? l32 : NCT - 1];
+            float cbx, cby;
+            mm_tile_group_circle(cc.x, cc.y, cc.z, s_cs + 2 * k0, k1 - k0, &cbx, &cby, &cc.z);
+            float ckey = __builtin_inff();                               // the column's smallest thr so far, -1 once a tile is close
+            int cbi = 0;
+            float4 rc = s_circ[NCT + (hw < nrt ? hw : nrt - 1)];
+            for (int p = 0; 2 * p < nrt; ++p) {
+                MXC_MARK("thr_pass:ghalf");
+                const int I = 2 * p + hw;
+                const float4 rn = s_circ[NCT + (I + 2 < nrt ? I + 2 : nrt - 1)];
+                const bool ok = jok && I < nrt;
+                const float t = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, cbx, cby, cc.z), e2s);
+                if (ok) s_th[I * 32 + l32] = t;
+                const bool close = ok && !(t > 0.0f);
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(close);
+                m1 = lane == 2 * p ? (unsigned)bal : lane == 2 * p + 1 ? (unsigned)(bal >> 32) : m1;
+                if (close) ckey = -1.0f;
+                else if (ok && t < ckey) { ckey = t; cbi = I; }         // (ascending I, strict: the smallest I of equal thr)
+                rc = rn;
+            }
+            MXC_MARK("m1:group");
+            __asm__ volatile("" ::: "memory");
+            // lane I (< nrt) without a close tile: the tile with the smallest thr of its row
+            if (lane < nrt && !m1) {
+                const float4* q = reinterpret_cast<const float4*>(s_th + lane * 32);
+                float th[NT4 * 4];
+#pragma unroll
+                for (int u = 0; u < NT4; ++u) { const float4 w4 = q[u]; th[4 * u] = w4.x; th[4 * u + 1] = w4.y; th[4 * u + 2] = w4.z; th[4 * u + 3] = w4.w; }
+                float best = __builtin_inff();
+                int bj = 0;
+#pragma unroll
+                for (int J = 0; J < NCT; ++J)
+                    if (th[J] < best) { best = th[J]; bj = J; }
+                m1 = 1u << bj;
+            }
+            // column tile J without a close tile: its nearest row tile.  The halves (even and odd row tiles) meet; both
+            // halves of lane pair J then hold the same answer, the lower half's lanes report it
+            int lone_i = -1;
+            {
+                const auto kk = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(ckey), (unsigned)__float_as_int(ckey), false, false);
+                const auto ii = __builtin_amdgcn_permlane32_swap((unsigned)cbi, (unsigned)cbi, false, false);
+                const float key0 = __int_as_float((int)kk[0]), key1 = __int_as_float((int)kk[1]);
+                const int i0 = (int)ii[0], i1 = (int)ii[1];
+                if (lane < NCT && key0 > 0.0f && key1 > 0.0f) lone_i = key1 < key0 ? i1 : key1 == key0 ? min(i0, i1) : i0;
+            }
+            for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
+                const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
+                if (lane == I) m1 |= 1u << L;
+            }
+          }
+          (void)m1; (void)carry;
+          for (int k = k0; k < k1; ++k) {
             const float c = s_cs[2 * k], s = s_cs[2 * k + 1];
             const int a = s_ci[k];
             if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
@@ -1198,72 +1275,18 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 }
                 __asm__ volatile("" ::: "memory");
 
-                // ---- thr(I, J) of every tile pair: lane (h, J) takes column tile J (its centre rotated once) against the row
-                // tiles 2 p + h, two row tiles per pass (the next pass's row circle already requested).  A pass's close tiles
-                // (thr <= 0) are one ballot: its two halves are the phase-1 masks of row tiles 2 p and 2 p + 1, kept by lanes
-                // 2 p and 2 p + 1.  Each lane keeps its column's nearest row tile on the way (no second sweep over the table).
-                MXC_MARK("thr:1");
-                const int hw = lane >> 5;
-                const bool jok = l32 < NCT;
-                const float4 cc = s_circ[jok ? l32 : NCT - 1];
-                const float cbx = __builtin_fmaf(cc.x, c, -(cc.y * s)), cby = __builtin_fmaf(cc.x, s, cc.y * c);
-                unsigned m1 = 0;
-                float ckey = __builtin_inff();                               // the column's smallest thr so far, -1 once a tile is close
-                int cbi = 0;
-                float4 rc = s_circ[NCT + (hw < nrt ? hw : nrt - 1)];
-                for (int p = 0; 2 * p < nrt; ++p) {
-                    MXC_MARK("thr_pass:half");
-                    const int I = 2 * p + hw;
-                    const float4 rn = s_circ[NCT + (I + 2 < nrt ? I + 2 : nrt - 1)];
-                    const bool ok = jok && I < nrt;
-                    const float t = mm_tile_threshold(mm_tile_gap(rc.x, rc.y, rc.z, cbx, cby, cc.z), e2s);
-                    if (ok) s_th[I * 32 + l32] = t;
-                    const bool close = ok && !(t > 0.0f);
-                    const unsigned long long bal = __builtin_amdgcn_ballot_w64(close);
-                    m1 = lane == 2 * p ? (unsigned)bal : lane == 2 * p + 1 ? (unsigned)(bal >> 32) : m1;
-                    if (close) ckey = -1.0f;
-                    else if (ok && t < ckey) { ckey = t; cbi = I; }         // (ascending I, strict: the smallest I of equal thr)
-                    rc = rn;
-                }
-                MXC_MARK("m1:1");
-                __asm__ volatile("" ::: "memory");
-                // lane I (< nrt) without a close tile: the tile with the smallest thr of its row
-                if (lane < nrt && !m1) {
-                    const float4* q = reinterpret_cast<const float4*>(s_th + lane * 32);
-                    float th[NT4 * 4];
-#pragma unroll
-                    for (int u = 0; u < NT4; ++u) { const float4 w4 = q[u]; th[4 * u] = w4.x; th[4 * u + 1] = w4.y; th[4 * u + 2] = w4.z; th[4 * u + 3] = w4.w; }
-                    float best = __builtin_inff();
-                    int bj = 0;
-#pragma unroll
-                    for (int J = 0; J < NCT; ++J)
-                        if (th[J] < best) { best = th[J]; bj = J; }
-                    m1 = 1u << bj;
-                }
-                // column tile J without a close tile: its nearest row tile.  The halves (even and odd row tiles) meet; both
-                // halves of lane pair J then hold the same answer, the lower half's lanes report it
-                int lone_i = -1;
-                {
-                    const auto kk = __builtin_amdgcn_permlane32_swap((unsigned)__float_as_int(ckey), (unsigned)__float_as_int(ckey), false, false);
-                    const auto ii = __builtin_amdgcn_permlane32_swap((unsigned)cbi, (unsigned)cbi, false, false);
-                    const float k0 = __int_as_float((int)kk[0]), k1 = __int_as_float((int)kk[1]);
-                    const int i0 = (int)ii[0], i1 = (int)ii[1];
-                    if (lane < NCT && k0 > 0.0f && k1 > 0.0f) lone_i = k1 < k0 ? i1 : k1 == k0 ? min(i0, i1) : i0;
-                }
-                for (unsigned long long lone = __builtin_amdgcn_ballot_w64(lone_i >= 0); lone; lone &= lone - 1) {
-                    const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
-                    if (lane == I) m1 |= 1u << L;
-                }
-
                 // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
+                // A follower of the group runs the leader's phase-2 tiles in phase 1 (neighbouring rotations leave the same
+                // tiles): a superset in phase 1 only lowers Umax and Vmax, so the skip rule below stays valid.
                 MXC_MARK("p1_init:1");
+                const unsigned p1m = m1 | carry;
                 regs_t cm;
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
                 h8v af = s_a[lane];
                 for (int I = 0; I < nrt; ++I) {
                     MXC_MARK("p1_row:nrt");
-                    const unsigned mask = __builtin_amdgcn_readlane(m1, I);
+                    const unsigned mask = __builtin_amdgcn_readlane(p1m, I);
                     const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
                     int rmin = 0x7f800000;
                     mxc_tiles<NCT, 1>(mask, af, blo, bhi, cm, rmin);
@@ -1312,9 +1335,10 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         const int lim = max(umax, vm[J]);
                         if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
                     }
-                    m2 &= ~m1;
+                    m2 &= ~p1m;
                     if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
                 }
+                if (k == k0) carry = m2;
 
                 // ---- phase 2: only the row tiles with tiles left ----
                 for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
@@ -1471,6 +1495,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
                 MXC_MARK("end:0");
             }
+          }
         }
     }
     if (tiles_done && lane == 0 && done) atomicAdd(tiles_done, done);
@@ -1492,6 +1517,8 @@ bool mx_cull_takes(int nct, int multi, int a_cap)
 {
     return !multi && nct >= MM_SCREEN_MX_NCT_MIN && nct <= MX_TMAX && a_cap >= 1 && a_cap <= MXC_ROW_TILES_MAX;
 }
+
+int mx_cull_group_max(int nct) { return nct >= MXC_SETBIT_MIN_NCT && nct <= MX_TMAX ? 8 : 1; }
 
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
                                  hipStream_t s)

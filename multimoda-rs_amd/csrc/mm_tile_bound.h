@@ -6,7 +6,9 @@
 // Units are the screen's scaled units (x = 2^e * coordinate, every point of the pair within 512 of the rotation centre:
 // every coordinate, centre and radius below 2^10 in magnitude, every distance below 2^11).
 #pragma once
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define MM_TB_HD __host__ __device__
@@ -69,6 +71,47 @@ MM_TB_HD inline void mm_tile_circle(const float* px, const float* py, int base, 
     }
     *cx = mx; *cy = my;
     *r = mm_tb_sqrt(m) * 1.000003814697265625f + 0.0009765625f;       // (1 + 2^-18), 2^-10
+}
+
+// One circle for a column tile under EVERY rotation of a group: (ux, uy, r) is the tile's unrotated circle, cs the group's
+// n >= 1 rotations as (cos, sin) pairs of f32, the values the columns are rotated by.  Centre: the tile's centre rotated
+// (in f32, the fused form the kernel rotates by) by the middle rotation, cs[n / 2].  Radius: r plus the largest distance from
+// there to the centre under any rotation of the group, that distance rounded UP as mm_tile_circle rounds a radius (its at
+// most 5 relative roundings below the factor 1 + 2^-18; 2^-10 covers the underflow of the squares and the two additions
+// here, 2^-13 each at magnitudes below 2^12).  A point of the tile under rotation g lies within r + 2^-11 of the centre
+// rotated by g (mm_tile_gap), so within the returned radius + 2^-11 of the returned centre: mm_tile_gap of this circle is
+// a lower bound for every rotation of the group.  Nothing is assumed of the rotations (far apart, unordered, repeated: the
+// circle only grows; its radius stays below 2^12, which mm_tile_gap's slack covers).  n == 1: the circle mm_tile_gap
+// takes today, bit for bit.
+MM_TB_HD inline void mm_tile_group_circle(float ux, float uy, float r, const float* cs, int n, float* cx, float* cy, float* rg)
+{
+    const float cm = cs[2 * (n >> 1)], sm = cs[2 * (n >> 1) + 1];
+    const float mx = fmaf(ux, cm, -(uy * sm)), my = fmaf(ux, sm, uy * cm);
+    float m = 0.0f;
+    for (int g = 0; g < n; ++g) {
+        const float c = cs[2 * g], s = cs[2 * g + 1];
+        const float dx = fmaf(ux, c, -(uy * s)) - mx, dy = fmaf(ux, s, uy * c) - my;
+        m = fmaxf(m, fmaf(dx, dx, dy * dy));
+    }
+    *cx = mx; *cy = my;
+    *rg = n > 1 ? r + (mm_tb_sqrt(m) * 1.000003814697265625f + 0.0009765625f) : r;   // (1 + 2^-18), 2^-10
+}
+
+// The group size the engine takes for a candidate list (radians), ScreenOptions::screen_group == 0: the largest G of 8, 4,
+// 2 whose span (G - 1) * step is at most 3.5 degrees, step the median of the absolute differences of neighbours; else 1.
+// A tile is an arc of some 22 degrees: a group that spans a sixth of it widens the circles by little.  The median ignores
+// a jump (two concatenated ranges) and needs no order; a wrong guess costs tiles, never a value (mm_tile_group_circle).
+inline int mm_tile_group_auto(const double* angles, int n)
+{
+    if (n < 2) return 1;
+    std::vector<double> d((size_t)n - 1);
+    for (int i = 0; i + 1 < n; ++i) d[(size_t)i] = std::fabs(angles[i + 1] - angles[i]);
+    std::nth_element(d.begin(), d.begin() + (n - 1) / 2, d.end());
+    const double step = d[(size_t)(n - 1) / 2] * 57.29577951308232;
+    if (!(step == step)) return 1;
+    for (int G = 8; G >= 2; G >>= 1)
+        if ((G - 1) * step <= 3.5 * (1.0 + 1e-9)) return G;       // (a list of 0.5-degree steps in radians: 3.5 to rounding)
+    return 1;
 }
 
 // Lower bound of the distance between a point of circle (ax, ay, ar) and a point of circle (bx, by, br), the second circle's

@@ -3,7 +3,7 @@
 
     hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -Imultimoda-rs_amd/csrc \\
           --cuda-device-only -S multimoda-rs_amd/csrc/mm_kernels.hip -o mm_kernels.s
-    python tools/count_cull_isa.py mm_kernels.s --nct 17 --nrt 17 --tiles 60
+    python tools/count_cull_isa.py mm_kernels.s --nct 17 --nrt 17 --tiles 60 --group 8
 
 The kernel's candidate loop carries section marks, comment lines `; mxc:<name>:<trips>` that emit no instruction.  Every
 instruction line after a mark belongs to that section, in the TEXT order of the assembly (the compiler may place a block
@@ -13,6 +13,7 @@ how often the section runs per candidate:
     1        once                       nrt      once per row tile            half     once per two row tiles
     rows2    once per row tile that has tiles left in phase 2 (--rows2, default nrt: the upper bound)
     pairs64  once per 64 tile pairs     tiles    once per computed tile (summed over the copies, divided by their number)
+    group    once per group of --group candidates (1 / G per candidate)      ghalf    `half`, per group
     0        not in the candidate loop
 
 and a section named `tile` is a computed tile's own body (its copies are averaged; every v_mfma counts to it).  A section
@@ -103,15 +104,16 @@ def sections(body):
     return secs
 
 
-def report(nct, body, inf, nrt, tiles, rows2, out):
+def report(nct, body, inf, nrt, tiles, rows2, out, group=1):
     secs = sections(body)
     copies = max(1, secs["tile"]["entries"]) if "tile" in secs else 1
     trips = {"0": 0.0, "1": 1.0, "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
-             "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles / copies, "tile": tiles / copies}
+             "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles / copies, "tile": tiles / copies,
+             "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group}
     out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (
         nct, info(inf, "NumVgprs"), info(inf, "NumAgprs"), info(inf, "ScratchSize"), info(inf, "Occupancy")))
-    out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g; tile bodies in the code: %d\n" % (
-        nrt, nct, tiles, rows2, copies))
+    out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g, candidates/group %d; tile bodies in the code: %d\n" % (
+        nrt, nct, tiles, rows2, group, copies))
     out.write("  %-10s %-8s %6s %6s %6s %6s %6s %6s %7s %9s\n" % ("section", "trips", "mfma", "valu", "salu", "lds", "vmem",
                                                                   "other", "static", "executed"))
     tot_tile = tot_rest = 0.0
@@ -139,7 +141,10 @@ def main(argv=None):
     ap.add_argument("--nrt", type=int, default=17, help="row tiles of the pair")
     ap.add_argument("--tiles", type=float, default=60, help="tiles computed per candidate")
     ap.add_argument("--rows2", type=float, default=None, help="row tiles with tiles left in phase 2 (default: nrt)")
+    ap.add_argument("--group", type=int, default=1, help="candidates per group: the sections marked group / ghalf run once per group")
     a = ap.parse_args(argv)
+    if a.group < 1:
+        raise SystemExit("--group must be at least 1")
     with open(a.asm) as f:
         ks = kernels(f.read())
     if not ks:
@@ -148,7 +153,7 @@ def main(argv=None):
         if a.nct and nct != a.nct:
             continue
         body, inf = ks[nct]
-        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout)
+        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group)
 
 
 if __name__ == "__main__":

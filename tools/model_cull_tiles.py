@@ -15,7 +15,14 @@ Layouts (--layout):
                   with its own last point (mm_tile_slot_point), taken where it adds no tile (mm_tile_split_main)
     both          the two side by side (default)
 
+Groups (--group G): G consecutive candidates share one threshold table and one phase-1 mask, built from circles that hold
+a column tile under every rotation of the group (mm_tile_group_circle: the middle rotation's centre, the radius widened by
+the farthest of the others), and the group's first candidate hands its phase-2 tiles to the others, which run them in
+phase 1 (--no-carry prices the shared thresholds alone).  --runs R prices R runs of G candidates spread over the list
+instead of all of it.
+
     python tools/model_cull_tiles.py --frames 12 --points 501 --pairs 1 2 3 4 --rotations 91
+    python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --runs 15
 """
 import argparse
 import os
@@ -63,10 +70,23 @@ def circles(p, S):
     return c[:, 0], c[:, 1], r.astype(F)
 
 
-def thresholds(rc, cc, c, s, e2s):
-    """thr[nrt, nct] (mm_tile_gap, mm_tile_threshold); the column centres rotated by the f32 (c, s)."""
-    bx = cc[0] * c - cc[1] * s
-    by = cc[0] * s + cc[1] * c
+def group_circles(cc, cs):
+    """mm_tile_group_circle of every column tile for the rotations cs[n, 2] (f32 cos, sin): (cx, cy, r) f32, centres rotated."""
+    n = len(cs)
+    bx = cc[0][None, :] * cs[:, 0:1] - cc[1][None, :] * cs[:, 1:2]
+    by = cc[0][None, :] * cs[:, 1:2] + cc[1][None, :] * cs[:, 0:1]
+    mx, my = bx[n // 2], by[n // 2]
+    if n == 1:
+        return mx, my, cc[2]
+    dx, dy = bx - mx[None, :], by - my[None, :]
+    m = (dx * dx + dy * dy).max(axis=0)
+    return mx, my, (cc[2] + (np.sqrt(m) * F(1.000003814697265625) + F(0.0009765625))).astype(F)
+
+
+def thresholds(rc, cc, c, s, e2s, rotated=False):
+    """thr[nrt, nct] (mm_tile_gap, mm_tile_threshold); the column centres rotated by the f32 (c, s), or taken as they are."""
+    bx = cc[0] if rotated else cc[0] * c - cc[1] * s
+    by = cc[1] if rotated else cc[0] * s + cc[1] * c
     dx, dy = rc[0][:, None] - bx[None, :], rc[1][:, None] - by[None, :]
     d = np.sqrt(dx * dx + dy * dy)
     gap = d * F(0.999996185302734375) - (rc[2][:, None] + cc[2][None, :]) - F(0.0078125)
@@ -84,9 +104,11 @@ def phase1(thr):
     return m1
 
 
-def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0):
+def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0, group=1, carry=True):
     """(phase-1 tiles, phase-2 tiles) per candidate and row tile, int arrays [len(angles), nrt], for sets around (0, 0)
-    laid out as asked (ref_main / tgt_main as the engine would take them: pass them through split_main first)."""
+    laid out as asked (ref_main / tgt_main as the engine would take them: pass them through split_main first).  group > 1:
+    the candidates [q group, (q + 1) group) of `angles` share thresholds and phase-1 mask, and with `carry` the first one's
+    phase-2 tiles are phase-1 tiles of the others."""
     e, e2 = scale_and_e2(ref, tgt)
     S = 2.0 ** e
     nrt, nct = (len(ref) + 31) // 32, (len(tgt) + 31) // 32
@@ -99,10 +121,15 @@ def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0):
     b0 = S * t32.astype(np.float64)
     p1 = np.zeros((len(angles), nrt), dtype=np.int64)
     p2 = np.zeros((len(angles), nrt), dtype=np.int64)
+    cs = np.stack([np.cos(angles).astype(F), np.sin(angles).astype(F)], axis=1)
+    lead = None
     for k, ang in enumerate(angles):
-        c, s = F(np.cos(ang)), F(np.sin(ang))
-        thr = thresholds(rc, cc, c, s, e2s)
-        m1 = phase1(thr)
+        c, s = cs[k]
+        if k % group == 0:
+            thr = thresholds(rc, group_circles(cc, cs[k:k + group]), c, s, e2s, rotated=True)
+            m1g = phase1(thr)
+            lead = None
+        m1 = m1g | lead if lead is not None and carry else m1g
         cd, sd = np.float64(c), np.float64(s)
         b = np.stack([b0[:, 0] * cd - b0[:, 1] * sd, b0[:, 0] * sd + b0[:, 1] * cd], axis=1)
         d2 = ((a[:, None, :] - b[None, :, :]) ** 2).sum(axis=2)
@@ -110,6 +137,8 @@ def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0):
         u = big.min(axis=1).reshape(nrt, 32).max(axis=1)
         v = big.min(axis=0).reshape(nct, 32).max(axis=1)
         m2 = ~m1 & ~((thr > 0) & (thr >= np.maximum(u[:, None], v[None, :])))
+        if k % group == 0:
+            lead = m2
         p1[k], p2[k] = m1.sum(axis=1), m2.sum(axis=1)
     return p1, p2
 
@@ -140,25 +169,32 @@ def main():
     ap.add_argument("--pairs", type=int, nargs="+", default=[1, 2, 3, 4], help="frame pairs (i - 1, i)")
     ap.add_argument("--rotations", type=int, default=91, help="candidates over +-180 degrees")
     ap.add_argument("--layout", choices=("consecutive", "split", "both"), default="both")
+    ap.add_argument("--group", type=int, default=1, help="candidates that share thresholds and phase-1 mask")
+    ap.add_argument("--no-carry", action="store_true", help="the first candidate's phase-2 tiles are not handed on")
+    ap.add_argument("--runs", type=int, default=0, help="price this many runs of --group candidates spread over the list (0: all)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from multimoda_rs_amd.synth import synthetic_pullback
     sets = search_sets(synthetic_pullback(a.frames, a.points), a.points)
     angles = np.radians(np.linspace(-180.0, 180.0, a.rotations))
+    if a.runs > 0:
+        starts = np.linspace(0, max(0, len(angles) - a.group), a.runs).astype(np.int64)
+        angles = np.concatenate([angles[i:i + a.group] for i in starts])
     layouts = ("consecutive", "split") if a.layout == "both" else (a.layout,)
-    print("layout        pair  tiles/candidate  phase 1   per row tile (phase 1 + 2)")
+    print("layout        pair  tiles/candidate  phase 1   rows2   per row tile (phase 1 + 2)")
     for lay in layouts:
-        tot, tot1, rows = [], [], []
+        tot, tot1, rows, rows2 = [], [], [], []
         for i in a.pairs:
             (ref, rm), (tgt, tm) = sets[i - 1], sets[i]
             if lay == "consecutive":
                 rm = tm = 0
-            p1, p2 = count_tiles(ref, tgt, angles, split_main(len(ref), rm), split_main(len(tgt), tm))
+            p1, p2 = count_tiles(ref, tgt, angles, split_main(len(ref), rm), split_main(len(tgt), tm), a.group, not a.no_carry)
             per_row = (p1 + p2).mean(axis=0)
             tot.append(per_row.sum()); tot1.append(p1.sum(axis=1).mean()); rows.append(per_row)
-            print("%-12s  %4d  %15.1f  %7.1f   %s" % (lay, i, tot[-1], tot1[-1], " ".join("%.1f" % x for x in per_row)))
-        print("%-12s  mean  %15.1f  %7.1f   %s" % (lay, np.mean(tot), np.mean(tot1),
-                                                   " ".join("%.1f" % x for x in np.mean(rows, axis=0))))
+            rows2.append((p2 > 0).sum(axis=1).mean())
+            print("%-12s  %4d  %15.1f  %7.1f  %6.1f   %s" % (lay, i, tot[-1], tot1[-1], rows2[-1], " ".join("%.1f" % x for x in per_row)))
+        print("%-12s  mean  %15.1f  %7.1f  %6.1f   %s" % (lay, np.mean(tot), np.mean(tot1), np.mean(rows2),
+                                                          " ".join("%.1f" % x for x in np.mean(rows, axis=0))))
 
 
 if __name__ == "__main__":
