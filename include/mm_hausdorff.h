@@ -177,6 +177,12 @@ int  mm_engine_set_screen_group(mm_engine* e, int group);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
+/* The culled screen's groups since the engine was created: out[1] the candidates that ran as followers of a group (all but
+ * a group's first), out[0] those of them that left after phase 1 on the group test -- no met row minimum of row tile I above
+ * Tr_I and no met column minimum of column tile J above Tc_J, the smallest thr of the row tile / column tile over the
+ * tiles outside the followers' phase 1: exactly the followers whose phase-2 masks are all empty.  They skip the column
+ * maxima, the masks and phase 2; values and tile counts are what the general path gives. */
+int  mm_engine_screen_early(mm_engine* e, int64_t out[2]);
 
 /* TEST HOOK (nothing in the product calls it): the lower bound MM_PRECISION_F32_BOUNDED's bound kernels give every
  * candidate of one search -- out_lb2[i] <= (exact cost of candidate i)^2 up to *e2 (error bound of the kernel's squared

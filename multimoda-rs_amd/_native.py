@@ -30,7 +30,7 @@ EXPORTS = [
     "mm_engine_create", "mm_engine_destroy", "mm_engine_synchronize", "mm_engine_stream", "mm_engine_wait_search",
     "mm_engine_profile", "mm_engine_profile_read", "mm_engine_profile_launches", "mm_engine_bound_stats", "mm_engine_first_min_stats", "mm_engine_screen_stats", "mm_engine_set_bound_matrix", "mm_lower_bounds", "mm_pick_minima",
     "mm_bound_state", "mm_hausdorff_first_min_state",
-    "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_screen_values", "mm_tile_bound_probe",
+    "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_engine_screen_early", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
     "mm_engine_set_screen_group", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto",
     "mm_engine_set_bound_min_candidates",
@@ -324,6 +324,8 @@ def lib():
     L.mm_engine_set_screen_cull.argtypes = [P, I]
     L.mm_engine_screen_tiles.restype = I
     L.mm_engine_screen_tiles.argtypes = [P, P]
+    L.mm_engine_screen_early.restype = I
+    L.mm_engine_screen_early.argtypes = [P, P]
     L.mm_screen_values.restype = I
     L.mm_screen_values.argtypes = [P, P, P, I, P, P, I, D, D, P, I, I, I, P, P]
     L.mm_tile_bound_probe.restype = I
@@ -1003,6 +1005,13 @@ class Engine:
         """Tiles of the culled screen since the engine was created: (computed, what the full screen computes)."""
         out = np.zeros(2, dtype=np.int64)
         check(lib().mm_engine_screen_tiles(self._h, _ptr(out)), "mm_engine_screen_tiles")
+        return int(out[0]), int(out[1])
+
+    def screen_early(self):
+        """Group followers of the culled screen since the engine was created: (left after phase 1 on the group test, all
+        followers)."""
+        out = np.zeros(2, dtype=np.int64)
+        check(lib().mm_engine_screen_early(self._h, _ptr(out)), "mm_engine_screen_early")
         return int(out[0]), int(out[1])
 
     def screen_values(self, ref, tgt, angles, centre, cull=True, skip_zero=True, split=None):

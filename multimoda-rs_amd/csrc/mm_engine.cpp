@@ -1125,7 +1125,7 @@ int mm_engine_create(int device, void* stream, mm_engine** out)
         if (e2 != hipSuccess) { (void)hipStreamDestroy(en->stream); delete en; return hip_error(e2, "hipStreamCreateWithPriority"); }
         en->own_aux = true;
     }
-    if (hipMalloc((void**)&en->dev_tiles, 8) != hipSuccess || hipMemset(en->dev_tiles, 0, 8) != hipSuccess) {
+    if (hipMalloc((void**)&en->dev_tiles, 24) != hipSuccess || hipMemset(en->dev_tiles, 0, 24) != hipSuccess) {
         mm_engine_destroy(reinterpret_cast<mm_engine*>(en));
         return set_error(MM_ERR_HIP, "hipMalloc (tile counter)");
     }
@@ -1319,6 +1319,19 @@ int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
     if (e->dev_tiles) MM_HIP(hipMemcpy(&d, e->dev_tiles, 8, hipMemcpyDeviceToHost));
     out[0] = (int64_t)d;
     out[1] = e->cull_tiles_full.load();
+    return MM_OK;
+}
+
+int mm_engine_screen_early(mm_engine* h, int64_t out[2])
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e || !out) return set_error(MM_ERR_INVALID, "engine or out == NULL");
+    MM_HIP(hipSetDevice(e->device));
+    if (int src = e->sync_all()) return src;
+    unsigned long long d[2] = {0, 0};
+    if (e->dev_tiles) MM_HIP(hipMemcpy(d, e->dev_tiles + 1, 16, hipMemcpyDeviceToHost));
+    out[0] = (int64_t)d[0];
+    out[1] = (int64_t)d[1];
     return MM_OK;
 }
 

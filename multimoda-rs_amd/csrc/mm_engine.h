@@ -102,7 +102,8 @@ struct Engine {
     std::atomic<int64_t> screened[5] = {};
     unsigned long long* dev_stats = nullptr;
     // k_screen_mx_cull's tile counts (mm_engine_screen_tiles): computed (device counter) and what the full kernel computes
-    // for the same candidates
+    // for the same candidates; behind the device counter two more words (mm_engine_screen_early): the group followers that
+    // left after phase 1, and all followers
     unsigned long long* dev_tiles = nullptr;
     std::atomic<int64_t> cull_tiles_full{0};
     int profile_begin(hipStream_t s);

@@ -1010,6 +1010,16 @@ int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 // not for rotations that are close, ordered or evenly spaced (far ones only cost tiles).  The group's first candidate runs
 // as described; the others take its phase-2 tiles into phase 1 (a superset there only lowers Umax and Vmax) and clear them
 // from their own phase-2 masks.  G = 1: the rule per candidate, from the same circle bit for bit.
+// A follower's phase 2 is then almost always empty, and it finds that out without the column maxima and the masks.  Its
+// phase-1 mask p1m = m1 | carry and thr are the group's, so once per group, behind the leader: Tr_I, the smallest thr(I, J)
+// of row tile I over the tiles outside p1m, and Tc_J, the same down column tile J (0x7f800000 where there is none; each
+// such thr is positive).  The rule above puts a tile outside p1m into m2 unless thr >= max(Umax_I, Vmax_J): m2 is empty for
+// every row tile exactly when Umax_I <= Tr_I for every I and Vmax_J <= Tc_J for every J, that is when no lane's met row
+// minimum of row tile I lies above Tr_I and no lane's met column minimum of column tile J above Tc_J -- compares against
+// wave-uniform values, no cross-lane maximum, no LDS.  A follower that passes leaves after phase 1 with the maximum of its
+// met minima, which is what the general path returns with empty masks (every row tile final with Umax_I); one that does
+// not falls into the general path as it stands.  tiles_done[1], [2] count the followers that left early and all followers
+// (mm_engine_screen_early).
 // Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
 // -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
 // no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
@@ -1054,8 +1064,10 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
 }
 
 // Section marks for tools/count_cull_isa.py: a comment line in the assembly, no instruction.  "<name>:<trips>" -- the
-// section's instructions run once per <trips> (1, nrt, rows2, half, tiles; group and ghalf: once, and once per two row tiles,
-// per GROUP of candidates; "tile" is a computed tile's own body).
+// section's instructions run once per <trips> (1, nrt, rows2, half, tiles; group and ghalf: once and once per two row tiles,
+// per GROUP of candidates; fgroup and fgnrt: once and once per row tile, per group that has followers; lrows and frows: once
+// per row tile of a leader and of a follower; fol, early, late: once per follower, per follower that leaves after phase 1,
+// per candidate that does not; "tile" is a computed tile's own body).
 #define MXC_MARK(s) __asm__ volatile("; mxc:" s)
 #define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
 
@@ -1067,6 +1079,7 @@ typedef int mxc_i4 __attribute__((ext_vector_type(4)));
 // the tiles of `mask` for one row tile (A fragment af): their column minima into cm, their row minima into rmin -- a loop
 // over the SET bits of the wave-uniform mask (its cost is per computed tile, not per column tile); per tile D = A.B and
 // D' = B.A, both MFMAs in flight before the minima.  (blo, bhi): the two dwords of every column tile's B fragment.
+// PH: 1 phase 1 of a leader, 3 of a follower, 2 phase 2 (the section the count charges what follows the tiles to).
 template <int NCT, int PH>
 static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, const typename mxc_regs<NCT>::type& blo,
                                                  const typename mxc_regs<NCT>::type& bhi, typename mxc_regs<NCT>::type& cm, int& rmin)
@@ -1089,7 +1102,9 @@ static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, c
         MXC_MARK_V("tloop:tiles", c1);
         cm[t] = c1;
     }
-    if constexpr (PH == 1) MXC_MARK_V("p1_row:nrt", rmin); else MXC_MARK_V("p2_row:rows2", rmin);
+    if constexpr (PH == 1) MXC_MARK_V("p1_row:lrows", rmin);
+    else if constexpr (PH == 3) MXC_MARK_V("p1f_row:frows", rmin);
+    else MXC_MARK_V("p2_row:rows2", rmin);
 }
 
 // the same by a bit test and a branch per column tile in front of NCT unrolled bodies (A fragment af): their column minima into cm, their row minima into rmin -- per tile
@@ -1127,7 +1142,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                  const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
                  const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done)
 {
-    constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128, VM = 40, NT4 = (NCT + 3) / 4;
+    constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128, VM = 40, NT4 = (NCT + 3) / 4, NP = (NCT + 1) / 2;
     typedef typename mxc_regs<NCT>::type regs_t;
     extern __shared__ __align__(16) unsigned char smem[];
     h8v* s_a = reinterpret_cast<h8v*>(smem);                          // [a_cap][64] row fragments of the pair (all waves)
@@ -1146,6 +1161,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
     // norm half, written once per work item, is not touched): [NCT][VS] ints, 32 used per row
     int* s_v = reinterpret_cast<int*>(s_b);
     unsigned long long done = 0;
+    unsigned n_foll = 0, n_early = 0;        // the wave's followers, and those of them that left after phase 1 (tiles_done[2], [1])
 
     for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work; wi += gridDim.x) {
         const WorkItem w = work[wi];
@@ -1191,6 +1207,11 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
         for (int k0 = wave * G; k0 < w.cnt; k0 += WAVES * G) {
           const int k1 = min(k0 + G, w.cnt);
           unsigned m1 = 0, carry = 0;
+          // the followers' exit test, built once per group behind the leader (see there): lane I its row tile's Tr_I, lane J
+          // its column tile's Tc_J, and the phase-1 tiles of a follower
+          int grp_tr = 0x7f800000;
+          int grp_tc[NP] = {};                       // (pair p of column tiles: lanes 0 .. 31 hold Tc of 2 p, lanes 32 .. 63 of 2 p + 1)
+          unsigned grp_p1 = 0;
           if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
             // ---- thr(I, J) of every tile pair, once per GROUP: lane (h, J) takes column tile J (one circle that holds the
             // tile under every rotation of the group, mm_tile_group_circle; a group of one: its centre rotated) against the
@@ -1250,7 +1271,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 if (lane == I) m1 |= 1u << L;
             }
           }
-          (void)m1; (void)carry;
+          (void)m1; (void)carry; (void)grp_tr; (void)grp_tc; (void)grp_p1;
           for (int k = k0; k < k1; ++k) {
             const float c = s_cs[2 * k], s = s_cs[2 * k + 1];
             const int a = s_ci[k];
@@ -1280,23 +1301,65 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 // tiles): a superset in phase 1 only lowers Umax and Vmax, so the skip rule below stays valid.
                 MXC_MARK("p1_init:1");
                 const unsigned p1m = m1 | carry;
+                const bool follower = __builtin_amdgcn_readfirstlane(k > k0) != 0;   // (wave-uniform, and known to be)
                 regs_t cm;
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
                 h8v af = s_a[lane];
-                for (int I = 0; I < nrt; ++I) {
-                    MXC_MARK("p1_row:nrt");
-                    const unsigned mask = __builtin_amdgcn_readlane(p1m, I);
-                    const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
-                    int rmin = 0x7f800000;
-                    mxc_tiles<NCT, 1>(mask, af, blo, bhi, cm, rmin);
-                    rmin = mxc_meet(rmin);
-                    if (lane < 32) s_rs[I * 32 + lane] = rmin;
-                    done += __builtin_popcount(mask);
-                    af = an;
+                // a follower on the way: the largest met row minimum so far (from 0, as the general path's rowmax), and
+                // whether a row minimum lies above its row tile's Tr_I (then row tile I has phase-2 tiles)
+                int fmax = 0;
+                unsigned long long late = 0;                                  // (a lane mask: scalar registers, no vector work)
+                // (the row loop twice in the code, so that a leader's is today's and a follower's has no branch per row tile)
+                auto p1_rows = [&](auto fol) {
+                    for (int I = 0; I < nrt; ++I) {
+                        constexpr bool FOL = decltype(fol)::value;
+                        if constexpr (FOL) MXC_MARK("p1f_row:frows"); else MXC_MARK("p1_row:lrows");
+                        const unsigned mask = __builtin_amdgcn_readlane(p1m, I);
+                        const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
+                        int rmin = 0x7f800000;
+                        mxc_tiles<NCT, FOL ? 3 : 1>(mask, af, blo, bhi, cm, rmin);
+                        rmin = mxc_meet(rmin);
+                        if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                        if constexpr (FOL) {
+                            fmax = max(fmax, rmin);
+                            late |= __builtin_amdgcn_ballot_w64(rmin > __builtin_amdgcn_readlane(grp_tr, I));
+                        } else {
+                            done += __builtin_popcount(mask);
+                        }
+                        af = an;
+                    }
+                };
+                if (follower) p1_rows(std::true_type{}); else p1_rows(std::false_type{});
+                if (follower) {
+                    // ---- the group test: this follower's phase-2 masks are all empty exactly when no met row
+                    // minimum of row tile I lies above Tr_I and no met column minimum of column tile J above Tc_J.  Then every
+                    // row tile is final with Umax_I, and the value is the maximum of the met minima: what the general path
+                    // returns with empty masks, without the column maxima, the masks, phase 2 and a second round of meets.
+                    MXC_MARK("fol_check:fol");
+                    __builtin_amdgcn_sched_barrier(0);                        // (the section's instructions stay behind its mark)
+                    done += grp_p1;
+                    ++n_foll;
+                    // (two column tiles meet in one swap: the lower lanes then hold tile 2 p's met minima, the upper tile 2 p + 1's)
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        const int c0 = cm[2 * p], c1 = cm[2 * p + 1 < NCT ? 2 * p + 1 : 2 * p];
+                        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)c0, (unsigned)c1, false, false);
+                        const int v = min((int)r[0], (int)r[1]);
+                        late |= __builtin_amdgcn_ballot_w64(v > grp_tc[p]);
+                        fmax = max(fmax, v);
+                    }
+                    if (!late) {
+                        MXC_MARK("fol_final:early");
+                        ++n_early;
+                        const int m = wave_max_i32_dpp(fmax);
+                        if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                        MXC_MARK("end:0");
+                        continue;
+                    }
                 }
                 // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
-                MXC_MARK("vmax:1");
+                MXC_MARK("vmax:late");
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) {
                     cm[t] = mxc_meet(cm[t]);
@@ -1312,9 +1375,10 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 }
                 __asm__ volatile("" ::: "memory");
                 // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
-                MXC_MARK("m2:1");
+                MXC_MARK("m2:late");
                 unsigned m2 = 0;
                 int rowmax = 0;
+                const bool leads = !follower && __builtin_amdgcn_readfirstlane(k1 - k0) > 1;   // (wave-uniform) a leader with followers
                 if (lane < nrt) {
                     const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
                     int umax = (int)0x80000000;
@@ -1337,8 +1401,43 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     }
                     m2 &= ~p1m;
                     if (!m2) rowmax = umax;                                   // row tile I is final after phase 1
+                    if (leads) {
+                        // Tr_I: the smallest thr of row tile I outside the followers' phase 1, p1m | m2 (each is positive: a
+                        // tile with !(thr > 0) is in m1)
+                        MXC_MARK("grp_tr:fgroup");
+                        const unsigned pf = p1m | m2;
+                        int tr = 0x7f800000;
+#pragma unroll
+                        for (int J = 0; J < NCT; ++J)
+                            if (!((pf >> J) & 1)) tr = min(tr, __float_as_int(th[J]));
+                        grp_tr = tr;
+                        MXC_MARK("m2:late");
+                    }
                 }
-                if (k == k0) carry = m2;
+                if (!follower) carry = m2;
+                if (leads) {
+                    // Tc_J: the same down column tile J (lane J reads the table's column: consecutive banks), and the
+                    // followers' phase-1 tile count.  A follower's m2 is then empty for every row tile exactly when
+                    // Umax_I <= Tr_I for every I and Vmax_J <= Tc_J for every J (0x7f800000 where nothing is outside).
+                    MXC_MARK("grp_tc:fgroup");
+                    const unsigned pf = m1 | carry;
+                    int tc = 0x7f800000;
+                    unsigned cnt = 0;
+                    for (int I = 0; I < nrt; ++I) {
+                        MXC_MARK("grp_tc_row:fgnrt");
+                        const unsigned pm = __builtin_amdgcn_readlane(pf, I);
+                        const int t = __float_as_int(s_th[I * 32 + l32]);
+                        if (!((pm >> l32) & 1)) tc = min(tc, t);
+                        cnt += __builtin_popcount(pm);
+                    }
+                    MXC_MARK("grp_tc:fgroup");
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        const int t0 = __builtin_amdgcn_readlane(tc, 2 * p), t1 = __builtin_amdgcn_readlane(tc, 2 * p + 1 < NCT ? 2 * p + 1 : 2 * p);
+                        grp_tc[p] = lane < 32 ? t0 : t1;
+                    }
+                    grp_p1 = cnt;
+                }
 
                 // ---- phase 2: only the row tiles with tiles left ----
                 for (unsigned long long rows = __builtin_amdgcn_ballot_w64(m2 != 0); rows; rows &= rows - 1) {
@@ -1352,7 +1451,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     done += __builtin_popcount(mask);
                     rowmax = max(rowmax, rmin);
                 }
-                MXC_MARK("final:1");
+                MXC_MARK("final:late");
                 int m = rowmax;
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
@@ -1498,7 +1597,10 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
           }
         }
     }
-    if (tiles_done && lane == 0 && done) atomicAdd(tiles_done, done);
+    if (tiles_done && lane == 0 && done) {
+        atomicAdd(tiles_done, done);
+        if (n_foll) { atomicAdd(tiles_done + 1, (unsigned long long)n_early); atomicAdd(tiles_done + 2, (unsigned long long)n_foll); }
+    }
 }
 
 template <int NCT>

@@ -3,7 +3,7 @@
 
     hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -Iinclude -Imultimoda-rs_amd/csrc \\
           --cuda-device-only -S multimoda-rs_amd/csrc/mm_kernels.hip -o mm_kernels.s
-    python tools/count_cull_isa.py mm_kernels.s --nct 17 --nrt 17 --tiles 60 --group 8
+    python tools/count_cull_isa.py mm_kernels.s --nct 17 --nrt 17 --tiles 60 --group 8 --early 0.8
 
 The kernel's candidate loop carries section marks, comment lines `; mxc:<name>:<trips>` that emit no instruction.  Every
 instruction line after a mark belongs to that section, in the TEXT order of the assembly (the compiler may place a block
@@ -14,6 +14,12 @@ how often the section runs per candidate:
     rows2    once per row tile that has tiles left in phase 2 (--rows2, default nrt: the upper bound)
     pairs64  once per 64 tile pairs     tiles    once per computed tile (summed over the copies, divided by their number)
     group    once per group of --group candidates (1 / G per candidate)      ghalf    `half`, per group
+    fgroup   once per group that has followers (1 / G per candidate, none at G = 1)     fgnrt    `nrt`, per such group
+    fol      once per follower of a group ((G - 1) / G per candidate)        frows    `nrt`, per follower
+    lrows    `nrt`, per leader (a group's first candidate: 1 / G per candidate)
+    early    once per follower that leaves after phase 1 on the group test (--early: their share of the followers, from
+             tools/model_cull_tiles.py --group G)
+    late     once per candidate that does not leave early (1 - early (G - 1) / G)
     0        not in the candidate loop
 
 and a section named `tile` is a computed tile's own body (its copies are averaged; every v_mfma counts to it).  A section
@@ -104,16 +110,20 @@ def sections(body):
     return secs
 
 
-def report(nct, body, inf, nrt, tiles, rows2, out, group=1):
+def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0):
     secs = sections(body)
     copies = max(1, secs["tile"]["entries"]) if "tile" in secs else 1
+    fol = (group - 1.0) / group
+    fgroup = 1.0 / group if group > 1 else 0.0
     trips = {"0": 0.0, "1": 1.0, "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
              "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles / copies, "tile": tiles / copies,
-             "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group}
+             "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group,
+             "fgroup": fgroup, "fgnrt": nrt * fgroup,
+             "fol": fol, "frows": nrt * fol, "lrows": nrt * (1.0 - fol), "early": early * fol, "late": 1.0 - early * fol}
     out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (
         nct, info(inf, "NumVgprs"), info(inf, "NumAgprs"), info(inf, "ScratchSize"), info(inf, "Occupancy")))
-    out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g, candidates/group %d; tile bodies in the code: %d\n" % (
-        nrt, nct, tiles, rows2, group, copies))
+    out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g, candidates/group %d, early share of the followers %g; tile bodies in the code: %d\n" % (
+        nrt, nct, tiles, rows2, group, early, copies))
     out.write("  %-10s %-8s %6s %6s %6s %6s %6s %6s %7s %9s\n" % ("section", "trips", "mfma", "valu", "salu", "lds", "vmem",
                                                                   "other", "static", "executed"))
     tot_tile = tot_rest = 0.0
@@ -142,9 +152,12 @@ def main(argv=None):
     ap.add_argument("--tiles", type=float, default=60, help="tiles computed per candidate")
     ap.add_argument("--rows2", type=float, default=None, help="row tiles with tiles left in phase 2 (default: nrt)")
     ap.add_argument("--group", type=int, default=1, help="candidates per group: the sections marked group / ghalf run once per group")
+    ap.add_argument("--early", type=float, default=0.0, help="share of a group's followers that leave after phase 1 (sections marked early / late)")
     a = ap.parse_args(argv)
     if a.group < 1:
         raise SystemExit("--group must be at least 1")
+    if not 0.0 <= a.early <= 1.0:
+        raise SystemExit("--early is a share, 0 .. 1")
     with open(a.asm) as f:
         ks = kernels(f.read())
     if not ks:
@@ -153,7 +166,7 @@ def main(argv=None):
         if a.nct and nct != a.nct:
             continue
         body, inf = ks[nct]
-        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group)
+        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group, a.early)
 
 
 if __name__ == "__main__":

@@ -19,10 +19,14 @@ Groups (--group G): G consecutive candidates share one threshold table and one p
 a column tile under every rotation of the group (mm_tile_group_circle: the middle rotation's centre, the radius widened by
 the farthest of the others), and the group's first candidate hands its phase-2 tiles to the others, which run them in
 phase 1 (--no-carry prices the shared thresholds alone).  --runs R prices R runs of G candidates spread over the list
-instead of all of it.
+instead of all of it.  With groups the last column is the share of the followers (all but a group's first candidate)
+whose phase 2 is empty: the ones the kernel lets go after phase 1 on the group test (mm_engine_screen_early counts them).
+--items W cuts the list into W work items the way the engine does (item k: candidates [n k / W, n (k + 1) / W)) and groups
+inside each item, as the kernel's waves do: the device's counters are matched item layout for item layout.
 
     python tools/model_cull_tiles.py --frames 12 --points 501 --pairs 1 2 3 4 --rotations 91
     python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --runs 15
+    python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --items 23
 """
 import argparse
 import os
@@ -171,6 +175,7 @@ def main():
     ap.add_argument("--layout", choices=("consecutive", "split", "both"), default="both")
     ap.add_argument("--group", type=int, default=1, help="candidates that share thresholds and phase-1 mask")
     ap.add_argument("--no-carry", action="store_true", help="the first candidate's phase-2 tiles are not handed on")
+    ap.add_argument("--items", type=int, default=1, help="work items the list is cut into; groups start anew in each")
     ap.add_argument("--runs", type=int, default=0, help="price this many runs of --group candidates spread over the list (0: all)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -181,20 +186,30 @@ def main():
         starts = np.linspace(0, max(0, len(angles) - a.group), a.runs).astype(np.int64)
         angles = np.concatenate([angles[i:i + a.group] for i in starts])
     layouts = ("consecutive", "split") if a.layout == "both" else (a.layout,)
-    print("layout        pair  tiles/candidate  phase 1   rows2   per row tile (phase 1 + 2)")
+    print("layout        pair  tiles/candidate  phase 1   rows2   per row tile (phase 1 + 2)" + ("   followers: empty phase 2" if a.group > 1 else ""))
     for lay in layouts:
-        tot, tot1, rows, rows2 = [], [], [], []
+        tot, tot1, rows, rows2, early = [], [], [], [], []
         for i in a.pairs:
             (ref, rm), (tgt, tm) = sets[i - 1], sets[i]
             if lay == "consecutive":
                 rm = tm = 0
-            p1, p2 = count_tiles(ref, tgt, angles, split_main(len(ref), rm), split_main(len(tgt), tm), a.group, not a.no_carry)
+            n, nw = len(angles), max(1, a.items)
+            cuts = [(n * k // nw, n * (k + 1) // nw) for k in range(nw)]
+            parts = [count_tiles(ref, tgt, angles[a0:a1], split_main(len(ref), rm), split_main(len(tgt), tm), a.group, not a.no_carry)
+                     for a0, a1 in cuts if a1 > a0]
+            p1, p2 = (np.concatenate([q[h] for q in parts]) for h in (0, 1))
             per_row = (p1 + p2).mean(axis=0)
             tot.append(per_row.sum()); tot1.append(p1.sum(axis=1).mean()); rows.append(per_row)
             rows2.append((p2 > 0).sum(axis=1).mean())
-            print("%-12s  %4d  %15.1f  %7.1f  %6.1f   %s" % (lay, i, tot[-1], tot1[-1], rows2[-1], " ".join("%.1f" % x for x in per_row)))
-        print("%-12s  mean  %15.1f  %7.1f  %6.1f   %s" % (lay, np.mean(tot), np.mean(tot1), np.mean(rows2),
-                                                          " ".join("%.1f" % x for x in np.mean(rows, axis=0))))
+            share = ""
+            if a.group > 1:
+                fol = np.concatenate([np.arange(a1 - a0) % a.group != 0 for a0, a1 in cuts if a1 > a0])
+                early.append((fol & (p2.sum(axis=1) == 0)).sum() / max(1, fol.sum()))
+                share = "   %d of %d = %.3f" % ((fol & (p2.sum(axis=1) == 0)).sum(), fol.sum(), early[-1])
+            print("%-12s  %4d  %15.1f  %7.1f  %6.1f   %s%s" % (lay, i, tot[-1], tot1[-1], rows2[-1], " ".join("%.1f" % x for x in per_row), share))
+        print("%-12s  mean  %15.1f  %7.1f  %6.1f   %s%s" % (lay, np.mean(tot), np.mean(tot1), np.mean(rows2),
+                                                            " ".join("%.1f" % x for x in np.mean(rows, axis=0)),
+                                                            "   %.3f" % np.mean(early) if early else ""))
 
 
 if __name__ == "__main__":
