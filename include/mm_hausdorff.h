@@ -229,6 +229,34 @@ int  mm_screen_values_group(mm_engine* e, const double* rx, const double* ry, in
                             int* n_items);
 /* TEST HOOK (host only): the group size chosen for a candidate list (radians) when the switch is automatic. */
 int  mm_screen_group_auto(const double* angles, int n);
+/* TEST HOOK (host only; no engine, no device): the level the engine plans for a batch of searches, as 64-bit words.
+ * Sets: set_len / set_rho (largest distance of a point from the set's centre) / set_main (points of the first of two runs,
+ * or 0) per set.  Pairs: ref_set, tgt_set, cx, cy, flags, tie_tol, delta_extra, slice_begin, slice_end per pair, and list_of,
+ * the pair's candidate list (radians): list k is angles[list_off[k] .. list_off[k + 1]), so pairs that name one list pass the
+ * same address and lists stored twice are equal by content only.  Then the precision, the candidate range, whether
+ * per-candidate costs are wanted, and the seven switches of mm_engine_set_* (bound_min_candidates, bound_matrix, its qt and
+ * nc, screen_cull, screen_split, screen_group).  out (room for cap words) receives *n_words words; a shorter buffer only
+ * reports the count.  Doubles are written by bit pattern.  Seven arrays, each preceded by its length in words:
+ *   header  precision (effective), P, W, W_lb, A, T, max_na, max_nbp, max_nt, use_fast, use_lb, lb_stride, lb_runs_cap,
+ *           lb_mx_tiles, kept_nct, kept_acap, pair_evals, lb_pair_evals, lb_sparse_total, slice_end, want_costs, the seven
+ *           switches in the order above
+ *   layout  byte offsets in the level blob of pairs, work, work_lb, cos32, sin32, cos64, sin64, ang64, sq32, sq64, flag,
+ *           items, n_items, lb32, pick, items_pick, items_lb, klist, emit, qlist, best_cost, best_idx, n_rescored, near_cnt,
+ *           near_idx; then lvl_in_bytes, lvl_bytes, off_best_cost, res_bytes, off_all_costs, r_best_idx, r_n_rescored,
+ *           r_near_cnt, r_near_idx, emit_rows, emit_cols
+ *   pairs   22 words a pair: ref_off, n_ref, tgt_off, n_tgt, tab_off, out_off, n_ang, flags, ang_full, ang_begin, n_slice,
+ *           pad0, ref_main, tgt_main, cx, cy, delta, tol2, e2, rho_t; then trivial, pair_slice_end
+ *   tables  the distinct candidate lists, slice by slice
+ *   work, work_lb   4 words an item: pair, a0, cnt, pad
+ *   groups  8 words a launch group: screen (0 none, 1 direct, 2 packed FMA, 3 matrix, 4 culled matrix), nct, multi, a_cap,
+ *           work_begin, work_count, candidates, tiles_full */
+int  mm_level_plan_probe(int n_sets, const int32_t* set_len, const double* set_rho, const int32_t* set_main, int n_pairs,
+                         const int32_t* ref_set, const int32_t* tgt_set, const double* cx, const double* cy,
+                         const int32_t* flags, const int32_t* list_of, int n_lists, const int64_t* list_off,
+                         const double* angles, const double* tie_tol, const double* delta_extra, const int32_t* slice_begin,
+                         const int32_t* slice_end, int precision, int32_t angle_begin, int32_t angle_end, int want_costs,
+                         int64_t bound_min_candidates, int bound_matrix, int bound_matrix_qt, int bound_matrix_nc,
+                         int screen_cull, int screen_split, int screen_group, int64_t* out, int64_t cap, int64_t* n_words);
 /* TEST HOOK (host only): the culled screen's layout of a set of n points in two runs (main, n - main): out[j] = the point
  * in slot j for j < slots, laid out as asked (main == 0: in order).  Returns the split the engine takes for (n, main):
  * main where it adds no tile, else 0; < 0 on bad arguments. */

@@ -32,7 +32,7 @@ EXPORTS = [
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_engine_screen_early", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
-    "mm_engine_set_screen_group", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto",
+    "mm_engine_set_screen_group", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -344,6 +344,9 @@ def lib():
     L.mm_tile_bound_probe_group.argtypes = [P, P, I, P, P, I, I, I, I, P, I, D, P, P]
     L.mm_screen_group_auto.restype = I
     L.mm_screen_group_auto.argtypes = [P, I]
+    L.mm_level_plan_probe.restype = I
+    L.mm_level_plan_probe.argtypes = [I, P, P, P, I, P, P, P, P, P, P, I, P, P, P, P, P, P, I, I32, I32, I,
+                                      I64, I, I, I, I, I, I, P, I64, P]
     L.mm_tile_slot_map.restype = I
     L.mm_tile_slot_map.argtypes = [I, I, I, P]
     L.mm_parse_contour_table.restype = I64

@@ -19,7 +19,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["mm_kernels.hip", "mm_nn_kernels.hip", "mm_ray_kernels.hip", "mm_slice_kernels.hip", "mm_engine.cpp", "mm_host.cpp", "mm_centerline.cpp", "mm_ccta.cpp",
+SOURCES = ["mm_kernels.hip", "mm_nn_kernels.hip", "mm_ray_kernels.hip", "mm_slice_kernels.hip", "mm_engine.cpp", "mm_level_plan.cpp", "mm_host.cpp", "mm_centerline.cpp", "mm_ccta.cpp",
            "mm_discretize.cpp", "mm_build.cpp", "mm_frames.cpp", "mm_comm.cpp", "mm_morph_kernels.hip",
            "mm_shape_kernels.hip", "mm_shape.cpp", "mm_trim_kernels.hip", "mm_trim.cpp", "mm_weld_kernels.hip",
            "mm_stitch.cpp", "mm_branch_kernels.hip", "mm_branch.cpp", "mm_cl_branches.cpp", "mm_close_kernels.hip",
@@ -27,7 +27,7 @@ SOURCES = ["mm_kernels.hip", "mm_nn_kernels.hip", "mm_ray_kernels.hip", "mm_slic
            "mm_bspline_kernels.hip", "mm_bspline.cpp", "mm_refine_kernels.hip", "mm_refine.cpp",
            "mm_tri_kernels.hip", "mm_surface.cpp", "mm_relax_kernels.hip", "mm_relax.cpp",
            "mm_flip_kernels.hip", "mm_flip.cpp"]
-HEADERS = ["mm_device.h", "mm_engine.h", "mm_pool.h", "mm_sort.h", "mm_trace.h", "mm_screen_mx_asm.inc", "mm_tile_bound.h",
+HEADERS = ["mm_device.h", "mm_engine.h", "mm_level_plan.h", "mm_search_records.h", "mm_screen_limits.h", "mm_pool.h", "mm_sort.h", "mm_trace.h", "mm_screen_mx_asm.inc", "mm_tile_bound.h",
            "mm_adjacency.h", "mm_stage.h", "mm_mesh_device.h", "mm_xcd.h", "mm_bspline_fit.h", "mm_point_records.h",
            "mm_point_device.h", "mm_prune.h", "mm_prune_device.h", "mm_tri_plan.h", "mm_tri_device.h"]
 PUBLIC_HEADERS = ["mm_hausdorff.h", "mm_centerline.h", "mm_ccta.h", "mm_build.h"]

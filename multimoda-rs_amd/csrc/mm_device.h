@@ -6,95 +6,10 @@
 #include <stdint.h>
 
 #include "mm_point_records.h"
+#include "mm_search_records.h"
+#include "mm_screen_limits.h"
 
 namespace mm {
-
-// One (reference set, target set, candidate list) search.  Point sets live in one pool
-// (several pairs may share a set: frame i is the target of pair i and the reference of
-// pair i+1); cos/sin tables are shared between pairs with identical candidate lists.
-struct PairDesc {
-    int32_t ref_off, n_ref;   // into the point pool
-    int32_t tgt_off, n_tgt;
-    int32_t tab_off;          // into the cos/sin tables
-    int32_t out_off;          // into the per-candidate outputs
-    int32_t n_ang;            // candidates of this pair in this plan (slice)
-    int32_t flags;            // MM_SEARCH_SKIP_ZERO
-    int32_t ang_full;         // length of the pair's full candidate list (>= n_ang)
-    int32_t ang_begin;        // first candidate of the slice this plan owns
-    int32_t n_slice;          // candidates in the slice (== n_ang, except for empty-set pairs: n_ang = 0 there)
-    int32_t pad0;             // k_screen_mx: scale exponent e (coordinates are multiplied by 2^e); otherwise 0
-    int32_t ref_main, tgt_main;   // k_screen_mx_cull: > 0 -- the set is two runs (main points, then the rest) and each run
-                                  // starts a tile of its own (mm_tile_slot_point, mm_tile_bound.h); 0: the points in order
-    double  cx, cy;           // rotation centre (exact kernel)
-    double  delta;            // f32 screening error bound (same unit as the costs)
-    double  tol2;             // candidates within tol2 of the exact minimum are reported as near-ties
-    double  e2;               // absolute error bound of the screened SQUARED value (fast kernel; else 0)
-    double  rho_t;            // largest distance of a target point from the rotation centre
-};
-
-// Source of one search set of the within-pullback search, built on the device from the raw pullback
-// (align_within.rs:173-191: downsample(lumen, S) ++ downsample(catheter, ceil(n_cath * S / len_lumen0)),
-// contour.rs:47-58), centred on the frame's centroid.  Raw pool = xyz triples (f64) as the caller holds them.
-struct SetSrc {
-    int64_t lum_at;           // first lumen point of the frame in the raw pool (point index)
-    int64_t cath_at;          // first catheter point of the frame (unused when cath_take == 0)
-    int32_t lum_len, lum_take;    // points of the contour, points asked for
-    int32_t cath_len, cath_take;
-    int32_t dst_off, n;       // into the point pool; n = min(lum_len, lum_take) + min(cath_len, cath_take)
-    double  cx, cy;           // the frame's centroid
-};
-
-// One workgroup's share: `cnt` consecutive candidates of one pair.
-struct WorkItem {
-    int32_t pair, a0, cnt, pad;   // pad: the bound kernels' candidate step; k_screen_mx_cull: candidates per group (0: 1)
-};
-
-static constexpr int kMaxNear = 8;  // near-tie slots per pair (MM_MAX_NEAR)
-
-struct BatchDev {
-    const PairDesc* pairs;
-    const WorkItem* work;
-    int32_t n_pairs, n_work;
-    // point pool: f32 copy relative to the set's centre, f64 copy as given
-    const float *p32x, *p32y;
-    const double *p64x, *p64y;
-    // candidate tables
-    const float *cos32, *sin32;
-    const double *cos64, *sin64;
-    const double *ang64;      // the candidate angles themselves (same indexing): device-side exchange records
-    // per-candidate outputs
-    float*    sq32;       // squared Hausdorff from the screening kernel
-    double*   sq64;       // exact squared Hausdorff (valid where flag != 0 or in exact mode)
-    uint8_t*  flag;       // 1 = shortlisted (re-scored in f64); before that, bounded search on the matrix pipe: 1 = needs a bound
-    int64_t   n_cand;     // candidates of the level (length of sq32 / lb32 / flag)
-    // shortlist queue
-    WorkItem* items;      // capacity = total candidates (bounded mode: first the survivors' runs)
-    int32_t*  n_items;    // 8 device counters: [0] re-score queue; bounded mode: [1] picks, [2] queue 0 (round 2),
-                          // [3] queue 1 (round 3), [4] second picks, [5] queue 2 (survivors)
-    // bounded screen (MM_PRECISION_F32_BOUNDED)
-    const WorkItem* work_lb;   // bound kernel's work list (more candidates per workgroup)
-    int32_t   n_work_lb, lb_stride;
-    int32_t   lb_mx;       // bounded search on the matrix pipe: row tiles per set of k_bound_mx's LDS layout
-    int32_t   lb_mx_qt, lb_mx_nc;   // its variant: column tiles of queries per side (1 | 2), candidates per wave at once (1 | 2)
-    int32_t   kept_mx_nct, kept_mx_acap;   // > 0: the bounded search runs on the matrix pipe; the picks' and the survivors'
-                                           // screen is k_screen_mx<kept_mx_nct, false> (every pair) with LDS for kept_mx_acap row tiles
-    float*    lb32;        // per-candidate lower bound of the screened squared value
-    int32_t*  pick_idx;    // [2 * n_pairs] per pair: candidate with the smallest bound after round 1 / round 3 (-1: none)
-    WorkItem* items_pick;  // [2 * n_pairs] queue entries of the two picks
-    WorkItem* items_lb;    // three queues of `runs cap` entries: round 2, round 3, survivors
-    int32_t*  klist;       // [n_cand] per pair (at its out_off): the survivors' candidate indices (k_lb_keep_mx)
-    float*    emit;        // per pair emit_rows + emit_cols: row / column minima of the first pick
-    int32_t   emit_rows, emit_cols;
-    int32_t*  qlist;       // per pair 2 * lb_list_queries(): decisive reference / target point indices
-    unsigned long long* stats;  // nullable: [1] candidates bounded in round 2, [3] in round 3, [2] fully screened
-    // per-pair results
-    double*   best_cost;
-    int32_t*  best_idx;
-    int32_t*  n_rescored;
-    int32_t*  near_cnt;   // exact-scored candidates with cost <= best + tol2 (may exceed kMaxNear)
-    int32_t*  near_idx;   // [n_pairs * kMaxNear] ascending candidate indices (full-list numbering)
-    double*   all_costs;  // optional per-candidate sqrt'ed costs
-};
 
 // Launchers (mm_kernels.hip).  All asynchronous on `s`.
 hipError_t launch_screen_f32(const BatchDev& b, int max_na, int max_nbp, hipStream_t s);
@@ -107,15 +22,7 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // tiles (nullable): device counter of the tiles computed
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
                                  hipStream_t s);
-bool       mx_cull_takes(int nct, int multi, int a_cap);
-int        mx_cull_group_max(int nct);   // candidates per group (WorkItem::pad) the culled screen of nct column tiles takes
 hipError_t launch_screen_none(const BatchDev& b, int work_begin, int n_work, hipStream_t s);   // screened value 0 for every candidate
-void       mx_variant(int n_tgt, int* nct, int* multi);
-size_t     lds_bytes_mx(int nct, bool multi, int a_cap, int waves);
-int        mx_min_points();
-int        mx_max_points();
-int        max_rows_fast();
-int        max_target_points_fast();
 // bounded screen: lower bound of every lb_candidate_step()-th candidate -> per-pair pick -> full screen of
 // the picks (upper bound) -> spread the bounds to the candidates in between (chord inequality) ->
 // lower bound of those still possible -> survivors -> full screen of the survivors (runs of <= 8
@@ -129,13 +36,7 @@ hipError_t launch_lb_keep(const BatchDev& b, int final, int cap, hipStream_t s);
 // round 3: the pick's decisive points (largest row / column minima) as queries for the survivors
 hipError_t launch_lb_topk(const BatchDev& b, int max_n, hipStream_t s);
 hipError_t launch_screen_lb_list(const BatchDev& b, int max_nap, int max_nbp, int cap, hipStream_t s);
-int        lb_list_queries();
-int        lb_candidate_step();
-int        lb_sparse_candidates(int n);   // candidates of a list of n the first round scores
 hipError_t launch_screen_kept(const BatchDev& b, int max_na, int max_nbp, int cap, hipStream_t s);
-int        lb_max_query_points();   // subset size the bound kernel holds in registers
-int        lb_mx_max_points();      // largest set (either side) the matrix-pipe bound kernel stages in LDS
-int        lb_max_points();         // largest set (either side) the bound kernel stages in LDS
 // large-set Hausdorff (no LDS limit on the set sizes); pairs/work are device arrays of the kernel's
 // LargePair {a_off, na, b_off, nb, col_off, pad} / LargeWork {pair, row0} records
 hipError_t launch_hausdorff_large(const void* pairs, const void* work, int n_pairs, int n_work, const double* px,
@@ -399,10 +300,6 @@ hipError_t launch_finalize(const BatchDev& b, int use_flags, hipStream_t s);
 hipError_t launch_export_cost(const BatchDev& b, const int32_t* pair_of_job, int n_jobs, double* cost, hipStream_t s);
 hipError_t launch_export_keys(const BatchDev& b, const int32_t* pair_of_job, int n_jobs, const double* gcost,
                               long long* keys, hipStream_t s);
-size_t     lds_bytes_f32(int nbp);
-size_t     lds_bytes_f64(int nbp);
-int        max_target_points_f32();
-int        max_target_points_f64();
 
 // closed smoothing B-spline contours (mm_bspline_kernels.hip): one job per contour (first point, count), one wave
 // each, the work arrays of a contour in lds_bytes = 8 * bspline_work_doubles(longest m, k) of dynamic LDS.

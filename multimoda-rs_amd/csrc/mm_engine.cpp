@@ -211,460 +211,69 @@ int Plan::stage_sets(Engine* e, const std::vector<SetRef>& sets, bool transient_
 // -------------------------------------------------------------------------------------
 // plan: level (descriptors, candidate tables, outputs)
 // -------------------------------------------------------------------------------------
-// f32 screening error bound (DESIGN.md "screen-then-exact"): with u = 2^-24 and rho_r, rho_t
-// the largest distance of a reference / target point from the rotation centre,
-// |H_f32 - H_true| <= u (3.9 rho_r + 10 rho_t); we use 24 u (rho_r + rho_t).
-// The screen works on coordinates relative to the rotation centre; the exact re-score is the REFERENCE's
-// arithmetic on the coordinates as given, whose rotation ends with "+ cx" (contour_point.rs:45-48): its result
-// is rounded at the magnitude of the coordinates, |H_f64 - H_true| <= 2^-53 (1.5 |c| + 10 rho_t + 3 rho_r).
-// That term only matters for point sets a billion times smaller than their coordinates (all points of a set
-// equal: every exact cost is 0.0, the screen sees 1e-17 -- found by the randomised search test), but the
-// shortlist has to hold every candidate whose EXACT cost can be minimal, so it is part of the bound:
-// 2^-49 (|cx| + |cy| + rho_r + rho_t), sixteen roundings at the coordinates' magnitude.
-static inline double screen_delta(double rho_r, double rho_t, double cx, double cy)
-{
-    const double u = 5.9604644775390625e-08;  // 2^-24
-    return 24.0 * u * (rho_r + rho_t) + std::ldexp(std::fabs(cx) + std::fabs(cy) + rho_r + rho_t, -49) + 1e-300;
-}
-
-// Error bound of the matrix-pipe screen's squared distances: |S~ - S| <= mx_e2(rho_a, rho_b), with rho_a (rho_b) the largest
-// distance of a reference (target) point from the rotation centre, R = rho_a + rho_b, u = 2^-24.  In the kernel's scaled
-// units (larger radius in [256, 512)) the screened value of a point pair is
-//     S~ = fl_acc( |a~|^2~ + n2(b) - 2 a~ . b~' ),   a~ = a1 + a2, b~' = b1' + b2' the f16 hi + lo splits of a and of R32(b),
-// the products exact in fp32 (11 x 11 bits), and the budget is (every term in units of u):
-//   * split of both points -- |a - a~|, |b' - b~'| <= 2^-22 |.| per coordinate (two roundings of relative size 2^-11), or
-//     2^-14 absolute where a lo piece falls into f16's subnormal range and the matrix pipe flushes it; the distance moves by
-//     2 |a - b| (|da| + |db|) <= 2 R sqrt(2) 2^-22 R = 11.3 R^2, with the absolute form 2 R 2 sqrt(2) 2^-14 = 22.6 R^2 (256 / R)
-//     <= 22.6 R^2 because the larger radius is at least 256:                                                        23 R^2
-//   * the row norm |a~|^2: two f32 roundings (2 rho_a^2), its own split n2 = 256 nh + nl (nh to 0.25, nl to 2^-6 absolute
-//     = 4 u rho^2 at rho = 256, less above):                                                                        6 rho_a^2
-//   * the column norm is taken from the UNROTATED target point, once per work item: the same 6, the f32 rotation (cos / sin
-//     tables rounded to f32: |c^2 + s^2 - 1| <= 1.5 u; two fma per coordinate: |b' - R b| <= 2 sqrt(2) u rho_b) keeps
-//     |b|^2 to 9, and the split of the rotated point moves |b'|^2 by 2 rho_b sqrt(2) 2^-22 rho_b = 11.3:               27 rho_b^2
-//   * twelve fp32 accumulations inside the MFMA, rounding mode and order unspecified: 2 u each on partial sums that stay
-//     below (|a| + |b|)^2 <= R^2:                                                                                   24 R^2
-// Sum: u (47 R^2 + 6 rho_a^2 + 27 rho_b^2) -- 55 u R^2 for equal radii.  (Rounds 3 shipped a flat 128 u R^2; the directed
-// search of tests/test_gpu_mx_error_bound.py -- coordinates on f16 ties, radii at both edges of the scale, far outliers,
-// subnormal lo pieces, tile-edge set sizes, the angles whose f32 (cos, sin) is furthest from unit norm -- found at most
-// 2.2 % of that, 5 % of this.)  min and max are 1-Lipschitz, so the bound carries over to the screened Hausdorff value.
-static double mx_e2(double rho_a, double rho_b)
-{
-    const double u = 5.9604644775390625e-08, R = rho_a + rho_b;
-    return u * (47.0 * R * R + 6.0 * rho_a * rho_a + 27.0 * rho_b * rho_b);
-}
-
-// The matrix-pipe kernels' scale exponent e: 2^e rmax in [256, 512) (f16 pieces, their doubles and |x|^2 / 256 stay in range)
-static int mx_scale_exp(double rmax)
-{
-    int k = 0;
-    (void)std::frexp(rmax * (1.0 + 1e-6), &k);   // radius < 2^k
-    return 9 - k;
-}
-
-// The screen of one pair searched without bound rounds; `multi`, `nct`, `cls`: the matrix pipe's variant (mx_variant) and
-// LDS class.  Pairs sort by (screen, multi, nct, cls), and a run of equal ones forms one launch (Plan::groups).
-struct PairScreen {
-    Screen screen; int multi, nct, cls;
-    auto key() const { return std::tie(screen, multi, nct, cls); }
-};
-
-// The matrix-pipe screen, chosen PER PAIR (MM_PRECISION_F32_MATRIX, or a bounded search without its bound rounds) for a
-// pair of nr, nt points and radii ra, rb: sets of mx_min_points() .. mx_max_points() points (the kernel is instantiated per
-// column-tile count, its row-tile count is a run-time operand, larger target sets are cut into column blocks) and radii the
-// scale exponent can take; then also *scale_exp and *e2, the error bound of its squared values.  A set of fewer than 64
-// points: no f32 screen, every candidate is scored exactly (cheap at that size, and no packed-FMA kernel runs under this
-// precision unless a set exceeds mx_max_points()).  Any other pair keeps `outside` (the packed-FMA screen, or in a batch
-// whose largest sets exceed that kernel's registers the direct form) and its e2.
-static PairScreen mx_pair_screen(int nr, int nt, double ra, double rb, Screen outside, int* scale_exp, double* e2)
-{
-    if (std::min(nr, nt) < mx_min_points() && std::max(nr, nt) <= mx_max_points()) return {Screen::None, 0, 0, 0};
-    const double rmax = std::max(ra, rb);
-    if (nr < mx_min_points() || nr > mx_max_points() || nt < mx_min_points() || nt > mx_max_points() || !(rmax > 1.0e-30) ||
-        !(rmax < 1.0e30))
-        return {outside, 0, 0, 0};
-    // LDS is sized per launch by the largest reference set of the group: up to 17 row tiles leave room for two workgroups
-    // per CU, more than that for one -- two classes, so that one long contour does not halve the occupancy of every other
-    // pair's launch
-    PairScreen c{Screen::Matrix, 0, 0, (nr + 31) / 32 <= 17 ? 0 : 1};
-    mx_variant(nt, &c.nct, &c.multi);
-    *scale_exp = mx_scale_exp(rmax);
-    *e2 = mx_e2(ra, rb);
-    return c;
-}
-
+// A level is DECIDED by plan_level (mm_level_plan.cpp: descriptors, screens, work lists, launch groups, layout -- no device)
+// and STAGED here: the candidate tables, the buffers, one upload, the device pointers.
 int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_t angle_begin, int32_t angle_end,
                       bool want_costs_, hipStream_t st, const ScreenOptions* opts_)
 {
     Engine* e = eng;
     if (!st) st = stream;
-    opts = opts_ ? *opts_ : e->screen_opts;
-    precision = precision_;
-    want_costs = want_costs_;
-    slice_end = angle_end;
-    P = (int)pairs.size();
-    if (precision != MM_PRECISION_F64 && precision != MM_PRECISION_F32 && precision != MM_PRECISION_F32_FAST &&
-        precision != MM_PRECISION_F32_BOUNDED && precision != MM_PRECISION_F32_MATRIX)
-        return set_error(MM_ERR_INVALID, "precision must be MM_PRECISION_F64, MM_PRECISION_F32, MM_PRECISION_F32_FAST, "
-                                         "MM_PRECISION_F32_BOUNDED or MM_PRECISION_F32_MATRIX");
-    // Non-finite (or overflowing) coordinates: the reference's metric skips the points whose distances are not finite
-    // (process_utils.rs:112-114) and carries on.  The exact kernels do the same; a screen cannot bound such values, so
-    // every candidate of this level is scored exactly.  (rho = inf marks such a set, see stage_sets / k_build_sets.)
-    // The same for finite coordinates an f32 screen cannot hold: squared distances reach (rho_r + rho_t)^2, which must
-    // stay below FLT_MAX (rho < 1e18 leaves a factor 1e2), and the error bounds of the screens (relative to rho) assume
-    // that u * rho^2 is far above the f32 denormals (rho > 1e-15 leaves a factor 1e8); rho == 0 (all points at the
-    // centre) is exact in any format.
-    auto f32_safe = [](double rho) { return rho < 1.0e18 && (rho == 0.0 || rho > 1.0e-15); };
-    if (precision != MM_PRECISION_F64)
-        for (const PairSpec& sp : pairs)
-            if (sp.ref_set >= 0 && sp.tgt_set >= 0 && (size_t)sp.ref_set < set_rho.size() && (size_t)sp.tgt_set < set_rho.size() &&
-                (!f32_safe(set_rho[sp.ref_set]) || !f32_safe(set_rho[sp.tgt_set]) || !std::isfinite(sp.cx) || !std::isfinite(sp.cy))) {
-                precision = MM_PRECISION_F64;
-                break;
-            }
-    const bool expanded = precision == MM_PRECISION_F32_FAST || precision == MM_PRECISION_F32_BOUNDED ||
-                          precision == MM_PRECISION_F32_MATRIX;
-    if (angle_begin < 0) angle_begin = 0;
-
-    TraceTimer tt_desc("stage_level: descriptors");
-    host_pairs.assign(P, PairDesc{});
-    trivial.assign(P, 0);
-    pair_slice_end.assign(P, 0);
-    host_tables.clear();
-    A = 0; T = 0;
-    max_na = 1; max_nbp = 16; max_nt = 1;
-    pair_evals = 0.0;
-    // table sharing: same list as the previous distinct table (pointer or content) and same slice
-    const double* last_ptr = nullptr; int32_t last_n = -1, last_b = -1, last_tab = 0, last_len = -1;
-    for (int p = 0; p < P; ++p) {
-        const PairSpec& sp = pairs[p];
-        if (sp.ref_set < 0 || sp.tgt_set < 0 || (size_t)sp.ref_set >= set_len.size() || (size_t)sp.tgt_set >= set_len.size())
-            return set_error(MM_ERR_INVALID, "pair references a set that was not staged");
-        if (sp.n_angles < 0) return set_error(MM_ERR_INVALID, "negative candidate count");
-        const int32_t nr = set_len[sp.ref_set], nt = set_len[sp.tgt_set];
-        const int32_t b = std::min(std::max(angle_begin, sp.slice_begin), sp.n_angles);
-        const int32_t en = std::min(std::min(angle_end, sp.slice_end), sp.n_angles);
-        const int32_t na = std::max(en - b, 0);
-        pair_slice_end[p] = std::max(en, b);
-        PairDesc& d = host_pairs[p];
-        d.ref_off = set_off[sp.ref_set]; d.n_ref = nr;
-        d.tgt_off = set_off[sp.tgt_set]; d.n_tgt = nt;
-        d.out_off = (int32_t)A; d.n_ang = na;
-        d.ang_full = sp.n_angles; d.ang_begin = b;
-        d.n_slice = na; d.pad0 = 0;
-        d.flags = sp.flags;
-        d.cx = sp.cx; d.cy = sp.cy;
-        d.tol2 = sp.tie_tol;
-        d.delta = (precision != MM_PRECISION_F64)
-                      ? screen_delta(set_rho[sp.ref_set], set_rho[sp.tgt_set], sp.cx, sp.cy) + sp.delta_extra : 0.0;
-        {   // expanded-form screening: |d2_f32 - d2| <= 5 u (rho_a + rho_b)^2; we use 8 u (..)^2
-            const double rs = set_rho[sp.ref_set] + set_rho[sp.tgt_set];
-            d.e2 = expanded ? 8.0 * 5.9604644775390625e-08 * rs * rs : 0.0;
-            d.rho_t = set_rho[sp.tgt_set];
-        }
-        if (nr == 0 || nt == 0) {
-            // process_utils.rs:86-88: an empty set makes every cost 0.0 -> the first candidate wins;
-            // nothing to launch for this pair (one table entry keeps its first angle).
-            trivial[p] = 1;
-            d.n_ang = 0;
-            d.tab_off = (int32_t)host_tables.size();
-            if (na > 0) host_tables.push_back(sp.angles[b]);
-            last_ptr = nullptr; last_len = -1;
-            continue;
-        }
-        const bool share = (na == last_len && b == last_b && sp.n_angles == last_n) &&
-                           (sp.angles == last_ptr ||
-                            (na > 0 && std::memcmp(sp.angles + b, host_tables.data() + last_tab, (size_t)na * 8) == 0));
-        if (!share) {
-            last_tab = (int32_t)host_tables.size();
-            host_tables.insert(host_tables.end(), sp.angles + b, sp.angles + b + na);
-            last_len = na; last_b = b; last_n = sp.n_angles;
-        }
-        last_ptr = sp.angles;
-        d.tab_off = last_tab;
-        A += na;
-        max_na = std::max<int>(max_na, nr);
-        max_nbp = std::max<int>(max_nbp, (nt + 15) & ~15);
-        max_nt = std::max<int>(max_nt, nt);
-        pair_evals += 2.0 * (double)nr * (double)nt * (double)na;
-        if (A > (int64_t)1 << 30) return set_error(MM_ERR_TOO_LARGE, "batch exceeds 2^30 candidates");
-    }
-    T = (int64_t)host_tables.size();
-    // the fast screening kernel keeps one row block in registers; bigger sets use the direct form
-    use_fast = expanded && max_na <= max_rows_fast() && max_nbp <= max_target_points_fast();
-    if (expanded && !use_fast)
-        for (PairDesc& d : host_pairs) d.e2 = 0.0;
-    // the bound rounds pay for themselves on sets of a few dozen points or more and on batches that keep
-    // the device busy for several rounds of workgroups (a dozen dependent launches cost more than
-    // screening a small batch outright: the between stage's 2 x 722 candidates are 40 % faster without);
-    // per-candidate costs need every candidate evaluated
-    use_lb = precision == MM_PRECISION_F32_BOUNDED && use_fast && !want_costs && A > 0 && A >= opts.bound_min_candidates &&
-             std::min(max_na, max_nt) >= 64 && std::max(max_na, max_nt) <= lb_max_points();
-    // The bound rounds on the matrix pipe (k_bound_mx) and the survivors through k_screen_mx: every non-trivial pair with
-    // sets of 64 .. lb_mx_max_points() points and a radius f16 can be scaled to; the pairs then carry the scale exponent and
-    // the matrix kernels' error bound (the larger of the two directions': pass 1 rotates reference queries against target
-    // rows, pass 2 target queries against reference rows).  The two per-pair picks stay on the packed-FMA screen (it emits
-    // the row / column minima the third round's query choice needs); its e2 is the smaller one.
-    lb_mx_tiles = 0; kept_nct = 0; kept_acap = 0;
-    if (use_lb && opts.bound_matrix) {
-        bool ok = true;
-        int tiles = 1, nct0 = -1, acap = 1;
-        for (int p = 0; p < P && ok; ++p) {
-            const PairDesc& d = host_pairs[p];
-            if (trivial[p] || d.n_ang == 0) continue;
-            const double rmax = std::max(set_rho[pairs[p].ref_set], set_rho[pairs[p].tgt_set]);
-            ok = d.n_ref >= mx_min_points() && d.n_tgt >= mx_min_points() && d.n_ref <= lb_mx_max_points() &&
-                 d.n_tgt <= lb_mx_max_points() && rmax > 1.0e-30 && rmax < 1.0e30;
-            tiles = std::max(tiles, (std::max(d.n_ref, d.n_tgt) + 31) / 32);
-            int nct = 0, multi = 0;
-            mx_variant(d.n_tgt, &nct, &multi);
-            if (multi) nct = 0;
-            nct0 = nct0 < 0 ? nct : (nct0 == nct ? nct0 : 0);     // 0: the pairs do not share one variant
-            acap = std::max(acap, (d.n_ref + 31) / 32);
-        }
-        // The picks and the survivors go through k_screen_mx from device queues, which takes ONE variant per launch: every
-        // pair must have the same column-tile count (and <= 17 row tiles, two workgroups per CU).  (k_screen_mx gives a
-        // candidate to one wave, ~10 us, where the packed-FMA screen spends 2 - 3 us of a whole workgroup -- 222 against
-        // 156 us per step for config3's survivors -- but the packed-FMA kernels are not to run beside MFMA kernels:
-        // profiles/README.md, "packed-FMA kernels beside MFMA kernels".)  A batch of mixed shapes, or one with sets beyond
-        // the bound kernel's range, is screened outright on the matrix pipe instead.
-        ok = ok && nct0 > 0 && acap <= 17;
-        if (!ok) use_lb = false;
-        if (ok) {
-            lb_mx_tiles = tiles;
-            kept_nct = nct0; kept_acap = acap;
-            for (int p = 0; p < P; ++p) {
-                PairDesc& d = host_pairs[p];
-                if (trivial[p] || d.n_ang == 0) continue;
-                const double ra = set_rho[pairs[p].ref_set], rb = set_rho[pairs[p].tgt_set];
-                d.pad0 = mx_scale_exp(std::max(ra, rb));
-                d.e2 = std::max(mx_e2(ra, rb), mx_e2(rb, ra));
-            }
-        }
-    }
-    // A bounded search that does not run its bound rounds (small batch, per-candidate costs asked for, sets outside the
-    // bound kernel's range) screens every candidate: on the matrix pipe, like MM_PRECISION_F32_MATRIX.
-    const bool mx_wanted = precision == MM_PRECISION_F32_MATRIX || (precision == MM_PRECISION_F32_BOUNDED && !use_lb);
-    bool use_mx = false;
-    const Screen outside = use_fast ? Screen::PackedFma : Screen::Direct;
-    std::vector<PairScreen> screen((size_t)P, PairScreen{outside, 0, 0, 0});
-    if (mx_wanted && A > 0) {
-        for (int p = 0; p < P; ++p) {
-            PairDesc& d = host_pairs[p];
-            if (trivial[p] || d.n_ang == 0) continue;
-            screen[(size_t)p] = mx_pair_screen(d.n_ref, d.n_tgt, set_rho[pairs[p].ref_set], set_rho[pairs[p].tgt_set], outside,
-                                               &d.pad0, &d.e2);
-            use_mx = use_mx || screen[(size_t)p].screen != outside;
-        }
-    }
-    if (max_nbp > max_target_points_f64() || (precision != MM_PRECISION_F64 && max_nbp > max_target_points_f32()))
-        return set_error(MM_ERR_TOO_LARGE, "target set does not fit the kernel's LDS budget (" +
-                                               std::to_string(max_target_points_f64()) + " points)");
-
-    tt_desc.stop();
-    TraceTimer tt_work("stage_level: work list");
-    // ---- work decomposition: one workgroup = `apb` consecutive candidates of one pair ----
-    const int64_t target_wgs = 256 * 24;
-    // the packed-FMA and exact kernels: at most 8 candidates per workgroup, measured on config3 (apb 2/4/8/16/64/128: 140.6/145.0/146.3/
-    // 144.6/138.2/122.3 TFLOP/s) -- many short workgroups keep the co-resident ones out of phase
-    // (rotation / epilogue of one overlaps the micro-tile loop of the others) and balance the tail
-    int apb = (int)std::min<int64_t>(8, std::max<int64_t>(1, (A + target_wgs - 1) / target_wgs));
-    // matrix-pipe screen: one WAVE per candidate, four waves per workgroup -- a workgroup of fewer than four candidates
-    // leaves waves idle for the whole item (small batches: a single search of 361 candidates)
-    if (use_mx) apb = std::max(apb, 4);
-    // ... and with the matrix-pipe screen more of them: a work item stages the pair's rows once (global loads, two barriers:
-    // ~3 us, with one other workgroup on the CU to hide it) and a 17 x 17-tile candidate takes a wave 10 us, a 7 x 7 one 1.8.
-    // A wave should see ~2300 tiles per item (17 x 17 tiles: 8 candidates, 32 per workgroup; small sets up to 16 per wave) as
-    // far as the batch has candidates for 24 workgroups per CU: config3's launch 16.19 ms at 578 tiles, 16.00 at 1156,
-    // 15.83 at 2312, 15.77 at 4624 (tools/exp_apb.sh).
-    const int64_t apb_fill = std::max<int64_t>(1, (A + target_wgs - 1) / target_wgs);
-    auto apb_of = [&](int p) {
-        if (screen[(size_t)p].screen != Screen::Matrix) return apb;
-        const PairDesc& d = host_pairs[p];
-        const int64_t tiles = (int64_t)((d.n_ref + 31) / 32) * ((d.n_tgt + 31) / 32);
-        const int64_t per_wave = std::min<int64_t>(16, std::max<int64_t>(2, (2312 + tiles - 1) / tiles));
-        return (int)std::max<int64_t>(apb, std::min<int64_t>(4 * per_wave, apb_fill));
-    };
-    // The culled screen's groups (ScreenOptions::screen_group): per pair the candidates that share one tile bound.  A forced
-    // size asks for work items of four groups, one per wave; the automatic one follows the pair's list and never takes more
-    // than a quarter of the item the batch gives the pair, so that a small batch keeps a candidate per wave.
-    std::vector<int> pair_group((size_t)P, 1);
-    if (use_mx && opts.screen_cull && opts.screen_group != 1) {
-        int32_t seen_tab = -1, seen_n = -1; int seen_g = 1;
-        for (int p = 0; p < P; ++p) {
-            const PairScreen& c = screen[(size_t)p];
-            const PairDesc& d = host_pairs[p];
-            if (c.screen != Screen::Matrix || c.multi || d.n_ang < 2) continue;
-            const int gmax = mx_cull_group_max(c.nct);
-            if (gmax < 2) continue;
-            int g = opts.screen_group;
-            if (g == 0) {
-                if (d.tab_off != seen_tab || d.n_ang != seen_n) {
-                    seen_g = mm_tile_group_auto(host_tables.data() + d.tab_off, d.n_ang);
-                    seen_tab = d.tab_off; seen_n = d.n_ang;
-                }
-                g = seen_g;
-                while (g > 1 && 4 * g > apb_of(p)) g >>= 1;
-            }
-            pair_group[(size_t)p] = std::min(g, gmax);
-        }
-    }
-    auto apb_grouped = [&](int p) {
-        const int g = pair_group[(size_t)p];
-        return g > 1 ? std::max(apb_of(p), 4 * g) : apb_of(p);
-    };
-    groups.clear();
-    {
-        // balanced chunks: ceil(n / apb) workgroups whose sizes differ by at most one (a 90-candidate
-        // slice is 12 x 7-8 candidates, not 11 x 8 + 2: the short tail would cost a full staging).
-        // 186 k items for config3: sized by a prefix sum and filled over the worker pool (one push_back at a time
-        // this was half of a case's staging time).  With the matrix-pipe screen the pairs are laid out group by group
-        // (stable: pair-major inside a group, as the XCD-aware work order wants it).
-        std::vector<int> order((size_t)P);
-        for (int p = 0; p < P; ++p) order[(size_t)p] = p;
-        if (use_mx) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return screen[(size_t)x].key() < screen[(size_t)y].key(); });
-        std::vector<int64_t> wstart((size_t)P + 1, 0);
-        for (int q = 0; q < P; ++q) {
-            const int ap = apb_grouped(order[(size_t)q]);
-            wstart[(size_t)q + 1] = wstart[(size_t)q] + (host_pairs[order[(size_t)q]].n_ang + ap - 1) / ap;
-        }
-        if (wstart[(size_t)P] > INT32_MAX) return set_error(MM_ERR_TOO_LARGE, "too many work items");
-        host_work.resize((size_t)wstart[(size_t)P]);
-        WorkItem* hw = host_work.data();
-        constexpr int kBlk = 64;
-        parallel_for((P + kBlk - 1) / kBlk, [&](int blk) {
-            for (int q = blk * kBlk; q < std::min(P, (blk + 1) * kBlk); ++q) {
-                const int p = order[(size_t)q];
-                const PairDesc& d = host_pairs[p];
-                const int nw = (int)(wstart[(size_t)q + 1] - wstart[(size_t)q]);
-                WorkItem* o = hw + wstart[(size_t)q];
-                for (int k = 0; k < nw; ++k) {
-                    const int a0 = (int)((int64_t)d.n_ang * k / nw), a1 = (int)((int64_t)d.n_ang * (k + 1) / nw);
-                    o[k] = WorkItem{p, a0, a1 - a0, pair_group[(size_t)p] > 1 ? pair_group[(size_t)p] : 0};
-                }
-            }
-        });
-        // one launch per run of pairs with the same screen; a matrix group takes the culled kernel if it can
-        if (precision != MM_PRECISION_F64 && !use_lb)
-            for (int q = 0; q < P;) {
-                const PairScreen c = screen[(size_t)order[(size_t)q]];
-                ScreenGroup g{c.screen, c.nct, c.multi, 1, (int)wstart[(size_t)q], 0, 0, 0};
-                int q1 = q;
-                for (; q1 < P && screen[(size_t)order[(size_t)q1]].key() == c.key(); ++q1) {
-                    const PairDesc& d = host_pairs[order[(size_t)q1]];
-                    if (d.n_ang > 0) g.a_cap = std::max(g.a_cap, (d.n_ref + 31) / 32);
-                    g.candidates += d.n_ang;
-                    g.tiles_full += (int64_t)d.n_ang * ((d.n_ref + 31) / 32) * c.nct;
-                }
-                g.work_count = (int)(wstart[(size_t)q1] - wstart[(size_t)q]);
-                if (g.screen == Screen::Matrix && opts.screen_cull && mx_cull_takes(g.nct, g.multi, g.a_cap)) g.screen = Screen::MatrixCull;
-                // the culled screen lays a set of two runs out run by run where that adds no tile: per set, per pair side
-                if (g.screen == Screen::MatrixCull && opts.screen_split)
-                    for (int k = q; k < q1; ++k) {
-                        const int p = order[(size_t)k];
-                        PairDesc& d = host_pairs[p];
-                        d.ref_main = mm_tile_split_main(d.n_ref, set_main[(size_t)pairs[p].ref_set]);
-                        d.tgt_main = mm_tile_split_main(d.n_tgt, set_main[(size_t)pairs[p].tgt_set]);
-                    }
-                if (g.work_count > 0) groups.push_back(g);
-                q = q1;
-            }
-    }
-    W = (int)host_work.size();
-    host_work_lb.clear();
-    W_lb = 0; lb_runs_cap = 0; lb_pair_evals = 0.0; lb_sparse_total = 0;
-    if (use_lb) {
-        // every lb_stride-th point of either set is a query; the subset has to fit the kernel's registers
-        const int qmax = kept_nct > 0 ? 32 * opts.bound_matrix_qt : lb_max_query_points();
-        lb_stride = std::max(kept_nct > 0 ? 1 : 8, (std::max(max_na, max_nt) + qmax - 1) / qmax);
-        // first round: every lb_candidate_step()-th candidate and the last one, 32 of them per workgroup
-        // (4 waves x 8: amortises staging the reference set)
-        const int apb_lb = 32, cstep = lb_candidate_step();
-        for (int p = 0; p < P; ++p) {
-            const PairDesc& d = host_pairs[p];
-            const int ne = lb_sparse_candidates(d.n_ang);
-            for (int i0 = 0; i0 < ne; i0 += apb_lb)
-                host_work_lb.push_back(WorkItem{p, i0 * cstep, std::min(apb_lb, ne - i0), cstep});
-            lb_runs_cap += (d.n_ang + 7) / 8;
-            const double qa = (d.n_ref + lb_stride - 1) / lb_stride, qb = (d.n_tgt + lb_stride - 1) / lb_stride;
-            lb_pair_evals += (qa * d.n_tgt + qb * d.n_ref) * (double)ne;
-            lb_sparse_total += ne;
-        }
-        W_lb = (int)host_work_lb.size();
-    }
-
-    tt_work.stop();
+    int rc = plan_level(set_off, set_len, set_rho, set_main, pairs, precision_, angle_begin, angle_end, want_costs_,
+                        opts_ ? *opts_ : e->screen_opts, lv);
+    if (rc) return rc;
     TraceTimer tt_copy("stage_level: layout + tables + copies");
-    // ---- layout ---------------------------------------------------------------------------
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = align_up(o + std::max<size_t>(bytes, 16)); return at; };
-    const size_t o_pairs = take((size_t)P * sizeof(PairDesc));
-    const size_t o_work = take((size_t)W * sizeof(WorkItem));
-    const size_t o_work_lb = take((size_t)W_lb * sizeof(WorkItem));
-    const size_t o_c32 = take((size_t)T * 4), o_s32 = take((size_t)T * 4);
-    const size_t o_c64 = take((size_t)T * 8), o_s64 = take((size_t)T * 8), o_a64 = take((size_t)T * 8);
-    lvl_in_bytes = o;
-    const size_t o_sq32 = take((size_t)A * 4), o_sq64 = take((size_t)A * 8), o_flag = take((size_t)A);
-    const size_t o_items = take((size_t)A * sizeof(WorkItem)), o_nitems = take(32);
-    const int emit_rows = (max_na + 3) & ~3, emit_cols = (max_nt + 3) & ~3;
-    const size_t o_lb32 = take(use_lb ? (size_t)A * 4 : 0), o_pick = take(use_lb ? (size_t)P * 8 : 0);
-    const size_t o_items_pick = take(use_lb ? (size_t)P * 2 * sizeof(WorkItem) : 0);
-    const size_t o_items_lb = take(use_lb ? (size_t)lb_runs_cap * 3 * sizeof(WorkItem) : 0);
-    const size_t o_klist = take(kept_nct > 0 ? (size_t)A * 4 : 0);
-    const size_t o_emit = take(use_lb ? (size_t)P * (size_t)(emit_rows + emit_cols) * 4 : 0);
-    const size_t o_qlist = take(use_lb ? (size_t)P * 2 * (size_t)lb_list_queries() * 4 : 0);
-    const size_t o_bc = take((size_t)P * 8), o_bi = take((size_t)P * 4), o_nr = take((size_t)P * 4);
-    const size_t o_nc = take((size_t)P * 4), o_ni = take((size_t)P * 4 * kMaxNear);
-    off_best_cost = o_bc; res_bytes = o - o_bc;
-    off_all_costs = want_costs ? take((size_t)A * 8) : 0;
-    lvl_bytes = o;
-    r_best_idx = o_bi - o_bc; r_n_rescored = o_nr - o_bc; r_near_cnt = o_nc - o_bc; r_near_idx = o_ni - o_bc;
+    const LevelLayout& l = lv.lay;
 
     // ---- stage inputs -----------------------------------------------------------------------
-    int rc = e->ensure(e->host_lvl, std::max(lvl_in_bytes, res_bytes), true);
-    if (rc) return rc;
+    if ((rc = e->ensure(e->host_lvl, std::max(l.lvl_in_bytes, l.res_bytes), true))) return rc;
     unsigned char* h = (unsigned char*)e->host_lvl.p;
-    float *c32 = (float*)(h + o_c32), *s32 = (float*)(h + o_s32);
-    double *c64 = (double*)(h + o_c64), *s64 = (double*)(h + o_s64);
-    if (T) std::memcpy(h + o_a64, host_tables.data(), (size_t)T * 8);
-    for (int64_t t = 0; t < T; ++t) {
+    float *c32 = (float*)(h + l.cos32), *s32 = (float*)(h + l.sin32);
+    double *c64 = (double*)(h + l.cos64), *s64 = (double*)(h + l.sin64);
+    if (lv.T) std::memcpy(h + l.ang64, lv.host_tables.data(), (size_t)lv.T * 8);
+    for (int64_t t = 0; t < lv.T; ++t) {
         double co, si;
-        ::sincos(host_tables[(size_t)t], &si, &co);   // one glibc sincos, like the reference's per-point cos()/sin() pair
+        ::sincos(lv.host_tables[(size_t)t], &si, &co);   // one glibc sincos, like the reference's per-point cos()/sin() pair
         c64[t] = co; s64[t] = si; c32[t] = (float)co; s32[t] = (float)si;
     }
-    if (P) std::memcpy(h + o_pairs, host_pairs.data(), (size_t)P * sizeof(PairDesc));
-    if (W) std::memcpy(h + o_work, host_work.data(), (size_t)W * sizeof(WorkItem));
-    if (W_lb) std::memcpy(h + o_work_lb, host_work_lb.data(), (size_t)W_lb * sizeof(WorkItem));
+    if (lv.P) std::memcpy(h + l.pairs, lv.host_pairs.data(), (size_t)lv.P * sizeof(PairDesc));
+    if (lv.W) std::memcpy(h + l.work, lv.host_work.data(), (size_t)lv.W * sizeof(WorkItem));
+    if (lv.W_lb) std::memcpy(h + l.work_lb, lv.host_work_lb.data(), (size_t)lv.W_lb * sizeof(WorkItem));
 
     if (transient) {
-        rc = e->ensure(e->dev_lvl, lvl_bytes, false);
-        if (rc) return rc;
+        if ((rc = e->ensure(e->dev_lvl, l.lvl_bytes, false))) return rc;
         lvl_blob = (unsigned char*)e->dev_lvl.p; own_lvl = false;
-    } else if (lvl_bytes > lvl_cap) {
+    } else if (l.lvl_bytes > lvl_cap) {
         if (lvl_blob) { MM_HIP(hipStreamSynchronize(stream)); MM_HIP(hipStreamSynchronize(st)); e->blob_release(lvl_blob, lvl_cap); lvl_blob = nullptr; }
-        if ((rc = e->blob_alloc((void**)&lvl_blob, lvl_bytes, &lvl_cap))) return rc;
+        if ((rc = e->blob_alloc((void**)&lvl_blob, l.lvl_bytes, &lvl_cap))) return rc;
         own_lvl = true;
     }
-    MM_HIP(upload(lvl_blob, h, lvl_in_bytes, transient, st));
+    MM_HIP(upload(lvl_blob, h, l.lvl_in_bytes, transient, st));
     if (!transient) MM_HIP(hipStreamSynchronize(st));  // host staging buffer is reused
-
-    unsigned char* B = lvl_blob;
-    dev.pairs = (const PairDesc*)(B + o_pairs); dev.work = (const WorkItem*)(B + o_work);
-    dev.n_pairs = P; dev.n_work = W;
-    dev.cos32 = (const float*)(B + o_c32); dev.sin32 = (const float*)(B + o_s32);
-    dev.cos64 = (const double*)(B + o_c64); dev.sin64 = (const double*)(B + o_s64);
-    dev.ang64 = (const double*)(B + o_a64);
-    dev.sq32 = (float*)(B + o_sq32); dev.sq64 = (double*)(B + o_sq64); dev.flag = (uint8_t*)(B + o_flag); dev.n_cand = A;
-    dev.items = (WorkItem*)(B + o_items); dev.n_items = (int32_t*)(B + o_nitems);
-    dev.work_lb = (const WorkItem*)(B + o_work_lb); dev.n_work_lb = W_lb; dev.lb_stride = lb_stride;
-    dev.lb_mx = lb_mx_tiles; dev.kept_mx_nct = kept_nct; dev.kept_mx_acap = kept_acap;
-    dev.lb_mx_qt = opts.bound_matrix_qt; dev.lb_mx_nc = opts.bound_matrix_nc;
-    dev.lb32 = (float*)(B + o_lb32); dev.pick_idx = (int32_t*)(B + o_pick); dev.items_pick = (WorkItem*)(B + o_items_pick);
-    dev.items_lb = (WorkItem*)(B + o_items_lb); dev.emit = (float*)(B + o_emit); dev.emit_rows = emit_rows; dev.emit_cols = emit_cols;
-    dev.qlist = (int32_t*)(B + o_qlist); dev.klist = (int32_t*)(B + o_klist);
-    dev.best_cost = (double*)(B + o_bc); dev.best_idx = (int32_t*)(B + o_bi); dev.n_rescored = (int32_t*)(B + o_nr);
-    dev.near_cnt = (int32_t*)(B + o_nc); dev.near_idx = (int32_t*)(B + o_ni);
-    dev.all_costs = want_costs ? (double*)(B + off_all_costs) : nullptr;
+    bind_level();
     return MM_OK;
+}
+
+// The device description of the staged level: every region of the blob at its offset, the plan's sizes and switches.
+void Plan::bind_level()
+{
+    const LevelLayout& l = lv.lay;
+    unsigned char* B = lvl_blob;
+    dev.pairs = (const PairDesc*)(B + l.pairs); dev.work = (const WorkItem*)(B + l.work);
+    dev.n_pairs = lv.P; dev.n_work = lv.W;
+    dev.cos32 = (const float*)(B + l.cos32); dev.sin32 = (const float*)(B + l.sin32);
+    dev.cos64 = (const double*)(B + l.cos64); dev.sin64 = (const double*)(B + l.sin64);
+    dev.ang64 = (const double*)(B + l.ang64);
+    dev.sq32 = (float*)(B + l.sq32); dev.sq64 = (double*)(B + l.sq64); dev.flag = (uint8_t*)(B + l.flag); dev.n_cand = lv.A;
+    dev.items = (WorkItem*)(B + l.items); dev.n_items = (int32_t*)(B + l.n_items);
+    dev.work_lb = (const WorkItem*)(B + l.work_lb); dev.n_work_lb = lv.W_lb; dev.lb_stride = lv.lb_stride;
+    dev.lb_mx = lv.lb_mx_tiles; dev.kept_mx_nct = lv.kept_nct; dev.kept_mx_acap = lv.kept_acap;
+    dev.lb_mx_qt = lv.opts.bound_matrix_qt; dev.lb_mx_nc = lv.opts.bound_matrix_nc;
+    dev.lb32 = (float*)(B + l.lb32); dev.pick_idx = (int32_t*)(B + l.pick); dev.items_pick = (WorkItem*)(B + l.items_pick);
+    dev.items_lb = (WorkItem*)(B + l.items_lb); dev.emit = (float*)(B + l.emit); dev.emit_rows = l.emit_rows; dev.emit_cols = l.emit_cols;
+    dev.qlist = (int32_t*)(B + l.qlist); dev.klist = (int32_t*)(B + l.klist);
+    dev.best_cost = (double*)(B + l.best_cost); dev.best_idx = (int32_t*)(B + l.best_idx); dev.n_rescored = (int32_t*)(B + l.n_rescored);
+    dev.near_cnt = (int32_t*)(B + l.near_cnt); dev.near_idx = (int32_t*)(B + l.near_idx);
+    dev.all_costs = lv.want_costs ? (double*)(B + l.off_all_costs) : nullptr;
 }
 
 // Engine::screened's slot of a screen: [0] direct form, [1] packed FMA, [2] / [3] matrix pipe in one block / in column
@@ -682,49 +291,49 @@ static int screened_slot(Screen screen, int multi)
 int Plan::run(bool screen_only)
 {
     hipStream_t s = stream;
-    if (W == 0) {
-        if (!screen_only && P > 0) { hipError_t e = launch_finalize(dev, 0, s); if (e != hipSuccess) return hip_error(e, "finalize"); }
+    if (lv.W == 0) {
+        if (!screen_only && lv.P > 0) { hipError_t e = launch_finalize(dev, 0, s); if (e != hipSuccess) return hip_error(e, "finalize"); }
         return MM_OK;
     }
     hipError_t e;
     int prc;
-    if (precision != MM_PRECISION_F64) {
-        if (use_lb) {
+    if (lv.precision != MM_PRECISION_F64) {
+        if (lv.use_lb) {
             // bound a sparse subset of the candidates, fully screen one per pair (upper bound), spread the
             // bounds to the candidates in between, bound those still possible, screen the survivors
             MM_HIP(hipMemsetAsync(dev.n_items, 0, 32, s));
             dev.stats = eng->profile ? eng->dev_stats : nullptr;
-            const int nap = (max_na + 31) & ~31, nbp = (max_nt + 31) & ~31, cap = lb_runs_cap;
+            const int nap = (lv.max_na + 31) & ~31, nbp = (lv.max_nt + 31) & ~31, cap = lv.lb_runs_cap;
             if ((prc = eng->profile_begin(s))) return prc;
             if ((e = launch_screen_lb(dev, nap, nbp, s)) != hipSuccess) return hip_error(e, "bound kernel launch");
-            if ((prc = eng->profile_end(s, lb_pair_evals, A))) return prc;
+            if ((prc = eng->profile_end(s, lv.lb_pair_evals, lv.A))) return prc;
             if ((prc = eng->profile_begin(s))) return prc;
             if ((e = launch_lb_pick(dev, 0, s)) != hipSuccess) return hip_error(e, "pick kernel launch");
-            if ((e = launch_screen_picks(dev, 0, max_na, max_nbp, s)) != hipSuccess) return hip_error(e, "screen kernel launch (picks)");
+            if ((e = launch_screen_picks(dev, 0, lv.max_na, lv.max_nbp, s)) != hipSuccess) return hip_error(e, "screen kernel launch (picks)");
             if ((e = launch_lb_spread(dev, s)) != hipSuccess) return hip_error(e, "spread kernel launch");
             if ((e = launch_screen_lb_queued(dev, nap, nbp, cap, s)) != hipSuccess) return hip_error(e, "bound kernel launch (round 2)");
             if ((e = launch_lb_keep(dev, 0, cap, s)) != hipSuccess) return hip_error(e, "keep kernel launch");
             // round 3: the pick's decisive points as queries, then a second pick on the sharpened bounds
-            if ((e = launch_lb_topk(dev, std::max(max_na, max_nt), s)) != hipSuccess) return hip_error(e, "top-k kernel launch");
+            if ((e = launch_lb_topk(dev, std::max(lv.max_na, lv.max_nt), s)) != hipSuccess) return hip_error(e, "top-k kernel launch");
             if ((e = launch_screen_lb_list(dev, nap, nbp, cap, s)) != hipSuccess) return hip_error(e, "bound kernel launch (round 3)");
             if ((e = launch_lb_pick(dev, 1, s)) != hipSuccess) return hip_error(e, "pick kernel launch (2)");
-            if ((e = launch_screen_picks(dev, 1, max_na, max_nbp, s)) != hipSuccess) return hip_error(e, "screen kernel launch (picks 2)");
+            if ((e = launch_screen_picks(dev, 1, lv.max_na, lv.max_nbp, s)) != hipSuccess) return hip_error(e, "screen kernel launch (picks 2)");
             if ((e = launch_lb_keep(dev, 1, cap, s)) != hipSuccess) return hip_error(e, "keep kernel launch (final)");
-            if ((e = launch_screen_kept(dev, max_na, max_nbp, cap, s)) != hipSuccess)
+            if ((e = launch_screen_kept(dev, lv.max_na, lv.max_nbp, cap, s)) != hipSuccess)
                 return hip_error(e, "screen kernel launch (survivors)");
             if ((prc = eng->profile_end(s, 0.0, 0))) return prc;
-            if (eng->profile) { eng->bound_offered += A; eng->bound_round1 += lb_sparse_total; }
+            if (eng->profile) { eng->bound_offered += lv.A; eng->bound_round1 += lv.lb_sparse_total; }
         } else {
             if ((prc = eng->profile_begin(s))) return prc;
             e = hipSuccess;
-            for (const ScreenGroup& g : groups) {
+            for (const ScreenGroup& g : lv.groups) {
                 eng->screened[screened_slot(g.screen, g.multi)] += g.candidates;
                 BatchDev sub = dev;              // the direct-form and packed-FMA kernels take their group's work items here
                 sub.work = dev.work + g.work_begin; sub.n_work = g.work_count;
                 switch (g.screen) {
                 case Screen::None: e = launch_screen_none(dev, g.work_begin, g.work_count, s); break;
-                case Screen::Direct: e = launch_screen_f32(sub, max_na, max_nbp, s); break;
-                case Screen::PackedFma: e = launch_screen_fast(sub, max_na, max_nbp, s); break;
+                case Screen::Direct: e = launch_screen_f32(sub, lv.max_na, lv.max_nbp, s); break;
+                case Screen::PackedFma: e = launch_screen_fast(sub, lv.max_na, lv.max_nbp, s); break;
                 case Screen::Matrix: e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s); break;
                 case Screen::MatrixCull:
                     eng->cull_tiles_full += g.tiles_full;
@@ -734,23 +343,23 @@ int Plan::run(bool screen_only)
                 if (e != hipSuccess) break;
             }
             if (e != hipSuccess) return hip_error(e, "screen kernel launch");
-            if ((prc = eng->profile_end(s, pair_evals, A))) return prc;
+            if ((prc = eng->profile_end(s, lv.pair_evals, lv.A))) return prc;
         }
         if ((prc = mark_search_done())) return prc;
         if (screen_only) return MM_OK;
         MM_HIP(hipMemsetAsync(dev.n_items, 0, 16, s));
         e = launch_shortlist(dev, s);
         if (e != hipSuccess) return hip_error(e, "shortlist kernel launch");
-        e = launch_rescore(dev, max_na, max_nbp, (int)std::min<int64_t>(A, INT32_MAX), s);
+        e = launch_rescore(dev, lv.max_na, lv.max_nbp, (int)std::min<int64_t>(lv.A, INT32_MAX), s);
         if (e != hipSuccess) return hip_error(e, "rescore kernel launch");
         e = launch_finalize(dev, 1, s);
         if (e != hipSuccess) return hip_error(e, "finalize kernel launch");
     } else {
         if ((prc = eng->profile_begin(s))) return prc;
-        eng->screened[4] += A;
-        e = launch_exact_all(dev, max_na, max_nbp, s);
+        eng->screened[4] += lv.A;
+        e = launch_exact_all(dev, lv.max_na, lv.max_nbp, s);
         if (e != hipSuccess) return hip_error(e, "exact kernel launch");
-        if ((prc = eng->profile_end(s, pair_evals, A))) return prc;
+        if ((prc = eng->profile_end(s, lv.pair_evals, lv.A))) return prc;
         if ((prc = mark_search_done())) return prc;
         if (screen_only) return MM_OK;
         e = launch_finalize(dev, 0, s);
@@ -770,22 +379,22 @@ int Plan::mark_search_done()
 
 int Plan::fetch(BatchResult& out, double* all_costs_plan_order)
 {
-    const size_t cost_bytes = (all_costs_plan_order && dev.all_costs) ? (size_t)A * 8 : 0;
+    const size_t cost_bytes = (all_costs_plan_order && dev.all_costs) ? (size_t)lv.A * 8 : 0;
     unsigned char* h = (unsigned char*)eng->host_lvl.p;  // sized in stage_level
-    if (P > 0) MM_HIP(launch_copy_small(h, lvl_blob + off_best_cost, res_bytes, stream));   // not hipMemcpyAsync: k_copy_small
+    if (lv.P > 0) MM_HIP(launch_copy_small(h, lvl_blob + lv.lay.off_best_cost, lv.lay.res_bytes, stream));   // not hipMemcpyAsync: k_copy_small
     if (cost_bytes)
         MM_HIP(hipMemcpyAsync(all_costs_plan_order, dev.all_costs, cost_bytes, hipMemcpyDeviceToHost, stream));
     MM_HIP(hipStreamSynchronize(stream));
     const double* hc = (const double*)h;
-    const int32_t* hi = (const int32_t*)(h + r_best_idx);
-    const int32_t* hn = (const int32_t*)(h + r_n_rescored);
-    const int32_t* hnc = (const int32_t*)(h + r_near_cnt);
-    const int32_t* hni = (const int32_t*)(h + r_near_idx);
-    out.best_idx.assign(P, -1); out.n_rescored.assign(P, 0); out.near_cnt.assign(P, 0);
-    out.near_idx.assign((size_t)P * kMaxNear, -1); out.best_cost.assign(P, INFINITY);
-    for (int p = 0; p < P; ++p) {
-        const PairDesc& d = host_pairs[p];
-        if (trivial[p]) {
+    const int32_t* hi = (const int32_t*)(h + lv.lay.r_best_idx);
+    const int32_t* hn = (const int32_t*)(h + lv.lay.r_n_rescored);
+    const int32_t* hnc = (const int32_t*)(h + lv.lay.r_near_cnt);
+    const int32_t* hni = (const int32_t*)(h + lv.lay.r_near_idx);
+    out.best_idx.assign(lv.P, -1); out.n_rescored.assign(lv.P, 0); out.near_cnt.assign(lv.P, 0);
+    out.near_idx.assign((size_t)lv.P * kMaxNear, -1); out.best_cost.assign(lv.P, INFINITY);
+    for (int p = 0; p < lv.P; ++p) {
+        const PairDesc& d = lv.host_pairs[p];
+        if (lv.trivial[p]) {
             // every candidate costs 0.0; the ordered first minimum is the first candidate of the slice
             if (d.ang_begin < slice_hi(p)) {
                 out.best_idx[p] = d.ang_begin; out.best_cost[p] = 0.0;
@@ -801,10 +410,10 @@ int Plan::fetch(BatchResult& out, double* all_costs_plan_order)
 
 double Plan::angle_of(int p, int32_t idx) const
 {
-    const PairDesc& d = host_pairs[p];
+    const PairDesc& d = lv.host_pairs[p];
     if (idx < d.ang_begin) return NAN;
     const size_t k = (size_t)d.tab_off + (size_t)(idx - d.ang_begin);
-    return k < host_tables.size() ? host_tables[k] : NAN;
+    return k < lv.host_tables.size() ? lv.host_tables[k] : NAN;
 }
 
 Plan::~Plan()
@@ -854,10 +463,10 @@ static int make_specs(int n_pairs, const int64_t* ref_off, const double* ref_x, 
 // Scatter plan-order costs into the caller's ang_off indexing (slices, empty-set pairs).
 static void scatter_costs(const Plan& plan, const double* plan_costs, const int64_t* ang_off, double* all_costs)
 {
-    for (int p = 0; p < plan.P; ++p) {
-        const PairDesc& d = plan.host_pairs[p];
+    for (int p = 0; p < plan.lv.P; ++p) {
+        const PairDesc& d = plan.lv.host_pairs[p];
         double* dst = all_costs + ang_off[p] + d.ang_begin;
-        if (plan.trivial[p]) {
+        if (plan.lv.trivial[p]) {
             const int32_t n = std::max(0, plan.slice_hi(p) - d.ang_begin);
             for (int32_t a = 0; a < n; ++a) dst[a] = 0.0;
         } else if (d.n_ang > 0) {
@@ -1369,7 +978,7 @@ int mm_best_rotation_batch(mm_engine* h, int n_pairs,
     if ((rc = plan.stage_level(pairs, precision, 0, INT32_MAX, all_costs != nullptr))) return rc;
     if ((rc = plan.run(false))) return rc;
     BatchResult res;
-    std::vector<double> costs(all_costs ? (size_t)plan.A : 0);
+    std::vector<double> costs(all_costs ? (size_t)plan.lv.A : 0);
     if ((rc = plan.fetch(res, all_costs ? costs.data() : nullptr))) return rc;
     for (int p = 0; p < n_pairs; ++p) {
         if (best_idx) best_idx[p] = res.best_idx[p];
@@ -1379,6 +988,20 @@ int mm_best_rotation_batch(mm_engine* h, int n_pairs,
     }
     if (all_costs) scatter_costs(plan, costs.data(), ang_off, all_costs);
     return MM_OK;
+}
+
+// What the single-search test hooks below share: one pair of sets staged on the engine's transient buffers, its level
+// staged with the hook's switches (bound_min_candidates 0: a single search never skips what the hook asks for).
+static int stage_single(Engine* e, Plan& plan, const SetRef& ref, const SetRef& tgt, int flags, const double* angles, int n_angles,
+                        int precision, ScreenOptions opts)
+{
+    MM_HIP(hipSetDevice(e->device));
+    std::vector<SetRef> sets{ref, tgt};
+    std::vector<PairSpec> pairs{PairSpec{0, 1, ref.cx, ref.cy, flags, angles, n_angles, 0.0, 0.0}};
+    opts.bound_min_candidates = 0;
+    int rc = plan.stage_sets(e, sets, true);
+    if (!rc) rc = plan.stage_level(pairs, precision, 0, INT32_MAX, false, nullptr, &opts);
+    return rc;
 }
 
 // The lower bound MM_PRECISION_F32_BOUNDED's first round would give EVERY candidate of one search (it scores every 8th):
@@ -1391,26 +1014,23 @@ int mm_lower_bounds(mm_engine* h, const double* rx, const double* ry, int nr, co
 {
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e || !out_lb2 || nr <= 0 || nt <= 0 || n_angles <= 0 || !angles) return set_error(MM_ERR_INVALID, "mm_lower_bounds: bad arguments");
-    MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
-    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
-    opts.bound_min_candidates = 0; opts.bound_matrix = matrix != 0;
+    opts.bound_matrix = matrix != 0;
     Plan plan;
-    int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
+    int rc = stage_single(e, plan, SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}, flags, angles, n_angles,
+                          MM_PRECISION_F32_BOUNDED, opts);
     if (rc) return rc;
-    if (!plan.use_lb || (matrix != 0) != (plan.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_lower_bounds: the bound kernel asked for does not take these sets");
+    if (!plan.lv.use_lb || (matrix != 0) != (plan.lv.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_lower_bounds: the bound kernel asked for does not take these sets");
     BatchDev sub = plan.dev;
-    sub.work_lb = plan.dev.work; sub.n_work_lb = plan.W;      // every candidate, step 1 (WorkItem::pad == 0)
-    const int nap = (plan.max_na + 31) & ~31, nbp = (plan.max_nt + 31) & ~31;
+    sub.work_lb = plan.dev.work; sub.n_work_lb = plan.lv.W;      // every candidate, step 1 (WorkItem::pad == 0)
+    const int nap = (plan.lv.max_na + 31) & ~31, nbp = (plan.lv.max_nt + 31) & ~31;
     hipError_t he = launch_screen_lb(sub, nap, nbp, plan.stream);
     if (he != hipSuccess) return hip_error(he, "bound kernel launch");
     MM_HIP(hipMemcpyAsync(out_lb2, plan.dev.lb32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));
-    if (e2) *e2 = plan.host_pairs[0].e2;
-    if (delta) *delta = plan.host_pairs[0].delta;
-    if (stride) *stride = plan.lb_stride;
+    if (e2) *e2 = plan.lv.host_pairs[0].e2;
+    if (delta) *delta = plan.lv.host_pairs[0].delta;
+    if (stride) *stride = plan.lv.lb_stride;
     return MM_OK;
 }
 
@@ -1424,24 +1044,21 @@ int mm_bound_state(mm_engine* h, const double* rx, const double* ry, int nr, con
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e || !rx || !ry || !tx || !ty || !angles || !out_lb2 || !out_sq2 || !picks || nr <= 0 || nt <= 0 || n_angles <= 0)
         return set_error(MM_ERR_INVALID, "mm_bound_state: bad arguments");
-    MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
-    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
-    opts.bound_min_candidates = 0; opts.bound_matrix = matrix != 0;
+    opts.bound_matrix = matrix != 0;
     Plan plan;
-    int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
+    int rc = stage_single(e, plan, SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}, flags, angles, n_angles,
+                          MM_PRECISION_F32_BOUNDED, opts);
     if (rc) return rc;
-    if (!plan.use_lb || (matrix != 0) != (plan.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_bound_state: the bound kernel asked for does not take these sets");
+    if (!plan.lv.use_lb || (matrix != 0) != (plan.lv.kept_nct > 0)) return set_error(MM_ERR_INVALID, "mm_bound_state: the bound kernel asked for does not take these sets");
     if ((rc = plan.run(true))) return rc;
     MM_HIP(hipMemcpyAsync(out_lb2, plan.dev.lb32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipMemcpyAsync(out_sq2, plan.dev.sq32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipMemcpyAsync(picks, plan.dev.pick_idx, 4, hipMemcpyDeviceToHost, plan.stream));                 // pick_idx[0]
-    MM_HIP(hipMemcpyAsync(picks + 1, plan.dev.pick_idx + plan.P, 4, hipMemcpyDeviceToHost, plan.stream));    // pick_idx[P]
+    MM_HIP(hipMemcpyAsync(picks + 1, plan.dev.pick_idx + plan.lv.P, 4, hipMemcpyDeviceToHost, plan.stream));    // pick_idx[P]
     MM_HIP(hipStreamSynchronize(plan.stream));
-    if (e2) *e2 = plan.host_pairs[0].e2;
-    if (delta) *delta = plan.host_pairs[0].delta;
+    if (e2) *e2 = plan.lv.host_pairs[0].e2;
+    if (delta) *delta = plan.lv.host_pairs[0].delta;
     return MM_OK;
 }
 
@@ -1450,28 +1067,25 @@ int mm_pick_minima(mm_engine* h, const double* rx, const double* ry, int nr, con
 {
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e || !row_min2 || !col_min2 || nr <= 0 || nt <= 0) return set_error(MM_ERR_INVALID, "mm_pick_minima: bad arguments");
-    MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}};
-    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, &angle, 1, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
-    opts.bound_min_candidates = 0; opts.bound_matrix = true;
+    opts.bound_matrix = true;
     Plan plan;
-    int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_BOUNDED, 0, INT32_MAX, false, nullptr, &opts);
+    int rc = stage_single(e, plan, SetRef{rx, ry, nr, cx, cy}, SetRef{tx, ty, nt, cx, cy}, flags, &angle, 1,
+                          MM_PRECISION_F32_BOUNDED, opts);
     if (rc) return rc;
-    if (!plan.use_lb || plan.kept_nct <= 0) return set_error(MM_ERR_INVALID, "mm_pick_minima: the matrix-pipe bounded search does not take these sets");
+    if (!plan.lv.use_lb || plan.lv.kept_nct <= 0) return set_error(MM_ERR_INVALID, "mm_pick_minima: the matrix-pipe bounded search does not take these sets");
     const WorkItem item{0, 0, 1, 0};
     const int32_t counters[8] = {0, 1, 0, 0, 0, 0, 0, 0};
     MM_HIP(hipMemcpyAsync(plan.dev.items_pick, &item, sizeof item, hipMemcpyHostToDevice, plan.stream));
     MM_HIP(hipMemcpyAsync(plan.dev.n_items, counters, sizeof counters, hipMemcpyHostToDevice, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));                     // (the sources are on this stack frame)
-    hipError_t he = launch_screen_picks(plan.dev, 0, plan.max_na, plan.max_nbp, plan.stream);
+    hipError_t he = launch_screen_picks(plan.dev, 0, plan.lv.max_na, plan.lv.max_nbp, plan.stream);
     if (he != hipSuccess) return hip_error(he, "pick kernel launch");
     MM_HIP(hipMemcpyAsync(row_min2, plan.dev.emit, (size_t)nr * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipMemcpyAsync(col_min2, plan.dev.emit + plan.dev.emit_rows, (size_t)nt * 4, hipMemcpyDeviceToHost, plan.stream));
     if (value2) MM_HIP(hipMemcpyAsync(value2, plan.dev.sq32, 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));
-    if (e2) *e2 = plan.host_pairs[0].e2;
+    if (e2) *e2 = plan.lv.host_pairs[0].e2;
     return MM_OK;
 }
 
@@ -1507,28 +1121,25 @@ int mm_screen_values_group(mm_engine* h, const double* rx, const double* ry, int
     if (!e || !rx || !ry || !tx || !ty || !angles || !out_sq2 || nr <= 0 || nt <= 0 || n_angles <= 0 || ref_main < 0 ||
         tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
         return set_error(MM_ERR_INVALID, "mm_screen_values: bad arguments");
-    MM_HIP(hipSetDevice(e->device));
-    std::vector<SetRef> sets{SetRef{rx, ry, nr, cx, cy, ref_main}, SetRef{tx, ty, nt, cx, cy, tgt_main}};
-    std::vector<PairSpec> pairs{PairSpec{0, 1, cx, cy, flags, angles, n_angles, 0.0, 0.0}};
     ScreenOptions opts = e->screen_opts;
-    opts.bound_min_candidates = 0; opts.screen_cull = cull != 0; opts.screen_group = group;
+    opts.screen_cull = cull != 0; opts.screen_group = group;
     Plan plan;
-    int rc = plan.stage_sets(e, sets, true);
-    if (!rc) rc = plan.stage_level(pairs, MM_PRECISION_F32_MATRIX, 0, INT32_MAX, false, nullptr, &opts);
+    int rc = stage_single(e, plan, SetRef{rx, ry, nr, cx, cy, ref_main}, SetRef{tx, ty, nt, cx, cy, tgt_main}, flags, angles, n_angles,
+                          MM_PRECISION_F32_MATRIX, opts);
     if (rc) return rc;
-    if (n_items) *n_items = plan.W;
-    for (int k = 0; items && k < plan.W && k < items_cap; ++k) {
-        const WorkItem& w = plan.host_work[(size_t)k];
+    if (n_items) *n_items = plan.lv.W;
+    for (int k = 0; items && k < plan.lv.W && k < items_cap; ++k) {
+        const WorkItem& w = plan.lv.host_work[(size_t)k];
         items[3 * k] = w.a0; items[3 * k + 1] = w.cnt; items[3 * k + 2] = std::max(w.pad, 1);
     }
-    bool ok = plan.A == n_angles && !plan.groups.empty();
-    for (const Plan::ScreenGroup& g : plan.groups)
+    bool ok = plan.lv.A == n_angles && !plan.lv.groups.empty();
+    for (const ScreenGroup& g : plan.lv.groups)
         ok = ok && (g.screen == Screen::Matrix || g.screen == Screen::MatrixCull) && mx_cull_takes(g.nct, g.multi, g.a_cap);
     if (!ok) return set_error(MM_ERR_INVALID, "mm_screen_values: these sets do not take the matrix-pipe screen in one block");
     if ((rc = plan.run(true))) return rc;
     MM_HIP(hipMemcpyAsync(out_sq2, plan.dev.sq32, (size_t)n_angles * 4, hipMemcpyDeviceToHost, plan.stream));
     MM_HIP(hipStreamSynchronize(plan.stream));
-    if (e2) *e2 = plan.host_pairs[0].e2;
+    if (e2) *e2 = plan.lv.host_pairs[0].e2;
     return MM_OK;
 }
 
@@ -1538,6 +1149,50 @@ int mm_screen_group_auto(const double* angles, int n)
 {
     if (!angles || n < 1) return set_error(MM_ERR_INVALID, "mm_screen_group_auto: bad arguments");
     return mm_tile_group_auto(angles, n);
+}
+
+// TEST HOOK (host only, no engine, no device): the level plan_level decides for these sets, pairs and switches, as words.
+int mm_level_plan_probe(int n_sets, const int32_t* set_len, const double* set_rho, const int32_t* set_main, int n_pairs,
+                        const int32_t* ref_set, const int32_t* tgt_set, const double* cx, const double* cy, const int32_t* flags,
+                        const int32_t* list_of, int n_lists, const int64_t* list_off, const double* angles, const double* tie_tol,
+                        const double* delta_extra, const int32_t* slice_begin, const int32_t* slice_end, int precision,
+                        int32_t angle_begin, int32_t angle_end, int want_costs, int64_t bound_min_candidates, int bound_matrix,
+                        int bound_matrix_qt, int bound_matrix_nc, int screen_cull, int screen_split, int screen_group,
+                        int64_t* out, int64_t cap, int64_t* n_words)
+{
+    if (n_sets < 0 || n_pairs < 0 || n_lists < 0 || !n_words || cap < 0 || (cap > 0 && !out) ||
+        (n_sets > 0 && (!set_len || !set_rho || !set_main)) || (n_lists > 0 && !list_off) ||
+        (n_pairs > 0 && (!ref_set || !tgt_set || !cx || !cy || !flags || !list_of || !tie_tol || !delta_extra || !slice_begin || !slice_end)))
+        return set_error(MM_ERR_INVALID, "mm_level_plan_probe: bad arguments");
+    if (n_lists > 0 && (!offsets_ok(list_off, n_lists) || (list_off[n_lists] > 0 && !angles)))
+        return set_error(MM_ERR_INVALID, "mm_level_plan_probe: bad candidate lists");
+    std::vector<int32_t> off((size_t)n_sets), len(set_len, set_len + n_sets), main_(set_main, set_main + n_sets);
+    std::vector<double> rho(set_rho, set_rho + n_sets);
+    int64_t at = 0;
+    for (int s = 0; s < n_sets; ++s) {
+        if (len[(size_t)s] < 0 || at + len[(size_t)s] > INT32_MAX) return set_error(MM_ERR_INVALID, "mm_level_plan_probe: bad set sizes");
+        off[(size_t)s] = (int32_t)at; at += len[(size_t)s];
+    }
+    std::vector<PairSpec> pairs((size_t)n_pairs);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int k = list_of[p];
+        if (k < 0 || k >= n_lists || list_off[k + 1] - list_off[k] > INT32_MAX)
+            return set_error(MM_ERR_INVALID, "mm_level_plan_probe: pair names a list that does not exist");
+        pairs[(size_t)p] = PairSpec{ref_set[p], tgt_set[p], cx[p], cy[p], flags[p], angles + list_off[k], (int32_t)(list_off[k + 1] - list_off[k]),
+                                    tie_tol[p], delta_extra[p], slice_begin[p], slice_end[p]};
+    }
+    ScreenOptions opts;
+    opts.bound_min_candidates = bound_min_candidates; opts.bound_matrix = bound_matrix != 0;
+    opts.bound_matrix_qt = bound_matrix_qt; opts.bound_matrix_nc = bound_matrix_nc;
+    opts.screen_cull = screen_cull != 0; opts.screen_split = screen_split != 0; opts.screen_group = screen_group;
+    LevelPlan lp;
+    const int rc = plan_level(off, len, rho, main_, pairs, precision, angle_begin, angle_end, want_costs != 0, opts, lp);
+    if (rc) return rc;
+    std::vector<int64_t> words;
+    serialize_level_plan(lp, words);
+    *n_words = (int64_t)words.size();
+    if ((int64_t)words.size() <= cap) std::copy(words.begin(), words.end(), out);
+    return MM_OK;
 }
 
 // TEST HOOK (host only, no device): the culled screen's tile bound (mm_tile_bound.h) for the f32 point sets (rx, ry) and
@@ -1806,10 +1461,10 @@ int mm_plan_fetch(mm_plan* h, int32_t* best_idx, double* best_angle, double* bes
     Plan& plan = p->plan;
     MM_HIP(hipSetDevice(plan.eng->device));
     BatchResult res;
-    std::vector<double> costs(all_costs ? (size_t)plan.A : 0);
+    std::vector<double> costs(all_costs ? (size_t)plan.lv.A : 0);
     int rc = plan.fetch(res, all_costs ? costs.data() : nullptr);
     if (rc) return rc;
-    for (int q = 0; q < plan.P; ++q) {
+    for (int q = 0; q < plan.lv.P; ++q) {
         if (best_idx) best_idx[q] = res.best_idx[q];
         if (best_cost) best_cost[q] = res.best_cost[q];
         if (n_rescored) n_rescored[q] = res.n_rescored[q];
@@ -1856,8 +1511,8 @@ int mm_plan_stats(mm_plan* h, int64_t* n_candidates, double* pair_evals, int64_t
 {
     PlanHandle* p = reinterpret_cast<PlanHandle*>(h);
     if (!p) return set_error(MM_ERR_INVALID, "plan == NULL");
-    if (n_candidates) *n_candidates = p->plan.A;
-    if (pair_evals) *pair_evals = p->plan.pair_evals;
+    if (n_candidates) *n_candidates = p->plan.lv.A;
+    if (pair_evals) *pair_evals = p->plan.lv.pair_evals;
     if (hbm_bytes) *hbm_bytes = (int64_t)p->plan.hbm_bytes();
     return MM_OK;
 }

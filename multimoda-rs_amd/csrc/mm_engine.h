@@ -11,11 +11,11 @@
 
 #include "../../include/mm_hausdorff.h"
 #include "mm_device.h"
+#include "mm_level_plan.h"
 
 namespace mm {
 
 extern thread_local std::string g_last_error;
-int set_error(int code, const std::string& msg);
 int hip_error(hipError_t e, const char* what);
 // n + 1 CSR offsets of a batch of jobs: they start at 0 and do not decrease
 inline bool offsets_ok(const int64_t* off, int n)
@@ -25,21 +25,6 @@ inline bool offsets_ok(const int64_t* off, int n)
         if (off[j + 1] < off[j]) return false;
     return true;
 }
-
-// The switches that choose a level's screens.  The engine holds the defaults (mm_engine_set_*); Plan::stage_level copies
-// them into the plan, and everything from there on -- the screen of every pair, the device description, run() -- reads
-// the plan's copy.
-struct ScreenOptions {
-    int64_t bound_min_candidates = 16384;   // MM_PRECISION_F32_BOUNDED: smaller batches skip the bound rounds
-    bool bound_matrix = true;               // MM_PRECISION_F32_BOUNDED: bounds, picks and survivors on the matrix pipe
-    int bound_matrix_qt = 1, bound_matrix_nc = 1;   // k_bound_mx's variant: query tiles per side, candidates per wave
-    bool screen_cull = true;                // MM_PRECISION_F32_MATRIX: sets of 64 .. 544 points through k_screen_mx_cull
-    bool screen_split = true;               // k_screen_mx_cull: a set of two runs (lumen ++ catheter) gives each run tiles of its
-                                            // own where that adds no tile (PairDesc::ref_main / tgt_main)
-    int screen_group = 0;                   // k_screen_mx_cull: consecutive candidates that share one tile bound and mask set
-                                            // (WorkItem::pad).  0: chosen per pair from its list (mm_tile_group_auto), never
-                                            // more than a quarter of a work item; 1: off; 2 | 4 | 8: forced
-};
 
 // One device + one stream + grow-only staging buffers (pinned host, device) reused by the
 // transient plans behind mm_best_rotation_batch, so the per-call cost in the sequential
@@ -115,15 +100,6 @@ struct SetRef {            // one point set: SoA f64 as given + the centre its f
     const double* x; const double* y; int32_t n; double cx, cy;
     int32_t main = 0;      // > 0: the set is two runs, `main` points and then the rest (Plan::set_main)
 };
-struct PairSpec {          // one search
-    int32_t ref_set, tgt_set;      // indices into the set list
-    double cx, cy;                 // rotation centre (must equal the centre of both sets' f32 copies)
-    int32_t flags;
-    const double* angles; int32_t n_angles;   // candidate list (pairs passing the same pointer share tables)
-    double tie_tol;                // near-tie tolerance on the exact cost (0 -> exact ties only)
-    double delta_extra;            // added to the f32 screening bound
-    int32_t slice_begin = 0, slice_end = INT32_MAX;   // this pair's share of the candidate axis
-};
 struct Comm;               // mm_comm.cpp: the RCCL communicator behind mm_comm_*
 
 struct BatchResult {
@@ -131,18 +107,12 @@ struct BatchResult {
     std::vector<double> best_cost;
 };
 
-// The screen of a pair searched without bound rounds, in the order the work list lays out its groups: none (a set of fewer
-// than 64 points: every candidate is scored exactly), direct-form f32, packed FMA, the matrix pipe (k_screen_mx), the
-// matrix pipe without the tiles that hold no minimum (k_screen_mx_cull).
-enum class Screen { None, Direct, PackedFma, Matrix, MatrixCull };
-
 // A staged batch: point pool (uploaded once) + a re-stageable level (descriptors, candidate
 // tables, outputs).  Transient plans borrow the engine's grow-only buffers.
 struct Plan {
     Engine* eng = nullptr;
     bool transient = false;
     hipStream_t stream = nullptr;   // run / fetch: the engine's aux stream for transient plans, its main stream otherwise
-    int precision = MM_PRECISION_F32;
     // sets
     std::vector<int32_t> set_off, set_len;
     std::vector<double> set_rho;   // max distance of a point from the set's centre
@@ -151,41 +121,10 @@ struct Plan {
     int64_t n_points = 0;
     unsigned char* pts_blob = nullptr; size_t pts_bytes = 0; bool own_pts = false; size_t pts_cap = 0;
     size_t o32x = 0, o32y = 0, o64x = 0, o64y = 0;   // planes of the pool inside pts_blob
-    // level
-    int P = 0, W = 0;
-    int64_t A = 0;            // candidates in this plan (sum of slices)
-    int64_t T = 0;            // cos/sin table entries
-    int max_na = 1, max_nbp = 16;
-    double pair_evals = 0.0;
+    // level: what plan_level decided (mm_level_plan.h), the blob it is staged in and the device's view of it
+    LevelPlan lv;
     unsigned char* lvl_blob = nullptr; size_t lvl_cap = 0; bool own_lvl = false;
-    size_t lvl_in_bytes = 0, lvl_bytes = 0;
-    size_t off_best_cost = 0, res_bytes = 0, off_all_costs = 0;
-    size_t r_best_idx = 0, r_n_rescored = 0, r_near_cnt = 0, r_near_idx = 0;  // offsets inside the result block
-    int32_t slice_end = INT32_MAX;
     BatchDev dev{};
-    std::vector<PairDesc> host_pairs;
-    std::vector<WorkItem> host_work;
-    std::vector<double> host_tables;          // distinct candidate lists (slice-local), dev tables mirror them
-    std::vector<uint8_t> trivial;             // pair has an empty set: every cost is 0.0
-    bool want_costs = false;
-    bool use_fast = false;                    // expanded-form screening kernel selected
-    ScreenOptions opts;                       // the switches this level was staged with
-    // Screens without bound rounds: the work list is grouped by screen, one launch per group, in the order of Screen and
-    // (multi, nct, cls).  Matrix / MatrixCull: k_screen_mx<nct, multi> / k_screen_mx_cull<nct> with LDS for a_cap row tiles;
-    // candidates and tiles_full (MatrixCull: the tiles the full kernel computes) feed Engine::screened / cull_tiles_full.
-    struct ScreenGroup {
-        Screen screen; int nct, multi, a_cap, work_begin, work_count;
-        int64_t candidates, tiles_full;
-    };
-    std::vector<ScreenGroup> groups;
-    bool use_lb = false;                      // lower-bound pass in front of the screen (MM_PRECISION_F32_BOUNDED)
-    int W_lb = 0, lb_stride = 0, lb_runs_cap = 0, max_nt = 1;
-    // bounded search on the matrix pipe (kept_nct > 0): row tiles of k_bound_mx's LDS layout, k_screen_mx's variant for the
-    // picks and the survivors and its LDS cap (BatchDev::lb_mx, kept_mx_*)
-    int lb_mx_tiles = 0, kept_nct = 0, kept_acap = 0;
-    double lb_pair_evals = 0.0;               // pair-distances of the first bound round
-    int64_t lb_sparse_total = 0;              // candidates the first bound round scores
-    std::vector<WorkItem> host_work_lb;
 
     // pool layout + allocation for sets of the given sizes, no data (the caller fills it on the device and
     // sets set_rho); stage_sets = alloc_pool + host conversion + one H2D copy
@@ -195,12 +134,12 @@ struct Plan {
     // `opts` (nullable -> the engine's current switches): what the level is staged with
     int stage_level(const std::vector<PairSpec>& pairs, int precision, int32_t angle_begin, int32_t angle_end,
                     bool want_costs, hipStream_t st = nullptr, const ScreenOptions* opts = nullptr);
+    void bind_level();        // dev from lv.lay and lvl_blob
     int run(bool screen_only);
     int mark_search_done();   // resident plans: record Engine::search_done behind the dominant kernel
     int fetch(BatchResult& out, double* all_costs_plan_order);
-    size_t hbm_bytes() const { return pts_bytes + lvl_bytes; }
-    std::vector<int32_t> pair_slice_end;      // per pair: end of the candidate slice this plan owns
-    int32_t slice_hi(int p) const { return pair_slice_end[(size_t)p]; }
+    size_t hbm_bytes() const { return pts_bytes + lv.lay.lvl_bytes; }
+    int32_t slice_hi(int p) const { return lv.pair_slice_end[(size_t)p]; }
     double angle_of(int p, int32_t idx) const;
     ~Plan();
 };

@@ -34,6 +34,7 @@
 #include <cstdio>
 
 #include "mm_device.h"
+#include "mm_screen_limits.h"
 #include "mm_xcd.h"
 #include "../../include/mm_hausdorff.h"
 
@@ -538,7 +539,7 @@ k_screen_fast(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ w
 // and computes all 17 x 17 tiles of each: column fragments written to a wave-private LDS copy and read from there ONCE, into
 // accumulation registers (every MFMA of a column tile takes its B operand from a[4t : 4t + 3]), column minima in registers
 // for the whole candidate, row minima across the 32 column lanes through a wave-private LDS transpose (or, for small sets,
-// in-lane from a second, transposed MFMA per tile: the DUAL form) -- no barrier and no shared accumulator in the candidate loop.  Error of the screened value: PairDesc::e2 = mx_e2(rho_a, rho_b) (mm_engine.cpp).
+// in-lane from a second, transposed MFMA per tile: the DUAL form) -- no barrier and no shared accumulator in the candidate loop.  Error of the screened value: PairDesc::e2 = mx_e2(rho_a, rho_b) (mm_level_plan.cpp).
 // Set sizes: the column-tile count NCT (target set, <= 17 per block) is a template parameter -- the column minima live in
 // one register per column tile -- and the row-tile count (reference set) is a run-time operand of the asm block; a target
 // set of more than 544 points is cut into equal blocks of NCT tiles (MULTI: the row minima are carried from block to block
@@ -550,10 +551,13 @@ k_screen_fast(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ w
 
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
-static constexpr int MX_TMAX = MM_SCREEN_MX_NCT_MAX;          // column tiles of one block
-static constexpr int MX_ROW_TILES_MAX = 64;                     // row tiles (LDS: 1 KB of fragments per row tile)
-static constexpr int MX_RED = 32 * (MM_SCREEN_MX_RED_STRIDE / 4);   // ints of one wave's reduction scratch
-static constexpr int MX_ITEM = 64;                              // candidates of one work item, at most (the engine's apb)
+// the limits the engine plans with (mm_screen_limits.h) are the ones the generated asm blocks were written for
+static_assert(MM_SCREEN_MX_NCT_MIN == kMxNctMin && MM_SCREEN_MX_NCT_MAX == kMxNctMax && MM_SCREEN_MX_RED_STRIDE == kMxRedStride,
+              "mm_screen_limits.h and mm_screen_mx_asm.inc disagree");
+static constexpr int MX_TMAX = kMxNctMax;                      // column tiles of one block
+static constexpr int MX_ROW_TILES_MAX = kMxRowTilesMax;        // row tiles (LDS: 1 KB of fragments per row tile)
+static constexpr int MX_RED = 32 * (kMxRedStride / 4);         // ints of one wave's reduction scratch
+static constexpr int MX_ITEM = kMxItemMax;                     // candidates of one work item, at most (the engine's apb)
 
 static __device__ __forceinline__ void mx_split(float X, _Float16& h, _Float16& l)
 {
@@ -903,12 +907,6 @@ static hipError_t launch_mx_emit(const BatchDev& b, const WorkItem* work, const 
 #undef MM_MXE
 }
 
-size_t lds_bytes_mx(int nct, bool multi, int a_cap, int waves)
-{
-    return (size_t)a_cap * 64 * 16 + (size_t)waves * nct * 64 * 8 + (size_t)waves * MX_RED * 4 +
-           (multi ? (size_t)waves * a_cap * 32 * 4 : 0) + (size_t)MX_ITEM * 12;
-}
-
 // n_dev == nullptr: one workgroup per item of the host-built list; else a device queue of at most `cap` items whose length is
 // *n_dev (a bounded grid strides over it)
 // waves: 4, or 1 for a queue of single candidates (the picks of a bounded search).  sel: see the kernel.
@@ -936,15 +934,6 @@ static hipError_t launch_mx_t(const BatchDev& b, const WorkItem* work, int n_wor
     return hipGetLastError();
 }
 
-// the variant for a target set of nb points: column tiles per block, and whether the set takes several blocks
-void mx_variant(int nb, int* nct, int* multi)
-{
-    const int nbt = (nb + 31) / 32;
-    if (nbt <= MX_TMAX) { *nct = nbt < MM_SCREEN_MX_NCT_MIN ? MM_SCREEN_MX_NCT_MIN : nbt; *multi = 0; return; }
-    const int nblk = (nbt + MX_TMAX - 1) / MX_TMAX;
-    *nct = (nbt + nblk - 1) / nblk; *multi = 1;
-}
-
 // work[0 .. n_work) of b.work + work_begin: items of pairs that all take the variant (nct, multi); a_cap >= their row tiles
 static hipError_t launch_mx_any(const BatchDev& b, const WorkItem* w, int n_work, const int* n_dev, int cap, int nct, int multi, int a_cap,
                                 hipStream_t s, int waves = 4, const int32_t* sel = nullptr)
@@ -966,8 +955,6 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
     if (n_work <= 0) return hipSuccess;
     return launch_mx_any(b, b.work + work_begin, n_work, nullptr, 0, nct, multi, a_cap, s);
 }
-int mx_min_points() { return 64; }
-int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 
 // -------------------------------------------------------------------------------------
 // k_screen_mx_cull<NCT>: k_screen_mx<NCT, false> (sets of 64 .. 544 points, the whole target set per wave) without the tiles
@@ -1026,12 +1013,8 @@ int mx_max_points() { return MX_ROW_TILES_MAX * 32; }
 // -------------------------------------------------------------------------------------
 typedef float f16x16 __attribute__((ext_vector_type(16)));
 
-static constexpr int MXC_ROW_TILES_MAX = 17;
-// Column tiles from which the culled screen loops over the set mask bits; below it keeps the bit-test chain and one tile
-// pair per lane.  The static budget (profiles/r6_cull_isa_budget.txt) has the loop cheaper from 9 column tiles on (a register
-// vector of fewer is indexed by compare and select) and dearer below; on the device it was measured to win at 17 and to lose
-// on the small launches at 16 (profiles/r6_config3_cull_kernel_stats.csv), so only 17 takes it.
-static constexpr int MXC_SETBIT_MIN_NCT = 17;
+static constexpr int MXC_ROW_TILES_MAX = kMxCullRowTilesMax;
+static constexpr int MXC_SETBIT_MIN_NCT = kMxCullSetbitMinNct;   // from here on the culled screen loops over the set mask bits
 
 static __device__ __forceinline__ int min3i(int a, int b, int c) { return min(a, min(b, c)); }
 
@@ -1130,12 +1113,6 @@ static __device__ __forceinline__ void mxc_tiles_chain(unsigned mask, const h8v&
     }
 }
 
-size_t lds_bytes_mx_cull(int nct, int a_cap)
-{
-    return (size_t)a_cap * 64 * 16 + (size_t)4 * nct * 64 * 8 + (size_t)4 * a_cap * 32 * 4 * 2 + (size_t)(nct + a_cap) * 16 +
-           (size_t)MX_ITEM * 12;
-}
-
 template <int NCT>
 __global__ void __launch_bounds__(256, 2)
 k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work, int a_cap,
@@ -1177,7 +1154,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
             s_cs[t] = (t & 1) ? sinv[pd.tab_off + a] : cosv[pd.tab_off + a];
             if (!(t & 1)) s_ci[t >> 1] = a;
         }
-        // a split set (ref_main / tgt_main > 0, Plan::stage_level): its two runs tile by tile, here and in the circles
+        // a split set (ref_main / tgt_main > 0, plan_level): its two runs tile by tile, here and in the circles
         mx_stage_rows<64 * WAVES>(s_a, nrt, na, ptx + pd.ref_off, pty + pd.ref_off, S, tid, pd.ref_main);
         float tx[NQ], ty[NQ];
 #pragma unroll
@@ -1615,13 +1592,6 @@ static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int 
     return hipGetLastError();
 }
 
-bool mx_cull_takes(int nct, int multi, int a_cap)
-{
-    return !multi && nct >= MM_SCREEN_MX_NCT_MIN && nct <= MX_TMAX && a_cap >= 1 && a_cap <= MXC_ROW_TILES_MAX;
-}
-
-int mx_cull_group_max(int nct) { return nct >= MXC_SETBIT_MIN_NCT && nct <= MX_TMAX ? 8 : 1; }
-
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
                                  hipStream_t s)
 {
@@ -1660,7 +1630,7 @@ hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, 
 // (24 u (rho_r + rho_t)) covers both.  (Tried: two candidates per wave sharing every LDS read -- 20 % fewer
 // instructions, 202 instead of 146 VGPRs, one wave per SIMD less: no gain.)
 // -------------------------------------------------------------------------------------
-static constexpr int kLbRP = 5;   // row PAIRS per row group: query sets up to 8 * kLbRP points
+static constexpr int kLbRP = kLbRowPairs;   // row PAIRS per row group: query sets up to 8 * kLbRP points
 
 static __device__ __forceinline__ float fmin3_f32(float a, float b, float c)
 {
@@ -2063,10 +2033,10 @@ k_bound_mx_scan(const PairDesc* __restrict__ pairs, int n_pairs, int split, cons
     }
 }
 
-static constexpr int kLbCandStep = 8;   // first round: every 8th candidate (and the last) gets a bound
+static constexpr int kLbCandStep = kLbCandidateStep;   // first round: every 8th candidate (and the last) gets a bound
 
 // number of candidates the sparse first round scores for a list of n: 0, 8, 16, ... and n - 1
-static __host__ __device__ __forceinline__ int lb_sparse_count(int n) { return n <= 0 ? 0 : (n - 1 + kLbCandStep - 1) / kLbCandStep + 1; }
+static __host__ __device__ __forceinline__ int lb_sparse_count(int n) { return lb_sparse_candidates(n); }
 
 // Per pair: among the candidates scored by the sparse round, the one with the smallest bound
 // (first one on ties) is queued for a full screen evaluation; its value is the pair's upper bound.
@@ -2233,6 +2203,7 @@ k_lb_keep_mx(const PairDesc* __restrict__ pairs, const float* __restrict__ lb32,
 // queries is almost exact where the optimum lies.  Sets with fewer points repeat their last choice.
 static constexpr int kLbListRP = 1;
 static constexpr int kLbListQ = 8 * kLbListRP;
+static_assert(kLbListQ == kLbListQueries, "mm_screen_limits.h: the level reserves kLbListQueries entries per pair and side");
 
 // One WAVE per (pair, side) -- four of them per workgroup: a lane scans its share of the minima, the wave agrees on the
 // largest value (first index among equals) with two DPP reductions per choice.  (Round 3's version gave a side to a
@@ -2545,13 +2516,6 @@ int large_rows_per_block() { return 16 * kLargeR; }
 // -------------------------------------------------------------------------------------
 // launch helpers
 // -------------------------------------------------------------------------------------
-static constexpr int LDS_CAP = 160 * 1024 - 256;
-
-size_t lds_bytes_f32(int nbp) { return (size_t)nbp * (8 + 8 + 4) + 16; }
-size_t lds_bytes_f64(int nbp) { return (size_t)nbp * (16 + 16 + 8) + 16; }
-int max_target_points_f32() { return ((LDS_CAP - 16) / 20) & ~15; }
-int max_target_points_f64() { return ((LDS_CAP - 16) / 40) & ~15; }
-
 template <typename T, int R, int NLI, bool EXACT, bool MULTI_RB, int MINB = 1>
 static hipError_t launch_one(const BatchDev& b, const WorkItem* work, int n_work, const int* n_work_dev,
                              int grid, size_t lds, const T* px, const T* py,
@@ -2587,10 +2551,6 @@ hipError_t launch_screen_f32(const BatchDev& b, int max_na, int max_nbp, hipStre
     return MM_F32(32, true);
 #undef MM_F32
 }
-
-size_t lds_bytes_fast(int nbp) { return (size_t)nbp * (16 + 8 + 4) + 16; }
-int max_rows_fast() { return 16 * 33; }
-int max_target_points_fast() { return ((LDS_CAP - 16) / 28) & ~15; }
 
 // Work from the host-built table (n_dev == nullptr: one workgroup per item -- a persistent grid
 // measured slower on the big launch) or from a device queue of at most `cap` items whose length is
@@ -2629,12 +2589,6 @@ hipError_t launch_screen_fast(const BatchDev& b, int max_na, int max_nbp, hipStr
 }
 
 // ---- bounded screen (k_screen_lb -> pick -> screen the picks -> keep -> screen the survivors) ----
-int lb_max_query_points() { return 8 * kLbRP; }
-int lb_max_points() { return 4096; }
-size_t lds_bytes_lb(int nap, int nbp) { return ((size_t)nap + (size_t)nbp) * 16; }
-
-int lb_mx_max_points() { return 1024; }     // 32 row tiles per set: 64 KB of row fragments
-
 // the bounded search runs on the matrix pipe: bounds from k_bound_mx, survivors from k_lb_keep_mx, picks and survivors
 // screened by k_screen_mx<kept_mx_nct, false>
 static bool lb_matrix(const BatchDev& b) { return b.kept_mx_nct > 0; }
@@ -2681,10 +2635,6 @@ static hipError_t launch_lb_t(const BatchDev& b, const WorkItem* work, int n_hos
                        b.p32x, b.p32y, b.cos32, b.sin32, b.lb32);
     return hipGetLastError();
 }
-
-int lb_candidate_step() { return kLbCandStep; }
-int lb_sparse_candidates(int n) { return lb_sparse_count(n); }
-int lb_list_queries() { return kLbListQ; }
 
 // round 1: every kLbCandStep-th candidate and the last one (host work list)
 hipError_t launch_screen_lb(const BatchDev& b, int max_nap, int max_nbp, hipStream_t s)

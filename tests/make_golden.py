@@ -13,6 +13,11 @@ Floats are stored as hex strings (bit-exact).  Run:
 plans of the pruned searches return (mm.ccta.nn_plan, surface.tri_plan) -- permutations, items, bounds, info -- on the
 inputs of tests/test_nn_plan_host.py and of the plan tests of tests/test_surface_host.py.  It pins order, ties and
 every bit of every bound; record it at the commit whose plans are to be kept (tests/test_prune_plan_golden.py compares).
+
+`python tests/make_golden.py level_plans` rewrites tests/golden/level_plans.json from ITSELF: every case's stored inputs go
+through mm_level_plan_probe (the search engine's level planner, no device) and the plan is written back in the file's
+format.  The file was recorded from the engine's staging code before the planner was cut out of it, so a run that changes
+a byte of it shows a planning decision that moved (tests/test_level_plan_golden.py compares case by case).
 """
 import hashlib
 import json
@@ -119,5 +124,124 @@ def main_prune_plans():
     print("wrote", path)
 
 
+# ---- level plans: the words of mm_level_plan_probe (include/mm_hausdorff.h) and the file that pins them ----
+LEVEL_HEADER = ["precision", "P", "W", "W_lb", "A", "T", "max_na", "max_nbp", "max_nt", "use_fast", "use_lb", "lb_stride",
+                "lb_runs_cap", "lb_mx_tiles", "kept_nct", "kept_acap", "pair_evals", "lb_pair_evals", "lb_sparse_total",
+                "slice_end", "want_costs", "bound_min_candidates", "bound_matrix", "bound_matrix_qt", "bound_matrix_nc",
+                "screen_cull", "screen_split", "screen_group"]
+LEVEL_LAYOUT = ["pairs", "work", "work_lb", "cos32", "sin32", "cos64", "sin64", "ang64", "sq32", "sq64", "flag", "items",
+                "n_items", "lb32", "pick", "items_pick", "items_lb", "klist", "emit", "qlist", "best_cost", "best_idx",
+                "n_rescored", "near_cnt", "near_idx", "lvl_in_bytes", "lvl_bytes", "off_best_cost", "res_bytes",
+                "off_all_costs", "r_best_idx", "r_n_rescored", "r_near_cnt", "r_near_idx", "emit_rows", "emit_cols"]
+LEVEL_GROUP = ["screen", "nct", "multi", "a_cap", "work_begin", "work_count", "candidates", "tiles_full"]
+LEVEL_PAIR_WORDS = 22          # PairDesc's 20 fields, trivial, pair_slice_end; ref_main / tgt_main are words 12, 13
+LEVEL_OPTS = LEVEL_HEADER[21:]
+LEVEL_F64_INPUTS = ["set_rho", "cx", "cy", "tie_tol", "delta_extra"]       # stored as the hex of their little-endian bytes
+LEVEL_I32_INPUTS = ["set_len", "set_main", "ref_set", "tgt_set", "flags", "list_of", "slice_begin", "slice_end"]
+
+
+def _f64_hex(a):
+    """f64 values as the hex of their little-endian bytes; a run of one value as {"fill": hex, "n": count}."""
+    b = np.ascontiguousarray(a, dtype="<f8").tobytes()
+    return {"fill": b[:8].hex(), "n": len(b) // 8} if len(b) > 8 and b == b[:8] * (len(b) // 8) else b.hex()
+
+
+def _f64_unhex(h):
+    if isinstance(h, dict):
+        return np.frombuffer(bytes.fromhex(h["fill"]) * h["n"], dtype="<f8").copy()
+    return np.frombuffer(bytes.fromhex(h), dtype="<f8").copy()
+
+
+def _i32_pack(a):
+    a = [int(v) for v in a]
+    return {"fill": a[0], "n": len(a)} if len(a) > 1 and a == a[:1] * len(a) else a
+
+
+def _i32_unpack(v):
+    return np.full(v["n"], v["fill"], dtype=np.int32) if isinstance(v, dict) else np.ascontiguousarray(v, dtype=np.int32)
+
+
+def _bits_f64(word):
+    return float(np.array([word], dtype=np.int64).view(np.float64)[0])
+
+
+def level_plan_arrays(words):
+    """The seven arrays of mm_level_plan_probe's words (each preceded by its length), as int64 arrays."""
+    words = np.asarray(words, dtype=np.int64)
+    out, at = [], 0
+    for _ in range(7):
+        n = int(words[at])
+        out.append(words[at + 1:at + 1 + n])
+        at += 1 + n
+    assert at == len(words), (at, len(words))
+    return out
+
+
+def level_plan_entry(inputs, words):
+    """One case of level_plans.json: the inputs as stored, header / layout / groups readably, a sha256 for the rest, and
+    what the hashed arrays show of the branches taken: the work items' pads, the pairs' ref_main / tgt_main, the trivial pairs."""
+    header, layout, pairs, tables, work, work_lb, groups = level_plan_arrays(words)
+    assert len(header) == len(LEVEL_HEADER) and len(layout) == len(LEVEL_LAYOUT) and len(groups) % len(LEVEL_GROUP) == 0
+    assert len(pairs) == LEVEL_PAIR_WORDS * int(header[1])
+    head = {k: int(v) for k, v in zip(LEVEL_HEADER, header)}
+    for k in ("pair_evals", "lb_pair_evals"):
+        head[k] = hexf(_bits_f64(head[k]))
+    sha = {k: hashlib.sha256(np.ascontiguousarray(a, dtype="<i8").tobytes()).hexdigest()
+           for k, a in (("pairs", pairs), ("tables", tables), ("work", work), ("work_lb", work_lb))}
+    split = pairs.reshape(-1, LEVEL_PAIR_WORDS)[:, 12:14]
+    return {"in": inputs, "header": head, "layout": {k: int(v) for k, v in zip(LEVEL_LAYOUT, layout)},
+            "groups": [{k: int(v) for k, v in zip(LEVEL_GROUP, g)} for g in groups.reshape(-1, len(LEVEL_GROUP))],
+            "pads": sorted({int(v) for v in work[3::4]}), "mains": sorted({int(v) for v in split.ravel()}),
+            "trivial": int(pairs.reshape(-1, LEVEL_PAIR_WORDS)[:, 20].sum()), "sha256": sha}
+
+
+def level_plan_probe(inputs, lists):
+    """mm_level_plan_probe on one case's stored inputs; `lists`: the file's pool of candidate lists (name -> hex)."""
+    import ctypes as C
+    import multimoda_rs_amd as mm
+    L = mm._native.lib()
+    f64 = {k: _f64_unhex(inputs[k]) for k in LEVEL_F64_INPUTS}
+    i32 = {k: _i32_unpack(inputs[k]) for k in LEVEL_I32_INPUTS}
+    pool = [_f64_unhex(lists[name]) for name in inputs["lists"]]
+    off = np.zeros(len(pool) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(a) for a in pool])
+    angles = np.concatenate(pool + [np.zeros(1)])
+
+    def ptr(a):
+        return a.ctypes.data_as(C.c_void_p)
+
+    def call(out, cap, n):
+        rc = L.mm_level_plan_probe(
+            len(i32["set_len"]), ptr(i32["set_len"]), ptr(f64["set_rho"]), ptr(i32["set_main"]), len(i32["ref_set"]),
+            ptr(i32["ref_set"]), ptr(i32["tgt_set"]), ptr(f64["cx"]), ptr(f64["cy"]), ptr(i32["flags"]), ptr(i32["list_of"]),
+            len(pool), ptr(off), ptr(angles), ptr(f64["tie_tol"]), ptr(f64["delta_extra"]), ptr(i32["slice_begin"]),
+            ptr(i32["slice_end"]), inputs["precision"], inputs["angle_begin"], inputs["angle_end"], inputs["want_costs"],
+            *[inputs["opts"][k] for k in LEVEL_OPTS], out, cap, C.byref(n))
+        assert rc == 0, L.mm_last_error().decode()
+
+    n = C.c_int64(0)
+    call(None, 0, n)
+    words = np.zeros(n.value, dtype=np.int64)
+    call(ptr(words), len(words), n)
+    assert n.value == len(words)
+    return words
+
+
+def dump_level_plans(doc, path):
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=None, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
+
+
+def main_level_plans():
+    path = os.path.join(GOLD, "level_plans.json")
+    with open(path) as f:
+        doc = json.load(f)
+    for name, case in doc["cases"].items():
+        doc["cases"][name] = level_plan_entry(case["in"], level_plan_probe(case["in"], doc["lists"]))
+    dump_level_plans(doc, path)
+    print("wrote", path)
+
+
 if __name__ == "__main__":
-    main_prune_plans() if sys.argv[1:] == ["prune_plans"] else main()
+    {"prune_plans": main_prune_plans, "level_plans": main_level_plans}.get(" ".join(sys.argv[1:]), main)()

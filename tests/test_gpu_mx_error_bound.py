@@ -43,7 +43,7 @@ def test_directed_search_for_the_largest_split_error(engine, oracle, mm, scale):
         assert bi == int(np.argmin(oc)) and bc == oc[bi], name           # the winner is the oracle's, always
         ra, rb = np.hypot(ref[:, 0], ref[:, 1]).max(), np.hypot(tgt[:, 0], tgt[:, 1]).max()
         rho = ra + rb
-        e2 = U * (47 * rho * rho + 6 * ra * ra + 27 * rb * rb)             # mx_e2 (csrc/mm_engine.cpp)
+        e2 = U * (47 * rho * rho + 6 * ra * ra + 27 * rb * rb)             # mx_e2 (csrc/mm_level_plan.cpp)
         delta = 24 * U * rho + 2.0 ** -49 * rho + 1e-300
         costs = np.asarray(costs)
         S = costs ** 2

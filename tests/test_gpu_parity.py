@@ -804,7 +804,7 @@ def _matrix_search_case(engine, oracle, mm, na, nb, scale, offset, step=1.0, wan
     assert bi == want and ba == angles[want] and bc == oc[want]
     ra, rb = np.sqrt(((ref - c) ** 2).sum(1)).max(), np.sqrt(((tgt - c) ** 2).sum(1)).max()
     rho = ra + rb
-    e2 = 2.0 ** -24 * (47 * rho * rho + 6 * ra * ra + 27 * rb * rb)      # mx_e2 (csrc/mm_engine.cpp)
+    e2 = 2.0 ** -24 * (47 * rho * rho + 6 * ra * ra + 27 * rb * rb)      # mx_e2 (csrc/mm_level_plan.cpp)
     delta = 24 * 2.0 ** -24 * rho + 2.0 ** -49 * (abs(c).sum() + rho) + 1e-300
     S = np.asarray(costs) ** 2
     lo = np.sqrt(np.maximum(0.0, S - e2)) - delta

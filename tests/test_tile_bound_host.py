@@ -54,7 +54,7 @@ def _check(native, ref, tgt, angles):
     rmax = max(ra, rb)
     e = 9 - int(np.frexp(rmax * (1.0 + 1e-6))[1])                     # the engine's scale exponent: radius in [256, 512)
     R = ra + rb
-    e2 = U * (47 * R * R + 6 * ra * ra + 27 * rb * rb)                   # mx_e2 (csrc/mm_engine.cpp)
+    e2 = U * (47 * R * R + 6 * ra * ra + 27 * rb * rb)                   # mx_e2 (csrc/mm_level_plan.cpp)
     S = np.float32(2.0 ** e)
     skipped = 0
     for ang in angles:
