@@ -591,7 +591,7 @@ int     mm_mesh_vertex_rings(mm_engine* e, const int64_t* faces, int64_t nf, int
 /* ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: fix_and_remesh_stitched_mesh brings the coarse CCTA
  *      triangles down to the intravascular resolution with MeshLab's isotropic remesh; of that filter this is the edge
  *      split alone; the flip is "mesh edge flips", the tangential relaxation and the reprojection "mesh relaxation" below;
- *      no collapse, no repair) ---------------------------------------------------------------------------------------
+ *      the collapse is "mesh edge collapse"; no repair) ---------------------------------------------------------------------------------------
  *
  * One pass on vertices v (f64) and triangles, with thr2 = (ratio target_len) (ratio target_len) computed once in f64:
  *   marked     the undirected edge lo < hi is marked when ((dx dx + dy dy) + dz dz) > thr2, d = v[hi] - v[lo] per
@@ -717,7 +717,7 @@ int     mm_tri_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris,
 
 /* ---- mesh relaxation (multimodars/ccta/fixing_functions.py:192-219: of MeshLab's isotropic remesh the tangential
  *      smoothing and the reprojection, smoothflag / reprojectflag / checksurfdist; the flip is "mesh edge flips" below,
- *      collapse and repair stay out) ------------------------------------------------------------------------------------
+ *      the collapse is "mesh edge collapse"; repair stays out) ----------------------------------------------------------
  * Slides the free vertices of a mesh (v, faces) along a reference surface (rv, rfaces; the mesh's own input where none is
  * given) and puts every one of them back on it exactly.  tests/mm_checkers/relax_mesh.py is the executable form.  All
  * arithmetic is unfused f64 in the order written; dot, the cross components and the closest point are those of "surface
@@ -789,7 +789,7 @@ int     mm_mesh_relax(mm_engine* e, const double* vertices_xyz, int64_t nv, cons
                       int64_t* out_ref_face, mm_relax_report* report);
 
 /* ---- mesh edge flips (multimodars/ccta/fixing_functions.py:207-219: of MeshLab's isotropic remesh the swap, swapflag;
- *      the collapse deletes vertices, needs a link condition and stays out) ---------------------------------------------
+ *      the collapse is "mesh edge collapse" below) ----------------------------------------------------------------------
  * Flips edges of a mesh (v, faces) until no single flip brings the valences closer to their targets.  No vertex moves, nv
  * and nf never change.  tests/mm_checkers/flip_edges.py is the executable form.  All f64 is unfused, in the order written;
  * len_sq is that of "mesh refinement", the cross components and dot are those of "surface distance".  One pass reads only
@@ -870,6 +870,98 @@ int     mm_mesh_valence(mm_engine* e, const double* vertices_xyz, int64_t nv, co
 int     mm_mesh_flip_edges(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
                            const uint8_t* mask, double crease_cos, double quality_keep, int64_t max_passes,
                            int64_t* out_tris, mm_flip_report* report);
+
+/* ---- mesh edge collapse (multimodars/ccta/fixing_functions.py:207-219: of MeshLab's isotropic remesh the collapse,
+ *      collapseflag; MeshLab's repair, its midpoint collapse and its checksurfdist bound stay out) ----------------------
+ * Removes the short edges of a mesh (v, faces) by half-edge collapses r -> k: r and the two faces at the edge vanish, k
+ * takes the place of r in the other faces at r, no surviving vertex moves.  The half-edge form is this project's choice,
+ * not MeshLab's (which collapses onto the midpoint): it lets no measured vertex move; quality_keep is ours too.
+ * tests/mm_checkers/collapse_edges.py is the executable form.  All f64 is unfused, in the order written; len_sq, the
+ * cross components, dot and the quality q are those of "mesh edge flips".  A NaN fails whichever comparison it meets.
+ * One pass reads only the state before it.
+ *
+ * Thresholds, each computed once: thr_min2 = (min_ratio L)(min_ratio L), thr_max2 = (max_ratio L)(max_ratio L), L =
+ * target_len; min_ratio 4/5 and max_ratio 4/3 are those of Botsch and Kobbelt and of MeshLab, as the split's 4/3 is.
+ *
+ * Edge table: the owner counts, the two owner words with their direction bits, first, deg, border and "inconsistent" are
+ * those of "mesh edge flips", over the faces still alive (a face killed by an earlier pass is not inserted; the corner ids
+ * are those of the input).  nbr(x) = the other ends of the edges lo != hi at x.
+ *
+ * Removable vertex.  r is removable when mask[r] == 0, r is not a border vertex, no edge at r is inconsistent (two owners
+ * of one direction; an (r, r) edge owned twice has both direction bits 0 and counts), and deg[r] >= 3.  Every face at a
+ * removable r holds r once, and exactly one of them traverses r -> n for every n in nbr(r).
+ *
+ * Short edge: lo < hi with len_sq(lo, hi) < thr_min2.  A direction (r -> k), {r, k} = {lo, hi}, is admissible when
+ *   (a) the edge has two owners of opposite directions, both with three distinct indices, and their opposite corners c
+ *       (of F+, which runs lo -> hi) and d (of F-) differ;
+ *   (b) r is removable -- k may be pinned or on a border: it neither moves nor vanishes;
+ *   (c) link condition: nbr(r) and nbr(k) share exactly c and d;
+ *   (d) valences after the collapse: deg[k] + deg[r] - 4 >= 3; deg[c] - 1 >= 3, >= 2 where c is a border vertex; the same
+ *       for d (no tetrahedron, no vertex of valence 2);
+ *   (e) for every n in nbr(r) \ {k, c, d}: len_sq(k, n) <= thr_max2 -- the split does not cut what the collapse makes;
+ *   (f) for every face at r other than F+ and F-, rotated to (r, x, y): n_old = (x-r) x (y-r), n_new = (x-k) x (y-k), dn =
+ *       dot(n_old, n_new) > 0 and dn dn >= (crease_cos crease_cos) (dot(n_old,n_old) dot(n_new,n_new)): no fold, and no
+ *       crease such as the rim of a flat cap is flattened;
+ *   (g) with k2 = quality_keep quality_keep: the smallest q(k,x,y; n_new) over those faces >= the smallest k2 q(r,x,y;
+ *       n_old) over all faces at r, F+ and F- too; a NaN among the q of either side fails.
+ * Every guard is a flag or an exact minimum / maximum over the ring: no order enters.  If both directions are admissible
+ * the edge takes the one whose longest new edge (the largest len_sq(k, n) of (e), 0 without one) is shorter, r = hi on a
+ * tie; else the admissible one.  It is then a candidate.
+ *
+ * A short edge without an admissible direction is counted once, summed over the passes: blocked_fixed where neither end is
+ * removable; else blocked_link where (a) fails (the edge has no link of two vertices); else by the first class of (c) ..
+ * (g) that fails for r = hi if hi is removable, else for r = lo: blocked_link, _valence, _long, _normal, _quality.  In
+ * every pass the short edges are the candidates and the blocked ones.
+ *
+ * Selection.  A candidate has the priority ((0xFFFFFFFF - (bits(len_sq(lo, hi)) >> 32)) << 32) | (0xFFFFFFFF - first): the
+ * shorter edge first, compared to 20 mantissa bits; unique per edge, never 0.  best[x] = the largest priority among the
+ * candidates with x in {r} + nbr(r).  A candidate collapses iff it is best at every one of those vertices.  So the closed
+ * stars of the removed vertices of a pass are pairwise disjoint: no two collapses create the same edge, and none changes
+ * a neighbourhood, a degree or a face that another one read, so every guard is exact whatever else collapses.  The largest
+ * priority of the mesh always collapses, so a pass with a candidate removes a vertex, and the vertex count ends the passes.
+ *
+ * Rewrite, in place: r <- k in every face at r; F+, F- and r die.  Every other face and every vertex keeps its bits.
+ * After the last pass one stable compaction of vertices and faces: survivors keep their relative order.  origin[new] =
+ * old; target[old] = the new index of the survivor the vertex ended in, chains across the passes followed.
+ *
+ * Passes repeat until one has no candidate (converged) or max_passes have run.  n_short_before / _after: the short edges
+ * of the input and of the result.  The edge counts are those of the input, as mm_flip_report's.
+ *
+ * Device (mm_collapse_kernels.hip; integer atomics only).  One upload: the vertices (24 nv), the faces as int32 (12 nf),
+ * the mask where given (nv): bytes_uploaded.  The vertices are never written, the faces are rewritten where they lie, dead
+ * faces and vertices are marked; per pass the 128 bytes of counters are read back.  One download: the compacted vertices
+ * and faces, origin, target and the counters, bytes_downloaded = 28 nv_out + 12 nf_out + 4 nv + 128.  Launches, with V(n)
+ * = 1 + max(1, ceil(ceil(log2 n) / 8)) for a volume: a pass is 10 -- the edge table with owners and first corners, the
+ * valences with the edge counts, the sorted adjacency (6), the candidates, the collapses.  Where no pass converged
+ * (max_passes == 0 too) the table of the result costs 2 more.  The end is 9: two scans (3 each), the gather, the remap,
+ * origin and target:
+ *     n_launches = V(nf) + V(nf_out) + 10 passes_run + (converged ? 0 : 2) + 9
+ * With nv == 0 or nf == 0 nothing is launched and the input is returned with origin = target = the identity.
+ *
+ * Limits as mm_mesh_flip_edges.  target_len not finite or not > 0, min_ratio outside (0, 1], max_ratio < 1 or not finite:
+ * MM_ERR_INVALID.  On an error no output is written. */
+
+#define MM_COLLAPSE_PASS_SLOTS 16
+
+typedef struct mm_collapse_report {
+    int64_t n_vertices, n_faces, n_vertices_out, n_faces_out;
+    int64_t n_edges, n_open_edges, n_nonmanifold_edges, n_inconsistent_edges;
+    int64_t n_short_before, n_short_after;
+    int64_t passes_run, converged, n_collapses;
+    int64_t collapses_per_pass[MM_COLLAPSE_PASS_SLOTS];    /* passes beyond 16 add into the last slot                  */
+    int64_t candidates_per_pass[MM_COLLAPSE_PASS_SLOTS];
+    int64_t blocked_fixed, blocked_link, blocked_valence, blocked_long, blocked_normal, blocked_quality;
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    double  volume_before, volume_after;
+} mm_collapse_report;                                      /* 448 bytes */
+
+/* The passes above.  mask (nullable): nv bytes, a nonzero byte pins the vertex.  out_vertices, out_origin: capacity nv;
+ * out_tris: capacity nf triples; out_target: nv entries.  max_passes == 0 returns the input with the counts and volumes
+ * filled. */
+int     mm_mesh_collapse_edges(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                               const uint8_t* mask, double target_len, double min_ratio, double max_ratio,
+                               double crease_cos, double quality_keep, int64_t max_passes, double* out_vertices,
+                               int64_t* out_tris, int64_t* out_origin, int64_t* out_target, mm_collapse_report* report);
 
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 

@@ -120,7 +120,7 @@ EXPORTS_CCTA = [
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
     "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan", "mm_mesh_relax",
-    "mm_mesh_valence", "mm_mesh_flip_edges",
+    "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -185,6 +185,18 @@ class MMFlipReport(C.Structure):
                [(name, C.c_int64) for name in (
                    "blocked_existing", "blocked_normal", "blocked_crease", "blocked_quality", "deviation_before",
                    "deviation_after", "n_launches", "bytes_uploaded", "bytes_downloaded")] + \
+               [("volume_before", C.c_double), ("volume_after", C.c_double)]
+
+
+class MMCollapseReport(C.Structure):
+    """``mm_collapse_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_vertices_out", "n_faces_out", "n_edges", "n_open_edges", "n_nonmanifold_edges",
+        "n_inconsistent_edges", "n_short_before", "n_short_after", "passes_run", "converged", "n_collapses")] + \
+               [("collapses_per_pass", C.c_int64 * 16), ("candidates_per_pass", C.c_int64 * 16)] + \
+               [(name, C.c_int64) for name in (
+                   "blocked_fixed", "blocked_link", "blocked_valence", "blocked_long", "blocked_normal", "blocked_quality",
+                   "n_launches", "bytes_uploaded", "bytes_downloaded")] + \
                [("volume_before", C.c_double), ("volume_after", C.c_double)]
 
 
@@ -633,6 +645,8 @@ def lib():
     L.mm_mesh_valence.argtypes = [P, P, I64, P, I64, P, P, P]
     L.mm_mesh_flip_edges.restype = I
     L.mm_mesh_flip_edges.argtypes = [P, P, I64, P, I64, P, D, D, I64, P, C.POINTER(MMFlipReport)]
+    L.mm_mesh_collapse_edges.restype = I
+    L.mm_mesh_collapse_edges.argtypes = [P, P, I64, P, I64, P, D, D, D, D, D, I64, P, P, P, P, C.POINTER(MMCollapseReport)]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

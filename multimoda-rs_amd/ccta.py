@@ -1520,7 +1520,7 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
            engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False,
-           flip=False) -> dict:
+           flip=False, collapse=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1540,7 +1540,10 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     (``flip_edges``) behind the refinement and in front of the relaxation, which is where it pays; no vertex moves, so
     the point lists stay, and the result carries ``flip_report``.  Where ``pinned`` is not given, the vertices of the
     intravascular lumen (``anomalous_points``) are pinned: its triangulation stays.  The default ``flip=False`` changes
-    nothing."""
+    nothing.  ``collapse=True``, or a dict of ``collapse_edges`` keywords, removes the short edges that the seam strips,
+    the rim fans and the split leave (``collapse_edges``) behind the refinement and in front of the flips, the
+    intravascular lumen pinned in the same way: a removed vertex leaves every point list that holds it by value, and the
+    result carries ``collapse_report``.  The default ``collapse=False`` changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1550,8 +1553,8 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_relax_result(_flip_result(_refine_result(out, refine, engine), flip, engine), relax, engine),
-                          smooth, engine)
+    out = _collapse_result(_refine_result(out, refine, engine), collapse, engine)
+    return _smooth_result(_relax_result(_flip_result(out, flip, engine), relax, engine), smooth, engine)
 
 
 def _refine_result(out: dict, refine, engine) -> dict:
@@ -1581,6 +1584,41 @@ def _refine_result(out: dict, refine, engine) -> dict:
     return out
 
 
+def _iv_lumen_vertices(out: dict) -> np.ndarray:
+    """The vertices of ``out["mesh"]`` that are points of the intravascular lumen (``anomalous_points``), ascending."""
+    iv = out.get("anomalous_points")
+    at = _match(_p3(_mesh_parts(out["mesh"])[0]), _p3(iv)) if iv is not None and len(iv) else np.zeros(0, dtype=np.int64)
+    return np.unique(at[at >= 0])
+
+
+def _collapse_result(out: dict, collapse, engine) -> dict:
+    """The ``collapse`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of collapse_edges keywords.
+    Without ``pinned`` the vertices of the intravascular lumen are pinned.  A removed vertex leaves every point list
+    (SYNC_KEYS, ``boundary_points_*``) that holds it by value, the counterpart of how ``_refine_result`` adds the new ones."""
+    if collapse is False or collapse is None:
+        return out
+    kw = dict(collapse) if isinstance(collapse, dict) else {}
+    kw.setdefault("engine", engine)
+    if "pinned" not in kw:
+        kw["pinned"] = _iv_lumen_vertices(out)
+    old = out["mesh"]
+    new, origin, _, report = collapse_edges(old, **kw)
+    v = _p3(_mesh_parts(old)[0])
+    gone = np.ones(v.shape[0], dtype=bool)
+    gone[origin] = False
+    out = dict(out)
+    out["mesh"] = new
+    out["collapse_report"] = report
+    if gone.any():
+        removed = np.ascontiguousarray(v[gone])
+        for key in SYNC_KEYS + tuple(sorted(k for k in out if k.startswith("boundary_points_"))):
+            pts = out.get(key)
+            if pts is None or len(pts) == 0:
+                continue
+            out[key] = _p3(pts)[_match(removed, _p3(pts)) < 0]
+    return out
+
+
 def _flip_result(out: dict, flip, engine) -> dict:
     """The ``flip`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of flip_edges keywords.
     Without ``pinned`` the vertices that are points of the intravascular lumen (``anomalous_points``) are pinned."""
@@ -1589,9 +1627,7 @@ def _flip_result(out: dict, flip, engine) -> dict:
     kw = dict(flip) if isinstance(flip, dict) else {}
     kw.setdefault("engine", engine)
     if "pinned" not in kw:
-        iv = out.get("anomalous_points")
-        at = _match(_p3(_mesh_parts(out["mesh"])[0]), _p3(iv)) if iv is not None and len(iv) else np.zeros(0, dtype=np.int64)
-        kw["pinned"] = np.unique(at[at >= 0])
+        kw["pinned"] = _iv_lumen_vertices(out)
     out = dict(out)
     out["mesh"], out["flip_report"] = flip_edges(out["mesh"], **kw)
     return out
@@ -1917,14 +1953,14 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
                        engine: Optional[N.Engine] = None, smooth=False, refine=False, relax=False, flip=False,
-                       **conditioning) -> dict:
+                       collapse=False, **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
     carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``refine`` and ``smooth`` as in ``stitch``:
     the refinement runs behind the hole fill and adds ``refine_report``, the smoothing runs last and adds
-    ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``, and ``flip`` in front
-    of it, adding ``flip_report``."""
+    ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``, ``flip`` in front
+    of it, adding ``flip_report``, and ``collapse`` in front of the flips, adding ``collapse_report``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
@@ -1936,8 +1972,8 @@ def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("
         new_v, new_f, report = _fill(v, f, True, engine)
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
-    return _smooth_result(_relax_result(_flip_result(_refine_result(out, refine, engine), flip, engine), relax, engine),
-                          smooth, engine)
+    out = _collapse_result(_refine_result(out, refine, engine), collapse, engine)
+    return _smooth_result(_relax_result(_flip_result(out, flip, engine), relax, engine), smooth, engine)
 
 
 # ---- mesh closing (multimodars/ccta/fixing_functions.py:13-49, ccta/__init__.py:432-499, ccta_py.rs:743-814) -----------
@@ -2372,8 +2408,9 @@ def refine_mesh(mesh, target_edge_length_mm: Optional[float] = None, *, ratio: f
     """Split every edge of ``mesh`` longer than ``ratio * target_edge_length_mm`` at its midpoint, pass after pass,
     on the device: ``(mesh, parents, report)``, the mesh of the kind given, the input not modified.  This is the edge
     split of the isotropic remesh with which the reference's post-processing (fixing_functions.py:114-239, MeshLab)
-    brings the coarse CCTA triangles down to the intravascular resolution; its flip is ``flip_edges``, its tangential
-    relaxation and reprojection ``relax_mesh``, its collapse and repair steps are not part of this project.  No existing vertex moves or changes its index: new
+    brings the coarse CCTA triangles down to the intravascular resolution; its collapse is ``collapse_edges``, its flip
+    ``flip_edges``, its tangential relaxation and reprojection ``relax_mesh``, the four together ``isotropic_remesh``;
+    its repair step is not part of this project.  No existing vertex moves or changes its index: new
     vertices follow the old ones, ``parents[k]`` = the ends ``(lo, hi)`` of the edge whose midpoint vertex
     ``nv + k`` is, and every face is replaced in place by 1 to 4 children of its winding (include/mm_ccta.h, "mesh
     refinement", states the rule; it has one bit pattern whatever the scheduling).  A closed manifold mesh stays closed
@@ -2461,8 +2498,8 @@ def flip_edges(mesh, *, crease_deg: float = 30.0, quality_keep: float = 0.5, pas
     """Flip the edges of ``mesh`` whose flip brings the valences of their four vertices closer to 6 (4 on a border),
     pass after pass, on the device: ``(mesh, report)``, the mesh of the kind given with the same vertices and new faces,
     the input not modified.  This is the swap of the isotropic remesh of the reference's post-processing
-    (fixing_functions.py:207-219); it runs behind ``refine_mesh``, whose midpoints have valence 4, and in front of
-    ``relax_mesh``.  A flip is made only where the new edge does not exist yet, no normal turns, the two faces meet at
+    (fixing_functions.py:207-219); it runs behind ``refine_mesh``, whose midpoints have valence 4, and
+    ``collapse_edges``, and in front of ``relax_mesh``; ``isotropic_remesh`` runs the four in turn.  A flip is made only where the new edge does not exist yet, no normal turns, the two faces meet at
     less than ``crease_deg`` (30 degrees, MeshLab's default crease angle) and the worse of the two new triangles keeps
     at least ``quality_keep``^2 of the quality of the worse old one.  In a pass the flips share no vertex, chosen by a
     priority and no order of visits, so the result has one bit pattern (include/mm_ccta.h, "mesh edge flips"); every
@@ -2499,17 +2536,162 @@ def flip_edges(mesh, *, crease_deg: float = 30.0, quality_keep: float = 0.5, pas
     return _with_mesh(mesh, v.copy(), out), report
 
 
+# ---- mesh edge collapse (multimodars/ccta/fixing_functions.py:207-219: the collapse of the isotropic remesh) ----------
+
+COLLAPSE_REPORT_KEYS = ("n_vertices", "n_faces", "n_vertices_out", "n_faces_out", "n_edges", "n_open_edges",
+                        "n_nonmanifold_edges", "n_inconsistent_edges", "n_short_before", "n_short_after", "passes_run",
+                        "converged", "n_collapses", "blocked_fixed", "blocked_link", "blocked_valence", "blocked_long",
+                        "blocked_normal", "blocked_quality", "n_launches", "bytes_uploaded", "bytes_downloaded",
+                        "volume_before", "volume_after")
+
+
+def _target_length(v: np.ndarray, f: np.ndarray, target_edge_length_mm, engine) -> float:
+    """``target_edge_length_mm``, or where it is None the 25th percentile of the edge lengths as ``refine_mesh`` takes it."""
+    if target_edge_length_mm is None:
+        lengths = np.sqrt(_edge_lengths_sq(v, f, engine)[1])
+        if lengths.size == 0:
+            raise ValueError("a mesh without an edge has no edge length target")
+        target_edge_length_mm = float(np.percentile(lengths, 25.0))
+    target = float(target_edge_length_mm)
+    if not (np.isfinite(target) and target > 0.0):
+        raise ValueError("target_edge_length_mm must be finite and greater than 0")
+    return target
+
+
+def collapse_edges(mesh, target_edge_length_mm: Optional[float] = None, *, min_ratio: float = 4.0 / 5.0,
+                   max_ratio: float = 4.0 / 3.0, crease_deg: float = 30.0, quality_keep: float = 0.5, passes: int = 50,
+                   pinned=None, band=None, engine: Optional[N.Engine] = None):
+    """Remove the edges of ``mesh`` shorter than ``min_ratio * target_edge_length_mm`` by half-edge collapses, pass after
+    pass, on the device: ``(mesh, origin, target, report)``, the mesh of the kind given, the input not modified.  This is
+    the collapse of the isotropic remesh of the reference's post-processing (fixing_functions.py:207-219); it runs
+    behind ``refine_mesh`` and in front of ``flip_edges``.  A collapse removes one end of the edge and the two faces at
+    it and puts the other end in its place: no surviving vertex moves, and survivors keep their order
+    (``origin[new] = old``; ``target[old]`` = the new index of the vertex an old one ended in).  The half-edge form is
+    this project's choice and not MeshLab's, which collapses onto the midpoint: here no measured vertex moves.
+    ``quality_keep`` is ours too.  MeshLab's repair and its ``checksurfdist`` bound are not part of this project
+    (``surface_distance`` between input and result measures what the bound would limit).
+
+    A collapse is made only where the removed end is neither pinned nor on a border, the two ends share exactly the two
+    opposite corners as neighbours (the link condition), no valence falls below 3, no new edge is longer than
+    ``max_ratio * target_edge_length_mm`` (so the split does not undo it), no normal turns by more than ``crease_deg``
+    and the worst new triangle keeps ``quality_keep``^2 of the worst old one.  In a pass the neighbourhoods of the
+    removed vertices are disjoint, chosen by a priority (the shortest edge first) and no order of visits, so the result
+    has one bit pattern (include/mm_ccta.h, "mesh edge collapse").  ``target_edge_length_mm=None`` takes
+    ``edge_length_target(mesh)`` as ``refine_mesh`` does; 4/5 and 4/3 are the thresholds of Botsch and Kobbelt and of
+    MeshLab's filter.
+
+    ``pinned`` and ``band`` as in ``flip_edges``: a pinned vertex is never removed; it may be the end that stays.
+    ``report``: COLLAPSE_REPORT_KEYS, ``collapses_per_pass`` and ``candidates_per_pass`` (16 entries each),
+    ``target_edge_length_mm``, ``min_ratio``, ``max_ratio``, ``crease_deg``, ``quality_keep`` and ``volume_ratio``."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    nv = v.shape[0]
+    f = _checked_faces(faces, nv)
+    nf = f.shape[0]
+    if int(passes) < 0:
+        raise ValueError("passes must not be negative")
+    crease_deg, quality_keep, min_ratio, max_ratio = float(crease_deg), float(quality_keep), float(min_ratio), float(max_ratio)
+    if not 0.0 <= crease_deg <= 90.0:
+        raise ValueError("crease_deg must lie in [0, 90]")
+    if not 0.0 <= quality_keep <= 1.0:
+        raise ValueError("quality_keep must lie in [0, 1]")
+    if not 0.0 < min_ratio <= 1.0:
+        raise ValueError("min_ratio must lie in (0, 1]")
+    if not (np.isfinite(max_ratio) and max_ratio >= 1.0):
+        raise ValueError("max_ratio must be finite and at least 1")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex coordinate")
+    target = _target_length(v, f, target_edge_length_mm, engine)
+    m8 = _pin_mask(pinned, band, v, f, engine)
+    out_v = np.zeros((max(nv, 1), 3), dtype=np.float64)
+    out_f = np.zeros((max(nf, 1), 3), dtype=np.int64)
+    origin = np.zeros(max(nv, 1), dtype=np.int64)
+    tgt = np.zeros(max(nv, 1), dtype=np.int64)
+    rep = N.MMCollapseReport()
+    crease_cos = min(1.0, max(0.0, math.cos(math.radians(crease_deg))))
+    N.check(N.lib().mm_mesh_collapse_edges(_engine(engine).handle, N._ptr(v), nv, N._ptr(f), nf, N._ptr(m8), target, min_ratio,
+                                           max_ratio, crease_cos, quality_keep, int(passes), N._ptr(out_v), N._ptr(out_f),
+                                           N._ptr(origin), N._ptr(tgt), C.byref(rep)), "collapse_edges")
+    report = {k: getattr(rep, k) for k in COLLAPSE_REPORT_KEYS}
+    report["collapses_per_pass"] = list(rep.collapses_per_pass)
+    report["candidates_per_pass"] = list(rep.candidates_per_pass)
+    report["target_edge_length_mm"], report["min_ratio"], report["max_ratio"] = target, min_ratio, max_ratio
+    report["crease_deg"], report["quality_keep"] = crease_deg, quality_keep
+    report["volume_ratio"] = report["volume_after"] / report["volume_before"] if report["volume_before"] != 0.0 \
+        else float("nan")
+    kv, kf = int(rep.n_vertices_out), int(rep.n_faces_out)
+    return _with_mesh(mesh, out_v[:kv].copy(), out_f[:kf].copy()), origin[:kv].copy(), tgt[:nv].copy(), report
+
+
+def _edge_share(v: np.ndarray, f: np.ndarray, lo: float, hi: float, engine) -> float:
+    """The share of the edges of (v, f) whose length lies in [lo, hi]; NaN without an edge."""
+    if v.shape[0] == 0 or f.shape[0] == 0:
+        return float("nan")
+    lengths = np.sqrt(_edge_lengths_sq(v, f, engine)[1])
+    return float(((lengths >= lo) & (lengths <= hi)).mean()) if lengths.size else float("nan")
+
+
+def isotropic_remesh(mesh, target_edge_length_mm: Optional[float] = None, *, iterations: int = 10, reference=None,
+                     pinned=None, band=None, crease_deg: float = 30.0, quality_keep: float = 0.5, relax=None,
+                     engine: Optional[N.Engine] = None):
+    """The isotropic explicit remesh of the reference's post-processing (fixing_functions.py:207-219: ``splitflag``,
+    ``collapseflag``, ``swapflag``, ``smoothflag``, ``reprojectflag``) as a composition of this project's four calls:
+    ``(mesh, report)``.  Each of the ``iterations`` runs one pass of ``refine_mesh``, ``collapse_edges``,
+    ``flip_edges`` and ``relax_mesh`` onto ``reference`` (None: ``mesh`` as it comes in), all at
+    ``target_edge_length_mm`` (None: ``edge_length_target(mesh)``), every call from its own upload: a composite that
+    stays on the device is not offered.  ``pinned`` and ``band`` as in ``flip_edges``, evaluated once on the input; the
+    pin mask is carried through the index changes: the midpoints of the split are free, the survivors of the collapse
+    are followed through its ``origin``.  ``relax``: a dict of further ``relax_mesh`` keywords (``iterations``,
+    ``lamb``).  The collapse is a half-edge collapse and ``quality_keep`` guards flips and collapses: both are this
+    project's choices, not MeshLab's; its repair, its midpoint collapse and its ``checksurfdist`` bound are not here.
+
+    ``report``: ``iterations`` (one dict a round with the reports ``refine``, ``collapse``, ``flip``, ``relax``),
+    ``target_edge_length_mm``, ``share_in_range_before`` / ``_after`` (the share of the edges with a length within
+    [4/5, 4/3] of the target), ``n_vertices_before`` / ``_after`` and ``n_faces_before`` / ``_after``."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    if int(iterations) < 0:
+        raise ValueError("iterations must not be negative")
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex coordinate")
+    target = _target_length(v, f, target_edge_length_mm, engine)
+    lo, hi = 4.0 / 5.0 * target, 4.0 / 3.0 * target
+    mask = _pin_mask(pinned, band, v, f, engine)
+    mask = None if mask is None else mask.astype(bool)
+    ref = (v.copy(), f.copy()) if reference is None else reference
+    relax_kw = dict(relax) if relax else {}
+    report = {"iterations": [], "target_edge_length_mm": target, "share_in_range_before": _edge_share(v, f, lo, hi, engine),
+              "n_vertices_before": v.shape[0], "n_faces_before": f.shape[0]}
+    cur = (v, f)
+    for _ in range(int(iterations)):
+        cur, parents, r_split = refine_mesh(cur, target, passes=1, engine=engine)
+        if mask is not None:
+            mask = np.concatenate([mask, np.zeros(parents.shape[0], dtype=bool)])
+        cur, origin, _, r_col = collapse_edges(cur, target, crease_deg=crease_deg, quality_keep=quality_keep, pinned=mask,
+                                               engine=engine)
+        if mask is not None:
+            mask = mask[origin]
+        cur, r_flip = flip_edges(cur, crease_deg=crease_deg, quality_keep=quality_keep, pinned=mask, engine=engine)
+        cur, _, r_relax = relax_mesh(cur, ref, pinned=mask, engine=engine, **relax_kw)
+        report["iterations"].append({"refine": r_split, "collapse": r_col, "flip": r_flip, "relax": r_relax})
+    report.update(share_in_range_after=_edge_share(cur[0], cur[1], lo, hi, engine), n_vertices_after=cur[0].shape[0],
+                  n_faces_after=cur[1].shape[0])
+    return _with_mesh(mesh, cur[0], cur[1]), report
+
+
 def postprocess_stitched_mesh(mesh, *, postprocessing: bool = False, lamb: float = 0.5, nu: float = 0.5,
                               iterations: int = 10, **kw):
     """fixing_functions.py:52-92 by the reference's name and flag.  ``postprocessing=False`` hands the mesh back as it
     is.  ``True`` runs the Taubin smoothing that ends the reference's post-processing (``filter_taubin``); its repair
-    and isotropic remesh in front are MeshLab's and not part of this project, so ``target_edge_length_mm`` or
-    ``remesh_iterations`` raise NotImplementedError.  Other keywords go to ``smooth_mesh``.  The edge split of that
-    remesh is ``refine_mesh``, to be called in front of this function."""
+    in front is MeshLab's and not part of this project, and its isotropic remesh is a call of its own,
+    ``isotropic_remesh``, to be made in front of this function, so ``target_edge_length_mm`` or ``remesh_iterations``
+    raise NotImplementedError.  Other keywords go to ``smooth_mesh``."""
     for name in ("target_edge_length_mm", "remesh_iterations"):
         if name in kw:
             raise NotImplementedError(f"{name}: the isotropic remesh of the reference's post-processing is not part of "
-                                      "this project; only its Taubin smoothing runs here")
+                                      "this function, only its Taubin smoothing runs here; call mm.isotropic_remesh "
+                                      "in front of it")
     if not postprocessing:
         return mesh
     return filter_taubin(mesh, lamb, nu, iterations, **kw)

@@ -251,6 +251,28 @@ hipError_t launch_flip_pass(int32_t* face, long long nv, const double* v, const 
                             const unsigned int* cnt, const unsigned int* own, const unsigned int* first, int log2_cap,
                             const unsigned int* vw, double cc2, double qk2, unsigned long long* prio, int32_t* opp,
                             unsigned long long* best, unsigned long long* counts, hipStream_t s);
+// mesh edge collapse (mm_collapse_kernels.hip; include/mm_ccta.h, "mesh edge collapse"): face = int32 triples, rewritten
+// in place; fkeep / vkeep: one byte a face / vertex, 0 once dead; the edge table as weld_edges sizes it, with first beside
+// it, of the live faces only; vw: one word a vertex, deg in the low 30 bits, bit 30 = ends an inconsistent edge, bit 31 =
+// border; counts: the col_num_* words, the first col_num_pass cleared by col_table.  col_table: the table, vw,
+// counts[edges .. short] and prio[s] = 1 at a short edge with two owners of opposite directions, 2 at any other short
+// edge, else 0 (2 kernels).  col_pass, behind it and behind launch_mesh_csr on the same keys (off, nb): prio (8
+// bytes a slot) and rk (the removed and the kept end, 8 bytes a slot) of the candidates, best (8 bytes a vertex),
+// counts[candidates .. quality]; then the collapses, to[r] = k (to: -1 before), counts[collapses] (2 kernels).
+// col_finish: target[v] = vidx of the survivor v ended in, origin[vidx[v]] = v (vidx: launch_trim_scan of vkeep).
+enum { col_num_edges = 0, col_num_open, col_num_nonmanifold, col_num_inconsistent, col_num_short, col_num_candidates,
+       col_num_fixed, col_num_link, col_num_valence, col_num_long, col_num_normal, col_num_quality, col_num_collapses,
+       col_num_pass, col_num_vol_before = 14, col_num_vol_after, col_num_words };
+hipError_t launch_col_table(const int32_t* face, long long nf, const uint8_t* fkeep, long long nv, const double* v,
+                            double thr_min2, unsigned long long* keys, unsigned int* cnt, unsigned int* own,
+                            unsigned int* first, int log2_cap, unsigned int* vw, unsigned long long* prio,
+                            unsigned long long* counts, hipStream_t s);
+hipError_t launch_col_pass(int32_t* face, long long nv, const double* v, const uint8_t* pin, const unsigned long long* keys,
+                           const unsigned int* own, const unsigned int* first, int log2_cap, const unsigned int* vw,
+                           const int32_t* off, const int32_t* nb, double thr_max2, double cc2, double qk2, unsigned long long* prio, int32_t* rk, unsigned long long* best,
+                           uint8_t* fkeep, uint8_t* vkeep, int32_t* to, unsigned long long* counts, hipStream_t s);
+hipError_t launch_col_finish(const int32_t* to, const int32_t* vidx, long long nv, int32_t* origin, int32_t* target,
+                             hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

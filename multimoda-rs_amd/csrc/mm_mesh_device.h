@@ -1,5 +1,5 @@
-// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_flip
-// _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
+// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_flip,
+// mm_collapse _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
 // refine and flip files insert, the close, smooth and flip files read, EdgeTable of mm_stage.h sizes it), the workgroup scan
 // and the two per-wave ballot idioms.  Header-only; internal.
 #pragma once

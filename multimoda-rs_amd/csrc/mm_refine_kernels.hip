@@ -2,8 +2,8 @@
 // none is longer than the threshold.
 //
 // The edge split of an isotropic remesh (multimodars/ccta/fixing_functions.py:114-239 hands the whole remesh to MeshLab;
-// the flip is mm_flip_kernels.hip, relaxation and reprojection mm_relax_kernels.hip, collapse is not part of this
-// project).  include/mm_ccta.h ("mesh refinement")
+// the flip is mm_flip_kernels.hip, relaxation and reprojection mm_relax_kernels.hip, the collapse
+// mm_collapse_kernels.hip).  include/mm_ccta.h ("mesh refinement")
 // states the rule, which has one answer whatever the scheduling: a marked edge's vertex number follows the smallest
 // corner id 3 f + j that names the edge, found with an integer atomicMin.  One lane per item in grid-stride loops (the
 // scan kernels: one workgroup per tile of mm_mesh_device.h's scan); integer atomics only.
