@@ -591,7 +591,7 @@ int     mm_mesh_vertex_rings(mm_engine* e, const int64_t* faces, int64_t nf, int
 /* ---- mesh refinement (multimodars/ccta/fixing_functions.py:114-239: fix_and_remesh_stitched_mesh brings the coarse CCTA
  *      triangles down to the intravascular resolution with MeshLab's isotropic remesh; of that filter this is the edge
  *      split alone; the flip is "mesh edge flips", the tangential relaxation and the reprojection "mesh relaxation" below;
- *      the collapse is "mesh edge collapse"; no repair) ---------------------------------------------------------------------------------------
+ *      the collapse is "mesh edge collapse", the repair "mesh repair") ---------------------------------------------------------------------------------------
  *
  * One pass on vertices v (f64) and triangles, with thr2 = (ratio target_len) (ratio target_len) computed once in f64:
  *   marked     the undirected edge lo < hi is marked when ((dx dx + dy dy) + dz dz) > thr2, d = v[hi] - v[lo] per
@@ -717,7 +717,7 @@ int     mm_tri_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris,
 
 /* ---- mesh relaxation (multimodars/ccta/fixing_functions.py:192-219: of MeshLab's isotropic remesh the tangential
  *      smoothing and the reprojection, smoothflag / reprojectflag / checksurfdist; the flip is "mesh edge flips" below,
- *      the collapse is "mesh edge collapse"; repair stays out) ----------------------------------------------------------
+ *      the collapse is "mesh edge collapse", the repair "mesh repair") ----------------------------------------------------------
  * Slides the free vertices of a mesh (v, faces) along a reference surface (rv, rfaces; the mesh's own input where none is
  * given) and puts every one of them back on it exactly.  tests/mm_checkers/relax_mesh.py is the executable form.  All
  * arithmetic is unfused f64 in the order written; dot, the cross components and the closest point are those of "surface
@@ -872,7 +872,7 @@ int     mm_mesh_flip_edges(mm_engine* e, const double* vertices_xyz, int64_t nv,
                            int64_t* out_tris, mm_flip_report* report);
 
 /* ---- mesh edge collapse (multimodars/ccta/fixing_functions.py:207-219: of MeshLab's isotropic remesh the collapse,
- *      collapseflag; MeshLab's repair, its midpoint collapse and its checksurfdist bound stay out) ----------------------
+ *      collapseflag; MeshLab's midpoint collapse and its checksurfdist bound stay out; the repair is "mesh repair") ----------------------
  * Removes the short edges of a mesh (v, faces) by half-edge collapses r -> k: r and the two faces at the edge vanish, k
  * takes the place of r in the other faces at r, no surviving vertex moves.  The half-edge form is this project's choice,
  * not MeshLab's (which collapses onto the midpoint): it lets no measured vertex move; quality_keep is ours too.
@@ -962,6 +962,100 @@ int     mm_mesh_collapse_edges(mm_engine* e, const double* vertices_xyz, int64_t
                                const uint8_t* mask, double target_len, double min_ratio, double max_ratio,
                                double crease_cos, double quality_keep, int64_t max_passes, double* out_vertices,
                                int64_t* out_tris, int64_t* out_origin, int64_t* out_target, mm_collapse_report* report);
+
+/* ---- mesh repair (multimodars/ccta/fixing_functions.py:114-239: the five MeshLab repair filters that stand in front of
+ *      the hole filling and behind the isotropic remesh of fix_and_remesh_stitched_mesh) -----------------------------------
+ * MeshLab and vcglib are not available to this project, so the rules are its own: they restate what the filters do as far
+ * as that is known and make every choice deterministic.  tests/mm_checkers/repair_mesh.py is the executable form.
+ *
+ * Input: vertices (nv, 3) f64, all finite (magnitudes up to 2^250, so that q below stays finite); faces (nf, 3) with
+ * indices in [0, nv).  The stages run in this order, each behind its flag.  A stage whose flag is off changes nothing but
+ * still counts what it finds (n_welded_vertices, n_null_faces, n_duplicate_faces, n_nonmanifold_edges_before,
+ * n_nonmanifold_vertices), which is what mm.mesh_manifold_report reads; n_faces_removed, n_new_vertices and
+ * n_unreferenced_dropped count what was done.
+ *
+ * (a) Duplicate vertices (MM_REPAIR_DUPLICATE_VERTICES).  Two vertices are duplicates when all three coordinates compare
+ *     equal with ==, so +0.0 equals -0.0; nothing is rounded, and unreferenced vertices take part (unlike
+ *     mm_mesh_assemble).  Of a set of duplicates the smallest index survives with its own bits; rep[i] is that index.
+ *     The faces are read through rep.
+ * (b) Degenerate and null faces.  A face with a repeated index (through rep) is dropped whatever the flags say:
+ *     n_degenerate_faces.  Of the others, with p0, p1, p2 the coordinates of its corners in face order, u = p1 - p0, w =
+ *     p2 - p0, cx = uy wz - uz wy, cy = uz wx - ux wz, cz = ux wy - uy wx (two products and one subtraction each, unfused),
+ *     q = (cx cx + cy cy) + cz cz: the squared double area.  A face with cx == 0, cy == 0 and cz == 0 is null
+ *     (n_null_faces) and dropped with MM_REPAIR_NULL_FACES.
+ * (c) Duplicate faces (MM_REPAIR_DUPLICATE_FACES).  Of the faces left with one vertex set, the smallest index stays with
+ *     its own corner order, as in mm_mesh_assemble; the others are counted (n_duplicate_faces) and dropped.
+ * (d) Non-manifold edges, by removing faces (MM_REPAIR_NONMANIFOLD_EDGES; MeshLab's method 0).  n_open_edges_before and
+ *     n_nonmanifold_edges_before: the edges of the faces left with one owner and with more than two.  The faces that
+ *     have an edge with more than two owners are visited in ascending order of the key (q, index) -- equal q: the
+ *     smaller index first, which vcglib's std::sort leaves open --, and a face is deleted when its turn comes iff it
+ *     still has such an edge.  The owners of one edge come in key order, so when the owner of rank r among c is
+ *     visited at least c - r are left: the walk equals its closed form, which the device computes in one pass --
+ *         a face is removed iff, on some edge with c > 2 owners, it is not one of the two owners with the largest keys.
+ *     A face that one of its edges keeps and another removes goes, and may leave an open edge.  n_faces_removed;
+ *     n_open_edges_after, n_nonmanifold_edges_after: the same counts of the faces left (the later stages keep them).
+ * (e) Non-manifold vertices, by splitting (MM_REPAIR_NONMANIFOLD_VERTICES; MeshLab's displacement 0).  Corner 3 f + k
+ *     is corner k of face f.  Two corners at one vertex are linked when their faces share an edge at that vertex that
+ *     has exactly two owners, whatever the directions (the adjacency of mm_fix_winding); edges with other counts link
+ *     nothing.  The corners at a vertex fall into components.  The component that holds the vertex's smallest corner
+ *     keeps the vertex; every other one gets a new vertex with the parent's bits.  n_nonmanifold_vertices: the vertices
+ *     with more than one component; n_new_vertices: the vertices made.  New vertices follow the vertices kept, in
+ *     increasing order of their component's smallest corner (survivors keep their order, so input and output corner ids
+ *     order alike).
+ *     A weld that the split would only undo is not made.  Where a component that does not keep the vertex consists of
+ *     exactly the corners of ONE input vertex w that stage (a) welded into the vertex -- every corner of the component is
+ *     w's, and every corner w has in the faces left is in it --, the component gets no new vertex: w comes back, at its
+ *     own place in the input order and with its own bits, is counted in neither n_welded_vertices nor n_new_vertices,
+ *     and does not make its vertex count as non-manifold; origin and target name w itself.  This holds with the split
+ *     switched off as well: stage (a) then creates no pinch.  So the output of a call is a mesh that needs nothing: a
+ *     second call welds each vertex the split made to its parent, finds the same components and undoes every such weld.
+ * (f) Unreferenced vertices (MM_REPAIR_DROP_UNREFERENCED; off in the Python default, MeshLab's five filters leave them):
+ *     a survivor of (a) that no face left names is dropped, n_unreferenced_dropped.
+ *
+ * The order is not the reference's (edges, vertices, duplicate faces, duplicate vertices, null faces): with a
+ * displacement of 0 its duplicate-vertex filter merges again what the split has just made.  Here the weld comes first and
+ * the split last, so what the split separates stays separate, within a call and, by the undone welds of (e), across calls.
+ *
+ * Outputs: the vertices kept in input order, then the new ones; the faces left in input order with their own corner order,
+ * renamed; origin[i] = the input vertex whose bits output vertex i carries; target[j] = the output vertex of input vertex
+ * j through rep, -1 where (f) dropped it.  A mesh that needs nothing comes back bit for bit with origin = target = the
+ * identity and every count 0.
+ *
+ * Device (mm_repair_kernels.hip; integer atomics only, no output depends on the order of arrival).  One upload (24 nv +
+ * 12 nf = bytes_uploaded), one download (28 n_vertices + 12 n_faces + 4 nv + 152 = bytes_downloaded) and 4 bytes a
+ * jumping round.  With nf > 0 a call launches MM_REPAIR_LAUNCHES kernels whatever the flags and the mesh -- (a) 2, (b)
+ * and (c) 2, the edge table and its report 2, (d) 5, the table and report of the faces left 2, (e) the hook 1 and
+ * 3, (f) 1, the three scans 9, the output 2 -- plus union_rounds pointer-jumping rounds of the corner union-find, each
+ * one launch: n_launches = MM_REPAIR_LAUNCHES + union_rounds, and union_rounds <= 2 + ceil(log2(max(3 nf, 2))).
+ * union_rounds is the one field that is not a function of the input alone (a round may or may not see a link another
+ * lane moves).  With nf == 0 the scans over faces and corners and the rounds are not launched; with nv == 0 nothing is.
+ *
+ * Limits: nv, nf < 2^31 and 6 nf < 2^31 (MM_ERR_TOO_LARGE beyond); an index out of range, a non-finite coordinate or an
+ * unknown flag bit: MM_ERR_INVALID, checked before anything is allocated.  tris: the nf faces; out_faces: capacity nf;
+ * out_vertices and out_origin: capacity vert_cap; out_target: nv.  Where n_vertices > vert_cap nothing but the report is written and the
+ * call returns MM_ERR_TOO_LARGE, the report complete: the protocol of mm_fill_holes. */
+
+#define MM_REPAIR_DUPLICATE_VERTICES   1
+#define MM_REPAIR_NULL_FACES           2
+#define MM_REPAIR_DUPLICATE_FACES      4
+#define MM_REPAIR_NONMANIFOLD_EDGES    8
+#define MM_REPAIR_NONMANIFOLD_VERTICES 16
+#define MM_REPAIR_DROP_UNREFERENCED    32
+#define MM_REPAIR_ALL_FLAGS            63
+#define MM_REPAIR_LAUNCHES             28
+
+typedef struct mm_repair_report {
+    int64_t n_vertices, n_faces;                           /* of the result                                            */
+    int64_t n_welded_vertices, n_degenerate_faces, n_null_faces, n_duplicate_faces;
+    int64_t n_nonmanifold_edges_before, n_nonmanifold_edges_after, n_faces_removed;
+    int64_t n_nonmanifold_vertices, n_new_vertices, n_unreferenced_dropped;
+    int64_t n_open_edges_before, n_open_edges_after;
+    int64_t union_rounds, n_launches, bytes_uploaded, bytes_downloaded;
+} mm_repair_report;                                        /* 144 bytes */
+
+int     mm_mesh_repair(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf, int flags,
+                       int64_t vert_cap, double* out_vertices, int64_t* out_faces, int64_t* out_origin,
+                       int64_t* out_target, mm_repair_report* report);
 
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 

@@ -39,7 +39,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
                    smooth_mesh_labels, create_wall_mesh, condition_boundary_rings, stitch_conditioned, smooth_mesh,
                    filter_taubin, filter_laplacian, mesh_adjacency_csr, vertex_rings, postprocess_stitched_mesh,
                    mesh_edge_lengths, edge_length_target, refine_mesh, relax_mesh, project_to_mesh,
-                   mesh_valence, flip_edges, collapse_edges, isotropic_remesh)
+                   mesh_valence, flip_edges, collapse_edges, isotropic_remesh, repair_mesh,
+                   mesh_manifold_report, fix_and_remesh_stitched_mesh)
 from . import surface
 from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport, point_mesh_distance,
                       sample_mesh_surface, surface_distance)
@@ -83,6 +84,7 @@ __all__ = [
     "smooth_mesh", "filter_taubin", "filter_laplacian", "mesh_adjacency_csr", "vertex_rings", "postprocess_stitched_mesh",
     "mesh_edge_lengths", "edge_length_target", "refine_mesh", "relax_mesh", "project_to_mesh",
     "mesh_valence", "flip_edges", "collapse_edges", "isotropic_remesh",
+    "repair_mesh", "mesh_manifold_report", "fix_and_remesh_stitched_mesh",
     "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
     "DirectedDistance", "SurfaceDistanceReport",
     "morphometry", "ContourMeasures", "contour_measures",

@@ -120,7 +120,7 @@ EXPORTS_CCTA = [
     "mm_rim_locate_chunk_points", "mm_mesh_layer_push", "mm_mesh_split_rim_edges", "mm_condition_rims",
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
     "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan", "mm_mesh_relax",
-    "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges",
+    "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges", "mm_mesh_repair",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -198,6 +198,15 @@ class MMCollapseReport(C.Structure):
                    "blocked_fixed", "blocked_link", "blocked_valence", "blocked_long", "blocked_normal", "blocked_quality",
                    "n_launches", "bytes_uploaded", "bytes_downloaded")] + \
                [("volume_before", C.c_double), ("volume_after", C.c_double)]
+
+
+class MMRepairReport(C.Structure):
+    """``mm_repair_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_welded_vertices", "n_degenerate_faces", "n_null_faces", "n_duplicate_faces",
+        "n_nonmanifold_edges_before", "n_nonmanifold_edges_after", "n_faces_removed", "n_nonmanifold_vertices",
+        "n_new_vertices", "n_unreferenced_dropped", "n_open_edges_before", "n_open_edges_after", "union_rounds",
+        "n_launches", "bytes_uploaded", "bytes_downloaded")]
 
 
 class MMRimParams(C.Structure):
@@ -647,6 +656,8 @@ def lib():
     L.mm_mesh_flip_edges.argtypes = [P, P, I64, P, I64, P, D, D, I64, P, C.POINTER(MMFlipReport)]
     L.mm_mesh_collapse_edges.restype = I
     L.mm_mesh_collapse_edges.argtypes = [P, P, I64, P, I64, P, D, D, D, D, D, I64, P, P, P, P, C.POINTER(MMCollapseReport)]
+    L.mm_mesh_repair.restype = I
+    L.mm_mesh_repair.argtypes = [P, P, I64, P, I64, I, I64, P, P, P, P, C.POINTER(MMRepairReport)]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

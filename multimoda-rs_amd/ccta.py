@@ -1520,7 +1520,7 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
            engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False,
-           flip=False, collapse=False) -> dict:
+           flip=False, collapse=False, repair=False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1543,11 +1543,15 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     nothing.  ``collapse=True``, or a dict of ``collapse_edges`` keywords, removes the short edges that the seam strips,
     the rim fans and the split leave (``collapse_edges``) behind the refinement and in front of the flips, the
     intravascular lumen pinned in the same way: a removed vertex leaves every point list that holds it by value, and the
-    result carries ``collapse_report``.  The default ``collapse=False`` changes nothing."""
+    result carries ``collapse_report``.  The default ``collapse=False`` changes nothing.  ``repair=True``, or a dict of
+    ``repair_mesh`` keywords, runs ``repair_mesh`` between the assembly and the hole filling, so that a rim with a pinch
+    vertex or beside a non-manifold edge becomes a loop the fill closes; its report goes under ``"repair"``.  The default
+    ``repair=False`` changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
                                        dist_start_mode=dist_start_mode, engine=engine)
+    out = _repair_result(out, repair, engine)
     if fill_holes:
         v, f = _mesh_parts(out["mesh"])
         new_v, new_f, report = _fill(v, f, True, engine)
@@ -1953,20 +1957,22 @@ def condition_boundary_rings(mesh, results: dict, iv_geometry: G.FlatGeometry, n
 def stitch_conditioned(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
                        prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv", fill_holes: bool = False,
                        engine: Optional[N.Engine] = None, smooth=False, refine=False, relax=False, flip=False,
-                       collapse=False, **conditioning) -> dict:
+                       collapse=False, repair=False, **conditioning) -> dict:
     """``stitch`` with the reference's rim conditioning in front of the seam: remove ``region_remove``
     (``target_boundaries=2``), ``condition_boundary_rings(**conditioning)``, ``stitch_ccta_to_intravascular`` and, with
     ``fill_holes``, ``manual_hole_fill``.  Together the middle two are the reference's stitching.py:355-481.  The result
     carries ``rim_report`` beside ``stitch_report`` (and ``fill_report``).  ``refine`` and ``smooth`` as in ``stitch``:
     the refinement runs behind the hole fill and adds ``refine_report``, the smoothing runs last and adds
     ``smooth_report``; ``relax`` as in ``stitch`` too, between the two, adding ``relax_report``, ``flip`` in front
-    of it, adding ``flip_report``, and ``collapse`` in front of the flips, adding ``collapse_report``."""
+    of it, adding ``flip_report``, and ``collapse`` in front of the flips, adding ``collapse_report``; ``repair`` as in
+    ``stitch``, between the assembly and the hole filling, adding ``"repair"``."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     cond = condition_boundary_rings(updated["mesh"], updated, geometry, engine=engine, **conditioning)
     n_iv = int(conditioning.get("n_points_iv_cont", 100))
     out = stitch_ccta_to_intravascular(geometry, cond["mesh"], cond, n_points_iv_cont=n_iv, prox_start_mode=prox_start_mode,
                                        dist_start_mode=dist_start_mode, engine=engine)
+    out = _repair_result(out, repair, engine)
     if fill_holes:
         v, f = _mesh_parts(out["mesh"])
         new_v, new_f, report = _fill(v, f, True, engine)
@@ -2410,7 +2416,7 @@ def refine_mesh(mesh, target_edge_length_mm: Optional[float] = None, *, ratio: f
     split of the isotropic remesh with which the reference's post-processing (fixing_functions.py:114-239, MeshLab)
     brings the coarse CCTA triangles down to the intravascular resolution; its collapse is ``collapse_edges``, its flip
     ``flip_edges``, its tangential relaxation and reprojection ``relax_mesh``, the four together ``isotropic_remesh``;
-    its repair step is not part of this project.  No existing vertex moves or changes its index: new
+    its repair step is ``repair_mesh``.  No existing vertex moves or changes its index: new
     vertices follow the old ones, ``parents[k]`` = the ends ``(lo, hi)`` of the edge whose midpoint vertex
     ``nv + k`` is, and every face is replaced in place by 1 to 4 children of its winding (include/mm_ccta.h, "mesh
     refinement", states the rule; it has one bit pattern whatever the scheduling).  A closed manifold mesh stays closed
@@ -2568,7 +2574,7 @@ def collapse_edges(mesh, target_edge_length_mm: Optional[float] = None, *, min_r
     it and puts the other end in its place: no surviving vertex moves, and survivors keep their order
     (``origin[new] = old``; ``target[old]`` = the new index of the vertex an old one ended in).  The half-edge form is
     this project's choice and not MeshLab's, which collapses onto the midpoint: here no measured vertex moves.
-    ``quality_keep`` is ours too.  MeshLab's repair and its ``checksurfdist`` bound are not part of this project
+    ``quality_keep`` is ours too.  MeshLab's ``checksurfdist`` bound is not part of this project; its repair is ``repair_mesh``
     (``surface_distance`` between input and result measures what the bound would limit).
 
     A collapse is made only where the removed end is neither pinned nor on a border, the two ends share exactly the two
@@ -2643,7 +2649,8 @@ def isotropic_remesh(mesh, target_edge_length_mm: Optional[float] = None, *, ite
     pin mask is carried through the index changes: the midpoints of the split are free, the survivors of the collapse
     are followed through its ``origin``.  ``relax``: a dict of further ``relax_mesh`` keywords (``iterations``,
     ``lamb``).  The collapse is a half-edge collapse and ``quality_keep`` guards flips and collapses: both are this
-    project's choices, not MeshLab's; its repair, its midpoint collapse and its ``checksurfdist`` bound are not here.
+    project's choices, not MeshLab's; its midpoint collapse and its ``checksurfdist`` bound are not here, its repair is
+    ``repair_mesh``, and ``fix_and_remesh_stitched_mesh`` runs repair, hole fill and this remesh in turn.
 
     ``report``: ``iterations`` (one dict a round with the reports ``refine``, ``collapse``, ``flip``, ``relax``),
     ``target_edge_length_mm``, ``share_in_range_before`` / ``_after`` (the share of the edges with a length within
@@ -2680,18 +2687,184 @@ def isotropic_remesh(mesh, target_edge_length_mm: Optional[float] = None, *, ite
     return _with_mesh(mesh, cur[0], cur[1]), report
 
 
+# ---- mesh repair (multimodars/ccta/fixing_functions.py:114-239: MeshLab's five repair filters; the composite) ---------
+
+REPAIR_REPORT_KEYS = ("n_vertices", "n_faces", "n_welded_vertices", "n_degenerate_faces", "n_null_faces",
+                      "n_duplicate_faces", "n_nonmanifold_edges_before", "n_nonmanifold_edges_after", "n_faces_removed",
+                      "n_nonmanifold_vertices", "n_new_vertices", "n_unreferenced_dropped", "n_open_edges_before",
+                      "n_open_edges_after", "union_rounds", "n_launches", "bytes_uploaded", "bytes_downloaded")
+MANIFOLD_REPORT_KEYS = ("n_vertices", "n_faces", "n_open_edges", "n_nonmanifold_edges", "n_nonmanifold_vertices",
+                        "n_duplicate_vertices", "n_degenerate_faces", "n_null_faces", "n_duplicate_faces")
+REPAIR_FLAGS = (("duplicate_vertices", 1), ("null_faces", 2), ("duplicate_faces", 4), ("nonmanifold_edges", 8),
+                ("nonmanifold_vertices", 16), ("drop_unreferenced", 32))
+
+
+def _repair_arrays(mesh):
+    """The checked arrays of a mesh for the repair: ValueError before the engine is touched."""
+    vertices, faces = _mesh_parts(mesh)
+    v = _p3(vertices)
+    f = _checked_faces(faces, v.shape[0])
+    if not np.isfinite(v).all():
+        raise ValueError("non-finite vertex coordinate")
+    return v, f
+
+
+def _repair(v: np.ndarray, f: np.ndarray, flags: int, engine):
+    """mm_mesh_repair on checked arrays: the outputs sized for a few new vertices first and, where they do not fit,
+    once more with the exact size the first call reports (the protocol of ``fill_holes``)."""
+    nv, nf = v.shape[0], f.shape[0]
+    h = _engine(engine).handle
+    rep = N.MMRepairReport()
+    vert_cap = nv + 16
+    out_f = np.zeros((max(nf, 1), 3), dtype=np.int64)
+    tgt = np.zeros(max(nv, 1), dtype=np.int64)
+    for attempt in (0, 1):
+        out_v = np.zeros((vert_cap, 3), dtype=np.float64)
+        origin = np.zeros(vert_cap, dtype=np.int64)
+        rc = N.lib().mm_mesh_repair(h, N._ptr(v), nv, N._ptr(f), nf, int(flags), vert_cap, N._ptr(out_v), N._ptr(out_f),
+                                    N._ptr(origin), N._ptr(tgt), C.byref(rep))
+        if rc == MM_ERR_TOO_LARGE and attempt == 0 and rep.n_vertices > vert_cap:
+            vert_cap = int(rep.n_vertices)
+            continue
+        N.check(rc, "repair_mesh")
+        break
+    kv, kf = int(rep.n_vertices), int(rep.n_faces)
+    return out_v[:kv].copy(), out_f[:kf].copy(), origin[:kv].copy(), tgt[:nv].copy(), rep
+
+
+def repair_mesh(mesh, *, duplicate_vertices: bool = True, null_faces: bool = True, duplicate_faces: bool = True,
+                nonmanifold_edges: bool = True, nonmanifold_vertices: bool = True, drop_unreferenced: bool = False,
+                engine: Optional[N.Engine] = None):
+    """The repair that stands in front of the hole filling in the reference's ``fix_and_remesh_stitched_mesh``
+    (fixing_functions.py:168-177, five MeshLab filters), on the device: ``(mesh, origin, target, report)``, the mesh of
+    the kind given, the input not modified.  MeshLab is not available to this project; the rules are its own
+    (include/mm_ccta.h, "mesh repair"), deterministic, and run in this order, each behind its switch:
+
+    (a) ``duplicate_vertices``: vertices whose three coordinates compare equal (``+0.0 == -0.0``; nothing is rounded,
+        unreferenced vertices take part) become the one with the smallest index;
+    (b) a face with a repeated index always goes; ``null_faces``: so does one whose cross product is exactly zero;
+    (c) ``duplicate_faces``: of the faces with one vertex set the first stays;
+    (d) ``nonmanifold_edges``: on an edge with more than two owners the two largest faces (by squared area, then index)
+        stay and every other owner is removed -- MeshLab's "remove faces", its area order made total;
+    (e) ``nonmanifold_vertices``: a vertex whose faces do not hang together across edges with two owners is split, one
+        new vertex with the same coordinates (MeshLab's displacement 0) per further fan;
+    (f) ``drop_unreferenced`` (off, as MeshLab's five filters leave them): a vertex no face names is dropped.
+
+    The order is not the reference's, which welds behind the split and so merges again what the split has made.  A
+    weld that the split would only undo is not made: a vertex whose faces would form a fan of their own at the vertex
+    it equals stays as it is, so a repaired mesh comes back from a second call bit for bit, with ``origin`` and
+    ``target`` the identity and every count zero.  A switched-off stage still counts what it finds.  Survivors keep their order and their bits; new vertices follow
+    them.  ``origin[new]`` = the input vertex whose bits the output vertex carries, ``target[old]`` = the output vertex
+    of an input vertex (-1 where (f) dropped it).  After (d) no edge has more than two owners, after (e) every rim is a
+    regular loop that ``fill_holes`` closes.  ``report``: REPAIR_REPORT_KEYS and ``watertight`` (no open and no
+    non-manifold edge, as ``fill_holes`` defines it)."""
+    flags = 0
+    for (name, bit), on in zip(REPAIR_FLAGS, (duplicate_vertices, null_faces, duplicate_faces, nonmanifold_edges,
+                                              nonmanifold_vertices, drop_unreferenced)):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"{name} must be True or False")
+        flags |= bit if on else 0
+    v, f = _repair_arrays(mesh)
+    out_v, out_f, origin, tgt, rep = _repair(v, f, flags, engine)
+    report = {k: getattr(rep, k) for k in REPAIR_REPORT_KEYS}
+    report["watertight"] = report["n_open_edges_after"] == 0 and report["n_nonmanifold_edges_after"] == 0
+    return _with_mesh(mesh, out_v, out_f), origin, tgt, report
+
+
+def mesh_manifold_report(mesh, engine: Optional[N.Engine] = None) -> dict:
+    """What ``repair_mesh`` would find in ``mesh``, as counts only (MANIFOLD_REPORT_KEYS and ``watertight``): the
+    same kernels with every switch off, so nothing is changed and every stage counts the mesh as given -- a weld would
+    change what the later stages see.  Faces with a repeated index are counted and left out of the edge counts."""
+    v, f = _repair_arrays(mesh)
+    rep = _repair(v, f, 0, engine)[4]
+    report = {"n_vertices": v.shape[0], "n_faces": f.shape[0], "n_open_edges": rep.n_open_edges_before,
+              "n_nonmanifold_edges": rep.n_nonmanifold_edges_before, "n_nonmanifold_vertices": rep.n_nonmanifold_vertices,
+              "n_duplicate_vertices": rep.n_welded_vertices, "n_degenerate_faces": rep.n_degenerate_faces,
+              "n_null_faces": rep.n_null_faces, "n_duplicate_faces": rep.n_duplicate_faces}
+    report["watertight"] = report["n_open_edges"] == 0 and report["n_nonmanifold_edges"] == 0
+    return report
+
+
+def fix_and_remesh_stitched_mesh(mesh, *, target_edge_length_mm: Optional[float] = None, remesh_iterations: int = 10,
+                                 verbose: bool = False, pinned=None, band=None, return_report: bool = False,
+                                 engine: Optional[N.Engine] = None):
+    """fixing_functions.py:114-239 as a composition of this project's public calls: ``repair_mesh``, ``fill_holes``,
+    ``isotropic_remesh`` and, where the result is not watertight, ``repair_mesh(duplicate_vertices=False)`` and
+    ``fill_holes`` once more, as the reference's third block does.  Returns the mesh of the kind given, with
+    ``return_report`` ``(mesh, report)``.  ``target_edge_length_mm=None``: ``edge_length_target`` of the input, taken
+    before anything changes (the reference's P25).  ``pinned`` and ``band`` as in ``flip_edges``, evaluated on the
+    input; the mask follows the vertices through every step's ``origin``: a vertex the split makes inherits its
+    parent's pin, the centroids of the hole fans are free.  ``verbose`` prints the reference's line (vertices, faces,
+    watertight) per stage.
+
+    Where this differs from the reference: the holes are closed by fans about the rim's centroid instead of MeshLab's
+    ear cut, and there is no ``maxholesize``; the collapse of the remesh is a half-edge collapse; there is no
+    ``checksurfdist`` bound; and the repair welds first and splits last (``repair_mesh``), where the reference's order
+    merges again what its split has made.
+
+    ``report``: ``target_edge_length_mm``, ``repair``, ``fill``, ``remesh``, ``manifold`` (``mesh_manifold_report`` behind
+    the remesh), ``post_repair`` and ``post_fill`` (None where the remesh left the mesh watertight), ``watertight``."""
+    v, f = _repair_arrays(mesh)
+    if int(remesh_iterations) < 0:
+        raise ValueError("remesh_iterations must not be negative")
+    target = _target_length(v, f, target_edge_length_mm, engine)
+    mask = _pin_mask(pinned, band, v, f, engine)
+    mask = None if mask is None else mask.astype(bool)
+
+    def log(label, m, watertight):
+        if verbose:
+            print(f"[{label:35s}] verts={len(m[0]):>7,}  faces={len(m[1]):>7,}  watertight={watertight}")
+
+    if verbose:
+        log("input", (v, f), mesh_manifold_report((v, f), engine)["watertight"])
+        print(f"  target edge length = {target:.4f} mm")
+    cur, origin, _, r_repair = repair_mesh((v, f), engine=engine)
+    if mask is not None:
+        mask = mask[origin]
+    fv, ff, r_fill = _fill(cur[0], cur[1], True, engine)
+    if mask is not None:
+        mask = np.concatenate([mask, np.zeros(fv.shape[0] - mask.shape[0], dtype=bool)])
+    log("after hole fill", (fv, ff), r_fill["watertight"])
+    cur, r_remesh = isotropic_remesh((fv, ff), target, iterations=int(remesh_iterations), pinned=mask, engine=engine)
+    r_manifold = mesh_manifold_report(cur, engine)
+    log("after remesh", cur, r_manifold["watertight"])
+    report = {"target_edge_length_mm": target, "repair": r_repair, "fill": r_fill, "remesh": r_remesh,
+              "manifold": r_manifold, "post_repair": None, "post_fill": None, "watertight": r_manifold["watertight"]}
+    if not r_manifold["watertight"]:
+        cur, _, _, report["post_repair"] = repair_mesh(cur, duplicate_vertices=False, engine=engine)
+        fv, ff, report["post_fill"] = _fill(cur[0], cur[1], True, engine)
+        cur = (fv, ff)
+        report["watertight"] = report["post_fill"]["watertight"]
+        log("after post-remesh fix", cur, report["watertight"])
+    out = _with_mesh(mesh, cur[0], cur[1])
+    return (out, report) if return_report else out
+
+
+def _repair_result(out: dict, repair, engine) -> dict:
+    """The ``repair`` keyword of ``stitch`` / ``stitch_conditioned``: False, True, or a dict of repair_mesh keywords.  The
+    mesh is repaired between the assembly and the hole filling; its report goes under ``"repair"``.  No vertex moves
+    and the new vertices repeat their parents' coordinates, so the point lists, which hold coordinates, stay."""
+    if repair is False or repair is None:
+        return out
+    kw = dict(repair) if isinstance(repair, dict) else {}
+    kw.setdefault("engine", engine)
+    out = dict(out)
+    out["mesh"], _, _, out["repair"] = repair_mesh(out["mesh"], **kw)
+    return out
+
+
 def postprocess_stitched_mesh(mesh, *, postprocessing: bool = False, lamb: float = 0.5, nu: float = 0.5,
                               iterations: int = 10, **kw):
     """fixing_functions.py:52-92 by the reference's name and flag.  ``postprocessing=False`` hands the mesh back as it
-    is.  ``True`` runs the Taubin smoothing that ends the reference's post-processing (``filter_taubin``); its repair
-    in front is MeshLab's and not part of this project, and its isotropic remesh is a call of its own,
-    ``isotropic_remesh``, to be made in front of this function, so ``target_edge_length_mm`` or ``remesh_iterations``
-    raise NotImplementedError.  Other keywords go to ``smooth_mesh``."""
+    is.  ``True`` runs the Taubin smoothing that ends the reference's post-processing (``filter_taubin``); the repair,
+    the hole fill and the isotropic remesh in front of it are a call of their own, ``fix_and_remesh_stitched_mesh``
+    (or ``isotropic_remesh`` alone), to be made in front of this function, so ``target_edge_length_mm`` or
+    ``remesh_iterations`` raise NotImplementedError.  Other keywords go to ``smooth_mesh``."""
     for name in ("target_edge_length_mm", "remesh_iterations"):
         if name in kw:
             raise NotImplementedError(f"{name}: the isotropic remesh of the reference's post-processing is not part of "
                                       "this function, only its Taubin smoothing runs here; call mm.isotropic_remesh "
-                                      "in front of it")
+                                      "(or mm.fix_and_remesh_stitched_mesh) in front of it")
     if not postprocessing:
         return mesh
     return filter_taubin(mesh, lamb, nu, iterations, **kw)

@@ -273,6 +273,43 @@ hipError_t launch_col_pass(int32_t* face, long long nv, const double* v, const u
                            uint8_t* fkeep, uint8_t* vkeep, int32_t* to, unsigned long long* counts, hipStream_t s);
 hipError_t launch_col_finish(const int32_t* to, const int32_t* vidx, long long nv, int32_t* origin, int32_t* target,
                              hipStream_t s);
+// mesh repair (mm_repair_kernels.hip; include/mm_ccta.h, "mesh repair"): face = the input's int32 triples, never written;
+// rep[i] = the name a vertex goes by between the stages (the first vertex with its coordinates, or i); wf = the faces
+// through rep; fkeep: one byte a face, 0 once dead; counts: the rep_num_* words, cleared by the host.  rep_vertices: rep
+// through an int32 table (at least 2 nv slots), counts[welded] (2 kernels).  rep_faces: wf, qb (the bits of q), frep,
+// fkeep through an int32 table (at least 2 nf slots), counts[degenerate .. copies] (2 kernels).  rep_edges: the edge
+// table of the live faces as weld_edges sizes it, with owners, and eslot[3 f + k] = the slot of the edge leaving corner k
+// (1 kernel).  rep_remove, behind it: m1q, m2q (8 bytes a slot), m1f, m2f (4 bytes a slot) = the two largest keys (q,
+// face) of every slot with more than two owners; with `act` the faces that are neither die, counts[removed]; link[c] =
+// c << 1 for all 3 nf corners (5 kernels).  rep_hook, behind rep_edges of the faces left: the corner sets (1 kernel;
+// launch_weld_jump over 3 nf links flattens them).  rep_split: vmin, wmin, wmax (4 bytes a vertex), ref, vsplit, vback,
+// vkeep (a byte a vertex), mixed, isnew, cback (a byte a corner), counts[unreferenced .. unwelded] (3 kernels).  rep_output: vidx, fidx, cidx are
+// launch_trim_scan of vkeep, fkeep, isnew; kv = the vertices kept; out_v and origin hold kv + the new vertices (2 kernels).
+enum { rep_num_welded = 0, rep_num_degenerate, rep_num_null, rep_num_copies, rep_num_edges_before,
+       rep_num_edges_after = rep_num_edges_before + 3, rep_num_removed = rep_num_edges_after + 3, rep_num_unreferenced,
+       rep_num_split, rep_num_unwelded, rep_num_words = 16 };
+hipError_t launch_rep_vertices(const double* v, long long nv, int weld, int32_t* table, int log2_cap, int32_t* rep,
+                               unsigned long long* counts, hipStream_t s);
+hipError_t launch_rep_faces(const int32_t* face, long long nf, const int32_t* rep, const double* v, int drop_null,
+                            int drop_copies, int32_t* table, int log2_cap, int32_t* wf, unsigned long long* qb,
+                            int32_t* frep, uint8_t* fkeep, unsigned long long* counts, hipStream_t s);
+hipError_t launch_rep_edges(const int32_t* wf, long long nf, const uint8_t* fkeep, unsigned long long* keys,
+                            unsigned int* cnt, unsigned int* own, int log2_cap, unsigned int* eslot, hipStream_t s);
+hipError_t launch_rep_remove(long long nf, uint8_t* fkeep, const unsigned int* eslot, const unsigned int* cnt,
+                             const unsigned long long* qb, int log2_cap, int act, unsigned long long* m1q, int32_t* m1f,
+                             unsigned long long* m2q, int32_t* m2f, unsigned int* link, unsigned long long* counts,
+                             hipStream_t s);
+hipError_t launch_rep_hook(const unsigned long long* keys, const unsigned int* cnt, const unsigned int* own, int log2_cap,
+                           const int32_t* wf, unsigned int* link, hipStream_t s);
+hipError_t launch_rep_split(long long nf, long long nv, const uint8_t* fkeep, const int32_t* face, const int32_t* wf,
+                            const unsigned int* link, const int32_t* rep, int split, int drop, unsigned int* vmin,
+                            unsigned int* wmin, unsigned int* wmax, uint8_t* ref, uint8_t* vsplit, uint8_t* vback,
+                            uint8_t* mixed, uint8_t* isnew, uint8_t* cback, uint8_t* vkeep, unsigned long long* counts,
+                            hipStream_t s);
+hipError_t launch_rep_output(const double* v, long long nv, const int32_t* rep, const int32_t* vidx, long long nf,
+                             const uint8_t* fkeep, const int32_t* fidx, const int32_t* face, const int32_t* wf,
+                             const unsigned int* link, const uint8_t* cback, const int32_t* cidx, long long kv, double* out_v, int32_t* out_f, int32_t* origin,
+                             int32_t* target, hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

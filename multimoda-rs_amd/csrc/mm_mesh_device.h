@@ -1,7 +1,8 @@
 // mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_flip,
-// mm_collapse _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
-// refine and flip files insert, the close, smooth and flip files read, EdgeTable of mm_stage.h sizes it), the workgroup scan
-// and the two per-wave ballot idioms.  Header-only; internal.
+// mm_collapse, mm_repair _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
+// refine, flip and repair files insert, the close, smooth and flip files read, EdgeTable of mm_stage.h sizes it), the
+// first-index-wins table and the hooking union-find of the weld and the repair, the workgroup scan and the two per-wave
+// ballot idioms.  Header-only; internal.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,15 +87,97 @@ static __device__ __forceinline__ unsigned long long edge_find(const unsigned lo
 }
 
 // the edge u - v of face f: its slot claimed, 32-bit atomicAdd on its count; with owners, the first two to arrive leave
-// f << 1 | (f traverses the edge from the smaller to the larger end)
+// f << 1 | (f traverses the edge from the smaller to the larger end).  Returns the slot.
 template <bool kOwners>
-static __device__ __forceinline__ void edge_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
+static __device__ __forceinline__ unsigned long long edge_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt,
                                                    unsigned int* __restrict__ own, unsigned long long mask, int shift,
                                                    int32_t u, int32_t v, unsigned int f)
 {
     const unsigned long long s = edge_claim(keys, mask, shift, u, v);
     const unsigned int p = atomicAdd(&cnt[s], 1u);
     if (kOwners && p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
+    return s;
+}
+
+// ---- the first-index-wins table (the welds of mm_weld_kernels.hip, the repair's duplicates): open addressing over int32
+// slots, kFirstEmpty before, each ending as the SMALLEST index inserted with the slot's key.  A slot is claimed with a
+// 32-bit atomicCAS from empty; a lane that finds it taken asks same(holder) -- every holder of a slot has one key, so
+// whichever it reads answers, provided the key derives from memory no lane writes -- and lowers the slot with atomicMin
+// or probes on.  Returns the slot of i's key; its final value is read in a later launch. ----
+
+static constexpr int32_t kFirstEmpty = -1;
+
+static __device__ __forceinline__ unsigned long long mesh_mix(unsigned long long h, unsigned long long k)
+{
+    h ^= k + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
+    h *= 0xBF58476D1CE4E5B9ull;
+    return h ^ (h >> 31);
+}
+
+template <class Same>
+static __device__ __forceinline__ int32_t first_index_insert(int32_t* __restrict__ table, unsigned long long mask,
+                                                             unsigned long long s, int32_t i, Same same)
+{
+    for (;;) {
+        const int32_t o = atomicCAS(&table[s], kFirstEmpty, i);
+        if (o != kFirstEmpty) {
+            if (!same(o)) { s = (s + 1) & mask; continue; }
+            if (i < o) atomicMin(&table[s], i);
+        }
+        return (int32_t)s;
+    }
+}
+
+static __device__ __forceinline__ void mesh_sort3(int32_t a, int32_t b, int32_t c, int32_t k[3])
+{
+    int32_t t;
+    if (a > b) { t = a; a = b; b = t; }
+    if (b > c) { t = b; b = c; c = t; }
+    if (a > b) { t = a; a = b; b = t; }
+    k[0] = a; k[1] = b; k[2] = c;
+}
+
+// where the probe of a sorted index triple starts
+static __device__ __forceinline__ unsigned long long mesh_triple_slot(const int32_t k[3], int shift)
+{
+    return mesh_mix(mesh_mix(0, ((unsigned long long)k[0] << 32) | (unsigned long long)k[1]), (unsigned long long)k[2]) >> shift;
+}
+
+// ---- the hooking union-find (the winding of mm_weld_kernels.hip over faces, the repair over corners): link[x] =
+// parent << 1 | parity to the parent, x << 1 at a root.  A root hooks under a smaller root with one atomicCAS (parents
+// only ever get smaller: no cycle, and the root of a set ends as its smallest member, whatever the order of arrival);
+// finds halve their path as they go.  Lock-free: a lane only retries after another lane's hook landed.  Rounds of
+// k_weld_jump flatten the links afterwards. ----
+
+static __device__ __forceinline__ unsigned int uf_load(const unsigned int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// the root of x and, xor-ed into *par, x's parity to it; every step moves x's link to its grandparent (any ancestor with
+// the parities added is a valid link, whichever lane writes it last)
+static __device__ __forceinline__ unsigned int uf_find(unsigned int* __restrict__ link, unsigned int x, unsigned int* par)
+{
+    unsigned int wx = uf_load(&link[x]);
+    while ((wx >> 1) != x) {
+        const unsigned int p = wx >> 1;
+        const unsigned int wp = uf_load(&link[p]);
+        if ((wp >> 1) != p) __atomic_store_n(&link[x], (wp & ~1u) | ((wx ^ wp) & 1u), __ATOMIC_RELAXED);
+        *par ^= wx & 1u;
+        x = p;
+        wx = wp;
+    }
+    return x;
+}
+
+// the sets of a and b become one, with parity e between a and b (0 where parities are not in use)
+static __device__ __forceinline__ void uf_union(unsigned int* __restrict__ link, unsigned int a, unsigned int b, unsigned int e)
+{
+    unsigned int pa = 0, pb = 0;
+    for (;;) {
+        a = uf_find(link, a, &pa);
+        b = uf_find(link, b, &pb);
+        if (a == b) break;                                          // joined already (or not orientable)
+        const unsigned int hi = a < b ? b : a, lo = a < b ? a : b;
+        if (atomicCAS(&link[hi], hi << 1, (lo << 1) | (pa ^ pb ^ e)) == hi << 1) break;
+    }
 }
 
 // ---- scans ----

@@ -1,5 +1,5 @@
 // mm_stage.h -- what the CCTA host files (mm_ccta, mm_shape, mm_branch, mm_discretize, mm_bspline, mm_trim, mm_stitch,
-// mm_close, mm_rim, mm_smooth, mm_refine, mm_surface .cpp) share when they stage points or a mesh on the engine's
+// mm_close, mm_rim, mm_smooth, mm_refine, mm_surface, mm_repair .cpp) share when they stage points or a mesh on the engine's
 // grow-only buffers: the engine behind the handle, 256-byte carving, the staged pass of the point kernels, the face
 // checks and the int64 <-> int32 face copies, the edge table's layout, a compaction's counts, the winding stage.
 // Header-only; internal.

@@ -9,10 +9,8 @@
 //   k_weld_mark          ref[v] = 1 for every corner of every face (plain byte stores, benign races).
 //   k_weld_vertex_insert one lane per referenced vertex with a key (the integer triple rint(c * scale)): an
 //                        open-addressing table of int32 slots, each holding the SMALLEST vertex index seen with the
-//                        slot's key.  A slot is claimed with a 32-bit atomicCAS from empty; a lane that finds a slot
-//                        taken re-derives the holder's key from the immutable coordinates (every holder of a slot has
-//                        the same key, so it does not matter which one it reads) and either lowers the slot with
-//                        atomicMin or probes on.  The lane remembers its slot in rep[v].
+//                        slot's key (first_index_insert of mm_mesh_device.h; a holder's key is re-derived from the
+//                        immutable coordinates).  The lane remembers its slot in rep[v].
 //   k_weld_vertex_rep    rep[v] = the slot's final value (v itself without a key, -1 unreferenced), keep[v] = rep[v] == v.
 //   k_weld_vmap / k_weld_face_insert   vmap[v] = the new index of v's representative; a face with a repeated index
 //                        after the weld is dropped, the others go through the same kind of table keyed by their
@@ -21,9 +19,8 @@
 //   k_weld_edge_insert   the three undirected edges of every face into the edge table of mm_mesh_device.h, with a
 //                        count and the first two owners (face << 1 | traverses it from the smaller to the larger end).
 //   k_weld_hook          union-find with parity over the edges owned by exactly two faces: link[f] = parent << 1 |
-//                        parity to the parent.  A root hooks under a smaller root with one atomicCAS (parents only
-//                        ever get smaller: no cycle, and the root of a component ends as its smallest face); finds halve
-//                        their path as they go.  Lock-free: a lane only retries after another lane's hook landed.
+//                        parity to the parent (uf_union of mm_mesh_device.h: the root of a component ends as its
+//                        smallest face).
 //   k_weld_jump          one round of pointer jumping, link[f] -> its grandparent with the parities added.
 //   k_weld_flip          a face of odd parity to its root is reversed (a, b, c) -> (c, b, a); counted per wave.
 //   k_weld_edge_report   open, non-manifold and winding-conflict edges of the table, one integer atomicAdd per wave each.
@@ -38,15 +35,6 @@
 #include "mm_mesh_device.h"
 
 namespace mm {
-
-static constexpr int32_t kWeldEmpty = -1;
-
-static __device__ __forceinline__ unsigned long long weld_mix(unsigned long long h, unsigned long long k)
-{
-    h ^= k + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
-    h *= 0xBF58476D1CE4E5B9ull;
-    return h ^ (h >> 31);
-}
 
 // the weld key of one vertex; false where it matches nothing (a non-finite coordinate or a scaled magnitude >= 2^62)
 static __device__ __forceinline__ bool weld_key(const double* __restrict__ v, long long i, double scale, long long k[3])
@@ -79,19 +67,13 @@ k_weld_vertex_insert(const double* __restrict__ v, long long nv, const uint8_t* 
         if (!ref[i]) { rep[i] = -1; continue; }
         long long k[3];
         if (!weld_key(v, i, scale, k)) { rep[i] = -2; continue; }
-        unsigned long long s = weld_mix(weld_mix(weld_mix(0, (unsigned long long)k[0]), (unsigned long long)k[1]),
-                                        (unsigned long long)k[2]) >> shift;
-        for (;;) {
-            int32_t o = atomicCAS(&table[s], kWeldEmpty, (int32_t)i);
-            if (o != kWeldEmpty) {
-                long long q[3];
-                weld_key(v, o, scale, q);                              // a holder always has a key
-                if (q[0] != k[0] || q[1] != k[1] || q[2] != k[2]) { s = (s + 1) & mask; continue; }
-                if ((int32_t)i < o) atomicMin(&table[s], (int32_t)i);
-            }
-            rep[i] = (int32_t)s;
-            break;
-        }
+        const unsigned long long s = mesh_mix(mesh_mix(mesh_mix(0, (unsigned long long)k[0]), (unsigned long long)k[1]),
+                                              (unsigned long long)k[2]) >> shift;
+        rep[i] = first_index_insert(table, mask, s, (int32_t)i, [&](int32_t o) {
+            long long q[3];
+            weld_key(v, o, scale, q);                                  // a holder always has a key
+            return q[0] == k[0] && q[1] == k[1] && q[2] == k[2];
+        });
     }
 }
 
@@ -113,15 +95,6 @@ k_weld_vertex_rep(long long nv_padded, long long nv, const int32_t* __restrict__
     }
 }
 
-static __device__ __forceinline__ void weld_sort3(int32_t a, int32_t b, int32_t c, int32_t k[3])
-{
-    int32_t t;
-    if (a > b) { t = a; a = b; b = t; }
-    if (b > c) { t = b; b = c; c = t; }
-    if (a > b) { t = a; a = b; b = t; }
-    k[0] = a; k[1] = b; k[2] = c;
-}
-
 // vmap[v] = the new index of the vertex v was welded into (-1 unreferenced): vidx is the scan of keep
 __global__ void __launch_bounds__(kMeshThreads)
 k_weld_vmap(long long nv, const int32_t* __restrict__ rep, const int32_t* __restrict__ vidx, int32_t* __restrict__ vmap)
@@ -138,21 +111,12 @@ k_weld_face_insert(const int32_t* __restrict__ face, long long nf, const int32_t
         const int32_t a = vmap[face[3 * f]], b = vmap[face[3 * f + 1]], c = vmap[face[3 * f + 2]];
         if (a == b || b == c || a == c) { frep[f] = -1; continue; }
         int32_t k[3];
-        weld_sort3(a, b, c, k);
-        unsigned long long s = weld_mix(weld_mix(0, ((unsigned long long)k[0] << 32) | (unsigned long long)k[1]),
-                                        (unsigned long long)k[2]) >> shift;
-        for (;;) {
-            int32_t o = atomicCAS(&table[s], kWeldEmpty, (int32_t)f);
-            if (o != kWeldEmpty) {
-                int32_t q[3];
-                weld_sort3(vmap[face[3 * (long long)o]], vmap[face[3 * (long long)o + 1]],
-                           vmap[face[3 * (long long)o + 2]], q);
-                if (q[0] != k[0] || q[1] != k[1] || q[2] != k[2]) { s = (s + 1) & mask; continue; }
-                if ((int32_t)f < o) atomicMin(&table[s], (int32_t)f);
-            }
-            frep[f] = (int32_t)s;
-            break;
-        }
+        mesh_sort3(a, b, c, k);
+        frep[f] = first_index_insert(table, mask, mesh_triple_slot(k, shift), (int32_t)f, [&](int32_t o) {
+            int32_t q[3];
+            mesh_sort3(vmap[face[3 * (long long)o]], vmap[face[3 * (long long)o + 1]], vmap[face[3 * (long long)o + 2]], q);
+            return q[0] == k[0] && q[1] == k[1] && q[2] == k[2];
+        });
     }
 }
 
@@ -192,24 +156,6 @@ k_weld_link_init(unsigned int* __restrict__ link, long long nf)
     for (long long f = mesh_tid(); f < nf; f += mesh_stride()) link[f] = (unsigned int)f << 1;
 }
 
-static __device__ __forceinline__ unsigned int weld_load(const unsigned int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
-// the root of x and, xor-ed into *par, x's parity to it; every step moves x's link to its grandparent (any ancestor with
-// the parities added is a valid link, whichever lane writes it last)
-static __device__ __forceinline__ unsigned int weld_find(unsigned int* __restrict__ link, unsigned int x, unsigned int* par)
-{
-    unsigned int wx = weld_load(&link[x]);
-    while ((wx >> 1) != x) {
-        const unsigned int p = wx >> 1;
-        const unsigned int wp = weld_load(&link[p]);
-        if ((wp >> 1) != p) __atomic_store_n(&link[x], (wp & ~1u) | ((wx ^ wp) & 1u), __ATOMIC_RELAXED);
-        *par ^= wx & 1u;
-        x = p;
-        wx = wp;
-    }
-    return x;
-}
-
 __global__ void __launch_bounds__(kMeshThreads)
 k_weld_hook(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ cnt,
             const unsigned int* __restrict__ own, unsigned long long cap, unsigned int* __restrict__ link)
@@ -219,15 +165,7 @@ k_weld_hook(const unsigned long long* __restrict__ keys, const unsigned int* __r
         const unsigned int oa = own[2 * s], ob = own[2 * s + 1];
         unsigned int a = oa >> 1, b = ob >> 1;
         if (a == b) continue;
-        unsigned int pa = 0, pb = 0;
-        const unsigned int e = ((oa ^ ob) & 1u) ^ 1u;                   // same direction: the two faces differ by a flip
-        for (;;) {
-            a = weld_find(link, a, &pa);
-            b = weld_find(link, b, &pb);
-            if (a == b) break;                                          // joined already (or not orientable)
-            const unsigned int hi = a < b ? b : a, lo = a < b ? a : b;
-            if (atomicCAS(&link[hi], hi << 1, (lo << 1) | (pa ^ pb ^ e)) == hi << 1) break;
-        }
+        uf_union(link, a, b, ((oa ^ ob) & 1u) ^ 1u);                    // same direction: the two faces differ by a flip
     }
 }
 
@@ -236,9 +174,9 @@ __global__ void __launch_bounds__(kMeshThreads)
 k_weld_jump(unsigned int* __restrict__ link, long long nf, unsigned int* __restrict__ changed)
 {
     for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
-        const unsigned int wx = weld_load(&link[f]);
+        const unsigned int wx = uf_load(&link[f]);
         const unsigned int p = wx >> 1;
-        const unsigned int wp = weld_load(&link[p]);
+        const unsigned int wp = uf_load(&link[p]);
         if ((wp >> 1) != p) {
             __atomic_store_n(&link[f], (wp & ~1u) | ((wx ^ wp) & 1u), __ATOMIC_RELAXED);
             *changed = 1u;
