@@ -170,6 +170,101 @@ int     mm_align_combined(mm_engine* e, const mm_clpoint* cl, int64_t ncl, mm_cl
                           int align_wall_anomalous, double* spacing, double* total_rotation,
                           int64_t* refined_idx, int64_t* n_evals);
 
+/* ---- centerline from a mesh: geodesic field, band skeleton, tree (mm_geodesic.cpp, mm_geodesic_kernels.hip; DESIGN
+ * 4.26).  The reference has no such function ("Create Centerline directly from mesh" is an open item of its roadmap); the
+ * rules are this project's own, restated in tests/mm_checkers/mesh_skeleton.py.  Arguments as the mesh calls of
+ * mm_ccta.h: nv, nf, n_seeds below 2^31 and 6 nf below 2^31 (MM_ERR_TOO_LARGE), a face index or a seed outside [0, nv),
+ * n_seeds == 0 and a band that is not finite and positive are MM_ERR_INVALID before anything is allocated; nv == 0
+ * launches nothing.  Coordinates may be anything: an edge with an end that is not finite is skipped, not refused.
+ *
+ * Rule G, the field.  The graph is the distinct undirected edges {lo < hi} of the faces; (a, a) is not an edge.  An
+ * edge weighs w = sqrt((dx dx + dy dy) + dz dz), d = v[hi] - v[lo] per component, unfused f64, computed once so that
+ * both directions see the same bits; an edge whose weight is not finite is left out and counted (n_skipped_edges).
+ * dist[s] = +0.0 at the seeds; elsewhere dist[v] is the minimum over the edge paths from any seed of the sum of the
+ * weights along the path, rounded after every addition, from the seed on; +inf where no path arrives.  That is what
+ * Dijkstra's algorithm returns, and it is the one fixpoint of d[v] = min(d[v], fl(d[u] + w)) below the start, in any
+ * order, because the rounded addition of a non-negative weight is monotone: the result has one bit pattern whatever the
+ * schedule.  pred[v] = the smallest neighbour u with fl(dist[u] + w(u, v)) == dist[v], -1 at seeds and where dist is
+ * +inf (edges of weight zero can make two vertices each other's predecessor).  n_edges counts the edges kept,
+ * n_reached the vertices with a finite distance (seeds included), max_dist the largest finite distance, max_edge the
+ * longest finite weight.  rounds, n_batches and n_launches describe the schedule and are no function of the input
+ * alone: a round relaxes every flagged block of 256 consecutive vertices to its local fixpoint, and the host reads the
+ * rounds' marks once per batch of 8, 16, 32, then 64 rounds. */
+typedef struct {
+    int64_t n_vertices, n_faces, n_edges, n_skipped_edges, n_reached, rounds, n_batches, n_launches, bytes_uploaded,
+            bytes_downloaded;
+    double  max_dist, max_edge;
+} mm_geodesic_report;
+
+int     mm_mesh_geodesic(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                         const int64_t* seeds, int64_t n_seeds, double* dist, int64_t* pred, mm_geodesic_report* report);
+
+/* Rule S, the nodes (on the device, mesh and field resident: one upload, one download).  band[v] = (int64)(dist[v] /
+ * band_mm) where dist is finite, from one f64 division, -1 elsewhere; a quotient of 2^31 or more is MM_ERR_TOO_LARGE.  A
+ * node is a connected component, under the graph's edges, of the vertices of one band; nodes are numbered by (band,
+ * smallest vertex) ascending and vertex_node[v] is that number, or -1.  A band narrower than the edges breaks the rings
+ * into crumbs: callers take twice the longest edge (the report's field.max_edge) unless they know better.
+ *   Sums, area-weighted.  a_f = 0.5 * sqrt((cx cx + cy cy) + cz cz), c = (v1 - v0) x (v2 - v0), c_x = e1_y e2_z - e1_z
+ * e2_y and so on; a3 = a_f / 3.  Over the faces in ascending index and in each the corners 0, 1, 2, a corner whose
+ * vertex p lies in node n adds a3 to W_n and a3 * p to S_n per component, sequentially, unfused f64; centre = S_n / W_n;
+ * radius = (the same sum of a3 * |p - centre|) / W_n; weight = W_n.  A node with a corner whose a3 is not finite, or
+ * with W_n not above zero, takes the plain mean of its vertices in ascending index instead (the sum, then one division
+ * by their number), radius the plain mean of |p - centre|, weight +0.0, and flag bit 1.  radius_min is the smallest
+ * |p - centre| over the node's vertices (a NaN is passed over).  |d| = sqrt((dx dx + dy dy) + dz dz).
+ *   flags bit 0: the node holds a rim vertex that is not a seed -- an end of an edge {lo < hi} that exactly one corner
+ * of one face spans, as the trimming counts open edges; bit 1: the plain mean was used; bit 2: the node holds a seed.
+ *   Node edges: the distinct pairs (lo node < hi node) joined by at least one edge of the graph, sorted.
+ * Capacities as mm_mesh_adjacency_csr: where n_nodes > node_cap or n_node_edges > edge_cap the report holds both counts,
+ * nothing else is written and MM_ERR_TOO_LARGE returns.  union_rounds, n_launches and the field's schedule numbers are no
+ * function of the input alone. */
+typedef struct {
+    double  x, y, z, radius, radius_min, weight;
+    int64_t band, first_vertex, n_vertices, flags;
+} mm_skeleton_node;
+
+typedef struct {
+    mm_geodesic_report field;
+    int64_t n_nodes, n_node_edges, union_rounds, n_launches, bytes_uploaded, bytes_downloaded;
+    double  band_mm;
+} mm_skeleton_report;
+
+int     mm_mesh_skeleton(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf,
+                         const int64_t* seeds, int64_t n_seeds, double band_mm, int64_t node_cap, int64_t edge_cap,
+                         double* dist, int64_t* pred, int64_t* vertex_node, mm_skeleton_node* nodes, int64_t* edges,
+                         mm_skeleton_report* report);
+
+/* Rule T, terminals, tree, branches (host only, no engine).  nodes in band order (as mm_mesh_skeleton numbers them),
+ * edges lo < hi; a terminal is a point behind a node (the node of a rim loop's smallest vertex).
+ *   Parent: the adjacent node of lower band with the smallest number; a node with flag bit 2, or without a lower
+ * neighbour, is a root.  n_loops = edges - nodes + components, reported, never an error.
+ *   Open ends: a node with flag bit 0 is dropped when all its descendants have the bit too (the partial rings before an
+ * open outlet, whose centroids walk off to the wall); a root is never dropped; elsewhere the bit means nothing here.
+ *   Terminals: terminal j becomes point n_nodes + j, a leaf behind the first kept node on the parent chain from its node.
+ *   Paths: the length of a tree edge is |child - parent| = sqrt((dx dx + dy dy) + dz dz), a path's length the sum from its
+ * upper end down, left to right.  Roots in ascending number.  A root's first branch is its path to the leaf of greatest
+ * length from the root (the smaller number among equals).  Then, repeatedly, of the leaves not yet taken the one whose
+ * path down from its first ancestor already in the output (the junction) is longest, the smaller number among equals: it
+ * is pruned when that length is below min_branch_mm -- below twice the junction's radius where min_branch_mm is negative --
+ * and the leaf is no terminal; else it becomes the next branch, from its first point off the junction to the leaf.
+ * Branch ids count from 0 across the roots; the first root's first branch is branch 0, the main vessel.
+ *   Output: out (cap >= n_nodes + n_terminals points) with radius = the node's or terminal's, tangents by the rule of
+ * recompute_tangents; point_node[i] = the node (or n_nodes + j) of point i; branch_info[4 b ..] = parent branch, the
+ * junction's index in out (-1, -1 for a root's first branch), 1 where the branch ends in a terminal, its number of
+ * points.  Returns the number of points, or a negative error. */
+typedef struct {
+    double  x, y, z, radius;
+    int64_t node;
+} mm_skeleton_terminal;
+
+typedef struct {
+    int64_t n_points, n_branches, n_roots, n_components, n_loops, n_dropped_open, n_pruned, n_terminals;
+} mm_tree_report;
+
+int64_t mm_skeleton_centerline(const mm_skeleton_node* nodes, int64_t n_nodes, const int64_t* edges, int64_t n_edges,
+                               const mm_skeleton_terminal* terminals, int64_t n_terminals, double min_branch_mm,
+                               mm_clpoint* out, int64_t* point_node, int64_t* branch_info, int64_t cap,
+                               mm_tree_report* report);
+
 #ifdef __cplusplus
 }
 #endif

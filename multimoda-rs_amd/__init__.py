@@ -44,6 +44,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
 from . import surface
 from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport, point_mesh_distance,
                       sample_mesh_surface, surface_distance)
+from . import skeleton
+from .skeleton import SkeletonGraph, centerline_from_mesh, mesh_geodesic_distance, mesh_skeleton, skeleton_centerline
 from .convert import numpy_to_geometry, to_array
 from . import morphometry
 from .morphometry import ContourMeasures, contour_measures
@@ -87,6 +89,7 @@ __all__ = [
     "repair_mesh", "mesh_manifold_report", "fix_and_remesh_stitched_mesh",
     "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
     "DirectedDistance", "SurfaceDistanceReport",
+    "skeleton", "mesh_geodesic_distance", "mesh_skeleton", "centerline_from_mesh", "skeleton_centerline", "SkeletonGraph",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",
     "MM_PRECISION_F32", "MM_PRECISION_F32_BOUNDED", "MM_PRECISION_F32_FAST", "MM_PRECISION_F32_MATRIX", "MM_PRECISION_F64", "MM_SEARCH_SKIP_ZERO",

@@ -56,6 +56,7 @@ EXPORTS_CENTERLINE = [
     "mm_centerline_calculate_branches", "mm_centerline_find_sharp_angles", "mm_centerline_split_branch",
     "mm_centerline_merge_branches", "mm_centerline_orient_by_max_z", "mm_centerline_orient_to_reference",
     "mm_centerline_remove_branch_overlap", "mm_centerline_trim_start", "mm_centerline_smooth",
+    "mm_mesh_geodesic", "mm_mesh_skeleton", "mm_skeleton_centerline",
 ]
 
 
@@ -207,6 +208,26 @@ class MMRepairReport(C.Structure):
         "n_nonmanifold_edges_before", "n_nonmanifold_edges_after", "n_faces_removed", "n_nonmanifold_vertices",
         "n_new_vertices", "n_unreferenced_dropped", "n_open_edges_before", "n_open_edges_after", "union_rounds",
         "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMGeodesicReport(C.Structure):
+    """``mm_geodesic_report`` (include/mm_centerline.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_vertices", "n_faces", "n_edges", "n_skipped_edges", "n_reached", "rounds", "n_batches", "n_launches",
+        "bytes_uploaded", "bytes_downloaded")] + [("max_dist", C.c_double), ("max_edge", C.c_double)]
+
+
+class MMSkeletonReport(C.Structure):
+    """``mm_skeleton_report`` (include/mm_centerline.h)."""
+    _fields_ = [("field", MMGeodesicReport)] + [(name, C.c_int64) for name in (
+        "n_nodes", "n_node_edges", "union_rounds", "n_launches", "bytes_uploaded", "bytes_downloaded")] + \
+               [("band_mm", C.c_double)]
+
+
+class MMTreeReport(C.Structure):
+    """``mm_tree_report`` (include/mm_centerline.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_points", "n_branches", "n_roots", "n_components", "n_loops", "n_dropped_open", "n_pruned", "n_terminals")]
 
 
 class MMRimParams(C.Structure):
@@ -531,6 +552,12 @@ def lib():
     L.mm_centerline_trim_start.argtypes = [P, I64, D, P]
     L.mm_centerline_smooth.restype = I64
     L.mm_centerline_smooth.argtypes = [P, I64, D, P]
+    L.mm_mesh_geodesic.restype = I
+    L.mm_mesh_geodesic.argtypes = [P, P, I64, P, I64, P, I64, P, P, C.POINTER(MMGeodesicReport)]
+    L.mm_mesh_skeleton.restype = I
+    L.mm_mesh_skeleton.argtypes = [P, P, I64, P, I64, P, I64, D, I64, I64, P, P, P, P, P, C.POINTER(MMSkeletonReport)]
+    L.mm_skeleton_centerline.restype = I64
+    L.mm_skeleton_centerline.argtypes = [P, I64, P, I64, P, I64, D, P, P, P, I64, C.POINTER(MMTreeReport)]
     L.mm_align_three_point.restype = I
     L.mm_align_three_point.argtypes = [P, I64, P, I, U32, P, P, P, D, I, C.POINTER(D), C.POINTER(D)]
     L.mm_align_walls.restype = I

@@ -248,6 +248,10 @@ int64_t first_run(const mm_clpoint* cl, int64_t n)                              
 bool bad(const mm_clpoint* cl, int64_t n, const void* out) { return n < 0 || (n > 0 && (!cl || !out)); }
 
 }  // namespace
+
+// recompute_tangents for the other files that build a centerline (mm_geodesic.cpp)
+void cl_recompute_tangents(mm_clpoint* p, int64_t n) { recompute_tangents(p, n); }
+
 }  // namespace mm
 
 using namespace mm;

@@ -173,6 +173,12 @@ hipError_t launch_smooth_csr(const int32_t* off, const int32_t* nb, long long nv
 // distinct seeds; mesh_ring: ring r >= 1 of the level-synchronous search, *reached += the vertices it set.  mesh_disp:
 // *max_bits = the bits of the largest squared distance between a and b
 size_t     mesh_csr_tiles(long long nv);
+// the two halves of mesh_csr that do not read the table, for any rows: row_offsets: off (n + 1) = the exclusive scan of
+// the n row lengths in deg, which become the rows' fill cursors, counts[1] += the empty rows, counts[2] = max(counts[2],
+// the longest), n >= 1 (3 kernels); row_sort: every row of nb ascending (its entries are distinct; 1 kernel)
+hipError_t launch_mesh_row_offsets(int32_t* deg, long long n, int32_t* off, long long* tile_sum, unsigned long long* counts,
+                                   int* launches, hipStream_t s);
+hipError_t launch_mesh_row_sort(const int32_t* off, int32_t* nb, long long n, int* launches, hipStream_t s);
 hipError_t launch_mesh_csr(const unsigned long long* keys, int log2_cap, long long nv, int32_t* deg, int32_t* off,
                            long long* tile_sum, int32_t* nb, unsigned long long* counts, int* launches, hipStream_t s);
 hipError_t launch_mesh_step(const int32_t* off, const int32_t* nb, const double* in, double* out, long long nv, double f,
@@ -310,6 +316,55 @@ hipError_t launch_rep_output(const double* v, long long nv, const int32_t* rep, 
                              const uint8_t* fkeep, const int32_t* fidx, const int32_t* face, const int32_t* wf,
                              const unsigned int* link, const uint8_t* cback, const int32_t* cidx, long long kv, double* out_v, int32_t* out_f, int32_t* origin,
                              int32_t* target, hipStream_t s);
+// geodesic field (mm_geodesic_kernels.hip; include/mm_centerline.h, "Rule G"): off, nb = the sorted adjacency of
+// launch_mesh_csr; w = one weight per entry of nb; dist = the bits of the field, one word a vertex; flags: geo_blocks(nv)
+// words each.  geo_weights: w, counts[skipped] += the edges without a finite weight, counts[max_edge] = the bits of the
+// longest finite one (counts cleared by the host).  geo_seed: dist = +inf, +0.0 at the seeds, is_seed, flag_a raised at
+// the blocks of the seeds and their neighbours, flag_b cleared (2 kernels).  geo_round: one round; the blocks flagged in
+// cur run and clear their flag, *mark += the flags they raise in next (all 0 before).  geo_pred: pred,
+// counts[reached], counts[max_dist].
+enum { geo_num_skipped = 0, geo_num_max_edge, geo_num_reached, geo_num_max_dist, geo_num_band_over, geo_num_csr,
+       geo_num_words = geo_num_csr + 4 };
+size_t     geo_blocks(long long nv);
+hipError_t launch_geo_weights(const double* v, const int32_t* off, const int32_t* nb, long long nv, double* w,
+                              unsigned long long* counts, hipStream_t s);
+hipError_t launch_geo_seed(const int32_t* seeds, long long n_seeds, const int32_t* off, const int32_t* nb, long long nv,
+                           unsigned long long* dist, uint8_t* is_seed, unsigned int* flag_a, unsigned int* flag_b,
+                           hipStream_t s);
+hipError_t launch_geo_round(const int32_t* off, const int32_t* nb, const double* w, long long nv, unsigned long long* dist,
+                            unsigned int* cur, unsigned int* next, unsigned long long* mark, hipStream_t s);
+hipError_t launch_geo_pred(const int32_t* off, const int32_t* nb, const double* w, const unsigned long long* dist,
+                           const uint8_t* is_seed, long long nv, int32_t* pred, unsigned long long* counts, hipStream_t s);
+// band skeleton (mm_geodesic_kernels.hip; "Rule S").  geo_sort: keys[0 .. n) ascending, distinct and below ~0, in a buffer
+// of geo_sort_size(n) entries (a bitonic network; *launches += its kernels).  skel_bands: band, counts[band_over] set
+// where a band index reaches 2^31, link = the hooking union-find over the edges inside a band (2 kernels;
+// launch_weld_jump flattens it).  skel_roots: is_root.  skel_keys: keys[ridx[i]] = band << 32 | i at the roots (ridx:
+// launch_trim_scan of is_root).  skel_number, behind the sort: node_of_root, rim (from the edge table's counts), vnode,
+// nflags (bits 0 and 2), vcnt; ccnt cleared (3 kernels).  skel_faces: area3[f] = a_f / 3, ccnt (1 kernel, none without
+// faces).  skel_fill: the corner and vertex lists through the cursors launch_mesh_row_offsets left.  skel_nodes: the
+// records, ten 8-byte words a node.  skel_edges: the node pairs through the edge table's keys (cleared here) into out,
+// unordered, *n_out their number (2 kernels).
+long long  geo_sort_size(long long n);
+hipError_t launch_geo_sort(unsigned long long* keys, long long n, int* launches, hipStream_t s);
+hipError_t launch_skel_bands(const unsigned long long* dist, long long nv, double h, const int32_t* off, const int32_t* nb,
+                             const double* w, int32_t* band, unsigned int* link, unsigned long long* counts, hipStream_t s);
+hipError_t launch_skel_roots(const unsigned int* link, const int32_t* band, long long nv, uint8_t* is_root, hipStream_t s);
+hipError_t launch_skel_keys(const int32_t* ridx, const int32_t* band, long long nv, long long n_nodes,
+                            unsigned long long* keys, hipStream_t s);
+hipError_t launch_skel_number(const unsigned long long* keys, long long n_nodes, int32_t* node_of_root,
+                              const unsigned long long* ekeys, const unsigned int* ecnt, int log2_cap,
+                              const unsigned int* link, const int32_t* band, const uint8_t* is_seed, long long nv,
+                              uint8_t* rim, int32_t* vnode, unsigned int* nflags, int32_t* vcnt, int32_t* ccnt, hipStream_t s);
+hipError_t launch_skel_faces(const double* v, const int32_t* face, long long nf, const int32_t* vnode, double* area3,
+                             int32_t* ccnt, hipStream_t s);
+hipError_t launch_skel_fill(const int32_t* face, long long nf, const int32_t* vnode, long long nv, int32_t* ccur,
+                            int32_t* clist, int32_t* vcur, int32_t* vlist, hipStream_t s);
+hipError_t launch_skel_nodes(long long n_nodes, const int32_t* coff, const int32_t* clist, const int32_t* voff,
+                             const int32_t* vlist, const int32_t* face, const double* area3, const double* v,
+                             const int32_t* band, const unsigned int* nflags, double* rec, hipStream_t s);
+hipError_t launch_skel_edges(const int32_t* off, const int32_t* nb, const double* w, const int32_t* vnode, long long nv,
+                             unsigned long long* keys, int log2_cap, unsigned long long* out, unsigned long long* n_out,
+                             hipStream_t s);
 // rim conditioning (mm_rim_kernels.hip): v = xyz triples, face = int32 triples, index = int32 vertex indices or -1.
 // rim_locate: index[k] = the last vertex equal by value to query k (q: 3 r folded bit patterns; index holds -1 before);
 // rim_write: v[index[i]] = pts[i]; rim_mark: arr[index[i]] = i (by_position) or 0; rim_layer: ring k of the BFS layers

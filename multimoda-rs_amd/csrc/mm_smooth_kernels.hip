@@ -243,21 +243,33 @@ k_smooth_disp(const double* __restrict__ a, const double* __restrict__ b, long l
 
 size_t mesh_csr_tiles(long long nv) { return scan_tiles(nv); }
 
+hipError_t launch_mesh_row_offsets(int32_t* deg, long long n, int32_t* off, long long* tile_sum, unsigned long long* counts,
+                                   int* launches, hipStream_t s)
+{
+    const long long tiles = (long long)scan_tiles(n);
+    SMOOTH_LAUNCH(k_smooth_scan_count, (unsigned)tiles, deg, n, tile_sum);
+    SMOOTH_LAUNCH(k_smooth_scan_tiles, 1u, tile_sum, tiles, off, n);
+    SMOOTH_LAUNCH(k_smooth_scan_offsets, (unsigned)tiles, deg, n, tile_sum, off, counts);
+    return hipSuccess;
+}
+
+hipError_t launch_mesh_row_sort(const int32_t* off, int32_t* nb, long long n, int* launches, hipStream_t s)
+{
+    SMOOTH_LAUNCH(k_smooth_row_sort, mesh_grid(n), off, nb, n);
+    return hipSuccess;
+}
+
 hipError_t launch_mesh_csr(const unsigned long long* keys, int log2_cap, long long nv, int32_t* deg, int32_t* off,
                            long long* tile_sum, int32_t* nb, unsigned long long* counts, int* launches, hipStream_t s)
 {
     const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
-    const long long tiles = (long long)scan_tiles(nv);
     hipError_t he;
     if ((he = hipMemsetAsync(deg, 0, (size_t)nv * 4, s)) != hipSuccess) return he;
     if ((he = hipMemsetAsync(counts, 0, 4 * 8, s)) != hipSuccess) return he;
     SMOOTH_LAUNCH(k_smooth_degree, mesh_grid((long long)cap), keys, cap, deg, counts);
-    SMOOTH_LAUNCH(k_smooth_scan_count, (unsigned)tiles, deg, nv, tile_sum);
-    SMOOTH_LAUNCH(k_smooth_scan_tiles, 1u, tile_sum, tiles, off, nv);
-    SMOOTH_LAUNCH(k_smooth_scan_offsets, (unsigned)tiles, deg, nv, tile_sum, off, counts);
+    if ((he = launch_mesh_row_offsets(deg, nv, off, tile_sum, counts, launches, s)) != hipSuccess) return he;
     SMOOTH_LAUNCH(k_smooth_fill, mesh_grid((long long)cap), keys, cap, deg, nb);
-    SMOOTH_LAUNCH(k_smooth_row_sort, mesh_grid(nv), off, nb, nv);
-    return hipSuccess;
+    return launch_mesh_row_sort(off, nb, nv, launches, s);
 }
 
 hipError_t launch_mesh_step(const int32_t* off, const int32_t* nb, const double* in, double* out, long long nv, double f,
