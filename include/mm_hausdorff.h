@@ -145,8 +145,8 @@ int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
  * MM_PRECISION_F32_MATRIX chooses per PAIR: only pairs with a set of fewer than 64 or more than 2048 points (or a radius
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
-/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull, mm_engine_set_screen_split and
- * mm_engine_set_screen_group apply to the levels staged
+/* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull, mm_engine_set_screen_split,
+ * mm_engine_set_screen_group and mm_engine_set_screen_pair apply to the levels staged
  * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
  * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
@@ -174,6 +174,11 @@ int  mm_engine_set_screen_split(mm_engine* e, int on);
  * pair's list, is at most 3.5 degrees, and never more than a quarter of a work item; 1: off (the A/B switch); 2, 4, 8:
  * forced, with work items of at least four groups.  Other values: MM_ERR_INVALID. */
 int  mm_engine_set_screen_group(mm_engine* e, int group);
+/* The culled screen's groups of four and eight run their followers' phase 1 two at a time: one pass over the group's tile
+ * list serves both (default, on != 0; a group's first candidate and a follower left over run alone).  on == 0: every
+ * follower alone, the A/B switch.  Values, tile counts and the followers' counters are the same either way, bit for bit;
+ * mm_screen_values_group takes the engine's setting. */
+int  mm_engine_set_screen_pair(mm_engine* e, int on);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);

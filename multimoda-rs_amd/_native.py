@@ -32,7 +32,7 @@ EXPORTS = [
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_engine_screen_early", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
-    "mm_engine_set_screen_group", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
+    "mm_engine_set_screen_group", "mm_engine_set_screen_pair", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -380,6 +380,8 @@ def lib():
     L.mm_tile_bound_probe_split.argtypes = [P, P, I, P, P, I, I, I, I, C.c_float, C.c_float, D, P, P]
     L.mm_engine_set_screen_group.restype = I
     L.mm_engine_set_screen_group.argtypes = [P, I]
+    L.mm_engine_set_screen_pair.restype = I
+    L.mm_engine_set_screen_pair.argtypes = [P, I]
     L.mm_screen_values_group.restype = I
     L.mm_screen_values_group.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, I, P, P, P, I, P]
     L.mm_tile_bound_probe_group.restype = I
@@ -1040,6 +1042,12 @@ class Engine:
         """Culled screen: consecutive candidates of a pair that share one tile bound and mask set.  0: chosen per pair from
         its candidate list (default); 1: off; 2, 4, 8: forced."""
         check(lib().mm_engine_set_screen_group(self._h, int(group)), "mm_engine_set_screen_group")
+
+    def set_screen_pair(self, on: bool):
+        """Culled screen: a group's followers run their phase 1 two at a time, one pass over the group's tile list for both
+        (default).  Off: every follower alone.  Values and counters are the same either way; ``screen_values_group`` takes
+        this setting."""
+        check(lib().mm_engine_set_screen_pair(self._h, int(bool(on))), "mm_engine_set_screen_pair")
 
     def screen_values_group(self, ref, tgt, angles, centre, group, cull=True, skip_zero=True, split=(0, 0)):
         """TEST HOOK (``mm_screen_values_group``): ``screen_values`` with the group size given; returns the values, e2 and

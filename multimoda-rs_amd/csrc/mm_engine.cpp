@@ -337,7 +337,7 @@ int Plan::run(bool screen_only)
                 case Screen::Matrix: e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s); break;
                 case Screen::MatrixCull:
                     eng->cull_tiles_full += g.tiles_full;
-                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, s);
+                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, lv.opts.screen_pair ? 1 : 0, s);
                     break;
                 }
                 if (e != hipSuccess) break;
@@ -918,6 +918,14 @@ int mm_engine_set_screen_group(mm_engine* h, int group)
     return MM_OK;
 }
 
+int mm_engine_set_screen_pair(mm_engine* h, int on)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    e->screen_opts.screen_pair = on != 0;
+    return MM_OK;
+}
+
 int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
 {
     Engine* e = reinterpret_cast<Engine*>(h);
@@ -1108,7 +1116,8 @@ int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int
                                   e2, nullptr, 0, nullptr);
 }
 
-// The same with the culled screen's group size given (1, 2, 4, 8; 0: the engine's choice for this list): the two hooks above
+// The same with the culled screen's group size given (1, 2, 4, 8; 0: the engine's choice for this list; the followers run in
+// pairs or alone as the engine's switch says, mm_engine_set_screen_pair): the two hooks above
 // screen candidate by candidate (group 1).  items (nullable, room for items_cap triples): the plan's work items as
 // (first candidate, candidates, group size) -- what the kernel's waves split into groups; *n_items: their number.
 int mm_screen_values_group(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,

@@ -998,7 +998,7 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // as described; the others take its phase-2 tiles into phase 1 (a superset there only lowers Umax and Vmax) and clear them
 // from their own phase-2 masks.  G = 1: the rule per candidate, from the same circle bit for bit.
 // A follower's phase 2 is then almost always empty, and it finds that out without the column maxima and the masks.  Its
-// phase-1 mask p1m = m1 | carry and thr are the group's, so once per group, behind the leader: Tr_I, the smallest thr(I, J)
+// phase-1 mask p1m (m1 and the leader's phase-2 tiles) and thr are the group's, so once per group, behind the leader: Tr_I, the smallest thr(I, J)
 // of row tile I over the tiles outside p1m, and Tc_J, the same down column tile J (0x7f800000 where there is none; each
 // such thr is positive).  The rule above puts a tile outside p1m into m2 unless thr >= max(Umax_I, Vmax_J): m2 is empty for
 // every row tile exactly when Umax_I <= Tr_I for every I and Vmax_J <= Tc_J for every J, that is when no lane's met row
@@ -1007,6 +1007,14 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // met minima, which is what the general path returns with empty masks (every row tile final with Umax_I); one that does
 // not falls into the general path as it stands.  tiles_done[1], [2] count the followers that left early and all followers
 // (mm_engine_screen_early).
+// Pairs (pair_on, ScreenOptions::screen_pair): every follower of a group has the group's phase-1 mask, so two followers in a row
+// (X = k0 + 1 and Y = k0 + 2, k0 + 3 and k0 + 4, ...) share ONE pass over it -- one mask read, one set-bit loop, one tile index
+// and one A fragment for both (mxc_tiles2); Y's fragments go through the same wave-private s_b behind X's, its row minima into
+// a row store of its own.  Each then takes the group test, and one that stays runs the general path on its own registers
+// and row store, X before Y (one copy of that path in the code: Y's state moves into X's variables).  The leader and a
+// follower left over run alone.  Neither a candidate's masks nor an MFMA's operands change, and a candidate's folds are its
+// own sequence over the same tiles in the same order: every cm, rmin, fmax and late has the bits of the unpaired path,
+// and the counters count per candidate what they count there.
 // Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
 // -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
 // no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
@@ -1050,44 +1058,125 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
 // section's instructions run once per <trips> (1, nrt, rows2, half, tiles; group and ghalf: once and once per two row tiles,
 // per GROUP of candidates; fgroup and fgnrt: once and once per row tile, per group that has followers; lrows and frows: once
 // per row tile of a leader and of a follower; fol, early, late: once per follower, per follower that leaves after phase 1,
-// per candidate that does not; "tile" is a computed tile's own body).
+// per candidate that does not; "tile" is a computed tile's own body; the pairs' counts -- xcand, pair, single, prows, ptiles,
+// tails, ptails, sfol, searly, pearly, ylate -- are listed in the tool).
 #define MXC_MARK(s) __asm__ volatile("; mxc:" s)
 #define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
 
 // one register per column tile, indexed by the wave-uniform tile index (a uniform index into a register vector is an
 // indexed register move, no branch per tile)
-template <int N> struct mxc_regs { typedef int type __attribute__((ext_vector_type(N))); };
+// A register vector is a register TUPLE, and a tuple of 17 takes the room of 32: the first N - 1 column tiles are the indexed
+// vector (16 registers for the 17 tiles of the set-bit variant) and the last tile has a register of its own, reached by name
+// behind the loop over the others (a mask's last bit is its last tile: the order of a candidate's folds is not changed).
+template <int N> struct mxc_regs {
+    typedef int vec __attribute__((ext_vector_type(N - 1)));
+    struct type {
+        vec v;
+        int last;
+        __device__ __forceinline__ int get(int t) const { return t < N - 1 ? v[t] : last; }          // (t a constant)
+        __device__ __forceinline__ void set(int t, int x) { if (t < N - 1) v[t] = x; else last = x; }
+    };
+};
 typedef int mxc_i4 __attribute__((ext_vector_type(4)));
 
+// one tile of one candidate: D = A.B and D' = B.A, both MFMAs in flight before the minima
+static __device__ __forceinline__ void mxc_tile(const h8v& af, int lo, int hi, int& c, int& rmin)
+{
+    const f16x16 z = {};
+    // a column fragment's K slots 4..7 repeat its slots 0..3 (mx_col_coords / mx_col_norm): kept as 8 bytes, widened here
+    const h8v b = __builtin_bit_cast(h8v, mxc_i4{lo, hi, lo, hi});
+    const f16x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, z, 0, 0, 0);
+    const f16x16 e = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, af, z, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    c = mxc_fold(c, d);
+    rmin = mxc_fold(rmin, e);
+}
+
+// one tile of two candidates X and Y that share the A fragment: four MFMAs in flight before the first minimum; per candidate
+// the operands and the folds of mxc_tile
+static __device__ __forceinline__ void mxc_tile2(const h8v& af, int loX, int hiX, int& cX, int& rminX, int loY, int hiY, int& cY,
+                                                 int& rminY)
+{
+    const f16x16 z = {};
+    const h8v bX = __builtin_bit_cast(h8v, mxc_i4{loX, hiX, loX, hiX});
+    const h8v bY = __builtin_bit_cast(h8v, mxc_i4{loY, hiY, loY, hiY});
+    // X's products, then Y's issued one by one behind X's folds, each into the registers the fold before it has read: two
+    // products in flight at any time and 32 accumulators, as in mxc_tile, and the matrix pipe never waits for the minima
+    const f16x16 dX = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bX, z, 0, 0, 0);
+    const f16x16 eX = __builtin_amdgcn_mfma_f32_32x32x16_f16(bX, af, z, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    cX = mxc_fold(cX, dX);
+    __builtin_amdgcn_sched_barrier(0);
+    const f16x16 dY = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bY, z, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    rminX = mxc_fold(rminX, eX);
+    __builtin_amdgcn_sched_barrier(0);
+    const f16x16 eY = __builtin_amdgcn_mfma_f32_32x32x16_f16(bY, af, z, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    cY = mxc_fold(cY, dY);
+    rminY = mxc_fold(rminY, eY);
+}
+
 // the tiles of `mask` for one row tile (A fragment af): their column minima into cm, their row minima into rmin -- a loop
-// over the SET bits of the wave-uniform mask (its cost is per computed tile, not per column tile); per tile D = A.B and
-// D' = B.A, both MFMAs in flight before the minima.  (blo, bhi): the two dwords of every column tile's B fragment.
+// over the SET bits of the wave-uniform mask (its cost is per computed tile, not per column tile), the last column tile
+// behind it by name (mxc_regs).  (blo, bhi): the two dwords of every column tile's B fragment.
 // PH: 1 phase 1 of a leader, 3 of a follower, 2 phase 2 (the section the count charges what follows the tiles to).
 template <int NCT, int PH>
 static __device__ __forceinline__ void mxc_tiles(unsigned mask, const h8v& af, const typename mxc_regs<NCT>::type& blo,
                                                  const typename mxc_regs<NCT>::type& bhi, typename mxc_regs<NCT>::type& cm, int& rmin)
 {
-    const f16x16 z = {};
+    const unsigned tail = mask >> (NCT - 1);
+    mask &= (1u << (NCT - 1)) - 1;
     while (mask) {
         MXC_MARK("tloop:tiles");
         const int t = __builtin_ctz(mask);
         mask &= mask - 1;
-        // a column fragment's K slots 4..7 repeat its slots 0..3 (mx_col_coords / mx_col_norm): kept as 8 bytes, widened here
-        const int lo = blo[t], hi = bhi[t];
-        const h8v b = __builtin_bit_cast(h8v, mxc_i4{lo, hi, lo, hi});
-        int c0 = cm[t];
-        MXC_MARK_V("tile", c0);
-        const f16x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, b, z, 0, 0, 0);
-        const f16x16 e = __builtin_amdgcn_mfma_f32_32x32x16_f16(b, af, z, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        int c1 = mxc_fold(c0, d);
-        rmin = mxc_fold(rmin, e);
-        MXC_MARK_V("tloop:tiles", c1);
-        cm[t] = c1;
+        const int lo = blo.v[t], hi = bhi.v[t];
+        int c = cm.v[t];
+        MXC_MARK_V("tile", c);
+        mxc_tile(af, lo, hi, c, rmin);
+        MXC_MARK_V("tloop:tiles", c);
+        cm.v[t] = c;
+    }
+    if (tail) {
+        MXC_MARK("tilet:tails");
+        mxc_tile(af, blo.last, bhi.last, cm.last, rmin);
     }
     if constexpr (PH == 1) MXC_MARK_V("p1_row:lrows", rmin);
     else if constexpr (PH == 3) MXC_MARK_V("p1f_row:frows", rmin);
     else MXC_MARK_V("p2_row:rows2", rmin);
+}
+
+// The same for TWO followers X and Y of one group in one pass: every follower of a group has the group's phase-1 mask, so
+// the set-bit loop, the tile index t and the A fragment are X's and Y's at once -- one s_ff1, one indexed region that reads
+// both candidates' fragment dwords and running column minima by the same wave-uniform index (one index, so no second
+// window into a register vector).  Per candidate the operands of each MFMA and the order of its folds are those of
+// mxc_tiles over the same tiles: every cm and rmin has the bits the unpaired loop gives.
+template <int NCT>
+static __device__ __forceinline__ void mxc_tiles2(unsigned mask, const h8v& af, const typename mxc_regs<NCT>::type& bloX,
+                                                  const typename mxc_regs<NCT>::type& bhiX, typename mxc_regs<NCT>::type& cmX, int& rminX,
+                                                  const typename mxc_regs<NCT>::type& bloY, const typename mxc_regs<NCT>::type& bhiY,
+                                                  typename mxc_regs<NCT>::type& cmY, int& rminY)
+{
+    const unsigned tail = mask >> (NCT - 1);
+    mask &= (1u << (NCT - 1)) - 1;
+    while (mask) {
+        MXC_MARK("tloop2:ptiles");
+        const int t = __builtin_ctz(mask);
+        mask &= mask - 1;
+        const int loX = bloX.v[t], hiX = bhiX.v[t], loY = bloY.v[t], hiY = bhiY.v[t];
+        int cX = cmX.v[t], cY = cmY.v[t];
+        MXC_MARK_V("tile2:ptiles", cX);
+        mxc_tile2(af, loX, hiX, cX, rminX, loY, hiY, cY, rminY);
+        MXC_MARK_V("tloop2:ptiles", cY);
+        cmX.v[t] = cX;
+        cmY.v[t] = cY;
+    }
+    if (tail) {
+        MXC_MARK("tile2t:ptails");
+        mxc_tile2(af, bloX.last, bhiX.last, cmX.last, rminX, bloY.last, bhiY.last, cmY.last, rminY);
+    }
+    MXC_MARK_V("p1p_row:prows", rminY);
 }
 
 // the same by a bit test and a branch per column tile in front of NCT unrolled bodies (A fragment af): their column minima into cm, their row minima into rmin -- per tile
@@ -1117,7 +1206,8 @@ template <int NCT>
 __global__ void __launch_bounds__(256, 2)
 k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work, int a_cap,
                  const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
-                 const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done)
+                 const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done,
+                 int pair_on)
 {
     constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128, VM = 40, NT4 = (NCT + 3) / 4, NP = (NCT + 1) / 2;
     typedef typename mxc_regs<NCT>::type regs_t;
@@ -1129,10 +1219,13 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
     float4* s_circ = reinterpret_cast<float4*>(s_thx + WAVES * a_cap * 32); // [NCT + a_cap] circles: columns (unrotated), rows
     float* s_cs = reinterpret_cast<float*>(s_circ + NCT + a_cap);     // [MX_ITEM][2] cos, sin of the work item's candidates
     int* s_ci = reinterpret_cast<int*>(s_cs + 2 * MX_ITEM);           // [MX_ITEM] their indices in the pair's list
+    int* s_ryx = s_ci + MX_ITEM;                                      // [WAVES][a_cap][32] row store of a pair's second follower
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31;
     h4v* s_b = s_bw + wave * NCT * 64;
     int* s_rs = s_rsx + wave * a_cap * 32;
+    int* s_ry = s_ryx + wave * a_cap * 32;
+    (void)s_ry; (void)pair_on;
     float* s_th = s_thx + wave * a_cap * 32;
     // column tile t's 32 minima after phase 1 go to the coordinate half of its fragments (read into registers by then; the
     // norm half, written once per work item, is not touched): [NCT][VS] ints, 32 used per row
@@ -1175,7 +1268,6 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
             s_circ[NCT + tid - 64] = float4{cx, cy, r, 0.0f};
         }
         __syncthreads();
-
         // A wave takes runs of G consecutive candidates (group q = candidates [q G, (q + 1) G) of the item, wave w the groups w,
         // w + 4, ...; G = WorkItem::pad, 1 | 2 | 4 | 8, chosen per pair at staging): the thresholds and the phase-1 masks are
         // built once per group, and the group's first candidate hands its phase-2 masks on (see below).  G = 1 is the rule per
@@ -1183,11 +1275,11 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
         const int G = NCT >= MXC_SETBIT_MIN_NCT ? min(max(w.pad, 1), 8) : 1;
         for (int k0 = wave * G; k0 < w.cnt; k0 += WAVES * G) {
           const int k1 = min(k0 + G, w.cnt);
-          unsigned m1 = 0, carry = 0;
+          unsigned m1 = 0;                            // (lane I: row tile I's phase-1 mask; behind the leader with its phase-2 tiles)
           // the followers' exit test, built once per group behind the leader (see there): lane I its row tile's Tr_I, lane J
           // its column tile's Tc_J, and the phase-1 tiles of a follower
           int grp_tr = 0x7f800000;
-          int grp_tc[NP] = {};                       // (pair p of column tiles: lanes 0 .. 31 hold Tc of 2 p, lanes 32 .. 63 of 2 p + 1)
+          int grp_tc = 0x7f800000;
           unsigned grp_p1 = 0;
           if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
             // ---- thr(I, J) of every tile pair, once per GROUP: lane (h, J) takes column tile J (one circle that holds the
@@ -1248,40 +1340,48 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 if (lane == I) m1 |= 1u << L;
             }
           }
-          (void)m1; (void)carry; (void)grp_tr; (void)grp_tc; (void)grp_p1;
+          (void)m1; (void)grp_tr; (void)grp_tc; (void)grp_p1;
           for (int k = k0; k < k1; ++k) {
             const float c = s_cs[2 * k], s = s_cs[2 * k + 1];
             const int a = s_ci[k];
             if constexpr (NCT >= MXC_SETBIT_MIN_NCT) {
-                MXC_MARK("setup:1");
+                // Two followers in a row run as a PAIR (X = k, Y = k + 1: the group's candidates k0 + 1 and k0 + 2, k0 + 3 and
+                // k0 + 4, ...; the leader and a follower left over run alone).  The marks' trip counts: xcand, once per
+                // candidate that is not a pair's Y; pair, once per pair; single, once per candidate outside a pair.
+                const bool follower = __builtin_amdgcn_readfirstlane(k > k0) != 0;   // (wave-uniform, and known to be)
+                const bool paired = __builtin_amdgcn_readfirstlane(pair_on && k > k0 && k + 1 < k1) != 0;
+                MXC_MARK("setup:xcand");
+                // the target rotated by (c, s) through the wave-private s_b into the two dwords of every column tile's fragment
+                auto stage_cols = [&](float c, float s, regs_t& blo, regs_t& bhi) {
 #pragma unroll
-                for (int q = 0; q < NQ; ++q) {
-                    const int j = lane + 64 * q;
-                    if (j < NB) {
-                        const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
-                        const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
-                        s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                    for (int q = 0; q < NQ; ++q) {
+                        const int j = lane + 64 * q;
+                        if (j < NB) {
+                            const float bx = __builtin_fmaf(tx[q], c, -(ty[q] * s));
+                            const float by = __builtin_fmaf(tx[q], s, ty[q] * c);
+                            s_b[(j >> 5) * 64 + (j & 31)] = mx_col_coords(bx, by);
+                        }
                     }
-                }
-                // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
-                __asm__ volatile("" ::: "memory");
-                regs_t blo, bhi;
+                    // (one wave writes and reads: its LDS operations execute in order; the compiler must not move them)
+                    __asm__ volatile("" ::: "memory");
 #pragma unroll
-                for (int t = 0; t < NCT; ++t) {
-                    const int2 v = reinterpret_cast<const int2*>(s_b)[t * 64 + lane];
-                    blo[t] = v.x; bhi[t] = v.y;
-                }
-                __asm__ volatile("" ::: "memory");
+                    for (int t = 0; t < NCT; ++t) {
+                        const int2 v = reinterpret_cast<const int2*>(s_b)[t * 64 + lane];
+                        blo.set(t, v.x); bhi.set(t, v.y);
+                    }
+                    __asm__ volatile("" ::: "memory");
+                };
+                regs_t blo, bhi;
+                stage_cols(c, s, blo, bhi);
 
                 // ---- phase 1 (the next row tile's A fragment is requested before this one's tiles) ----
                 // A follower of the group runs the leader's phase-2 tiles in phase 1 (neighbouring rotations leave the same
                 // tiles): a superset in phase 1 only lowers Umax and Vmax, so the skip rule below stays valid.
-                MXC_MARK("p1_init:1");
-                const unsigned p1m = m1 | carry;
-                const bool follower = __builtin_amdgcn_readfirstlane(k > k0) != 0;   // (wave-uniform, and known to be)
+                MXC_MARK("p1_init:xcand");
+                const unsigned p1m = m1;
                 regs_t cm;
 #pragma unroll
-                for (int t = 0; t < NCT; ++t) cm[t] = 0x7f800000;
+                for (int t = 0; t < NCT; ++t) cm.set(t, 0x7f800000);
                 h8v af = s_a[lane];
                 // a follower on the way: the largest met row minimum so far (from 0, as the general path's rowmax), and
                 // whether a row minimum lies above its row tile's Tr_I (then row tile I has phase-2 tiles)
@@ -1307,40 +1407,106 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         af = an;
                     }
                 };
-                if (follower) p1_rows(std::true_type{}); else p1_rows(std::false_type{});
-                if (follower) {
-                    // ---- the group test: this follower's phase-2 masks are all empty exactly when no met row
-                    // minimum of row tile I lies above Tr_I and no met column minimum of column tile J above Tc_J.  Then every
-                    // row tile is final with Umax_I, and the value is the maximum of the met minima: what the general path
-                    // returns with empty masks, without the column maxima, the masks, phase 2 and a second round of meets.
-                    MXC_MARK("fol_check:fol");
+                // ---- the group test: a follower's phase-2 masks are all empty exactly when no met row minimum of
+                // row tile I lies above Tr_I and no met column minimum of column tile J above Tc_J.  Then every row tile is
+                // final with Umax_I, and the value is the maximum of the met minima: what the general path returns with empty
+                // masks, without the column maxima, the masks, phase 2 and a second round of meets.
+                auto fol_check = [&](const regs_t& cmf, int& fm, unsigned long long& lt) {
                     __builtin_amdgcn_sched_barrier(0);                        // (the section's instructions stay behind its mark)
                     done += grp_p1;
                     ++n_foll;
                     // (two column tiles meet in one swap: the lower lanes then hold tile 2 p's met minima, the upper tile 2 p + 1's)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
-                        const int c0 = cm[2 * p], c1 = cm[2 * p + 1 < NCT ? 2 * p + 1 : 2 * p];
+                        const int c0 = cmf.get(2 * p), c1 = cmf.get(2 * p + 1 < NCT ? 2 * p + 1 : 2 * p);
                         const auto r = __builtin_amdgcn_permlane32_swap((unsigned)c0, (unsigned)c1, false, false);
                         const int v = min((int)r[0], (int)r[1]);
-                        late |= __builtin_amdgcn_ballot_w64(v > grp_tc[p]);
-                        fmax = max(fmax, v);
+                        const int t0 = __builtin_amdgcn_readlane(grp_tc, 2 * p), t1 = __builtin_amdgcn_readlane(grp_tc, 2 * p + 1 < NCT ? 2 * p + 1 : 2 * p);
+                        lt |= __builtin_amdgcn_ballot_w64(v > (lane < 32 ? t0 : t1));
+                        fm = max(fm, v);
                     }
+                };
+                auto fol_store = [&](int fm, int ai) {
+                    ++n_early;
+                    const int m = wave_max_i32_dpp(fm);
+                    if (lane == 0) out_sq[pd.out_off + ai] = __int_as_float(m) * inv_s2;
+                };
+                // What runs the general path below: bit 0 this candidate (X of a pair), bit 1 a pair's Y, on its own registers and
+                // its own row store, after X.
+                unsigned stay = 1;
+                regs_t bloY, bhiY, cmY;
+                int aY = a;
+                if (paired) {
+                    // ---- a pair: Y's fragments through the same s_b (X's are in registers), one row loop for both, X's row
+                    // minima into s_rs and Y's into the second row store; then the group test, once for X and once for Y
+                    MXC_MARK("setup2:pair");
+                    aY = s_ci[k + 1];
+                    stage_cols(s_cs[2 * k + 2], s_cs[2 * k + 3], bloY, bhiY);
+                    MXC_MARK("p1_init2:pair");
+#pragma unroll
+                    for (int t = 0; t < NCT; ++t) cmY.set(t, 0x7f800000);
+                    int fmaxY = 0;
+                    unsigned long long lateY = 0;
+                    for (int I = 0; I < nrt; ++I) {
+                        MXC_MARK("p1p_row:prows");
+                        const unsigned mask = __builtin_amdgcn_readlane(p1m, I);
+                        const int tr = __builtin_amdgcn_readlane(grp_tr, I);
+                        const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
+                        int rminX = 0x7f800000, rminY = 0x7f800000;
+                        mxc_tiles2<NCT>(mask, af, blo, bhi, cm, rminX, bloY, bhiY, cmY, rminY);
+                        rminX = mxc_meet(rminX);
+                        rminY = mxc_meet(rminY);
+                        if (lane < 32) { s_rs[I * 32 + lane] = rminX; s_ry[I * 32 + lane] = rminY; }
+                        fmax = max(fmax, rminX);
+                        fmaxY = max(fmaxY, rminY);
+                        late |= __builtin_amdgcn_ballot_w64(rminX > tr);
+                        lateY |= __builtin_amdgcn_ballot_w64(rminY > tr);
+                        af = an;
+                    }
+                    MXC_MARK("fol_check2:pair");
+                    fol_check(cm, fmax, late);
+                    fol_check(cmY, fmaxY, lateY);
+                    stay = (late ? 1u : 0u) | (lateY ? 2u : 0u);
                     if (!late) {
-                        MXC_MARK("fol_final:early");
-                        ++n_early;
-                        const int m = wave_max_i32_dpp(fmax);
-                        if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
-                        MXC_MARK("end:0");
-                        continue;
+                        MXC_MARK("fol_final2x:pearly");
+                        fol_store(fmax, a);
                     }
+                    if (!lateY) {
+                        MXC_MARK("fol_final2y:pearly");
+                        fol_store(fmaxY, aY);
+                    }
+                    MXC_MARK("end:0");
+                } else {
+                    if (follower) p1_rows(std::true_type{}); else p1_rows(std::false_type{});
+                    if (follower) {
+                        MXC_MARK("fol_check:sfol");
+                        fol_check(cm, fmax, late);
+                        if (!late) {
+                            MXC_MARK("fol_final:searly");
+                            fol_store(fmax, a);
+                            stay = 0;
+                            MXC_MARK("end:0");
+                        }
+                    }
+                    // (Y's registers are nobody's here.  Said at this point, with no instruction: otherwise they count as
+                    // undefined from the kernel's entry on and keep 51 registers through every other section.)
+                    __asm__ volatile("" : "=v"(bloY.v), "=v"(bhiY.v), "=v"(cmY.v), "=v"(bloY.last), "=v"(bhiY.last), "=v"(cmY.last));
+                }
+                int acur = a;
+                int* rs = s_rs;
+                for (; stay; stay &= stay - 1) {
+                if (!(stay & 1)) {
+                    // X is finished: Y's state into X's variables (only a pair's Y that stays pays for this)
+                    MXC_MARK("ymove:ylate");
+                    blo = bloY; bhi = bhiY; cm = cmY;
+                    acur = aY; rs = s_ry;
                 }
                 // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
                 MXC_MARK("vmax:late");
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) {
-                    cm[t] = mxc_meet(cm[t]);
-                    if (lane < 32) s_v[t * VS + lane] = cm[t];
+                    cm.set(t, mxc_meet(cm.get(t)));
+                    if (lane < 32) s_v[t * VS + lane] = cm.get(t);
                 }
                 __asm__ volatile("" ::: "memory");
                 if (lane < NCT) {
@@ -1357,7 +1523,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 int rowmax = 0;
                 const bool leads = !follower && __builtin_amdgcn_readfirstlane(k1 - k0) > 1;   // (wave-uniform) a leader with followers
                 if (lane < nrt) {
-                    const int4* q = reinterpret_cast<const int4*>(s_rs + lane * 32);
+                    const int4* q = reinterpret_cast<const int4*>(rs + lane * 32);
                     int umax = (int)0x80000000;
 #pragma unroll
                     for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
@@ -1391,13 +1557,13 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         MXC_MARK("m2:late");
                     }
                 }
-                if (!follower) carry = m2;
+                if (!follower) m1 |= m2;                                     // (the hand-over: the followers' phase 1)
                 if (leads) {
                     // Tc_J: the same down column tile J (lane J reads the table's column: consecutive banks), and the
                     // followers' phase-1 tile count.  A follower's m2 is then empty for every row tile exactly when
                     // Umax_I <= Tr_I for every I and Vmax_J <= Tc_J for every J (0x7f800000 where nothing is outside).
                     MXC_MARK("grp_tc:fgroup");
-                    const unsigned pf = m1 | carry;
+                    const unsigned pf = m1;
                     int tc = 0x7f800000;
                     unsigned cnt = 0;
                     for (int I = 0; I < nrt; ++I) {
@@ -1408,11 +1574,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         cnt += __builtin_popcount(pm);
                     }
                     MXC_MARK("grp_tc:fgroup");
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) {
-                        const int t0 = __builtin_amdgcn_readlane(tc, 2 * p), t1 = __builtin_amdgcn_readlane(tc, 2 * p + 1 < NCT ? 2 * p + 1 : 2 * p);
-                        grp_tc[p] = lane < 32 ? t0 : t1;
-                    }
+                    grp_tc = tc;                                              // (one register: the followers' check reads it lane by lane)
                     grp_p1 = cnt;
                 }
 
@@ -1422,7 +1584,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     const int I = __builtin_ctzll(rows);
                     const unsigned mask = __builtin_amdgcn_readlane(m2, I);
                     const h8v ai = s_a[I * 64 + lane];
-                    int rmin = s_rs[I * 32 + l32];
+                    int rmin = rs[I * 32 + l32];
                     mxc_tiles<NCT, 2>(mask, ai, blo, bhi, cm, rmin);
                     rmin = mxc_meet(rmin);
                     done += __builtin_popcount(mask);
@@ -1431,10 +1593,12 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 MXC_MARK("final:late");
                 int m = rowmax;
 #pragma unroll
-                for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
+                for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm.get(t)));
                 m = wave_max_i32_dpp(m);
-                if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                if (lane == 0) out_sq[pd.out_off + acur] = __int_as_float(m) * inv_s2;
                 MXC_MARK("end:0");
+                }
+                if (paired) ++k;                                              // (Y is done with X)
             } else {
                 // fewer column tiles: the bit-test chain in front of unrolled tile bodies and one tile pair per lane are
                 // cheaper there (profiles/r6_cull_isa_budget.txt)
@@ -1582,23 +1746,23 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 
 template <int NCT>
 static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int n_work, int a_cap, unsigned long long* tiles,
-                                   hipStream_t s)
+                                   int pair, hipStream_t s)
 {
     const size_t lds = lds_bytes_mx_cull(NCT, a_cap);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_screen_mx_cull<NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_screen_mx_cull<NCT>), dim3(n_work), dim3(256), lds, s, b.pairs, work, n_work, a_cap, b.p32x, b.p32y,
-                       b.cos32, b.sin32, b.sq32, tiles);
+                       b.cos32, b.sin32, b.sq32, tiles, pair);
     return hipGetLastError();
 }
 
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
-                                 hipStream_t s)
+                                 int pair, hipStream_t s)
 {
     if (n_work <= 0) return hipSuccess;
     if (!mx_cull_takes(nct, 0, a_cap)) return hipErrorInvalidValue;
     const WorkItem* w = b.work + work_begin;
-#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, s);
+#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, pair, s);
     switch (nct) {
         MM_MXC(2) MM_MXC(3) MM_MXC(4) MM_MXC(5) MM_MXC(6) MM_MXC(7) MM_MXC(8) MM_MXC(9) MM_MXC(10) MM_MXC(11) MM_MXC(12)
         MM_MXC(13) MM_MXC(14) MM_MXC(15) MM_MXC(16) MM_MXC(17)

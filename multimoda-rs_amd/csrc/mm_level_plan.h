@@ -30,6 +30,8 @@ struct ScreenOptions {
     int screen_group = 0;                   // k_screen_mx_cull: consecutive candidates that share one tile bound and mask set
                                             // (WorkItem::pad).  0: chosen per pair from its list (mm_tile_group_auto), never
                                             // more than a quarter of a work item; 1: off; 2 | 4 | 8: forced
+    bool screen_pair = true;                // k_screen_mx_cull: a group's followers run their phase 1 two at a time (one tile
+                                            // loop for both).  A launch argument: the plan is the same either way
 };
 
 struct PairSpec {          // one search

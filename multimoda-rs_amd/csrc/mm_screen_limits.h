@@ -47,11 +47,15 @@ constexpr size_t lds_bytes_mx(int nct, bool multi, int a_cap, int waves)
            (multi ? (size_t)waves * a_cap * 32 * 4 : 0) + (size_t)kMxItemMax * 12;
 }
 
+// (row fragments, the waves' column fragments, per wave a row store and the thr table, the circles, the item's candidates, and
+// at the end, where the set-bit variant pairs its followers, per wave the row store of a pair's second follower)
 constexpr size_t lds_bytes_mx_cull(int nct, int a_cap)
 {
     return (size_t)a_cap * 64 * 16 + (size_t)4 * nct * 64 * 8 + (size_t)4 * a_cap * 32 * 4 * 2 + (size_t)(nct + a_cap) * 16 +
-           (size_t)kMxItemMax * 12;
+           (size_t)kMxItemMax * 12 + (nct >= kMxCullSetbitMinNct ? (size_t)4 * a_cap * 32 * 4 : 0);
 }
+static_assert(2 * lds_bytes_mx_cull(kMxNctMax, kMxCullRowTilesMax) <= 160 * 1024,
+              "k_screen_mx_cull: two workgroups a CU at the largest row and column tile counts");
 
 // ---- direct-form, packed-FMA and exact kernels: the target set in LDS ----
 constexpr int LDS_CAP = 160 * 1024 - 256;

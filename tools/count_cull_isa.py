@@ -22,6 +22,19 @@ how often the section runs per candidate:
     late     once per candidate that does not leave early (1 - early (G - 1) / G)
     0        not in the candidate loop
 
+Pairs (--pair, default on, the set-bit variant at G >= 4): a group's followers run two at a time, P = (G - 2) // 2 pairs a group,
+so 2 P / G of the candidates are paired, (G - 1 - 2 P) / G are single followers:
+
+    pair     once per pair (P / G per candidate)        prows    `nrt`, per pair        ptiles   once per tile of a pair (a section
+             named `tile2` is the paired tile body: the MFMAs behind a tloop2 / tile2 mark count to it)
+    xcand    once per candidate that is not a pair's second (1 - P / G)       single   once per candidate outside a pair
+    sfol     once per single follower                   sfrows   `nrt`, per single follower (what frows counts with --pair 0)
+    searly   once per single follower that leaves early               pearly   once per pair whose X (or whose Y) leaves early
+    ylate    once per pair's second follower that does not leave early
+    tails    once per computed tile of the LAST column tile, which has a register of its own and a body (`tilet`, paired
+             `tile2t`: ptails) behind the loop over the others; --tail is its share of the computed tiles (default 1 / NCT)
+    tiles    ... of the candidates outside a pair (their phase-2 tiles, few, are charged to the pairs' loop at its rate)
+
 and a section named `tile` is a computed tile's own body (its copies are averaged; every v_mfma counts to it).  A section
 ends at the next mark or at an unconditional branch; instructions between such a branch and the next mark are listed as
 `unmarked` and not charged.  Instructions are classified by the
@@ -104,22 +117,37 @@ def sections(body):
         if not m or ln.lstrip().startswith((".", ";")):
             continue
         mn, cl = m.group(1), classify(m.group(1))
-        (sec("tile", "tile") if cl == "mfma" else cur)[cl] += 1      # (the scheduler may lift a tile's MFMAs above its mark)
+        if cl == "mfma":                                             # (the scheduler may lift a tile's MFMAs above its mark)
+            if cur is secs.get("tilet") or cur is secs.get("tile2t"):
+                cur[cl] += 1                                             # (the last column tile's body, reached by name)
+            else:
+                paired = cur is secs.get("tloop2") or cur is secs.get("tile2") or cur is secs.get("p1p_row")
+                (sec("tile2", "ptiles") if paired else sec("tile", "tile"))[cl] += 1
+        else:
+            cur[cl] += 1
         if mn in ("s_branch", "s_endpgm") or mn.startswith("s_setpc"):
             cur = sec("unmarked", "0")                               # no fall-through: what follows is another block
     return secs
 
 
-def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0):
+def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True, tail=None):
     secs = sections(body)
     copies = max(1, secs["tile"]["entries"]) if "tile" in secs else 1
     fol = (group - 1.0) / group
     fgroup = 1.0 / group if group > 1 else 0.0
+    tcopies = max(1, secs["tilet"]["entries"]) if "tilet" in secs else 1
+    tail = (1.0 / nct if tail is None else tail) if "tilet" in secs else 0.0     # share of the computed tiles in the last column tile
+    npair = max(0, (group - 2) // 2) if pair and "tile2" in secs else 0      # pairs per group: followers 1 .. 2 P
+    pshare, sfol = 2.0 * npair / group, (group - 1.0 - 2 * npair) / group
     trips = {"0": 0.0, "1": 1.0, "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
-             "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles / copies, "tile": tiles / copies,
+             "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles * (1.0 - pshare) * (1.0 - tail) / copies,
+             "tile": tiles * (1.0 - pshare) * (1.0 - tail) / copies, "tails": tiles * (1.0 - pshare) * tail / tcopies,
+             "ptiles": tiles * pshare * (1.0 - tail) / 2, "ptails": tiles * pshare * tail / 2, "pair": pshare / 2, "prows": nrt * pshare / 2, "xcand": 1.0 - pshare / 2,
+             "single": 1.0 - pshare, "sfol": sfol, "sfrows": nrt * sfol, "searly": early * sfol, "pearly": early * pshare / 2,
+             "ylate": (1.0 - early) * pshare / 2,
              "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group,
              "fgroup": fgroup, "fgnrt": nrt * fgroup,
-             "fol": fol, "frows": nrt * fol, "lrows": nrt * (1.0 - fol), "early": early * fol, "late": 1.0 - early * fol}
+             "fol": fol, "frows": nrt * sfol, "lrows": nrt * (1.0 - fol), "early": early * fol, "late": 1.0 - early * fol}
     out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (
         nct, info(inf, "NumVgprs"), info(inf, "NumAgprs"), info(inf, "ScratchSize"), info(inf, "Occupancy")))
     out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g, candidates/group %d, early share of the followers %g; tile bodies in the code: %d\n" % (
@@ -132,7 +160,7 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0):
         if s["trips"] not in trips:
             raise SystemExit("unknown trip count %r in mark %r" % (s["trips"], name))
         ex = static * trips[s["trips"]]
-        if name == "tile":
+        if name in ("tile", "tile2", "tilet", "tile2t"):
             tot_tile += ex
         else:
             tot_rest += ex
@@ -140,6 +168,8 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0):
                                                                        s["vmem"], s["other"], static, ex))
     if "tile" in secs:
         out.write("  a computed tile's body: %.1f instructions\n" % (sum(secs["tile"][c] for c in CLASSES) / copies))
+    if "tile2" in secs:
+        out.write("  a paired tile's body (two candidates): %.1f instructions; pairs per group %d\n" % (sum(secs["tile2"][c] for c in CLASSES), npair))
     out.write("  executed per candidate: tiles %.0f, everything else %.0f\n\n" % (tot_tile, tot_rest))
     return tot_tile, tot_rest
 
@@ -153,6 +183,8 @@ def main(argv=None):
     ap.add_argument("--rows2", type=float, default=None, help="row tiles with tiles left in phase 2 (default: nrt)")
     ap.add_argument("--group", type=int, default=1, help="candidates per group: the sections marked group / ghalf run once per group")
     ap.add_argument("--early", type=float, default=0.0, help="share of a group's followers that leave after phase 1 (sections marked early / late)")
+    ap.add_argument("--tail", type=float, default=None, help="share of the computed tiles that are the last column tile's (default 1 / NCT)")
+    ap.add_argument("--pair", type=int, default=1, help="0: the pair switch off (every follower runs alone)")
     a = ap.parse_args(argv)
     if a.group < 1:
         raise SystemExit("--group must be at least 1")
@@ -166,7 +198,7 @@ def main(argv=None):
         if a.nct and nct != a.nct:
             continue
         body, inf = ks[nct]
-        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group, a.early)
+        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group, a.early, a.pair != 0, a.tail)
 
 
 if __name__ == "__main__":
