@@ -1057,6 +1057,83 @@ int     mm_mesh_repair(mm_engine* e, const double* vertices_xyz, int64_t nv, con
                        int64_t vert_cap, double* out_vertices, int64_t* out_faces, int64_t* out_origin,
                        int64_t* out_target, mm_repair_report* report);
 
+/* ---- mesh intersections (multimodars/ccta/fixing_functions.py:182-185, 234: meshing_close_holes(selfintersection=False),
+ *      the question the reference leaves to MeshLab and switches off) ---------------------------------------------------
+ * Which pairs of faces of one mesh (the self form), or of two, pass through each other.  tests/mm_checkers/
+ * mesh_intersections.py is the executable form of the rule; csrc/mm_isect_device.h is its C++ text.
+ *
+ * Every pair of faces is DISJOINT (0), INTERSECTING (1) or UNDECIDED (2).  A state other than UNDECIDED is a proof in
+ * exact arithmetic on the f64 inputs: DISJOINT by a separating witness, INTERSECTING by a strict crossing.  UNDECIDED is
+ * what the filtered predicates cannot prove: touching or coplanar within rounding.  The state is a pure function of the
+ * two faces' coordinates and vertex identities, computed in unfused f64 in the order written below, so chunking,
+ * scheduling and culling cannot change a bit.  In the self form face 1 of a pair is the one with the lower index; in the
+ * two-mesh form it is the face of mesh a.
+ *
+ * 1. Vertex identity (self form).  The canonical id of a vertex is the lowest index with equal coordinates, +0.0 == -0.0
+ *    as in "mesh repair": an unwelded seam reads as adjacent.  The two-mesh form has no identities.
+ * 2. A degenerate face -- two equal canonical ids, or every component of ab x ac exactly 0.0 as in "surface distance" -- is
+ *    counted, tested against nothing, and has state 0.
+ * 3. Box step.  Closed coordinate boxes of the two faces disjoint on an axis: DISJOINT.  Corners lie in their boxes
+ *    exactly, so there is no slack, and a cull by the boxes of groups of faces loses nothing.
+ * 4. Predicates, sign +1, -1 or 0 = not certain; eps = 2^-53.
+ *    orient3d(a,b,c,d): adx = ax-dx ... cdz = cz-dz; det = (adz*(bdx*cdy - cdx*bdy) + bdz*(cdx*ady - adx*cdy)) +
+ *    cdz*(adx*bdy - bdx*ady); permanent = ((|bdx*cdy| + |cdx*bdy|)*|adz| + (|cdx*ady| + |adx*cdy|)*|bdz|) +
+ *    (|adx*bdy| + |bdx*ady|)*|cdz|; certain iff |det| > (7 + 56 eps) eps * permanent (stage A of Shewchuk's orient3d).
+ *    orient2d(a,b,c) on the two coordinates left when the axis of the largest |component| of face 1's normal
+ *    (q1-p1) x (r1-p1) is dropped (the first of equal ones; x drops to (y, z), y to (x, z), z to (x, y)):
+ *    left = (au-cu)*(bv-cv), right = (av-cv)*(bu-cu), det = left - right, detsum = |left| + |right|; certain iff
+ *    |det| > (3 + 16 eps) eps * detsum.  A permanent or detsum that is not finite or is below 2^-900 is not certain.
+ * 5. No shared vertex.  a_k = orient3d(p1,q1,r1, corner k of face 2): all three certain and equal: DISJOINT; then b_k =
+ *    orient3d(p2,q2,r2, corner k of face 1) likewise.  All six not certain: in the projection of 4., DISJOINT if an edge
+ *    of one triangle (inner side certain) has the other's three corners certainly on its outer side -- face 1's edges pq,
+ *    qr, rp first, then face 2's -- else UNDECIDED.  Any of the six not certain: UNDECIDED.  Otherwise rotate each face so
+ *    that the corner whose sign differs from the other two comes first (Guigue-Devillers); if that corner of face 1 is
+ *    negative swap q2, r2, if that of face 2 is negative swap q1, r1; e1 = orient3d(p1,q1,p2,q2): positive: DISJOINT;
+ *    e2 = orient3d(p1,r1,r2,p2): positive: DISJOINT; both negative: INTERSECTING; else UNDECIDED.
+ * 6. One shared vertex.  Rotate each face so that it comes first.  q1, r1 certainly on one side of face 2's plane:
+ *    DISJOINT; q2, r2 against face 1's likewise.  The segment q1 r1 against face 2: crossing iff its ends are certainly
+ *    on opposite sides and orient3d(q1,r1,p2,q2), (q1,r1,q2,r2), (q1,r1,r2,p2) are certain and equal; missing iff two of
+ *    those three are certainly opposite.  Crossing: INTERSECTING; else q2 r2 against face 1 likewise; both missing:
+ *    DISJOINT.  Else, with all four plane signs not certain (a flat pair, as the children of a refined face), in the
+ *    projection of 4. taken on the rotated face 1: DISJOINT if one of the edges at the shared vertex -- p1 q1, r1 p1,
+ *    p2 q2, r2 p2 in that order -- has its inner side certain and the other face's two far corners certainly on its
+ *    outer side; else UNDECIDED.
+ * 7. Two shared vertices.  The unshared corner of face 2 certainly off face 1's plane, or that of face 1 off face 2's:
+ *    DISJOINT.  Else, with (c1, a, b) face 1 rotated so that its unshared corner comes first, orient2d(a,b,c1) and
+ *    orient2d(a,b,c2) certain and opposite: DISJOINT (a flat pair); else UNDECIDED (a fold-over).
+ * 8. Three shared vertices: INTERSECTING, counted in n_coincident_pairs. */
+
+typedef struct mm_intersect_report {
+    int64_t n_intersecting_pairs, n_undecided_pairs;
+    int64_t n_degenerate_faces;   /* of both meshes */
+    int64_t n_coincident_pairs;   /* among the intersecting ones */
+    int64_t items;                /* chunk pairs whose boxes overlap: the workgroups that ran */
+    int64_t items_total;          /* chunk pairs before the cull */
+    int64_t pair_box_tests;       /* face pairs inside the items */
+    int64_t narrow_tests;         /* face pairs that passed the box step: the same whatever the cull */
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    int64_t pairs_complete;       /* 0: more pairs than max_pairs, no list */
+} mm_intersect_report;
+
+/* vb == NULL selects the self form (nvb, fb, nfb are not read, out_state_b not written).  out_state_a / out_state_b: one
+ * byte per face, bit 0 = in an intersecting pair, bit 1 = in an undecided one.  out_pairs (2 per pair, original face
+ * indices: i < j in the self form, (face of a, face of b) otherwise; rows ascending) and out_pair_state (1 or 2) hold at
+ * most max_pairs pairs and may be NULL (then max_pairs counts as 0); with more pairs than that nothing is written to
+ * them and pairs_complete is 0, the counts and flags are complete all the same.  Empty meshes are valid.
+ * MM_ERR_INVALID: a non-finite coordinate, a face index out of range, a size of 2^31 or more; MM_ERR_TOO_LARGE: more
+ * than 2^31 - 1 items.  On an error the outputs are not written. */
+int     mm_mesh_intersections(mm_engine* e, const double* va, int64_t nva, const int64_t* fa, int64_t nfa, const double* vb,
+                              int64_t nvb, const int64_t* fb, int64_t nfb, int64_t max_pairs, uint8_t* out_state_a,
+                              uint8_t* out_state_b, int64_t* out_pairs, int8_t* out_pair_state, mm_intersect_report* report);
+/* TEST HOOK (nothing in the product calls it; no engine, no device): the host side of mm_mesh_intersections.
+ * order_a[j] / order_b[j] = the face staged at position j (slabs by corner sum across the longest axis of all corners).
+ * chunk_boxes (nullable): lo xyz, hi xyz of every chunk of a, then of b.  items (2 int32 each: chunk I of a, chunk J of b
+ * or, in the self form, of a with I <= J) receives at most cap items.  info[5] = {items, chunk pairs before the cull,
+ * faces per chunk, chunks of a, chunks of b}.  Errors as mm_mesh_intersections. */
+int     mm_isect_plan(const double* va, int64_t nva, const int64_t* fa, int64_t nfa, const double* vb, int64_t nvb,
+                      const int64_t* fb, int64_t nfb, int32_t* order_a, int32_t* order_b, int64_t* info, double* chunk_boxes,
+                      int32_t* items, int64_t cap);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

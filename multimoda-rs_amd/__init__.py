@@ -44,6 +44,8 @@ from .ccta import (DiscretizedVesselTree, adjust_diameter_centerline_morphing_si
 from . import surface
 from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport, point_mesh_distance,
                       sample_mesh_surface, surface_distance)
+from . import intersect
+from .intersect import MeshIntersections, mesh_intersections, mesh_self_intersections
 from . import skeleton
 from .skeleton import SkeletonGraph, centerline_from_mesh, mesh_geodesic_distance, mesh_skeleton, skeleton_centerline
 from .convert import numpy_to_geometry, to_array
@@ -89,6 +91,7 @@ __all__ = [
     "repair_mesh", "mesh_manifold_report", "fix_and_remesh_stitched_mesh",
     "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
     "DirectedDistance", "SurfaceDistanceReport",
+    "intersect", "mesh_self_intersections", "mesh_intersections", "MeshIntersections",
     "skeleton", "mesh_geodesic_distance", "mesh_skeleton", "centerline_from_mesh", "skeleton_centerline", "SkeletonGraph",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",

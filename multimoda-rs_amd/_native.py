@@ -122,6 +122,7 @@ EXPORTS_CCTA = [
     "mm_mesh_adjacency_csr", "mm_mesh_smooth", "mm_mesh_vertex_rings",
     "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan", "mm_mesh_relax",
     "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges", "mm_mesh_repair",
+    "mm_mesh_intersections", "mm_isect_plan",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -165,6 +166,13 @@ class MMSurfaceReport(C.Structure):
     """``mm_surface_report`` (include/mm_ccta.h)."""
     _fields_ = [(name, C.c_int64) for name in (
         "items_pass_a", "items_pass_b", "items_skipped", "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMIntersectReport(C.Structure):
+    """``mm_intersect_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_intersecting_pairs", "n_undecided_pairs", "n_degenerate_faces", "n_coincident_pairs", "items", "items_total",
+        "pair_box_tests", "narrow_tests", "n_launches", "bytes_uploaded", "bytes_downloaded", "pairs_complete")]
 
 
 class MMRelaxReport(C.Structure):
@@ -687,6 +695,10 @@ def lib():
     L.mm_mesh_collapse_edges.argtypes = [P, P, I64, P, I64, P, D, D, D, D, D, I64, P, P, P, P, C.POINTER(MMCollapseReport)]
     L.mm_mesh_repair.restype = I
     L.mm_mesh_repair.argtypes = [P, P, I64, P, I64, I, I64, P, P, P, P, C.POINTER(MMRepairReport)]
+    L.mm_mesh_intersections.restype = I
+    L.mm_mesh_intersections.argtypes = [P, P, I64, P, I64, P, I64, P, I64, I64, P, P, P, P, C.POINTER(MMIntersectReport)]
+    L.mm_isect_plan.restype = I
+    L.mm_isect_plan.argtypes = [P, I64, P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

@@ -1520,7 +1520,7 @@ def stitch_ccta_to_intravascular(iv_geometry: G.FlatGeometry, mesh, results: dic
 def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_points", "proximal_points"),
            prox_start_mode: str = "highest_z", dist_start_mode: str = "nearest_iv",
            engine: Optional[N.Engine] = None, fill_holes: bool = False, smooth=False, refine=False, relax=False,
-           flip=False, collapse=False, repair=False) -> dict:
+           flip=False, collapse=False, repair=False, check_intersections: bool = False) -> dict:
     """ccta/__init__.py:261-338: remove the labelled regions ``region_remove`` from the CCTA mesh and stitch what is left
     to the intravascular ``geometry``.  The reference's wrapper leaves ``target_boundaries`` of the removal at its
     default of 1 although its own stitch then asks for two rings; this one passes ``target_boundaries=2``.  The
@@ -1546,7 +1546,9 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
     result carries ``collapse_report``.  The default ``collapse=False`` changes nothing.  ``repair=True``, or a dict of
     ``repair_mesh`` keywords, runs ``repair_mesh`` between the assembly and the hole filling, so that a rim with a pinch
     vertex or beside a non-manifold edge becomes a loop the fill closes; its report goes under ``"repair"``.  The default
-    ``repair=False`` changes nothing."""
+    ``repair=False`` changes nothing.  ``check_intersections=True`` ends with the self-intersection check of the final
+    mesh (``mesh_self_intersections``): the result carries its report under ``intersection_report``.  The default
+    ``check_intersections=False`` changes nothing."""
     keys = [region_remove] if isinstance(region_remove, str) else list(region_remove)
     updated = remove_labeled_points_from_mesh(results, keys, target_boundaries=2, engine=engine)
     out = stitch_ccta_to_intravascular(geometry, updated["mesh"], updated, prox_start_mode=prox_start_mode,
@@ -1558,7 +1560,18 @@ def stitch(results: dict, geometry: G.FlatGeometry, region_remove=("anomalous_po
         out["mesh"] = _with_mesh(out["mesh"], new_v, new_f)
         out["fill_report"] = report
     out = _collapse_result(_refine_result(out, refine, engine), collapse, engine)
-    return _smooth_result(_relax_result(_flip_result(out, flip, engine), relax, engine), smooth, engine)
+    out = _smooth_result(_relax_result(_flip_result(out, flip, engine), relax, engine), smooth, engine)
+    if check_intersections:
+        out = dict(out)
+        out["intersection_report"] = _intersection_report(out["mesh"], engine)
+    return out
+
+
+def _intersection_report(mesh, engine) -> dict:
+    """The ``check_intersections`` keyword of ``stitch``: the report of ``mesh_self_intersections`` on ``mesh``
+    (imported here: intersect.py imports this module)."""
+    from .intersect import mesh_self_intersections
+    return mesh_self_intersections(mesh, engine=engine).report
 
 
 def _refine_result(out: dict, refine, engine) -> dict:

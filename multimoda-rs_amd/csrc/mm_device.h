@@ -81,6 +81,18 @@ hipError_t launch_tri_seeded(const TriWork* work, int n_work, const double* tri1
 int        tri_seeded_launches();
 int        tri_queries_per_block();
 int        tri_chunk_faces();
+// mesh intersections (mm_intersect_kernels.hip; the rule: include/mm_ccta.h, "mesh intersections").  tri12: the staged
+// faces, 12 doubles each (a, b, c as x y z w; a.w = canonical id of a | that of b << 32, b.w = that of c | original face
+// index << 32, c.w = 1 where the face is degenerate): n_a faces of the first mesh, then n_b of the second from record
+// off_b; the self form passes self_form with n_b = n_a, off_b = 0.  items: n_items chunk pairs (I of the first, J of the
+// second).  state: one byte per staged record (bit 0 intersecting, bit 1 undecided), n_state_words words; counters[8]:
+// intersecting pairs, undecided pairs, coincident pairs, narrow tests, pairs found; pairs: the first `cap` found, as
+// state << 62 | first original index << 31 | second.  The clear of state and counters is the first launch.
+hipError_t launch_isect_pairs(const int32_t* items, int n_items, const double* tri12, int n_a, int n_b, int off_b,
+                              bool self_form, unsigned int* state, long long n_state_words, unsigned long long* counters,
+                              unsigned long long* pairs, unsigned long long cap, hipStream_t s);
+int        isect_launches();
+int        isect_chunk_faces();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
 // xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = n_rays x ceil(n_faces /
 // ray_chunk_faces()) records of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits at least 3
