@@ -146,7 +146,7 @@ int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
 /* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull, mm_engine_set_screen_split,
- * mm_engine_set_screen_group and mm_engine_set_screen_pair apply to the levels staged
+ * mm_engine_set_screen_group, mm_engine_set_screen_pair and mm_engine_set_screen_floor apply to the levels staged
  * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
  * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
@@ -179,6 +179,13 @@ int  mm_engine_set_screen_group(mm_engine* e, int group);
  * follower alone, the A/B switch.  Values, tile counts and the followers' counters are the same either way, bit for bit;
  * mm_screen_values_group takes the engine's setting. */
 int  mm_engine_set_screen_pair(mm_engine* e, int on);
+/* The culled screen of 17 column tiles keeps a value floor: a candidate's value is the MAXIMUM of its row and column minima,
+ * so once some minimum is known to be exact after phase 1 (it lies at or below every threshold of the tiles not computed),
+ * rows and columns whose phase-1 minimum is not above it cannot raise the value, and phase 2 computes tiles only for the
+ * others (default, on != 0).  on == 0: every row and column minimum is made exact, the A/B switch.  Screened values are the
+ * same bit for bit; the tiles computed and the followers that leave after phase 1 differ.  The hooks mm_screen_values,
+ * mm_screen_values_split and mm_screen_values_group screen with the floor off; mm_screen_values_floor takes it. */
+int  mm_engine_set_screen_floor(mm_engine* e, int on);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);
@@ -232,6 +239,11 @@ int  mm_screen_values_group(mm_engine* e, const double* rx, const double* ry, in
                             int nt, int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles,
                             int flags, int cull, int group, float* out_sq2, double* e2, int32_t* items, int items_cap,
                             int* n_items);
+/* The same with the value floor given (floor != 0: on; the three hooks above screen with it off). */
+int  mm_screen_values_floor(mm_engine* e, const double* rx, const double* ry, int nr, const double* tx, const double* ty,
+                            int nt, int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles,
+                            int flags, int cull, int group, int floor, float* out_sq2, double* e2, int32_t* items,
+                            int items_cap, int* n_items);
 /* TEST HOOK (host only): the group size chosen for a candidate list (radians) when the switch is automatic. */
 int  mm_screen_group_auto(const double* angles, int n);
 /* TEST HOOK (host only; no engine, no device): the level the engine plans for a batch of searches, as 64-bit words.

@@ -32,7 +32,7 @@ EXPORTS = [
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_engine_screen_early", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
-    "mm_engine_set_screen_group", "mm_engine_set_screen_pair", "mm_screen_values_group", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
+    "mm_engine_set_screen_group", "mm_engine_set_screen_pair", "mm_engine_set_screen_floor", "mm_screen_values_group", "mm_screen_values_floor", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -390,6 +390,10 @@ def lib():
     L.mm_engine_set_screen_group.argtypes = [P, I]
     L.mm_engine_set_screen_pair.restype = I
     L.mm_engine_set_screen_pair.argtypes = [P, I]
+    L.mm_engine_set_screen_floor.restype = I
+    L.mm_engine_set_screen_floor.argtypes = [P, I]
+    L.mm_screen_values_floor.restype = I
+    L.mm_screen_values_floor.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, I, I, P, P, P, I, P]
     L.mm_screen_values_group.restype = I
     L.mm_screen_values_group.argtypes = [P, P, P, I, P, P, I, I, I, D, D, P, I, I, I, I, P, P, P, I, P]
     L.mm_tile_bound_probe_group.restype = I
@@ -1061,19 +1065,30 @@ class Engine:
         this setting."""
         check(lib().mm_engine_set_screen_pair(self._h, int(bool(on))), "mm_engine_set_screen_pair")
 
+    def set_screen_floor(self, on: bool):
+        """Culled screen: phase 2 only for rows and columns whose phase-1 minimum lies above the largest minimum that is
+        already exact (default).  Off: every minimum is made exact.  Same values; fewer tiles with it on.  The hooks
+        ``screen_values`` and ``screen_values_group`` screen with it off, ``screen_values_floor`` takes the flag."""
+        check(lib().mm_engine_set_screen_floor(self._h, int(bool(on))), "mm_engine_set_screen_floor")
+
     def screen_values_group(self, ref, tgt, angles, centre, group, cull=True, skip_zero=True, split=(0, 0)):
         """TEST HOOK (``mm_screen_values_group``): ``screen_values`` with the group size given; returns the values, e2 and
-        the work items as rows (first candidate, candidates, group size)."""
+        the work items as rows (first candidate, candidates, group size).  The value floor is off."""
+        return self.screen_values_floor(ref, tgt, angles, centre, group, False, cull, skip_zero, split)
+
+    def screen_values_floor(self, ref, tgt, angles, centre, group, floor, cull=True, skip_zero=True, split=(0, 0)):
+        """TEST HOOK (``mm_screen_values_floor``): ``screen_values_group`` with the value floor on or off."""
         ref = np.ascontiguousarray(ref, dtype=np.float64); tgt = np.ascontiguousarray(tgt, dtype=np.float64)
         rx, ry = np.ascontiguousarray(ref[:, 0]), np.ascontiguousarray(ref[:, 1])
         tx, ty = np.ascontiguousarray(tgt[:, 0]), np.ascontiguousarray(tgt[:, 1])
         ang = np.ascontiguousarray(angles, dtype=np.float64)
         out, e2 = np.zeros(len(ang), dtype=np.float32), C.c_double(0.0)
         items, n_items = np.zeros((len(ang), 3), dtype=np.int32), C.c_int(0)
-        check(lib().mm_screen_values_group(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), int(split[0]),
+        check(lib().mm_screen_values_floor(self._h, _ptr(rx), _ptr(ry), len(rx), _ptr(tx), _ptr(ty), len(tx), int(split[0]),
                                            int(split[1]), float(centre[0]), float(centre[1]), _ptr(ang), len(ang),
-                                           MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(cull)), int(group), _ptr(out),
-                                           C.byref(e2), _ptr(items), len(ang), C.byref(n_items)), "mm_screen_values_group")
+                                           MM_SEARCH_SKIP_ZERO if skip_zero else 0, int(bool(cull)), int(group),
+                                           int(bool(floor)), _ptr(out), C.byref(e2), _ptr(items), len(ang),
+                                           C.byref(n_items)), "mm_screen_values_floor")
         return out, e2.value, items[:n_items.value].copy()
 
     def screen_tiles(self):

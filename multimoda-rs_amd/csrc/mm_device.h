@@ -21,7 +21,7 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // the same screen without the tiles that provably hold no minimum (k_screen_mx_cull): pairs whose variant mx_cull_takes;
 // tiles (nullable): device counter of the tiles computed
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles, int pair,
-                                 hipStream_t s);
+                                 int floor, hipStream_t s);
 hipError_t launch_screen_none(const BatchDev& b, int work_begin, int n_work, hipStream_t s);   // screened value 0 for every candidate
 // bounded screen: lower bound of every lb_candidate_step()-th candidate -> per-pair pick -> full screen of
 // the picks (upper bound) -> spread the bounds to the candidates in between (chord inequality) ->

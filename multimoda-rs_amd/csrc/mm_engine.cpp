@@ -337,7 +337,8 @@ int Plan::run(bool screen_only)
                 case Screen::Matrix: e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s); break;
                 case Screen::MatrixCull:
                     eng->cull_tiles_full += g.tiles_full;
-                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, lv.opts.screen_pair ? 1 : 0, s);
+                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, lv.opts.screen_pair ? 1 : 0,
+                                              lv.opts.screen_floor ? 1 : 0, s);
                     break;
                 }
                 if (e != hipSuccess) break;
@@ -926,6 +927,14 @@ int mm_engine_set_screen_pair(mm_engine* h, int on)
     return MM_OK;
 }
 
+int mm_engine_set_screen_floor(mm_engine* h, int on)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    e->screen_opts.screen_floor = on != 0;
+    return MM_OK;
+}
+
 int mm_engine_screen_tiles(mm_engine* h, int64_t out[2])
 {
     Engine* e = reinterpret_cast<Engine*>(h);
@@ -1112,17 +1121,27 @@ int mm_screen_values_split(mm_engine* h, const double* rx, const double* ry, int
                            int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
                            int cull, float* out_sq2, double* e2)
 {
-    return mm_screen_values_group(h, rx, ry, nr, tx, ty, nt, ref_main, tgt_main, cx, cy, angles, n_angles, flags, cull, 1, out_sq2,
+    return mm_screen_values_floor(h, rx, ry, nr, tx, ty, nt, ref_main, tgt_main, cx, cy, angles, n_angles, flags, cull, 1, 0, out_sq2,
                                   e2, nullptr, 0, nullptr);
 }
 
 // The same with the culled screen's group size given (1, 2, 4, 8; 0: the engine's choice for this list; the followers run in
 // pairs or alone as the engine's switch says, mm_engine_set_screen_pair): the two hooks above
-// screen candidate by candidate (group 1).  items (nullable, room for items_cap triples): the plan's work items as
+// screen candidate by candidate (group 1).  All three screen with the value floor OFF, whatever the engine's switch says:
+// their callers state tile counts for the plain rule (mm_screen_values_floor takes the flag).  items (nullable, room for items_cap triples): the plan's work items as
 // (first candidate, candidates, group size) -- what the kernel's waves split into groups; *n_items: their number.
 int mm_screen_values_group(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
                            int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
                            int cull, int group, float* out_sq2, double* e2, int32_t* items, int items_cap, int* n_items)
+{
+    return mm_screen_values_floor(h, rx, ry, nr, tx, ty, nt, ref_main, tgt_main, cx, cy, angles, n_angles, flags, cull, group, 0,
+                                  out_sq2, e2, items, items_cap, n_items);
+}
+
+// The same with the value floor given too (floor != 0: ScreenOptions::screen_floor on, 0: off).
+int mm_screen_values_floor(mm_engine* h, const double* rx, const double* ry, int nr, const double* tx, const double* ty, int nt,
+                           int ref_main, int tgt_main, double cx, double cy, const double* angles, int n_angles, int flags,
+                           int cull, int group, int floor, float* out_sq2, double* e2, int32_t* items, int items_cap, int* n_items)
 {
     if (group != 0 && group != 1 && group != 2 && group != 4 && group != 8)
         return set_error(MM_ERR_INVALID, "mm_screen_values_group: group must be 0, 1, 2, 4 or 8");
@@ -1131,7 +1150,7 @@ int mm_screen_values_group(mm_engine* h, const double* rx, const double* ry, int
         tgt_main < 0 || ref_main >= nr || tgt_main >= nt)
         return set_error(MM_ERR_INVALID, "mm_screen_values: bad arguments");
     ScreenOptions opts = e->screen_opts;
-    opts.screen_cull = cull != 0; opts.screen_group = group;
+    opts.screen_cull = cull != 0; opts.screen_group = group; opts.screen_floor = floor != 0;
     Plan plan;
     int rc = stage_single(e, plan, SetRef{rx, ry, nr, cx, cy, ref_main}, SetRef{tx, ty, nt, cx, cy, tgt_main}, flags, angles, n_angles,
                           MM_PRECISION_F32_MATRIX, opts);

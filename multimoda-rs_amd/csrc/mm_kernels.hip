@@ -1015,6 +1015,26 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // follower left over run alone.  Neither a candidate's masks nor an MFMA's operands change, and a candidate's folds are its
 // own sequence over the same tiles in the same order: every cm, rmin, fmax and late has the bits of the unpaired path,
 // and the counters count per candidate what they count there.
+// The value floor (floor_on, ScreenOptions::screen_floor; set-bit variant): the value is the MAXIMUM of the row and column
+// minima, so a minimum that provably lies below an exact one need not be made exact.  P is the candidate's phase-1 mask (m1, or
+// m1 and the leader's phase-2 tiles for a follower), u_r / v_c the minima after phase 1 over P, Tr_I / Tc_J as above for P
+// (built once per group for m1 as well, in front of the leader).  A row is SETTLED if u_r <= Tr_I: every tile not computed
+// holds only values >= thr >= Tr_I >= u_r, so u_r is the row's full minimum; columns with Tc_J alike.  The floor L is the
+// largest settled minimum (0 without one, as rowmax starts at 0): an exact minimum, so L <= V, the full kernel's value.  A
+// row or column is LIVE if its minimum lies above L (a settled one never does), U'_I / V'_J is the largest live minimum of a
+// tile -- Umax_I if that lies above L, else "none" (0x80000000, below every thr) -- and phase 2 computes a tile outside P
+// unless thr >= max(U'_I, V'_J): the rule above with U', V' for Umax, Vmax.  The value is the maximum of all minima as they
+// then stand, by the code that took it before.  Why its bits cannot change: a live row has every tile with thr < u_r
+// computed (u_r <= U'_I), so its minimum is the full one, by the argument above.  A row that is not live ends with some m,
+// full minimum <= m <= u_r <= L <= V: it cannot raise the maximum above V, and nothing pulls the maximum below V, for every
+// m is a minimum over some of the row's values, at or above the full one, the row or column that gives V included (and
+// the settled one that gave L is in the maximum with its exact value).  Columns alike.  A superset of P only
+// lowers u and v and can only settle more; tile order, MFMA operands and the folds of a computed tile are untouched.
+// A follower leaves after phase 1 iff it has no live row or column, which is iff its phase-2 masks are all empty under this
+// rule: a live row r of row tile I is not settled, u_r > Tr_I = thr(I, J*) for a tile (I, J*) outside P, and u_r <= U'_I puts
+// that tile into the mask; without a live row or column every U', V' is "none" and every thr outside P (positive) skips.
+// With F the largest met minimum, "no minimum that is not settled lies above L" is F <= L; the follower's value is F.  Without
+// the floor L is "none" throughout, the rule is the plain one and the followers' test is the one above.
 // Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
 // -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
 // no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
@@ -1059,7 +1079,8 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
 // per GROUP of candidates; fgroup and fgnrt: once and once per row tile, per group that has followers; lrows and frows: once
 // per row tile of a leader and of a follower; fol, early, late: once per follower, per follower that leaves after phase 1,
 // per candidate that does not; "tile" is a computed tile's own body; the pairs' counts -- xcand, pair, single, prows, ptiles,
-// tails, ptails, sfol, searly, pearly, ylate -- are listed in the tool).
+// tails, ptails, sfol, searly, pearly, ylate -- are listed in the tool; gnrt and lead, once per row tile per group and once
+// per leader, are the value floor's).
 #define MXC_MARK(s) __asm__ volatile("; mxc:" s)
 #define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
 
@@ -1207,7 +1228,7 @@ __global__ void __launch_bounds__(256, 2)
 k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work, int a_cap,
                  const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
                  const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done,
-                 int pair_on)
+                 int pair_on, int floor_on)
 {
     constexpr int WAVES = 4, NB = NCT * 32, NQ = (NCT + 1) / 2, VS = 128, VM = 40, NT4 = (NCT + 3) / 4, NP = (NCT + 1) / 2;
     typedef typename mxc_regs<NCT>::type regs_t;
@@ -1225,7 +1246,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
     h4v* s_b = s_bw + wave * NCT * 64;
     int* s_rs = s_rsx + wave * a_cap * 32;
     int* s_ry = s_ryx + wave * a_cap * 32;
-    (void)s_ry; (void)pair_on;
+    (void)s_ry; (void)pair_on; (void)floor_on;
     float* s_th = s_thx + wave * a_cap * 32;
     // column tile t's 32 minima after phase 1 go to the coordinate half of its fragments (read into registers by then; the
     // norm half, written once per work item, is not touched): [NCT][VS] ints, 32 used per row
@@ -1339,6 +1360,31 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 const int L = __builtin_ctzll(lone), I = __builtin_amdgcn_readlane(lone_i, L);
                 if (lane == I) m1 |= 1u << L;
             }
+            // The value floor (see the header): Tr_I and Tc_J of the group's phase-1 mask m1, for the candidate that runs it
+            // (the leader, a group of one).  Built as behind the leader for the followers' larger mask, which replaces them.
+            if (floor_on) {
+                MXC_MARK("flr_tr:group");
+                if (lane < nrt) {
+                    const float4* q = reinterpret_cast<const float4*>(s_th + lane * 32);
+                    float th[NT4 * 4];
+#pragma unroll
+                    for (int u = 0; u < NT4; ++u) { const float4 w4 = q[u]; th[4 * u] = w4.x; th[4 * u + 1] = w4.y; th[4 * u + 2] = w4.z; th[4 * u + 3] = w4.w; }
+                    int tr = 0x7f800000;
+#pragma unroll
+                    for (int J = 0; J < NCT; ++J)
+                        if (!((m1 >> J) & 1)) tr = min(tr, __float_as_int(th[J]));
+                    grp_tr = tr;
+                }
+                int tc = 0x7f800000;
+                for (int I = 0; I < nrt; ++I) {
+                    MXC_MARK("flr_tc_row:gnrt");
+                    const unsigned pm = __builtin_amdgcn_readlane(m1, I);
+                    const int t = __float_as_int(s_th[I * 32 + l32]);
+                    if (!((pm >> l32) & 1)) tc = min(tc, t);
+                }
+                MXC_MARK("flr_tr:group");
+                grp_tc = tc;
+            }
           }
           (void)m1; (void)grp_tr; (void)grp_tc; (void)grp_p1;
           for (int k = k0; k < k1; ++k) {
@@ -1385,8 +1431,13 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 h8v af = s_a[lane];
                 // a follower on the way: the largest met row minimum so far (from 0, as the general path's rowmax), and
                 // whether a row minimum lies above its row tile's Tr_I (then row tile I has phase-2 tiles)
+                // The value floor on the way: the largest met row minimum that is SETTLED, at or below its row tile's Tr_I and
+                // therefore exact (from 0 too).  Both halves of the wave hold the same met row minima, so ONE register keeps
+                // both maxima of a follower -- the lower lanes the largest minimum, the upper lanes the largest settled one
+                // (no register more than without the floor in the loops); a leader keeps the settled one in every lane.
                 int fmax = 0;
                 unsigned long long late = 0;                                  // (a lane mask: scalar registers, no vector work)
+                const bool upper = lane >= 32;
                 // (the row loop twice in the code, so that a leader's is today's and a follower's has no branch per row tile)
                 auto p1_rows = [&](auto fol) {
                     for (int I = 0; I < nrt; ++I) {
@@ -1398,10 +1449,12 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         mxc_tiles<NCT, FOL ? 3 : 1>(mask, af, blo, bhi, cm, rmin);
                         rmin = mxc_meet(rmin);
                         if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                        const bool above = rmin > __builtin_amdgcn_readlane(grp_tr, I);
                         if constexpr (FOL) {
-                            fmax = max(fmax, rmin);
-                            late |= __builtin_amdgcn_ballot_w64(rmin > __builtin_amdgcn_readlane(grp_tr, I));
+                            fmax = max(fmax, above && upper ? 0 : rmin);
+                            late |= __builtin_amdgcn_ballot_w64(above);
                         } else {
+                            fmax = max(fmax, above ? 0 : rmin);
                             done += __builtin_popcount(mask);
                         }
                         af = an;
@@ -1411,10 +1464,8 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 // row tile I lies above Tr_I and no met column minimum of column tile J above Tc_J.  Then every row tile is
                 // final with Umax_I, and the value is the maximum of the met minima: what the general path returns with empty
                 // masks, without the column maxima, the masks, phase 2 and a second round of meets.
-                auto fol_check = [&](const regs_t& cmf, int& fm, unsigned long long& lt) {
+                auto fol_check = [&](const regs_t& cmf, int& fm, unsigned long long& lt, int& lo) {
                     __builtin_amdgcn_sched_barrier(0);                        // (the section's instructions stay behind its mark)
-                    done += grp_p1;
-                    ++n_foll;
                     // (two column tiles meet in one swap: the lower lanes then hold tile 2 p's met minima, the upper tile 2 p + 1's)
 #pragma unroll
                     for (int p = 0; p < NP; ++p) {
@@ -1422,18 +1473,33 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         const auto r = __builtin_amdgcn_permlane32_swap((unsigned)c0, (unsigned)c1, false, false);
                         const int v = min((int)r[0], (int)r[1]);
                         const int t0 = __builtin_amdgcn_readlane(grp_tc, 2 * p), t1 = __builtin_amdgcn_readlane(grp_tc, 2 * p + 1 < NCT ? 2 * p + 1 : 2 * p);
-                        lt |= __builtin_amdgcn_ballot_w64(v > (lane < 32 ? t0 : t1));
+                        const bool above = v > (lane < 32 ? t0 : t1);
+                        lt |= __builtin_amdgcn_ballot_w64(above);
                         fm = max(fm, v);
+                        lo = max(lo, above ? 0 : v);
                     }
                 };
-                auto fol_store = [&](int fm, int ai) {
-                    ++n_early;
-                    const int m = wave_max_i32_dpp(fm);
-                    if (lane == 0) out_sq[pd.out_off + ai] = __int_as_float(m) * inv_s2;
+                // A follower's verdict.  The floor L is the largest settled minimum and F the largest minimum met at all;
+                // without the floor a follower leaves iff every minimum is settled (no bit in lt), with it iff no minimum
+                // that is not settled lies above L, that is iff F <= L: exactly when it has no live row or column, which is
+                // when its phase-2 masks are all empty under the floor's rule (the header).  Its value is F either way.
+                auto fol_leaves = [&](int fm, unsigned long long lt, int lo, int ai, int& L) -> bool {
+                    done += grp_p1;
+                    ++n_foll;
+                    const int F = wave_max_i32_dpp(fm);
+                    L = floor_on ? wave_max_i32_dpp(lo) : (int)0x80000000;
+                    const bool leaves = floor_on ? F <= L : lt == 0;
+                    if (leaves) {
+                        ++n_early;
+                        if (lane == 0) out_sq[pd.out_off + ai] = __int_as_float(F) * inv_s2;
+                    }
+                    return leaves;
                 };
                 // What runs the general path below: bit 0 this candidate (X of a pair), bit 1 a pair's Y, on its own registers and
                 // its own row store, after X.
                 unsigned stay = 1;
+                // the floor L of X and of Y (wave-uniform); "none", below every minimum, with the switch off
+                int LX = (int)0x80000000, LY = (int)0x80000000;
                 regs_t bloY, bhiY, cmY;
                 int aY = a;
                 if (paired) {
@@ -1457,36 +1523,35 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         rminX = mxc_meet(rminX);
                         rminY = mxc_meet(rminY);
                         if (lane < 32) { s_rs[I * 32 + lane] = rminX; s_ry[I * 32 + lane] = rminY; }
-                        fmax = max(fmax, rminX);
-                        fmaxY = max(fmaxY, rminY);
-                        late |= __builtin_amdgcn_ballot_w64(rminX > tr);
-                        lateY |= __builtin_amdgcn_ballot_w64(rminY > tr);
+                        const bool aboveX = rminX > tr, aboveY = rminY > tr;
+                        late |= __builtin_amdgcn_ballot_w64(aboveX);
+                        lateY |= __builtin_amdgcn_ballot_w64(aboveY);
+                        fmax = max(fmax, aboveX && upper ? 0 : rminX);
+                        fmaxY = max(fmaxY, aboveY && upper ? 0 : rminY);
                         af = an;
                     }
                     MXC_MARK("fol_check2:pair");
-                    fol_check(cm, fmax, late);
-                    fol_check(cmY, fmaxY, lateY);
-                    stay = (late ? 1u : 0u) | (lateY ? 2u : 0u);
-                    if (!late) {
-                        MXC_MARK("fol_final2x:pearly");
-                        fol_store(fmax, a);
-                    }
-                    if (!lateY) {
-                        MXC_MARK("fol_final2y:pearly");
-                        fol_store(fmaxY, aY);
-                    }
+                    int flo = upper ? fmax : 0, floY = upper ? fmaxY : 0;
+                    fol_check(cm, fmax, late, flo);
+                    fol_check(cmY, fmaxY, lateY, floY);
+                    const bool goX = fol_leaves(fmax, late, flo, a, LX), goY = fol_leaves(fmaxY, lateY, floY, aY, LY);
+                    stay = (goX ? 0u : 1u) | (goY ? 0u : 2u);
                     MXC_MARK("end:0");
                 } else {
                     if (follower) p1_rows(std::true_type{}); else p1_rows(std::false_type{});
                     if (follower) {
                         MXC_MARK("fol_check:sfol");
-                        fol_check(cm, fmax, late);
-                        if (!late) {
-                            MXC_MARK("fol_final:searly");
-                            fol_store(fmax, a);
-                            stay = 0;
-                            MXC_MARK("end:0");
-                        }
+                        int flo = upper ? fmax : 0;
+                        fol_check(cm, fmax, late, flo);
+                        if (fol_leaves(fmax, late, flo, a, LX)) stay = 0;
+                        MXC_MARK("end:0");
+                    } else if (floor_on) {
+                        // the leader, a group of one: the floor from its met minima against the Tr_I, Tc_J of m1
+                        MXC_MARK("flr_lead:lead");
+                        int flo = fmax;
+                        fol_check(cm, fmax, late, flo);
+                        LX = wave_max_i32_dpp(flo);
+                        MXC_MARK("end:0");
                     }
                     // (Y's registers are nobody's here.  Said at this point, with no instruction: otherwise they count as
                     // undefined from the kernel's entry on and keep 51 registers through every other section.)
@@ -1499,7 +1564,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     // X is finished: Y's state into X's variables (only a pair's Y that stays pays for this)
                     MXC_MARK("ymove:ylate");
                     blo = bloY; bhi = bhiY; cm = cmY;
-                    acur = aY; rs = s_ry;
+                    acur = aY; rs = s_ry; LX = LY;
                 }
                 // Vmax_J: the column halves meet, lane j gathers column tile j's 32 minima and publishes their maximum
                 MXC_MARK("vmax:late");
@@ -1514,7 +1579,8 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     int v = (int)0x80000000;
 #pragma unroll
                     for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; v = max(v, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
-                    s_v[VM + lane] = v;                                       // (column tile 0's coordinate half, past its 32 minima)
+                    // (the floor: a column tile whose largest minimum is not above L has no live column: "none")
+                    s_v[VM + lane] = v > LX ? v : (int)0x80000000;           // (column tile 0's coordinate half, past its 32 minima)
                 }
                 __asm__ volatile("" ::: "memory");
                 // lane I (< nrt): Umax_I and the phase-2 mask of row tile I
@@ -1527,6 +1593,8 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     int umax = (int)0x80000000;
 #pragma unroll
                     for (int u = 0; u < 8; ++u) { const int4 w4 = q[u]; umax = max(umax, max(max(w4.x, w4.y), max(w4.z, w4.w))); }
+                    // (the floor: U'_I, the largest LIVE row minimum, is Umax_I if that lies above L, else there is none)
+                    const int ulive = umax > LX ? umax : (int)0x80000000;
                     const float4* qt = reinterpret_cast<const float4*>(s_th + lane * 32);
                     const int4* qv = reinterpret_cast<const int4*>(s_v + VM);
                     float th[NT4 * 4];
@@ -1539,7 +1607,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 #pragma unroll
                     for (int J = 0; J < NCT; ++J) {
                         const float t = th[J];
-                        const int lim = max(umax, vm[J]);
+                        const int lim = max(ulive, vm[J]);
                         if (!(t > 0.0f && __float_as_int(t) >= lim)) m2 |= 1u << J;
                     }
                     m2 &= ~p1m;
@@ -1746,23 +1814,23 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 
 template <int NCT>
 static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int n_work, int a_cap, unsigned long long* tiles,
-                                   int pair, hipStream_t s)
+                                   int pair, int floor, hipStream_t s)
 {
     const size_t lds = lds_bytes_mx_cull(NCT, a_cap);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_screen_mx_cull<NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_screen_mx_cull<NCT>), dim3(n_work), dim3(256), lds, s, b.pairs, work, n_work, a_cap, b.p32x, b.p32y,
-                       b.cos32, b.sin32, b.sq32, tiles, pair);
+                       b.cos32, b.sin32, b.sq32, tiles, pair, floor);
     return hipGetLastError();
 }
 
 hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
-                                 int pair, hipStream_t s)
+                                 int pair, int floor, hipStream_t s)
 {
     if (n_work <= 0) return hipSuccess;
     if (!mx_cull_takes(nct, 0, a_cap)) return hipErrorInvalidValue;
     const WorkItem* w = b.work + work_begin;
-#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, pair, s);
+#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, pair, floor, s);
     switch (nct) {
         MM_MXC(2) MM_MXC(3) MM_MXC(4) MM_MXC(5) MM_MXC(6) MM_MXC(7) MM_MXC(8) MM_MXC(9) MM_MXC(10) MM_MXC(11) MM_MXC(12)
         MM_MXC(13) MM_MXC(14) MM_MXC(15) MM_MXC(16) MM_MXC(17)

@@ -32,6 +32,9 @@ struct ScreenOptions {
                                             // more than a quarter of a work item; 1: off; 2 | 4 | 8: forced
     bool screen_pair = true;                // k_screen_mx_cull: a group's followers run their phase 1 two at a time (one tile
                                             // loop for both).  A launch argument: the plan is the same either way
+    bool screen_floor = true;               // k_screen_mx_cull (set-bit variant): the value floor -- phase 2 only for rows and
+                                            // columns whose phase-1 minimum lies above the largest minimum that is already
+                                            // exact.  A launch argument too: same plan, same values, fewer tiles
 };
 
 struct PairSpec {          // one search

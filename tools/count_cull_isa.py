@@ -14,6 +14,8 @@ how often the section runs per candidate:
     rows2    once per row tile that has tiles left in phase 2 (--rows2, default nrt: the upper bound)
     pairs64  once per 64 tile pairs     tiles    once per computed tile (summed over the copies, divided by their number)
     group    once per group of --group candidates (1 / G per candidate)      ghalf    `half`, per group
+    gnrt     `nrt`, per group           lead     once per leader (a group's first candidate; the value floor's sections: flr_tr
+             and flr_tc_row, Tr_I / Tc_J of the group's phase-1 mask, and flr_lead, the leader's floor L)
     fgroup   once per group that has followers (1 / G per candidate, none at G = 1)     fgnrt    `nrt`, per such group
     fol      once per follower of a group ((G - 1) / G per candidate)        frows    `nrt`, per follower
     lrows    `nrt`, per leader (a group's first candidate: 1 / G per candidate)
@@ -145,7 +147,7 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True
              "ptiles": tiles * pshare * (1.0 - tail) / 2, "ptails": tiles * pshare * tail / 2, "pair": pshare / 2, "prows": nrt * pshare / 2, "xcand": 1.0 - pshare / 2,
              "single": 1.0 - pshare, "sfol": sfol, "sfrows": nrt * sfol, "searly": early * sfol, "pearly": early * pshare / 2,
              "ylate": (1.0 - early) * pshare / 2,
-             "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group,
+             "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group, "gnrt": float(nrt) / group, "lead": 1.0 / group,
              "fgroup": fgroup, "fgnrt": nrt * fgroup,
              "fol": fol, "frows": nrt * sfol, "lrows": nrt * (1.0 - fol), "early": early * fol, "late": 1.0 - early * fol}
     out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (

@@ -27,6 +27,10 @@ inside each item, as the kernel's waves do: the device's counters are matched it
     python tools/model_cull_tiles.py --frames 12 --points 501 --pairs 1 2 3 4 --rotations 91
     python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --runs 15
     python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --items 23
+    python tools/model_cull_tiles.py --layout split --rotations 721 --group 8 --runs 15 --floor
+
+--floor prices the value floor (ScreenOptions::screen_floor): a candidate's value is the MAXIMUM of its minima, so a row or
+column whose phase-1 minimum lies at or below a minimum that is already exact cannot raise it and takes no phase-2 tile.
 """
 import argparse
 import os
@@ -108,11 +112,26 @@ def phase1(thr):
     return m1
 
 
-def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0, group=1, carry=True):
+def floor_maxima(u, v, thr, m1):
+    """The value floor (--floor; the kernel's header): u[nrt * 32], v[nct * 32] the row and column minima after
+    phase 1 over the mask m1.  A row is SETTLED if u_r <= Tr_I, the smallest thr of its row tile outside m1 (inf where
+    nothing is outside): its minimum is already the full one.  The floor L is the largest settled minimum, rows and columns
+    (0 without one), a row is LIVE if u_r > L (a settled one never is).  Returns (U', V', L): the largest live minimum of
+    every row tile and column tile, -inf where a tile has none (below every thr)."""
+    nrt, nct = thr.shape
+    out = np.where(m1, np.inf, thr)
+    tr, tc = np.repeat(out.min(axis=1), 32), np.repeat(out.min(axis=0), 32)
+    L = max(0.0, u[u <= tr].max(initial=0.0), v[v <= tc].max(initial=0.0))
+    ul = np.where(u > L, u, -np.inf).reshape(nrt, 32).max(axis=1)
+    vl = np.where(v > L, v, -np.inf).reshape(nct, 32).max(axis=1)
+    return ul, vl, L
+
+
+def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0, group=1, carry=True, floor=False):
     """(phase-1 tiles, phase-2 tiles) per candidate and row tile, int arrays [len(angles), nrt], for sets around (0, 0)
     laid out as asked (ref_main / tgt_main as the engine would take them: pass them through split_main first).  group > 1:
     the candidates [q group, (q + 1) group) of `angles` share thresholds and phase-1 mask, and with `carry` the first one's
-    phase-2 tiles are phase-1 tiles of the others."""
+    phase-2 tiles are phase-1 tiles of the others.  floor: phase 2 by the largest LIVE minima (floor_maxima)."""
     e, e2 = scale_and_e2(ref, tgt)
     S = 2.0 ** e
     nrt, nct = (len(ref) + 31) // 32, (len(tgt) + 31) // 32
@@ -138,8 +157,11 @@ def count_tiles(ref, tgt, angles, ref_main=0, tgt_main=0, group=1, carry=True):
         b = np.stack([b0[:, 0] * cd - b0[:, 1] * sd, b0[:, 0] * sd + b0[:, 1] * cd], axis=1)
         d2 = ((a[:, None, :] - b[None, :, :]) ** 2).sum(axis=2)
         big = np.where(np.repeat(np.repeat(m1, 32, axis=0), 32, axis=1), d2, np.inf)
-        u = big.min(axis=1).reshape(nrt, 32).max(axis=1)
-        v = big.min(axis=0).reshape(nct, 32).max(axis=1)
+        if floor:
+            u, v, _ = floor_maxima(big.min(axis=1), big.min(axis=0), thr, m1)
+        else:
+            u = big.min(axis=1).reshape(nrt, 32).max(axis=1)
+            v = big.min(axis=0).reshape(nct, 32).max(axis=1)
         m2 = ~m1 & ~((thr > 0) & (thr >= np.maximum(u[:, None], v[None, :])))
         if k % group == 0:
             lead = m2
@@ -175,6 +197,7 @@ def main():
     ap.add_argument("--layout", choices=("consecutive", "split", "both"), default="both")
     ap.add_argument("--group", type=int, default=1, help="candidates that share thresholds and phase-1 mask")
     ap.add_argument("--no-carry", action="store_true", help="the first candidate's phase-2 tiles are not handed on")
+    ap.add_argument("--floor", action="store_true", help="phase 2 by the value floor: only rows and columns that can still raise the value")
     ap.add_argument("--items", type=int, default=1, help="work items the list is cut into; groups start anew in each")
     ap.add_argument("--runs", type=int, default=0, help="price this many runs of --group candidates spread over the list (0: all)")
     a = ap.parse_args()
@@ -195,7 +218,7 @@ def main():
                 rm = tm = 0
             n, nw = len(angles), max(1, a.items)
             cuts = [(n * k // nw, n * (k + 1) // nw) for k in range(nw)]
-            parts = [count_tiles(ref, tgt, angles[a0:a1], split_main(len(ref), rm), split_main(len(tgt), tm), a.group, not a.no_carry)
+            parts = [count_tiles(ref, tgt, angles[a0:a1], split_main(len(ref), rm), split_main(len(tgt), tm), a.group, not a.no_carry, a.floor)
                      for a0, a1 in cuts if a1 > a0]
             p1, p2 = (np.concatenate([q[h] for q in parts]) for h in (0, 1))
             per_row = (p1 + p2).mean(axis=0)
