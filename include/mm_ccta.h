@@ -1134,6 +1134,108 @@ int     mm_isect_plan(const double* va, int64_t nva, const int64_t* fa, int64_t 
                       const int64_t* fb, int64_t nfb, int32_t* order_a, int32_t* order_b, int64_t* info, double* chunk_boxes,
                       int32_t* items, int64_t cap);
 
+/* ---- mesh cross-sections (no counterpart in the reference, whose roadmap lists "assess lumen area, minor-, major axis,
+ *      mla ... from the CCTA mesh" as open) ---------------------------------------------------------------------------
+ * The exact intersection of a triangle mesh with P planes, as contours with their measures.  tests/mm_checkers/
+ * mesh_sections.py is the executable form of the rule; csrc/mm_section_device.h is the C++ text of rules 1-4 and 8,
+ * csrc/mm_section.cpp that of rules 5-7.
+ *
+ * Inputs: v f64[nv,3], f int64[nf,3]; per plane an origin o and a normal n, which need not be unit.  Everything is
+ * unfused f64 in the order written, so chunking, scheduling, the cull and the order of the faces cannot change a bit of
+ * a point or a measure.
+ *
+ * 1. Height and side.  h(x) = (nx*(x.x-o.x) + ny*(x.y-o.y)) + nz*(x.z-o.z); side(x) = 0 if h < 0, else 1: a vertex
+ *    exactly on the plane is above it.  This is the whole degeneracy policy: the side is a function of the vertex alone,
+ *    so every face that shares it agrees, a plane through a vertex, an edge or a whole face needs no special case, and
+ *    every crossed face has exactly two crossed edges.
+ * 2. Faces.  A face with a repeated index is skipped and counted (n_skipped_faces).  Every other face is crossed by a
+ *    plane iff its three sides are not equal; faces without area are included.  Vertex identity is the index, not the
+ *    coordinates: an unwelded seam cuts into open polylines (mm_mesh_repair welds it).
+ * 3. Crossing point of a crossed edge.  The edge is keyed (lo, hi) by vertex index, lo < hi, and its point is always
+ *    computed from lo to hi: t = h_lo / (h_lo - h_hi); p = v_lo + t*(v_hi - v_lo) per component.  The two faces of an
+ *    edge compute the same bits.  One height is < 0 and the other >= 0, so the denominator is never 0 and 0 <= t <= 1.
+ * 4. Segment.  One per (plane, crossed face): the plane, the face, its two edge keys, the smaller key first (by lo, then
+ *    by hi), and the two points in that order.
+ * 5. Chaining, per plane, of its segments in ascending face order.  Segments that share an edge key are joined; a
+ *    component is a connected set of them.
+ *    - Some edge key has more than two segments: BRANCHED (kind 2).  Its distinct points are listed in ascending edge-key
+ *      order, with point_face = -1; area and centroid are NaN; length = the sum of its segments' lengths |p1 - p0| in
+ *      ascending face order.
+ *    - Two keys of one segment each: OPEN (kind 1), listed from the end with the smaller key.
+ *    - Every other component: a CLOSED loop (kind 0), listed from its smallest edge key, leaving it towards the smaller
+ *      of the two neighbouring keys (by the segment of the smaller face where both lead to the same key).  s (rule 6) is
+ *      computed in this order; if s < 0 the loop is listed the other way round (p0, p(m-1), ..., p1) and rule 6 is
+ *      computed anew in that order, whose s is the one reported; at s >= 0 the first order stays.
+ *    point_face of a point is the face of the segment that leaves it, -1 at the far end of an open polyline.  The
+ *    components of a plane are ordered by their smallest edge key.
+ * 6. Measures, with p(m) = p(0) for a loop, from i = 0, every sum started at 0.0:
+ *    d_i = p_i - o; c_i = d_i x d_(i+1) = (dy*ez - dz*ey, dz*ex - dx*ez, dx*ey - dy*ex) with e = d_(i+1); A += c_i;
+ *    w_i = (c.x*nx + c.y*ny) + c.z*nz; W += w_i; G += w_i * (d_i + d_(i+1)) per component.
+ *    s = (A.x*nx + A.y*ny) + A.z*nz; area = (0.5 * s) / sqrt((nx*nx + ny*ny) + nz*nz).
+ *    len_i = sqrt((ex*ex + ey*ey) + ez*ez) with e = p_(i+1) - p_i; length L += len_i; M += len_i * (0.5 * (p_i + p_(i+1))).
+ *    centroid = o + G / (3.0 * W) per component, the area centroid of the fan about o; where s == 0 or W == 0 it is M / L,
+ *    the length-weighted mean, and p_0 where L == 0.  An open polyline (its m - 1 segments) has length L and centroid
+ *    M / L (p_0 where L == 0); its area is NaN.
+ * 7. Selection.  Drop the axis of the largest |n| component, the first among equals (x leaves (u, v) = (y, z), y leaves
+ *    (x, z), z leaves (x, y)), as in rule 4 of "mesh intersections".  o is inside a closed loop iff the number of its
+ *    segments (a, b) with (a.v > o.v) != (b.v > o.v) and o.u < a.u + ((o.v - a.v) * (b.u - a.u)) / (b.v - a.v) is odd
+ *    (half-open in v).  selected[p] = among the closed loops of plane p that hold o the one with the smallest area (a
+ *    lumen inside a wall), the first of equal ones; -1 if there is none.
+ * 8. The cull loses nothing, with no slack.  h is monotone in each coordinate of x under rounding, so over a box it takes
+ *    its extremes at the two corners the signs of n pick: h_min at (n.k < 0 ? hi.k : lo.k), h_max at the opposite corner.
+ *    A chunk of 256 faces in slab order takes part for a plane iff h_min < 0 and not h_max < 0.  Heights
+ *    that overflow are outside the rule. */
+
+#define MM_SECTION_CLOSED   0
+#define MM_SECTION_OPEN     1
+#define MM_SECTION_BRANCHED 2
+#define MM_SECTION_SEGMENT_BYTES 72
+
+typedef struct mm_section_report {
+    int64_t n_planes, n_faces;
+    int64_t n_skipped_faces;      /* faces with a repeated index */
+    int64_t n_segments;           /* (plane, crossed face) pairs: complete also where the call returns MM_ERR_TOO_LARGE */
+    int64_t n_contours, n_closed, n_open, n_branched;
+    int64_t items;                /* (plane, chunk) pairs that pass rule 8 */
+    int64_t items_total;          /* planes x chunks */
+    int64_t face_tests;           /* (plane, face) pairs inside the items */
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+} mm_section_report;              /* 112 bytes */
+
+/* Contours of every plane, plane after plane (plane_off: n_planes + 1 entries into the contours; selected: n_planes
+ * contour indices or -1).  contour_off (one more entry than contours) indexes points (3 doubles), point_edge (2 int64:
+ * lo, hi) and point_face.  The contour arrays hold max_segments entries (contour_off one more), the point arrays
+ * 2 max_segments: no result is larger.  With more segments than max_segments the call returns MM_ERR_TOO_LARGE with
+ * report->n_segments set and no other output written: call once more with that capacity.  An empty mesh and zero planes
+ * are valid.  MM_ERR_INVALID: a non-finite coordinate or origin, a normal that is zero or not finite, a face index out
+ * of range, a size of 2^31 or more. */
+int     mm_mesh_sections(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                         const double* origins, const double* normals, int64_t n_planes, int64_t max_segments,
+                         int64_t* contour_off, double* points, int64_t* point_edge, int64_t* point_face,
+                         int64_t* contour_plane, int8_t* contour_kind, double* contour_area, double* contour_length,
+                         double* contour_centroid, int64_t* plane_off, int64_t* selected, mm_section_report* report);
+/* TEST HOOK (nothing in the product calls it; no engine, no device): the host plan of mm_mesh_sections.  order[j] = the
+ * face staged at position j (slabs by corner sum across the longest axis of all corners); chunk_boxes (nullable): lo xyz,
+ * hi xyz of every chunk; plane_list: per chunk, ascending, the planes that pass rule 8, chunk after chunk, at most
+ * list_cap entries; items (4 int32 each: chunk, first entry of the run in plane_list, planes of the run, 0), at most
+ * item_cap of them.  info[8] = {(plane, chunk) pairs, planes x chunks, faces per chunk, chunks, items, planes per run,
+ * face tests, skipped faces}. */
+int     mm_section_plan(const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf, const double* origins,
+                        const double* normals, int64_t n_planes, int32_t* order, int64_t* info, double* chunk_boxes,
+                        int32_t* plane_list, int64_t list_cap, int32_t* items, int64_t item_cap);
+/* TEST HOOK (no engine, no device): the items of that plan cut on the host by the arithmetic the kernel runs
+ * (csrc/mm_section_device.h).  segments: at most cap records of MM_SECTION_SEGMENT_BYTES (uint64 plane << 32 | face;
+ * 4 int32: the two edge keys; 6 doubles: the two points), sorted by (plane, face); *n_segments = their full number. */
+int     mm_section_cut_host(const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf, const double* origins,
+                            const double* normals, int64_t n_planes, int64_t cap, void* segments, int64_t* n_segments);
+/* TEST HOOK (no engine, no device): rules 5 to 7 on segment records sorted by (plane, face) -- the code
+ * mm_mesh_sections runs on what the device returns.  The arrays as there, with n_segments in the place of max_segments.
+ * counts[5] = {contours, points, closed, open, branched}. */
+int     mm_section_chain(const void* segments, int64_t n_segments, const double* origins, const double* normals,
+                         int64_t n_planes, int64_t* contour_off, double* points, int64_t* point_edge, int64_t* point_face,
+                         int64_t* contour_plane, int8_t* contour_kind, double* contour_area, double* contour_length,
+                         double* contour_centroid, int64_t* plane_off, int64_t* selected, int64_t* counts);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

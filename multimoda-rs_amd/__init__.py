@@ -46,6 +46,8 @@ from .surface import (DirectedDistance, PointMeshDistance, SurfaceDistanceReport
                       sample_mesh_surface, surface_distance)
 from . import intersect
 from .intersect import MeshIntersections, mesh_intersections, mesh_self_intersections
+from . import section
+from .section import MeshCrossSections, VesselProfile, centerline_cross_sections, mesh_cross_sections, vessel_profile
 from . import skeleton
 from .skeleton import SkeletonGraph, centerline_from_mesh, mesh_geodesic_distance, mesh_skeleton, skeleton_centerline
 from .convert import numpy_to_geometry, to_array
@@ -92,6 +94,7 @@ __all__ = [
     "surface", "point_mesh_distance", "sample_mesh_surface", "surface_distance", "PointMeshDistance",
     "DirectedDistance", "SurfaceDistanceReport",
     "intersect", "mesh_self_intersections", "mesh_intersections", "MeshIntersections",
+    "section", "mesh_cross_sections", "centerline_cross_sections", "vessel_profile", "MeshCrossSections", "VesselProfile",
     "skeleton", "mesh_geodesic_distance", "mesh_skeleton", "centerline_from_mesh", "skeleton_centerline", "SkeletonGraph",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",

@@ -123,6 +123,7 @@ EXPORTS_CCTA = [
     "mm_mesh_edge_lengths", "mm_mesh_refine", "mm_point_mesh_distance", "mm_tri_plan", "mm_mesh_relax",
     "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges", "mm_mesh_repair",
     "mm_mesh_intersections", "mm_isect_plan",
+    "mm_mesh_sections", "mm_section_plan", "mm_section_cut_host", "mm_section_chain",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -166,6 +167,13 @@ class MMSurfaceReport(C.Structure):
     """``mm_surface_report`` (include/mm_ccta.h)."""
     _fields_ = [(name, C.c_int64) for name in (
         "items_pass_a", "items_pass_b", "items_skipped", "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMSectionReport(C.Structure):
+    """``mm_section_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_planes", "n_faces", "n_skipped_faces", "n_segments", "n_contours", "n_closed", "n_open", "n_branched", "items",
+        "items_total", "face_tests", "n_launches", "bytes_uploaded", "bytes_downloaded")]
 
 
 class MMIntersectReport(C.Structure):
@@ -703,6 +711,14 @@ def lib():
     L.mm_mesh_intersections.argtypes = [P, P, I64, P, I64, P, I64, P, I64, I64, P, P, P, P, C.POINTER(MMIntersectReport)]
     L.mm_isect_plan.restype = I
     L.mm_isect_plan.argtypes = [P, I64, P, I64, P, I64, P, I64, P, P, P, P, P, I64]
+    L.mm_mesh_sections.restype = I
+    L.mm_mesh_sections.argtypes = [P, P, I64, P, I64, P, P, I64, I64, P, P, P, P, P, P, P, P, P, P, P, C.POINTER(MMSectionReport)]
+    L.mm_section_plan.restype = I
+    L.mm_section_plan.argtypes = [P, I64, P, I64, P, P, I64, P, P, P, P, I64, P, I64]
+    L.mm_section_cut_host.restype = I
+    L.mm_section_cut_host.argtypes = [P, I64, P, I64, P, P, I64, I64, P, P]
+    L.mm_section_chain.restype = I
+    L.mm_section_chain.argtypes = [P, I64, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, P]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

@@ -93,6 +93,16 @@ hipError_t launch_isect_pairs(const int32_t* items, int n_items, const double* t
                               unsigned long long* pairs, unsigned long long cap, hipStream_t s);
 int        isect_launches();
 int        isect_chunk_faces();
+// mesh cross-sections (mm_section_kernels.hip; the arithmetic is mm_section_device.h): tri12 = n_faces staged records of
+// 12 doubles in slab order (a, b, c as x y z w; a.w = index 0 | index 1 << 32, b.w = index 2 | original face << 32,
+// c.w = 1 for a face with a repeated index); planes = 6 doubles each (origin, normal); items = 4 int32 each (chunk,
+// first entry of its run in plane_list, planes of the run (at most 64), 0).  counters[8]: [0] = the segments found;
+// segments: the first `cap` of them, 72-byte records (section::Segment), in no order.  The clear of the counters is the
+// first launch.
+hipError_t launch_section_cut(const int32_t* items, int n_items, const int32_t* plane_list, const double* planes,
+                              const double* tri12, int n_faces, unsigned long long* counters, void* segments,
+                              unsigned long long cap, hipStream_t s);
+int        section_launches();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
 // xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = n_rays x ceil(n_faces /
 // ray_chunk_faces()) records of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits at least 3
