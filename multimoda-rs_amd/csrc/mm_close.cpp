@@ -192,25 +192,22 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
 
     // ---- phase 1 (dev_pts): faces up, winding, open half-edges down
     enum { kFlipped = 0, kOpen = 1, kNonManifold = 2, kConflict = 3, kOpen2 = 4, kNonManifold2 = 5, kConflict2 = 6, kCounts = 8 };
-    Carve lay;
     EdgeTable t;
-    const size_t o_face = lay.take((size_t)nf * 12);
-    t.plan(lay, nf);
-    const size_t o_link = lay.take((size_t)nf * 4), o_list = lay.take((size_t)nf * 24), o_nlist = lay.take(8);
-    const size_t o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
+    int32_t* d_face;
+    unsigned int *d_link, *d_changed;
+    unsigned long long *d_counts, *d_list, *d_nlist;
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 24 + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d_face, 3 * (size_t)nf);
+        t.lay(c, nf);
+        c.place(d_link, (size_t)nf); c.place(d_list, 3 * (size_t)nf); c.place(d_nlist, 1);
+        c.place(d_counts, kCounts); c.place(d_changed, 1);
+    });
+    if (rc) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)hb;
     narrow_faces(hf, faces, 3 * nf);
-    t.bind(b);
-    int32_t* d_face = (int32_t*)(b + o_face);
-    unsigned long long* d_counts = (unsigned long long*)(b + o_counts);
-    unsigned long long* d_list = (unsigned long long*)(b + o_list);
-    unsigned long long* d_nlist = (unsigned long long*)(b + o_nlist);
-    WindDev w{t.keys, t.cnt, t.own, (unsigned int*)(b + o_link), (unsigned int*)(b + o_changed), d_counts + kFlipped,
-              d_counts + kOpen, t.log2_e};
+    WindDev w{t.keys, t.cnt, t.own, d_link, d_changed, d_counts + kFlipped, d_counts + kOpen, t.log2_e};
     MM_TRY_HIP(hipMemcpyAsync(d_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemsetAsync(d_counts, 0, kCounts * 8, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));                      // the pinned buffer takes the round flags next
@@ -259,18 +256,22 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         return set_error(MM_ERR_TOO_LARGE, "mm_fill_holes: vert_cap / face_cap too small (the report holds the sizes)");
 
     // ---- phase 2 (dev_lvl): sized by the result
-    Carve lay2;
     EdgeTable t2;
-    const size_t p_fan = lay2.take((size_t)n_fan * 12), p_vert = lay2.take(fix ? (size_t)nv2 * 24 : 0);
-    const size_t up_bytes = lay2.size();
-    const size_t p_face = lay2.take((size_t)nf2 * 12);
-    t2.plan(lay2, nf2);
-    const size_t p_sa = lay2.take(fix ? (size_t)nf2 * 8 : 0), p_sb = lay2.take(fix ? weld_sum_scratch(nf2) * 8 : 0);
-    const size_t p_vol = lay2.take(8);
+    const int32_t* d_fan;
+    int32_t* d_face2;
+    double *d_vert, *d_sa, *d_sb, *d_vol;
+    size_t p_fan = 0, p_vert = 0, up_bytes = 0;
+    rc = carve_on(e, e->dev_lvl, [&](Carve& c) {
+        p_fan = c.place(d_fan, 3 * (size_t)n_fan); p_vert = c.place(d_vert, fix ? 3 * (size_t)nv2 : 0);
+        up_bytes = c.size();
+        c.place(d_face2, 3 * (size_t)nf2);
+        t2.lay(c, nf2);
+        c.place(d_sa, fix ? (size_t)nf2 : 0); c.place(d_sb, fix ? weld_sum_scratch(nf2) : 0);
+        c.place(d_vol, 1);
+    });
+    if (rc) return rc;
     if ((rc = e->ensure(e->host_pts, std::max(up_bytes, (size_t)nf2 * 12) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_lvl, lay2.size(), false))) return rc;
     hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b2 = (unsigned char*)e->dev_lvl.p;
     int32_t* h_fan = (int32_t*)(hb + p_fan);
     std::vector<double> centroids((size_t)(3 * n_loops));
     {
@@ -290,19 +291,15 @@ int mm_fill_holes(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         std::memcpy(hb + p_vert, vertices_xyz, (size_t)nv * 24);
         if (n_loops > 0) std::memcpy(hb + p_vert + (size_t)nv * 24, centroids.data(), (size_t)n_loops * 24);
     }
-    int32_t* d_face2 = (int32_t*)(b2 + p_face);
-    t2.bind(b2);
-    if (up_bytes > 0) MM_TRY_HIP(hipMemcpyAsync(b2, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
+    if (up_bytes > 0) MM_TRY_HIP(hipMemcpyAsync(e->dev_lvl.p, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(d_face2, d_face, (size_t)nf * 12, hipMemcpyDeviceToDevice, e->stream));
-    MM_TRY_HIP(launch_close_fan((const int32_t*)(b2 + p_fan), n_fan, nv, d_face2, nf, e->stream));
+    MM_TRY_HIP(launch_close_fan(d_fan, n_fan, nv, d_face2, nf, e->stream));
     MM_TRY_HIP(launch_weld_edges(d_face2, nf2, t2.keys, t2.cnt, t2.own, t2.log2_e, e->stream));
     MM_TRY_HIP(launch_weld_edge_report(t2.keys, t2.cnt, t2.own, t2.log2_e, nullptr, d_counts + kOpen2, e->stream));
     double volume = 0.0;
     int inverted = 0;
     if (fix) {
-        double* d_vol = (double*)(b2 + p_vol);
-        MM_TRY_HIP(launch_weld_volume((const double*)(b2 + p_vert), d_face2, nf2, (double*)(b2 + p_sa), (double*)(b2 + p_sb),
-                                      d_vol, e->stream));
+        MM_TRY_HIP(launch_weld_volume(d_vert, d_face2, nf2, d_sa, d_sb, d_vol, e->stream));
         double* hv = (double*)hb;                                     // stream order: behind the upload from there
         MM_TRY_HIP(hipMemcpyAsync(hv, d_vol, 8, hipMemcpyDeviceToHost, e->stream));
         MM_TRY_HIP(hipStreamSynchronize(e->stream));

@@ -14,66 +14,7 @@
 #include <cstring>
 
 #include "../../include/mm_ccta.h"
-#include "mm_stage.h"
-
-namespace mm {
-namespace {
-
-struct Scratch {
-    EdgeTable t;
-    size_t o_first, o_prio, o_rk, o_vw, o_best, o_counts, o_csr_counts, o_deg, o_off, o_tile, o_nb, o_fkeep, o_vkeep, o_to,
-        o_vtile, o_ftile, o_vidx, o_fidx, o_out_v, o_out_f, o_origin, o_target, o_sa, o_sb, size;
-    unsigned int *first, *vw;
-    unsigned long long *prio, *best, *counts, *csr_counts;
-    int32_t *rk, *deg, *off, *nb, *to, *vidx, *fidx, *out_f, *origin, *target;
-    uint8_t *fkeep, *vkeep;
-    long long *tile, *vtile, *ftile;
-    double *out_v, *sa, *sb;
-
-    void plan(int64_t nv, int64_t nf)
-    {
-        Carve lay;
-        t.plan(lay, nf);
-        const size_t cap = (size_t)1 << t.log2_e, V = (size_t)nv, Fn = (size_t)nf;
-        o_first = lay.take(cap * 4); o_prio = lay.take(cap * 8); o_rk = lay.take(cap * 8);
-        o_vw = lay.take(V * 4); o_best = lay.take(V * 8); o_counts = lay.take(col_num_words * 8);
-        o_csr_counts = lay.take(4 * 8);
-        o_deg = lay.take(V * 4); o_off = lay.take((V + 1) * 4); o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8);
-        o_nb = lay.take(cap * 4);                                      // twice the edges: at most 6 nf <= cap entries
-        o_fkeep = lay.take(Fn); o_vkeep = lay.take(V); o_to = lay.take(V * 4);
-        o_vtile = lay.take((trim_scan_tiles(nv) + 1) * 8); o_ftile = lay.take((trim_scan_tiles(nf) + 1) * 8);
-        o_vidx = lay.take(V * 4); o_fidx = lay.take(Fn * 4);
-        o_out_v = lay.take(V * 24); o_out_f = lay.take(Fn * 12); o_origin = lay.take(V * 4); o_target = lay.take(V * 4);
-        o_sa = lay.take(Fn * 8); o_sb = lay.take(weld_sum_scratch(nf) * 8);
-        size = lay.size();
-    }
-    void bind(unsigned char* b)
-    {
-        t.bind(b);
-        first = (unsigned int*)(b + o_first); prio = (unsigned long long*)(b + o_prio); rk = (int32_t*)(b + o_rk);
-        vw = (unsigned int*)(b + o_vw); best = (unsigned long long*)(b + o_best);
-        counts = (unsigned long long*)(b + o_counts); csr_counts = (unsigned long long*)(b + o_csr_counts);
-        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); tile = (long long*)(b + o_tile); nb = (int32_t*)(b + o_nb);
-        fkeep = b + o_fkeep; vkeep = b + o_vkeep; to = (int32_t*)(b + o_to);
-        vtile = (long long*)(b + o_vtile); ftile = (long long*)(b + o_ftile);
-        vidx = (int32_t*)(b + o_vidx); fidx = (int32_t*)(b + o_fidx);
-        out_v = (double*)(b + o_out_v); out_f = (int32_t*)(b + o_out_f);
-        origin = (int32_t*)(b + o_origin); target = (int32_t*)(b + o_target);
-        sa = (double*)(b + o_sa); sb = (double*)(b + o_sb);
-    }
-};
-
-// the counters of a pass, or of the table alone, through the first words of e->host_pts (behind the upload in stream order)
-int read_counts(Engine* e, const Scratch& s, const unsigned long long** words)
-{
-    MM_TRY_HIP(hipMemcpyAsync(e->host_pts.p, s.counts, col_num_words * 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    *words = (const unsigned long long*)e->host_pts.p;
-    return MM_OK;
-}
-
-}  // namespace
-}  // namespace mm
+#include "mm_mesh_layout.h"
 
 using namespace mm;
 
@@ -90,13 +31,10 @@ int mm_mesh_collapse_edges(mm_engine* h, const double* vertices_xyz, int64_t nv,
     if (rc) return rc;
     if (!report || max_passes < 0 || !(crease_cos >= 0.0 && crease_cos <= 1.0) || !(quality_keep >= 0.0 && quality_keep <= 1.0) ||
         !(target_len > 0.0) || !std::isfinite(target_len) || !(min_ratio > 0.0 && min_ratio <= 1.0) ||
-        !(max_ratio >= 1.0) || !std::isfinite(max_ratio) || (nv > 0 && (!vertices_xyz || !out_vertices || !out_origin || !out_target)) ||
+        !(max_ratio >= 1.0) || !std::isfinite(max_ratio) || (nv > 0 && (!out_vertices || !out_origin || !out_target)) ||
         (nf > 0 && !out_tris))
         return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (nf > 0 && !tris))
-        return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    if ((rc = faces_in_range(tris, nf, nv, who))) return rc;
-    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
+    if ((rc = mesh_args(who, vertices_xyz, nv, tris, nf, true))) return rc;
     mm_collapse_report rep;
     std::memset(&rep, 0, sizeof(rep));
     rep.n_vertices = rep.n_vertices_out = nv;
@@ -109,25 +47,18 @@ int mm_mesh_collapse_edges(mm_engine* h, const double* vertices_xyz, int64_t nv,
         return MM_OK;
     }
 
-    const size_t vbytes = (size_t)nv * 24, fbytes = (size_t)nf * 12, up_bytes = vbytes + fbytes + (mask ? (size_t)nv : 0);
+    const size_t vbytes = (size_t)nv * 24, fbytes = (size_t)nf * 12;
     const size_t h_f = up256(vbytes), h_origin = h_f + up256(fbytes), h_target = h_origin + up256((size_t)nv * 4);
     const size_t h_num = h_target + up256((size_t)nv * 4);
-    if ((rc = e->ensure(e->host_pts, std::max(up_bytes, h_num + col_num_words * 8) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, up_bytes, false))) return rc;
+    MeshUp up;
+    if ((rc = mesh_upload(e, vertices_xyz, nv, tris, nf, mask, h_num + col_num_words * 8, up))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    std::memcpy(hb, vertices_xyz, vbytes);
-    narrow_faces((int32_t*)(hb + vbytes), tris, 3 * nf);
-    if (mask) std::memcpy(hb + vbytes + fbytes, mask, (size_t)nv);
-    MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
-    const double* v = (const double*)b;
-    int32_t* face = (int32_t*)(b + vbytes);
-    const uint8_t* pin = mask ? b + vbytes + fbytes : nullptr;
+    const double* v = up.v;
+    int32_t* face = up.face;
+    const uint8_t* pin = up.pin;
 
-    Scratch s;
-    s.plan(nv, nf);
-    if ((rc = e->ensure(e->dev_raw, s.size, false))) return rc;
-    s.bind((unsigned char*)e->dev_raw.p);
+    CollapseScratch s;
+    if ((rc = carve_on(e, e->dev_raw, [&](Carve& c) { s.lay(c, nv, nf); }))) return rc;
     const double lo_len = min_ratio * target_len, hi_len = max_ratio * target_len;
     const double thr_min2 = lo_len * lo_len, thr_max2 = hi_len * hi_len;
     const double cc2 = crease_cos * crease_cos, qk2 = quality_keep * quality_keep;
@@ -160,7 +91,7 @@ int mm_mesh_collapse_edges(mm_engine* h, const double* vertices_xyz, int64_t nv,
                                    thr_max2, cc2, qk2, s.prio, s.rk, s.best, s.fkeep, s.vkeep, s.to, s.counts,
                                    e->stream));
         launches += 2;
-        if ((rc = read_counts(e, s, &c))) return rc;
+        if ((rc = read_words(e, s.counts, col_num_words, &c))) return rc;
         const int64_t n_cand = (int64_t)c[col_num_candidates], n_col = (int64_t)c[col_num_collapses];
         if (n_col > n_cand || (n_cand > 0 && n_col == 0))
             return set_error(MM_ERR_HIP, std::string(who) + ": the candidates and the collapses disagree");
@@ -181,7 +112,7 @@ int mm_mesh_collapse_edges(mm_engine* h, const double* vertices_xyz, int64_t nv,
     }
     if (!rep.converged) {                                              // the short edges of the result, a table of their own
         if ((rc = table())) return rc;
-        if ((rc = read_counts(e, s, &c))) return rc;
+        if ((rc = read_words(e, s.counts, col_num_words, &c))) return rc;
         if (rep.passes_run == 0) edge_counts(c);
         rep.n_short_after = (int64_t)c[col_num_short];
     }
@@ -213,7 +144,7 @@ int mm_mesh_collapse_edges(mm_engine* h, const double* vertices_xyz, int64_t nv,
     rep.n_vertices_out = kv;
     rep.n_faces_out = kf;
     rep.n_launches = launches;
-    rep.bytes_uploaded = (int64_t)up_bytes;
+    rep.bytes_uploaded = (int64_t)up.up_bytes;
     rep.bytes_downloaded = (int64_t)((size_t)kv * 28 + (size_t)kf * 12 + (size_t)nv * 4 + col_num_words * 8);
     std::memcpy(out_vertices, hb, (size_t)kv * 24);
     widen_faces(out_tris, (const int32_t*)(hb + h_f), 3 * kf);

@@ -8,7 +8,7 @@
 // integer atomics only.  The ring of r is its row of the sorted adjacency (launch_mesh_csr of mm_smooth_kernels.hip, built
 // from the same table); the faces at a removable r are, one per ring vertex n, the owner that traverses r -> n.
 //
-//   k_col_edge_insert  the three edges of every live face into the edge table of mm_mesh_device.h: the count, the first
+//   k_edge_insert_first (mm_mesh_device.h) the three edges of every live face into the edge table: the count, the first
 //                      two owners with their direction bits, and the smallest corner id with an atomicMin.
 //   k_col_valence      one lane per slot: deg (low 30 bits of a vertex word, atomicAdd), the border flag (bit 31) and the
 //                      inconsistent flag (bit 30) with an atomicOr; the edges, the open, non-manifold, inconsistent and
@@ -24,45 +24,13 @@
 
 #include "mm_device.h"
 #include "mm_mesh_device.h"
+#include "mm_tri_device.h"
 
 namespace mm {
 
 static constexpr unsigned int kColBorder = 0x80000000u;
 static constexpr unsigned int kColTwisted = 0x40000000u;
 static constexpr unsigned int kColDeg = 0x3FFFFFFFu;
-
-struct ColVec { double x, y, z; };
-
-static __device__ __forceinline__ ColVec col_sub(const double* __restrict__ p, const double* __restrict__ q)
-{
-    return ColVec{p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-}
-
-// the cross components and the dot of "surface distance", unfused
-static __device__ __forceinline__ ColVec col_cross(const ColVec& u, const ColVec& w)
-{
-    return ColVec{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-
-static __device__ __forceinline__ double col_dot(const ColVec& u, const ColVec& w)
-{
-    return (u.x * w.x + u.y * w.y) + u.z * w.z;
-}
-
-// ((dx dx + dy dy) + dz dz) of d = q - p: the squared length of "mesh refinement"
-static __device__ __forceinline__ double col_len_sq(const double* __restrict__ p, const double* __restrict__ q)
-{
-    const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// dot(n, n) / (S S) of the triangle (i, j, k) with normal n; 0 where S is 0
-static __device__ __forceinline__ double col_quality(const double* __restrict__ i, const double* __restrict__ j,
-                                                     const double* __restrict__ k, const ColVec& n)
-{
-    const double s = (col_len_sq(i, j) + col_len_sq(j, k)) + col_len_sq(k, i);
-    return s == 0.0 ? 0.0 : col_dot(n, n) / (s * s);
-}
 
 static __device__ __forceinline__ bool col_removable(unsigned int w, const uint8_t* __restrict__ pin, int32_t x)
 {
@@ -78,24 +46,6 @@ static __device__ __forceinline__ long long col_face_at(const unsigned long long
     if (s == kEdgeEmpty) return -1;
     const unsigned int o0 = own[2 * s], o1 = own[2 * s + 1];
     return (long long)((((o0 & 1u) != 0u) == (r < n) ? o0 : o1) >> 1);
-}
-
-__global__ void __launch_bounds__(kMeshThreads)
-k_col_edge_insert(const int32_t* __restrict__ face, long long nf, const uint8_t* __restrict__ fkeep,
-                  unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt, unsigned int* __restrict__ own,
-                  unsigned int* __restrict__ first, unsigned long long mask, int shift)
-{
-    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
-        if (!fkeep[f]) continue;
-        int32_t c[3] = {face[3 * f], face[3 * f + 1], face[3 * f + 2]};
-        for (int j = 0; j < 3; ++j) {
-            const int32_t u = c[j], w = c[j == 2 ? 0 : j + 1];
-            const unsigned long long s = edge_claim(keys, mask, shift, u, w);
-            const unsigned int p = atomicAdd(&cnt[s], 1u);
-            if (p < 2) own[2 * s + p] = ((unsigned int)f << 1) | (u < w ? 1u : 0u);
-            atomicMin(&first[s], (unsigned int)(3 * f + j));
-        }
-    }
 }
 
 // cap is a multiple of kMeshThreads, as is the stride
@@ -115,7 +65,7 @@ k_col_valence(const unsigned long long* __restrict__ keys, const unsigned int* _
         if (edge) {
             atomicAdd(&vw[lo], 1u);
             atomicAdd(&vw[hi], 1u);
-            is_short = col_len_sq(v + 3 * (long long)lo, v + 3 * (long long)hi) < thr_min2;
+            is_short = len_sq3(load3(v, lo), load3(v, hi)) < thr_min2;
         }
         if (used && c != 2u) {
             atomicOr(&vw[lo], kColBorder);
@@ -149,7 +99,6 @@ static __device__ __forceinline__ int col_direction(int32_t r, int32_t k, int32_
     const long long after_k = (long long)(vw[k] & kColDeg) + (long long)(vw[r] & kColDeg) - 4;
     const bool valence_ok = after_k >= 3 && (long long)(wc & kColDeg) - 1 >= ((wc & kColBorder) ? 2 : 3) &&
                             (long long)(wd & kColDeg) - 1 >= ((wd & kColBorder) ? 2 : 3);
-    const double *pr = v + 3 * (long long)r, *pk = v + 3 * (long long)k;
     int common = 0;
     bool too_long = false, turned = false, nan = false;
     double lng = 0.0, q_new = __longlong_as_double(0x7FF0000000000000ll), t_old = q_new;
@@ -157,7 +106,7 @@ static __device__ __forceinline__ int col_direction(int32_t r, int32_t k, int32_
         const int32_t n = nb[i];
         if (n != k && edge_find(keys, mask, shift, n, k) != kEdgeEmpty) ++common;
         if (n != k && n != c && n != d) {
-            const double x = col_len_sq(pk, v + 3 * (long long)n);
+            const double x = len_sq3(load3(v, k), load3(v, n));
             if (!(x <= thr_max2)) too_long = true;
             else if (x > lng) lng = x;
         }
@@ -165,16 +114,17 @@ static __device__ __forceinline__ int col_direction(int32_t r, int32_t k, int32_
         if (f < 0) continue;
         const int32_t a0 = face[3 * f], a1 = face[3 * f + 1], a2 = face[3 * f + 2];
         const int32_t x = a0 == r ? a1 : (a1 == r ? a2 : a0), y = a0 == r ? a2 : (a1 == r ? a0 : a1);
-        const double *px = v + 3 * (long long)x, *py = v + 3 * (long long)y;
-        const ColVec n_old = col_cross(col_sub(px, pr), col_sub(py, pr));
-        const double t = qk2 * col_quality(pr, px, py, n_old);
+        const V3 pr = load3(v, r), px = load3(v, x), py = load3(v, y);
+        const V3 n_old = cross3(sub3(px, pr), sub3(py, pr));
+        const double t = qk2 * tri_quality(pr, px, py, n_old);
         nan = nan || t != t;
         t_old = t < t_old ? t : t_old;
         if (f == fp || f == fm) continue;
-        const ColVec n_new = col_cross(col_sub(px, pk), col_sub(py, pk));
-        const double dn = col_dot(n_old, n_new);
-        if (!(dn > 0.0 && dn * dn >= cc2 * (col_dot(n_old, n_old) * col_dot(n_new, n_new)))) turned = true;
-        const double qn = col_quality(pk, px, py, n_new);
+        const V3 pk = load3(v, k);
+        const V3 n_new = cross3(sub3(px, pk), sub3(py, pk));
+        const double dn = dot3(n_old, n_new);
+        if (!(dn > 0.0 && dn * dn >= cc2 * (dot3(n_old, n_old) * dot3(n_new, n_new)))) turned = true;
+        const double qn = tri_quality(pk, px, py, n_new);
         nan = nan || qn != qn;
         q_new = qn < q_new ? qn : q_new;
     }
@@ -242,7 +192,7 @@ k_col_candidates(const unsigned long long* __restrict__ keys, const unsigned int
         }
         unsigned long long p = 0;
         if (reason == 0) {
-            const double l2 = col_len_sq(v + 3 * (long long)lo, v + 3 * (long long)hi);
+            const double l2 = len_sq3(load3(v, lo), load3(v, hi));
             const unsigned long long top = 0xFFFFFFFFull - ((unsigned long long)__double_as_longlong(l2) >> 32);
             p = (top << 32) | (unsigned long long)(0xFFFFFFFFu - first[s]);
             rk[2 * s] = r;
@@ -318,13 +268,9 @@ hipError_t launch_col_table(const int32_t* face, long long nf, const uint8_t* fk
                             unsigned long long* counts, hipStream_t s)
 {
     const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
-    hipError_t he;
-    if ((he = hipMemsetAsync(keys, 0xFF, cap * 8, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(first, 0xFF, cap * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(vw, 0, (size_t)nv * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(counts, 0, col_num_pass * 8, s)) != hipSuccess) return he;
-    MESH_LAUNCH(k_col_edge_insert, mesh_grid(nf), face, nf, fkeep, keys, cnt, own, first, cap - 1, 64 - log2_cap);
+    const hipError_t he = edge_first_clear(keys, cnt, first, cap, vw, nv, counts, col_num_pass, s);
+    if (he != hipSuccess) return he;
+    MESH_LAUNCH(k_edge_insert_first<true>, mesh_grid(nf), face, nf, fkeep, keys, cnt, own, first, cap - 1, 64 - log2_cap);
     MESH_LAUNCH(k_col_valence, mesh_grid((long long)cap), keys, cnt, own, cap, v, thr_min2, vw, prio, counts);
     return hipSuccess;
 }

@@ -6,7 +6,7 @@
 // flipped edges share no vertex and the answer is one whatever the scheduling.  One lane per item in grid-stride loops;
 // integer atomics only.
 //
-//   k_flip_edge_insert  the three edges of every face into the edge table of mm_mesh_device.h: the count, the first two
+//   k_edge_insert_first (mm_mesh_device.h) the three edges of every face into the edge table: the count, the first two
 //                       owners with their direction bits, and the smallest corner id with an atomicMin.
 //   k_flip_valence      one lane per slot: deg (low 31 bits of a vertex word, atomicAdd) and the border flag (bit 31,
 //                       atomicOr); the edges, the open, non-manifold, inconsistent and masked ones by ballot.
@@ -20,65 +20,16 @@
 
 #include "mm_device.h"
 #include "mm_mesh_device.h"
+#include "mm_tri_device.h"
 
 namespace mm {
 
 static constexpr unsigned int kFlipBorder = 0x80000000u;
 
-struct FlipVec { double x, y, z; };
-
-static __device__ __forceinline__ FlipVec flip_sub(const double* __restrict__ p, const double* __restrict__ q)
-{
-    return FlipVec{p[0] - q[0], p[1] - q[1], p[2] - q[2]};
-}
-
-// the cross components and the dot of "surface distance", unfused
-static __device__ __forceinline__ FlipVec flip_cross(const FlipVec& u, const FlipVec& w)
-{
-    return FlipVec{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-
-static __device__ __forceinline__ double flip_dot(const FlipVec& u, const FlipVec& w)
-{
-    return (u.x * w.x + u.y * w.y) + u.z * w.z;
-}
-
-// ((dx dx + dy dy) + dz dz) of d = q - p: the squared length of "mesh refinement"
-static __device__ __forceinline__ double flip_len_sq(const double* __restrict__ p, const double* __restrict__ q)
-{
-    const double dx = q[0] - p[0], dy = q[1] - p[1], dz = q[2] - p[2];
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// dot(n, n) / (S S) of the triangle (i, j, k) with normal n; 0 where S is 0
-static __device__ __forceinline__ double flip_quality(const double* __restrict__ i, const double* __restrict__ j,
-                                                      const double* __restrict__ k, const FlipVec& n)
-{
-    const double s = (flip_len_sq(i, j) + flip_len_sq(j, k)) + flip_len_sq(k, i);
-    return s == 0.0 ? 0.0 : flip_dot(n, n) / (s * s);
-}
-
 // deg - (border ? 4 : 6) of a vertex word
 static __device__ __forceinline__ long long flip_excess(unsigned int w)
 {
     return (long long)(w & ~kFlipBorder) - ((w & kFlipBorder) ? 4 : 6);
-}
-
-__global__ void __launch_bounds__(kMeshThreads)
-k_flip_edge_insert(const int32_t* __restrict__ face, long long nf, unsigned long long* __restrict__ keys,
-                   unsigned int* __restrict__ cnt, unsigned int* __restrict__ own, unsigned int* __restrict__ first,
-                   unsigned long long mask, int shift)
-{
-    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
-        int32_t c[3] = {face[3 * f], face[3 * f + 1], face[3 * f + 2]};
-        for (int j = 0; j < 3; ++j) {
-            const int32_t u = c[j], w = c[j == 2 ? 0 : j + 1];
-            const unsigned long long s = edge_claim(keys, mask, shift, u, w);
-            const unsigned int p = atomicAdd(&cnt[s], 1u);
-            if (p < 2) own[2 * s + p] = ((unsigned int)f << 1) | (u < w ? 1u : 0u);
-            atomicMin(&first[s], (unsigned int)(3 * f + j));
-        }
-    }
 }
 
 // cap is a multiple of kMeshThreads, as is the stride
@@ -159,23 +110,22 @@ k_flip_candidates(const unsigned long long* __restrict__ keys, const unsigned in
         }
         int blocked = 0;                                               // 1 .. 4: the guard (e) .. (h) that failed
         if (open) {
-            const double *pl = v + 3 * (long long)lo, *ph = v + 3 * (long long)hi;
-            const double *pc = v + 3 * (long long)c, *pd = v + 3 * (long long)d;
             if (edge_find(keys, cap - 1, shift, c, d) != kEdgeEmpty) {
                 blocked = 1;
             } else {
-                const FlipVec n0 = flip_cross(flip_sub(ph, pl), flip_sub(pc, pl));
-                const FlipVec n1 = flip_cross(flip_sub(pl, ph), flip_sub(pd, ph));
-                const FlipVec m0 = flip_cross(flip_sub(pd, pl), flip_sub(pc, pl));
-                const FlipVec m1 = flip_cross(flip_sub(pc, ph), flip_sub(pd, ph));
-                const double dn = flip_dot(n0, n1);
-                if (!(flip_dot(m0, n0) > 0.0 && flip_dot(m0, n1) > 0.0 && flip_dot(m1, n0) > 0.0 && flip_dot(m1, n1) > 0.0)) {
+                const V3 pl = load3(v, lo), ph = load3(v, hi), pc = load3(v, c), pd = load3(v, d);
+                const V3 n0 = cross3(sub3(ph, pl), sub3(pc, pl));
+                const V3 n1 = cross3(sub3(pl, ph), sub3(pd, ph));
+                const V3 m0 = cross3(sub3(pd, pl), sub3(pc, pl));
+                const V3 m1 = cross3(sub3(pc, ph), sub3(pd, ph));
+                const double dn = dot3(n0, n1);
+                if (!(dot3(m0, n0) > 0.0 && dot3(m0, n1) > 0.0 && dot3(m1, n0) > 0.0 && dot3(m1, n1) > 0.0)) {
                     blocked = 2;
-                } else if (!(dn > 0.0 && dn * dn >= cc2 * (flip_dot(n0, n0) * flip_dot(n1, n1)))) {
+                } else if (!(dn > 0.0 && dn * dn >= cc2 * (dot3(n0, n0) * dot3(n1, n1)))) {
                     blocked = 3;
                 } else {
-                    const double t0 = qk2 * flip_quality(pl, ph, pc, n0), t1 = qk2 * flip_quality(ph, pl, pd, n1);
-                    const double q0 = flip_quality(pl, pd, pc, m0), q1 = flip_quality(ph, pc, pd, m1);
+                    const double t0 = qk2 * tri_quality(pl, ph, pc, n0), t1 = qk2 * tri_quality(ph, pl, pd, n1);
+                    const double q0 = tri_quality(pl, pd, pc, m0), q1 = tri_quality(ph, pc, pd, m1);
                     if (!(q0 >= t0 && q0 >= t1 && q1 >= t0 && q1 >= t1)) blocked = 4;
                 }
             }
@@ -230,13 +180,10 @@ hipError_t launch_flip_valence(const int32_t* face, long long nf, long long nv, 
                                int log2_cap, unsigned int* vw, unsigned long long* counts, hipStream_t s)
 {
     const unsigned long long cap = 1ull << log2_cap;                   // at least kMeshThreads (the host sizes it)
-    hipError_t he;
-    if ((he = hipMemsetAsync(keys, 0xFF, cap * 8, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(first, 0xFF, cap * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(vw, 0, (size_t)nv * 4, s)) != hipSuccess) return he;
-    if ((he = hipMemsetAsync(counts, 0, flip_num_pass * 8, s)) != hipSuccess) return he;
-    MESH_LAUNCH(k_flip_edge_insert, mesh_grid(nf), face, nf, keys, cnt, own, first, cap - 1, 64 - log2_cap);
+    const hipError_t he = edge_first_clear(keys, cnt, first, cap, vw, nv, counts, flip_num_pass, s);
+    if (he != hipSuccess) return he;
+    MESH_LAUNCH(k_edge_insert_first<false>, mesh_grid(nf), face, nf, (const uint8_t*)nullptr, keys, cnt, own, first, cap - 1,
+                64 - log2_cap);
     MESH_LAUNCH(k_flip_valence, mesh_grid((long long)cap), keys, cnt, own, cap, pin, vw, counts);
     MESH_LAUNCH(k_flip_deviation, mesh_grid(nv), vw, nv, mesh_pad(nv), counts);
     return hipSuccess;

@@ -11,13 +11,13 @@
 //
 // The upload, [vertices | faces | seeds], lives in e->dev_pts and is never written.  The rest is carved from e->dev_raw:
 // the adjacency (CsrDev of mm_stage.h), one weight per adjacency entry, the seed bytes, the two flag arrays, the marks
-// of a batch, [dist | pred | counters] and, for the skeleton, what Skel lists.
+// of a batch, [dist | pred | counters] and, for the skeleton, what SkelScratch lists (mm_mesh_layout.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "../../include/mm_centerline.h"
-#include "mm_stage.h"
+#include "mm_mesh_layout.h"
 
 namespace mm {
 
@@ -27,75 +27,34 @@ namespace {
 
 constexpr int kFirstBatch = 8, kLongestBatch = 64;     // rounds between two reads of the marks
 
-// the skeleton's device buffers, behind the field's
-struct Skel {
-    size_t o_band, o_link, o_changed, o_root, o_ridx, o_rtile, o_sort, o_vnode, o_rim, o_nflags, o_vcnt, o_voff, o_ccnt,
-        o_coff, o_tile, o_scan, o_vlist, o_clist, o_area, o_rec, o_nout;
-    long long sort_cap;
-
-    void plan(Carve& lay, int64_t nv, int64_t nf)
-    {
-        const size_t V = (size_t)nv, Cn = 3 * (size_t)nf;
-        sort_cap = geo_sort_size(std::max<long long>(nv, 3 * nf));
-        o_band = lay.take(V * 4); o_link = lay.take(V * 4); o_changed = lay.take(4); o_root = lay.take(V);
-        o_ridx = lay.take(V * 4); o_rtile = lay.take((trim_scan_tiles(nv) + 1) * 8); o_sort = lay.take((size_t)sort_cap * 8);
-        o_vnode = lay.take(V * 4); o_rim = lay.take(V); o_nflags = lay.take(V * 4); o_vcnt = lay.take(V * 4);
-        o_voff = lay.take((V + 1) * 4); o_ccnt = lay.take(V * 4); o_coff = lay.take((V + 1) * 4);
-        o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8); o_scan = lay.take(4 * 8); o_vlist = lay.take(V * 4);
-        o_clist = lay.take(Cn * 4); o_area = lay.take((size_t)nf * 8); o_rec = lay.take(V * 80); o_nout = lay.take(8);
-    }
-};
-
-// The field, staged and computed: everything stays on the device.  plan() -> reserve() -> run().
-struct Field {
+// The field, staged and computed: everything stays on the device.  reserve() -> run().  The device buffers are those
+// of FieldScratch (mm_mesh_layout.h).
+struct Field : FieldScratch {
     Engine* e = nullptr;
     int64_t nv = 0, nf = 0, n_seeds = 0;
-    Carve up, lay;
-    CsrDev d;
-    Skel sk;
-    size_t u_v, u_f, u_s, o_w, o_seed, o_fa, o_fb, o_marks, o_dist, o_pred, o_counts;
-    unsigned char *hb = nullptr, *b = nullptr, *r = nullptr;
+    size_t u_v = 0, u_f = 0, u_s = 0, up_bytes = 0;                    // the upload: the same offsets on host and device
+    unsigned char *hb = nullptr, *b = nullptr;
     const double* v = nullptr;
     const int32_t *face = nullptr, *seeds = nullptr;
-    double* w = nullptr;
-    uint8_t* is_seed = nullptr;
-    unsigned long long *counts = nullptr, *dist = nullptr;
-    int32_t* pred = nullptr;
     int launches = 0;
     int64_t mark_bytes = 0;
 
-    void plan(int64_t nv_, int64_t nf_, int64_t ns, bool skeleton)
-    {
-        nv = nv_; nf = nf_; n_seeds = ns;
-        u_v = up.take((size_t)nv * 24); u_f = up.take((size_t)nf * 12); u_s = up.take((size_t)ns * 4);
-        d.plan(lay, nf, nv);
-        const size_t n_blocks = geo_blocks(nv);
-        o_w = lay.take(6 * (size_t)nf * 8); o_seed = lay.take((size_t)nv); o_fa = lay.take(n_blocks * 4);
-        o_fb = lay.take(n_blocks * 4); o_marks = lay.take(kLongestBatch * 8);
-        o_dist = lay.take((size_t)nv * 8); o_pred = lay.take((size_t)nv * 4); o_counts = lay.take(geo_num_words * 8);
-        if (skeleton) sk.plan(lay, nv, nf);
-    }
-    size_t field_down() const { return o_counts + geo_num_words * 8 - o_dist; }
-
-    int reserve(Engine* engine, size_t host_bytes)
+    // behind: what the caller downloads behind the field's block, from up256(field_down()) on
+    int reserve(Engine* engine, int64_t nv_, int64_t nf_, int64_t ns, bool skeleton, size_t behind)
     {
         e = engine;
-        int rc = e->ensure(e->host_pts, std::max(std::max(up.size(), field_down()), host_bytes) + 512, true);
+        nv = nv_; nf = nf_; n_seeds = ns;
+        int rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+            u_v = c.place(v, 3 * (size_t)nv); u_f = c.place(face, 3 * (size_t)nf); u_s = c.place(seeds, (size_t)ns);
+            up_bytes = c.size();
+        });
         if (rc) return rc;
-        if ((rc = e->ensure(e->dev_pts, up.size(), false))) return rc;
-        if ((rc = e->ensure(e->dev_raw, lay.size(), false))) return rc;
+        if ((rc = carve_on(e, e->dev_raw, [&](Carve& c) { lay(c, nv, nf, kLongestBatch, skeleton); }))) return rc;
+        const size_t down = behind ? up256(field_down()) + behind : field_down();
+        if ((rc = e->ensure(e->host_pts, std::max(up_bytes, down) + 512, true))) return rc;
         hb = (unsigned char*)e->host_pts.p;
         b = (unsigned char*)e->dev_pts.p;
-        r = (unsigned char*)e->dev_raw.p;
-        counts = (unsigned long long*)(r + o_counts);
-        d.bind(r, counts + geo_num_csr);
-        w = (double*)(r + o_w);
-        is_seed = r + o_seed;
-        dist = (unsigned long long*)(r + o_dist);
-        pred = (int32_t*)(r + o_pred);
-        v = (const double*)(b + u_v);
-        face = (const int32_t*)(b + u_f);
-        seeds = (const int32_t*)(b + u_s);
+        d.counts = counts + geo_num_csr;
         return MM_OK;
     }
 
@@ -105,9 +64,8 @@ struct Field {
         std::memcpy(hb + u_v, vertices_xyz, (size_t)nv * 24);
         narrow_faces((int32_t*)(hb + u_f), faces, 3 * nf);
         narrow_faces((int32_t*)(hb + u_s), seed_idx, n_seeds);
-        MM_TRY_HIP(hipMemcpyAsync(b, hb, up.size(), hipMemcpyHostToDevice, e->stream));
-        unsigned int *cur = (unsigned int*)(r + o_fa), *next = (unsigned int*)(r + o_fb);
-        unsigned long long* marks = (unsigned long long*)(r + o_marks);
+        MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
+        unsigned int *cur = flag_a, *next = flag_b;
         MM_TRY_HIP(hipMemsetAsync(counts, 0, geo_num_words * 8, e->stream));
         if (const int rc = csr_build(e, d, face, nf, nv, &launches)) return rc;
         MM_TRY_HIP(launch_geo_weights(v, d.off, d.nb, nv, w, counts, e->stream));
@@ -171,13 +129,11 @@ struct Field {
 int field_args(const char* who, const double* vertices_xyz, int64_t nv, const int64_t* faces, int64_t nf, const int64_t* seeds,
                int64_t n_seeds, const double* dist, const int64_t* pred)
 {
-    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || n_seeds <= 0 || n_seeds > kMaxIndex || !seeds ||
-        (nv > 0 && (!vertices_xyz || !dist || !pred)) || (nf > 0 && !faces))
+    if (n_seeds <= 0 || n_seeds > kMaxIndex || !seeds || (nv > 0 && (!dist || !pred)))
         return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    if (const int rc = faces_in_range(faces, nf, nv, who)) return rc;
+    if (const int rc = mesh_args(who, vertices_xyz, nv, faces, nf, true)) return rc;
     for (int64_t k = 0; k < n_seeds; ++k)
         if (seeds[k] < 0 || seeds[k] >= nv) return set_error(MM_ERR_INVALID, std::string(who) + ": seed out of range");
-    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
     return MM_OK;
 }
 
@@ -208,10 +164,9 @@ int mm_mesh_geodesic(mm_engine* h, const double* vertices_xyz, int64_t nv, const
     rep.n_vertices = nv;
     rep.n_faces = nf;
     Field fd;
-    fd.plan(nv, nf, n_seeds, false);
-    if ((rc = fd.reserve(e, 0))) return rc;
+    if ((rc = fd.reserve(e, nv, nf, n_seeds, false, 0))) return rc;
     if ((rc = fd.run(vertices_xyz, faces, seeds, rep, who))) return rc;
-    MM_TRY_HIP(hipMemcpyAsync(fd.hb, fd.r + fd.o_dist, fd.field_down(), hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(fd.hb, fd.dist, fd.field_down(), hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     if ((rc = fd.finish(fd.hb, dist, pred, rep, who))) return rc;
     *report = rep;
@@ -238,46 +193,34 @@ int mm_mesh_skeleton(mm_engine* h, const double* vertices_xyz, int64_t nv, const
     rep.field.n_faces = nf;
     rep.band_mm = band_mm;
     Field fd;
-    fd.plan(nv, nf, n_seeds, true);
-    const Skel& sk = fd.sk;
     // the host side of the download: the field's block, vertex_node, the nodes, the edges
-    const size_t h_vnode = up256(fd.field_down()), h_rec = h_vnode + up256((size_t)nv * 4), h_edges = h_rec + up256((size_t)nv * 80),
-                 h_end = h_edges + 3 * (size_t)nf * 8;
-    if ((rc = fd.reserve(e, h_end))) return rc;
+    const size_t behind = up256((size_t)nv * 4) + up256((size_t)nv * 80) + 3 * (size_t)nf * 8;
+    if ((rc = fd.reserve(e, nv, nf, n_seeds, true, behind))) return rc;
+    const size_t h_vnode = up256(fd.field_down()), h_rec = h_vnode + up256((size_t)nv * 4), h_edges = h_rec + up256((size_t)nv * 80);
     if ((rc = fd.run(vertices_xyz, faces, seeds, rep.field, who))) return rc;
 
-    unsigned char* r = fd.r;
-    int32_t *band = (int32_t*)(r + sk.o_band), *ridx = (int32_t*)(r + sk.o_ridx), *vnode = (int32_t*)(r + sk.o_vnode);
-    unsigned int *link = (unsigned int*)(r + sk.o_link), *changed = (unsigned int*)(r + sk.o_changed),
-                 *nflags = (unsigned int*)(r + sk.o_nflags);
-    uint8_t *is_root = r + sk.o_root, *rim = r + sk.o_rim;
-    long long *rtile = (long long*)(r + sk.o_rtile), *tile = (long long*)(r + sk.o_tile);
-    unsigned long long *sortbuf = (unsigned long long*)(r + sk.o_sort), *scan_counts = (unsigned long long*)(r + sk.o_scan),
-                       *n_out = (unsigned long long*)(r + sk.o_nout);
-    int32_t *vcnt = (int32_t*)(r + sk.o_vcnt), *voff = (int32_t*)(r + sk.o_voff), *ccnt = (int32_t*)(r + sk.o_ccnt),
-            *coff = (int32_t*)(r + sk.o_coff), *vlist = (int32_t*)(r + sk.o_vlist), *clist = (int32_t*)(r + sk.o_clist);
-    double *area3 = (double*)(r + sk.o_area), *rec = (double*)(r + sk.o_rec);
+    const SkelScratch& sk = fd.sk;
     int launches = fd.launches;
 
     // bands and their components
-    MM_TRY_HIP(launch_skel_bands(fd.dist, nv, band_mm, fd.d.off, fd.d.nb, fd.w, band, link, fd.counts, e->stream));
+    MM_TRY_HIP(launch_skel_bands(fd.dist, nv, band_mm, fd.d.off, fd.d.nb, fd.w, sk.band, sk.link, fd.counts, e->stream));
     launches += 2;
     unsigned int* hc = (unsigned int*)fd.hb;
     const int64_t bound = 2 + log2_at_least((unsigned long long)nv) + 8;   // a jumping round halves the depth
     for (;;) {
-        MM_TRY_HIP(launch_weld_jump(link, nv, changed, e->stream));
-        MM_TRY_HIP(hipMemcpyAsync(hc, changed, 4, hipMemcpyDeviceToHost, e->stream));
+        MM_TRY_HIP(launch_weld_jump(sk.link, nv, sk.changed, e->stream));
+        MM_TRY_HIP(hipMemcpyAsync(hc, sk.changed, 4, hipMemcpyDeviceToHost, e->stream));
         MM_TRY_HIP(hipStreamSynchronize(e->stream));
         ++rep.union_rounds;
         if (!hc[0]) break;
         if (rep.union_rounds > bound) return set_error(MM_ERR_HIP, std::string(who) + ": pointer jumping did not settle");
     }
     launches += (int)rep.union_rounds;
-    MM_TRY_HIP(launch_skel_roots(link, band, nv, is_root, e->stream));
-    MM_TRY_HIP(launch_trim_scan(is_root, nv, rtile, ridx, e->stream));
+    MM_TRY_HIP(launch_skel_roots(sk.link, sk.band, nv, sk.is_root, e->stream));
+    MM_TRY_HIP(launch_trim_scan(sk.is_root, nv, sk.rtile, sk.ridx, e->stream));
     launches += 4;
     unsigned long long* hn = (unsigned long long*)fd.hb;
-    MM_TRY_HIP(hipMemcpyAsync(hn, rtile + trim_scan_tiles(nv), 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hn, sk.rtile + trim_scan_tiles(nv), 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(hn + 1, fd.counts + geo_num_band_over, 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     if (hn[1]) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": a band index passes 2^31");
@@ -285,27 +228,27 @@ int mm_mesh_skeleton(mm_engine* h, const double* vertices_xyz, int64_t nv, const
     if (K < 1 || K > nv) return set_error(MM_ERR_HIP, std::string(who) + ": node count out of range");
 
     // numbered by (band, smallest vertex); the lists of every node in order; the records
-    MM_TRY_HIP(launch_skel_keys(ridx, band, nv, K, sortbuf, e->stream));
+    MM_TRY_HIP(launch_skel_keys(sk.ridx, sk.band, nv, K, sk.sortbuf, e->stream));
     ++launches;
-    MM_TRY_HIP(launch_geo_sort(sortbuf, K, &launches, e->stream));
-    MM_TRY_HIP(launch_skel_number(sortbuf, K, ridx, fd.d.edges.keys, fd.d.edges.cnt, fd.d.edges.log2_e, link, band, fd.is_seed,
-                                  nv, rim, vnode, nflags, vcnt, ccnt, e->stream));
-    MM_TRY_HIP(launch_skel_faces(fd.v, fd.face, nf, vnode, area3, ccnt, e->stream));
+    MM_TRY_HIP(launch_geo_sort(sk.sortbuf, K, &launches, e->stream));
+    MM_TRY_HIP(launch_skel_number(sk.sortbuf, K, sk.ridx, fd.d.edges.keys, fd.d.edges.cnt, fd.d.edges.log2_e, sk.link, sk.band, fd.is_seed,
+                                  nv, sk.rim, sk.vnode, sk.nflags, sk.vcnt, sk.ccnt, e->stream));
+    MM_TRY_HIP(launch_skel_faces(fd.v, fd.face, nf, sk.vnode, sk.area3, sk.ccnt, e->stream));
     launches += 3 + (nf > 0);
-    MM_TRY_HIP(hipMemsetAsync(scan_counts, 0, 4 * 8, e->stream));
-    MM_TRY_HIP(launch_mesh_row_offsets(vcnt, K, voff, tile, scan_counts, &launches, e->stream));
-    MM_TRY_HIP(launch_mesh_row_offsets(ccnt, K, coff, tile, scan_counts, &launches, e->stream));
-    MM_TRY_HIP(launch_skel_fill(fd.face, nf, vnode, nv, ccnt, clist, vcnt, vlist, e->stream));
+    MM_TRY_HIP(hipMemsetAsync(sk.scan_counts, 0, 4 * 8, e->stream));
+    MM_TRY_HIP(launch_mesh_row_offsets(sk.vcnt, K, sk.voff, sk.tile, sk.scan_counts, &launches, e->stream));
+    MM_TRY_HIP(launch_mesh_row_offsets(sk.ccnt, K, sk.coff, sk.tile, sk.scan_counts, &launches, e->stream));
+    MM_TRY_HIP(launch_skel_fill(fd.face, nf, sk.vnode, nv, sk.ccnt, sk.clist, sk.vcnt, sk.vlist, e->stream));
     ++launches;
-    MM_TRY_HIP(launch_mesh_row_sort(voff, vlist, K, &launches, e->stream));
-    MM_TRY_HIP(launch_mesh_row_sort(coff, clist, K, &launches, e->stream));
-    MM_TRY_HIP(launch_skel_nodes(K, coff, clist, voff, vlist, fd.face, area3, fd.v, band, nflags, rec, e->stream));
+    MM_TRY_HIP(launch_mesh_row_sort(sk.voff, sk.vlist, K, &launches, e->stream));
+    MM_TRY_HIP(launch_mesh_row_sort(sk.coff, sk.clist, K, &launches, e->stream));
+    MM_TRY_HIP(launch_skel_nodes(K, sk.coff, sk.clist, sk.voff, sk.vlist, fd.face, sk.area3, fd.v, sk.band, sk.nflags, sk.rec, e->stream));
     ++launches;
 
     // the node edges: the edge table's keys are free once the rim is marked
-    MM_TRY_HIP(launch_skel_edges(fd.d.off, fd.d.nb, fd.w, vnode, nv, fd.d.edges.keys, fd.d.edges.log2_e, sortbuf, n_out, e->stream));
+    MM_TRY_HIP(launch_skel_edges(fd.d.off, fd.d.nb, fd.w, sk.vnode, nv, fd.d.edges.keys, fd.d.edges.log2_e, sk.sortbuf, sk.n_out, e->stream));
     launches += 2;
-    MM_TRY_HIP(hipMemcpyAsync(hn, n_out, 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hn, sk.n_out, 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     const int64_t M = (int64_t)hn[0];
     if (M < 0 || M > 3 * nf) return set_error(MM_ERR_HIP, std::string(who) + ": node edge count out of range");
@@ -315,13 +258,13 @@ int mm_mesh_skeleton(mm_engine* h, const double* vertices_xyz, int64_t nv, const
         *report = rep;
         return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": node_cap or edge_cap too small (the report holds the sizes)");
     }
-    MM_TRY_HIP(launch_geo_sort(sortbuf, M, &launches, e->stream));
+    MM_TRY_HIP(launch_geo_sort(sk.sortbuf, M, &launches, e->stream));
 
     unsigned char* hb = fd.hb;
-    MM_TRY_HIP(hipMemcpyAsync(hb, r + fd.o_dist, fd.field_down(), hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(hb + h_vnode, vnode, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(hb + h_rec, rec, (size_t)K * 80, hipMemcpyDeviceToHost, e->stream));
-    if (M > 0) MM_TRY_HIP(hipMemcpyAsync(hb + h_edges, sortbuf, (size_t)M * 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hb, fd.dist, fd.field_down(), hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hb + h_vnode, sk.vnode, (size_t)nv * 4, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hb + h_rec, sk.rec, (size_t)K * 80, hipMemcpyDeviceToHost, e->stream));
+    if (M > 0) MM_TRY_HIP(hipMemcpyAsync(hb + h_edges, sk.sortbuf, (size_t)M * 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     fd.launches = launches;
     if ((rc = fd.finish(hb, dist, pred, rep.field, who))) return rc;

@@ -1,8 +1,8 @@
-// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_flip,
-// mm_collapse, mm_repair _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim,
-// refine, flip and repair files insert, the close, smooth and flip files read, EdgeTable of mm_stage.h sizes it), the
-// first-index-wins table and the hooking union-find of the weld and the repair, the workgroup scan and the two per-wave
-// ballot idioms.  Header-only; internal.
+// mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_relax,
+// mm_flip, mm_collapse, mm_repair, mm_geodesic _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim, refine, flip, collapse and repair files
+// insert, the close, smooth, flip, collapse and geodesic files read, EdgeTable of mm_stage.h sizes it) with the insert
+// kernel and the clear the flips and the collapse share, the first-index-wins table and the hooking union-find of the
+// weld and the repair, the workgroup scan and the two per-wave ballot idioms.  Header-only; internal.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -97,6 +97,38 @@ static __device__ __forceinline__ unsigned long long edge_insert(unsigned long l
     const unsigned int p = atomicAdd(&cnt[s], 1u);
     if (kOwners && p < 2) own[2 * s + p] = (f << 1) | (u < v ? 1u : 0u);
     return s;
+}
+
+// The table of the flips and the collapse: owners, and per slot in `first` the smallest corner id (3 f + the corner the
+// edge starts at) of the faces that own it -- what makes a priority unique.  One lane per face; kLive: only the faces
+// with fkeep set.
+template <bool kLive>
+__global__ void __launch_bounds__(kMeshThreads)
+k_edge_insert_first(const int32_t* __restrict__ face, long long nf, const uint8_t* __restrict__ fkeep,
+                    unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt, unsigned int* __restrict__ own,
+                    unsigned int* __restrict__ first, unsigned long long mask, int shift)
+{
+    for (long long f = mesh_tid(); f < nf; f += mesh_stride()) {
+        if (kLive && !fkeep[f]) continue;
+        int32_t c[3] = {face[3 * f], face[3 * f + 1], face[3 * f + 2]};
+        for (int j = 0; j < 3; ++j) {
+            const unsigned long long s = edge_insert<true>(keys, cnt, own, mask, shift, c[j], c[j == 2 ? 0 : j + 1], (unsigned int)f);
+            atomicMin(&first[s], (unsigned int)(3 * f + j));
+        }
+    }
+}
+
+// that table and the words beside it before an insertion: keys, cnt and first of cap slots, the nv vertex words, the
+// first n_counts counters
+inline hipError_t edge_first_clear(unsigned long long* keys, unsigned int* cnt, unsigned int* first, unsigned long long cap,
+                                   unsigned int* vw, long long nv, unsigned long long* counts, int n_counts, hipStream_t s)
+{
+    hipError_t he;
+    if ((he = hipMemsetAsync(keys, 0xFF, cap * 8, s)) != hipSuccess) return he;
+    if ((he = hipMemsetAsync(cnt, 0, cap * 4, s)) != hipSuccess) return he;
+    if ((he = hipMemsetAsync(first, 0xFF, cap * 4, s)) != hipSuccess) return he;
+    if ((he = hipMemsetAsync(vw, 0, (size_t)nv * 4, s)) != hipSuccess) return he;
+    return hipMemsetAsync(counts, 0, (size_t)n_counts * 8, s);
 }
 
 // ---- the first-index-wins table (the welds of mm_weld_kernels.hip, the repair's duplicates): open addressing over int32

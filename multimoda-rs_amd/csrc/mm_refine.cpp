@@ -14,22 +14,14 @@
 #include <cstring>
 
 #include "../../include/mm_ccta.h"
-#include "mm_stage.h"
+#include "mm_mesh_layout.h"
 
 namespace mm {
 namespace {
 
 // words of the counters block: those of mm_refine_kernels.hip, then the volume
-enum { kEdges = 0, kOpen, kNonManifold, kLongest, kMarked, kOne, kTwo, kThree, kNewVerts, kChildren, kVolume, kWords = 16 };
-
-int refine_args(const double* vertices, int64_t nv, const int64_t* tris, int64_t nf, const char* who)
-{
-    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (nv > 0 && !vertices) || (nf > 0 && !tris))
-        return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    if (const int rc = faces_in_range(tris, nf, nv, who)) return rc;
-    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
-    return MM_OK;
-}
+enum { kEdges = 0, kOpen, kNonManifold, kLongest, kMarked, kOne, kTwo, kThree, kNewVerts, kChildren, kVolume,
+       kWords = kRefineWords };
 
 // one generation of the mesh on the device
 struct Block {
@@ -37,32 +29,6 @@ struct Block {
     size_t o_par() const { return (size_t)nv * 24; }
     size_t o_face() const { return o_par() + (size_t)(nv - nv0) * 8; }
     size_t bytes() const { return o_face() + (size_t)nf * 12; }
-};
-
-// what a pass over nf faces needs beside the mesh
-struct Scratch {
-    EdgeTable t;
-    size_t o_slot, o_code, o_foff, o_tile, o_counts, o_sa, o_sb, o_list, size;
-    unsigned int* slot; uint8_t* code; int32_t* foff; long long* tile; unsigned long long* counts;
-    double *sa, *sb; unsigned char* list;
-
-    void plan(int64_t nf, size_t list_bytes = 0)
-    {
-        Carve lay;
-        t.plan(lay, nf);
-        o_slot = lay.take((size_t)nf * 12); o_code = lay.take((size_t)nf); o_foff = lay.take((size_t)nf * 4);
-        o_tile = lay.take((refine_tiles(nf) + 1) * 8); o_counts = lay.take(kWords * 8);
-        o_sa = lay.take((size_t)nf * 8); o_sb = lay.take(weld_sum_scratch(nf) * 8);
-        o_list = lay.take(list_bytes);
-        size = lay.size();
-    }
-    void bind(unsigned char* b)
-    {
-        t.bind(b);
-        slot = (unsigned int*)(b + o_slot); code = b + o_code; foff = (int32_t*)(b + o_foff);
-        tile = (long long*)(b + o_tile); counts = (unsigned long long*)(b + o_counts);
-        sa = (double*)(b + o_sa); sb = (double*)(b + o_sb); list = b + o_list;
-    }
 };
 
 // the edges of one generation, as its marks counted them
@@ -76,22 +42,9 @@ struct EdgeStats {
     }
 };
 
-// [vertices | int32 triangles] through e->host_pts into e->dev_pts, where the scratch of the first pass is ready too
-int upload(Engine* e, const double* vertices, int64_t nv, const int64_t* tris, int64_t nf)
-{
-    const size_t vbytes = (size_t)nv * 24, bytes = vbytes + (size_t)nf * 12;
-    if (const int rc = e->ensure(e->host_pts, bytes + 512, true)) return rc;
-    if (const int rc = e->ensure(e->dev_pts, bytes, false)) return rc;
-    unsigned char* hb = (unsigned char*)e->host_pts.p;
-    std::memcpy(hb, vertices, vbytes);
-    narrow_faces((int32_t*)(hb + vbytes), tris, 3 * nf);
-    MM_TRY_HIP(hipMemcpyAsync(e->dev_pts.p, hb, bytes, hipMemcpyHostToDevice, e->stream));
-    return MM_OK;
-}
-
 // the front of a pass over the mesh at `b`: the edge table and the marks, with `counts` the faces' codes and the scan of
 // their tile sums; the counters come back through the first words of e->host_pts (behind the upload in stream order)
-int pass_front(Engine* e, const Scratch& s, const Block& m, const unsigned char* b, double thr2, int all, bool counts,
+int pass_front(Engine* e, const RefineScratch& s, const Block& m, const unsigned char* b, double thr2, int all, bool counts,
                int64_t* launches, const unsigned long long** words)
 {
     const double* v = (const double*)b;
@@ -103,10 +56,7 @@ int pass_front(Engine* e, const Scratch& s, const Block& m, const unsigned char*
         MM_TRY_HIP(launch_refine_counts(s.slot, s.t.own, m.nf, s.code, s.tile, s.counts, e->stream));
         *launches += 2;
     }
-    MM_TRY_HIP(hipMemcpyAsync(e->host_pts.p, s.counts, kWords * 8, hipMemcpyDeviceToHost, e->stream));
-    MM_TRY_HIP(hipStreamSynchronize(e->stream));
-    *words = (const unsigned long long*)e->host_pts.p;
-    return MM_OK;
+    return read_words(e, s.counts, kWords, words);
 }
 
 }  // namespace
@@ -124,16 +74,15 @@ int mm_mesh_edge_lengths(mm_engine* h, const double* vertices_xyz, int64_t nv, c
     if (rc) return rc;
     if (!info || edge_cap < 0 || (edge_cap > 0 && (!out_edges || !out_len_sq)))
         return set_error(MM_ERR_INVALID, "mm_mesh_edge_lengths: bad arguments");
-    if ((rc = refine_args(vertices_xyz, nv, tris, nf, "mm_mesh_edge_lengths"))) return rc;
+    if ((rc = mesh_args("mm_mesh_edge_lengths", vertices_xyz, nv, tris, nf, true))) return rc;
     std::memset(info, 0, 4 * sizeof(int64_t));
     if (nv == 0 || nf == 0) return MM_OK;
-    if ((rc = upload(e, vertices_xyz, nv, tris, nf))) return rc;
+    MeshUp up;
+    if ((rc = mesh_upload(e, vertices_xyz, nv, tris, nf, nullptr, 0, up))) return rc;
     const Block m{nv, nf, nv};
-    Scratch s;
+    RefineScratch s;
     const size_t o_len = up256((size_t)nf * 24);                       // at most 3 nf edges: int32 pairs, then doubles
-    s.plan(nf, o_len + (size_t)nf * 24);
-    if ((rc = e->ensure(e->dev_raw, s.size, false))) return rc;
-    s.bind((unsigned char*)e->dev_raw.p);
+    if ((rc = carve_on(e, e->dev_raw, [&](Carve& c) { s.lay(c, nf, o_len + (size_t)nf * 24); }))) return rc;
     const unsigned char* b = (const unsigned char*)e->dev_pts.p;
     int64_t launches = 0;
     const unsigned long long* c;
@@ -170,7 +119,7 @@ int mm_mesh_refine(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
         !(ratio > 0.0) || !std::isfinite(thr2) || !(thr2 > 0.0) || (vert_cap > 0 && !out_vertices) ||
         (face_cap > 0 && !out_tris) || (nv >= 0 && vert_cap > nv && !out_parents))
         return set_error(MM_ERR_INVALID, "mm_mesh_refine: bad arguments");
-    if ((rc = refine_args(vertices_xyz, nv, tris, nf, "mm_mesh_refine"))) return rc;
+    if ((rc = mesh_args("mm_mesh_refine", vertices_xyz, nv, tris, nf, true))) return rc;
     std::memset(report, 0, sizeof(*report));
     report->n_vertices = nv;
     report->n_faces = nf;
@@ -181,19 +130,18 @@ int mm_mesh_refine(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
         if (nf > 0) std::memcpy(out_tris, tris, (size_t)nf * 24);
         return MM_OK;
     }
-    if ((rc = upload(e, vertices_xyz, nv, tris, nf))) return rc;
-    report->bytes_uploaded = nv * 24 + nf * 12;
+    MeshUp up;
+    if ((rc = mesh_upload(e, vertices_xyz, nv, tris, nf, nullptr, 0, up))) return rc;
+    report->bytes_uploaded = (int64_t)up.up_bytes;
 
     Engine::Buf* cur = &e->dev_pts;
     Engine::Buf* oth = &e->dev_lvl;
     Block m{nv, nf, nv};
-    Scratch s;
+    RefineScratch s;
     EdgeStats before, after;
     int64_t launches = 0, passes = 0;
     for (bool first = true;; first = false) {
-        s.plan(m.nf);
-        if ((rc = e->ensure(e->dev_raw, s.size, false))) return rc;
-        s.bind((unsigned char*)e->dev_raw.p);
+        if ((rc = carve_on(e, e->dev_raw, [&](Carve& c) { s.lay(c, m.nf); }))) return rc;
         unsigned char* b = (unsigned char*)cur->p;
         if (first) {
             MM_TRY_HIP(launch_weld_volume((const double*)b, (const int32_t*)(b + m.o_face()), m.nf, s.sa, s.sb,

@@ -99,25 +99,36 @@ int mm_mesh_relax(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
 
     // device: [faces | v0 | staged reference | queries | their vertices | items | chunk boxes] (the upload),
     // [x | the queries' faces | numbers] (the download), then scratch
-    const size_t vbytes = (size_t)nv * 24;
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12), o_v0 = lay.take(vbytes);
-    const size_t o_tri = lay.take(project ? (size_t)ref_nf * 96 : 0), o_q = lay.take((size_t)nq * 24);
-    const size_t o_qv = lay.take((size_t)nq * 4), o_work = lay.take((size_t)n_items * sizeof(TriWork));
-    const size_t o_cbox = lay.take((size_t)nch * sizeof(Box3));
-    const size_t up_bytes = lay.size();
-    const size_t o_x = lay.take(vbytes), o_fkey = lay.take((size_t)nq * 8), o_num = lay.take(256);
-    const size_t down_bytes = lay.size() - up_bytes;
-    const size_t o_sq = lay.take((size_t)nq * 8), o_key = lay.take((size_t)nq * 8), o_cl = lay.take((size_t)nq * 24);
-    const size_t o_reg = lay.take((size_t)nq * 4), o_state = lay.take((size_t)nq * 4), o_vq = lay.take((size_t)nv * 4);
+    const size_t vbytes = (size_t)nv * 24, V = (size_t)nv, Q = (size_t)nq;
     CsrDev d;
-    if (iterate) d.plan(lay, nf, nv);
-    const size_t o_sa = lay.take((size_t)nf * 8), o_sb = lay.take(weld_sum_scratch(nf) * 8);
-    static_assert(relax_num_words * 8 <= 256, "the numbers block");
+    const int32_t *d_face, *qv;
+    const double *v0, *tri, *cbox;
+    double *qxyz, *x, *cl, *sa, *sb;
+    TriWork* work;
+    unsigned long long *fkey, *num, *sq, *key;
+    int32_t *reg, *vq;
+    unsigned int* state;
+    size_t o_face = 0, o_v0 = 0, o_tri = 0, o_q = 0, o_qv = 0, o_work = 0, o_cbox = 0, o_x = 0, o_fkey = 0, o_num = 0;
+    size_t up_bytes = 0, down_bytes = 0;
+    static_assert(relax_num_words * 8 <= 256 && sizeof(Box3) == 48, "the numbers block; six doubles a chunk box");
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        o_face = c.place(d_face, 3 * (size_t)nf); o_v0 = c.place(v0, 3 * V);
+        o_tri = c.place(tri, project ? 12 * (size_t)ref_nf : 0); o_q = c.place(qxyz, 3 * Q);
+        o_qv = c.place(qv, Q); o_work = c.place(work, (size_t)n_items);
+        o_cbox = c.place(cbox, 6 * (size_t)nch);
+        up_bytes = c.size();
+        o_x = c.place(x, 3 * V); o_fkey = c.place(fkey, Q); o_num = c.place(num, 32);
+        down_bytes = c.size() - up_bytes;
+        c.place(sq, Q); c.place(key, Q); c.place(cl, 3 * Q);
+        c.place(reg, Q); c.place(state, Q); c.place(vq, V);
+        if (iterate) d.lay(c, nf, nv);
+        c.place(sa, (size_t)nf); c.place(sb, weld_sum_scratch(nf));
+    });
+    if (rc) return rc;
     if ((rc = e->ensure(e->host_pts, std::max(up_bytes, down_bytes) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
+    d.counts = num + relax_num_csr;
 
     narrow_faces((int32_t*)(hb + o_face), faces, 3 * nf);
     std::memcpy(hb + o_v0, vertices_xyz, vbytes);
@@ -133,22 +144,6 @@ int mm_mesh_relax(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         std::memcpy(hb + o_work, pl.work.data(), (size_t)n_items * sizeof(TriWork));
         std::memcpy(hb + o_cbox, pl.cbox.data(), (size_t)nch * sizeof(Box3));
     }
-
-    const int32_t* d_face = (const int32_t*)(b + o_face);
-    const double* v0 = (const double*)(b + o_v0);
-    const double* tri = (const double*)(b + o_tri);
-    double* qxyz = (double*)(b + o_q);
-    const int32_t* qv = (const int32_t*)(b + o_qv);
-    TriWork* work = (TriWork*)(b + o_work);
-    double* x = (double*)(b + o_x);
-    unsigned long long* fkey = (unsigned long long*)(b + o_fkey);
-    unsigned long long* num = (unsigned long long*)(b + o_num);
-    unsigned long long *sq = (unsigned long long*)(b + o_sq), *key = (unsigned long long*)(b + o_key);
-    double* cl = (double*)(b + o_cl);
-    int32_t *reg = (int32_t*)(b + o_reg), *vq = (int32_t*)(b + o_vq);
-    unsigned int* state = (unsigned int*)(b + o_state);
-    double *sa = (double*)(b + o_sa), *sb = (double*)(b + o_sb);
-    if (iterate) d.bind(b, num + relax_num_csr);
 
     int launches = 0;
     MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
@@ -169,7 +164,7 @@ int mm_mesh_relax(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
         if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
         for (int64_t it = 0; it < n_iterations; ++it) {
             MM_TRY_HIP(launch_relax_candidates(d.off, d.nb, x, qv, (int)nq, fkey, tri, factor, qxyz, sq, key, state, work,
-                                               (int)pl.n_a, (int)pl.n_b, (const double*)(b + o_cbox), e->stream));
+                                               (int)pl.n_a, (int)pl.n_b, cbox, e->stream));
             MM_TRY_HIP(launch_tri_seeded(work, (int)n_items, tri, (int)ref_nf, qxyz, (int)nq, sq, key, cl, reg,
                                          num + relax_num_skipped, e->stream));
             MM_TRY_HIP(launch_relax_guard(d_face, nf, x, cl, key, vq, state, e->stream));
@@ -182,7 +177,7 @@ int mm_mesh_relax(mm_engine* h, const double* vertices_xyz, int64_t nv, const in
     MM_TRY_HIP(launch_relax_flipped(d_face, nf, v0, x, num, e->stream));
     ++launches;
     MM_TRY_HIP(launch_mesh_disp(v0, x, nv, num + relax_num_disp, &launches, e->stream));
-    MM_TRY_HIP(hipMemcpyAsync(hb, b + o_x, down_bytes, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(hb, x, down_bytes, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
 
     std::memcpy(out_vertices, hb, vbytes);

@@ -34,13 +34,6 @@ namespace mm {
 static constexpr unsigned long long kNoFace = ~0ull;
 enum : unsigned int { kRelaxStays = 1u, kRelaxGuarded = 2u };          // bits of a query's state
 
-// (u x w) with the component expressions of the degenerate test
-static __device__ __forceinline__ V3 cross3(const V3& u, const V3& w)
-{
-    return V3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
-}
-
-static __device__ __forceinline__ V3 load3(const double* p, long long i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 static __device__ __forceinline__ void store3(double* p, long long i, const V3& v)
 {
     p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z;

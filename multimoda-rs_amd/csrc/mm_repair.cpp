@@ -14,65 +14,7 @@
 #include <cstring>
 
 #include "../../include/mm_ccta.h"
-#include "mm_stage.h"
-
-namespace mm {
-namespace {
-
-struct Scratch {
-    EdgeTable t;
-    size_t o_rep, o_wf, o_qb, o_frep, o_fkeep, o_table, o_eslot, o_m1q, o_m2q, o_m1f, o_m2f, o_link, o_changed, o_vmin,
-        o_ref, o_vsplit, o_vkeep, o_isnew, o_wmin, o_wmax, o_vback, o_mixed, o_cback, o_vtile, o_ftile, o_ctile, o_vidx, o_fidx, o_cidx, o_counts, o_out_v, o_out_f,
-        o_origin, o_target, size;
-    int log2_v, log2_f;
-    int32_t *rep, *wf, *frep, *table, *m1f, *m2f, *vidx, *fidx, *cidx, *out_f, *origin, *target;
-    unsigned long long *qb, *m1q, *m2q, *counts;
-    unsigned int *eslot, *link, *changed, *vmin, *wmin, *wmax;
-    uint8_t *fkeep, *ref, *vsplit, *vkeep, *isnew, *vback, *mixed, *cback;
-    long long *vtile, *ftile, *ctile;
-    double* out_v;
-
-    void plan(int64_t nv, int64_t nf)
-    {
-        Carve lay;
-        t.plan(lay, nf);
-        const size_t cap = (size_t)1 << t.log2_e, V = (size_t)nv, Fn = (size_t)nf, Cn = 3 * Fn;
-        log2_v = log2_at_least(2ull * V); log2_f = log2_at_least(2ull * Fn);
-        o_rep = lay.take(V * 4); o_wf = lay.take(Cn * 4); o_qb = lay.take(Fn * 8); o_frep = lay.take(Fn * 4);
-        o_fkeep = lay.take(Fn); o_table = lay.take(((size_t)1 << std::max(log2_v, log2_f)) * 4);
-        o_eslot = lay.take(Cn * 4); o_m1q = lay.take(cap * 8); o_m2q = lay.take(cap * 8); o_m1f = lay.take(cap * 4);
-        o_m2f = lay.take(cap * 4); o_link = lay.take(Cn * 4); o_changed = lay.take(4);
-        o_vmin = lay.take(V * 4); o_ref = lay.take(V); o_vsplit = lay.take(V); o_vkeep = lay.take(V); o_isnew = lay.take(Cn);
-        o_wmin = lay.take(V * 4); o_wmax = lay.take(V * 4); o_vback = lay.take(V); o_mixed = lay.take(Cn); o_cback = lay.take(Cn);
-        o_vtile = lay.take((trim_scan_tiles(nv) + 1) * 8); o_ftile = lay.take((trim_scan_tiles(nf) + 1) * 8);
-        o_ctile = lay.take((trim_scan_tiles(3 * nf) + 1) * 8);
-        o_vidx = lay.take(V * 4); o_fidx = lay.take(Fn * 4); o_cidx = lay.take(Cn * 4);
-        o_counts = lay.take(rep_num_words * 8);
-        o_out_v = lay.take((V + Cn) * 24); o_out_f = lay.take(Cn * 4); o_origin = lay.take((V + Cn) * 4);
-        o_target = lay.take(V * 4);
-        size = lay.size();
-    }
-    void bind(unsigned char* b)
-    {
-        t.bind(b);
-        rep = (int32_t*)(b + o_rep); wf = (int32_t*)(b + o_wf); qb = (unsigned long long*)(b + o_qb);
-        frep = (int32_t*)(b + o_frep); fkeep = b + o_fkeep; table = (int32_t*)(b + o_table);
-        eslot = (unsigned int*)(b + o_eslot); m1q = (unsigned long long*)(b + o_m1q); m2q = (unsigned long long*)(b + o_m2q);
-        m1f = (int32_t*)(b + o_m1f); m2f = (int32_t*)(b + o_m2f); link = (unsigned int*)(b + o_link);
-        changed = (unsigned int*)(b + o_changed); vmin = (unsigned int*)(b + o_vmin);
-        ref = b + o_ref; vsplit = b + o_vsplit; vkeep = b + o_vkeep; isnew = b + o_isnew;
-        wmin = (unsigned int*)(b + o_wmin); wmax = (unsigned int*)(b + o_wmax); vback = b + o_vback; mixed = b + o_mixed;
-        cback = b + o_cback;
-        vtile = (long long*)(b + o_vtile); ftile = (long long*)(b + o_ftile); ctile = (long long*)(b + o_ctile);
-        vidx = (int32_t*)(b + o_vidx); fidx = (int32_t*)(b + o_fidx); cidx = (int32_t*)(b + o_cidx);
-        counts = (unsigned long long*)(b + o_counts);
-        out_v = (double*)(b + o_out_v); out_f = (int32_t*)(b + o_out_f); origin = (int32_t*)(b + o_origin);
-        target = (int32_t*)(b + o_target);
-    }
-};
-
-}  // namespace
-}  // namespace mm
+#include "mm_mesh_layout.h"
 
 using namespace mm;
 
@@ -86,14 +28,12 @@ int mm_mesh_repair(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
     Engine* e;
     int rc = engine_of(h, e);
     if (rc) return rc;
-    if (!report || nv < 0 || nf < 0 || vert_cap < 0 || nv > kMaxIndex || nf > kMaxIndex || (flags & ~MM_REPAIR_ALL_FLAGS) ||
-        (nv > 0 && (!vertices_xyz || !out_target)) || (vert_cap > 0 && (!out_vertices || !out_origin)) ||
-        (nf > 0 && (!faces || !out_faces)))
+    if (!report || vert_cap < 0 || (flags & ~MM_REPAIR_ALL_FLAGS) || (nv > 0 && !out_target) ||
+        (vert_cap > 0 && (!out_vertices || !out_origin)) || (nf > 0 && !out_faces))
         return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
+    if ((rc = mesh_args(who, vertices_xyz, nv, faces, nf, true))) return rc;
     for (int64_t k = 0; k < 3 * nv; ++k)
         if (!std::isfinite(vertices_xyz[k])) return set_error(MM_ERR_INVALID, std::string(who) + ": non-finite coordinate");
-    if ((rc = faces_in_range(faces, nf, nv, who))) return rc;
-    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
     mm_repair_report rep;
     std::memset(&rep, 0, sizeof(rep));
     if (nv == 0) {                                                     // no vertex, so no face either
@@ -101,24 +41,17 @@ int mm_mesh_repair(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
         return MM_OK;
     }
 
-    const size_t vbytes = (size_t)nv * 24, fbytes = (size_t)nf * 12, up_bytes = vbytes + fbytes;
-    Scratch s;
-    s.plan(nv, nf);
     // the host side of the download, worst case: every corner a new vertex
-    const size_t most_v = (size_t)nv + 3 * (size_t)nf;
+    const size_t fbytes = (size_t)nf * 12, most_v = (size_t)nv + 3 * (size_t)nf;
     const size_t h_f = up256(most_v * 24), h_origin = h_f + up256(fbytes), h_target = h_origin + up256(most_v * 4);
     const size_t h_num = h_target + up256((size_t)nv * 4), h_end = h_num + rep_num_words * 8 + 3 * 8;
-    if ((rc = e->ensure(e->host_pts, std::max(up_bytes, h_end) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, up_bytes, false))) return rc;
-    if ((rc = e->ensure(e->dev_raw, s.size, false))) return rc;
+    MeshUp up;
+    if ((rc = mesh_upload(e, vertices_xyz, nv, faces, nf, nullptr, h_end, up))) return rc;
+    RepairScratch s;
+    if ((rc = carve_on(e, e->dev_raw, [&](Carve& c) { s.lay(c, nv, nf); }))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    s.bind((unsigned char*)e->dev_raw.p);
-    std::memcpy(hb, vertices_xyz, vbytes);
-    narrow_faces((int32_t*)(hb + vbytes), faces, 3 * nf);
-    MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
-    const double* v = (const double*)b;
-    const int32_t* face = (const int32_t*)(b + vbytes);
+    const double* v = up.v;
+    const int32_t* face = up.face;
 
     int64_t launches = 0;
     MM_TRY_HIP(hipMemsetAsync(s.counts, 0, rep_num_words * 8, e->stream));
@@ -179,7 +112,7 @@ int mm_mesh_repair(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
     rep.n_nonmanifold_vertices = (int64_t)hn[rep_num_split];
     rep.n_new_vertices = kn;
     rep.n_unreferenced_dropped = (int64_t)hn[rep_num_unreferenced];
-    rep.bytes_uploaded = (int64_t)up_bytes;
+    rep.bytes_uploaded = (int64_t)up.up_bytes;
     rep.bytes_downloaded = (int64_t)((size_t)rep.n_vertices * 28 + (size_t)kf * 12 + (size_t)nv * 4 + rep_num_words * 8 + 24);
     rep.n_launches = launches + 2 + rep.union_rounds;
     if (rep.n_vertices > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": the result passes 2^31 vertices");

@@ -393,23 +393,16 @@ int rim_open(Rim& R, Engine* e, const double* v, int64_t nv, const int64_t* face
     R.e = e;
     R.nv = nv; R.nf = nf;
     R.v_cap = std::max(v_cap, nv); R.f_cap = std::max(f_cap, nf); R.r_cap = std::max<int64_t>(r_cap, 1);
-    Carve lay;
     const size_t vc = (size_t)R.v_cap, fc = (size_t)R.f_cap, rc = (size_t)R.r_cap;
-    const size_t o_v = lay.take(vc * 24), o_f = lay.take(fc * 12), o_f2 = lay.take(fc * 12), o_layer = lay.take(vc * 4);
-    const size_t o_fidx = lay.take(fc * 4), o_list = lay.take(fc * 16), o_keep = lay.take(fc);
-    const size_t o_tile = lay.take((trim_scan_tiles((long long)fc) + 1) * 8);
-    const size_t o_q = lay.take(rc * 24), o_index = lay.take(rc * 4), o_counts = lay.take(rc * 4), o_pts = lay.take(rc * 24);
-    const size_t o_counter = lay.take(8);
-    int rc_;
-    if ((rc_ = e->ensure(e->dev_pts, lay.size(), false))) return rc_;
+    int rc_ = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(R.v, 3 * vc); c.place(R.face, 3 * fc); c.place(R.face2, 3 * fc); c.place(R.layer, vc);
+        c.place(R.fidx, fc); c.place(R.list, 4 * fc); c.place(R.keep, fc);
+        c.place(R.tile, trim_scan_tiles((long long)fc) + 1);
+        c.place(R.d_q, 3 * rc); c.place(R.d_index, rc); c.place(R.d_counts, rc); c.place(R.d_pts, 3 * rc);
+        c.place(R.d_counter, 2);                                       // the eight bytes the stages clear; one word is read
+    });
+    if (rc_) return rc_;
     if ((rc_ = e->ensure(e->host_pts, std::max((size_t)R.v_cap * 24, (size_t)R.f_cap * 12) + 256, true))) return rc_;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    R.v = (double*)(b + o_v);
-    R.face = (int32_t*)(b + o_f); R.face2 = (int32_t*)(b + o_f2);
-    R.layer = (int32_t*)(b + o_layer); R.fidx = (int32_t*)(b + o_fidx); R.list = (int32_t*)(b + o_list);
-    R.keep = b + o_keep; R.tile = (long long*)(b + o_tile);
-    R.d_q = (unsigned long long*)(b + o_q); R.d_index = (int32_t*)(b + o_index); R.d_counts = (int32_t*)(b + o_counts);
-    R.d_pts = (double*)(b + o_pts); R.d_counter = (unsigned int*)(b + o_counter);
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     if (nv > 0) {
         std::memcpy(hb, v, (size_t)nv * 24);

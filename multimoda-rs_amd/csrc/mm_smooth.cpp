@@ -14,22 +14,6 @@
 #include "../../include/mm_ccta.h"
 #include "mm_stage.h"
 
-namespace mm {
-namespace {
-
-// the checks every entry point shares; the faces are read once here
-int mesh_args(const int64_t* faces, int64_t nf, int64_t nv, const char* who)
-{
-    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (nf > 0 && !faces))
-        return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
-    if (const int rc = faces_in_range(faces, nf, nv, who)) return rc;
-    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
-    return MM_OK;
-}
-
-}  // namespace
-}  // namespace mm
-
 using namespace mm;
 
 extern "C" {
@@ -41,28 +25,27 @@ int mm_mesh_adjacency_csr(mm_engine* h, const int64_t* faces, int64_t nf, int64_
     int rc = engine_of(h, e);
     if (rc) return rc;
     if (nb_cap < 0 || !off || !info || (nb_cap > 0 && !nb)) return set_error(MM_ERR_INVALID, "mm_mesh_adjacency_csr: bad arguments");
-    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_adjacency_csr"))) return rc;
+    if ((rc = mesh_args("mm_mesh_adjacency_csr", nullptr, nv, faces, nf, false))) return rc;
     std::memset(info, 0, 4 * sizeof(int64_t));
     if (nv == 0 || nf == 0) {
         for (int64_t i = 0; i <= nv; ++i) off[i] = 0;
         info[2] = nv;
         return MM_OK;
     }
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12);
     CsrDev d;
-    d.plan(lay, nf, nv);
-    const size_t o_counts = lay.take(4 * 8);
+    int32_t* d_face;
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 12 + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d_face, 3 * (size_t)nf);
+        d.lay(c, nf, nv);
+        c.place(d.counts, 4);
+    });
+    if (rc) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    d.bind(b, (unsigned long long*)(b + o_counts));
     int32_t* hf = (int32_t*)hb;
     narrow_faces(hf, faces, 3 * nf);
-    const int32_t* d_face = (const int32_t*)(b + o_face);
     int launches = 0;
-    MM_TRY_HIP(hipMemcpyAsync(b + o_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(d_face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
     if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
     MM_TRY_HIP(hipMemcpyAsync(hb, d.counts, 4 * 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
@@ -92,9 +75,9 @@ int mm_mesh_smooth(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
     Engine* e;
     int rc = engine_of(h, e);
     if (rc) return rc;
-    if (!report || n_steps < 0 || (n_steps > 0 && !factors) || (nv > 0 && (!vertices_xyz || !out_vertices)))
+    if (!report || n_steps < 0 || (n_steps > 0 && !factors) || (nv > 0 && !out_vertices))
         return set_error(MM_ERR_INVALID, "mm_mesh_smooth: bad arguments");
-    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_smooth"))) return rc;
+    if ((rc = mesh_args("mm_mesh_smooth", vertices_xyz, nv, faces, nf, true))) return rc;
     std::memset(report, 0, sizeof(*report));
     report->n_vertices = nv;
     report->n_faces = nf;
@@ -108,31 +91,31 @@ int mm_mesh_smooth(mm_engine* h, const double* vertices_xyz, int64_t nv, const i
     }
 
     // device: [faces | mask | v0] (the upload), vA, the report's numbers, vB, the adjacency, the volume's scratch
-    const size_t vbytes = (size_t)nv * 24;
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12), o_mask = lay.take(pinned ? (size_t)nv : 0), o_v0 = lay.take(vbytes);
-    const size_t up_bytes = o_v0 + vbytes;
-    const size_t o_va = lay.take(vbytes), o_num = lay.take(256), o_vb = lay.take(vbytes);
+    const size_t vbytes = (size_t)nv * 24, V = (size_t)nv;
     CsrDev d;
-    d.plan(lay, nf, nv);
-    const size_t o_sa = lay.take((size_t)nf * 8), o_sb = lay.take(weld_sum_scratch(nf) * 8);
-    const size_t down_bytes = o_vb + vbytes - o_va;
+    const int32_t* d_face;
+    const uint8_t* d_mask;
+    const double* v0;
+    double *va, *vb, *d_num, *sa, *sb;
+    size_t o_face = 0, o_mask = 0, o_v0 = 0, o_va = 0, o_num = 0, o_vb = 0;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        o_face = c.place(d_face, 3 * (size_t)nf); o_mask = c.place(d_mask, pinned ? V : 0); o_v0 = c.place(v0, 3 * V);
+        o_va = c.place(va, 3 * V); o_num = c.place(d_num, 32); o_vb = c.place(vb, 3 * V);
+        d.lay(c, nf, nv);
+        c.place(sa, (size_t)nf); c.place(sb, weld_sum_scratch(nf));
+    });
+    if (rc) return rc;
+    const size_t up_bytes = o_v0 + vbytes, down_bytes = o_vb + vbytes - o_va;
     if ((rc = e->ensure(e->host_pts, std::max(up_bytes, down_bytes) + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
     unsigned char* b = (unsigned char*)e->dev_pts.p;
-    enum { kVolBefore = 0, kVolAfter = 1, kDisp = 2, kCounts = 3 };    // 8-byte words of the numbers block
-    double* d_num = (double*)(b + o_num);
-    d.bind(b, (unsigned long long*)(d_num + kCounts));
+    enum { kVolBefore = 0, kVolAfter = 1, kDisp = 2, kCounts = 3 };    // 8-byte words of the numbers block (32 of them)
+    d.counts = (unsigned long long*)(d_num + kCounts);
+    if (!pinned) d_mask = nullptr;
     int32_t* hf = (int32_t*)(hb + o_face);
     narrow_faces(hf, faces, 3 * nf);
-    if (pinned) std::memcpy(hb + o_mask, pinned, (size_t)nv);
+    if (pinned) std::memcpy(hb + o_mask, pinned, V);
     std::memcpy(hb + o_v0, vertices_xyz, vbytes);
-    const int32_t* d_face = (const int32_t*)(b + o_face);
-    const uint8_t* d_mask = pinned ? (const uint8_t*)(b + o_mask) : nullptr;
-    const double* v0 = (const double*)(b + o_v0);
-    double *va = (double*)(b + o_va), *vb = (double*)(b + o_vb);
-    double *sa = (double*)(b + o_sa), *sb = (double*)(b + o_sb);
     int launches = 0;
     MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
     if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
@@ -174,7 +157,7 @@ int mm_mesh_vertex_rings(mm_engine* h, const int64_t* faces, int64_t nf, int64_t
     if (rc) return rc;
     if (!info || n_seeds < 0 || n_seeds > kMaxIndex || max_ring < 0 || (n_seeds > 0 && !seeds) || (nv > 0 && !ring_out))
         return set_error(MM_ERR_INVALID, "mm_mesh_vertex_rings: bad arguments");
-    if ((rc = mesh_args(faces, nf, nv, "mm_mesh_vertex_rings"))) return rc;
+    if ((rc = mesh_args("mm_mesh_vertex_rings", nullptr, nv, faces, nf, false))) return rc;
     for (int64_t k = 0; k < n_seeds; ++k)
         if (seeds[k] < 0 || seeds[k] >= nv) return set_error(MM_ERR_INVALID, "mm_mesh_vertex_rings: seed out of range");
     std::memset(info, 0, 3 * sizeof(int64_t));
@@ -187,30 +170,29 @@ int mm_mesh_vertex_rings(mm_engine* h, const int64_t* faces, int64_t nf, int64_t
         }
         return MM_OK;
     }
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12), o_seed = lay.take((size_t)n_seeds * 4);
-    const size_t up_bytes = o_seed + (size_t)n_seeds * 4;
     CsrDev d;
-    d.plan(lay, nf, nv);
-    const size_t o_ring = lay.take((size_t)nv * 4), o_counts = lay.take(4 * 8), o_reached = lay.take(8);
+    const int32_t *d_face, *d_seed;
+    int32_t* d_ring;
+    unsigned long long* d_reached;
+    size_t o_seed = 0;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d_face, 3 * (size_t)nf); o_seed = c.place(d_seed, (size_t)n_seeds);
+        d.lay(c, nf, nv);
+        c.place(d_ring, (size_t)nv); c.place(d.counts, 4); c.place(d_reached, 1);
+    });
+    if (rc) return rc;
+    const size_t up_bytes = o_seed + (size_t)n_seeds * 4;
     const size_t h_flag = up256(std::max(up_bytes, (size_t)nv * 4));   // the round's count, behind upload and download
     if ((rc = e->ensure(e->host_pts, h_flag + 512, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    d.bind(b, (unsigned long long*)(b + o_counts));
-    int32_t* hf = (int32_t*)(hb + o_face);
-    narrow_faces(hf, faces, 3 * nf);
+    narrow_faces((int32_t*)hb, faces, 3 * nf);
     int32_t* hs = (int32_t*)(hb + o_seed);
     for (int64_t k = 0; k < n_seeds; ++k) hs[k] = (int32_t)seeds[k];
-    const int32_t* d_face = (const int32_t*)(b + o_face);
-    int32_t* d_ring = (int32_t*)(b + o_ring);
-    unsigned long long* d_reached = (unsigned long long*)(b + o_reached);
     const unsigned long long* h_reached = (const unsigned long long*)(hb + h_flag);
     int launches = 0;
-    MM_TRY_HIP(hipMemcpyAsync(b, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(e->dev_pts.p, hb, up_bytes, hipMemcpyHostToDevice, e->stream));
     if ((rc = csr_build(e, d, d_face, nf, nv, &launches))) return rc;
-    MM_TRY_HIP(launch_mesh_ring_seed((const int32_t*)(b + o_seed), n_seeds, d_ring, nv, d_reached, &launches, e->stream));
+    MM_TRY_HIP(launch_mesh_ring_seed(d_seed, n_seeds, d_ring, nv, d_reached, &launches, e->stream));
     MM_TRY_HIP(hipMemcpyAsync(hb + h_flag, d_reached, 8, hipMemcpyDeviceToHost, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));
     int64_t reached = (int64_t)h_reached[0], rounds = 0;

@@ -1,7 +1,9 @@
 // mm_stage.h -- what the CCTA host files (mm_ccta, mm_shape, mm_branch, mm_discretize, mm_bspline, mm_trim, mm_stitch,
-// mm_close, mm_rim, mm_smooth, mm_refine, mm_surface, mm_repair .cpp) share when they stage points or a mesh on the engine's
-// grow-only buffers: the engine behind the handle, 256-byte carving, the staged pass of the point kernels, the face
-// checks and the int64 <-> int32 face copies, the edge table's layout, a compaction's counts, the winding stage.
+// mm_close, mm_rim, mm_smooth, mm_relax, mm_refine, mm_flip, mm_collapse, mm_surface, mm_repair, mm_geodesic, mm_intersect,
+// mm_section .cpp) share when they stage points or a mesh on the engine's grow-only buffers: the engine behind the
+// handle, 256-byte carving (typed: one statement a buffer), the staged pass of the point kernels, the mesh argument
+// check, the face checks and the int64 <-> int32 face copies, the mesh upload, a counter block's read, the edge table's
+// layout, a compaction's counts, the winding stage.  The scratch layouts of the mesh passes are in mm_mesh_layout.h.
 // Header-only; internal.
 #pragma once
 
@@ -44,12 +46,32 @@ inline int log2_at_least(unsigned long long n)
     return l;
 }
 
-// Offsets of consecutive buffers, each starting on a multiple of 256 bytes.
+// Consecutive buffers, each starting on a multiple of 256 bytes.  take() reserves bytes and returns their offset.  place()
+// reserves count elements of the pointer's type and points p at them, so a buffer's size and its type are one statement:
+// a layout is one function over a Carve that runs twice, measuring (base == nullptr: p = nullptr) and then placing.
 struct Carve {
+    unsigned char* base = nullptr;
     size_t o = 0;
     size_t take(size_t bytes) { const size_t at = o; o = up256(o + bytes); return at; }
+    template <class T> size_t place(T*& p, size_t count)
+    {
+        const size_t at = take(count * sizeof(T));
+        p = base ? (T*)(base + at) : nullptr;
+        return at;
+    }
     size_t size() const { return o; }
 };
+
+// lay(Carve&) measured, buf grown to that size, lay placed over it
+template <class Lay> int carve_on(Engine* e, Engine::Buf& buf, Lay lay)
+{
+    Carve measure;
+    lay(measure);
+    if (const int rc = e->ensure(buf, measure.size(), false)) return rc;
+    Carve c{(unsigned char*)buf.p};
+    lay(c);
+    return MM_OK;
+}
 
 // One pass of a point kernel over e->host_pts (pinned) and e->dev_pts: inputs, outputs and device-only scratch, carved
 // apart.  On the device they follow each other in that order; on the host the downloaded outputs take the inputs'
@@ -152,6 +174,17 @@ inline int faces_in_range(const int64_t* faces, int64_t nf, int64_t nv, const ch
     return MM_OK;
 }
 
+// The checks every mesh entry point shares: nv and nf in range, the arrays present (the vertices where the call reads
+// them), every index in range, and 6 nf, the edge table's insertions doubled, below 2^31.
+inline int mesh_args(const char* who, const double* vertices, int64_t nv, const int64_t* faces, int64_t nf, bool need_vertices)
+{
+    if (nv < 0 || nf < 0 || nv > kMaxIndex || nf > kMaxIndex || (need_vertices && nv > 0 && !vertices) || (nf > 0 && !faces))
+        return set_error(MM_ERR_INVALID, std::string(who) + ": bad arguments");
+    if (const int rc = faces_in_range(faces, nf, nv, who)) return rc;
+    if (6 * nf > kMaxIndex) return set_error(MM_ERR_TOO_LARGE, std::string(who) + ": 6 nf passes 2^31");
+    return MM_OK;
+}
+
 // checked indices to the device's int32 (base: the part's first vertex) and back
 inline void narrow_faces(int32_t* dst, const int64_t* src, int64_t n_indices, int64_t base = 0)
 {
@@ -163,49 +196,73 @@ inline void widen_faces(int64_t* dst, const int32_t* src, int64_t n_indices)
     for (int64_t k = 0; k < n_indices; ++k) dst[k] = src[k];
 }
 
+// [vertices | int32 faces | mask (nullable)] through e->host_pts into e->dev_pts in one copy, queued on the stream.
+// host_bytes: what the caller's downloads need of e->host_pts.
+struct MeshUp {
+    const double* v = nullptr;
+    int32_t* face = nullptr;
+    const uint8_t* pin = nullptr;          // nullptr without a mask
+    size_t up_bytes = 0;
+};
+inline int mesh_upload(Engine* e, const double* vertices, int64_t nv, const int64_t* faces, int64_t nf, const uint8_t* mask,
+                       size_t host_bytes, MeshUp& m)
+{
+    const size_t vbytes = (size_t)nv * 24, fbytes = (size_t)nf * 12;
+    m.up_bytes = vbytes + fbytes + (mask ? (size_t)nv : 0);
+    if (const int rc = e->ensure(e->host_pts, std::max(m.up_bytes, host_bytes) + 512, true)) return rc;
+    if (const int rc = e->ensure(e->dev_pts, m.up_bytes, false)) return rc;
+    unsigned char* hb = (unsigned char*)e->host_pts.p;
+    unsigned char* b = (unsigned char*)e->dev_pts.p;
+    std::memcpy(hb, vertices, vbytes);
+    narrow_faces((int32_t*)(hb + vbytes), faces, 3 * nf);
+    if (mask) std::memcpy(hb + vbytes + fbytes, mask, (size_t)nv);
+    MM_TRY_HIP(hipMemcpyAsync(b, hb, m.up_bytes, hipMemcpyHostToDevice, e->stream));
+    m.v = (const double*)b;
+    m.face = (int32_t*)(b + vbytes);
+    m.pin = mask ? b + vbytes + fbytes : nullptr;
+    return MM_OK;
+}
+
+// a pass's counter block through the first words of e->host_pts (behind the upload in stream order); synchronises
+inline int read_words(Engine* e, const unsigned long long* dev_counts, size_t n_words, const unsigned long long** words)
+{
+    MM_TRY_HIP(hipMemcpyAsync(e->host_pts.p, dev_counts, n_words * 8, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    *words = (const unsigned long long*)e->host_pts.p;
+    return MM_OK;
+}
+
 // The edge table of launch_weld_edges: 2^log2_e slots, at least 6 nf (twice the 3 nf insertions of a pass), in three
-// planes -- keys (8 bytes a slot), counts (4), the two owners (8).  plan() carves them back to back, bind() places them.
+// planes back to back -- keys (8 bytes a slot), counts (4), the two owners (8).
 struct EdgeTable {
-    size_t o_keys = 0, o_cnt = 0, o_own = 0;
     unsigned long long* keys = nullptr;
     unsigned int *cnt = nullptr, *own = nullptr;
     int log2_e = 8;
 
     static int log2_slots(int64_t nf) { return log2_at_least(6ull * (unsigned long long)nf); }
-    void plan(Carve& c, int64_t nf)
+    size_t slots() const { return (size_t)1 << log2_e; }
+    void lay(Carve& c, int64_t nf)
     {
         log2_e = log2_slots(nf);
-        const size_t cap = (size_t)1 << log2_e;
-        o_keys = c.take(cap * 8); o_cnt = c.take(cap * 4); o_own = c.take(cap * 8);
-    }
-    void bind(unsigned char* b)
-    {
-        keys = (unsigned long long*)(b + o_keys); cnt = (unsigned int*)(b + o_cnt); own = (unsigned int*)(b + o_own);
+        c.place(keys, slots()); c.place(cnt, slots()); c.place(own, 2 * slots());
     }
 };
 
 // The sorted vertex adjacency of mm_smooth_kernels.hip (mm_smooth.cpp and mm_relax.cpp build it): its device buffers,
 // laid out behind whatever the caller placed first.  nb takes the place of the edge table's owner words (8 bytes a slot,
-// at least 6 nf slots): the fill runs behind the insertion, which alone writes them.
+// at least 6 nf slots): the fill runs behind the insertion, which alone writes them.  The caller points counts at four
+// words of its own.
 struct CsrDev {
     EdgeTable edges;
-    size_t o_deg, o_off, o_tile;
-    int32_t *deg, *off, *nb;
-    long long* tile;
-    unsigned long long* counts;           // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
+    int32_t *deg = nullptr, *off = nullptr, *nb = nullptr;
+    long long* tile = nullptr;
+    unsigned long long* counts = nullptr;  // [0] edges, [1] isolated vertices, [2] the longest row, [3] spare
 
-    void plan(Carve& lay, int64_t nf, int64_t nv)
+    void lay(Carve& c, int64_t nf, int64_t nv)
     {
-        edges.plan(lay, nf);
-        o_deg = lay.take((size_t)nv * 4); o_off = lay.take(((size_t)nv + 1) * 4);
-        o_tile = lay.take((mesh_csr_tiles(nv) + 1) * 8);
-    }
-    void bind(unsigned char* b, unsigned long long* counts_at)
-    {
-        edges.bind(b);
-        deg = (int32_t*)(b + o_deg); off = (int32_t*)(b + o_off); nb = (int32_t*)edges.own;
-        tile = (long long*)(b + o_tile);
-        counts = counts_at;
+        edges.lay(c, nf);
+        c.place(deg, (size_t)nv); c.place(off, (size_t)nv + 1); c.place(tile, mesh_csr_tiles(nv) + 1);
+        nb = (int32_t*)edges.own;
     }
 };
 

@@ -153,19 +153,15 @@ int mm_fix_winding(mm_engine* h, const int64_t* faces, int64_t nf, int64_t* out_
     std::memset(info, 0, 3 * sizeof(int64_t));
     if (nf == 0) return MM_OK;
     WeldDev d;
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12);
-    d.edges.plan(lay, nf);
-    const size_t o_link = lay.take((size_t)nf * 4), o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
     if ((rc = e->ensure(e->host_pts, (size_t)nf * 12 + 256, true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d.face, 3 * (size_t)nf);
+        d.edges.lay(c, nf);
+        c.place(d.link, (size_t)nf); c.place(d.counts, kCounts); c.place(d.changed, 1);
+    });
+    if (rc) return rc;
     int32_t* hf = (int32_t*)e->host_pts.p;
     narrow_faces(hf, faces, 3 * nf);
-    d.face = (int32_t*)(b + o_face);
-    d.edges.bind(b);
-    d.link = (unsigned int*)(b + o_link); d.counts = (unsigned long long*)(b + o_counts);
-    d.changed = (unsigned int*)(b + o_changed);
     MM_TRY_HIP(hipMemcpyAsync(d.face, hf, (size_t)nf * 12, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemsetAsync(d.counts, 0, kCounts * 8, e->stream));
     MM_TRY_HIP(hipStreamSynchronize(e->stream));                        // the pinned buffer takes the round flags next
@@ -214,39 +210,30 @@ int mm_mesh_assemble(mm_engine* h, int n_parts, const double* vertices_xyz, cons
     WeldDev d;
     d.log2_v = log2_at_least(2ull * (unsigned long long)nv);
     d.log2_f = log2_at_least(2ull * (unsigned long long)nf);
-    const size_t cap_t = (size_t)1 << std::max(d.log2_v, d.log2_f);
-    const size_t nvt = trim_scan_tiles(nv) + 1, nft = trim_scan_tiles(nf) + 1;
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12), o_vert = lay.take((size_t)nv * 24);
-    const size_t in_bytes = lay.size();
-    const size_t o_ref = lay.take((size_t)nv), o_keep = lay.take((size_t)nv), o_rep = lay.take((size_t)nv * 4);
-    const size_t o_vidx = lay.take((size_t)nv * 4), o_vmap = lay.take((size_t)nv * 4), o_vt = lay.take(nvt * 8);
-    const size_t o_table = lay.take(cap_t * 4), o_frep = lay.take((size_t)nf * 4), o_fkeep = lay.take((size_t)nf);
-    const size_t o_fidx = lay.take((size_t)nf * 4), o_ft = lay.take(nft * 8);
-    const size_t o_ov = lay.take((size_t)nv * 24), o_of = lay.take((size_t)nf * 12);
-    d.edges.plan(lay, nf);
-    const size_t o_link = lay.take((size_t)nf * 4);
-    const size_t o_sa = lay.take((size_t)nf * 8), o_sb = lay.take(weld_sum_scratch(nf) * 8), o_vol = lay.take(8);
-    const size_t o_counts = lay.take(kCounts * 8), o_changed = lay.take(4);
-    if ((rc = e->ensure(e->host_pts, std::max(in_bytes, (size_t)nv * 24 + (size_t)nf * 12 + 512), true))) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
+    const size_t cap_t = (size_t)1 << std::max(d.log2_v, d.log2_f), V = (size_t)nv, Fn = (size_t)nf;
+    size_t o_vert = 0, in_bytes = 0;
+    rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d.face, 3 * Fn); o_vert = c.place(d.vert, 3 * V);
+        in_bytes = c.size();
+        c.place(d.ref, V); c.place(d.keep, V); c.place(d.rep, V);
+        c.place(d.vidx, V); c.place(d.vmap, V); c.place(d.vtile, trim_scan_tiles(nv) + 1);
+        c.place(d.table, cap_t); c.place(d.frep, Fn); c.place(d.fkeep, Fn);
+        c.place(d.fidx, Fn); c.place(d.ftile, trim_scan_tiles(nf) + 1);
+        c.place(d.out_v, 3 * V); c.place(d.out_f, 3 * Fn);
+        d.edges.lay(c, nf);
+        c.place(d.link, Fn);
+        c.place(d.sum_a, Fn); c.place(d.sum_b, weld_sum_scratch(nf)); c.place(d.volume, 1);
+        c.place(d.counts, kCounts); c.place(d.changed, 1);
+    });
+    if (rc) return rc;
+    if ((rc = e->ensure(e->host_pts, std::max(in_bytes, V * 24 + Fn * 12 + 512), true))) return rc;
     unsigned char* hb = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
     int32_t* hf = (int32_t*)hb;
     for (int p = 0; p < n_parts; ++p)
         narrow_faces(hf + 3 * face_off[p], faces + 3 * face_off[p], 3 * (face_off[p + 1] - face_off[p]), vert_off[p]);
-    if (nv > 0) std::memcpy(hb + o_vert, vertices_xyz, (size_t)nv * 24);
-    d.face = (int32_t*)(b + o_face); d.vert = (double*)(b + o_vert);
-    d.ref = b + o_ref; d.keep = b + o_keep; d.rep = (int32_t*)(b + o_rep); d.vidx = (int32_t*)(b + o_vidx);
-    d.vmap = (int32_t*)(b + o_vmap); d.vtile = (long long*)(b + o_vt); d.table = (int32_t*)(b + o_table);
-    d.frep = (int32_t*)(b + o_frep); d.fkeep = b + o_fkeep; d.fidx = (int32_t*)(b + o_fidx);
-    d.ftile = (long long*)(b + o_ft); d.out_v = (double*)(b + o_ov); d.out_f = (int32_t*)(b + o_of);
-    d.edges.bind(b);
-    d.link = (unsigned int*)(b + o_link); d.sum_a = (double*)(b + o_sa); d.sum_b = (double*)(b + o_sb);
-    d.volume = (double*)(b + o_vol); d.counts = (unsigned long long*)(b + o_counts);
-    d.changed = (unsigned int*)(b + o_changed);
+    if (nv > 0) std::memcpy(hb + o_vert, vertices_xyz, V * 24);
 
-    MM_TRY_HIP(hipMemcpyAsync(b, hb, in_bytes, hipMemcpyHostToDevice, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(d.face, hb, in_bytes, hipMemcpyHostToDevice, e->stream));
     MM_TRY_HIP(hipMemsetAsync(d.counts, 0, kCounts * 8, e->stream));
     MM_TRY_HIP(hipMemsetAsync(d.volume, 0, 8, e->stream));
     MM_TRY_HIP(launch_weld_vertices(d.vert, nv, d.face, nf, scale, d.ref, d.table, d.log2_v, d.rep, d.keep,

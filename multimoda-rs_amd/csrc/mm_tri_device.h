@@ -2,7 +2,8 @@
 // states them: what k_tri_min / k_tri_closest (mm_tri_kernels.hip) fold over and what the mesh relaxation
 // (mm_relax_kernels.hip) seeds its minima with -- one inlined face_d2, so a seed is a member of the set the fold
 // runs over, bit for bit.  Every operation unfused and in the header's order (the files are built with
-// -ffp-contract=off), every quotient a true division.  Device code only.
+// -ffp-contract=off), every quotient a true division.  The vector helpers (V3, sub3, dot3, cross3, load3, len_sq3,
+// tri_quality) also serve the flips and the collapse (mm_flip_kernels.hip, mm_collapse_kernels.hip).  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,21 @@ __device__ __forceinline__ double dot3(const V3& u, const V3& v) { return (u.x *
 // u + e * t, one rounding for each product and each sum
 __device__ __forceinline__ V3 along(const V3& u, const V3& e, double t) { return V3{u.x + e.x * t, u.y + e.y * t, u.z + e.z * t}; }
 __device__ __forceinline__ double dist2(const V3& p, const V3& q) { const V3 d = sub3(p, q); return dot3(d, d); }
+// (u x w) with the component expressions of the degenerate test
+__device__ __forceinline__ V3 cross3(const V3& u, const V3& w)
+{
+    return V3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x};
+}
+// point i of an array of xyz triples
+__device__ __forceinline__ V3 load3(const double* p, long long i) { return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+// ((dx dx + dy dy) + dz dz) of d = q - p: the squared length of "mesh refinement"
+__device__ __forceinline__ double len_sq3(const V3& p, const V3& q) { return dist2(q, p); }
+// dot(n, n) / (S S) of the triangle (i, j, k) with normal n, S the sum of its squared edge lengths; 0 where S is 0
+__device__ __forceinline__ double tri_quality(const V3& i, const V3& j, const V3& k, const V3& n)
+{
+    const double s = (len_sq3(i, j) + len_sq3(j, k)) + len_sq3(k, i);
+    return s == 0.0 ? 0.0 : dot3(n, n) / (s * s);
+}
 
 // closest point of a proper face; ab = b - a, ac = c - a
 __device__ __forceinline__ V3 tri_closest(const V3& p, const V3& a, const V3& b, const V3& c, const V3& ab, const V3& ac,

@@ -226,35 +226,25 @@ struct TrimDev {
 int trim_alloc(Engine* e, const double* v, int64_t nv, const int64_t* faces, int64_t nf, bool with_vertices, TrimDev& d)
 {
     d.log2_cap = EdgeTable::log2_slots(nf);
-    const size_t cap = (size_t)1 << d.log2_cap;
-    const size_t nvt = trim_scan_tiles(nv) + 1, nft = trim_scan_tiles(nf) + 1;
-    Carve lay;
-    const size_t o_face = lay.take((size_t)nf * 12), o_vert = lay.take(with_vertices ? (size_t)nv * 24 : 0);
-    const size_t in_bytes = lay.size();
-    const size_t o_in = lay.take((size_t)nv), o_fk = lay.take((size_t)nf), o_mark = lay.take((size_t)nv);
-    const size_t o_keys = lay.take(cap * 8), o_cnt = lay.take(cap * 4);
-    const size_t o_open = lay.take((size_t)nf * 24), o_nopen = lay.take(8);
-    const size_t o_vidx = lay.take((size_t)nv * 4), o_fidx = lay.take((size_t)nf * 4), o_drop = lay.take((size_t)nv * 4);
-    const size_t o_vt = lay.take(nvt * 8), o_ft = lay.take(nft * 8);
-    const size_t o_ov = lay.take(with_vertices ? (size_t)nv * 24 : 0), o_of = lay.take((size_t)nf * 12);
-    const size_t host_bytes = std::max({in_bytes, (size_t)nf * 24, (size_t)nv * 24 + (size_t)nf * 12, (size_t)nv + 256});
-    int rc = e->ensure(e->host_pts, host_bytes, true);
+    const size_t cap = (size_t)1 << d.log2_cap, V = (size_t)nv, Fn = (size_t)nf, vert_n = with_vertices ? 3 * V : 0;
+    size_t o_vert = 0, in_bytes = 0;
+    int rc = carve_on(e, e->dev_pts, [&](Carve& c) {
+        c.place(d.face, 3 * Fn); o_vert = c.place(d.vert, vert_n);
+        in_bytes = c.size();
+        c.place(d.in, V); c.place(d.fk, Fn); c.place(d.mark, V);
+        c.place(d.keys, cap); c.place(d.cnt, cap);
+        c.place(d.open, 3 * Fn); c.place(d.n_open, 1);
+        c.place(d.vidx, V); c.place(d.fidx, Fn); c.place(d.drop, V);
+        c.place(d.vtile, trim_scan_tiles(nv) + 1); c.place(d.ftile, trim_scan_tiles(nf) + 1);
+        c.place(d.out_v, vert_n); c.place(d.out_f, 3 * Fn);
+    });
     if (rc) return rc;
-    if ((rc = e->ensure(e->dev_pts, lay.size(), false))) return rc;
+    const size_t host_bytes = std::max({in_bytes, Fn * 24, V * 24 + Fn * 12, V + 256});
+    if ((rc = e->ensure(e->host_pts, host_bytes, true))) return rc;
     unsigned char* h = (unsigned char*)e->host_pts.p;
-    unsigned char* b = (unsigned char*)e->dev_pts.p;
-    int32_t* hf = (int32_t*)h;
-    narrow_faces(hf, faces, 3 * nf);
-    if (with_vertices && nv > 0) std::memcpy(h + o_vert, v, (size_t)nv * 24);
-    d.face = (int32_t*)(b + o_face);
-    d.vert = (double*)(b + o_vert);
-    d.in = b + o_in; d.fk = b + o_fk; d.mark = b + o_mark;
-    d.keys = (unsigned long long*)(b + o_keys); d.cnt = (unsigned int*)(b + o_cnt);
-    d.open = (unsigned long long*)(b + o_open); d.n_open = (unsigned long long*)(b + o_nopen);
-    d.vidx = (int32_t*)(b + o_vidx); d.fidx = (int32_t*)(b + o_fidx); d.drop = (int32_t*)(b + o_drop);
-    d.vtile = (long long*)(b + o_vt); d.ftile = (long long*)(b + o_ft);
-    d.out_v = (double*)(b + o_ov); d.out_f = (int32_t*)(b + o_of);
-    if (in_bytes) MM_TRY_HIP(hipMemcpyAsync(b, h, in_bytes, hipMemcpyHostToDevice, e->stream));
+    narrow_faces((int32_t*)h, faces, 3 * nf);
+    if (with_vertices && nv > 0) std::memcpy(h + o_vert, v, V * 24);
+    if (in_bytes) MM_TRY_HIP(hipMemcpyAsync(d.face, h, in_bytes, hipMemcpyHostToDevice, e->stream));
     return MM_OK;
 }
 

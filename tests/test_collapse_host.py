@@ -42,7 +42,7 @@ from test_morph_kernel_resources import HIPCC, ROOT, _compile, _flags
 
 import multimoda_rs_amd as mm
 
-KERNELS = ("k_col_edge_insert", "k_col_valence", "k_col_candidates", "k_col_apply", "k_col_finish")
+KERNELS = ("k_edge_insert_first", "k_col_valence", "k_col_candidates", "k_col_apply", "k_col_finish")
 PATCH_FACES = [(0, 1, 2), (0, 2, 3), (0, 3, 4), (0, 4, 5), (0, 5, 1), (1, 5, 6), (1, 6, 7), (1, 7, 2)]
 
 

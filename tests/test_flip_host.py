@@ -29,7 +29,7 @@ from test_morph_kernel_resources import HIPCC, ROOT, _compile, _flags
 
 import multimoda_rs_amd as mm
 
-KERNELS = ("k_flip_edge_insert", "k_flip_valence", "k_flip_deviation", "k_flip_candidates", "k_flip_apply")
+KERNELS = ("k_edge_insert_first", "k_flip_valence", "k_flip_deviation", "k_flip_candidates", "k_flip_apply")
 
 
 def tube():

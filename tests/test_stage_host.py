@@ -1,6 +1,7 @@
 """csrc/mm_stage.h and csrc/mm_point_records.h on the CPU (tests/stage_host.cpp, a program of its own): the 256-byte
-carving and the staged pass's regions on empty and odd sizes (0, 1, 255, 256, 257), the block work lists, and the record
-layouts' static_asserts, which fail the compile.  No GPU, no engine."""
+carving (take and the typed place) and the staged pass's regions on empty and odd sizes (0, 1, 255, 256, 257), the mesh
+scratch layouts of csrc/mm_mesh_layout.h against recorded sizes and offsets, the block work lists, and the record layouts'
+static_asserts, which fail the compile.  No GPU, no engine."""
 import os
 import shutil
 import subprocess
