@@ -686,6 +686,15 @@ int     mm_mesh_refine(mm_engine* e, const double* vertices_xyz, int64_t nv, con
  * segment (u, v): e = v-u; l = dot(e,e); t = 0 where l == 0, else dot(p-u,e)/l, replaced by 0 where it is < 0 and by 1
  * where it is > 1; the point is u + e*t.  The region is 4, 5 or 6 for the winning segment.
  *
+ * Thin faces -- not degenerate, and dot(n, n) < 2^-34 * (l*l) with n = ab x ac as above and l the largest of dot(ab,ab),
+ * dot(ac,ac), dot(bc,bc), bc = c-b: the smallest altitude is below 2^-17 of the longest edge, as computed -- do not go
+ * through the tests 1 to 7, whose cross terms va, vb, vc are cancellation noise on such a face.  They take the segment
+ * rule of the degenerate faces first; then, with d1 .. d6, vc, vb, va as in 1 to 6, where va > 0 && vb > 0 && vc > 0, the
+ * interior point of 7 replaces the segments' point iff its d2 is strictly smaller (region 0).  Every candidate is a convex
+ * combination of the corners up to rounding, so the closest point is a point of the closed triangle and d2 is never too
+ * small; the nearest segment point is within the inradius (at most half the smallest altitude) of the true closest point,
+ * so the distance is too large by at most that.  A face that is neither degenerate nor thin is proper.
+ *
  * The fold over faces is exact: face f replaces the best iff its d2 < best, so equal d2 keeps the lowest face index and a
  * NaN d2 is never chosen; a query that no face beat returns +inf, face -1, closest NaN, region -1.  The result has one
  * bit pattern whatever the chunking, the order or the pruning.  The device computes every d2 (mm_tri_kernels.hip). */

@@ -66,7 +66,7 @@ int        nn_queries_per_block();
 int        nn_chunk_points();
 int        nn_span_chunks();
 // point-to-triangle distances (mm_tri_kernels.hip).  tri12: nf staged faces of 12 doubles (a, b, c as x y z w; a.w = the
-// bits of the degenerate flag, b.w = those of the original face index); qxyz: nq staged queries; work: n_a items of pass
+// bits of the face's kind, b.w = those of the original face index); qxyz: nq staged queries; work: n_a items of pass
 // A, then n_b of pass B.  sq: the minima's bits; key: original face << 32 | staged face of the winner (~0: none); closest:
 // 3 per query; region: one; counters[0] = items pass B skipped.  All outputs per query in staged order.
 hipError_t launch_tri_distance(const TriWork* work, int n_a, int n_b, const double* tri12, int nf, const double* qxyz, int nq,

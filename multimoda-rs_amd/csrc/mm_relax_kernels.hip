@@ -101,12 +101,12 @@ k_relax_candidates(const int32_t* __restrict__ off, const int32_t* __restrict__ 
         bool stays = fk == kNoFace;
         V3 cand = p;
         V3 fa{}, fb{}, fc{};
-        bool degenerate = false;
+        int kind = kFaceProper;
         if (!stays) {
             const long long j = (long long)(fk & 0xffffffffull);
             const double4 ta = tri[3 * j], tb = tri[3 * j + 1], tc = tri[3 * j + 2];
             fa = V3{ta.x, ta.y, ta.z}; fb = V3{tb.x, tb.y, tb.z}; fc = V3{tc.x, tc.y, tc.z};
-            degenerate = __double_as_longlong(ta.w) != 0;
+            kind = (int)__double_as_longlong(ta.w);
             const V3 n = cross3(sub3(fb, fa), sub3(fc, fa));
             const double nn = dot3(n, n);
             V3 t = d;
@@ -120,7 +120,7 @@ k_relax_candidates(const int32_t* __restrict__ off, const int32_t* __restrict__ 
         }
         unsigned long long seed = kInfBits;
         if (fk != kNoFace) {
-            const double d2 = face_d2(cand, fa, fb, fc, sub3(fb, fa), sub3(fc, fa), degenerate);
+            const double d2 = face_d2(cand, fa, fb, fc, sub3(fb, fa), sub3(fc, fa), kind);
             if (d2 == d2) seed = (unsigned long long)__double_as_longlong(d2);
         }
         store3(qxyz, q, cand);

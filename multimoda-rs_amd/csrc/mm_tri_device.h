@@ -71,27 +71,66 @@ __device__ __forceinline__ V3 seg_closest(const V3& p, const V3& u, const V3& v)
     return along(u, e, t);
 }
 
-// closest point of a degenerate face: the nearest of ab, bc, ca, the first on ties
-__device__ __forceinline__ V3 degenerate_closest(const V3& p, const V3& a, const V3& b, const V3& c, int& region)
+// the nearest of ab, bc, ca, the first on ties; best = its squared distance
+__device__ __forceinline__ V3 segments_closest(const V3& p, const V3& a, const V3& b, const V3& c, int& region, double& best)
 {
     V3 q = seg_closest(p, a, b);
-    double best = dist2(p, q);
+    best = dist2(p, q);
     region = 4;
     const V3 q2 = seg_closest(p, b, c);
     const double v2 = dist2(p, q2);
     if (v2 < best) { best = v2; q = q2; region = 5; }
     const V3 q3 = seg_closest(p, c, a);
     const double v3 = dist2(p, q3);
-    if (v3 < best) { q = q3; region = 6; }
+    if (v3 < best) { best = v3; q = q3; region = 6; }
     return q;
 }
 
+// closest point of a degenerate face: its segments
+__device__ __forceinline__ V3 degenerate_closest(const V3& p, const V3& a, const V3& b, const V3& c, int& region)
+{
+    double best;
+    return segments_closest(p, a, b, c, region, best);
+}
+
+// closest point of a thin face: its segments, then the interior point where all three of va, vb, vc are positive (the
+// point is then a convex combination of the corners) and it is strictly nearer
+__device__ __forceinline__ V3 thin_closest(const V3& p, const V3& a, const V3& b, const V3& c, const V3& ab, const V3& ac,
+                                           int& region)
+{
+    double best;
+    V3 q = segments_closest(p, a, b, c, region, best);
+    const V3 ap = sub3(p, a), bp = sub3(p, b), cp = sub3(p, c);
+    const double d1 = dot3(ab, ap), d2 = dot3(ac, ap);
+    const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
+    const double d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+    const double vc = d1 * d4 - d3 * d2;
+    const double vb = d5 * d2 - d1 * d6;
+    const double va = d3 * d6 - d5 * d4;
+    if (va > 0.0 && vb > 0.0 && vc > 0.0) {
+        const double s = (va + vb) + vc;
+        const V3 q0 = along(along(a, ab, vb / s), ac, vc / s);
+        if (dist2(p, q0) < best) { q = q0; region = 0; }
+    }
+    return q;
+}
+
+// the kind of a staged face, as the bits of a.w carry it (mm_tri_plan.h: face_kind)
+enum : int { kFaceProper = 0, kFaceDegenerate = 1, kFaceThin = 2 };
+
+__device__ __forceinline__ V3 face_closest(const V3& p, const V3& a, const V3& b, const V3& c, const V3& ab, const V3& ac,
+                                           int kind, int& region)
+{
+    if (kind == kFaceProper) return tri_closest(p, a, b, c, ab, ac, region);
+    if (kind == kFaceDegenerate) return degenerate_closest(p, a, b, c, region);
+    return thin_closest(p, a, b, c, ab, ac, region);
+}
+
 __device__ __forceinline__ double face_d2(const V3& p, const V3& a, const V3& b, const V3& c, const V3& ab, const V3& ac,
-                                          bool degenerate)
+                                          int kind)
 {
     int region;
-    const V3 q = degenerate ? degenerate_closest(p, a, b, c, region) : tri_closest(p, a, b, c, ab, ac, region);
-    return dist2(p, q);
+    return dist2(p, face_closest(p, a, b, c, ab, ac, kind, region));
 }
 
 }  // namespace mm

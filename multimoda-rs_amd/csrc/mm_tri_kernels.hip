@@ -6,8 +6,8 @@
 //
 // Mapping: one work item = 256 lanes x QPT queries against one chunk of CH faces; a chunk is staged in LDS as three
 // double4 per face (corner a, b, c), so that a corner is two ds_read broadcasts (all lanes read the same address:
-// conflict-free).  a.w carries the bits of the face's degenerate flag, b.w those of its original index; both are the
-// same for all lanes and are made scalar with readfirstlane, so the degenerate branch is uniform.
+// conflict-free).  a.w carries the bits of the face's kind (0 proper, 1 degenerate, 2 thin), b.w those of its original
+// index; both are the same for all lanes and are made scalar with readfirstlane, so the branch on the kind is uniform.
 // Per (query, face): 9 sub, 6 dots (30), 3 cross terms (9), then the branch of the query's region -- a vertex (nothing),
 // an edge (1 division, 3 mul-add pairs) or the interior (2 divisions, 6 pairs) -- and the squared distance (8): about 60
 // fp64 VALU operations and at most 2 divisions against 6/QPT LDS reads -> fp64-VALU bound.  The divisions stay inside
@@ -98,11 +98,11 @@ k_tri_min(const TriWork* __restrict__ work, int n_work, const double4* __restric
             const double4 ta = s_t[3 * j], tb = s_t[3 * j + 1], tc = s_t[3 * j + 2];
             const V3 a{ta.x, ta.y, ta.z}, b{tb.x, tb.y, tb.z}, c{tc.x, tc.y, tc.z};
             const V3 ab = sub3(b, a), ac = sub3(c, a);
-            const bool degenerate = scalar_bits(ta.w) != 0ull;
+            const int kind = (int)scalar_bits(ta.w);   // uniform: proper, degenerate or thin
             const unsigned long long id = WHO ? (scalar_bits(tb.w) << 32) | (unsigned int)(w.c0 + j) : 0ull;
 #pragma unroll
             for (int k = 0; k < QPT; ++k) {
-                const double v = face_d2(p[k], a, b, c, ab, ac, degenerate);
+                const double v = face_d2(p[k], a, b, c, ab, ac, kind);
                 if (WHO) best[k] = v == fin[k] && id < best[k] ? id : best[k];
                 else m[k] = v < m[k] ? v : m[k];
             }
@@ -133,8 +133,7 @@ k_tri_closest(const double4* __restrict__ tri, const double* __restrict__ qxyz, 
         const double4 ta = tri[3 * j], tb = tri[3 * j + 1], tc = tri[3 * j + 2];
         const V3 a{ta.x, ta.y, ta.z}, b{tb.x, tb.y, tb.z}, cc{tc.x, tc.y, tc.z};
         const V3 p{qxyz[3 * (long long)q], qxyz[3 * (long long)q + 1], qxyz[3 * (long long)q + 2]};
-        c = __double_as_longlong(ta.w) != 0 ? degenerate_closest(p, a, b, cc, r)
-                                            : tri_closest(p, a, b, cc, sub3(b, a), sub3(cc, a), r);
+        c = face_closest(p, a, b, cc, sub3(b, a), sub3(cc, a), (int)__double_as_longlong(ta.w), r);
     }
     closest[3 * (long long)q] = c.x; closest[3 * (long long)q + 1] = c.y; closest[3 * (long long)q + 2] = c.z;
     region[q] = r;

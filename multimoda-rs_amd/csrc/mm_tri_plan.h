@@ -1,5 +1,5 @@
 // mm_tri_plan.h -- the host plan of the point-to-triangle search (mm_tri_kernels.hip), shared by mm_surface.cpp and
-// mm_relax.cpp: the argument checks, the slab order of faces and queries, the degenerate flags, the boxes of query blocks
+// mm_relax.cpp: the argument checks, the slab order of faces and queries, the faces' kinds, the boxes of query blocks
 // and chunks, the (query block, chunk) items with their lower bounds (mm_prune.h) and the staged face records.
 // Header-only; internal.
 #pragma once
@@ -23,6 +23,7 @@ struct TriPlan {
     std::vector<int32_t> forder;       // staged face j is face forder[j]
     std::vector<int32_t> qperm;        // staged query j is query qperm[j]
     std::vector<uint8_t> degenerate;   // per staged face
+    std::vector<uint8_t> thin;         // per staged face: not degenerate and thin (face_kind == 2)
     std::vector<TriWork> work;         // n_a items of pass A (one per query block), then n_b of pass B
     std::vector<Box3> cbox;            // the box of every chunk's corners
     int64_t n_a = 0, n_b = 0;
@@ -53,6 +54,24 @@ inline bool is_degenerate(const double* a, const double* b, const double* c, con
     return nx == 0.0 && ny == 0.0 && nz == 0.0;
 }
 
+// The kind of a face as include/mm_ccta.h ("surface distance") states it: 1 degenerate; else 2 (thin) where
+// dot(n, n) < 2^-34 (l l) with n = ab x ac and l the largest of dot(ab, ab), dot(ac, ac), dot(bc, bc); else 0.  The values
+// are kFaceProper, kFaceDegenerate and kFaceThin of mm_tri_device.h.  Unfused f64 like the degenerate test: the host
+// code is built with -ffp-contract=off too.
+inline uint8_t face_kind(const double* a, const double* b, const double* c, const int64_t* f)
+{
+    if (is_degenerate(a, b, c, f)) return 1;
+    const double ab[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ac[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double bc[3] = {c[0] - b[0], c[1] - b[1], c[2] - b[2]};
+    const double nx = ab[1] * ac[2] - ab[2] * ac[1], ny = ab[2] * ac[0] - ab[0] * ac[2], nz = ab[0] * ac[1] - ab[1] * ac[0];
+    const double nn = (nx * nx + ny * ny) + nz * nz;
+    double l = (ab[0] * ab[0] + ab[1] * ab[1]) + ab[2] * ab[2];
+    const double lac = (ac[0] * ac[0] + ac[1] * ac[1]) + ac[2] * ac[2], lbc = (bc[0] * bc[0] + bc[1] * bc[1]) + bc[2] * bc[2];
+    l = lac > l ? lac : l;
+    l = lbc > l ? lbc : l;
+    return nn < 0x1p-34 * (l * l) ? 2 : 0;
+}
+
 // Slab order of faces (by centroid: the sum of the three corners) and queries across the longest axis of the faces'
 // corners, the boxes of query blocks and chunks, and the items.  Arguments checked by plan_args.
 inline int build_plan(const double* v, const int64_t* f, int64_t nf, const double* q, int64_t nq, const char* who, TriPlan& pl)
@@ -70,9 +89,12 @@ inline int build_plan(const double* v, const int64_t* f, int64_t nf, const doubl
     for (int64_t i = 0; i < nq; ++i) key[(size_t)i] = q[3 * i + ax];
     slab_permutation(key, pl.qperm);
     pl.degenerate.resize((size_t)nf);
+    pl.thin.resize((size_t)nf);
     for (int64_t j = 0; j < nf; ++j) {
         const int64_t* t = f + 3 * (int64_t)pl.forder[(size_t)j];
-        pl.degenerate[(size_t)j] = is_degenerate(v + 3 * t[0], v + 3 * t[1], v + 3 * t[2], t);
+        const uint8_t kind = face_kind(v + 3 * t[0], v + 3 * t[1], v + 3 * t[2], t);
+        pl.degenerate[(size_t)j] = kind == 1;
+        pl.thin[(size_t)j] = kind == 2;
     }
     t_order.stop();
     TraceTimer t_items("tri: boxes and items");
@@ -103,13 +125,14 @@ inline int build_plan(const double* v, const int64_t* f, int64_t nf, const doubl
     return MM_OK;
 }
 
-// The staged faces: 12 doubles each (a, b, c as x y z w; a.w = the bits of the degenerate flag, b.w = those of the
+// The staged faces: 12 doubles each (a, b, c as x y z w; a.w = the bits of the face's kind, b.w = those of the
 // original face index), in the plan's order.
 inline void stage_tri_records(const TriPlan& pl, const double* v, const int64_t* f, int64_t nf, double* t)
 {
     for (int64_t j = 0; j < nf; ++j, t += 12) {
         const int64_t orig = pl.forder[(size_t)j];
-        const unsigned long long w[3] = {pl.degenerate[(size_t)j] ? 1ull : 0ull, (unsigned long long)orig, 0ull};
+        const unsigned long long w[3] = {pl.degenerate[(size_t)j] ? 1ull : (pl.thin[(size_t)j] ? 2ull : 0ull),
+                                         (unsigned long long)orig, 0ull};
         for (int k = 0; k < 3; ++k) {
             std::memcpy(t + 4 * k, v + 3 * f[3 * orig + k], 24);
             std::memcpy(t + 4 * k + 3, &w[k], 8);

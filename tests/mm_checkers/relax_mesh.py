@@ -163,7 +163,7 @@ def refreshed_items(plan, step, rv, rf):
     for k in np.unique(prev[prev >= 0]):
         sel = prev == k
         t = rf[k]
-        q = SD.closest_on_face(cand[sel], rv[t[0]], rv[t[1]], rv[t[2]], SD.is_degenerate(rv, t))[0]
+        q = SD.closest_on_face(cand[sel], rv[t[0]], rv[t[1]], rv[t[2]], SD.face_kind(rv, t))[0]
         with np.errstate(all="ignore"):
             seed[sel] = SD.dist_sq(cand[sel], q)
     corners = rv[rf[plan["face_order"]]]                                   # (staged face, corner, xyz)

@@ -2,8 +2,9 @@
 csrc/mm_tri_kernels.hip and csrc/mm_surface.cpp.  Vectorised over the queries, one face at a time; numpy's elementwise
 f64 operations are IEEE and unfused, so every line below is one rounding, in the header's order.
 
-* `closest_on_face`: Ericson's closest point of a proper face, the first test that holds winning, or the segment rule of a
-  degenerate one; the region with it.
+* `face_kind`: 0 a proper face, 1 a degenerate one, 2 a thin one (the header's f64 test on ab x ac and the longest edge).
+* `closest_on_face`: Ericson's closest point of a proper face, the first test that holds winning; the segment rule of a
+  degenerate one; of a thin one the segment rule and then the interior candidate; the region with it.
 * `scan`: the fold over the faces in index order with strict <, unpruned: the lowest face index wins ties, a NaN never.
 * `predict_report`: the integer report fields of mm_point_mesh_distance that do not depend on the data.
 """
@@ -31,6 +32,27 @@ def is_degenerate(v, face):
     return n[0] == 0.0 and n[1] == 0.0 and n[2] == 0.0
 
 
+THIN_K = 17                     # thin: (smallest altitude / longest edge)^2 < 2^-34 as computed; see the header
+THIN_SQ = 2.0 ** (-2 * THIN_K)
+PROPER, DEGENERATE, THIN = 0, 1, 2
+
+
+def face_kind(v, face):
+    """0, 1 (degenerate: is_degenerate) or 2 (thin: dot(n, n) < 2^-34 * (l * l) with n = ab x ac and l the largest of
+    dot(ab, ab), dot(ac, ac), dot(bc, bc), bc = c - b)."""
+    if is_degenerate(v, face):
+        return DEGENERATE
+    i, j, k = (int(x) for x in face)
+    with np.errstate(all="ignore"):
+        ab, ac, bc = v[j] - v[i], v[k] - v[i], v[k] - v[j]
+        n = np.array([ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]])
+        l = dot(ab, ab)
+        for e in (ac, bc):
+            m = dot(e, e)
+            l = m if m > l else l
+        return THIN if dot(n, n) < THIN_SQ * (l * l) else PROPER
+
+
 def _segment(p, u, v):
     e = v - u
     l = dot(e, e)
@@ -47,25 +69,46 @@ def dist_sq(p, q):
     return dot(d, d)
 
 
-def closest_on_face(p, a, b, c, degenerate):
-    """(closest (n, 3), region (n,)) of the queries p (n, 3) on the face (a, b, c)."""
+def _segments(p, a, b, c):
+    """(closest, its d2, region 4 5 6): the nearest of ab, bc, ca, the first on ties."""
+    q = _segment(p, a, b)
+    best = dist_sq(p, q)
+    region = np.full(len(p), 4, dtype=np.int32)
+    for r, (u, w) in ((5, (b, c)), (6, (c, a))):
+        q2 = _segment(p, u, w)
+        v2 = dist_sq(p, q2)
+        take = v2 < best
+        best = np.where(take, v2, best)
+        q = np.where(take[:, None], q2, q)
+        region = np.where(take, r, region).astype(np.int32)
+    return q, best, region
+
+
+def closest_on_face(p, a, b, c, kind):
+    """(closest (n, 3), region (n,)) of the queries p (n, 3) on the face (a, b, c) of kind 0, 1 or 2 (face_kind; False and
+    True stand for 0 and 1)."""
     p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
     a, b, c = (np.asarray(x, dtype=np.float64) for x in (a, b, c))
     n = len(p)
+    kind = int(kind)
     with np.errstate(all="ignore"):
-        if degenerate:
-            q = _segment(p, a, b)
-            best = dist_sq(p, q)
-            region = np.full(n, 4, dtype=np.int32)
-            for r, (u, w) in ((5, (b, c)), (6, (c, a))):
-                q2 = _segment(p, u, w)
-                v2 = dist_sq(p, q2)
-                take = v2 < best
-                best = np.where(take, v2, best)
-                q = np.where(take[:, None], q2, q)
-                region = np.where(take, r, region).astype(np.int32)
+        if kind == DEGENERATE:
+            q, _, region = _segments(p, a, b, c)
             return q, region
         ab, ac = b - a, c - a
+        if kind == THIN:
+            q, best, region = _segments(p, a, b, c)
+            ap, bp, cp = p - a, p - b, p - c
+            d1, d2 = dot(ab, ap), dot(ac, ap)
+            d3, d4 = dot(ab, bp), dot(ac, bp)
+            d5, d6 = dot(ab, cp), dot(ac, cp)
+            vc = d1 * d4 - d3 * d2
+            vb = d5 * d2 - d1 * d6
+            va = d3 * d6 - d5 * d4
+            s = (va + vb) + vc
+            q0 = along(along(a, ab, vb / s), ac, vc / s)
+            take = (va > 0.0) & (vb > 0.0) & (vc > 0.0) & (dist_sq(p, q0) < best)
+            return np.where(take[:, None], q0, q), np.where(take, 0, region).astype(np.int32)
         ap = p - a
         d1, d2 = dot(ab, ap), dot(ac, ap)
         bp = p - b
@@ -108,7 +151,7 @@ def scan(points, vertices, faces):
     closest = np.full((n, 3), np.nan)
     region = np.full(n, -1, dtype=np.int32)
     for k, t in enumerate(f):
-        q, r = closest_on_face(p, v[t[0]], v[t[1]], v[t[2]], is_degenerate(v, t))
+        q, r = closest_on_face(p, v[t[0]], v[t[1]], v[t[2]], face_kind(v, t))
         with np.errstate(all="ignore"):
             d = dist_sq(p, q)
             take = d < sq
@@ -123,7 +166,7 @@ def pair_sq(points, vertices, faces):
     out = np.zeros((len(faces), len(p)))
     for k, t in enumerate(np.asarray(faces, dtype=np.int64).reshape(-1, 3)):
         with np.errstate(all="ignore"):
-            out[k] = dist_sq(p, closest_on_face(p, v[t[0]], v[t[1]], v[t[2]], is_degenerate(v, t))[0])
+            out[k] = dist_sq(p, closest_on_face(p, v[t[0]], v[t[1]], v[t[2]], face_kind(v, t))[0])
     return out
 
 

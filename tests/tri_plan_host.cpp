@@ -41,6 +41,8 @@ int main()
             f.insert(f.end(), quad, quad + 6);
         }
     f.insert(f.end(), {0, 0, 1});                                         // a degenerate face
+    for (int k = 0; k < 3; ++k) v.push_back(0.5 * (v[(size_t)k] + v[(size_t)(3 + k)]) + (k == 2 ? 0x1p-25 : 0.0));
+    f.insert(f.end(), {0, 1, (int64_t)v.size() / 3 - 1});                 // a thin face: a cap of height 2^-25 over 0 - 1
     const int64_t nv = (int64_t)v.size() / 3, nf = (int64_t)f.size() / 3;
     std::vector<double> q;
     for (int64_t i = 0; i < nv; ++i)
@@ -67,9 +69,11 @@ int main()
     for (int32_t j : pl.qperm) { CHECK(j >= 0 && j < nq); if (j >= 0 && j < nq) ++seen_q[(size_t)j]; }
     for (int c : seen_f) CHECK(c == 1);
     for (int c : seen_q) CHECK(c == 1);
-    int n_degenerate = 0;
+    int n_degenerate = 0, n_thin = 0;
     for (uint8_t d : pl.degenerate) n_degenerate += d;
-    CHECK(n_degenerate == 1);
+    for (uint8_t d : pl.thin) n_thin += d;
+    CHECK(n_degenerate == 1 && n_thin == 1);
+    for (int64_t j = 0; j < nf; ++j) CHECK(!(pl.degenerate[(size_t)j] && pl.thin[(size_t)j]));
     for (int64_t j = 0; j < nf; ++j)                                      // every corner inside its chunk's box
         for (int k = 0; k < 3; ++k) {
             const double* p = v.data() + 3 * f[(size_t)(3 * pl.forder[(size_t)j] + k)];
@@ -104,7 +108,7 @@ int main()
             std::memcpy(&w[k], &rec[(size_t)(12 * j + 4 * k + 3)], 8);
             CHECK(std::memcmp(&rec[(size_t)(12 * j + 4 * k)], v.data() + 3 * f[(size_t)(3 * pl.forder[(size_t)j] + k)], 24) == 0);
         }
-        CHECK(w[0] == pl.degenerate[(size_t)j] && w[1] == (unsigned long long)pl.forder[(size_t)j] && w[2] == 0);
+        CHECK(w[0] == (pl.degenerate[(size_t)j] ? 1u : pl.thin[(size_t)j] ? 2u : 0u) && w[1] == (unsigned long long)pl.forder[(size_t)j] && w[2] == 0);
     }
 
     TriPlan none;
