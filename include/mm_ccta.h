@@ -1245,6 +1245,83 @@ int     mm_section_chain(const void* segments, int64_t n_segments, const double*
                          int64_t* contour_plane, int8_t* contour_kind, double* contour_area, double* contour_length,
                          double* contour_centroid, int64_t* plane_off, int64_t* selected, int64_t* counts);
 
+/* ---- winding number (no counterpart in the reference, whose roadmap lists "write a more stable function to find
+ *      intramural points on aorta" and "intramural length etc. from the CCTA mesh" as open) -----------------------------
+ * The generalized winding number (Jacobson et al. 2013) of a triangle mesh at query points,
+ * w(p) = (1 / 4 pi) sum_f Omega_f(p): 1 inside and 0 outside a closed mesh of positive volume (mm_fix_winding leaves it
+ * so), a smooth fraction near the openings of an open one, where w > 1/2 stays a sound "inside".
+ * tests/mm_checkers/winding_number.py is the executable form of the rule; csrc/mm_winding_device.h is its C++ text.
+ * Everything is unfused f64 in the order written; dot(u, v) = (ux*vx + uy*vy) + uz*vz.  No atan2 runs on the device.
+ *
+ * 1. Staging.  Faces are taken in the caller's order.  Degenerate faces ("surface distance": a repeated index, or every
+ *    component of ab x ac exactly 0.0) are removed first: a mesh with them gives the bits of the mesh without them.  nf'
+ *    is the number of staged faces.  A coordinate of magnitude above 2^300 is an argument error, so L (2) stays finite.
+ * 2. Per query p and staged face (A, B, C): a = A-p, b = B-p, c = C-p; la = sqrt(dot(a,a)), lb, lc likewise;
+ *    L = (la*lb)*lc; u = b x c = (by*cz - bz*cy, bz*cx - bx*cz, bx*cy - by*cx); num = (ax*ux + ay*uy) + az*uz;
+ *    den = ((la*lb)*lc + dot(a,b)*lc) + (dot(b,c)*la + dot(c,a)*lb).  Van Oosterom-Strackee:
+ *    Omega_f / 2 = arg(den + i num), in (-pi, pi].
+ * 3. A running angle is a pair (n, P): n an integer number of quarter turns, P = (pr, pi) a complex number in the cone
+ *    pr >= |pi|; it stands for n*pi/2 + arg P.  cone(re, im) rotates a complex number into the cone by an exact multiple m
+ *    of 90 degrees; the first case that holds:
+ *      im > re && im >= -re && im > 0:   m = 1,  (im, -re)
+ *      im < -re && im <= re && im < 0:   m = -1, (-im, re)
+ *      re < 0:                           m = 2 where im >= 0, else -2; (-re, -im)
+ *      otherwise:                        m = 0,  (re, im).
+ * 4. To add m quarter turns and a z = (zr, zi) of the cone to (n, P): qr = pr*zr - pi*zi, qi = pr*zi + pi*zr;
+ *    (m2, qr, qi) = cone(qr, qi) -- both factors lie in the cone and rounding is monotone, so qr >= 0 before the call and
+ *    |m2| <= 1; n += m + m2; P = (qr, qi) scaled by the power of two that puts qr in [1/2, 1) (frexp, ldexp: exact).
+ *    A face is folded with (m, z) = cone(den, num).  Two partial angles fold the same way: the second one's n is m, its P
+ *    is z.
+ * 5. Flags of a face, folded per query: touch (OR): den <= 0 && |num| <= 2^-47 * L -- the sign of num is not proven (the
+ *    bound is Shewchuk's orient3d A-bound (7 + 56 eps) eps times a permanent of at most 6 L), so the face may lie on
+ *    either side of its +-2 pi jump.  rho (min): max(|den|, |num|) / L, a true division: how far den + i num is from 0
+ *    relative to its scale; small exactly when p is near the face's edges or corners.
+ * 6. The zero face: max(|den|, |num|) < 2^-600, or the least of dot(a,a), dot(b,b), dot(c,c) < 2^-960 (a query on a
+ *    vertex, and everything that could underflow).  It is not folded and sets rho = 0.
+ * 7. Grouping, which fixes the bits.  A chunk is 256 consecutive staged faces; a group is G = ceil(chunks / 16)
+ *    consecutive chunks, so there are ceil(chunks / G) <= 16 groups (mm_winding_plan reports the numbers).  A group's
+ *    partial is the sequential fold of its faces from n = 0, P = (1, 0), rho = +inf, touch = 0; a query's total is the
+ *    fold of its group partials in ascending order, the first one taken as it is.  G depends on nf' alone, so a query's
+ *    bits do not depend on which other queries share the call.
+ * 8. Result (host): w = (n * (pi/2) + atan2(pi, pr)) / (2 pi) with the C library's atan2.
+ *    err = nf' * (MM_WINDING_ERR_C1 + MM_WINDING_ERR_C2 / rho) * 2^-53, a proven bound on |w - w_exact| for the f64 inputs
+ *    (DESIGN 4.29); +inf where touch is set or rho < MM_WINDING_RHO_MIN (rho == 0 included).  Without a staged face
+ *    w = 0, err = 0. */
+
+#define MM_WINDING_ERR_C1  4.0
+#define MM_WINDING_ERR_C2  9.0
+#define MM_WINDING_RHO_MIN 9.094947017729282379150390625e-13   /* 2^-40 */
+
+typedef struct mm_winding_report {
+    int64_t n_staged_faces;       /* nf' */
+    int64_t n_degenerate_faces;   /* nf - nf' */
+    int64_t chunk_faces;          /* faces a chunk */
+    int64_t chunks_per_group;     /* G */
+    int64_t groups;
+    int64_t items;                /* (query block, group) work items */
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;
+    int64_t bytes_scratch;        /* the partial records: nq x groups x 32 */
+} mm_winding_report;              /* 80 bytes */
+
+/* Per query i: out_n[i] quarter turns, out_p[2 i], out_p[2 i + 1] = P, out_rho[i], out_touch[i] (0 or 1); without a
+ * staged face n = 0, P = (1, 0), rho = +inf, touch = 0.  nf == 0 or nq == 0 is valid.  MM_ERR_INVALID: a non-finite
+ * coordinate or one above 2^300 in vertices or queries, a face index out of range, nv, nf or nq of 2^31 or more;
+ * MM_ERR_TOO_LARGE: more than 2^31 - 1 work items.  On an error the outputs are not written. */
+int     mm_mesh_winding(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                        const double* queries_xyz, int64_t nq, int32_t* out_n, double* out_p, double* out_rho,
+                        uint8_t* out_touch, mm_winding_report* report);
+/* Rule 8 on the host: out_w and out_err from (n, p, rho, touch) of nq queries and nf' = n_staged. */
+int     mm_winding_result(const int32_t* n, const double* p, const double* rho, const uint8_t* touch, int64_t nq,
+                          int64_t n_staged, double* out_w, double* out_err);
+/* TEST HOOK (no engine, no device): the grouping of rule 7 for n_staged faces.  info[4] = {faces per chunk, G, groups,
+ * n_staged}. */
+int     mm_winding_plan(int64_t n_staged, int64_t* info);
+/* TEST HOOK (no engine, no device): mm_mesh_winding on the host by the arithmetic the kernels run
+ * (csrc/mm_winding_device.h), in the same grouping.  *n_staged = nf'. */
+int     mm_winding_fold_host(const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                             const double* queries_xyz, int64_t nq, int32_t* out_n, double* out_p, double* out_rho,
+                             uint8_t* out_touch, int64_t* n_staged);
+
 /* ---- branch labelling(multimodars/ccta/labeling.py:415-487) -------------------------------------------------------- */
 
 #define MM_BRANCH_MASK_BITS 64   /* branch ids a mask holds: a centerline point with a larger branch_id is MM_ERR_INVALID */

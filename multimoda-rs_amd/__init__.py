@@ -48,6 +48,10 @@ from . import intersect
 from .intersect import MeshIntersections, mesh_intersections, mesh_self_intersections
 from . import section
 from .section import MeshCrossSections, VesselProfile, centerline_cross_sections, mesh_cross_sections, vessel_profile
+from . import winding
+from .winding import (ContainmentReport, IntramuralCourse, IntramuralPoints, SignedPointMeshDistance, WindingNumber,
+                      intramural_course, intramural_points, mesh_containment, mesh_winding_number, points_in_mesh,
+                      signed_point_mesh_distance)
 from . import skeleton
 from .skeleton import SkeletonGraph, centerline_from_mesh, mesh_geodesic_distance, mesh_skeleton, skeleton_centerline
 from .convert import numpy_to_geometry, to_array
@@ -95,6 +99,9 @@ __all__ = [
     "DirectedDistance", "SurfaceDistanceReport",
     "intersect", "mesh_self_intersections", "mesh_intersections", "MeshIntersections",
     "section", "mesh_cross_sections", "centerline_cross_sections", "vessel_profile", "MeshCrossSections", "VesselProfile",
+    "winding", "mesh_winding_number", "points_in_mesh", "signed_point_mesh_distance", "mesh_containment",
+    "intramural_points", "intramural_course", "WindingNumber", "SignedPointMeshDistance", "ContainmentReport",
+    "IntramuralPoints", "IntramuralCourse",
     "skeleton", "mesh_geodesic_distance", "mesh_skeleton", "centerline_from_mesh", "skeleton_centerline", "SkeletonGraph",
     "morphometry", "ContourMeasures", "contour_measures",
     "synthetic_case", "synthetic_pullback", "catheter_points", "contour_centroid",

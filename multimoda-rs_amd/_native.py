@@ -124,6 +124,7 @@ EXPORTS_CCTA = [
     "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges", "mm_mesh_repair",
     "mm_mesh_intersections", "mm_isect_plan",
     "mm_mesh_sections", "mm_section_plan", "mm_section_cut_host", "mm_section_chain",
+    "mm_mesh_winding", "mm_winding_result", "mm_winding_plan", "mm_winding_fold_host",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
 
@@ -174,6 +175,13 @@ class MMSectionReport(C.Structure):
     _fields_ = [(name, C.c_int64) for name in (
         "n_planes", "n_faces", "n_skipped_faces", "n_segments", "n_contours", "n_closed", "n_open", "n_branched", "items",
         "items_total", "face_tests", "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMWindingReport(C.Structure):
+    """``mm_winding_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_staged_faces", "n_degenerate_faces", "chunk_faces", "chunks_per_group", "groups", "items", "n_launches",
+        "bytes_uploaded", "bytes_downloaded", "bytes_scratch")]
 
 
 class MMIntersectReport(C.Structure):
@@ -719,6 +727,14 @@ def lib():
     L.mm_section_cut_host.argtypes = [P, I64, P, I64, P, P, I64, I64, P, P]
     L.mm_section_chain.restype = I
     L.mm_section_chain.argtypes = [P, I64, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, P]
+    L.mm_mesh_winding.restype = I
+    L.mm_mesh_winding.argtypes = [P, P, I64, P, I64, P, I64, P, P, P, P, C.POINTER(MMWindingReport)]
+    L.mm_winding_result.restype = I
+    L.mm_winding_result.argtypes = [P, P, P, P, I64, I64, P, P]
+    L.mm_winding_plan.restype = I
+    L.mm_winding_plan.argtypes = [I64, P]
+    L.mm_winding_fold_host.restype = I
+    L.mm_winding_fold_host.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P]
     L.mm_tri_plan.restype = I
     L.mm_tri_plan.argtypes = [P, I64, P, I64, P, I64, P, P, P, P, P, I64]
     L.mm_assign_rings_to_ends.restype = I

@@ -103,6 +103,16 @@ hipError_t launch_section_cut(const int32_t* items, int n_items, const int32_t* 
                               const double* tri12, int n_faces, unsigned long long* counters, void* segments,
                               unsigned long long cap, hipStream_t s);
 int        section_launches();
+// winding numbers (mm_winding_kernels.hip; the arithmetic is mm_winding_device.h): tri9 = nf staged faces of 9 doubles
+// (a, b, c as x y z) in the caller's order, degenerate ones removed; a group is chunks_per_group chunks of
+// wind_chunk_faces() faces, none of the `groups` (at most wind_max_groups()) empty.  partials: nq x groups records of 32
+// bytes, device scratch, every one written before it is read.  Per query: n quarter turns, p = (pr, pi), rho, touch.
+hipError_t launch_winding(const double* tri9, int nf, int chunks_per_group, int groups, const double* qxyz, int nq,
+                          void* partials, int32_t* out_n, double* out_p, double* out_rho, int32_t* out_touch, hipStream_t s);
+int        wind_launches();
+int        wind_queries_per_block();
+int        wind_chunk_faces();
+int        wind_max_groups();
 // ray casting of the occlusion removal (mm_ray_kernels.hip): ray = 6 planes of n_rays doubles (origin xyz, direction
 // xyz), tri = 9 planes of n_faces doubles (v0 xyz, e1 = v1 - v0, e2 = v2 - v0); part = n_rays x ceil(n_faces /
 // ray_chunk_faces()) records of scratch; closest[r] = the face of ray r's smallest (t, index) if it hits at least 3
