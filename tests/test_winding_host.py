@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import multimoda_rs_amd as mm
+import winding_attack_cases as ac
 import winding_cases as wc
 from mm_checkers import winding_number as chk
 
@@ -88,7 +89,18 @@ def test_adversarial_queries(name, mesh, stride):
     pts, kind, h = wc.adversarial(v, f, stride)
     e, ref = wc.expected(name), wc.expected_reference(name)
     # touch: every query placed on a face's interior, none that is 1e-12 or more off its face; a query placed on an edge
-    # or a vertex is caught by touch or by rho, whichever way its own rounding moved it
+    # or a vertex is caught by touch or by rho, whichever way its own rounding moved it.  Where the rounding of an h = 0
+    # query left it, by the exact oracle of tests/winding_attack_cases.py: of the 32 placed on a face's interior 1 is
+    # exactly on its face on the sphere and none on the tube, the others are off the plane by less than an ulp of a
+    # coordinate; of the 96 on edge midpoints 15 and 39 are exactly on the edge; all 96 on corners are the corner; and of
+    # the 32 placed in the plane outside the triangle 1 (sphere) and 0 (tube) are exactly in the plane.
+    zero = np.flatnonzero(h == 0.0)
+    owner = (zero // (pts.shape[0] // len(range(0, f.shape[0], stride)))) * stride
+    cls = ac.owner_classes(pts[zero], v, f, [[int(o)] for o in owner])["cls"]
+    on = [int(((cls == ac.ON) & (kind[zero] == k)).sum()) for k in range(4)]
+    assert on == {"sphere512": [1, 15, 96, 0], "tube": [0, 39, 96, 0]}[mesh]
+    assert int(((cls == ac.PLANE_OUT) & (kind[zero] == 3)).sum()) == {"sphere512": 1, "tube": 0}[mesh]
+    assert np.isinf(e["err"][zero][cls == ac.ON]).all() and (e["inside"][zero][cls == ac.ON] == -1).all()
     assert e["touch"][(kind == 0) & (h == 0.0)].all()
     assert not e["touch"][np.abs(h) >= 1e-12].any()
     assert (e["rho"][(kind == 2) & (h == 0.0)] == 0.0).all()          # a query on a vertex
