@@ -146,7 +146,7 @@ int  mm_engine_first_min_stats(mm_engine* e, int64_t out[2]);
  * beyond 1e+-30) show up under out[0] / out[1]. */
 int  mm_engine_screen_stats(mm_engine* e, int64_t out[5]);
 /* mm_engine_set_bound_min_candidates, mm_engine_set_bound_matrix, mm_engine_set_screen_cull, mm_engine_set_screen_split,
- * mm_engine_set_screen_group, mm_engine_set_screen_pair and mm_engine_set_screen_floor apply to the levels staged
+ * mm_engine_set_screen_group, mm_engine_set_screen_pair, mm_engine_set_screen_floor and mm_engine_set_screen_run apply to the levels staged
  * after the call: a plan runs with the switches in force when it was created (mm_plan_create*), a within-plan's level with
  * those in force when it is staged. */
 /* MM_PRECISION_F32_BOUNDED runs its bound rounds only on batches of at least n candidates (default
@@ -186,6 +186,13 @@ int  mm_engine_set_screen_pair(mm_engine* e, int on);
  * same bit for bit; the tiles computed and the followers that leave after phase 1 differ.  The hooks mm_screen_values,
  * mm_screen_values_split and mm_screen_values_group screen with the floor off; mm_screen_values_floor takes it. */
 int  mm_engine_set_screen_floor(mm_engine* e, int on);
+/* The culled screen's workgroups take RUNS of consecutive work items of one pair and stage the pair -- row fragments, target
+ * points, norms, bounding circles -- once per run instead of once per item.  run == 0 (default): chosen per launch; a launch
+ * of fewer than 32 rounds of resident workgroups has none, a larger one runs of up to (items / 16 rounds) items that shrink
+ * to single items towards its end, so that the end of the launch stays as even as without runs.  1: off, a workgroup per
+ * item (the A/B switch); n > 1: forced, as far as a pair has items.  run < 0: MM_ERR_INVALID.  Screened values, tile counts
+ * and the followers' counters are the same whatever the size, bit for bit; the hooks mm_screen_values* take the setting. */
+int  mm_engine_set_screen_run(mm_engine* e, int run);
 /* Tiles of 32 x 32 distances since the engine was created, of the candidates the culled screen took: out[0] computed,
  * out[1] what the full screen computes for the same candidates. */
 int  mm_engine_screen_tiles(mm_engine* e, int64_t out[2]);

@@ -32,7 +32,7 @@ EXPORTS = [
     "mm_bound_state", "mm_hausdorff_first_min_state",
     "mm_engine_set_screen_cull", "mm_engine_screen_tiles", "mm_engine_screen_early", "mm_screen_values", "mm_tile_bound_probe",
     "mm_engine_set_screen_split", "mm_screen_values_split", "mm_tile_bound_probe_split", "mm_tile_slot_map",
-    "mm_engine_set_screen_group", "mm_engine_set_screen_pair", "mm_engine_set_screen_floor", "mm_screen_values_group", "mm_screen_values_floor", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
+    "mm_engine_set_screen_group", "mm_engine_set_screen_pair", "mm_engine_set_screen_floor", "mm_engine_set_screen_run", "mm_screen_values_group", "mm_screen_values_floor", "mm_tile_bound_probe_group", "mm_screen_group_auto", "mm_level_plan_probe",
     "mm_engine_set_bound_min_candidates",
     "mm_hausdorff_2d", "mm_hausdorff_batch", "mm_refine_angles", "mm_filter_points_in_region",
     "mm_refine_downsample_count", "mm_search_angles", "mm_best_rotation", "mm_best_rotation_batch",
@@ -406,6 +406,8 @@ def lib():
     L.mm_engine_set_screen_group.argtypes = [P, I]
     L.mm_engine_set_screen_pair.restype = I
     L.mm_engine_set_screen_pair.argtypes = [P, I]
+    L.mm_engine_set_screen_run.restype = I
+    L.mm_engine_set_screen_run.argtypes = [P, I]
     L.mm_engine_set_screen_floor.restype = I
     L.mm_engine_set_screen_floor.argtypes = [P, I]
     L.mm_screen_values_floor.restype = I
@@ -1102,6 +1104,13 @@ class Engine:
         already exact (default).  Off: every minimum is made exact.  Same values; fewer tiles with it on.  The hooks
         ``screen_values`` and ``screen_values_group`` screen with it off, ``screen_values_floor`` takes the flag."""
         check(lib().mm_engine_set_screen_floor(self._h, int(bool(on))), "mm_engine_set_screen_floor")
+
+    def set_screen_run(self, run: int):
+        """Culled screen: consecutive work items of one pair that one workgroup runs, staging the pair's fragments, norms and
+        circles once.  0: chosen per launch from its size (none for a launch of few items); 1: off, a workgroup per item;
+        n: forced, as far as a pair has items.  Values and counters are the same whatever the size; the hooks
+        ``screen_values*`` take this setting."""
+        check(lib().mm_engine_set_screen_run(self._h, int(run)), "mm_engine_set_screen_run")
 
     def screen_values_group(self, ref, tgt, angles, centre, group, cull=True, skip_zero=True, split=(0, 0)):
         """TEST HOOK (``mm_screen_values_group``): ``screen_values`` with the group size given; returns the values, e2 and

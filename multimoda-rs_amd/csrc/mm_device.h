@@ -19,9 +19,11 @@ hipError_t launch_screen_fast(const BatchDev& b, int max_na, int max_nbp, hipStr
 // (nct, multi), a reference set of at most a_cap row tiles of 32, and PairDesc::pad0 = the pair's scale exponent
 hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int nct, int multi, int a_cap, hipStream_t s);
 // the same screen without the tiles that provably hold no minimum (k_screen_mx_cull): pairs whose variant mx_cull_takes;
-// tiles (nullable): device counter of the tiles computed
-hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles, int pair,
-                                 int floor, hipStream_t s);
+// tiles (nullable): device counter of the tiles computed.  runs (nullable, device memory): n_runs runs that hold every one
+// of the n_work items once, `first` counted from work_begin, each of one pair -- a workgroup per run, in the table's order;
+// without it a workgroup per item
+hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, const WorkRun* runs, int n_runs, int nct, int a_cap,
+                                 unsigned long long* tiles, int pair, int floor, hipStream_t s);
 hipError_t launch_screen_none(const BatchDev& b, int work_begin, int n_work, hipStream_t s);   // screened value 0 for every candidate
 // bounded screen: lower bound of every lb_candidate_step()-th candidate -> per-pair pick -> full screen of
 // the picks (upper bound) -> spread the bounds to the candidates in between (chord inequality) ->

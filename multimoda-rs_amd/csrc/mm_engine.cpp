@@ -238,6 +238,7 @@ int Plan::stage_level(const std::vector<PairSpec>& pairs, int precision_, int32_
     if (lv.P) std::memcpy(h + l.pairs, lv.host_pairs.data(), (size_t)lv.P * sizeof(PairDesc));
     if (lv.W) std::memcpy(h + l.work, lv.host_work.data(), (size_t)lv.W * sizeof(WorkItem));
     if (lv.W_lb) std::memcpy(h + l.work_lb, lv.host_work_lb.data(), (size_t)lv.W_lb * sizeof(WorkItem));
+    if (!lv.host_runs.empty()) std::memcpy(h + l.runs, lv.host_runs.data(), lv.host_runs.size() * sizeof(WorkRun));
 
     if (transient) {
         if ((rc = e->ensure(e->dev_lvl, l.lvl_bytes, false))) return rc;
@@ -337,8 +338,9 @@ int Plan::run(bool screen_only)
                 case Screen::Matrix: e = launch_screen_mx(dev, g.work_begin, g.work_count, g.nct, g.multi, g.a_cap, s); break;
                 case Screen::MatrixCull:
                     eng->cull_tiles_full += g.tiles_full;
-                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count, g.nct, g.a_cap, eng->dev_tiles, lv.opts.screen_pair ? 1 : 0,
-                                              lv.opts.screen_floor ? 1 : 0, s);
+                    e = launch_screen_mx_cull(dev, g.work_begin, g.work_count,
+                                              g.run_count ? (const WorkRun*)(lvl_blob + lv.lay.runs) + g.run_begin : nullptr, g.run_count,
+                                              g.nct, g.a_cap, eng->dev_tiles, lv.opts.screen_pair ? 1 : 0, lv.opts.screen_floor ? 1 : 0, s);
                     break;
                 }
                 if (e != hipSuccess) break;
@@ -932,6 +934,15 @@ int mm_engine_set_screen_floor(mm_engine* h, int on)
     Engine* e = reinterpret_cast<Engine*>(h);
     if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
     e->screen_opts.screen_floor = on != 0;
+    return MM_OK;
+}
+
+int mm_engine_set_screen_run(mm_engine* h, int run)
+{
+    Engine* e = reinterpret_cast<Engine*>(h);
+    if (!e) return set_error(MM_ERR_INVALID, "engine == NULL");
+    if (run < 0) return set_error(MM_ERR_INVALID, "mm_engine_set_screen_run: 0 (automatic), 1 (off) or the items of a run");
+    e->screen_opts.screen_run = run;
     return MM_OK;
 }
 

@@ -963,8 +963,8 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // the same 1024 values as the full kernel's, in the DUAL form (D = A.B for the column minima, D' = B.A for the row minima,
 // both in-lane: a row tile meets few column tiles, which the single form's LDS row transpose cannot amortise).
 //
-// The bound (mm_tile_bound.h): a bounding circle per row tile (once per work item) and per column tile (unrotated, once per
-// work item; per candidate only its centre is rotated, by the f32 cos / sin the columns take), and per tile pair (I, J)
+// The bound (mm_tile_bound.h): a bounding circle per row tile (once per run of work items, see Runs) and per column tile
+// (unrotated, once per run; per candidate only its centre is rotated, by the f32 cos / sin the columns take), and per tile pair (I, J)
 // a threshold thr(I, J) <= every SCREENED squared distance of the tile (a rigorous lower bound of the exact squared
 // distance, less the screen's error bound PairDesc::e2).
 // Two phases per candidate:
@@ -1037,7 +1037,19 @@ hipError_t launch_screen_mx(const BatchDev& b, int work_begin, int n_work, int n
 // the floor L is "none" throughout, the rule is the plain one and the followers' test is the one above.
 // Layout: a set's points fill its tiles in order, or -- PairDesc::ref_main / tgt_main > 0, a search set of lumen ++ catheter
 // -- run by run (mm_tile_slot_point): the tile that would hold the end of one run and the start of the other has a circle
-// no tile is far from.  Only the per-work-item prologue knows the layout; the minima are over the same values either way.
+// no tile is far from.  Only the staging of a pair knows the layout; the minima are over the same values either way.
+// Runs (ScreenOptions::screen_run, the planner's run table, mm_level_plan.h): what a work item's prologue builds -- the row
+// fragments in s_a, the scaled target points tx / ty, the norm half of s_b, the 34 circles (each by one thread, two serial
+// loops over 32 points, the others at the barrier), S, inv_s2, e2s, nrt -- depends on the pair alone, and a pair of the
+// flagship has 23 items.  A workgroup therefore takes a RUN, consecutive items of one pair, and stages at its first item
+// only; a later item loads its WorkItem, fills s_cs / s_ci between the two barriers that protect them and enters the
+// candidate loop, which writes none of the staged state (the coordinate half of s_b, the row stores, s_th and s_v only).
+// The planner guarantees that a run stays inside one pair and one launch; the kernel does not check.  Block b takes run b:
+// dispatch order is list order, so that the planner's sizes, which fall to single items at the list's end, keep the end of
+// the launch even (xcd_work_index, which spreads a pair's items over one XCD's L2, has nothing left to share: one staging per
+// run).  A candidate sees the same operands in the same order whichever workgroup runs its item: values and counters do not
+// depend on the runs.  Without a table (runs == nullptr: small launches, the switch off) a workgroup takes one item, in
+// xcd_work_index's order, as before runs.
 // -------------------------------------------------------------------------------------
 typedef float f16x16 __attribute__((ext_vector_type(16)));
 
@@ -1080,7 +1092,8 @@ static __device__ __forceinline__ int half_max_i32_dpp(int v)
 // per row tile of a leader and of a follower; fol, early, late: once per follower, per follower that leaves after phase 1,
 // per candidate that does not; "tile" is a computed tile's own body; the pairs' counts -- xcand, pair, single, prows, ptiles,
 // tails, ptails, sfol, searly, pearly, ylate -- are listed in the tool; gnrt and lead, once per row tile per group and once
-// per leader, are the value floor's).
+// per leader, are the value floor's; fghalf: once per two row tiles, per group that has followers; item and run: the
+// prologue's, once per work item and once per run of work items).
 #define MXC_MARK(s) __asm__ volatile("; mxc:" s)
 #define MXC_MARK_V(s, x) __asm__ volatile("; mxc:" s : "+v"(x))      // the mark stays between x's producer and its users
 
@@ -1225,7 +1238,8 @@ static __device__ __forceinline__ void mxc_tiles_chain(unsigned mask, const h8v&
 
 template <int NCT>
 __global__ void __launch_bounds__(256, 2)
-k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work, int a_cap,
+k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict__ work, int n_work,
+                 const WorkRun* __restrict__ runs, int n_runs, int a_cap,
                  const float* __restrict__ ptx, const float* __restrict__ pty, const float* __restrict__ cosv,
                  const float* __restrict__ sinv, float* __restrict__ out_sq, unsigned long long* __restrict__ tiles_done,
                  int pair_on, int floor_on)
@@ -1254,23 +1268,43 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
     unsigned long long done = 0;
     unsigned n_foll = 0, n_early = 0;        // the wave's followers, and those of them that left after phase 1 (tiles_done[2], [1])
 
-    for (int wi = (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; wi < n_work; wi += gridDim.x) {
+    // A workgroup takes a RUN of work items (the planner's run table: consecutive items of ONE pair, which the kernel does not
+    // check; block b the b-th run, so that dispatch order is list order and the guided sizes at the list's end mean what
+    // they say) and stages the pair at the run's first item only: the row fragments, the scaled target points (tx / ty), the
+    // norm half of s_b, the circles and the pair's scalars do not depend on the item, and the candidate loop writes none of
+    // them (only the coordinate half of s_b, the row stores, s_th and s_v).  Every later item loads its WorkItem and its
+    // candidates' cos / sin.  Without a table a run is one item, in xcd_work_index's order.
+    const int n_blocks = runs ? n_runs : n_work;
+    for (int bi = runs ? (int)blockIdx.x : (int)gridDim.x == n_work ? xcd_work_index(blockIdx.x, n_work) : (int)blockIdx.x; bi < n_blocks;
+         bi += gridDim.x) {
+      int wi0 = bi, wi1 = bi + 1;
+      if (runs) { const WorkRun r = runs[bi]; wi0 = r.first; wi1 = r.first + r.count; }
+      // the pair's state, staged at the run's first item (every run has one: the values below are never read before)
+      int nrt = 0, tab_off = 0, out_off = 0;
+      float inv_s2 = 0.0f, e2s = 0.0f;
+      float tx[NQ], ty[NQ];
+      for (int wi = wi0; wi < wi1; ++wi) {
+        MXC_MARK("pro_item:item");
         const WorkItem w = work[wi];
-        const PairDesc pd = pairs[w.pair];
-        const int na = pd.n_ref, nb = pd.n_tgt;
-        const int nrt = (na + 31) >> 5;
-        const float S = __builtin_ldexpf(1.0f, pd.pad0), inv_s2 = __builtin_ldexpf(1.0f, -2 * pd.pad0);
-        const float e2s = mm_tile_e2s(pd.e2, pd.pad0);
+        if (wi == wi0) { const PairDesc& pd0 = pairs[w.pair]; tab_off = pd0.tab_off; out_off = pd0.out_off; }
 
         __syncthreads();
         for (int t = tid; t < 2 * w.cnt; t += 64 * WAVES) {
             const int a = w.a0 + (t >> 1);
-            s_cs[t] = (t & 1) ? sinv[pd.tab_off + a] : cosv[pd.tab_off + a];
+            s_cs[t] = (t & 1) ? sinv[tab_off + a] : cosv[tab_off + a];
             if (!(t & 1)) s_ci[t >> 1] = a;
         }
+        if (wi == wi0) {
+        MXC_MARK("pro_run:run");
+        const PairDesc pd = pairs[w.pair];
+        const int na = pd.n_ref, nb = pd.n_tgt;
+        nrt = (na + 31) >> 5;
+        const float S = __builtin_ldexpf(1.0f, pd.pad0);
+        inv_s2 = __builtin_ldexpf(1.0f, -2 * pd.pad0);
+        e2s = mm_tile_e2s(pd.e2, pd.pad0);
         // a split set (ref_main / tgt_main > 0, plan_level): its two runs tile by tile, here and in the circles
         mx_stage_rows<64 * WAVES>(s_a, nrt, na, ptx + pd.ref_off, pty + pd.ref_off, S, tid, pd.ref_main);
-        float tx[NQ], ty[NQ];
+        MXC_MARK("pro_run:run");
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int j = lane + 64 * q;
@@ -1279,16 +1313,24 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
             if (j < NB) s_b[(j >> 5) * 64 + (j & 31) + 32] = mx_col_norm(tx[q], ty[q]);
         }
         // the circles: thread t < NCT column tile t, thread 64 + t row tile t
+        MXC_MARK("pro_run:run");
         if (tid < NCT) {
             float cx, cy, r;
+            MXC_MARK("pro_run:run");
             mm_tile_circle(ptx + pd.tgt_off, pty + pd.tgt_off, tid * 32, nb, S, &cx, &cy, &r, pd.tgt_main);
+            MXC_MARK("pro_run:run");
             s_circ[tid] = float4{cx, cy, r, 0.0f};
         } else if (tid >= 64 && tid < 64 + nrt) {
             float cx, cy, r;
+            MXC_MARK("pro_run:run");
             mm_tile_circle(ptx + pd.ref_off, pty + pd.ref_off, (tid - 64) * 32, na, S, &cx, &cy, &r, pd.ref_main);
+            MXC_MARK("pro_run:run");
             s_circ[NCT + tid - 64] = float4{cx, cy, r, 0.0f};
         }
+        MXC_MARK("pro_item:item");
+        }
         __syncthreads();
+        MXC_MARK("end:0");
         // A wave takes runs of G consecutive candidates (group q = candidates [q G, (q + 1) G) of the item, wave w the groups w,
         // w + 4, ...; G = WorkItem::pad, 1 | 2 | 4 | 8, chosen per pair at staging): the thresholds and the phase-1 masks are
         // built once per group, and the group's first candidate hands its phase-2 masks on (see below).  G = 1 is the rule per
@@ -1375,15 +1417,18 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         if (!((m1 >> J) & 1)) tr = min(tr, __float_as_int(th[J]));
                     grp_tr = tr;
                 }
+                // (both halves of the wave: lane (h, J) takes the row tiles 2 p + h, the halves meet once -- a minimum does not
+                // depend on its order; with an odd nrt the upper half takes the last row tile a second time)
                 int tc = 0x7f800000;
-                for (int I = 0; I < nrt; ++I) {
-                    MXC_MARK("flr_tc_row:gnrt");
-                    const unsigned pm = __builtin_amdgcn_readlane(m1, I);
-                    const int t = __float_as_int(s_th[I * 32 + l32]);
-                    if (!((pm >> l32) & 1)) tc = min(tc, t);
+                for (int p = 0; 2 * p < nrt; ++p) {
+                    MXC_MARK("flr_tc_row:ghalf");
+                    const int I1 = min(2 * p + 1, nrt - 1);
+                    const unsigned pm0 = __builtin_amdgcn_readlane(m1, 2 * p), pm1 = __builtin_amdgcn_readlane(m1, I1);
+                    const int t = __float_as_int(s_th[(hw ? I1 : 2 * p) * 32 + l32]);
+                    if (!(((hw ? pm1 : pm0) >> l32) & 1)) tc = min(tc, t);
                 }
                 MXC_MARK("flr_tr:group");
-                grp_tc = tc;
+                grp_tc = mxc_meet(tc);
             }
           }
           (void)m1; (void)grp_tr; (void)grp_tc; (void)grp_p1;
@@ -1491,7 +1536,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     const bool leaves = floor_on ? F <= L : lt == 0;
                     if (leaves) {
                         ++n_early;
-                        if (lane == 0) out_sq[pd.out_off + ai] = __int_as_float(F) * inv_s2;
+                        if (lane == 0) out_sq[out_off + ai] = __int_as_float(F) * inv_s2;
                     }
                     return leaves;
                 };
@@ -1634,15 +1679,18 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     const unsigned pf = m1;
                     int tc = 0x7f800000;
                     unsigned cnt = 0;
-                    for (int I = 0; I < nrt; ++I) {
-                        MXC_MARK("grp_tc_row:fgnrt");
-                        const unsigned pm = __builtin_amdgcn_readlane(pf, I);
-                        const int t = __float_as_int(s_th[I * 32 + l32]);
-                        if (!((pm >> l32) & 1)) tc = min(tc, t);
-                        cnt += __builtin_popcount(pm);
+                    // (both halves of the wave, as for the floor's Tc_J in front of the leader; cnt stays a scalar sum over
+                    // all row tiles)
+                    for (int p = 0; 2 * p < nrt; ++p) {
+                        MXC_MARK("grp_tc_row:fghalf");
+                        const int I1 = min(2 * p + 1, nrt - 1);
+                        const unsigned pm0 = __builtin_amdgcn_readlane(pf, 2 * p), pm1 = __builtin_amdgcn_readlane(pf, I1);
+                        const int t = __float_as_int(s_th[(upper ? I1 : 2 * p) * 32 + l32]);
+                        if (!(((upper ? pm1 : pm0) >> l32) & 1)) tc = min(tc, t);
+                        cnt += __builtin_popcount(pm0) + (2 * p + 1 < nrt ? __builtin_popcount(pm1) : 0);
                     }
                     MXC_MARK("grp_tc:fgroup");
-                    grp_tc = tc;                                              // (one register: the followers' check reads it lane by lane)
+                    grp_tc = mxc_meet(tc);                                    // (one register: the followers' check reads it lane by lane)
                     grp_p1 = cnt;
                 }
 
@@ -1663,7 +1711,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm.get(t)));
                 m = wave_max_i32_dpp(m);
-                if (lane == 0) out_sq[pd.out_off + acur] = __int_as_float(m) * inv_s2;
+                if (lane == 0) out_sq[out_off + acur] = __int_as_float(m) * inv_s2;
                 MXC_MARK("end:0");
                 }
                 if (paired) ++k;                                              // (Y is done with X)
@@ -1800,11 +1848,12 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 #pragma unroll
                 for (int t = 0; t < NCT; ++t) m = max(m, mxc_meet(cm[t]));
                 m = wave_max_i32_dpp(m);
-                if (lane == 0) out_sq[pd.out_off + a] = __int_as_float(m) * inv_s2;
+                if (lane == 0) out_sq[out_off + a] = __int_as_float(m) * inv_s2;
                 MXC_MARK("end:0");
             }
           }
         }
+      }
     }
     if (tiles_done && lane == 0 && done) {
         atomicAdd(tiles_done, done);
@@ -1813,24 +1862,26 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
 }
 
 template <int NCT>
-static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int n_work, int a_cap, unsigned long long* tiles,
-                                   int pair, int floor, hipStream_t s)
+static hipError_t launch_mx_cull_t(const BatchDev& b, const WorkItem* work, int n_work, const WorkRun* runs, int n_runs, int a_cap,
+                                   unsigned long long* tiles, int pair, int floor, hipStream_t s)
 {
     const size_t lds = lds_bytes_mx_cull(NCT, a_cap);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_screen_mx_cull<NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_screen_mx_cull<NCT>), dim3(n_work), dim3(256), lds, s, b.pairs, work, n_work, a_cap, b.p32x, b.p32y,
-                       b.cos32, b.sin32, b.sq32, tiles, pair, floor);
+    // a workgroup per run, block b the b-th run; without a table a workgroup per item
+    hipLaunchKernelGGL((k_screen_mx_cull<NCT>), dim3(runs ? n_runs : n_work), dim3(256), lds, s, b.pairs, work, n_work, runs, n_runs,
+                       a_cap, b.p32x, b.p32y, b.cos32, b.sin32, b.sq32, tiles, pair, floor);
     return hipGetLastError();
 }
 
-hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, int nct, int a_cap, unsigned long long* tiles,
-                                 int pair, int floor, hipStream_t s)
+hipError_t launch_screen_mx_cull(const BatchDev& b, int work_begin, int n_work, const WorkRun* runs, int n_runs, int nct, int a_cap,
+                                 unsigned long long* tiles, int pair, int floor, hipStream_t s)
 {
     if (n_work <= 0) return hipSuccess;
-    if (!mx_cull_takes(nct, 0, a_cap)) return hipErrorInvalidValue;
+    if (!mx_cull_takes(nct, 0, a_cap) || (runs && n_runs <= 0)) return hipErrorInvalidValue;
+    if (!runs) n_runs = 0;
     const WorkItem* w = b.work + work_begin;
-#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, a_cap, tiles, pair, floor, s);
+#define MM_MXC(N) case N: return launch_mx_cull_t<N>(b, w, n_work, runs, n_runs, a_cap, tiles, pair, floor, s);
     switch (nct) {
         MM_MXC(2) MM_MXC(3) MM_MXC(4) MM_MXC(5) MM_MXC(6) MM_MXC(7) MM_MXC(8) MM_MXC(9) MM_MXC(10) MM_MXC(11) MM_MXC(12)
         MM_MXC(13) MM_MXC(14) MM_MXC(15) MM_MXC(16) MM_MXC(17)

@@ -301,12 +301,16 @@ int Planner::choose_screens()
     return MM_OK;
 }
 
-// ---- work decomposition: one workgroup = `apb` consecutive candidates of one pair ----
-// With the matrix-pipe screen more of them: a work item stages the pair's rows once (global loads, two barriers:
-// ~3 us, with one other workgroup on the CU to hide it) and a 17 x 17-tile candidate takes a wave 10 us, a 7 x 7 one 1.8.
-// A wave should see ~2300 tiles per item (17 x 17 tiles: 8 candidates, 32 per workgroup; small sets up to 16 per wave) as
-// far as the batch has candidates for 24 workgroups per CU: config3's launch 16.19 ms at 578 tiles, 16.00 at 1156,
-// 15.83 at 2312, 15.77 at 4624 (tools/exp_apb.sh).
+// ---- work decomposition: one work item = `apb` consecutive candidates of one pair ----
+// With the matrix-pipe screen more of them: a work item of the FULL kernel (k_screen_mx) stages the pair's rows once (global
+// loads, two barriers: ~3 us, with one other workgroup on the CU to hide it) and a 17 x 17-tile candidate takes a wave
+// 10 us, a 7 x 7 one 1.8.  A wave should see ~2300 tiles per item (17 x 17 tiles: 8 candidates, 32 per workgroup; small sets
+// up to 16 per wave) as far as the batch has candidates for 24 workgroups per CU: config3's launch 16.19 ms at 578 tiles,
+// 16.00 at 1156, 15.83 at 2312, 15.77 at 4624 (tools/exp_apb.sh, on the full kernel).
+// The CULLED kernel keeps the item size (the groups of eight candidates and the waves' shares hang on it) but computes
+// 40.45 of the 289 tiles of such a candidate: a wave sees ~320 tiles per item, and the item's prologue -- rows, target points,
+// norms and 34 bounding circles, each circle by one thread -- is larger than the full kernel's.  That is paid per RUN of
+// items instead (plan_runs below): a workgroup keeps its pair for up to five items of config3's launch.
 int Planner::apb_of(int p) const
 {
     if (screen[(size_t)p].screen != Screen::Matrix) return apb;
@@ -400,6 +404,7 @@ void Planner::form_launch_groups()
 {
     const int P = lp.P;
     lp.groups.clear();
+    lp.host_runs.clear();
     if (lp.precision == MM_PRECISION_F64 || lp.use_lb) return;
     for (int q = 0; q < P;) {
         const PairScreen c = screen[(size_t)order[(size_t)q]];
@@ -421,6 +426,11 @@ void Planner::form_launch_groups()
                 d.ref_main = mm_tile_split_main(d.n_ref, set_main[(size_t)pairs[p].ref_set]);
                 d.tgt_main = mm_tile_split_main(d.n_tgt, set_main[(size_t)pairs[p].tgt_set]);
             }
+        // the culled screen's runs: a workgroup keeps its pair for consecutive items (plan_runs)
+        if (g.screen == Screen::MatrixCull && g.work_count > 0) {
+            g.run_begin = (int)lp.host_runs.size();
+            g.run_count = plan_runs(lp.host_work.data() + g.work_begin, g.work_count, lp.opts.screen_run, lp.host_runs);
+        }
         if (g.work_count > 0) lp.groups.push_back(g);
         q = q1;
     }
@@ -464,6 +474,7 @@ void Planner::lay_out()
     l.work_lb = take((size_t)lp.W_lb * sizeof(WorkItem));
     l.cos32 = take(T * 4); l.sin32 = take(T * 4);
     l.cos64 = take(T * 8); l.sin64 = take(T * 8); l.ang64 = take(T * 8);
+    l.runs = lp.host_runs.empty() ? 0 : take(lp.host_runs.size() * sizeof(WorkRun));
     l.lvl_in_bytes = o;
     l.sq32 = take(A * 4); l.sq64 = take(A * 8); l.flag = take(A);
     l.items = take(A * sizeof(WorkItem)); l.n_items = take(32);
@@ -484,6 +495,22 @@ void Planner::lay_out()
 }
 
 }  // namespace
+
+int plan_runs(const WorkItem* w, int n, int run, std::vector<WorkRun>& out)
+{
+    if (run == 1 || run < 0 || n <= 0) return 0;
+    const int cap = run ? run : n / (kRunMinRounds * kRunResidentWgs);
+    if (cap < 2) return 0;
+    const size_t before = out.size();
+    for (int i = 0; i < n;) {
+        const int want = run ? cap : std::min(cap, std::max(1, (n - i + 2 * kRunResidentWgs - 1) / (2 * kRunResidentWgs)));
+        int e = i + 1;
+        while (e < n && e - i < want && w[e].pair == w[i].pair) ++e;
+        out.push_back(WorkRun{i, e - i});
+        i = e;
+    }
+    return (int)(out.size() - before);
+}
 
 int plan_level(const std::vector<int32_t>& set_off, const std::vector<int32_t>& set_len, const std::vector<double>& set_rho,
                const std::vector<int32_t>& set_main, const std::vector<PairSpec>& pairs, int precision, int32_t angle_begin,

@@ -35,7 +35,16 @@ struct ScreenOptions {
     bool screen_floor = true;               // k_screen_mx_cull (set-bit variant): the value floor -- phase 2 only for rows and
                                             // columns whose phase-1 minimum lies above the largest minimum that is already
                                             // exact.  A launch argument too: same plan, same values, fewer tiles
+    int screen_run = 0;                     // k_screen_mx_cull: consecutive work items of one pair that one workgroup runs,
+                                            // staging the pair once (LevelPlan::host_runs).  0: chosen per launch group
+                                            // (plan_runs: none below kRunMinRounds rounds of workgroups); 1: off, a
+                                            // workgroup per item; n > 1: forced, up to the pair's items
 };
+
+// The run rule's constants (plan_runs): the workgroups of k_screen_mx_cull a device holds at once (256 CUs, two each), and
+// the rounds of them a launch must keep for its end to stay even.
+constexpr int kRunResidentWgs = 512;
+constexpr int kRunMinRounds = 16;
 
 struct PairSpec {          // one search
     int32_t ref_set, tgt_set;      // indices into the set list
@@ -55,16 +64,20 @@ enum class Screen { None, Direct, PackedFma, Matrix, MatrixCull };
 // Screens without bound rounds: the work list is grouped by screen, one launch per group, in the order of Screen and
 // (multi, nct, cls).  Matrix / MatrixCull: k_screen_mx<nct, multi> / k_screen_mx_cull<nct> with LDS for a_cap row tiles;
 // candidates and tiles_full (MatrixCull: the tiles the full kernel computes) feed Engine::screened / cull_tiles_full.
+// MatrixCull: [run_begin, run_begin + run_count) of LevelPlan::host_runs are the group's runs; run_count == 0: none, one
+// workgroup per work item.
 struct ScreenGroup {
     Screen screen; int nct, multi, a_cap, work_begin, work_count;
     int64_t candidates, tiles_full;
+    int run_begin = 0, run_count = 0;
 };
 
 // Byte offsets of the level blob's regions, in the order they lie: steps of 256 bytes, and an empty region still takes 16
 // bytes and an offset of its own.  [pairs .. ang64] are the inputs (one upload of lvl_in_bytes), [best_cost .. near_idx] the
 // result block (one copy back of res_bytes from off_best_cost; the r_* are offsets inside it), all_costs is optional.
+// runs (LevelPlan::host_runs) is optional too and the last of the inputs: a level without a run table has no such region.
 struct LevelLayout {
-    size_t pairs = 0, work = 0, work_lb = 0, cos32 = 0, sin32 = 0, cos64 = 0, sin64 = 0, ang64 = 0;
+    size_t pairs = 0, work = 0, work_lb = 0, cos32 = 0, sin32 = 0, cos64 = 0, sin64 = 0, ang64 = 0, runs = 0;
     size_t sq32 = 0, sq64 = 0, flag = 0, items = 0, n_items = 0;
     size_t lb32 = 0, pick = 0, items_pick = 0, items_lb = 0, klist = 0, emit = 0, qlist = 0;
     size_t best_cost = 0, best_idx = 0, n_rescored = 0, near_cnt = 0, near_idx = 0;
@@ -94,6 +107,7 @@ struct LevelPlan {
     ScreenOptions opts;                       // the switches this level was planned with
     std::vector<PairDesc> host_pairs;
     std::vector<WorkItem> host_work, host_work_lb;
+    std::vector<WorkRun> host_runs;           // the culled launch groups' runs (ScreenGroup::run_begin), group by group
     std::vector<double> host_tables;          // distinct candidate lists (slice-local), dev tables mirror them
     std::vector<uint8_t> trivial;             // pair has an empty set: every cost is 0.0
     std::vector<int32_t> pair_slice_end;      // per pair: end of the candidate slice this plan owns
@@ -108,6 +122,15 @@ struct LevelPlan {
 int plan_level(const std::vector<int32_t>& set_off, const std::vector<int32_t>& set_len, const std::vector<double>& set_rho,
                const std::vector<int32_t>& set_main, const std::vector<PairSpec>& pairs, int precision, int32_t angle_begin,
                int32_t angle_end, bool want_costs, const ScreenOptions& opts, LevelPlan& out);
+
+// The runs of one culled launch group's work items w[0 .. n) (ScreenOptions::screen_run = run), appended to `out`: every
+// item in exactly one run, in list order, and no run holds items of two pairs.  run > 1: runs of `run` items, as far as
+// the pair has items.  run == 0: nothing for a launch of fewer than 2 kRunMinRounds rounds; else guided sizes -- with
+// R = n / (kRunMinRounds kRunResidentWgs), the run at item i takes ceil((n - i) / (2 kRunResidentWgs)) items, at least 1
+// and at most R, and never more than its pair has left: the launch keeps kRunMinRounds rounds of workgroups, the sizes
+// only fall along the list (but for a run cut short by its pair's end) and the last kRunResidentWgs workgroups' worth
+// of items run one by one, as without runs.  Returns the number of runs appended (0: no table, a workgroup per item).
+int plan_runs(const WorkItem* w, int n, int run, std::vector<WorkRun>& out);
 
 // The plan as 64-bit words, seven arrays each preceded by its length (doubles by bit pattern); the order is written down at
 // mm_level_plan_probe (include/mm_hausdorff.h).

@@ -46,6 +46,12 @@ struct WorkItem {
     int32_t pair, a0, cnt, pad;   // pad: the bound kernels' candidate step; k_screen_mx_cull: candidates per group (0: 1)
 };
 
+// k_screen_mx_cull: one workgroup's RUN of work items -- `count` consecutive items of one pair, the first at `first` of its
+// launch group's items (the planner's run table, mm_level_plan.h): the workgroup stages the pair once for all of them.
+struct WorkRun {
+    int32_t first, count;
+};
+
 static constexpr int kMaxNear = 8;  // near-tie slots per pair (MM_MAX_NEAR)
 
 struct BatchDev {

@@ -17,12 +17,22 @@ how often the section runs per candidate:
     gnrt     `nrt`, per group           lead     once per leader (a group's first candidate; the value floor's sections: flr_tr
              and flr_tc_row, Tr_I / Tc_J of the group's phase-1 mask, and flr_lead, the leader's floor L)
     fgroup   once per group that has followers (1 / G per candidate, none at G = 1)     fgnrt    `nrt`, per such group
+    fghalf   `half`, per such group
     fol      once per follower of a group ((G - 1) / G per candidate)        frows    `nrt`, per follower
     lrows    `nrt`, per leader (a group's first candidate: 1 / G per candidate)
     early    once per follower that leaves after phase 1 on the group test (--early: their share of the followers, from
              tools/model_cull_tiles.py --group G)
     late     once per candidate that does not leave early (1 - early (G - 1) / G)
     0        not in the candidate loop
+
+The prologue in front of the candidate loop is charged per candidate too, from --run-items and --item-cands:
+
+    item     once per work item (pro_item: the item's WorkItem, its candidates' cos / sin, the barriers):
+             1 / --item-cands per candidate
+    run      once per run of --run-items work items that one workgroup executes (pro_run: the pair's row fragments, target
+             points, norms and circles, staged at the run's first item): 1 / (--run-items x --item-cands) per candidate.  A
+             workgroup per item is --run-items 1.  The section's loops (a tile's circle is two serial loops over 32 points,
+             mx_stage_rows one over the row tiles) count once: the static figure is a floor of what a run executes
 
 Pairs (--pair, default on, the set-bit variant at G >= 4): a group's followers run two at a time, P = (G - 2) // 2 pairs a group,
 so 2 P / G of the candidates are paired, (G - 1 - 2 P) / G are single followers:
@@ -132,8 +142,11 @@ def sections(body):
     return secs
 
 
-def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True, tail=None):
+def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True, tail=None, run_items=1.0, item_cands=32.0,
+           unmarked="0"):
     secs = sections(body)
+    if "unmarked" in secs:
+        secs["unmarked"]["trips"] = unmarked
     copies = max(1, secs["tile"]["entries"]) if "tile" in secs else 1
     fol = (group - 1.0) / group
     fgroup = 1.0 / group if group > 1 else 0.0
@@ -141,38 +154,43 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True
     tail = (1.0 / nct if tail is None else tail) if "tilet" in secs else 0.0     # share of the computed tiles in the last column tile
     npair = max(0, (group - 2) // 2) if pair and "tile2" in secs else 0      # pairs per group: followers 1 .. 2 P
     pshare, sfol = 2.0 * npair / group, (group - 1.0 - 2 * npair) / group
-    trips = {"0": 0.0, "1": 1.0, "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
+    trips = {"0": 0.0, "1": 1.0, "item": 1.0 / item_cands, "run": 1.0 / (run_items * item_cands), "nrt": float(nrt), "half": float((nrt + 1) // 2), "rows2": float(rows2),
              "pairs64": float((nrt * nct + 63) // 64), "tiles": tiles * (1.0 - pshare) * (1.0 - tail) / copies,
              "tile": tiles * (1.0 - pshare) * (1.0 - tail) / copies, "tails": tiles * (1.0 - pshare) * tail / tcopies,
              "ptiles": tiles * pshare * (1.0 - tail) / 2, "ptails": tiles * pshare * tail / 2, "pair": pshare / 2, "prows": nrt * pshare / 2, "xcand": 1.0 - pshare / 2,
              "single": 1.0 - pshare, "sfol": sfol, "sfrows": nrt * sfol, "searly": early * sfol, "pearly": early * pshare / 2,
              "ylate": (1.0 - early) * pshare / 2,
              "group": 1.0 / group, "ghalf": float((nrt + 1) // 2) / group, "gnrt": float(nrt) / group, "lead": 1.0 / group,
-             "fgroup": fgroup, "fgnrt": nrt * fgroup,
+             "fgroup": fgroup, "fgnrt": nrt * fgroup, "fghalf": float((nrt + 1) // 2) * fgroup,
              "fol": fol, "frows": nrt * sfol, "lrows": nrt * (1.0 - fol), "early": early * fol, "late": 1.0 - early * fol}
     out.write("k_screen_mx_cull<%d>: VGPRs %s, AGPRs %s, scratch %s bytes/lane, occupancy %s waves/SIMD\n" % (
         nct, info(inf, "NumVgprs"), info(inf, "NumAgprs"), info(inf, "ScratchSize"), info(inf, "Occupancy")))
     out.write("  trip counts: nrt %d, NCT %d, tiles/candidate %g, phase-2 row tiles %g, candidates/group %d, early share of the followers %g; tile bodies in the code: %d\n" % (
         nrt, nct, tiles, rows2, group, early, copies))
+    out.write("  prologue: %g candidates per work item, %g work items per run\n" % (item_cands, run_items))
     out.write("  %-10s %-8s %6s %6s %6s %6s %6s %6s %7s %9s\n" % ("section", "trips", "mfma", "valu", "salu", "lds", "vmem",
                                                                   "other", "static", "executed"))
-    tot_tile = tot_rest = 0.0
+    tot_tile = tot_rest = tot_pro = 0.0
     for name, s in secs.items():
         static = sum(s[c] for c in CLASSES)
         if s["trips"] not in trips:
             raise SystemExit("unknown trip count %r in mark %r" % (s["trips"], name))
         ex = static * trips[s["trips"]]
-        if name in ("tile", "tile2", "tilet", "tile2t"):
+        if s["trips"] in ("item", "run"):
+            tot_pro += ex
+        elif name in ("tile", "tile2", "tilet", "tile2t"):
             tot_tile += ex
         else:
             tot_rest += ex
-        out.write("  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.0f\n" % (name, s["trips"], s["mfma"], s["valu"], s["salu"], s["lds"],
+        out.write(("  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.1f\n" if s["trips"] in ("item", "run") else
+                   "  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.0f\n") % (name, s["trips"], s["mfma"], s["valu"], s["salu"], s["lds"],
                                                                        s["vmem"], s["other"], static, ex))
     if "tile" in secs:
         out.write("  a computed tile's body: %.1f instructions\n" % (sum(secs["tile"][c] for c in CLASSES) / copies))
     if "tile2" in secs:
         out.write("  a paired tile's body (two candidates): %.1f instructions; pairs per group %d\n" % (sum(secs["tile2"][c] for c in CLASSES), npair))
-    out.write("  executed per candidate: tiles %.0f, everything else %.0f\n\n" % (tot_tile, tot_rest))
+    out.write("  executed per candidate: tiles %.0f, everything else %.0f" % (tot_tile, tot_rest))
+    out.write("; the prologue %.1f (static, its loops counted once)\n\n" % tot_pro if tot_pro else "\n\n")
     return tot_tile, tot_rest
 
 
@@ -187,11 +205,18 @@ def main(argv=None):
     ap.add_argument("--early", type=float, default=0.0, help="share of a group's followers that leave after phase 1 (sections marked early / late)")
     ap.add_argument("--tail", type=float, default=None, help="share of the computed tiles that are the last column tile's (default 1 / NCT)")
     ap.add_argument("--pair", type=int, default=1, help="0: the pair switch off (every follower runs alone)")
+    ap.add_argument("--run-items", type=float, default=1.0, help="work items per run (sections marked run: once per run); 1: a workgroup per item")
+    ap.add_argument("--unmarked", choices=("0", "run"), default="0",
+                    help="run: charge the unmarked blocks once per run too -- most of them are blocks of the staging that lie behind a "
+                         "branch (the circles' loops, the row fragments); with the marked part, the two ends of the prologue's static cost")
+    ap.add_argument("--item-cands", type=float, default=32.0, help="candidates per work item (sections marked item and run)")
     a = ap.parse_args(argv)
     if a.group < 1:
         raise SystemExit("--group must be at least 1")
     if not 0.0 <= a.early <= 1.0:
         raise SystemExit("--early is a share, 0 .. 1")
+    if a.run_items < 1 or a.item_cands < 1:
+        raise SystemExit("--run-items and --item-cands must be at least 1")
     with open(a.asm) as f:
         ks = kernels(f.read())
     if not ks:
@@ -200,7 +225,8 @@ def main(argv=None):
         if a.nct and nct != a.nct:
             continue
         body, inf = ks[nct]
-        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group, a.early, a.pair != 0, a.tail)
+        report(nct, body, inf, a.nrt, a.tiles, a.nrt if a.rows2 is None else a.rows2, sys.stdout, a.group, a.early, a.pair != 0, a.tail,
+               a.run_items, a.item_cands, a.unmarked)
 
 
 if __name__ == "__main__":
