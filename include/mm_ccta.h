@@ -1178,11 +1178,15 @@ int     mm_isect_plan(const double* va, int64_t nva, const int64_t* fa, int64_t 
  *    point_face of a point is the face of the segment that leaves it, -1 at the far end of an open polyline.  The
  *    components of a plane are ordered by their smallest edge key.
  * 6. Measures, with p(m) = p(0) for a loop, from i = 0, every sum started at 0.0:
- *    d_i = p_i - o; c_i = d_i x d_(i+1) = (dy*ez - dz*ey, dz*ex - dx*ez, dx*ey - dy*ex) with e = d_(i+1); A += c_i;
- *    w_i = (c.x*nx + c.y*ny) + c.z*nz; W += w_i; G += w_i * (d_i + d_(i+1)) per component.
+ *    d_i = p_i - p_0, the loop's own first listed point (the same point in both directions), so that no measure depends
+ *    on where o lies in its plane; c_i = d_i x d_(i+1) = (dy*ez - dz*ey, dz*ex - dx*ez, dx*ey - dy*ex) with e = d_(i+1);
+ *    A += c_i; w_i = (c.x*nx + c.y*ny) + c.z*nz; W += w_i; G += w_i * (d_i + d_(i+1)) per component;
+ *    q_i = (|dy*ez| + |dz*ey|, |dz*ex| + |dx*ez|, |dx*ey| + |dy*ex|); B += (q.x*|nx| + q.y*|ny|) + q.z*|nz|.
  *    s = (A.x*nx + A.y*ny) + A.z*nz; area = (0.5 * s) / sqrt((nx*nx + ny*ny) + nz*nz).
  *    len_i = sqrt((ex*ex + ey*ey) + ez*ez) with e = p_(i+1) - p_i; length L += len_i; M += len_i * (0.5 * (p_i + p_(i+1))).
- *    centroid = o + G / (3.0 * W) per component, the area centroid of the fan about o; where s == 0 or W == 0 it is M / L,
+ *    A loop is flat iff not |W| > ((m + 6) * 2^-52) * B: W differs from its exact value by at most (m + 6) * 2^-53 * B
+ *    (DESIGN 4.28), so W of a loop that is not flat has its sign and is within a factor 2 of the truth.
+ *    centroid = p_0 + G / (3.0 * W) per component, the area centroid of the fan about p_0; of a flat loop it is M / L,
  *    the length-weighted mean, and p_0 where L == 0.  An open polyline (its m - 1 segments) has length L and centroid
  *    M / L (p_0 where L == 0); its area is NaN.
  * 7. Selection.  Drop the axis of the largest |n| component, the first among equals (x leaves (u, v) = (y, z), y leaves

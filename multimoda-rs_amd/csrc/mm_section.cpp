@@ -175,21 +175,27 @@ void curve_mean(const double* p, int64_t m, bool closed, double* length, double*
     for (int k = 0; k < 3; ++k) mean[k] = L == 0.0 ? p[k] : M[k] / L;
 }
 
-// rule 6 on a closed loop in its listed order: s = the vector area dotted with n
-double loop_signed(const double* p, int64_t m, const Plane& pl, double* W_out, double* G)
+// rule 6 on a closed loop in its listed order, about its own first point: s = the vector area dotted with n; B = the
+// sum of the magnitudes of every product that enters W, the scale of W's rounding error
+double loop_signed(const double* p, int64_t m, const Plane& pl, double* W_out, double* B_out, double* G)
 {
-    double A[3] = {0.0, 0.0, 0.0}, W = 0.0;
+    double A[3] = {0.0, 0.0, 0.0}, W = 0.0, B = 0.0;
+    const double an[3] = {std::fabs(pl.nx), std::fabs(pl.ny), std::fabs(pl.nz)};
     G[0] = G[1] = G[2] = 0.0;
     for (int64_t i = 0; i < m; ++i) {
         const double *a = p + 3 * i, *b = p + 3 * ((i + 1) % m);
-        const double d[3] = {a[0] - pl.ox, a[1] - pl.oy, a[2] - pl.oz}, e[3] = {b[0] - pl.ox, b[1] - pl.oy, b[2] - pl.oz};
+        const double d[3] = {a[0] - p[0], a[1] - p[1], a[2] - p[2]}, e[3] = {b[0] - p[0], b[1] - p[1], b[2] - p[2]};
         const double c[3] = {d[1] * e[2] - d[2] * e[1], d[2] * e[0] - d[0] * e[2], d[0] * e[1] - d[1] * e[0]};
         for (int k = 0; k < 3; ++k) A[k] += c[k];
         const double w = (c[0] * pl.nx + c[1] * pl.ny) + c[2] * pl.nz;
         W += w;
+        const double q[3] = {std::fabs(d[1] * e[2]) + std::fabs(d[2] * e[1]), std::fabs(d[2] * e[0]) + std::fabs(d[0] * e[2]),
+                             std::fabs(d[0] * e[1]) + std::fabs(d[1] * e[0])};
+        B += (q[0] * an[0] + q[1] * an[1]) + q[2] * an[2];
         for (int k = 0; k < 3; ++k) G[k] += w * (d[k] + e[k]);
     }
     *W_out = W;
+    *B_out = B;
     return (A[0] * pl.nx + A[1] * pl.ny) + A[2] * pl.nz;
 }
 
@@ -304,22 +310,22 @@ void chain_plane(const Segment* seg, int64_t m, const Plane& pl, int64_t plane, 
                 curve_mean(pts.data(), n, false, out.contour_length + c, cen);
                 ++out.n_open;
             } else {
-                double W, G[3];
-                double sgn = loop_signed(pts.data(), n, pl, &W, G);
+                double W, B, G[3];
+                double sgn = loop_signed(pts.data(), n, pl, &W, &B, G);
                 if (sgn < 0.0) {                                       // the other direction: p0, p(n-1), ..., p1
                     std::reverse(walk_key.begin() + 1, walk_key.end());
                     std::reverse(walk_seg.begin(), walk_seg.end());
                     for (int64_t i = 0; i < n; ++i) std::memcpy(pts.data() + 3 * i, key_point(walk_key[(size_t)i]), 24);
-                    sgn = loop_signed(pts.data(), n, pl, &W, G);
+                    sgn = loop_signed(pts.data(), n, pl, &W, &B, G);
                 }
                 for (int64_t i = 0; i < n; ++i) emit(walk_key[(size_t)i], (int64_t)(seg[walk_seg[(size_t)i]].key & 0xffffffffull));
                 out.contour_kind[c] = 0;
                 out.contour_area[c] = (0.5 * sgn) / std::sqrt((pl.nx * pl.nx + pl.ny * pl.ny) + pl.nz * pl.nz);
                 double mean[3];
                 curve_mean(pts.data(), n, true, out.contour_length + c, mean);
-                const double o[3] = {pl.ox, pl.oy, pl.oz};
-                const bool flat = sgn == 0.0 || W == 0.0;
-                for (int a = 0; a < 3; ++a) cen[a] = flat ? mean[a] : o[a] + G[a] / (3.0 * W);
+                // flat: |W| within twice the rounding bound of its own sum
+                const bool flat = !(std::fabs(W) > ((double)(n + 6) * std::numeric_limits<double>::epsilon()) * B);
+                for (int a = 0; a < 3; ++a) cen[a] = flat ? mean[a] : pts[(size_t)a] + G[a] / (3.0 * W);
                 ++out.n_closed;
             }
         }

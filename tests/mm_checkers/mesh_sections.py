@@ -86,9 +86,14 @@ def curve_mean(pts, closed):
     return L, [pts[0][k] if L == 0.0 else M[k] / L for k in range(3)]
 
 
-def loop_signed(pts, o, n):
-    A, G, W = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], 0.0
+EPS = 2.0 ** -52
+
+
+def loop_signed(pts, n):
+    """s, W, B, G of a closed loop in its listed order, about its own first point"""
+    A, G, W, B = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], 0.0, 0.0
     m = len(pts)
+    o = pts[0]
     for i in range(m):
         a, b = pts[i], pts[(i + 1) % m]
         d = [a[k] - o[k] for k in range(3)]
@@ -98,9 +103,15 @@ def loop_signed(pts, o, n):
             A[k] += c[k]
         w = (c[0] * n[0] + c[1] * n[1]) + c[2] * n[2]
         W += w
+        q = [abs(d[1] * e[2]) + abs(d[2] * e[1]), abs(d[2] * e[0]) + abs(d[0] * e[2]), abs(d[0] * e[1]) + abs(d[1] * e[0])]
+        B += (q[0] * abs(n[0]) + q[1] * abs(n[1])) + q[2] * abs(n[2])
         for k in range(3):
             G[k] += w * (d[k] + e[k])
-    return (A[0] * n[0] + A[1] * n[1]) + A[2] * n[2], W, G
+    return (A[0] * n[0] + A[1] * n[1]) + A[2] * n[2], W, B, G
+
+
+def loop_flat(m, W, B):
+    return not abs(W) > (float(m + 6) * EPS) * B
 
 
 # ---- rule 7 ---------------------------------------------------------------------------------------------------------
@@ -185,15 +196,15 @@ def chain_plane(segs, o, n):
             contours.append(dict(kind=OPEN, keys=wk, faces=[segs[x][1] for x in ws] + [-1], points=pts, area=NAN, length=L,
                                  centroid=mean))
             continue
-        sgn, W, G = loop_signed(pts, o, n)
+        sgn, W, B, G = loop_signed(pts, n)
         if sgn < 0.0:
             wk = wk[:1] + wk[1:][::-1]
             ws = ws[::-1]
             pts = [point[k] for k in wk]
-            sgn, W, G = loop_signed(pts, o, n)
+            sgn, W, B, G = loop_signed(pts, n)
         L, mean = curve_mean(pts, True)
-        flat = sgn == 0.0 or W == 0.0
-        cen = [mean[k] if flat else o[k] + G[k] / (3.0 * W) for k in range(3)]
+        flat = loop_flat(len(pts), W, B)
+        cen = [mean[k] if flat else pts[0][k] + G[k] / (3.0 * W) for k in range(3)]
         area = (0.5 * sgn) / math.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
         contours.append(dict(kind=CLOSED, keys=wk, faces=[segs[x][1] for x in ws], points=pts, area=area, length=L, centroid=cen))
     best = -1
