@@ -1249,6 +1249,115 @@ int     mm_section_chain(const void* segments, int64_t n_segments, const double*
                          int64_t* contour_plane, int8_t* contour_kind, double* contour_area, double* contour_length,
                          double* contour_centroid, int64_t* plane_off, int64_t* selected, int64_t* counts);
 
+/* ---- mesh clipping (no counterpart in the reference, whose paper names "patient-specific CFD and FSI simulations" as
+ *      the first use of its surface: a solver wants flat inlets and outlets) ------------------------------------------
+ * A mesh cut open along plane sections: the crossed faces are split along a section's loop, one side of the loop is
+ * thrown away by connectivity, the rim is left open, capped, or extended by a straight piece, and every face says which
+ * patch it belongs to.  tests/mm_checkers/mesh_clip.py is the executable form of the rule; csrc/mm_clip_device.h is the
+ * C++ text of C4's per-face step, csrc/mm_clip.cpp that of C1, C5 and C6, csrc/mm_clip_kernels.hip that of C2, C4, C7.
+ *
+ * Inputs: v f64[nv,3], f int64[nf,3] and K cuts, each an origin o, a normal n (need not be unit), keep in {BELOW (the
+ * side h < 0 stays), ABOVE (h >= 0 stays)} and scope in {LOOP, PLANE}; cap (0/1), ext_length >= 0 and ext_layers >= 0
+ * (both zero: no extension).  All arithmetic is unfused f64 in the order written.  Heights, sides, crossing points,
+ * chaining, measures and selection are rules 1-7 of "mesh cross-sections", unchanged.
+ *
+ * C1. Cut set.  The sections of the K planes are taken.  LOOP: the faces of the segments of selected[k], the smallest
+ *     closed loop around o; no such loop, or one of fewer than 3 points: status NO_LOOP.  PLANE: every crossed face of
+ *     plane k (rules 1 and 2); its loop points are those of every contour of the plane.  A face in the cut sets of two
+ *     cuts gives both status OVERLAP.  The measures reported for a cut are those of its first closed loop in contour order
+ *     (LOOP: the selected one), NaN without one.  Where C1 leaves a status other than OK, C2 is not run.
+ * C2. Connectivity.  A union-find over the vertex indices: a face in no cut set unites its three vertices, a face in a
+ *     cut set only the two on the same side of its plane.  For every cut face of a LOOP cut the root of its apex (C4) is
+ *     compared with the root of the next corner, one on the kept and one on the drop side: equal, the cut is
+ *     NOT_SEPARATING; otherwise the drop-side root is marked.  A vertex is dropped iff its root is marked or it lies on
+ *     the drop side of a PLANE cut.  Only root equality and the marks are used, never which member is the root.
+ * C3. All or nothing.  If any status is not OK nothing is cut: the outputs are the input mesh with identity maps,
+ *     n_applied = 0, no rims, and the statuses and measures are reported.
+ * C4. Pieces.  A face in no cut set is kept iff none of its vertices is dropped.  A cut face (c0, c1, c2) is rotated,
+ *     winding preserved, to (a, b, c) with a, the apex, the vertex alone on its side (a = c2 if side(c0) == side(c1), c1
+ *     if side(c0) == side(c2), else c0).  m_ab and m_ca are the loop points on the edges (a, b) and (c, a): the section's
+ *     points, same bits.  Pieces, in this order: the apex piece (a, m_ab, m_ca); then the quad m_ab, b, c, m_ca cut by
+ *     its shorter diagonal, with d2(p, q) = ((dx*dx + dy*dy) + dz*dz): if d2(m_ab, c) < d2(b, m_ca): (m_ab, b, c),
+ *     (m_ab, c, m_ca); otherwise, ties included: (m_ab, b, m_ca), (b, c, m_ca).  A piece is kept iff none of its old
+ *     vertices is dropped.  A piece with two corners of equal coordinates is emitted and counted (n_null_pieces): a vertex
+ *     on a plane counts as above it, so such pieces are legitimate; mm_mesh_repair removes them.
+ * C5. Vertices, in this order: the kept old vertices, bits and relative order unchanged; then per cut, in cut order, its
+ *     loop points in the section's listing order (every contour of its cut set, in contour order), then rings
+ *     1..ext_layers, each the points of the cut's closed loops in that order, then, with cap, one centre per closed
+ *     loop.  vertex_origin is the old index, or -1 - k for a vertex made for cut k.
+ * C6. Extension and cap, for every closed loop of every applied cut; open and branched contours of a PLANE cut stay open
+ *     and are counted (n_open_loops).  u = n / sqrt((nx*nx + ny*ny) + nz*nz) per component; sgn = +1 where the dropped
+ *     side is above (keep BELOW), else -1; step = ext_length / ext_layers.  The point of ring j is
+ *     p + (sgn * (j * step)) * u per component.  The centre is the loop's rule-6 centroid shifted the same way by
+ *     ext_layers * step; without an extension it is the centroid's bits.  For rim edge i (p_i, p_(i+1); the segment of
+ *     point_face[i]) the kept side of that face runs along the edge x -> y: m_ab -> m_ca where the apex is kept, m_ca ->
+ *     m_ab otherwise.  Faces: per layer j = 0..ext_layers-1 (ring 0 = the rim) (y_j, x_j, x_(j+1)) and
+ *     (y_j, x_(j+1), y_(j+1)); the cap face (y_L, x_L, centre) with L = ext_layers.  The orientation follows the adjacent
+ *     piece edge by edge and assumes no oriented mesh.
+ * C7. Faces, in this order: the kept faces and pieces in parent order (a face's pieces in C4's order); per cut its
+ *     extension faces, layer-major, in rim order (loop after loop, edge i after edge i - 1); per cut its cap faces in
+ *     rim order.  face_origin is the parent face, or -1 - k; face_kind 0 untouched, 1 piece, 2 extension, 3 cap.
+ * C8. Report: mm_clip_report, and per cut status, loop points, closed loops, cut faces (cut_status, 4 int64 a cut) and
+ *     area, perimeter, centroid (cut_measures, 5 doubles a cut).
+ *
+ * Launches of the clip's own device pass (the section pass before it is mm_mesh_sections'): none without a cut, without
+ * a vertex or with a status C1 set; otherwise 5 + R (initialise, scatter, sides, unions, R pointer-jumping rounds
+ * including the one that changes nothing, verdict), and where the cuts are applied 11 more (keep flags, 3 of their scan,
+ * piece counts, 3 of their scan -- none on a mesh without faces: 8 --, vertices, faces, rim faces). */
+
+#define MM_CLIP_KEEP_BELOW 0
+#define MM_CLIP_KEEP_ABOVE 1
+#define MM_CLIP_SCOPE_LOOP  0
+#define MM_CLIP_SCOPE_PLANE 1
+#define MM_CLIP_OK             0
+#define MM_CLIP_NO_LOOP        1
+#define MM_CLIP_OVERLAP        2
+#define MM_CLIP_NOT_SEPARATING 3
+#define MM_CLIP_KIND_UNTOUCHED 0
+#define MM_CLIP_KIND_PIECE     1
+#define MM_CLIP_KIND_EXTENSION 2
+#define MM_CLIP_KIND_CAP       3
+
+typedef struct mm_clip_report {
+    int64_t n_cuts, n_applied;    /* n_applied: n_cuts where every status is OK, else 0 */
+    int64_t n_vertices, n_faces;  /* of the result: the capacities needed where the call returns MM_ERR_TOO_LARGE */
+    int64_t n_new_vertices;       /* loop points, ring points and centres */
+    int64_t n_dropped_vertices;
+    int64_t n_dropped_faces;      /* input faces of which nothing is left */
+    int64_t n_cut_faces;
+    int64_t n_pieces, n_null_pieces;
+    int64_t n_ext_faces, n_cap_faces;
+    int64_t n_closed_loops;       /* the rims */
+    int64_t n_open_loops;         /* open and branched contours of PLANE cuts: left as they are */
+    int64_t jump_rounds;          /* R */
+    int64_t n_launches, bytes_uploaded, bytes_downloaded;   /* of the clip's own device pass */
+} mm_clip_report;                 /* 144 bytes */
+
+/* keep and scope: n_cuts int32 each.  out_vertices (3 doubles) and vertex_origin hold vert_cap entries, out_tris (3
+ * int64), face_origin and face_kind face_cap; rim_off holds vert_cap + 1 entries and rim_index vert_cap: rim r, the
+ * outermost ring of closed loop r (cut after cut, loop after loop), is rim_index[rim_off[r] .. rim_off[r + 1]), vertex
+ * indices of the result in loop order; n_closed_loops of them.  cut_status: 4 int64 a cut, cut_measures: 5 doubles a
+ * cut (C8).  Capacities as mm_mesh_refine: too small, report->n_vertices and n_faces hold the sizes needed, nothing else
+ * is written and the call returns MM_ERR_TOO_LARGE.  An empty mesh and zero cuts are valid.  MM_ERR_INVALID, before the
+ * engine's buffers are touched: a non-finite coordinate or origin, a zero or non-finite normal, a face index out of
+ * range, a keep, scope or cap outside its values, a negative or non-finite ext_length, ext_layers < 0 (or above 2^20),
+ * exactly one of ext_length and ext_layers zero, a size of 2^31 or more.  int32 indices on the device: a result of 2^31
+ * or more vertices or faces is MM_ERR_TOO_LARGE. */
+int     mm_mesh_clip(mm_engine* e, const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf,
+                     const double* origins, const double* normals, const int32_t* keep, const int32_t* scope, int64_t n_cuts,
+                     int32_t cap, double ext_length, int64_t ext_layers, int64_t vert_cap, int64_t face_cap,
+                     double* out_vertices, int64_t* out_tris, int64_t* vertex_origin, int64_t* face_origin, int8_t* face_kind,
+                     int64_t* cut_status, double* cut_measures, int64_t* rim_off, int64_t* rim_index, mm_clip_report* report);
+/* TEST HOOK (nothing in the product calls it; no engine, no device): the same rule in host C++ -- the sections by
+ * mm_section_cut_host and mm_section_chain, a sequential union-find, csrc/mm_clip_device.h for the pieces.  jump_rounds,
+ * n_launches and the byte counts stay 0. */
+int     mm_mesh_clip_host(const double* vertices_xyz, int64_t nv, const int64_t* tris, int64_t nf, const double* origins,
+                          const double* normals, const int32_t* keep, const int32_t* scope, int64_t n_cuts, int32_t cap,
+                          double ext_length, int64_t ext_layers, int64_t vert_cap, int64_t face_cap, double* out_vertices,
+                          int64_t* out_tris, int64_t* vertex_origin, int64_t* face_origin, int8_t* face_kind,
+                          int64_t* cut_status, double* cut_measures, int64_t* rim_off, int64_t* rim_index,
+                          mm_clip_report* report);
+
 /* ---- winding number (no counterpart in the reference, whose roadmap lists "write a more stable function to find
  *      intramural points on aorta" and "intramural length etc. from the CCTA mesh" as open) -----------------------------
  * The generalized winding number (Jacobson et al. 2013) of a triangle mesh at query points,

@@ -48,6 +48,8 @@ from . import intersect
 from .intersect import MeshIntersections, mesh_intersections, mesh_self_intersections
 from . import section
 from .section import MeshCrossSections, VesselProfile, centerline_cross_sections, mesh_cross_sections, vessel_profile
+from . import clip
+from .clip import ClipError, ClippedMesh, clip_mesh, open_vessel_ends, vessel_end_stations
 from . import winding
 from .winding import (ContainmentReport, IntramuralCourse, IntramuralPoints, SignedPointMeshDistance, WindingNumber,
                       intramural_course, intramural_points, mesh_containment, mesh_winding_number, points_in_mesh,
@@ -99,6 +101,7 @@ __all__ = [
     "DirectedDistance", "SurfaceDistanceReport",
     "intersect", "mesh_self_intersections", "mesh_intersections", "MeshIntersections",
     "section", "mesh_cross_sections", "centerline_cross_sections", "vessel_profile", "MeshCrossSections", "VesselProfile",
+    "clip", "clip_mesh", "open_vessel_ends", "vessel_end_stations", "ClippedMesh", "ClipError",
     "winding", "mesh_winding_number", "points_in_mesh", "signed_point_mesh_distance", "mesh_containment",
     "intramural_points", "intramural_course", "WindingNumber", "SignedPointMeshDistance", "ContainmentReport",
     "IntramuralPoints", "IntramuralCourse",

@@ -124,6 +124,7 @@ EXPORTS_CCTA = [
     "mm_mesh_valence", "mm_mesh_flip_edges", "mm_mesh_collapse_edges", "mm_mesh_repair",
     "mm_mesh_intersections", "mm_isect_plan",
     "mm_mesh_sections", "mm_section_plan", "mm_section_cut_host", "mm_section_chain",
+    "mm_mesh_clip", "mm_mesh_clip_host",
     "mm_mesh_winding", "mm_winding_result", "mm_winding_plan", "mm_winding_fold_host",
     "mm_bspline_fit_closed_batch", "mm_bspline_max_points",
 ]
@@ -168,6 +169,14 @@ class MMSurfaceReport(C.Structure):
     """``mm_surface_report`` (include/mm_ccta.h)."""
     _fields_ = [(name, C.c_int64) for name in (
         "items_pass_a", "items_pass_b", "items_skipped", "n_launches", "bytes_uploaded", "bytes_downloaded")]
+
+
+class MMClipReport(C.Structure):
+    """``mm_clip_report`` (include/mm_ccta.h)."""
+    _fields_ = [(name, C.c_int64) for name in (
+        "n_cuts", "n_applied", "n_vertices", "n_faces", "n_new_vertices", "n_dropped_vertices", "n_dropped_faces",
+        "n_cut_faces", "n_pieces", "n_null_pieces", "n_ext_faces", "n_cap_faces", "n_closed_loops", "n_open_loops",
+        "jump_rounds", "n_launches", "bytes_uploaded", "bytes_downloaded")]
 
 
 class MMSectionReport(C.Structure):
@@ -729,6 +738,11 @@ def lib():
     L.mm_section_cut_host.argtypes = [P, I64, P, I64, P, P, I64, I64, P, P]
     L.mm_section_chain.restype = I
     L.mm_section_chain.argtypes = [P, I64, P, P, I64, P, P, P, P, P, P, P, P, P, P, P, P]
+    clip_tail = [P, P, P, P, I64, C.c_int32, C.c_double, I64, I64, I64, P, P, P, P, P, P, P, P, P, C.POINTER(MMClipReport)]
+    L.mm_mesh_clip.restype = I
+    L.mm_mesh_clip.argtypes = [P, P, I64, P, I64] + clip_tail
+    L.mm_mesh_clip_host.restype = I
+    L.mm_mesh_clip_host.argtypes = [P, I64, P, I64] + clip_tail
     L.mm_mesh_winding.restype = I
     L.mm_mesh_winding.argtypes = [P, P, I64, P, I64, P, I64, P, P, P, P, C.POINTER(MMWindingReport)]
     L.mm_winding_result.restype = I

@@ -29,11 +29,11 @@ SOURCES = ["mm_kernels.hip", "mm_nn_kernels.hip", "mm_ray_kernels.hip", "mm_slic
            "mm_flip_kernels.hip", "mm_flip.cpp", "mm_collapse_kernels.hip", "mm_collapse.cpp",
            "mm_repair_kernels.hip", "mm_repair.cpp", "mm_geodesic_kernels.hip", "mm_geodesic.cpp",
            "mm_intersect_kernels.hip", "mm_intersect.cpp", "mm_section_kernels.hip", "mm_section.cpp",
-           "mm_winding_kernels.hip", "mm_winding.cpp"]
+           "mm_winding_kernels.hip", "mm_winding.cpp", "mm_clip_kernels.hip", "mm_clip.cpp"]
 HEADERS = ["mm_device.h", "mm_engine.h", "mm_level_plan.h", "mm_search_records.h", "mm_screen_limits.h", "mm_pool.h", "mm_sort.h", "mm_trace.h", "mm_screen_mx_asm.inc", "mm_tile_bound.h",
            "mm_adjacency.h", "mm_stage.h", "mm_mesh_layout.h", "mm_mesh_device.h", "mm_xcd.h", "mm_bspline_fit.h", "mm_point_records.h",
            "mm_point_device.h", "mm_prune.h", "mm_prune_device.h", "mm_tri_plan.h", "mm_tri_device.h",
-           "mm_isect_device.h", "mm_section_device.h", "mm_winding_device.h"]
+           "mm_isect_device.h", "mm_section_device.h", "mm_winding_device.h", "mm_clip_device.h"]
 PUBLIC_HEADERS = ["mm_hausdorff.h", "mm_centerline.h", "mm_ccta.h", "mm_build.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]

@@ -1,8 +1,8 @@
 // mm_mesh_device.h -- what the CCTA mesh kernel files (mm_trim, mm_weld, mm_close, mm_smooth, mm_rim, mm_refine, mm_relax,
-// mm_flip, mm_collapse, mm_repair, mm_geodesic _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim, refine, flip, collapse and repair files
+// mm_flip, mm_collapse, mm_repair, mm_geodesic, mm_clip _kernels.hip) share, the device-side counterpart of mm_stage.h: the launch geometry, the 64-bit edge table (the weld, trim, refine, flip, collapse and repair files
 // insert, the close, smooth, flip, collapse and geodesic files read, EdgeTable of mm_stage.h sizes it) with the insert
 // kernel and the clear the flips and the collapse share, the first-index-wins table and the hooking union-find of the
-// weld and the repair, the workgroup scan and the two per-wave ballot idioms.  Header-only; internal.
+// weld, the repair and the clip, the workgroup scan and the two per-wave ballot idioms.  Header-only; internal.
 #pragma once
 
 #include <hip/hip_runtime.h>

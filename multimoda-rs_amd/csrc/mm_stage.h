@@ -1,6 +1,6 @@
 // mm_stage.h -- what the CCTA host files (mm_ccta, mm_shape, mm_branch, mm_discretize, mm_bspline, mm_trim, mm_stitch,
 // mm_close, mm_rim, mm_smooth, mm_relax, mm_refine, mm_flip, mm_collapse, mm_surface, mm_repair, mm_geodesic, mm_intersect,
-// mm_section .cpp) share when they stage points or a mesh on the engine's grow-only buffers: the engine behind the
+// mm_section, mm_clip .cpp) share when they stage points or a mesh on the engine's grow-only buffers: the engine behind the
 // handle, 256-byte carving (typed: one statement a buffer), the staged pass of the point kernels, the mesh argument
 // check, the face checks and the int64 <-> int32 face copies, the mesh upload, a counter block's read, the edge table's
 // layout, a compaction's counts, the winding stage.  The scratch layouts of the mesh passes are in mm_mesh_layout.h.

@@ -1,0 +1,201 @@
+"""Mesh clipping on the host (no GPU): the host hook mm_mesh_clip_host (the sections' hooks, a sequential union-find,
+csrc/mm_clip_device.h for the pieces) against the checker (tests/mm_checkers/mesh_clip.py), every array bit for bit and
+every count; known answers on a cube, two arms, a jittered closed tube, a tube on a grid and a torus; the stations of
+open_vessel_ends; the argument checks.  The assertions that need mm.mesh_manifold_report and mm.fix_mesh_winding (both
+device passes) are in tests/test_gpu_clip.py, on the same cases; here closedness and orientation are counted in numpy."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+
+import clip_cases as CC
+from clip_cases import CASES, checked, edge_report, run
+from mm_checkers import mesh_clip as Y
+from mm_checkers import smooth_mesh as SM
+from test_section_host import tube
+
+import multimoda_rs_amd as mm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST = mm.clip.clip_mesh_host
+
+
+def test_public_names_and_abi():
+    for name in ("clip", "clip_mesh", "open_vessel_ends", "ClippedMesh", "ClipError"):
+        assert hasattr(mm, name) and name in mm.__all__
+    header = open(os.path.join(ROOT, "include", "mm_ccta.h")).read()
+    for sym in ("mm_mesh_clip", "mm_mesh_clip_host"):
+        assert f"int     {sym}(" in header and sym in mm._native.EXPORTS_CCTA and hasattr(mm._native.lib(), sym)
+    assert C.sizeof(mm._native.MMClipReport) == 144 and "} mm_clip_report;                 /* 144 bytes */" in header
+    assert [n for n, _t in mm._native.MMClipReport._fields_] == list(mm.clip.CLIP_REPORT_KEYS)
+    assert mm.clip.CLIP_REPORT_KEYS[:len(Y.COUNT_KEYS)] == Y.COUNT_KEYS
+    for name, value in (("KEEP_BELOW", Y.BELOW), ("KEEP_ABOVE", Y.ABOVE), ("SCOPE_LOOP", Y.LOOP), ("SCOPE_PLANE", Y.PLANE),
+                        ("OK", Y.OK), ("NO_LOOP", Y.NO_LOOP), ("OVERLAP", Y.OVERLAP), ("NOT_SEPARATING", Y.NOT_SEPARATING),
+                        ("KIND_UNTOUCHED", Y.UNTOUCHED), ("KIND_PIECE", Y.PIECE), ("KIND_EXTENSION", Y.EXTENSION), ("KIND_CAP", Y.CAP)):
+        assert any(line.split() == ["#define", "MM_CLIP_" + name, str(value)] for line in header.splitlines()), name
+    assert (mm.clip.KEEP, mm.clip.SCOPE) == ({"below": Y.BELOW, "above": Y.ABOVE}, {"loop": Y.LOOP, "plane": Y.PLANE})
+    assert "mesh clipping" in header and "connectivity" in mm.clip_mesh.__doc__
+
+
+def test_unit_cube_cut_in_half_and_capped():
+    got = run("cube_plane_cap", HOST)
+    assert got.cut_points.tolist() == [8] and got.cut_faces.tolist() == [8] and got.cut_loops.tolist() == [1]
+    new = got.vertices[got.vertex_origin < 0]
+    assert new.shape == (9, 3) and (new[:, 0] == 0.5).all() and new[8].tolist() == [0.5, 0.5, 0.5]
+    assert got.cut_area.tolist() == [1.0] and got.cut_length.tolist() == [4.0] and got.cut_centroid.tolist() == [[0.5, 0.5, 0.5]]
+    assert (got.vertices[:, 0] <= 0.5).all() and got.report["n_dropped_vertices"] == 4
+    assert np.bincount(got.face_kind, minlength=4).tolist() == [2, 12, 0, 8]
+    assert edge_report(got.faces) == (0, 0, 0)                             # closed, manifold, consistently oriented
+    assert abs(SM.volume(got.vertices, got.faces)) == 0.5
+    assert SM.volume(got.vertices, got.faces) == 0.5 * SM.volume(*CASES["cube_plane_cap"][:2])
+    assert [r.tolist() for r in got.rims[0]] == [list(range(4, 12))]
+
+
+def test_a_loop_cut_leaves_the_other_arm_alone_and_a_plane_cut_does_not():
+    v, f = CASES["two_arms_loop"][:2]
+    loop, plane = run("two_arms_loop", HOST), run("two_arms_plane", HOST)
+    other = np.arange(0, 50)                                               # the arm the origin is not in
+    kept = loop.vertex_origin[loop.vertex_origin >= 0]
+    assert np.isin(other, kept).all()
+    where = {int(o): i for i, o in enumerate(loop.vertex_origin) if o >= 0}
+    assert all(loop.vertices[where[int(i)]].tobytes() == v[i].tobytes() for i in other)
+    other_faces = np.nonzero((f < 50).all(axis=1))[0]
+    whole = {int(o) for o, k in zip(loop.face_origin, loop.face_kind) if k == Y.UNTOUCHED}
+    assert set(other_faces.tolist()) <= whole and loop.cut_faces.tolist() == [20] and loop.cut_loops.tolist() == [1]
+    # the plane passes through both arms
+    assert plane.cut_faces.tolist() == [40] and plane.cut_loops.tolist() == [2]
+    assert not np.isin(other, plane.vertex_origin).all() and plane.report["n_dropped_vertices"] == 2 * loop.report["n_dropped_vertices"]
+
+
+@pytest.mark.parametrize("name", ["tube_both_ends", "tube_inward"])
+def test_closed_tube_opened_extended_and_capped_at_both_ends(name):
+    got = run(name, HOST)
+    assert got.applied and edge_report(got.faces) == (0, 0, 0)             # the caps follow the mesh's orientation, either way
+    kinds = np.bincount(got.face_kind, minlength=4)
+    m = got.cut_points
+    assert kinds[Y.CAP] == m.sum() and kinds[Y.EXTENSION] == 2 * 3 * m.sum() and kinds[Y.PIECE] == got.report["n_pieces"]
+    for k in range(2):
+        assert (got.face_origin[got.face_kind == Y.CAP] == -1 - k).sum() == m[k]
+        assert (got.face_origin[got.face_kind == Y.EXTENSION] == -1 - k).sum() == 2 * 3 * m[k]
+        (rim,) = got.rims[k]
+        assert len(rim) == m[k] and (got.vertex_origin[rim] == -1 - k).all()
+        # consecutive rim vertices share a cap face; every rim vertex lies 2.0 from its loop point along the unit normal
+        caps = got.faces[(got.face_kind == Y.CAP) & (got.face_origin == -1 - k)]
+        edges = {frozenset(t[:2]) for t in caps.tolist()}
+        assert edges == {frozenset((int(rim[i]), int(rim[(i + 1) % len(rim)]))) for i in range(len(rim))}
+        n = np.asarray(CASES[name][3][k])
+        loop = got.vertices[got.vertex_origin == -1 - k][:m[k]]
+        shift = got.vertices[rim] - loop
+        assert np.allclose(shift, (1 if k == 1 else -1) * 2.0 * n / np.linalg.norm(n), atol=1e-12)
+    vol_in, vol_out = SM.volume(*CASES[name][:2]), SM.volume(got.vertices, got.faces)
+    assert vol_in * vol_out > 0 and (name == "tube_inward") == (vol_out < 0)
+
+
+def test_planes_through_vertices_leave_null_pieces_that_are_counted():
+    got = run("grid_tube", HOST)
+    assert got.applied and got.report["n_null_pieces"] == checked("grid_tube")["counts"]["n_null_pieces"] == 5
+    p = got.vertices[got.faces[got.face_kind == Y.PIECE]]
+    null = [(a == b).all() or (b == c).all() or (a == c).all() for a, b, c in p]
+    assert sum(null) == 5 and edge_report(got.faces) == (0, 0, 0)
+
+
+def test_torus():
+    v, f = CASES["torus_one_cut"][:2]
+    one = run("torus_one_cut", HOST)                                       # the loop leaves the torus in one piece
+    assert one.cut_status.tolist() == [Y.NOT_SEPARATING] and not one.applied and one.report["n_applied"] == 0
+    assert one.vertices.tobytes() == v.tobytes() and one.faces.tobytes() == f.tobytes() and one.rims == [[]]
+    assert one.vertex_origin.tolist() == list(range(len(v))) and one.face_origin.tolist() == list(range(len(f)))
+    two = run("torus_two_cuts", HOST)
+    assert two.cut_status.tolist() == [Y.OK, Y.OK] and edge_report(two.faces) == (0, 0, 0)
+    assert 0 < two.report["n_dropped_vertices"] < len(v) and (two.vertices[two.vertex_origin >= 0][:, 1] < 0.6).all()
+    assert run("torus_overlap", HOST).cut_status.tolist() == [Y.OVERLAP, Y.OVERLAP]
+    miss = run("torus_miss", HOST)
+    assert miss.cut_status.tolist() == [Y.OK, Y.NO_LOOP] and np.isnan(miss.cut_area[1]) and miss.cut_area[0] > 0
+
+
+@pytest.mark.parametrize("name", ["faces_257", "scan_tiles", "long_thin", "three_cuts", "open_tube_plane"])
+def test_hook_equals_the_checker(name):
+    got = run(name, HOST)
+    assert got.applied
+    if name == "open_tube_plane":                                         # an open contour stays open and is counted
+        assert got.report["n_open_loops"] == 1 and got.report["n_cap_faces"] == 0 and got.rims == [[]]
+    if name == "three_cuts":
+        assert got.report["n_closed_loops"] == 2 and (got.vertex_origin[got.vertex_origin >= 0] >= 50).all()
+        assert edge_report(got.faces) == (0, 0, 0)
+
+
+def test_too_small_buffers_report_the_sizes_and_write_nothing_else():
+    v, f, o, n = CASES["cube_plane_cap"][:4]
+    o, n = np.array(o, dtype=float), np.array(n, dtype=float)
+    keep, scope = np.zeros(1, dtype=np.int32), np.ones(1, dtype=np.int32)
+    rep = mm._native.MMClipReport()
+    ov, of = np.full((12, 3), 7.0), np.full((22, 3), 7, dtype=np.int64)
+    vo, fo, fk = np.zeros(12, dtype=np.int64), np.zeros(22, dtype=np.int64), np.zeros(22, dtype=np.int8)
+    st, me, ro, ri = np.zeros((1, 4), dtype=np.int64), np.zeros((1, 5)), np.zeros(13, dtype=np.int64), np.zeros(12, dtype=np.int64)
+    P = mm._native._ptr
+    rc = mm._native.lib().mm_mesh_clip_host(P(v), 8, P(f), 12, P(o), P(n), P(keep), P(scope), 1, 1, 0.0, 0, 12, 22, P(ov), P(of), P(vo),
+                                            P(fo), P(fk), P(st), P(me), P(ro), P(ri), C.byref(rep))
+    assert rc == -3 and (rep.n_vertices, rep.n_faces) == (13, 22) and (ov == 7.0).all() and (of == 7).all()
+
+
+def test_open_vessel_ends_stations_and_cuts():
+    n_rings, dx = 41, 0.25
+    v, f = tube(12, n_rings, 1.0, dx, jitter=0.01, seed=12)
+    xs = np.arange(0.0, 10.01, 0.4) + 0.013
+    cl = mm.Centerline.from_contour_points(np.stack([xs, 0 * xs, 0 * xs], 1))
+    stations, origins, normals, keep = mm.vessel_end_stations(cl, outlet_mm=1.5, inlet_mm=1.0)
+    # the rule, restated: sequential sums of sqrt((dx dx + dy dy) + dz dz)
+    arc = [0.0]
+    for a, b in zip(xs[:-1], xs[1:]):
+        d = float(b) - float(a)
+        arc.append(arc[-1] + math.sqrt((d * d + 0.0 * 0.0) + 0.0 * 0.0))
+    inlet = min(k for k in range(len(xs)) if arc[k] >= 1.0)
+    outlet = max(k for k in range(len(xs)) if arc[-1] - arc[k] >= 1.5)
+    assert stations.tolist() == [inlet, outlet] and keep == ["above", "below"]
+    assert origins.tolist() == [[float(xs[inlet]), 0.0, 0.0], [float(xs[outlet]), 0.0, 0.0]]
+    assert normals.tolist() == [[float(xs[inlet + 1]) - float(xs[inlet]), 0.0, 0.0], [float(xs[outlet + 1]) - float(xs[outlet]), 0.0, 0.0]]
+    only_out = mm.vessel_end_stations(cl, outlet_mm=0.0)
+    assert only_out[0].tolist() == [len(xs) - 1] and only_out[2].tolist() == [[float(xs[-1]) - float(xs[-2]), 0.0, 0.0]]
+    got = HOST((v, f), origins, normals, keep=keep, cap=True, extension=(1.0, 2))
+    CC.same_as_checker(got, CC.check(v, f, origins, normals, keep, "loop", True, (1.0, 2)))
+    assert got.applied and edge_report(got.faces) == (0, 0, 0)
+    with pytest.raises(ValueError, match="shorter"):
+        mm.vessel_end_stations(cl, outlet_mm=50.0)
+
+
+def test_argument_checks_come_before_the_engine():
+    v, f, o, n = CASES["cube_plane_cap"][:4]
+    bad_v, bad_f = v.copy(), f.copy()
+    bad_v[3, 1], bad_f[2, 2] = np.nan, 8
+    for args, kw, match in ((((v, f), o, [[0, 0, 0.0]]), {}, "zero"), (((v, f), o, [[0, np.inf, 1.0]]), {}, "finite"),
+                            (((v, f), [[np.nan, 0, 0]], n), {}, "finite"), (((bad_v, f), o, n), {}, "finite"),
+                            (((v, bad_f), o, n), {}, "out of range"), (((v, f), o, n), {"keep": "left"}, "keep"),
+                            (((v, f), o, n), {"scope": ["loop", "plane"]}, "scope"), (((v, f), o, n), {"extension": (-1.0, 2)}, "extension"),
+                            (((v, f), o, n), {"extension": (1.0, 0)}, "extension"), (((v, f), o, n), {"extension": (np.nan, 1)}, "extension"),
+                            (((v, f), o, n), {"extension": (0.0, 2)}, "extension")):
+        with pytest.raises(ValueError, match=match):
+            mm.clip_mesh(*args, engine=object(), **kw)                    # never reached
+    # the C entry points refuse the same before anything else
+    o, n = np.array(o, dtype=float), np.array(n, dtype=float)
+    rep = mm._native.MMClipReport()
+    P = mm._native._ptr
+    buf = [np.zeros((64, 3)), np.zeros((64, 3), dtype=np.int64), np.zeros(64, dtype=np.int64), np.zeros(64, dtype=np.int64),
+           np.zeros(64, dtype=np.int8), np.zeros((1, 4), dtype=np.int64), np.zeros((1, 5)), np.zeros(65, dtype=np.int64), np.zeros(64, dtype=np.int64)]
+    for keep, scope, cap, length, layers in ((2, 0, 0, 0.0, 0), (0, 2, 0, 0.0, 0), (0, 0, 2, 0.0, 0), (0, 0, 0, -1.0, 1), (0, 0, 0, 1.0, -1),
+                                             (0, 0, 0, 1.0, 0), (0, 0, 0, 0.0, 1), (0, 0, 0, float("inf"), 1)):
+        k, s = np.array([keep], dtype=np.int32), np.array([scope], dtype=np.int32)
+        rc = mm._native.lib().mm_mesh_clip_host(P(v), 8, P(f), 12, P(o), P(n), P(k), P(s), 1, cap, length, layers, 64, 64,
+                                                *[P(b) for b in buf], C.byref(rep))
+        assert rc == -2, (keep, scope, cap, length, layers)
+
+
+def test_empty_inputs_on_the_host():
+    v, f = CASES["cube_plane_cap"][:2]
+    got = HOST((v, f), np.zeros((0, 3)), np.zeros((0, 3)))
+    assert got.applied and got.vertices.tobytes() == v.tobytes() and got.faces.tobytes() == f.tobytes() and got.rims == []
+    got = HOST((np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64)), [[0, 0, 0.0]], [[0, 0, 1.0]])
+    assert got.cut_status.tolist() == [Y.NO_LOOP] and got.vertices.shape == (0, 3) and got.faces.shape == (0, 3)
+    got = HOST((np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64)), [[0, 0, 0.0]], [[0, 0, 1.0]], scope="plane")
+    assert got.cut_status.tolist() == [Y.OK] and got.report["n_vertices"] == 0
