@@ -1271,6 +1271,10 @@ int     mm_section_chain(const void* segments, int64_t n_segments, const double*
  *     compared with the root of the next corner, one on the kept and one on the drop side: equal, the cut is
  *     NOT_SEPARATING; otherwise the drop-side root is marked.  A vertex is dropped iff its root is marked or it lies on
  *     the drop side of a PLANE cut.  Only root equality and the marks are used, never which member is the root.
+ *     Where C2 leaves every status OK: a cut face whose kept-side old vertices (the apex where the apex is kept,
+ *     otherwise b and c) include a dropped vertex is orphaned, and its cut gets status KEPT_SIDE_DROPPED: another cut
+ *     throws away the side this one keeps, and its rim would be emitted joined to nothing.  A cut that is
+ *     NOT_SEPARATING stays so: the orphan check reads the marks only after a verdict that left every status OK.
  * C3. All or nothing.  If any status is not OK nothing is cut: the outputs are the input mesh with identity maps,
  *     n_applied = 0, no rims, and the statuses and measures are reported.
  * C4. Pieces.  A face in no cut set is kept iff none of its vertices is dropped.  A cut face (c0, c1, c2) is rotated,
@@ -1302,8 +1306,11 @@ int     mm_section_chain(const void* segments, int64_t n_segments, const double*
  *
  * Launches of the clip's own device pass (the section pass before it is mm_mesh_sections'): none without a cut, without
  * a vertex or with a status C1 set; otherwise 5 + R (initialise, scatter, sides, unions, R pointer-jumping rounds
- * including the one that changes nothing, verdict), and where the cuts are applied 11 more (keep flags, 3 of their scan,
- * piece counts, 3 of their scan -- none on a mesh without faces: 8 --, vertices, faces, rim faces). */
+ * including the one that changes nothing, verdict); where no cut is NOT_SEPARATING 1 more (the orphan check); and where
+ * the cuts are applied 11 more (keep flags, 3 of their scan, piece counts, 3 of their scan -- none on a mesh without
+ * faces: 8 --, vertices, faces, rim faces).  bytes_downloaded: 4 R + 4 K with a cut NOT_SEPARATING, otherwise 4 R + 8 K
+ * (the K status words are read once after the verdict and once after the orphan check), and where the cuts are applied
+ * 16 + 64 + 28 n_vertices + 17 n_faces more. */
 
 #define MM_CLIP_KEEP_BELOW 0
 #define MM_CLIP_KEEP_ABOVE 1
@@ -1313,6 +1320,7 @@ int     mm_section_chain(const void* segments, int64_t n_segments, const double*
 #define MM_CLIP_NO_LOOP        1
 #define MM_CLIP_OVERLAP        2
 #define MM_CLIP_NOT_SEPARATING 3
+#define MM_CLIP_KEPT_SIDE_DROPPED 4
 #define MM_CLIP_KIND_UNTOUCHED 0
 #define MM_CLIP_KIND_PIECE     1
 #define MM_CLIP_KIND_EXTENSION 2

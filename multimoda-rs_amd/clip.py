@@ -28,13 +28,14 @@ CLIP_REPORT_KEYS = ("n_cuts", "n_applied", "n_vertices", "n_faces", "n_new_verti
                     "n_closed_loops", "n_open_loops", "jump_rounds", "n_launches", "bytes_uploaded", "bytes_downloaded")
 KEEP = {"below": 0, "above": 1}
 SCOPE = {"loop": 0, "plane": 1}
-OK, NO_LOOP, OVERLAP, NOT_SEPARATING = 0, 1, 2, 3
-STATUS_NAMES = ("ok", "no_loop", "overlap", "not_separating")
+OK, NO_LOOP, OVERLAP, NOT_SEPARATING, KEPT_SIDE_DROPPED = 0, 1, 2, 3, 4
+STATUS_NAMES = ("ok", "no_loop", "overlap", "not_separating", "kept_side_dropped")
 UNTOUCHED, PIECE, EXTENSION, CAP = 0, 1, 2, 3
 
 
 class ClipError(RuntimeError):
-    """A cut that cannot be applied; ``statuses`` holds every cut's status (OK, NO_LOOP, OVERLAP, NOT_SEPARATING)."""
+    """A cut that cannot be applied; ``statuses`` holds every cut's status (OK, NO_LOOP, OVERLAP, NOT_SEPARATING,
+    KEPT_SIDE_DROPPED)."""
 
     def __init__(self, statuses):
         self.statuses = [int(s) for s in statuses]
@@ -47,8 +48,8 @@ class ClippedMesh:
     """``vertices`` / ``faces``: the result.  ``vertex_origin``: the input vertex, or -1 - k for a vertex made for cut k;
     ``face_origin``: the parent face, or -1 - k; ``face_kind``: 0 untouched, 1 piece of a cut face, 2 extension, 3 cap.
     ``rims[k]``: per closed loop of cut k the vertex indices of its outermost ring (the rim itself without an
-    extension), in loop order.  ``cut_status`` (0 OK, 1 NO_LOOP, 2 OVERLAP, 3 NOT_SEPARATING), ``cut_area``,
-    ``cut_length``, ``cut_centroid``: per cut, of its first closed loop (NaN without one); ``cut_points``, ``cut_loops``,
+    extension), in loop order.  ``cut_status`` (0 OK, 1 NO_LOOP, 2 OVERLAP, 3 NOT_SEPARATING, 4 KEPT_SIDE_DROPPED),
+    ``cut_area``, ``cut_length``, ``cut_centroid``: per cut, of its first closed loop (NaN without one); ``cut_points``, ``cut_loops``,
     ``cut_faces``: its loop points, closed loops and cut faces.  ``report``: CLIP_REPORT_KEYS and ``attempts``."""
     vertices: np.ndarray
     faces: np.ndarray
@@ -156,7 +157,7 @@ def clip_mesh(mesh, origins, normals, *, keep="below", scope="loop", cap=False, 
     outermost ring of every end.  A vertex exactly on a plane counts as above it; pieces without area that this leaves
     are kept and counted (``n_null_pieces``; ``repair_mesh`` removes them).  All cuts are applied or none: with
     ``strict`` a status other than OK (no loop around an origin, two cuts through one face, a loop that does not separate
-    the mesh) raises ``ClipError`` carrying the statuses, otherwise the input comes back unchanged with them.  Bad
+    the mesh, a cut whose kept side another cut throws away) raises ``ClipError`` carrying the statuses, otherwise the input comes back unchanged with them.  Bad
     arguments raise ``ValueError`` before the engine is touched; an empty mesh and zero cuts are valid; buffers that turn
     out too small are grown once."""
     args = _checked(mesh, origins, normals, keep, scope, cap, extension)

@@ -20,7 +20,8 @@
 using namespace mm;
 using clip::Record;
 
-static_assert(MM_CLIP_SCOPE_PLANE == kClipScopePlane && MM_CLIP_NOT_SEPARATING == kClipNotSeparating, "the kernels' constants");
+static_assert(MM_CLIP_SCOPE_PLANE == kClipScopePlane && MM_CLIP_NOT_SEPARATING == kClipNotSeparating &&
+              MM_CLIP_KEPT_SIDE_DROPPED == kClipKeptSideDropped, "the kernels' constants");
 static_assert(MM_CLIP_KIND_UNTOUCHED == kClipUntouched && MM_CLIP_KIND_PIECE == kClipPiece &&
               MM_CLIP_KIND_EXTENSION == kClipExtension && MM_CLIP_KIND_CAP == kClipCap, "the kernels' face kinds");
 static_assert(MM_CLIP_KEEP_BELOW == 0 && MM_CLIP_KEEP_ABOVE == 1, "keep is the side of rule 1 that stays");
@@ -380,6 +381,15 @@ int clip_on_host(const Args& a, Plan& pl, const Out& o, mm_clip_report& rep, con
         if (mark[(size_t)find((int32_t)i)]) dropped[(size_t)i] = 1;
         vidx[(size_t)i] = dropped[(size_t)i] ? -1 : (int32_t)kv++;
     }
+    // the orphan check: every status is OK here, so the marks are complete
+    bool orphaned = false;
+    for (const Record& r : pl.rec) {
+        const int64_t* t = a.f + 3 * (int64_t)r.face;
+        if (!clip::kept_side_dropped(r.flags, dropped[(size_t)t[0]] != 0, dropped[(size_t)t[1]] != 0, dropped[(size_t)t[2]] != 0)) continue;
+        pl.info[(size_t)(4 * r.cut)] = MM_CLIP_KEPT_SIDE_DROPPED;
+        orphaned = true;
+    }
+    if (orphaned) return write_identity(a, pl, o, rep, who);
     // two passes over the faces: the count, then the result
     report_plan(pl, a, rep);
     auto corner = [&](int64_t i) {
@@ -460,8 +470,9 @@ int clip_on_host(const Args& a, Plan& pl, const Out& o, mm_clip_report& rep, con
     return MM_OK;
 }
 
-// C2, C4 and C7 on the device: 5 + R launches (R = the jump rounds, the one that changes nothing included), and 11 more
-// where the cuts are applied (8 on a mesh without faces, whose face scan has no tile)
+// C2, C4 and C7 on the device: 5 + R launches (R = the jump rounds, the one that changes nothing included), 1 more (the
+// orphan check) where no cut is NOT_SEPARATING, and 11 more where the cuts are applied (8 on a mesh without faces, whose
+// face scan has no tile)
 int clip_on_device(Engine* e, const Args& a, Plan& pl, const Out& o, mm_clip_report& rep, const char* who)
 {
     const int64_t nv = a.nv, nf = a.nf, K = a.K, nr = (int64_t)pl.rec.size(), nn = pl.n_new();
@@ -533,6 +544,18 @@ int clip_on_device(Engine* e, const Args& a, Plan& pl, const Out& o, mm_clip_rep
         if (status[(size_t)k] != 0 && status[(size_t)k] != MM_CLIP_NOT_SEPARATING)
             return set_error(MM_ERR_HIP, std::string(who) + ": cut status out of range");
         if (status[(size_t)k]) { pl.info[(size_t)(4 * k)] = MM_CLIP_NOT_SEPARATING; applied = false; }
+    }
+    if (!applied) return write_identity(a, pl, o, rep, who);
+    // every status word is zero: the marks are complete, and the orphan check can leave nothing but its own value
+    MM_TRY_HIP(launch_clip_orphan(d_f, d_rec, nr, d_link, d_mark, d_vdrop, d_status, &launches, e->stream));
+    MM_TRY_HIP(hipMemcpyAsync(status.data(), d_status, (size_t)K * 4, hipMemcpyDeviceToHost, e->stream));
+    MM_TRY_HIP(hipStreamSynchronize(e->stream));
+    rep.bytes_downloaded += K * 4;
+    rep.n_launches = launches;
+    for (int64_t k = 0; k < K; ++k) {
+        if (status[(size_t)k] != 0 && status[(size_t)k] != MM_CLIP_KEPT_SIDE_DROPPED)
+            return set_error(MM_ERR_HIP, std::string(who) + ": cut status out of range");
+        if (status[(size_t)k]) { pl.info[(size_t)(4 * k)] = MM_CLIP_KEPT_SIDE_DROPPED; applied = false; }
     }
     if (!applied) return write_identity(a, pl, o, rep, who);
 

@@ -1,6 +1,6 @@
 // mm_clip_device.h -- the per-face step of "mesh clipping" (include/mm_ccta.h, rule C4) as C++ for host and device: the
 // rotation of a cut face to its apex, its three pieces, the shorter-diagonal rule of the quad, which pieces stay and
-// which are null.  Every operation is unfused f64 in the order written (the files that include it are built with
+// which are null, and C2's per-face orphan test.  Every operation is unfused f64 in the order written (the files that include it are built with
 // -ffp-contract=off), so the kernel (mm_clip_kernels.hip), the host hook (mm_clip.cpp), the stand-alone program
 // (tests/clip_device_host.cpp) and the checker (tests/mm_checkers/mesh_clip.py) produce the same bits.  Selects only, no
 // indexed arrays: on the device everything stays in registers.  Internal.
@@ -82,6 +82,16 @@ MM_CLIP_HD Pieces face_pieces(const Corner& c0, const Corner& c1, const Corner& 
     out.first = piece(m_ab, b, pick(through_c, c, m_ca));
     out.second = piece(pick(through_c, m_ab, b), c, m_ca);
     return out;
+}
+
+// C2's orphan check for one cut face: its kept-side old vertices (the apex where the apex is kept, otherwise b and c)
+// include a dropped one.  d0, d1, d2: whether the corners c0, c1, c2 of the face are dropped.
+MM_CLIP_HD bool kept_side_dropped(int32_t flags, bool d0, bool d1, bool d2)
+{
+    const int apex = flags & kApexMask;
+    const bool a = apex == 0 ? d0 : (apex == 1 ? d1 : d2);
+    const bool others = apex == 0 ? (d1 || d2) : (apex == 1 ? (d2 || d0) : (d0 || d1));
+    return (flags & kApexKept) ? a : others;
 }
 
 // C6: the kept side of a cut face runs x -> y along its rim edge: the apex piece runs m_ab -> m_ca, the quad's the other way

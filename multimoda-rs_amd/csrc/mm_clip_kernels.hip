@@ -12,6 +12,8 @@
 //                    its three vertices, a cut face the two that are not its apex.  launch_weld_jump flattens the links.
 //   k_clip_verdict   one lane per record of a LOOP cut, links flat: the roots of the apex and of its neighbour; equal ->
 //                    atomicOr of NOT_SEPARATING into the cut's status, else mark[drop-side root] = 1.
+//   k_clip_orphan    one lane per record, after a verdict that left every status zero (the marks are complete): a
+//                    kept-side vertex of the face is dropped (mark[root] | vdrop) -> atomicOr of KEPT_SIDE_DROPPED.
 //   k_clip_keep      vkeep = not (mark[root] or vdrop); launch_trim_scan numbers the kept vertices.
 //   k_clip_count     one lane per face: the pieces it leaves (0 to 3), the dropped and the untouched faces counted per
 //                    wave (wave_count); k_clip_tile_sum / k_clip_tile_scan / k_clip_offsets scan the counts (the
@@ -100,6 +102,19 @@ k_clip_verdict(const int32_t* __restrict__ face, const Record* __restrict__ rec,
         const unsigned int ra = link[a] >> 1, rb = link[b] >> 1;
         if (ra == rb) atomicOr(&status[q.cut], kClipNotSeparating);
         else mark[(q.flags & clip::kApexKept) ? rb : ra] = 1;
+    }
+}
+
+// links flat, marks complete: every status is zero when this runs, so the only value it leaves is kClipKeptSideDropped
+__global__ void __launch_bounds__(kMeshThreads)
+k_clip_orphan(const int32_t* __restrict__ face, const Record* __restrict__ rec, long long nr, const unsigned int* __restrict__ link,
+              const uint8_t* __restrict__ mark, const uint8_t* __restrict__ vdrop, int32_t* __restrict__ status)
+{
+    for (long long r = mesh_tid(); r < nr; r += mesh_stride()) {
+        const Record q = rec[r];
+        const int32_t c0 = face[3 * (long long)q.face], c1 = face[3 * (long long)q.face + 1], c2 = face[3 * (long long)q.face + 2];
+        auto dropped = [&](int32_t x) { return (mark[link[x] >> 1] | vdrop[x]) != 0; };
+        if (clip::kept_side_dropped(q.flags, dropped(c0), dropped(c1), dropped(c2))) atomicOr(&status[q.cut], kClipKeptSideDropped);
     }
 }
 
@@ -297,6 +312,14 @@ hipError_t launch_clip_verdict(const int32_t* face, const void* rec, long long n
                                int32_t* status, int* launches, hipStream_t s)
 {
     MESH_LAUNCH(k_clip_verdict, mesh_grid(nr), face, (const Record*)rec, nr, link, mark, status);
+    *launches += 1;
+    return hipSuccess;
+}
+
+hipError_t launch_clip_orphan(const int32_t* face, const void* rec, long long nr, const unsigned int* link, const uint8_t* mark,
+                              const uint8_t* vdrop, int32_t* status, int* launches, hipStream_t s)
+{
+    MESH_LAUNCH(k_clip_orphan, mesh_grid(nr), face, (const Record*)rec, nr, link, mark, vdrop, status);
     *launches += 1;
     return hipSuccess;
 }

@@ -109,19 +109,23 @@ int        section_launches();
 // bytes, one a cut face), newv (n_new new vertices, new_cut their cuts) and cuts stay resident.  clip_unions: link, the
 // marks, frec, counts[clip_num_counts] and status[n_cuts] initialised, the records scattered, the PLANE sides, the unions
 // (launch_weld_jump flattens link afterwards).  clip_verdict, links flat: status |= kClipNotSeparating, the drop marks.
+// clip_orphan, after a verdict that left every status zero: status |= kClipKeptSideDropped where a kept-side vertex of a
+// cut face is dropped.
 // clip_counts: vkeep and its scan (vidx, vtile: clip_scan_tiles(nv) + 1 entries, the last the kept vertices), the pieces
 // of every face and their scan (foff, ftile likewise, the last the kept faces and pieces).  clip_emit: the result; kv =
 // the kept vertices, first_ext / first_cap = where the extension and the cap faces start.  nv > 0 in all of them.
 struct ClipCut { double o[3], n[3]; int32_t keep, scope; int32_t pad[2]; };   // 64 bytes
 static_assert(sizeof(ClipCut) == 64, "a clip cut is 64 bytes");
 enum { clip_num_dropped_faces = 0, clip_num_untouched = 1, clip_num_null_pieces = 2, clip_num_counts = 8 };
-enum { kClipScopePlane = 1, kClipNotSeparating = 3 };
+enum { kClipScopePlane = 1, kClipNotSeparating = 3, kClipKeptSideDropped = 4 };
 enum { kClipUntouched = 0, kClipPiece = 1, kClipExtension = 2, kClipCap = 3 };
 hipError_t launch_clip_unions(const double* v, long long nv, const int32_t* face, long long nf, const void* rec, long long nr,
                               const ClipCut* cuts, int n_cuts, unsigned int* link, uint8_t* mark, uint8_t* vdrop, int32_t* frec,
                               unsigned long long* counts, int32_t* status, int* launches, hipStream_t s);
 hipError_t launch_clip_verdict(const int32_t* face, const void* rec, long long nr, const unsigned int* link, uint8_t* mark,
                                int32_t* status, int* launches, hipStream_t s);
+hipError_t launch_clip_orphan(const int32_t* face, const void* rec, long long nr, const unsigned int* link, const uint8_t* mark,
+                              const uint8_t* vdrop, int32_t* status, int* launches, hipStream_t s);
 size_t     clip_scan_tiles(long long n);
 hipError_t launch_clip_counts(const double* v, long long nv, const double* newv, const int32_t* face, long long nf, const int32_t* frec,
                               const void* rec, const unsigned int* link, const uint8_t* mark, const uint8_t* vdrop, uint8_t* vkeep,

@@ -1,7 +1,7 @@
 // csrc/mm_clip_device.h as plain host C++, a program of its own (tests/test_clip_kernel_resources.py builds it with g++,
 // plain and under the address and undefined-behaviour sanitizers, and runs it directly): rule C4 on fixed faces whose
 // arithmetic is exact -- the rotation to every apex, both diagonals and the tie, the kept pieces under every drop
-// pattern, null pieces where a loop point lies on a vertex.
+// pattern, null pieces where a loop point lies on a vertex; C2's orphan test at every apex, kept and not.
 #include <cstdio>
 
 #include "mm_clip_device.h"
@@ -72,6 +72,15 @@ int main()
         CHECK(same_point(mab.p, v1.p) && !same_point(mab.p, mca.p));
     }
     CHECK(rim_runs_ab_to_ca(kApexKept | 1) && !rim_runs_ab_to_ca(kLoopCut | kClosedRim | 2));
+    // the orphan test: apex kept -> the apex alone decides; apex dropped -> either of the other two
+    for (int apex = 0; apex < 3; ++apex)
+        for (int d = 0; d < 8; ++d) {
+            const bool d0 = d & 1, d1 = d & 2, d2 = d & 4;
+            const bool da = apex == 0 ? d0 : (apex == 1 ? d1 : d2);
+            const int others = (d0 + d1 + d2) - da;
+            CHECK(kept_side_dropped(apex | kApexKept | kLoopCut, d0, d1, d2) == da);
+            CHECK(kept_side_dropped(apex | kClosedRim, d0, d1, d2) == (others > 0));
+        }
     if (failures) return 1;
     std::printf("clip_device_host OK\n");
     return 0;

@@ -11,7 +11,7 @@ from . import mesh_sections as X
 
 BELOW, ABOVE = 0, 1                  # keep: the side of rule 1 that stays (h < 0: below)
 LOOP, PLANE = 0, 1
-OK, NO_LOOP, OVERLAP, NOT_SEPARATING = 0, 1, 2, 3
+OK, NO_LOOP, OVERLAP, NOT_SEPARATING, KEPT_SIDE_DROPPED = 0, 1, 2, 3, 4
 UNTOUCHED, PIECE, EXTENSION, CAP = 0, 1, 2, 3
 RECORD_BYTES, CUT_BYTES = 48, 64
 
@@ -121,6 +121,13 @@ def clip(v, f, origins, normals, keep, scope, cap=0, ext_length=0.0, ext_layers=
                     marked.add(_find(root, drop))
         for x in range(nv):
             dropped[x] = _find(root, x) in marked or any(scope[k] == PLANE and side_of[k][x] != keep[k] for k in range(K))
+        if all(s == OK for s in status):                   # the orphan check: the marks are complete
+            for face, k in owner.items():
+                a = apex_of[face]
+                t = f[face]
+                kept_side = [t[a]] if side_of[k][t[a]] == keep[k] else [t[(a + 1) % 3], t[(a + 2) % 3]]
+                if any(dropped[x] for x in kept_side):
+                    status[k] = KEPT_SIDE_DROPPED
         for k in range(K):
             info[k][0] = status[k]
 
@@ -248,13 +255,16 @@ def predict_report(nv, nf, n_cuts, want, jump_rounds):
     """The launches and the bytes of the clip's own device pass (the section pass before it reports its own) from the
     sizes, the checker's result ``want`` and the measured jump rounds R.  Nothing runs on the device without a cut,
     without a vertex or where C1 leaves a status other than OK.  Otherwise 5 + R launches (initialise, scatter, sides,
-    unions, R jumps, verdict) and, where the cuts are applied, 11 more (keep flags, 3 of their scan, piece counts, 3 of
+    unions, R jumps, verdict), 1 more (the orphan check, whose K status words are read a second time) where no cut is
+    NOT_SEPARATING and, where the cuts are applied, 11 more (keep flags, 3 of their scan, piece counts, 3 of
     their scan -- none on a mesh without faces --, vertices, faces, rim faces).  bytes_uploaded is restated where the
     cuts are applied (the new vertices of a call that is NOT_SEPARATING are not part of its result)."""
     status = want["cut_status"][:, 0].tolist()
     if n_cuts == 0 or nv == 0 or NO_LOOP in status or OVERLAP in status:
         return {"n_launches": 0, "bytes_uploaded": 0, "bytes_downloaded": 0, "jump_rounds": 0}
-    out = {"n_launches": 5 + jump_rounds, "bytes_downloaded": 4 * jump_rounds + 4 * n_cuts, "jump_rounds": jump_rounds}
+    checked = NOT_SEPARATING not in status
+    out = {"n_launches": 5 + jump_rounds + checked, "bytes_downloaded": 4 * jump_rounds + 4 * n_cuts * (1 + checked),
+           "jump_rounds": jump_rounds}
     if want["applied"]:
         c = want["counts"]
         out["n_launches"] += 11 if nf > 0 else 8

@@ -32,9 +32,10 @@ def test_public_names_and_abi():
     assert [n for n, _t in mm._native.MMClipReport._fields_] == list(mm.clip.CLIP_REPORT_KEYS)
     assert mm.clip.CLIP_REPORT_KEYS[:len(Y.COUNT_KEYS)] == Y.COUNT_KEYS
     for name, value in (("KEEP_BELOW", Y.BELOW), ("KEEP_ABOVE", Y.ABOVE), ("SCOPE_LOOP", Y.LOOP), ("SCOPE_PLANE", Y.PLANE),
-                        ("OK", Y.OK), ("NO_LOOP", Y.NO_LOOP), ("OVERLAP", Y.OVERLAP), ("NOT_SEPARATING", Y.NOT_SEPARATING),
+                        ("OK", Y.OK), ("NO_LOOP", Y.NO_LOOP), ("OVERLAP", Y.OVERLAP), ("NOT_SEPARATING", Y.NOT_SEPARATING), ("KEPT_SIDE_DROPPED", Y.KEPT_SIDE_DROPPED),
                         ("KIND_UNTOUCHED", Y.UNTOUCHED), ("KIND_PIECE", Y.PIECE), ("KIND_EXTENSION", Y.EXTENSION), ("KIND_CAP", Y.CAP)):
         assert any(line.split() == ["#define", "MM_CLIP_" + name, str(value)] for line in header.splitlines()), name
+    assert mm.clip.KEPT_SIDE_DROPPED == Y.KEPT_SIDE_DROPPED == 4 and mm.clip.STATUS_NAMES[4] == "kept_side_dropped"
     assert (mm.clip.KEEP, mm.clip.SCOPE) == ({"below": Y.BELOW, "above": Y.ABOVE}, {"loop": Y.LOOP, "plane": Y.PLANE})
     assert "mesh clipping" in header and "connectivity" in mm.clip_mesh.__doc__
 

@@ -13,7 +13,7 @@ import pytest
 from test_morph_kernel_resources import FUSED, HIPCC, ROOT, _body, _compile, _flags
 
 CSRC = os.path.join(ROOT, "multimoda-rs_amd", "csrc")
-KERNELS = ("k_clip_init", "k_clip_scatter", "k_clip_sides", "k_clip_union", "k_clip_verdict", "k_clip_keep", "k_clip_count",
+KERNELS = ("k_clip_init", "k_clip_scatter", "k_clip_sides", "k_clip_union", "k_clip_verdict", "k_clip_orphan", "k_clip_keep", "k_clip_count",
            "k_clip_tile_sum", "k_clip_tile_scan", "k_clip_offsets", "k_clip_vertices", "k_clip_emit", "k_clip_rim")
 
 

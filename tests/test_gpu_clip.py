@@ -142,7 +142,7 @@ def test_empty_inputs_and_open_vessel_ends(engine):
     with pytest.raises(mm.ClipError):
         mm.clip_mesh(empty, [[0, 0, 0.0]], [[0, 0, 1.0]], engine=engine)
     cloud = mm.clip_mesh((v, np.zeros((0, 3), dtype=np.int64)), [[0.5, 0, 0]], [[1.0, 0, 0]], scope="plane", engine=engine)
-    assert cloud.vertex_origin.tolist() == [0, 1, 2, 3] and cloud.report["n_launches"] == 5 + cloud.report["jump_rounds"] + 8
+    assert cloud.vertex_origin.tolist() == [0, 1, 2, 3] and cloud.report["n_launches"] == 5 + cloud.report["jump_rounds"] + 1 + 8
     from test_section_host import tube
     tv, tf = tube(12, 41, 1.0, 0.25, jitter=0.01, seed=12)
     xs = np.arange(0.0, 10.01, 0.4) + 0.013
