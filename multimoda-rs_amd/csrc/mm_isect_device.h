@@ -20,7 +20,7 @@ struct P2 { double u, v; };
 constexpr double kEps = 1.1102230246251565e-16;
 constexpr double kO3dBound = (7.0 + 56.0 * kEps) * kEps;
 constexpr double kO2dBound = (3.0 + 16.0 * kEps) * kEps;
-constexpr double kTiny = 1.1832913578315177e-271;   // 2^-900
+constexpr double kTiny = 0x1p-900;                   // 2^-900, as a power of two and not in decimal digits
 constexpr double kHuge = 1.7976931348623157e308;     // DBL_MAX: `perm <= kHuge` is false for +inf and NaN
 
 MM_HD inline double absd(double x) { return __builtin_fabs(x); }
