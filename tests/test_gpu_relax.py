@@ -3,7 +3,11 @@ vertices and ref_face bit for bit, the integer fields of the report equal, the d
 bytes as predicted -- over the small solids, tubes one past a workgroup and one past a query block, references of one
 chunk and one past it, 0 / 1 / 3 iterations and three factors; a reference that is not the mesh; masks, bands and
 borders; messy face lists on both sides; the guard's two cases; the pruning on the long tube; the errors; random small
-meshes; and the line label -> remove -> stitch(fill_holes=True, refine=True, relax=True, smooth=True)."""
+meshes; and the line label -> remove -> stitch(fill_holes=True, refine=True, relax=True, smooth=True).
+
+The worst cases -- ties across chunks, query blocks flung across the reference, large offsets and scales, degenerate,
+thin and NaN seeds, the exact grid -- are in tests/test_gpu_relax_attack.py, with an exact oracle (tests/relax_exact.py)
+asked about the device's own output."""
 import ctypes as C
 import os
 
