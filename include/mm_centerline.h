@@ -184,8 +184,11 @@ int     mm_align_combined(mm_engine* e, const mm_clpoint* cl, int64_t ncl, mm_cl
  * weights along the path, rounded after every addition, from the seed on; +inf where no path arrives.  That is what
  * Dijkstra's algorithm returns, and it is the one fixpoint of d[v] = min(d[v], fl(d[u] + w)) below the start, in any
  * order, because the rounded addition of a non-negative weight is monotone: the result has one bit pattern whatever the
- * schedule.  pred[v] = the smallest neighbour u with fl(dist[u] + w(u, v)) == dist[v], -1 at seeds and where dist is
- * +inf (edges of weight zero can make two vertices each other's predecessor).  n_edges counts the edges kept,
+ * schedule.  A finite weight is the square root of a finite double and so below 2^512: fewer than 2^31 of them cannot sum
+ * to +inf, and every vertex joined to a seed by kept edges is reached.  A mesh whose squared differences all underflow has
+ * every weight +0.0, and every vertex reached lies at +0.0.  pred[v] = the smallest neighbour u with fl(dist[u] + w(u, v))
+ * == dist[v], -1 at seeds and where dist is +inf (edges of weight zero can make two vertices each other's predecessor).
+ * n_edges counts the edges kept,
  * n_reached the vertices with a finite distance (seeds included), max_dist the largest finite distance, max_edge the
  * longest finite weight.  rounds, n_batches and n_launches describe the schedule and are no function of the input
  * alone: a round relaxes every flagged block of 256 consecutive vertices to its local fixpoint, and the host reads the
