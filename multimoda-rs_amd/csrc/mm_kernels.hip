@@ -1056,9 +1056,15 @@ typedef float f16x16 __attribute__((ext_vector_type(16)));
 static constexpr int MXC_ROW_TILES_MAX = kMxCullRowTilesMax;
 static constexpr int MXC_SETBIT_MIN_NCT = kMxCullSetbitMinNct;   // from here on the culled screen loops over the set mask bits
 
-static __device__ __forceinline__ int min3i(int a, int b, int c) { return min(a, min(b, c)); }
+// One v_min3_i32, written as the binary tree the instruction selector tiles into one: it forms min3 from the root down and
+// takes a minimum's FIRST operand into it before the second.  min(a, min(b, c)) under a root min(acc, .) loses its inner
+// minimum to the root's min3 and leaves min(b, c) as a v_min_i32 of its own: mxc_fold was 7 v_min3_i32 + 2 v_min_i32 that
+// way, nine instructions where eight do.  With the inner minimum in front, every min3i below is one instruction whether it
+// is met from above or from below.  (Integer minimum is associative and commutative: the bits are the same either way.)
+static __device__ __forceinline__ int min3i(int a, int b, int c) { return min(min(a, b), c); }
 
-// fold the 16 values of one lane's share of a tile into acc (8 three-operand minima, five of them independent)
+// fold the 16 values of one lane's share of a tile into acc: 8 three-operand minima as written and as compiled
+// (tools/count_cull_isa.py: 16 valu per computed tile), five of them independent, no inline assembly near an MFMA's result
 static __device__ __forceinline__ int mxc_fold(int acc, const f16x16& d)
 {
     const int a0 = min3i(__float_as_int(d[0]), __float_as_int(d[1]), __float_as_int(d[2]));
@@ -1127,17 +1133,22 @@ static __device__ __forceinline__ void mxc_tile(const h8v& af, int lo, int hi, i
 }
 
 // one tile of two candidates X and Y that share the A fragment: four MFMAs in flight before the first minimum; per candidate
-// the operands and the folds of mxc_tile
-static __device__ __forceinline__ void mxc_tile2(const h8v& af, int loX, int hiX, int& cX, int& rminX, int loY, int hiY, int& cY,
-                                                 int& rminY)
+// the operands and the folds of mxc_tile.  `rest` fetches what X's products do not need -- Y's fragment dwords and both
+// running column minima -- and runs behind X's two MFMAs: in the set-bit loop these are four indexed reads in ONE region
+// (with X's two dwords in front of the MFMAs: two regions a tile step, where the scheduler left to itself made three), and
+// they cover wait states of the first product instead of standing in front of it.
+template <class Rest>
+static __device__ __forceinline__ void mxc_tile2(const h8v& af, int loX, int hiX, int& cX, int& rminX, int& cY, int& rminY, Rest&& rest)
 {
     const f16x16 z = {};
     const h8v bX = __builtin_bit_cast(h8v, mxc_i4{loX, hiX, loX, hiX});
-    const h8v bY = __builtin_bit_cast(h8v, mxc_i4{loY, hiY, loY, hiY});
     // X's products, then Y's issued one by one behind X's folds, each into the registers the fold before it has read: two
     // products in flight at any time and 32 accumulators, as in mxc_tile, and the matrix pipe never waits for the minima
     const f16x16 dX = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bX, z, 0, 0, 0);
     const f16x16 eX = __builtin_amdgcn_mfma_f32_32x32x16_f16(bX, af, z, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    h8v bY;
+    rest(bY, cX, cY);
     __builtin_amdgcn_sched_barrier(0);
     cX = mxc_fold(cX, dX);
     __builtin_amdgcn_sched_barrier(0);
@@ -1198,17 +1209,31 @@ static __device__ __forceinline__ void mxc_tiles2(unsigned mask, const h8v& af, 
         MXC_MARK("tloop2:ptiles");
         const int t = __builtin_ctz(mask);
         mask &= mask - 1;
-        const int loX = bloX.v[t], hiX = bhiX.v[t], loY = bloY.v[t], hiY = bhiY.v[t];
-        int cX = cmX.v[t], cY = cmY.v[t];
-        MXC_MARK_V("tile2:ptiles", cX);
-        mxc_tile2(af, loX, hiX, cX, rminX, loY, hiY, cY, rminY);
+        const int loX = bloX.v[t], hiX = bhiX.v[t];
+        int cX, cY;
+        MXC_MARK("tile2:ptiles");
+        mxc_tile2(af, loX, hiX, cX, rminX, cY, rminY, [&](h8v& bY, int& x, int& y) {
+            const int loY = bloY.v[t], hiY = bhiY.v[t];
+            x = cmX.v[t]; y = cmY.v[t];
+            __builtin_amdgcn_sched_barrier(0);                             // (the four indexed reads stay one region)
+            bY = __builtin_bit_cast(h8v, mxc_i4{loY, hiY, loY, hiY});
+            __asm__("" : "+v"(bY));                                        // (and Y's fragment is whole before the folds start)
+        });
         MXC_MARK_V("tloop2:ptiles", cY);
         cmX.v[t] = cX;
         cmY.v[t] = cY;
     }
     if (tail) {
         MXC_MARK("tile2t:ptails");
-        mxc_tile2(af, bloX.last, bhiX.last, cmX.last, rminX, bloY.last, bhiY.last, cmY.last, rminY);
+        // (the last tile's fragments stay the two dwords they are outside this body: widened once per candidate, they would
+        // hold eight registers through every section for one tile in seventeen)
+        int loX = bloX.last, hiX = bhiX.last;
+        __asm__ volatile("" : "+v"(loX), "+v"(hiX));
+        mxc_tile2(af, loX, hiX, cmX.last, rminX, cmY.last, rminY, [&](h8v& bY, int&, int&) {
+            int loY = bloY.last, hiY = bhiY.last;
+            __asm__ volatile("" : "+v"(loY), "+v"(hiY));
+            bY = __builtin_bit_cast(h8v, mxc_i4{loY, hiY, loY, hiY});
+        });
     }
     MXC_MARK_V("p1p_row:prows", rminY);
 }
@@ -1493,7 +1518,7 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         int rmin = 0x7f800000;
                         mxc_tiles<NCT, FOL ? 3 : 1>(mask, af, blo, bhi, cm, rmin);
                         rmin = mxc_meet(rmin);
-                        if (lane < 32) s_rs[I * 32 + lane] = rmin;
+                        s_rs[I * 32 + l32] = rmin;                            // (lanes l and l + 32: one value to one address)
                         const bool above = rmin > __builtin_amdgcn_readlane(grp_tr, I);
                         if constexpr (FOL) {
                             fmax = max(fmax, above && upper ? 0 : rmin);
@@ -1528,17 +1553,20 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                 // without the floor a follower leaves iff every minimum is settled (no bit in lt), with it iff no minimum
                 // that is not settled lies above L, that is iff F <= L: exactly when it has no live row or column, which is
                 // when its phase-2 masks are all empty under the floor's rule (the header).  Its value is F either way.
-                auto fol_leaves = [&](int fm, unsigned long long lt, int lo, int ai, int& L) -> bool {
+                // (F, Lw: the wave-uniform maxima of the met and of the settled minima; late: a minimum is not settled)
+                auto fol_verdict = [&](int F, int Lw, bool late, int ai, int& L) -> bool {
                     done += grp_p1;
                     ++n_foll;
-                    const int F = wave_max_i32_dpp(fm);
-                    L = floor_on ? wave_max_i32_dpp(lo) : (int)0x80000000;
-                    const bool leaves = floor_on ? F <= L : lt == 0;
+                    L = floor_on ? Lw : (int)0x80000000;
+                    const bool leaves = floor_on ? F <= L : !late;
                     if (leaves) {
                         ++n_early;
                         if (lane == 0) out_sq[out_off + ai] = __int_as_float(F) * inv_s2;
                     }
                     return leaves;
+                };
+                auto fol_leaves = [&](int fm, unsigned long long lt, int lo, int ai, int& L) -> bool {
+                    return fol_verdict(wave_max_i32_dpp(fm), floor_on ? wave_max_i32_dpp(lo) : 0, lt != 0, ai, L);
                 };
                 // What runs the general path below: bit 0 this candidate (X of a pair), bit 1 a pair's Y, on its own registers and
                 // its own row store, after X.
@@ -1556,8 +1584,14 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                     MXC_MARK("p1_init2:pair");
 #pragma unroll
                     for (int t = 0; t < NCT; ++t) cmY.set(t, 0x7f800000);
-                    int fmaxY = 0;
-                    unsigned long long lateY = 0;
+                    // One swap meets both candidates' row minima: the lower lanes then hold X's 32 met minima and the upper
+                    // lanes Y's (mxc_meet leaves each candidate's in both halves, and only one half of them is ever used).  So
+                    // one store writes both row stores, one compare takes both against Tr_I, and the maxima on the way are
+                    // one register pair for both: fall the largest met row minimum, fset the largest settled one, X's in
+                    // the lower lanes and Y's in the upper.  The same values as the unpaired loop's enter each maximum.
+                    int fall = 0, fset = 0;
+                    unsigned long long lateXY = 0;                            // (bits 0 .. 31 X's rows above Tr_I, bits 32 .. 63 Y's)
+                    int* const rsxy = upper ? s_ry : s_rs;
                     for (int I = 0; I < nrt; ++I) {
                         MXC_MARK("p1p_row:prows");
                         const unsigned mask = __builtin_amdgcn_readlane(p1m, I);
@@ -1565,21 +1599,44 @@ k_screen_mx_cull(const PairDesc* __restrict__ pairs, const WorkItem* __restrict_
                         const h8v an = s_a[(I + 1 < nrt ? I + 1 : I) * 64 + lane];
                         int rminX = 0x7f800000, rminY = 0x7f800000;
                         mxc_tiles2<NCT>(mask, af, blo, bhi, cm, rminX, bloY, bhiY, cmY, rminY);
-                        rminX = mxc_meet(rminX);
-                        rminY = mxc_meet(rminY);
-                        if (lane < 32) { s_rs[I * 32 + lane] = rminX; s_ry[I * 32 + lane] = rminY; }
-                        const bool aboveX = rminX > tr, aboveY = rminY > tr;
-                        late |= __builtin_amdgcn_ballot_w64(aboveX);
-                        lateY |= __builtin_amdgcn_ballot_w64(aboveY);
-                        fmax = max(fmax, aboveX && upper ? 0 : rminX);
-                        fmaxY = max(fmaxY, aboveY && upper ? 0 : rminY);
+                        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)rminX, (unsigned)rminY, false, false);
+                        const int rm = min((int)r[0], (int)r[1]);
+                        rsxy[I * 32 + l32] = rm;
+                        const bool above = rm > tr;
+                        lateXY |= __builtin_amdgcn_ballot_w64(above);
+                        fall = max(fall, rm);
+                        fset = max(fset, above ? 0 : rm);
                         af = an;
                     }
                     MXC_MARK("fol_check2:pair");
-                    int flo = upper ? fmax : 0, floY = upper ? fmaxY : 0;
-                    fol_check(cm, fmax, late, flo);
-                    fol_check(cmY, fmaxY, lateY, floY);
-                    const bool goX = fol_leaves(fmax, late, flo, a, LX), goY = fol_leaves(fmaxY, lateY, floY, aY, LY);
+                    // The group test of both, the columns as the rows: X's and Y's minima of column tile t meet in one swap,
+                    // X's 32 into the lower lanes and Y's into the upper, and both stand against the same Tc_t, a scalar -- no
+                    // choice between two thresholds per lane, as fol_check makes for the two column tiles of ONE candidate.
+                    // Per candidate the same minima meet the same thresholds as there; a maximum does not depend on its order.
+                    __builtin_amdgcn_sched_barrier(0);                        // (the section's instructions stay behind its mark)
+#pragma unroll
+                    for (int t = 0; t < NCT; ++t) {
+                        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)cm.get(t), (unsigned)cmY.get(t), false, false);
+                        const int v = min((int)r[0], (int)r[1]);
+                        const bool above = v > __builtin_amdgcn_readlane(grp_tc, t);
+                        lateXY |= __builtin_amdgcn_ballot_w64(above);
+                        fall = max(fall, v);
+                        fset = max(fset, above ? 0 : v);
+                        // (a few tiles at a time: left to itself the scheduler keeps all 17 compare masks and thresholds in
+                        // scalar registers at once, more than there are)
+                        if (t % 4 == 3) __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // X's maxima are over the lower lanes and Y's over the upper: one pass over the rows of 16 lanes for both
+                    auto halves = [&](int v, int& x, int& y) {
+                        v = dpp_max_i32<0xB1>(v); v = dpp_max_i32<0x4E>(v); v = dpp_max_i32<0x141>(v); v = dpp_max_i32<0x140>(v);
+                        x = max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16));
+                        y = max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48));
+                    };
+                    int FX, FY, SX = 0, SY = 0;
+                    halves(fall, FX, FY);
+                    if (floor_on) halves(fset, SX, SY);
+                    const bool goX = fol_verdict(FX, SX, (unsigned)lateXY != 0, a, LX);
+                    const bool goY = fol_verdict(FY, SY, (lateXY >> 32) != 0, aY, LY);
                     stay = (goX ? 0u : 1u) | (goY ? 0u : 2u);
                     MXC_MARK("end:0");
                 } else {

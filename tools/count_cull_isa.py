@@ -171,6 +171,7 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True
     out.write("  %-10s %-8s %6s %6s %6s %6s %6s %6s %7s %9s\n" % ("section", "trips", "mfma", "valu", "salu", "lds", "vmem",
                                                                   "other", "static", "executed"))
     tot_tile = tot_rest = tot_pro = 0.0
+    by_class = {c: 0.0 for c in CLASSES}                                 # executed per candidate, the candidate loop's sections
     for name, s in secs.items():
         static = sum(s[c] for c in CLASSES)
         if s["trips"] not in trips:
@@ -182,6 +183,9 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True
             tot_tile += ex
         else:
             tot_rest += ex
+        if s["trips"] not in ("item", "run"):
+            for c in CLASSES:
+                by_class[c] += s[c] * trips[s["trips"]]
         out.write(("  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.1f\n" if s["trips"] in ("item", "run") else
                    "  %-10s %-8s %6d %6d %6d %6d %6d %6d %7d %9.0f\n") % (name, s["trips"], s["mfma"], s["valu"], s["salu"], s["lds"],
                                                                        s["vmem"], s["other"], static, ex))
@@ -189,6 +193,7 @@ def report(nct, body, inf, nrt, tiles, rows2, out, group=1, early=0.0, pair=True
         out.write("  a computed tile's body: %.1f instructions\n" % (sum(secs["tile"][c] for c in CLASSES) / copies))
     if "tile2" in secs:
         out.write("  a paired tile's body (two candidates): %.1f instructions; pairs per group %d\n" % (sum(secs["tile2"][c] for c in CLASSES), npair))
+    out.write("  executed per candidate by class: " + ", ".join("%s %.0f" % (c, by_class[c]) for c in CLASSES if by_class[c]) + "\n")
     out.write("  executed per candidate: tiles %.0f, everything else %.0f" % (tot_tile, tot_rest))
     out.write("; the prologue %.1f (static, its loops counted once)\n\n" % tot_pro if tot_pro else "\n\n")
     return tot_tile, tot_rest
